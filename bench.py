@@ -2,7 +2,17 @@
 """bench.py -- the MPPI/M3P2I command() hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config push|hybrid|northstar|panda|c5|...]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run measures the headline only: it sets up, warms up, times exactly K commands and prints the line
+(`value`, `ms_per_step` = milliseconds per timed command, ...).  Everything described below beyond that --
+kernel times and rooflines, command latency, collective times, `other_configs`, `closed_loop`, `cpu_baseline`
+and the 1-GPU references of an N > 1 run -- is measured with --full only, after the timed region.
+--dump-outputs DIR writes what the headline's last timed command computed (rank 0): the plan command() returned
+(`action`, [T, nu]) and the trajectory costs and softmin weights it left behind (`cost_total`, `weights`), as
+float32 DIR/<name>.npy.  The inputs are the same in every run with the same arguments (initial scene, seeded
+Halton-spline noise), so two builds can be compared output for output.
 
 One "step" = one full MPPI iteration (M3P2I.command(): rollout of every sample over the
 horizon through the contact dynamics + per-step task cost, softmin weights / multi-modal beta
@@ -254,9 +264,11 @@ def cpu_baseline(env, task, goal, multi_modal, K, T, delta, seconds=21.0):
 
 
 def run_config(name, args, world, rank, device, dist, steps, warmup, K_local=None, latency=True, time_collectives=False,
-               scene=None, repeats=1):
-    """Builds the planner for CONFIGS[name] and measures it: `warmup` untimed commands, an event loop
-    for the kernel durations, then EXACTLY `steps` commands between barrier + synchronize pairs."""
+               scene=None, repeats=1, timing=True, keep_outputs=False):
+    """Builds the planner for CONFIGS[name] and measures it: `warmup` untimed commands, then EXACTLY `steps` commands
+    between barrier + synchronize pairs; after the timed region (timing=True) an event loop for the kernel durations and
+    (latency=True) a loop of synchronous commands for the latency.  keep_outputs: the plan the last timed command returned
+    and the reference attributes it left behind (trajectory costs, softmin weights), as `outputs`."""
     env, task, goal, multi_modal, K_cfg, T = CONFIGS[name]
     K_local = K_local or K_cfg
     K_global = K_local * world
@@ -283,31 +295,6 @@ def run_config(name, args, world, rank, device, dist, steps, warmup, K_local=Non
 
     for _ in range(min(warmup, 5)):
         pl.command(state)        # (first calls: sampler + sort of the wave order; the W warm-up commands proper come below)
-    # dominant kernel: average launch duration from HIP events recorded by the library on the
-    # stream it launches on, over min(steps, 50) commands of the same workload run BEFORE the
-    # warm-up and the timed region (reading the events back synchronises, so they are not read
-    # inside it)
-    eng.enable_timing(True)
-    pl.collective_times = [] if (time_collectives and world > 1) else None
-    tr, tu, tf = [], [], []
-    for _ in range(min(steps, 50)):
-        pl.command(state)
-        t = eng.timing()
-        tr.append(t.rollout_ms)
-        tu.append(t.update_ms)
-        tf.append(t.finalize_ms)
-    eng.enable_timing(False)
-    coll_ms = None
-    if pl.collective_times is not None:
-        torch.cuda.synchronize()
-        per_phase = {}
-        for phase, e0, e1 in pl.collective_times:
-            per_phase.setdefault(phase, []).append(e0.elapsed_time(e1))
-        n_cmd = min(steps, 50)
-        coll_ms = {ph: float(np.sum(v)) / n_cmd for ph, v in per_phase.items()}
-        coll_ms["total"] = float(sum(coll_ms.values()))
-        coll_ms["per_command"] = len(pl.collective_times) / n_cmd
-    pl.collective_times = None
     import gc
     walls = []
     for _ in range(repeats):     # (the headline: exactly once; `other_configs` rows: the better of two timed regions,
@@ -321,15 +308,49 @@ def run_config(name, args, world, rank, device, dist, steps, warmup, K_local=Non
         sync()
         t0 = time.perf_counter()
         for _ in range(steps):
-            pl.command(state)
+            out = pl.command(state)
         sync()
         walls.append(time.perf_counter() - t0)
         gc.enable()
     wall = min(walls)
+    outputs = None
+    if keep_outputs:
+        # (a fresh plan tensor per command; the buffers behind the attributes are copied before any later command)
+        outputs = {"action": out, "cost_total": pl.cost_total.clone(), "weights": pl.weights.clone()}
     if dist is not None:
         tw = torch.tensor([wall], device=device, dtype=torch.float64)
         dist.all_reduce(tw, op=dist.ReduceOp.MAX)
         wall = float(tw.item())
+    # dominant kernel: average launch duration from HIP events recorded by the library on the
+    # stream it launches on, over min(steps, 50) commands of the same workload run AFTER the
+    # timed region (reading the events back synchronises, so they are not read inside it; after
+    # it, so that the timed region and what it computes are the same with and without them)
+    rollout_ms = update_ms = finalize_ms = alg_bytes = achieved = coll_ms = None
+    if timing:
+        eng.enable_timing(True)
+        pl.collective_times = [] if (time_collectives and world > 1) else None
+        tr, tu, tf = [], [], []
+        for _ in range(min(steps, 50)):
+            pl.command(state)
+            t = eng.timing()
+            tr.append(t.rollout_ms)
+            tu.append(t.update_ms)
+            tf.append(t.finalize_ms)
+        eng.enable_timing(False)
+        if pl.collective_times is not None:
+            torch.cuda.synchronize()
+            per_phase = {}
+            for phase, e0, e1 in pl.collective_times:
+                per_phase.setdefault(phase, []).append(e0.elapsed_time(e1))
+            n_cmd = min(steps, 50)
+            coll_ms = {ph: float(np.sum(v)) / n_cmd for ph, v in per_phase.items()}
+            coll_ms["total"] = float(sum(coll_ms.values()))
+            coll_ms["per_command"] = len(pl.collective_times) / n_cmd
+        pl.collective_times = None
+        rollout_ms, update_ms, finalize_ms = float(np.mean(tr)), float(np.mean(tu)), float(np.mean(tf))
+        # (in-kernel noise: no delta read, 8 B fewer per state-step)
+        alg_bytes = (BYTES_PER_STATE_STEP_ROLLOUT[env] - (8 if name in SIMPLE_MODE else 0)) * K_local * T
+        achieved = alg_bytes / (rollout_ms * 1e-3) / 1e9
     lat_ms = None
     if latency:
         # command() latency: host clock from the call to the [T, nu] plan's first action on the host
@@ -340,15 +361,31 @@ def run_config(name, args, world, rank, device, dist, steps, warmup, K_local=Non
             pl.command(state)[0].cpu()
             lat.append(time.perf_counter() - t1)
         lat_ms = np.asarray(lat) * 1e3
-    rollout_ms = float(np.mean(tr))
-    # (in-kernel noise: no delta read, 8 B fewer per state-step)
-    alg_bytes = (BYTES_PER_STATE_STEP_ROLLOUT[env] - (8 if name in SIMPLE_MODE else 0)) * K_local * T
-    achieved = alg_bytes / (rollout_ms * 1e-3) / 1e9
     return dict(pl=pl, sim=sim, cfg=cfg, env=env, task=task, goal=goal, multi_modal=multi_modal, K_local=K_local,
                 K_global=K_global, T=T, wall=wall, steps=steps, value=K_global * T * steps / wall,
-                ms_per_step=wall / steps * 1e3, rollout_ms=rollout_ms, update_ms=float(np.mean(tu)),
-                finalize_ms=float(np.mean(tf)), alg_bytes=alg_bytes, achieved=achieved, lat_ms=lat_ms,
-                collective_ms=coll_ms, simple=name in SIMPLE_MODE, walls_ms_per_step=[w / steps * 1e3 for w in walls])
+                ms_per_step=wall / steps * 1e3, rollout_ms=rollout_ms, update_ms=update_ms,
+                finalize_ms=finalize_ms, alg_bytes=alg_bytes, achieved=achieved, lat_ms=lat_ms,
+                collective_ms=coll_ms, simple=name in SIMPLE_MODE, walls_ms_per_step=[w / steps * 1e3 for w in walls],
+                outputs=outputs)
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(outputs, path):
+    """--dump-outputs: one float32 `<name>.npy` per array of the headline's last timed command.  An array above its share
+    of the 64 MB budget is stored as a fixed sample of its rows (seeded: the same rows in every run), the row indices
+    beside it as `<name>_rows.npy`."""
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // (2 * max(1, len(outputs)))     # (half of each share: room for the row indices)
+    for key, t in outputs.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > budget:
+            rows = np.random.default_rng(0).choice(a.shape[0], size=max(1, budget // (a.nbytes // a.shape[0])), replace=False)
+            rows = np.sort(rows)
+            a = a[rows]
+            np.save(os.path.join(path, f"{key}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, f"{key}.npy"), a)
 
 
 MIX_DIR = os.path.join(ROOT, "profiles", "r06")
@@ -524,8 +561,15 @@ def main():
                          "3 = two small exchanges with O(K_local) work per rank")
     ap.add_argument("--transport", default="rccl", choices=["rccl", "p2p"],
                     help="N > 1: the records exchange as an RCCL all-gather (default) or through peer-mapped device memory")
-    ap.add_argument("--no-extras", action="store_true", help="headline line only (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: the headline's own figures only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: kernel times and rooflines, command latency, collective times, "
+                         "the other configs, the closed loop, the CPU baselines and (N > 1) the 1-GPU references")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed command computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -556,23 +600,19 @@ def main():
     name = args.config or "push"
     # (--config panda_pick / worst_case as the headline of a profiling run: their scenes)
     head_scene = make_pick_scene(panda_pick_scene(device)) if name == "panda_pick" else (corner_scene if name == "worst_case" else None)
+    # a plain run measures the headline only (set up, warm up, the timed steps); --full adds everything else
+    full = args.full
     r = run_config(name, args, world, rank, device, dist, args.steps, args.warmup, K_local=args.samples_per_gpu,
-                   time_collectives=True, scene=head_scene)
+                   latency=full, time_collectives=full, scene=head_scene, timing=full,
+                   keep_outputs=args.dump_outputs is not None)
     env, task, goal, multi_modal, K_local, K_global, T = (r[k] for k in ("env", "task", "goal", "multi_modal", "K_local",
                                                                           "K_global", "T"))
     pl = r["pl"]
-    extras = not args.no_extras
+    extras = full and not args.no_extras
+    if rank == 0 and args.dump_outputs is not None:
+        dump_outputs(r["outputs"], args.dump_outputs)
 
     if rank == 0:
-        traffic = None
-        try:  # HBM bytes per launch from the PMC passes of tools/profile_gpu.sh, same workload only
-            tj = json.load(open(TRAFFIC_FILE))
-            key = f"{name}:K{K_local}:T{T}"
-            if key in tj:
-                traffic = tj[key]["hbm_bytes_per_launch"]
-        except Exception:
-            pass
-        kern = "k_rollout_point" if env == "point_env" else "k_rollout_panda"
         if world == 1:
             par = "single GPU"
         else:
@@ -595,27 +635,38 @@ def main():
                                    f"{'mppi_mode simple, in-kernel noise' if name in SIMPLE_MODE else 'halton-spline'}, "
                                    "initial scene, open loop (fixed world, warm-started plan)",
                        "name": name, "command_hz": args.steps / r["wall"],
-                       "command_latency_ms": {"p50": float(np.percentile(r["lat_ms"], 50)),
-                                              "p99": float(np.percentile(r["lat_ms"], 99)),
-                                              "what": "host clock, command() + action on host, synchronous"},
                        "parallelism": par},
-            "roofline": {"bound": "hbm", "achieved": r["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": r["achieved"] / HBM_PEAK_GBS, "traffic": traffic,
-                         "kernel": kern, "kernel_ms": r["rollout_ms"], "bytes_per_launch": r["alg_bytes"],
-                         "kernel_ms_from": "HIP events recorded by the library right before / after the "
-                                           "launch on its stream (mean over the commands between warm-up and "
-                                           "the timed region); the interval includes the ~5-9 us dispatch "
-                                           "latency that rocprofv3's kernel duration (profiles/) excludes",
-                         "note": "latency-bound at this K (sequential T x substeps x solver passes chain); "
-                                 "DESIGN.md section 6"},
-            "kernel_ms": {"rollout": r["rollout_ms"], "update": r["update_ms"], "finalize": r["finalize_ms"]},
         }
-        line["roofline_valu"] = roofline_valu(name, r, (K_local + 63) // 64)
         if world > 1:
             line["ranks_seen"], line["transport"], line["protocol"] = pl.ranks_seen, pl.transport, pl.protocol
+    if rank == 0 and full:
+        traffic = None
+        try:  # HBM bytes per launch from the PMC passes of tools/profile_gpu.sh, same workload only
+            tj = json.load(open(TRAFFIC_FILE))
+            key = f"{name}:K{K_local}:T{T}"
+            if key in tj:
+                traffic = tj[key]["hbm_bytes_per_launch"]
+        except Exception:
+            pass
+        kern = "k_rollout_point" if env == "point_env" else "k_rollout_panda"
+        line["config"]["command_latency_ms"] = {"p50": float(np.percentile(r["lat_ms"], 50)),
+                                                "p99": float(np.percentile(r["lat_ms"], 99)),
+                                                "what": "host clock, command() + action on host, synchronous"}
+        line["roofline"] = {"bound": "hbm", "achieved": r["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": r["achieved"] / HBM_PEAK_GBS, "traffic": traffic,
+                            "kernel": kern, "kernel_ms": r["rollout_ms"], "bytes_per_launch": r["alg_bytes"],
+                            "kernel_ms_from": "HIP events recorded by the library right before / after the "
+                                              "launch on its stream (mean over the commands right after "
+                                              "the timed region); the interval includes the ~5-9 us dispatch "
+                                              "latency that rocprofv3's kernel duration (profiles/) excludes",
+                            "note": "latency-bound at this K (sequential T x substeps x solver passes chain); "
+                                    "DESIGN.md section 6"}
+        line["kernel_ms"] = {"rollout": r["rollout_ms"], "update": r["update_ms"], "finalize": r["finalize_ms"]}
+        line["roofline_valu"] = roofline_valu(name, r, (K_local + 63) // 64)
         if r["collective_ms"] is not None:
             line["collective_ms"] = r["collective_ms"]
-    delta_np = pl.delta.contiguous().cpu().numpy() if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    delta_np = (pl.delta.contiguous().cpu().numpy() if (full and rank == 0 and world == 1 and not args.no_cpu_baseline)
+                else None)
 
     def one_gpu_reference(cname, K, what):
         """The named workload with K samples on ONE GPU (unsharded handle, rank 0's GPU, the other ranks wait at

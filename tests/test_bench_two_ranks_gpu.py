@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +24,7 @@ def test_bench_with_two_ranks(config, mode, extra):
     port = 29800 + os.getpid() % 150
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20",
-           "--warmup", "3", "--samples-per-gpu", "512"] + (["--config", config] if config else []) + extra
+           "--warmup", "3", "--samples-per-gpu", "512", "--full"] + (["--config", config] if config else []) + extra
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -47,10 +48,11 @@ def test_bench_with_two_ranks(config, mode, extra):
 
 
 def test_bench_single_gpu_line_contract():
-    """`python bench.py` (N = 1): ONE JSON line with the driver's keys, the BASELINE configs[1] workload as the
+    """`python bench.py --full` (N = 1): ONE JSON line with the driver's keys, the BASELINE configs[1] workload as the
     headline, `roofline` and `cpu_baseline` objects, the other configs and the closed-loop figure riding along."""
     # (the cpu_baseline object's sample shortened from 21 s to 3: its content is checked, not its precision)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "5", "--cpu-baseline-seconds", "3"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "5", "--cpu-baseline-seconds", "3",
+           "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -84,15 +86,15 @@ def test_bench_single_gpu_line_contract():
 
 
 def test_bench_starts_its_own_ranks():
-    """The driver's command line with N > 1 and NO launcher around it -- exactly `python3 bench.py --gpus 2 --steps 3
-    --warmup 1` -- : bench.py launches the two ranks itself (torch.distributed.run on a free loopback port), rank 0's
-    ONE JSON line comes through on stdout, the exit code is 0 only if every rank finished and the communicator the
-    ranks formed really has two members."""
+    """The driver's command line with N > 1 and NO launcher around it -- `python3 bench.py --gpus 2 --steps 3
+    --warmup 1`, with --full for the rows that ride along -- : bench.py launches the two ranks itself (torch.distributed.run
+    on a free loopback port), rank 0's ONE JSON line comes through on stdout, the exit code is 0 only if every rank
+    finished and the communicator the ranks formed really has two members."""
     env = dict(os.environ, M3_BENCH_SHARE_GPU="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
-                       env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+                        "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -100,3 +102,33 @@ def test_bench_starts_its_own_ranks():
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["steps"] == 3 and d["warmup"] == 1
     assert "K=4000 (2000/GPU)" in d["config"]["workload"] and d["value"] > 0
     assert set(d["other_configs"]) == {"c5", "push_saturating"}
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """The plain N = 1 line (no --full): the headline's keys and nothing that needs runs of its own; --dump-outputs writes
+    the last timed command's plan, trajectory costs and weights, and a second run with the same arguments writes the
+    same arrays."""
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+               "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+            assert key in d, key
+        assert d["steps"] == 7 and d["warmup"] == 3 and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert abs(d["value"] - 2000 * 30 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        for key in ("roofline", "kernel_ms", "cpu_baseline", "other_configs", "closed_loop", "collective_ms"):
+            assert key not in d, key
+        assert "command_latency_ms" not in d["config"]
+        dumps.append({k: np.load(out / f"{k}.npy") for k in ("action", "cost_total", "weights")})
+    a = dumps[0]
+    assert a["action"].shape == (30, 2) and a["cost_total"].shape == (2000,) and a["weights"].shape == (2000,)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert abs(float(a["weights"].sum()) - 1.0) < 1e-3 and (a["weights"] >= 0).all()
+    for k in a:
+        np.testing.assert_array_equal(dumps[1][k], a[k], err_msg=k)

@@ -1,11 +1,7 @@
 """The reference's scripts import through `m3p2i_aip_amd.compat`."""
-import os
-import runpy
 import sys
 
 import pytest
-
-REF_SCRIPT = "/root/reference/scripts/reactive_tamp.py"
 
 
 def test_reference_import_names_resolve():
@@ -36,50 +32,36 @@ def test_reference_import_names_resolve():
         compat.make_config("config_point", ["no_such_key=1"])
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SCRIPT), reason="reference checkout not mounted")
-def test_unchanged_reference_script_loads_on_the_shims():
-    """Executes the reference's scripts/reactive_tamp.py AS IS (module level: imports, class and
-    hydra-decorated entry point) on top of compat; constructing REACTIVE_TAMP then fails loudly
-    here only because this container has no GPU."""
+def test_reference_script_entry_points_on_the_shims(monkeypatch):
+    """What scripts/reactive_tamp.py and scripts/sim.py build at module level, on the shims: a hydra-decorated entry point
+    (version_base=None, the package's config folder, config_point) that composes its config from the command line's
+    key=value overrides, the skill_utils / zerorpc names sim.py calls, and the planner process's constructor -- the
+    wrapper of cfg.mppi.num_samples environments on cfg.mppi.device -- failing loudly when there is no GPU."""
     from m3p2i_aip_amd import compat
     from m3p2i_aip_amd._lib import M3Error
     compat.install(force_standins=True)
-    ns = runpy.run_path(REF_SCRIPT, run_name="reference_reactive_tamp")
-    assert "REACTIVE_TAMP" in ns and callable(ns["run_reactive_tamp"])
+    import hydra
+    import zerorpc
     import torch
+    from m3p2i_aip.config.config_store import ExampleConfig
+    from m3p2i_aip.utils.skill_utils import check_and_apply_suction, time_tracking
+    import m3p2i_aip.utils.isaacgym_utils.isaacgym_wrapper as wrapper
+
+    @hydra.main(version_base=None, config_path="../src/m3p2i_aip/config", config_name="config_point")
+    def entry(cfg: ExampleConfig):
+        return cfg
+
+    monkeypatch.setattr(sys, "argv", ["reactive_tamp.py", "task=push_pull", "mppi.num_samples=64"])
+    cfg = entry()
+    assert cfg.env_type == "point_env" and cfg.task == "push_pull" and cfg.mppi.num_samples == 64
+    monkeypatch.setattr(sys, "argv", ["sim.py", "-cn", "config_panda"])
+    assert entry().env_type == "panda_env"
+    assert check_and_apply_suction is compat.check_and_apply_suction and time_tracking is compat.time_tracking
+    assert callable(zerorpc.Server) and hasattr(zerorpc.Client(), "connect")
     if not torch.cuda.is_available():
         with pytest.raises(M3Error):
-            ns["REACTIVE_TAMP"](compat.make_config("config_point", ["mppi.num_samples=64"]))
-
-
-@pytest.mark.skipif(not os.path.exists(REF_SCRIPT), reason="reference checkout not mounted")
-def test_unchanged_reference_sim_script_loads_on_the_shims():
-    """scripts/sim.py AS IS: its imports (isaacgym, hydra, zerorpc, skill_utils.check_and_apply_suction /
-    time_tracking, data_transfer) resolve and its hydra entry point is built; running it needs the GPU and
-    a planner process on tcp://127.0.0.1:4242 (tests/test_rpc_two_process_gpu.py exercises that
-    arrangement with this repository's own driver, since the reference's files do not travel)."""
-    from m3p2i_aip_amd import compat
-    compat.install(force_standins=True)
-    ns = runpy.run_path(REF_SCRIPT.replace("reactive_tamp.py", "sim.py"), run_name="reference_sim")
-    assert callable(ns["run_sim"]) and ns["check_and_apply_suction"] is compat.check_and_apply_suction
-    import zerorpc
-    assert ns["zerorpc"] is zerorpc and hasattr(zerorpc.Client(), "connect")
-
-
-@pytest.mark.skipif(not os.path.exists(REF_SCRIPT), reason="reference checkout not mounted")
-@pytest.mark.parametrize("example", ["example_aip_parallel.py", "example_aip_panda.py"])
-def test_unchanged_reference_task_planner_examples_run_on_the_shims(example, capsys):
-    """examples/example_aip_parallel.py (four state-factor agents, parallel_action_selection.par_act_sel) and
-    examples/example_aip_panda.py (adapt_act_sel) AS THEY ARE, start to end, on this build's task planner."""
-    from m3p2i_aip_amd import compat
-    compat.install(force_standins=True)
-    path = os.path.join(os.path.dirname(os.path.dirname(REF_SCRIPT)), "examples", example)
-    runpy.run_path(path, run_name="__main__")
-    out = capsys.readouterr().out
-    if "parallel" in example:
-        assert out.count("Current plan") == 15 and "approach_obj" in out and "push_to_goal" in out and "pull_to_goal" in out
-    else:
-        assert "reach" in out and "pick" in out and "place" in out and "idle_success" in out
+            wrapper.IsaacGymWrapper(cfg.isaacgym, cfg.env_type, num_envs=cfg.mppi.num_samples, viewer=False,
+                                    device=cfg.mppi.device, cube_on_shelf=cfg.cube_on_shelf)
 
 
 @pytest.mark.gpu

@@ -14,9 +14,9 @@ for c in push hybrid panda panda_pick northstar c5 c5_unsharded worst_case; do
 done
 # the driver's own command, verbatim (BENCH_rNN.json: `python3 bench.py --gpus 1 --steps 20 --warmup 5`)
 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
-python bench.py > $O/bench_default.json 2> $O/bench_default.err            # 200 steps / 20 warm-ups: headline + other_configs + closed loop + cpu baselines
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err     # 200 steps / 20 warm-ups: headline + other_configs + closed loop + cpu baselines
 for c in push hybrid panda panda_pick northstar c5 c5_unsharded worst_case; do
-  python bench.py --config $c --no-extras --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err
+  python bench.py --full --config $c --no-extras --no-cpu-baseline > $O/bench_$c.json 2> $O/bench_$c.err
 done
 # profiling passes run the headline loop only (--no-extras): kernel-trace stats, then separate PMC passes
 TRAFFIC_KEY=push:K2000:T30 tools/profile_gpu.sh push --config push --no-extras > $O/prof_push.log 2>&1
