@@ -128,6 +128,11 @@ SYMBOLS = [
     ("m3_p2p_clear_error", C.c_int, [_H]),
     ("m3_p2p_detach", C.c_int, [_H]),
     ("m3_p2p_set_memory_kind", C.c_int, [_H, C.c_int]),
+    ("m3_batch_create", C.c_int, [C.c_int, C.c_int, C.POINTER(_H)]),
+    ("m3_batch_destroy", None, [_H]),
+    ("m3_batch_last_error", C.c_char_p, [_H]),
+    ("m3_batch_command", C.c_int, [_H, C.POINTER(_H), C.c_int, _FP]),
+    ("m3_batch_launches", C.c_int, [_H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("m3_get_buffer", C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]),
     ("m3_reduce_len", C.c_int, [_H]),
     ("m3_record_len", C.c_int, [_H]),

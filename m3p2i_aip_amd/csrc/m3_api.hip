@@ -871,16 +871,21 @@ extern "C" int m3_bind_sim_panda(m3_handle* h, const float* dof, const float* ro
 // 842: 0.784 / 0.450, 60 ticks 993: 1.530 / 0.831 -- the forms cross near 240; the eight-lane form's own count runs ~10 % higher,
 // its shadow slots included)
 
-extern "C" int m3_rollout(m3_handle* h) {
-    if (!h) return M3_ERR_BAD_ARG;
+// the conditions under which m3_rollout refuses (M3_ERR_STATE; nullptr: none) -- m3_batch_command checks them too
+static const char* rollout_refusal(const m3_handle* h) {
     const m3_config& c = h->cfg;
-    if (c.sim_only) return fail(h, M3_ERR_STATE, "m3_rollout: handle was created sim_only");
+    if (c.sim_only) return "m3_rollout: handle was created sim_only";
     if (!c.sampling_random && !c.mode_simple && !h->have_noise)
-        return fail(h, M3_ERR_STATE, "m3_rollout: no noise set (m3_set_noise) and sampling_random == 0");
+        return "m3_rollout: no noise set (m3_set_noise) and sampling_random == 0";
     if (c.mode_simple && !c.sampling_random && !h->have_noise)
-        return fail(h, M3_ERR_STATE, "m3_rollout: simple mode needs m3_set_noise or sampling_random");
-    if (h->task == M3_TASK_PUSH_PULL && !c.multi_modal) return fail(h, M3_ERR_STATE, "m3_rollout: push_pull needs multi_modal");
-    RolloutArgs a;
+        return "m3_rollout: simple mode needs m3_set_noise or sampling_random";
+    if (h->task == M3_TASK_PUSH_PULL && !c.multi_modal) return "m3_rollout: push_pull needs multi_modal";
+    return nullptr;
+}
+
+// the rollout's arguments; refreshes the wavefront order when it is due (a stream-ordered launch)
+static int prepare_rollout(m3_handle* h, RolloutArgs& a) {
+    const m3_config& c = h->cfg;
     std::memset(&a, 0, sizeof(a));
     a.Kg = c.K_global; a.Kl = c.K_local; a.k0 = c.k_offset; a.T = c.T; a.nu = c.nu;
     a.multi_modal = c.multi_modal; a.mode_simple = c.mode_simple;
@@ -925,6 +930,16 @@ extern "C" int m3_rollout(m3_handle* h) {
     a.J = (float*)h->buf[M3_BUF_TRAJ_COST];
     a.wave_min = h->wave_min;   // (null unless the handle's update is the three-launch one)
     h->wave_min_rows = 0;
+    return M3_OK;
+}
+
+extern "C" int m3_rollout(m3_handle* h) {
+    if (!h) return M3_ERR_BAD_ARG;
+    const m3_config& c = h->cfg;
+    if (const char* why = rollout_refusal(h)) return fail(h, M3_ERR_STATE, why);
+    RolloutArgs a;
+    const int rc = prepare_rollout(h, a);
+    if (rc != M3_OK) return rc;
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     if (c.env_type == M3_ENV_POINT) {
         if (launch_rollout_point(a, h->scene, h->stream)) h->wave_min_rows = (a.Kl + a.lanes - 1) / a.lanes;
@@ -1500,6 +1515,280 @@ extern "C" int m3_command(m3_handle* h, float* action_host) {
         const int rows = c.mode_simple ? c.u_per_command : c.T;
         HIPCHK(h, hipMemcpyAsync(action_host, h->action_out ? h->action_out : (float*)h->buf[M3_BUF_ACTION_OUT], (size_t)rows * c.nu * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return M3_OK;
+}
+
+// ---------------------------------- batched command ------------------------------------
+// One command() of each of n unsharded point_env handles: per group of handles that run the same kernel instance, ONE
+// rollout launch and ONE update launch (a multi-modal group: as many as its residency chunks), the handles' arguments
+// read from a device table indexed by blockIdx.y (DESIGN.md "Batched command").  The handles keep all of their state;
+// the batch owns only the table: BATCH_SLOTS pinned host slots, each with a device slot and an event recorded after the
+// call's last launch (so it guards the host slot's copy AND the device slot's readers, whichever stream they ran on).
+static thread_local std::string g_batch_err;
+constexpr int BATCH_SLOTS = 4;
+
+namespace {
+struct BatchKey {
+    int instance, ref, K, T, lanes;   // rollout: rollout_point_instance, reference scene compiled in, sizes
+    SmallUpdateInstance upd;          // update: k_update_small's template arguments, width, top-k workgroups
+};
+bool same_rollout(const BatchKey& x, const BatchKey& y) {
+    return x.instance == y.instance && x.ref == y.ref && x.K == y.K && x.T == y.T && x.lanes == y.lanes;
+}
+bool less_rollout(const BatchKey& x, const BatchKey& y) {
+    if (x.instance != y.instance) return x.instance < y.instance;
+    if (x.ref != y.ref) return x.ref < y.ref;
+    if (x.K != y.K) return x.K < y.K;
+    if (x.T != y.T) return x.T < y.T;
+    return x.lanes < y.lanes;
+}
+bool same_update(const BatchKey& x, const BatchKey& y) {
+    return x.upd.multi == y.upd.multi && x.upd.jr == y.upd.jr && x.upd.wt == y.upd.wt && x.upd.n_cand == y.upd.n_cand &&
+           x.T == y.T;
+}
+bool less_update(const BatchKey& x, const BatchKey& y) {
+    if (x.upd.multi != y.upd.multi) return x.upd.multi < y.upd.multi;
+    if (x.upd.jr != y.upd.jr) return x.upd.jr < y.upd.jr;
+    if (x.upd.wt != y.upd.wt) return x.upd.wt < y.upd.wt;
+    if (x.upd.n_cand != y.upd.n_cand) return x.upd.n_cand < y.upd.n_cand;
+    return x.T < y.T;
+}
+size_t align16(size_t n) { return (n + 15) / 16 * 16; }
+}  // namespace
+
+struct m3_batch {
+    int device = 0, max_handles = 0;
+    std::string err;
+    size_t upd_off = 0, slot_bytes = 0;   // a slot: [max_handles] BatchRolloutEntry (from 0) | [max_handles] UpdateArgs
+    char* host[BATCH_SLOTS] = {};
+    char* dev[BATCH_SLOTS] = {};
+    hipEvent_t done[BATCH_SLOTS] = {};
+    bool in_flight[BATCH_SLOTS] = {};
+    int next = 0;
+    int rollout_launches = 0, update_launches = 0;   // of the last successful m3_batch_command
+    // host scratch, sized by m3_batch_create
+    std::vector<m3_handle*> seen;
+    std::vector<BatchKey> key;
+    std::vector<int> by_roll, by_upd;
+};
+
+#define BATCHK(b, expr)                                                                  \
+    do {                                                                                 \
+        hipError_t e_ = (expr);                                                          \
+        if (e_ != hipSuccess) {                                                          \
+            (b)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                \
+            return M3_ERR_HIP;                                                           \
+        }                                                                                \
+    } while (0)
+
+extern "C" const char* m3_batch_last_error(const m3_batch* b) { return b ? b->err.c_str() : g_batch_err.c_str(); }
+
+extern "C" void m3_batch_destroy(m3_batch* b) {
+    if (!b) return;
+    for (int q = 0; q < BATCH_SLOTS; ++q) {
+        if (b->in_flight[q]) (void)hipEventSynchronize(b->done[q]);   // (kernels may still read the device slot)
+        if (b->done[q]) (void)hipEventDestroy(b->done[q]);
+        if (b->dev[q]) (void)hipFree(b->dev[q]);
+        if (b->host[q]) (void)hipHostFree(b->host[q]);
+    }
+    delete b;
+}
+
+extern "C" int m3_batch_create(int device, int max_handles, m3_batch** out) {
+    if (!out) { g_batch_err = "m3_batch_create: null argument"; return M3_ERR_BAD_ARG; }
+    *out = nullptr;
+    if (max_handles < 1 || max_handles > 65535) {   // (blockIdx.y picks the handle)
+        g_batch_err = "m3_batch_create: max_handles must be in 1 .. 65535";
+        return M3_ERR_BAD_ARG;
+    }
+    int count = 0;
+    const hipError_t ce = hipGetDeviceCount(&count);
+    if (ce != hipSuccess) {
+        g_batch_err = std::string("m3_batch_create: hipGetDeviceCount: ") + hipGetErrorString(ce);
+        return M3_ERR_HIP;
+    }
+    if (device < 0 || device >= count) { g_batch_err = "m3_batch_create: no such HIP device"; return M3_ERR_BAD_ARG; }
+    m3_batch* b = new (std::nothrow) m3_batch();
+    if (!b) { g_batch_err = "m3_batch_create: out of host memory"; return M3_ERR_HIP; }
+    b->device = device;
+    b->max_handles = max_handles;
+    b->upd_off = align16((size_t)max_handles * sizeof(BatchRolloutEntry));
+    b->slot_bytes = b->upd_off + (size_t)max_handles * sizeof(UpdateArgs);
+    try {
+        b->seen.resize(max_handles);
+        b->key.resize(max_handles);
+        b->by_roll.resize(max_handles);
+        b->by_upd.resize(max_handles);
+    } catch (...) {
+        delete b;
+        g_batch_err = "m3_batch_create: out of host memory";
+        return M3_ERR_HIP;
+    }
+    int prev = -1;
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    hipError_t e = hipSetDevice(device);
+    for (int q = 0; q < BATCH_SLOTS && e == hipSuccess; ++q) {
+        e = hipHostMalloc((void**)&b->host[q], b->slot_bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc((void**)&b->dev[q], b->slot_bytes);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&b->done[q], hipEventDisableTiming);
+    }
+    if (prev >= 0) (void)hipSetDevice(prev);
+    if (e != hipSuccess) {
+        g_batch_err = std::string("m3_batch_create: ") + hipGetErrorString(e);
+        m3_batch_destroy(b);
+        return M3_ERR_HIP;
+    }
+    *out = b;
+    return M3_OK;
+}
+
+extern "C" int m3_batch_launches(const m3_batch* b, int* rollout_launches, int* update_launches) {
+    if (!b) return M3_ERR_BAD_ARG;
+    if (rollout_launches) *rollout_launches = b->rollout_launches;
+    if (update_launches) *update_launches = b->update_launches;
+    return M3_OK;
+}
+
+static int batch_refuse(m3_batch* b, int code, int i, const char* msg) {
+    char head[64];
+    if (i >= 0) std::snprintf(head, sizeof(head), "m3_batch_command: handle %d: ", i);
+    else std::snprintf(head, sizeof(head), "m3_batch_command: ");
+    b->err = std::string(head) + msg;
+    return code;
+}
+
+extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float* actions_host) {
+    if (!b) { g_batch_err = "m3_batch_command: null batch"; return M3_ERR_BAD_ARG; }
+    // ---- every check before any launch: a refused call leaves every handle as it was ----
+    if (!hs) return batch_refuse(b, M3_ERR_BAD_ARG, -1, "null handle list");
+    if (n <= 0 || n > b->max_handles) return batch_refuse(b, M3_ERR_BAD_ARG, -1, "n must be in 1 .. max_handles");
+    for (int i = 0; i < n; ++i) {
+        if (!hs[i]) return batch_refuse(b, M3_ERR_BAD_ARG, i, "null handle");
+        if (hs[i]->cfg.device != b->device) return batch_refuse(b, M3_ERR_BAD_ARG, i, "handle on another device than the batch");
+        b->seen[i] = hs[i];
+    }
+    std::sort(b->seen.begin(), b->seen.begin() + n);
+    if (std::adjacent_find(b->seen.begin(), b->seen.begin() + n) != b->seen.begin() + n) {
+        for (int i = 1; i < n; ++i)
+            for (int j = 0; j < i; ++j)
+                if (hs[j] == hs[i]) return batch_refuse(b, M3_ERR_BAD_ARG, i, "handle listed twice");
+    }
+    const hipStream_t s = hs[0]->stream;
+    for (int i = 0; i < n; ++i) {
+        m3_handle* h = hs[i];
+        const m3_config& c = h->cfg;
+        if (c.env_type != M3_ENV_POINT) return batch_refuse(b, M3_ERR_UNSUPPORTED, i, "panda_env handle (point_env only)");
+        if (c.K_local != c.K_global) return batch_refuse(b, M3_ERR_STATE, i, "sharded handle (K_local != K_global)");
+        if (c.sim_only) return batch_refuse(b, M3_ERR_STATE, i, "handle was created sim_only");
+        if (h->stream != s) return batch_refuse(b, M3_ERR_STATE, i, "its stream differs from handle 0's");
+        if (const char* why = rollout_refusal(h)) return batch_refuse(b, M3_ERR_STATE, i, why);
+        UpdateArgs ua;   // (what m3_command's update would be handed: update_impl with the finalize fused in)
+        fill_update_args(h, ua);
+        ua.fuse_finalize = 1;
+        ua.Jall = (const float*)h->buf[M3_BUF_TRAJ_COST];
+        if (!can_fuse_finalize(h) || !update_small_applies(ua))
+            return batch_refuse(b, M3_ERR_UNSUPPORTED, i, "its command does not take the one-launch update (nu = 2: K <= 16384; "
+                                                          "multi-modal K <= 8192)");
+        RolloutArgs ka;   // (the fields the rollout's instance depends on, as prepare_rollout sets them)
+        std::memset(&ka, 0, sizeof(ka));
+        ka.multi_modal = c.multi_modal; ka.mode_simple = c.mode_simple; ka.sampling_random = c.sampling_random;
+        ka.scale_dev = h->cov_active ? (const float*)h->buf[M3_BUF_COV] + c.nu : nullptr;
+        fill_cost_params(h, ka.cp);
+        BatchKey& k = b->key[i];
+        k.instance = rollout_point_instance(ka);
+        k.ref = point_scene_is_reference(h->scene) ? 1 : 0;
+        k.K = c.K_local; k.T = c.T;
+        k.lanes = h->lanes_override > 0 ? h->lanes_override : rollout_lanes_for(c.K_local);
+        k.upd = update_small_instance(ua);
+        b->by_roll[i] = b->by_upd[i] = i;
+    }
+    // ---- groups: handles in key order (ties in call order) ----
+    const BatchKey* key = b->key.data();
+    std::sort(b->by_roll.begin(), b->by_roll.begin() + n, [key](int x, int y) {
+        return less_rollout(key[x], key[y]) || (!less_rollout(key[y], key[x]) && x < y);
+    });
+    std::sort(b->by_upd.begin(), b->by_upd.begin() + n, [key](int x, int y) {
+        return less_update(key[x], key[y]) || (!less_update(key[y], key[x]) && x < y);
+    });
+    // ---- the argument table: a free ring slot, filled on the host, ONE copy ----
+    const int slot = b->next;
+    if (b->in_flight[slot]) {
+        BATCHK(b, hipEventSynchronize(b->done[slot]));
+        b->in_flight[slot] = false;
+    }
+    BatchRolloutEntry* hr = reinterpret_cast<BatchRolloutEntry*>(b->host[slot]);
+    const size_t upd_off = align16((size_t)n * sizeof(BatchRolloutEntry));
+    UpdateArgs* hu = reinterpret_cast<UpdateArgs*>(b->host[slot] + upd_off);
+    for (int p = 0; p < n; ++p) {
+        m3_handle* h = hs[b->by_roll[p]];
+        const int rc = prepare_rollout(h, hr[p].a);   // (+ the handle's wave-order refresh when it is due: its own launch)
+        if (rc != M3_OK) { b->err = "m3_batch_command: " + h->err; return rc; }
+        hr[p].sc = h->scene;
+    }
+    for (int p = 0; p < n; ++p) {
+        const int i = b->by_upd[p];
+        m3_handle* h = hs[i];
+        fill_update_args(h, hu[p]);
+        hu[p].fuse_finalize = 1;
+        hu[p].Jall = (const float*)h->buf[M3_BUF_TRAJ_COST];
+        hu[p].n_cand = key[i].upd.n_cand;   // (what launch_update_small hands its instance)
+    }
+    char* dslot = b->dev[slot];
+    BATCHK(b, hipMemcpyAsync(dslot, b->host[slot], upd_off + (size_t)n * sizeof(UpdateArgs), hipMemcpyHostToDevice, s));
+    const BatchRolloutEntry* dr = reinterpret_cast<const BatchRolloutEntry*>(dslot);
+    const UpdateArgs* du = reinterpret_cast<const UpdateArgs*>(dslot + upd_off);
+    // ---- one rollout launch per group ----
+    int n_roll = 0, n_upd = 0;
+    for (int p = 0; p < n;) {
+        const BatchKey& k = key[b->by_roll[p]];
+        int q = p + 1;
+        while (q < n && same_rollout(key[b->by_roll[q]], k)) ++q;
+        const int blocks = (k.K + k.lanes - 1) / k.lanes;
+        launch_rollout_point_batch(dr + p, q - p, k.instance, blocks, k.ref != 0, s);
+        ++n_roll;
+        for (int r = p; r < q; ++r)   // (as m3_rollout: the instances that can leave the workgroups' minima)
+            hs[b->by_roll[r]]->wave_min_rows = (hr[r].a.wave_min && (k.instance == -1 || k.instance == 3)) ? blocks : 0;
+        p = q;
+    }
+    BATCHK(b, hipGetLastError());
+    // ---- one update launch per group; multi-modal groups in chunks whose whole grid is resident ----
+    for (int p = 0; p < n;) {
+        const BatchKey& k = key[b->by_upd[p]];
+        int q = p + 1;
+        while (q < n && same_update(key[b->by_upd[q]], k)) ++q;
+        int chunk = q - p;
+        if (k.upd.multi) chunk = std::max(1, M3_CUS * update_small_batch_blocks_per_cu(k.upd) / (k.T + k.upd.n_cand));
+        for (int r = p; r < q; r += chunk) {
+            launch_update_small_batch(du + r, std::min(chunk, q - r), k.upd, k.T, s);
+            ++n_upd;
+        }
+        p = q;
+    }
+    BATCHK(b, hipGetLastError());
+    // ---- per handle, as m3_update_finalize: the covariance step, the call count ----
+    for (int i = 0; i < n; ++i) {
+        m3_handle* h = hs[i];
+        const int rc = after_finalize(h);
+        if (rc != M3_OK) { b->err = "m3_batch_command: " + h->err; return rc; }
+        h->calls += 1;
+    }
+    BATCHK(b, hipEventRecord(b->done[slot], s));
+    b->in_flight[slot] = true;
+    b->next = (slot + 1) % BATCH_SLOTS;
+    b->rollout_launches = n_roll;
+    b->update_launches = n_upd;
+    if (actions_host) {   // the plans one after the other: [rows_i][nu] each (rows = u_per_command in simple mode, else T)
+        size_t off = 0;
+        for (int i = 0; i < n; ++i) {
+            const m3_handle* h = hs[i];
+            const m3_config& c = h->cfg;
+            const size_t len = (size_t)(c.mode_simple ? c.u_per_command : c.T) * c.nu;
+            BATCHK(b, hipMemcpyAsync(actions_host + off, h->action_out ? h->action_out : (float*)h->buf[M3_BUF_ACTION_OUT],
+                                     len * sizeof(float), hipMemcpyDeviceToHost, s));
+            off += len;
+        }
+        BATCHK(b, hipStreamSynchronize(s));
     }
     return M3_OK;
 }

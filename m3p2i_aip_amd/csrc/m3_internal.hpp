@@ -157,6 +157,29 @@ __host__ __device__ inline int regen_off_mins(int Kls, int T) { return Kls + 2 *
 __host__ __device__ inline int regen_off_table(int Kls, int T) { return regen_off_mins(Kls, T) + 4; }
 __host__ __device__ inline int regen_record_length(int Kls, int T) { return (regen_off_table(Kls, T) + LAD_N * 3 + 3) / 4 * 4; }
 
+// ---- batched command (m3_batch_command): the per-handle entries of the device argument table ----------------------
+struct BatchRolloutEntry {   // one point_env handle's rollout (the scene is not read by the _ref build)
+    RolloutArgs a;
+    PointScene sc;
+};
+// the k_update_small instance (template arguments, workgroup width, top-k workgroups) an unsharded command takes
+struct SmallUpdateInstance {
+    int nu, multi, jr, wt, n_cand;
+};
+SmallUpdateInstance update_small_instance(const UpdateArgs& a);
+// blocks of the batched multi-modal update that are resident per CU (update_small.hip; DESIGN.md "Batched command")
+int update_small_batch_blocks_per_cu(const SmallUpdateInstance& in);
+// one launch of k_update_small's body for n handles whose entries (tab[0 .. n-1], device) share `in` and T
+void launch_update_small_batch(const UpdateArgs* tab, int n, const SmallUpdateInstance& in, int T, hipStream_t s);
+// -1: the general instance of the point_env rollout; 0..3: the per-task instance of that task (launch_rollout_point)
+int rollout_point_instance(const RolloutArgs& a);
+// one launch of the instance for n handles of K_local = a.Kl and the same lanes (tab: device, n entries)
+void launch_rollout_point_batch(const BatchRolloutEntry* tab, int n, int instance, int blocks, bool ref, hipStream_t s);
+void launch_rollout_point_nav_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
+void launch_rollout_point_push_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
+void launch_rollout_point_pull_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
+void launch_rollout_point_pushpull_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
+
 // ---- launchers (defined in the .hip files) ---------------------------------------------
 bool launch_rollout_point(const RolloutArgs& a, const PointScene& sc, hipStream_t s);
 void launch_rollout_point_nav(const RolloutArgs& a, const PointScene& sc, int blocks, hipStream_t s);
@@ -199,6 +222,7 @@ int regen_chunks(int Kg);   // workgroups per time step of k_regen_part
 int rollout_lanes_for(int Kl);
 // MI355X: 256 CUs x 4 SIMDs.  A rollout launch with more wavefronts than that is throughput-bound: the point_env
 // kernels then run in their two-waves-per-SIMD build (rollout_point_kernel.hpp)
+constexpr int M3_CUS = 256;
 constexpr int M3_SIMDS = 1024;
 inline bool rollout_two_waves(int wavefronts) { return wavefronts > M3_SIMDS; }
 inline bool rollout_three_waves(int wavefronts) { return wavefronts > 4 * M3_SIMDS; }   // (measured: equal at 4 per SIMD, -11 % at 8)

@@ -15,9 +15,9 @@ int rollout_lanes_for(int Kl) {
     return 64;
 }
 
-// returns whether the instance launched leaves the workgroups' cost minima in a.wave_min (wave_min.hpp)
-bool launch_rollout_point(const RolloutArgs& a, const PointScene& sc, hipStream_t s) {
-    const int blocks = (a.Kl + a.lanes - 1) / a.lanes;
+// -1: the general instance (every sampler mode, task at run time); 0..3: the instance with the reference's default sampler
+// and that task compiled in (rollout_point_task*.hip)
+int rollout_point_instance(const RolloutArgs& a) {
 #if defined(M3_ABL_GENERAL_ONLY) || defined(M3_ABL_COUNT) || defined(M3_ABL_PHASES)   // (experiments: one kernel for all modes;
     // the instrumented builds keep their counters in this translation unit)
     const bool general = true;
@@ -27,14 +27,30 @@ bool launch_rollout_point(const RolloutArgs& a, const PointScene& sc, hipStream_
                          (a.cp.task == 3 && !a.multi_modal) || a.scale_dev != nullptr /* update_cov */ ||
                          a.cp.avoid_dyn_obs != 0 /* the extension: the dyn-obs contact force must be formed */;
 #endif
-    if (general) { launch_rollout_point_instance<true, -1>(a, sc, blocks, s); return a.wave_min != nullptr; }
-    switch (a.cp.task) {   // the reference's default sampler: one instance per task (rollout_point_task*.hip)
+    return general ? -1 : a.cp.task;
+}
+
+// returns whether the instance launched leaves the workgroups' cost minima in a.wave_min (wave_min.hpp)
+bool launch_rollout_point(const RolloutArgs& a, const PointScene& sc, hipStream_t s) {
+    const int blocks = (a.Kl + a.lanes - 1) / a.lanes;
+    switch (rollout_point_instance(a)) {   // the reference's default sampler: one instance per task (rollout_point_task*.hip)
+        case -1: launch_rollout_point_instance<true, -1>(a, sc, blocks, s); return a.wave_min != nullptr;
         case 0: launch_rollout_point_nav(a, sc, blocks, s); break;
         case 1: launch_rollout_point_push(a, sc, blocks, s); break;
         case 2: launch_rollout_point_pull(a, sc, blocks, s); break;
         default: launch_rollout_point_pushpull(a, sc, blocks, s); return a.wave_min != nullptr;
     }
     return false;
+}
+
+void launch_rollout_point_batch(const BatchRolloutEntry* tab, int n, int instance, int blocks, bool ref, hipStream_t s) {
+    switch (instance) {
+        case -1: launch_rollout_point_batch_instance<true, -1>(tab, blocks, n, ref, s); break;
+        case 0: launch_rollout_point_nav_batch(tab, blocks, n, ref, s); break;
+        case 1: launch_rollout_point_push_batch(tab, blocks, n, ref, s); break;
+        case 2: launch_rollout_point_pull_batch(tab, blocks, n, ref, s); break;
+        default: launch_rollout_point_pushpull_batch(tab, blocks, n, ref, s); break;
+    }
 }
 
 // delta [K][T][nu] (reference layout) -> [T][K][nu]

@@ -231,5 +231,40 @@ inline void launch_rollout_point_instance(const RolloutArgs& a, const PointScene
     else hipLaunchKernelGGL((k_rollout_point<GENERAL, TASK>), dim3(blocks), dim3(64), 0, s, a, sc);
 }
 
+// ---- batched command (m3_batch_command): one launch for a group of handles that share the instance, K, T and lanes.
+// blockIdx.y picks the handle's entry of the argument table (BatchRolloutEntry, m3_internal.hpp; read-only, so
+// `__restrict__`: nothing the body stores can alias it) and the unchanged body runs on it.  The same four builds with the same
+// attributes, picked by the GROUP's wavefront count (rollout_two_waves / rollout_three_waves): same bits.
+template <bool GENERAL, int TASK>
+__global__ __launch_bounds__(64) void kb_rollout_point(const BatchRolloutEntry* __restrict__ tab) {
+    rollout_point_body<GENERAL, TASK>(tab[blockIdx.y].a, tab[blockIdx.y].sc);
+}
+template <bool GENERAL, int TASK>
+__global__ __launch_bounds__(64) void kb_rollout_point_ref(const BatchRolloutEntry* __restrict__ tab) {
+    constexpr PointScene sc = POINT_SCENE_REFERENCE;
+    rollout_point_body<GENERAL, TASK>(tab[blockIdx.y].a, sc);
+}
+template <bool GENERAL, int TASK>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void kb_rollout_point_occ2(
+    const BatchRolloutEntry* __restrict__ tab) {
+    rollout_point_body<GENERAL, TASK>(tab[blockIdx.y].a, tab[blockIdx.y].sc);
+}
+template <bool GENERAL, int TASK>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void kb_rollout_point_occ3(
+    const BatchRolloutEntry* __restrict__ tab) {
+    rollout_point_body<GENERAL, TASK>(tab[blockIdx.y].a, tab[blockIdx.y].sc);
+}
+// blocks: workgroups of ONE handle (all handles of the group have the same); n: handles; ref: the group runs the
+// reference's solver settings
+template <bool GENERAL, int TASK>
+inline void launch_rollout_point_batch_instance(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s) {
+    const dim3 grid(blocks, n);
+    const int waves = blocks * n;
+    if (rollout_three_waves(waves)) hipLaunchKernelGGL((kb_rollout_point_occ3<GENERAL, TASK>), grid, dim3(64), 0, s, tab);
+    else if (rollout_two_waves(waves)) hipLaunchKernelGGL((kb_rollout_point_occ2<GENERAL, TASK>), grid, dim3(64), 0, s, tab);
+    else if (ref) hipLaunchKernelGGL((kb_rollout_point_ref<GENERAL, TASK>), grid, dim3(64), 0, s, tab);
+    else hipLaunchKernelGGL((kb_rollout_point<GENERAL, TASK>), grid, dim3(64), 0, s, tab);
+}
+
 
 }  // namespace m3

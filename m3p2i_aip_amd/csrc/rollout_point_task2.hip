@@ -7,5 +7,8 @@ namespace m3 {
 void launch_rollout_point_pull(const RolloutArgs& a, const PointScene& sc, int blocks, hipStream_t s) {
     launch_rollout_point_instance<false, 2>(a, sc, blocks, s);
 }
+void launch_rollout_point_pull_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s) {
+    launch_rollout_point_batch_instance<false, 2>(tab, blocks, n, ref, s);
+}
 
 }  // namespace m3

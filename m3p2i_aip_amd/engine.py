@@ -499,3 +499,68 @@ class HipEngine:
             out = torch.empty(self.cfg.K_local, device=self.device, dtype=torch.float32)
         self._ck(self.lib.m3_cost(self._h, out.data_ptr()))
         return out
+
+
+class HipBatch:
+    """One command() of each of several HipEngines (unsharded point_env handles) in one rollout launch and one update
+    launch per group of handles that run the same kernel instance (``m3_batch_command``, include/m3p2i_hip.h).  Each
+    engine's results are bit-identical to its own ``command()``; the batch holds no planner state, only the device
+    workspace of its argument table (allocated here, for up to ``max_handles`` engines per call)."""
+
+    def __init__(self, max_handles, device=0):
+        if not torch.cuda.is_available():
+            raise L.M3Error("HipBatch needs a HIP device (torch.cuda.is_available() is False); there is no CPU fallback")
+        self.lib = L.load()
+        self.max_handles = int(max_handles)
+        self.device = torch.device(f"cuda:{int(device)}")
+        self._b = C.c_void_p()
+        torch.cuda.set_device(self.device)
+        torch.zeros(1, device=self.device)  # make sure the HIP context exists
+        rc = self.lib.m3_batch_create(int(device), self.max_handles, C.byref(self._b))
+        if rc != 0:
+            msg = self.lib.m3_batch_last_error(None)
+            raise L.M3Error(f"m3p2i_hip error {rc}: {msg.decode() if msg else ''}")
+        self._arr = (C.c_void_p * self.max_handles)()
+
+    def close(self):
+        if getattr(self, "_b", None) is not None and self._b:
+            self.lib.m3_batch_destroy(self._b)
+            self._b = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc != 0:
+            msg = self.lib.m3_batch_last_error(self._b)
+            raise L.M3Error(f"m3p2i_hip error {rc}: {msg.decode() if msg else ''}")
+
+    def command(self, engines, sync_host=False):
+        """One MPPI iteration of every engine.  Returns each engine's plan tensor (its set_action_out tensor or the
+        library's ACTION_OUT view), or with sync_host=True the plans on the host: an [n, rows, nu] array (a list of
+        [rows, nu] arrays when the engines' row counts differ)."""
+        engines = list(engines)
+        n = len(engines)
+        arr = self._arr if n <= self.max_handles else (C.c_void_p * n)()   # (the library refuses n > max_handles)
+        for i, e in enumerate(engines):
+            arr[i] = e._h.value
+        if sync_host:
+            rows = [e.cfg.u_per_command if e.cfg.mode_simple else e.cfg.T for e in engines]
+            sizes = [r * e.cfg.nu for r, e in zip(rows, engines)]
+            out = np.zeros(max(sum(sizes), 1), np.float32)
+            self._ck(self.lib.m3_batch_command(self._b, arr, n, out.ctypes.data))
+            if len(set(rows)) == 1 and len({e.cfg.nu for e in engines}) == 1:
+                return out[:sum(sizes)].reshape(n, rows[0], engines[0].cfg.nu)
+            offs = np.cumsum([0] + sizes)
+            return [out[offs[i]:offs[i + 1]].reshape(rows[i], engines[i].cfg.nu) for i in range(n)]
+        self._ck(self.lib.m3_batch_command(self._b, arr, n, None))
+        return [e._action_out if e._action_out is not None else e.buffer(L.BUF_ACTION_OUT) for e in engines]
+
+    def launches(self):
+        """(rollout launches, update launches) of the last successful command."""
+        r, u = C.c_int(), C.c_int()
+        self._ck(self.lib.m3_batch_launches(self._b, C.byref(r), C.byref(u)))
+        return r.value, u.value

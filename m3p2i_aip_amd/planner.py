@@ -33,7 +33,7 @@ import torch
 
 from . import _lib as L
 from . import sampling, scenes
-from .engine import HipEngine, make_config
+from .engine import HipBatch, HipEngine, make_config
 
 # The engine class the planner instantiates.  The product always uses HipEngine (HIP kernels,
 # no fallback); the world_size-2 gloo tests substitute an oracle-backed stand-in to exercise
@@ -580,6 +580,54 @@ class MPPI():
         action_seq = torch.roll(action_seq, -1, dims=0)
         action_seq[-1] = saved
         return action_seq
+
+
+_BATCHES = {}   # device index -> the HipBatch command_batch uses (grown when a call lists more planners)
+
+
+def command_batch(planners, states):
+    """``[p.command(s) for p, s in zip(planners, states)]`` with ONE batched library call (m3_batch_command): the
+    planners' rollouts and updates run in one launch per group of planners that use the same kernel instance.  Each
+    planner does its own preparation (noise, objective, world binding, action slot) and keeps all of its state; the
+    returned tensors are the ones its own command() would have returned, bit for bit.  A planner whose fused / step
+    decision is still pending gets that first command on its own.  Unsharded fused-path point_env planners on the current
+    torch stream only: step-mode or sharded planners and planners with collectives installed raise ValueError (the
+    library refuses the rest, e.g. panda_env, with M3Error)."""
+    planners, states = list(planners), list(states)
+    if len(planners) != len(states):
+        raise ValueError("command_batch: one state per planner")
+    for i, p in enumerate(planners):
+        if p._fused is False:
+            raise ValueError(f"command_batch: planner {i} runs in step mode (user dynamics / running_cost callables)")
+        if p.world_size > 1 or p.collective is not None:
+            raise ValueError(f"command_batch: planner {i} is sharded or has collectives installed")
+        if not isinstance(p._engine, HipEngine):
+            raise ValueError(f"command_batch: planner {i} does not run on the HIP library")
+    if len({id(p) for p in planners}) != len(planners):
+        raise ValueError("command_batch: a planner is listed twice")
+    outs, batched = [None] * len(planners), []
+    for i, (p, state) in enumerate(zip(planners, states)):
+        if p._fused is None:          # (the probe of fused='auto': on its own, as command() does it)
+            outs[i] = p.command(state)
+            continue
+        if not torch.is_tensor(state):
+            state = torch.tensor(state)
+        p.state = state.to(**p.tensor_args)
+        p._engine.use_torch_stream()
+        p._ensure_noise()
+        p._push_objective()
+        p._bind_world()
+        outs[i] = p._next_action_slot()
+        batched.append(p._engine)
+    if batched:
+        dev = batched[0].device.index or 0
+        b = _BATCHES.get(dev)
+        if b is None or b.max_handles < len(batched):
+            if b is not None:
+                b.close()
+            b = _BATCHES[dev] = HipBatch(max(64, len(batched)), device=dev)
+        b.command(batched)
+    return outs
 
 
 class M3P2I(MPPI):

@@ -1,0 +1,152 @@
+"""Batched command (m3_batch_command) vs the best a caller can do without it: n independent point_env planners, each with its
+own jittered world (tools/band_stats.py: jitter_of), commanded
+  batched        ONE m3_batch_command per iteration (one rollout + one update launch per group; multi-modal groups in
+                 residency chunks)
+  back_to_back   n m3_command calls per iteration on the same stream, no host synchronisation in between
+Both are timed with HIP events around `--iters` iterations after `--warmup` (ms per iteration, median of `--repeats`).
+Each configuration runs in a child process of its own under a time limit; the parent prints ONE JSON line.
+
+    python tools/batch_bench.py [--only c2_push] [--json out.json] [--iters 50] [--warmup 10] [--repeats 5]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+# name -> (scenario of band_stats whose jitter the worlds take, task, goal, K, T, multi_modal, the n to measure)
+CONFIGS = {
+    "c2_push": ("corner1_push", "push", (-3.75, -3.75), 2000, 30, False, (1, 4, 16, 64)),
+    "shipped_push": ("case2_halton_push_coll", "push", (-3.0, 3.0), 200, 15, False, (1, 16, 64)),
+    "c3_push_pull": ("corner1_hybrid", "push_pull", (-3.75, -3.75), 4000, 30, True, (1, 4, 16)),
+}
+
+
+def world_of(scenario, episode):
+    """the reference's initial scene (robot at the origin, box (0, 2), dyn-obs (-2, 2) walking in -y) with the episode's
+    jitter: robot / box displaced, the dyn-obs `dyn_phase` ticks into its walk (0.01 m per tick, isaacgym_wrapper.py)"""
+    from band_stats import jitter_of
+    j = jitter_of(scenario, episode)
+    w = np.zeros(18, np.float32)
+    w[0:2] = j["robot"]
+    bx, by = j["box_start"] if j["box_start"] is not None else (0.0, 2.0)
+    w[4:7] = (bx + j["box"][0], by + j["box"][1], 1.0)
+    w[11:14] = (-2.0, 2.0 - 0.01 * j["dyn_phase"], 1.0)
+    return w
+
+
+def measure(name, iters, warmup, repeats):
+    import torch
+    from m3p2i_aip_amd import sampling
+    from m3p2i_aip_amd.engine import HipBatch, HipEngine, make_config
+    scenario, task, goal, K, T, mm, ns = CONFIGS[name]
+    pk = dict(u_min=[-3, -3], u_max=[3, 3], noise_sigma_diag=[3, 3], lambda_=0.5)
+    n_max = max(ns)
+    knots = sampling.halton_knots(K, T, 2, 4, 2, 0, K, scramble="none")
+    engs = []
+    for e_i in range(n_max):
+        e = HipEngine(make_config(K=K, T=T, nu=2, multi_modal=mm, **pk))
+        e.set_noise_knots(knots, 2, 0.5)
+        e.relabel_samples()
+        e.set_objective(task, goal)
+        e.set_world_point_raw(world_of(scenario, e_i))
+        engs.append(e)
+    lib = engs[0].lib
+    batch = HipBatch(n_max)
+    stream = torch.cuda.current_stream()
+
+    def timed(fn):
+        for _ in range(warmup):
+            fn()
+        torch.cuda.synchronize()
+        out = []
+        for _ in range(repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(iters):
+                fn()
+            e1.record(stream)
+            e1.synchronize()
+            out.append(e0.elapsed_time(e1) / iters)
+        return float(np.median(out)), out
+
+    rows = []
+    for n in ns:
+        sel = engs[:n]
+        arr = (C.c_void_p * n)(*[e._h.value for e in sel])
+
+        def batched():
+            rc = lib.m3_batch_command(batch._b, arr, n, None)
+            if rc != 0:
+                raise RuntimeError(lib.m3_batch_last_error(batch._b).decode())
+
+        def back_to_back():
+            for e in sel:
+                if lib.m3_command(e._h, None) != 0:
+                    raise RuntimeError(lib.m3_last_error(e._h).decode())
+
+        t0 = time.perf_counter()
+        b_ms, b_all = timed(batched)
+        r_launch, u_launch = batch.launches()
+        s_ms, s_all = timed(back_to_back)
+        rows.append(dict(n=n, batched_ms=round(b_ms, 4), back_to_back_ms=round(s_ms, 4),
+                         speedup=round(s_ms / b_ms, 3), rollout_launches=r_launch, update_launches=u_launch,
+                         batched_repeats_ms=[round(x, 4) for x in b_all], back_to_back_repeats_ms=[round(x, 4) for x in s_all],
+                         wall_s=round(time.perf_counter() - t0, 2)))
+    batch.close()
+    for e in engs:
+        e.close()
+    return dict(config=name, K=K, T=T, task=task, multi_modal=mm, rows=rows)
+
+
+def main(argv):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--only", default=None, help="comma-separated configuration names")
+    ap.add_argument("--one", default=None, help=argparse.SUPPRESS)     # (child process: one configuration)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--timeout", type=float, default=240.0, help="seconds per configuration")
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args(argv)
+    if a.one:
+        print("RESULT" + json.dumps(measure(a.one, a.iters, a.warmup, a.repeats)), flush=True)
+        return 0
+    from m3p2i_aip_amd import _lib as L
+    names = a.only.split(",") if a.only else list(CONFIGS)
+    res = dict(tool="batch_bench", build_id=L.load().m3_build_id().decode(), iters=a.iters, warmup=a.warmup,
+               repeats=a.repeats, configs=[])
+    rc = 0
+    for name in names:
+        cmd = [sys.executable, os.path.abspath(__file__), "--one", name, "--iters", str(a.iters), "--warmup", str(a.warmup),
+               "--repeats", str(a.repeats)]
+        try:
+            p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout)
+        except subprocess.TimeoutExpired:
+            res["configs"].append(dict(config=name, error="time limit"))
+            rc = 1
+            break      # (a configuration that hung: nothing more on the GPU)
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT")]
+        if p.returncode != 0 or not lines:
+            res["configs"].append(dict(config=name, error="exit %d" % p.returncode, stderr=p.stderr[-2000:]))
+            rc = 1
+            break
+        res["configs"].append(json.loads(lines[-1][6:]))
+    line = json.dumps(res)
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(line + "\n")
+    print(line)
+    return rc
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))
