@@ -125,6 +125,8 @@ __device__ __forceinline__ bool vi_less(float av, int ai, float bv, int bi) {
 // (value, index) argmin as a min over 64-bit keys: the float is mapped to an order-preserving
 // unsigned (sign flip) in the high word, the index sits in the low word, so one unsigned
 // 64-bit min is the lexicographic (value, index) min.  Same DPP butterfly as wave_sum.
+// (-0.0 gets a key below +0.0's: the top-k stages load costs as J + 0.0f, which is +0.0 for both zeros -- they
+// compare equal and are ordered by index, as torch.argsort(J, stable=True) / torch.topk(weights) order them)
 __device__ __forceinline__ unsigned f2ord(float f) {
     const unsigned u = (unsigned)__float_as_int(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -240,7 +242,7 @@ __device__ __noinline__ void topk_stage_a_rounds(const float* J, int Kg, int kba
 #pragma unroll
     for (int e = 0; e < PREP_RPT; ++e) {
         const int k = base + e * WT + tid;
-        const float jv = J[min(k, Kg - 1)];
+        const float jv = J[min(k, Kg - 1)] + 0.0f;   // (-0.0 -> +0.0: see f2ord)
         rv[e] = (k < Kg) ? jv : INF;
     }
     unsigned used = 0u;
@@ -385,7 +387,7 @@ __device__ __forceinline__ void topk_stage_a(const UpdateArgs& a, int blk) {
 #pragma unroll
     for (int e = 0; e < PREP_RPT; ++e) {
         const int k = base + e * PREP_T + tid;
-        const float jv = a.Jall[min(k, Kg - 1)];  // unconditional: the 16 loads stay in flight together
+        const float jv = a.Jall[min(k, Kg - 1)] + 0.0f;  // unconditional: the 16 loads stay in flight together; -0.0 -> +0.0 (f2ord)
         rv[e] = (k < Kg) ? jv : __builtin_inff();
         if (k < Kg) mk = min(mk, f2ord(rv[e]));
     }
@@ -825,7 +827,7 @@ __device__ __forceinline__ void finalize_body(const UpdateArgs& a, float* sm /* 
     }
     const bool multi = a.multi_modal && !a.mode_simple;
     const float* ps = a.reduce + reduce_off_psum(0, T, nu);
-    const float wtot = a.info->wsum_push + a.info->wsum_pull;
+    const float wtot = rd_reduce<SC1>(&a.info->wsum_push) + rd_reduce<SC1>(&a.info->wsum_pull);   // (SC1: written by another workgroup)
     for (int o = tid; o < n; o += blockDim.x) {
         const int t = o / nu, j = o % nu;
         float nv;

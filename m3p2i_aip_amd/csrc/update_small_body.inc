@@ -305,7 +305,9 @@
         f->best_idx = a.kbase + bi[0].i;
         f->best_idx_1 = MULTI ? bi[1].i : -1;
         f->best_idx_2 = MULTI ? bi[2].i : -1;
-        f->wsum_push = hs[0]; f->wsum_pull = hs[1];
+        // (write-through: simple mode's finalize, in the LAST workgroup to arrive, reads the sums back)
+        __hip_atomic_store(&f->wsum_push, hs[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&f->wsum_pull, hs[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         f->pull_preference = hs[1] > hs[0];
         f->beta_1 = beta[1]; f->beta_2 = beta[2];
         if (a.record) {  // shard_mix: local softmin only; k_mix owns eta, beta and the best index

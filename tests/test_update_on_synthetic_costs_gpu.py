@@ -9,6 +9,8 @@ iterative from the start."""
 import numpy as np
 import pytest
 
+from tests import update_ref as R
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
@@ -55,13 +57,21 @@ def test_multi_modal_weights_on_synthetic_costs(K, scale, path):
         w_ref, eta_ref, beta_ref, it_ref = search(JJ)
         w = eng.buffer(buf).cpu().numpy()
         assert 3.0 <= eta <= 10.0
-        # the pass counts agree unless eta grazes a bound of the window in f32
+        # the pass counts agree unless eta grazes a bound of the window in f32: then the reference's eta at the
+        # deciding pass lies within 1e-5 relative of 3 or 10, and the comparison is made against the reference with
+        # that decision reversed (tests/update_ref.py) -- never skipped
         assert abs(iters - it_ref) <= 1, (iters, it_ref)
-        if iters == it_ref:
-            if beta is not None:
-                assert abs(beta - beta_ref) <= 2e-5 * beta_ref
-            np.testing.assert_allclose(w, w_ref, rtol=5e-3, atol=1e-7)
-            assert abs(eta - eta_ref) <= 5e-3 * eta_ref
+        if iters != it_ref:
+            p = min(iters, it_ref)
+            eta_p = R.update_infinite_beta(JJ - JJ.astype(np.float64).min(), 1.0, 10, 3)["etas"][p - 1]
+            assert min(abs(eta_p - 3.0) / 3.0, abs(eta_p - 10.0) / 10.0) <= 1e-5, (iters, it_ref, eta_p)
+            r = R.update_infinite_beta(JJ - JJ.astype(np.float64).min(), 1.0, 10, 3, flip_at=p)
+            assert r["iters"] == iters
+            w_ref, eta_ref, beta_ref = r["exp_"] / r["eta"], r["eta"], r["beta"]
+        if beta is not None:
+            assert abs(beta - beta_ref) <= 2e-5 * beta_ref
+        np.testing.assert_allclose(w, w_ref, rtol=5e-3, atol=1e-7)
+        assert abs(eta - eta_ref) <= 5e-3 * eta_ref
         assert abs(w.sum() - 1.0) < 1e-4
     if scale != 1.0:   # beyond the shrink ladder (64 entries) / the grow ladder (32): the fallback ran
         assert max(info.iters, info.iters_1, info.iters_2) > (65 if scale < 1 else 34)
