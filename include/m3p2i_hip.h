@@ -445,23 +445,28 @@ int m3_p2p_set_memory_kind(m3_handle* h, int first_kind);
  * planner._command_step).  M3_ERR_STATE on a sharded handle (the collectives go in between). */
 int m3_update_finalize(m3_handle* h);
 
-/* ---- batched command: many independent point_env planners in one launch --------------------------------------------
+/* ---- batched command: many independent planners of one environment in one launch -----------------------------------
  * m3_batch_command runs one m3_command of each of hs[0..n-1] -- per group of handles whose own command would run the same
- * kernel instance and build (rollout: the general or the per-task instance, reference scene compiled in or not, K, T,
- * lanes; update: k_update_small's template arguments and workgroup width) ONE rollout launch and ONE update launch (a
- * multi-modal group: one per residency chunk, DESIGN.md "Batched command").  Mixed tasks and sizes are allowed; the
- * grouping is internal.  Each handle's results are bit-identical to what its own m3_command(hs[i], NULL) would have left:
- * plans, buffers, m3_info, wave-order refresh, update_cov step, m3_set_action_out destination, `calls` + 1.  The handles
- * keep all of their state; the batch adds no planner state, only device workspace (allocated by m3_batch_create; a call
- * allocates nothing beyond the lazy allocations m3_command itself makes on a handle's first command).  Handles not
+ * kernel instance and build ONE rollout launch and ONE update launch (a multi-modal group: one per residency chunk,
+ * DESIGN.md "Batched command").  One environment per call: handle 0's.  point_env groups: the general or the per-task
+ * rollout instance, reference scene compiled in or not, K, T, lanes.  panda_env groups: the kernel form each handle's
+ * own m3_rollout would choose from its own busy report and hysteresis, or its m3_set_panda_lanes_per_sample /
+ * m3_set_panda_reach_cost_kernel overrides (lanes per sample, instance, shadow slots, reach-cost record kept), K, T and
+ * lanes per wavefront; a group that keeps the record adds one reach-cost launch, which m3_batch_launches does not count.
+ * Update: k_update_small's template arguments, nu and workgroup width.  Mixed tasks and sizes are allowed; the grouping
+ * is internal.  Each handle's results are bit-identical to what its own m3_command(hs[i], NULL) would have left: plans,
+ * buffers, m3_info, wave-order refresh, update_cov step, m3_set_action_out destination, `calls` + 1, and for panda_env
+ * m3_panda_lanes_per_sample_used and m3_panda_near_share.  The handles keep all of their state; the batch adds no
+ * planner state, only device workspace (allocated by m3_batch_create, its table slots sized for either environment; a
+ * call allocates nothing beyond the lazy allocations m3_command itself makes on a handle's first command).  Handles not
  * listed are not touched: the list may change from call to call.
  * Every check comes before any launch; on a refusal every handle is left as it was:
  *   M3_ERR_BAD_ARG      null batch / handle list / handle, n <= 0, n > max_handles, a handle listed twice, a handle on
  *                       another device
  *   M3_ERR_STATE        a sharded or sim_only handle, handles whose streams differ, and whatever makes m3_rollout refuse
  *                       (no noise set, push_pull without multi_modal)
- *   M3_ERR_UNSUPPORTED  a panda_env handle, a handle whose command does not take the one-launch update (nu = 2:
- *                       K <= 16384, multi-modal K <= 8192)
+ *   M3_ERR_UNSUPPORTED  a handle of the other environment than handle 0's, a handle whose command does not take the
+ *                       one-launch update (nu = 2: K <= 16384, multi-modal K <= 8192; nu = 9: K <= 4096; T * nu <= 2048)
  * The message (m3_batch_last_error) names the offending index.  All work is enqueued on the handles' common stream.
  * actions_host: NULL, or a host buffer that receives the handles' plans one after the other, [rows][nu] each (rows =
  * u_per_command in simple mode, else T: [n][rows][nu] when all agree); the call then synchronises.
@@ -471,7 +476,7 @@ int m3_batch_create(int device, int max_handles, m3_batch** out);   /* all devic
 void m3_batch_destroy(m3_batch* b);
 const char* m3_batch_last_error(const m3_batch* b);   /* b may be NULL: the last failed m3_batch_create on this thread */
 int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float* actions_host);
-/* rollout and update launches of the last successful m3_batch_command */
+/* rollout-kernel and update launches of the last successful m3_batch_command (panda reach-cost launches not counted) */
 int m3_batch_launches(const m3_batch* b, int* rollout_launches, int* update_launches);
 
 int m3_get_buffer(m3_handle* h, int which, void** dev_ptr, long long* nbytes);

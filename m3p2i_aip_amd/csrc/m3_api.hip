@@ -933,6 +933,35 @@ static int prepare_rollout(m3_handle* h, RolloutArgs& a) {
     return M3_OK;
 }
 
+// the panda part of a rollout's arguments (m3_rollout, m3_batch_command): world, objective, quirk Q8's shadow slots, the
+// record buffer of k_panda_reach_cost, and the handle's reading of its last busy report (hysteresis: updates h->panda_reach_busy)
+static void fill_panda_args(m3_handle* h, const RolloutArgs& a, PandaArgs& pa) {
+    std::memcpy(pa.world0, h->pworld0, sizeof(pa.world0));
+    pa.cubeA_actor = h->bind_box; pa.cubeB_actor = h->bind_dyn; pa.obs_actor = h->bind_obs;
+    fill_panda_cost_params(h, pa.cp);
+    // quirk Q8: the reach cost is measured against environment 0's cube (shadow lanes, rollout_panda.hip); a rank of
+    // a sharded command does not hold sample 0's noise row and uses each sample's own cube
+    pa.shadows = (pa.cp.task == 4 && a.k0 == 0 && a.Kl == a.Kg && a.Kg >= 2) ? (pa.cp.multi_modal ? 2 : 1) : 0;
+    pa.lps = h->panda_lps;
+    // reach on a handle that would need shadow slots: with room for one round of wavefronts in a many-lane form (K <= 8192)
+    // the cost moves into a kernel of its own behind the rollout (rollout_panda.hip: k_panda_reach_cost) -- 17 floats per
+    // (step, sample) in between
+    pa.reach_rec = (pa.shadows != 0 && a.Kl <= PANDA_REACH_REC_MAX_K && h->panda_reach_deferred) ? h->panda_reach_rec : nullptr;
+    // the reach command's kernel form follows what the last command's rollouts met (rollout_panda.hip: panda_lps_for): the
+    // kernel's last wavefront reports the share of (sample, substep) pairs with the gripper within reach of a box or an awake
+    // cube into a word of mapped host memory (m3_create), read here without a synchronisation (so it is the report of the
+    // last FINISHED command); a many-lane form from PANDA_BUSY_ON(_REC) per mille, one lane again below PANDA_BUSY_OFF(_REC).
+    pa.busy_hint = h->panda_busy_hint_dev; pa.busy_count = h->panda_busy_count; pa.reach_busy = 0;
+    if (h->panda_busy_hint) {
+        const int share = *(volatile const int*)h->panda_busy_hint - 1;    // (-1: nothing reported yet)
+        // (with the cost kernel available the many-lane form has no shadow slots and takes over earlier)
+        const int on = pa.reach_rec ? PANDA_BUSY_ON_REC : PANDA_BUSY_ON, off = pa.reach_rec ? PANDA_BUSY_OFF_REC : PANDA_BUSY_OFF;
+        if (share >= on) h->panda_reach_busy = 1;
+        else if (share >= 0 && share < off) h->panda_reach_busy = 0;
+        pa.reach_busy = h->panda_reach_busy;
+    }
+}
+
 extern "C" int m3_rollout(m3_handle* h) {
     if (!h) return M3_ERR_BAD_ARG;
     const m3_config& c = h->cfg;
@@ -945,30 +974,7 @@ extern "C" int m3_rollout(m3_handle* h) {
         if (launch_rollout_point(a, h->scene, h->stream)) h->wave_min_rows = (a.Kl + a.lanes - 1) / a.lanes;
     } else {
         PandaArgs pa;
-        std::memcpy(pa.world0, h->pworld0, sizeof(pa.world0));
-        pa.cubeA_actor = h->bind_box; pa.cubeB_actor = h->bind_dyn; pa.obs_actor = h->bind_obs;
-        fill_panda_cost_params(h, pa.cp);
-        // quirk Q8: the reach cost is measured against environment 0's cube (shadow lanes, rollout_panda.hip); a rank of
-        // a sharded command does not hold sample 0's noise row and uses each sample's own cube
-        pa.shadows = (pa.cp.task == 4 && a.k0 == 0 && a.Kl == a.Kg && a.Kg >= 2) ? (pa.cp.multi_modal ? 2 : 1) : 0;
-        pa.lps = h->panda_lps;
-        // reach on a handle that would need shadow slots: with room for one round of wavefronts in a many-lane form (K <= 8192)
-        // the cost moves into a kernel of its own behind the rollout (rollout_panda.hip: k_panda_reach_cost) -- 17 floats per
-        // (step, sample) in between
-        pa.reach_rec = (pa.shadows != 0 && a.Kl <= PANDA_REACH_REC_MAX_K && h->panda_reach_deferred) ? h->panda_reach_rec : nullptr;
-        // the reach command's kernel form follows what the last command's rollouts met (rollout_panda.hip: panda_lps_for): the
-        // kernel's last wavefront reports the share of (sample, substep) pairs with the gripper within reach of a box or an awake
-        // cube into a word of mapped host memory (m3_create), read here without a synchronisation (so it is the report of the
-        // last FINISHED command); a many-lane form from PANDA_BUSY_ON(_REC) per mille, one lane again below PANDA_BUSY_OFF(_REC).
-        pa.busy_hint = h->panda_busy_hint_dev; pa.busy_count = h->panda_busy_count; pa.reach_busy = 0;
-        if (h->panda_busy_hint) {
-            const int share = *(volatile const int*)h->panda_busy_hint - 1;    // (-1: nothing reported yet)
-            // (with the cost kernel available the many-lane form has no shadow slots and takes over earlier)
-            const int on = pa.reach_rec ? PANDA_BUSY_ON_REC : PANDA_BUSY_ON, off = pa.reach_rec ? PANDA_BUSY_OFF_REC : PANDA_BUSY_OFF;
-            if (share >= on) h->panda_reach_busy = 1;
-            else if (share >= 0 && share < off) h->panda_reach_busy = 0;
-            pa.reach_busy = h->panda_reach_busy;
-        }
+        fill_panda_args(h, a, pa);
         const int wgs = launch_rollout_panda(a, pa, h->pscene, h->stream, &h->panda_lps_used);
         if (a.wave_min) h->wave_min_rows = wgs;
     }
@@ -1520,34 +1526,45 @@ extern "C" int m3_command(m3_handle* h, float* action_host) {
 }
 
 // ---------------------------------- batched command ------------------------------------
-// One command() of each of n unsharded point_env handles: per group of handles that run the same kernel instance, ONE
-// rollout launch and ONE update launch (a multi-modal group: as many as its residency chunks), the handles' arguments
-// read from a device table indexed by blockIdx.y (DESIGN.md "Batched command").  The handles keep all of their state;
-// the batch owns only the table: BATCH_SLOTS pinned host slots, each with a device slot and an event recorded after the
-// call's last launch (so it guards the host slot's copy AND the device slot's readers, whichever stream they ran on).
+// One command() of each of n unsharded handles of one environment (handle 0's): per group of handles that run the same
+// kernel instance, ONE rollout launch and ONE update launch (a multi-modal group: as many as its residency chunks), the
+// handles' arguments read from a device table indexed by blockIdx.y (DESIGN.md "Batched command").  A panda_env group that
+// keeps the reach-cost record adds one k_panda_reach_cost launch (not counted by m3_batch_launches).  The handles keep
+// all of their state; the batch owns only the table: BATCH_SLOTS pinned host slots, each with a device slot and an event
+// recorded after the call's last launch (so it guards the host slot's copy AND the device slot's readers, whichever
+// stream they ran on).
 static thread_local std::string g_batch_err;
 constexpr int BATCH_SLOTS = 4;
 
 namespace {
 struct BatchKey {
-    int instance, ref, K, T, lanes;   // rollout: rollout_point_instance, reference scene compiled in, sizes
+    int instance, ref, K, T, lanes;   // rollout: rollout_point_instance, reference scene compiled in, sizes (panda: 0, 0,
+                                      // K, T, the plan's lanes per wavefront)
+    int lps, forces, general, shadows, rec;   // panda_env: the plan's form (PandaRolloutPlan; point_env: all 0)
     SmallUpdateInstance upd;          // update: k_update_small's template arguments, width, top-k workgroups
 };
 bool same_rollout(const BatchKey& x, const BatchKey& y) {
-    return x.instance == y.instance && x.ref == y.ref && x.K == y.K && x.T == y.T && x.lanes == y.lanes;
+    return x.instance == y.instance && x.ref == y.ref && x.K == y.K && x.T == y.T && x.lanes == y.lanes && x.lps == y.lps &&
+           x.forces == y.forces && x.general == y.general && x.shadows == y.shadows && x.rec == y.rec;
 }
 bool less_rollout(const BatchKey& x, const BatchKey& y) {
     if (x.instance != y.instance) return x.instance < y.instance;
     if (x.ref != y.ref) return x.ref < y.ref;
+    if (x.lps != y.lps) return x.lps < y.lps;
+    if (x.forces != y.forces) return x.forces < y.forces;
+    if (x.general != y.general) return x.general < y.general;
+    if (x.shadows != y.shadows) return x.shadows < y.shadows;
+    if (x.rec != y.rec) return x.rec < y.rec;
     if (x.K != y.K) return x.K < y.K;
     if (x.T != y.T) return x.T < y.T;
     return x.lanes < y.lanes;
 }
 bool same_update(const BatchKey& x, const BatchKey& y) {
-    return x.upd.multi == y.upd.multi && x.upd.jr == y.upd.jr && x.upd.wt == y.upd.wt && x.upd.n_cand == y.upd.n_cand &&
-           x.T == y.T;
+    return x.upd.nu == y.upd.nu && x.upd.multi == y.upd.multi && x.upd.jr == y.upd.jr && x.upd.wt == y.upd.wt &&
+           x.upd.n_cand == y.upd.n_cand && x.T == y.T;
 }
 bool less_update(const BatchKey& x, const BatchKey& y) {
+    if (x.upd.nu != y.upd.nu) return x.upd.nu < y.upd.nu;
     if (x.upd.multi != y.upd.multi) return x.upd.multi < y.upd.multi;
     if (x.upd.jr != y.upd.jr) return x.upd.jr < y.upd.jr;
     if (x.upd.wt != y.upd.wt) return x.upd.wt < y.upd.wt;
@@ -1560,7 +1577,8 @@ size_t align16(size_t n) { return (n + 15) / 16 * 16; }
 struct m3_batch {
     int device = 0, max_handles = 0;
     std::string err;
-    size_t upd_off = 0, slot_bytes = 0;   // a slot: [max_handles] BatchRolloutEntry (from 0) | [max_handles] UpdateArgs
+    size_t upd_off = 0, slot_bytes = 0;   // a slot: [max_handles] BatchRolloutEntry or BatchPandaEntry (from 0) |
+                                          // [max_handles] UpdateArgs
     char* host[BATCH_SLOTS] = {};
     char* dev[BATCH_SLOTS] = {};
     hipEvent_t done[BATCH_SLOTS] = {};
@@ -1571,6 +1589,8 @@ struct m3_batch {
     std::vector<m3_handle*> seen;
     std::vector<BatchKey> key;
     std::vector<int> by_roll, by_upd;
+    std::vector<BatchPandaEntry> pent;      // panda_env: the rollout entries in call order (copied into the slot by group)
+    std::vector<PandaRolloutPlan> plan;
 };
 
 #define BATCHK(b, expr)                                                                  \
@@ -1613,13 +1633,16 @@ extern "C" int m3_batch_create(int device, int max_handles, m3_batch** out) {
     if (!b) { g_batch_err = "m3_batch_create: out of host memory"; return M3_ERR_HIP; }
     b->device = device;
     b->max_handles = max_handles;
-    b->upd_off = align16((size_t)max_handles * sizeof(BatchRolloutEntry));
+    constexpr size_t entry = std::max(sizeof(BatchRolloutEntry), sizeof(BatchPandaEntry));
+    b->upd_off = align16((size_t)max_handles * entry);
     b->slot_bytes = b->upd_off + (size_t)max_handles * sizeof(UpdateArgs);
     try {
         b->seen.resize(max_handles);
         b->key.resize(max_handles);
         b->by_roll.resize(max_handles);
         b->by_upd.resize(max_handles);
+        b->pent.resize(max_handles);
+        b->plan.resize(max_handles);
     } catch (...) {
         delete b;
         g_batch_err = "m3_batch_create: out of host memory";
@@ -1675,10 +1698,13 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
                 if (hs[j] == hs[i]) return batch_refuse(b, M3_ERR_BAD_ARG, i, "handle listed twice");
     }
     const hipStream_t s = hs[0]->stream;
+    const bool panda = hs[0]->cfg.env_type == M3_ENV_PANDA;   // one environment per call: handle 0's
     for (int i = 0; i < n; ++i) {
         m3_handle* h = hs[i];
         const m3_config& c = h->cfg;
-        if (c.env_type != M3_ENV_POINT) return batch_refuse(b, M3_ERR_UNSUPPORTED, i, "panda_env handle (point_env only)");
+        if (c.env_type != hs[0]->cfg.env_type)
+            return batch_refuse(b, M3_ERR_UNSUPPORTED, i, panda ? "point_env handle in a batch of panda_env handles (one environment per call)"
+                                                                : "panda_env handle in a batch of point_env handles (one environment per call)");
         if (c.K_local != c.K_global) return batch_refuse(b, M3_ERR_STATE, i, "sharded handle (K_local != K_global)");
         if (c.sim_only) return batch_refuse(b, M3_ERR_STATE, i, "handle was created sim_only");
         if (h->stream != s) return batch_refuse(b, M3_ERR_STATE, i, "its stream differs from handle 0's");
@@ -1688,20 +1714,44 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
         ua.fuse_finalize = 1;
         ua.Jall = (const float*)h->buf[M3_BUF_TRAJ_COST];
         if (!can_fuse_finalize(h) || !update_small_applies(ua))
-            return batch_refuse(b, M3_ERR_UNSUPPORTED, i, "its command does not take the one-launch update (nu = 2: K <= 16384; "
-                                                          "multi-modal K <= 8192)");
+            return batch_refuse(b, M3_ERR_UNSUPPORTED, i, panda ? "its command does not take the one-launch update (nu = 9: "
+                                                                  "K <= 4096, T * nu <= 2048)"
+                                                                : "its command does not take the one-launch update (nu = 2: K <= "
+                                                                  "16384; multi-modal K <= 8192)");
+        BatchKey& k = b->key[i];
+        k.upd = update_small_instance(ua);
+        b->by_roll[i] = b->by_upd[i] = i;
+        if (panda) continue;   // (the rollout's form is planned below, after every check)
         RolloutArgs ka;   // (the fields the rollout's instance depends on, as prepare_rollout sets them)
         std::memset(&ka, 0, sizeof(ka));
         ka.multi_modal = c.multi_modal; ka.mode_simple = c.mode_simple; ka.sampling_random = c.sampling_random;
         ka.scale_dev = h->cov_active ? (const float*)h->buf[M3_BUF_COV] + c.nu : nullptr;
         fill_cost_params(h, ka.cp);
-        BatchKey& k = b->key[i];
         k.instance = rollout_point_instance(ka);
         k.ref = point_scene_is_reference(h->scene) ? 1 : 0;
         k.K = c.K_local; k.T = c.T;
         k.lanes = h->lanes_override > 0 ? h->lanes_override : rollout_lanes_for(c.K_local);
-        k.upd = update_small_instance(ua);
-        b->by_roll[i] = b->by_upd[i] = i;
+        k.lps = k.forces = k.general = k.shadows = k.rec = 0;
+    }
+    // ---- panda_env: each handle's rollout form, as m3_rollout would choose it (its own busy report and hysteresis) ----
+    if (panda) {
+        for (int i = 0; i < n; ++i) {
+            m3_handle* h = hs[i];
+            BatchPandaEntry& e = b->pent[i];
+            const int rc = prepare_rollout(h, e.a);
+            if (rc != M3_OK) { b->err = "m3_batch_command: " + h->err; return rc; }
+            fill_panda_args(h, e.a, e.pa);
+            const PandaRolloutPlan pl = plan_rollout_panda(e.a, e.pa);
+            e.a.lanes = pl.lanes;
+            e.sc = h->pscene;
+            b->plan[i] = pl;
+            h->panda_lps_used = pl.lps;
+            if (e.a.wave_min) h->wave_min_rows = pl.rows;
+            BatchKey& k = b->key[i];
+            k.instance = k.ref = 0;
+            k.K = h->cfg.K_local; k.T = h->cfg.T; k.lanes = pl.lanes;
+            k.lps = pl.lps; k.forces = pl.forces; k.general = pl.general; k.shadows = e.pa.shadows; k.rec = pl.rec;
+        }
     }
     // ---- groups: handles in key order (ties in call order) ----
     const BatchKey* key = b->key.data();
@@ -1718,9 +1768,14 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
         b->in_flight[slot] = false;
     }
     BatchRolloutEntry* hr = reinterpret_cast<BatchRolloutEntry*>(b->host[slot]);
-    const size_t upd_off = align16((size_t)n * sizeof(BatchRolloutEntry));
+    BatchPandaEntry* hp = reinterpret_cast<BatchPandaEntry*>(b->host[slot]);
+    const size_t upd_off = align16((size_t)n * (panda ? sizeof(BatchPandaEntry) : sizeof(BatchRolloutEntry)));
     UpdateArgs* hu = reinterpret_cast<UpdateArgs*>(b->host[slot] + upd_off);
     for (int p = 0; p < n; ++p) {
+        if (panda) {
+            hp[p] = b->pent[b->by_roll[p]];
+            continue;
+        }
         m3_handle* h = hs[b->by_roll[p]];
         const int rc = prepare_rollout(h, hr[p].a);   // (+ the handle's wave-order refresh when it is due: its own launch)
         if (rc != M3_OK) { b->err = "m3_batch_command: " + h->err; return rc; }
@@ -1737,6 +1792,7 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
     char* dslot = b->dev[slot];
     BATCHK(b, hipMemcpyAsync(dslot, b->host[slot], upd_off + (size_t)n * sizeof(UpdateArgs), hipMemcpyHostToDevice, s));
     const BatchRolloutEntry* dr = reinterpret_cast<const BatchRolloutEntry*>(dslot);
+    const BatchPandaEntry* dp = reinterpret_cast<const BatchPandaEntry*>(dslot);
     const UpdateArgs* du = reinterpret_cast<const UpdateArgs*>(dslot + upd_off);
     // ---- one rollout launch per group ----
     int n_roll = 0, n_upd = 0;
@@ -1744,6 +1800,12 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
         const BatchKey& k = key[b->by_roll[p]];
         int q = p + 1;
         while (q < n && same_rollout(key[b->by_roll[q]], k)) ++q;
+        if (panda) {   // (+ one k_panda_reach_cost launch when the group keeps the record buffer: not counted)
+            launch_rollout_panda_batch(dp + p, q - p, b->plan[b->by_roll[p]], k.K, s);
+            ++n_roll;
+            p = q;
+            continue;
+        }
         const int blocks = (k.K + k.lanes - 1) / k.lanes;
         launch_rollout_point_batch(dr + p, q - p, k.instance, blocks, k.ref != 0, s);
         ++n_roll;
@@ -1758,7 +1820,10 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
         int q = p + 1;
         while (q < n && same_update(key[b->by_upd[q]], k)) ++q;
         int chunk = q - p;
-        if (k.upd.multi) chunk = std::max(1, M3_CUS * update_small_batch_blocks_per_cu(k.upd) / (k.T + k.upd.n_cand));
+        if (k.upd.multi) {
+            const int per_cu = k.upd.nu == 9 ? update_small9_batch_blocks_per_cu(k.upd) : update_small_batch_blocks_per_cu(k.upd);
+            chunk = std::max(1, M3_CUS * per_cu / (k.T + k.upd.n_cand));
+        }
         for (int r = p; r < q; r += chunk) {
             launch_update_small_batch(du + r, std::min(chunk, q - r), k.upd, k.T, s);
             ++n_upd;

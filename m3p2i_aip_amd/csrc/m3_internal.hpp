@@ -169,7 +169,9 @@ struct SmallUpdateInstance {
 SmallUpdateInstance update_small_instance(const UpdateArgs& a);
 // blocks of the batched multi-modal update that are resident per CU (update_small.hip; DESIGN.md "Batched command")
 int update_small_batch_blocks_per_cu(const SmallUpdateInstance& in);
-// one launch of k_update_small's body for n handles whose entries (tab[0 .. n-1], device) share `in` and T
+// the same for the nu = 9 (panda_env) instances, kb_update_small9
+int update_small9_batch_blocks_per_cu(const SmallUpdateInstance& in);
+// one launch of k_update_small's body for n handles whose entries (tab[0 .. n-1], device) share `in` and T (and nu)
 void launch_update_small_batch(const UpdateArgs* tab, int n, const SmallUpdateInstance& in, int T, hipStream_t s);
 // -1: the general instance of the point_env rollout; 0..3: the per-task instance of that task (launch_rollout_point)
 int rollout_point_instance(const RolloutArgs& a);
@@ -295,6 +297,21 @@ struct PandaArgs {
 };
 int launch_rollout_panda(const RolloutArgs& a, const PandaArgs& pa, const PandaScene& sc, hipStream_t s,
                          int* lps_used = nullptr);   // returns its workgroups; *lps_used = the kernel form it chose
+// the kernel form a panda rollout launch takes (rollout_panda.hip: plan_rollout_panda): lanes per sample, instance
+// (FORCES = pick / place, GENERAL = random sampler or simple mode), k_panda_reach_cost behind it, active lanes per
+// wavefront, rollout workgroups, and the rows of minima the launch leaves (the reach-cost kernel's workgroups with it)
+struct PandaRolloutPlan {
+    int lps, forces, general, rec, lanes, blocks, rows;
+};
+PandaRolloutPlan plan_rollout_panda(const RolloutArgs& a, PandaArgs& pa);
+struct BatchPandaEntry {     // one panda_env handle's rollout in m3_batch_command's table (a.lanes: the plan's)
+    RolloutArgs a;
+    PandaArgs pa;
+    PandaScene sc;
+};
+// one launch of the plan's instance for n handles of K_local = Kl and the same plan (tab: device, n entries), + one launch
+// of the reach-cost kernel when the plan keeps the record buffer
+void launch_rollout_panda_batch(const BatchPandaEntry* tab, int n, const PandaRolloutPlan& p, int Kl, hipStream_t s);
 void launch_psim_step(const PandaScene& sc, const SimViews& v, float* world, const float* u, float* u_keep, int Kl,
                       hipStream_t s);
 void launch_psim_pull(const PandaScene& sc, const SimViews& v, float* world, int Kl, hipStream_t s);

@@ -78,243 +78,7 @@ __device__ __forceinline__ float in_vgpr(float v) {   // keep a uniform value in
 template <bool FORCES, bool GENERAL, int LPS>
 __global__ __launch_bounds__(64) void k_rollout_panda(const RolloutArgs a_, const PandaArgs pa,
                                                       const PandaScene sc_) {
-    PANDA_CORNER_LDS(LPS);
-    // (a_.lanes samples per 64-wide wavefront: m3_set_rollout_lanes; the idle lanes leave at once)
-    // Shadow lanes (quirk Q8, pa.shadows = 1 or 2; reach on an unsharded handle): the reference's reach cost measures every
-    // rollout against the cube of ENVIRONMENT 0 (and, for the tilted mode, the orientation of the first environment of the
-    // second half), which under world spec v2 is a quantity of THAT rollout's simulation.  The last sample slot of every
-    // wavefront (lane 63; with LPS = 16 the last group of sixteen) re-simulates sample 0 and the one before it sample K / 2 in
-    // lockstep with the wavefront's own samples (same noise rows, same operations, so the same bits in every wavefront);
-    // their cubes are read with v_readlane after each step.  They store nothing.  Cost: 64 / 63 (62) more wavefronts
-    // (LPS = 16: 4 / 3, 4 / 2), no cross-wavefront synchronisation.
-    constexpr int SPW = 64 / LPS;                       // sample slots per wavefront
-    const bool deferred = LPS != 1 && pa.reach_rec != nullptr;   // (the one-lane form keeps its shadow slots: launch_rollout_panda)
-    const int slot = (int)threadIdx.x / LPS, gl = (int)threadIdx.x % LPS;
-    const bool shadow = slot >= SPW - pa.shadows;
-    const bool writer = !shadow && gl == 0;             // the lane that stores the sample's scalars
-    int i = blockIdx.x * a_.lanes + slot;
-    if (shadow) i = (slot == SPW - 1) ? 0 : pa.cp.half_K;
-    else if (slot >= a_.lanes || i >= a_.Kl) return;
-    // The per-joint constants (bounds, noise scale, servo coefficients: 54 floats) are uniform, but
-    // there are not enough scalar registers to keep them across the step loop, and the compiler
-    // re-read them from the kernel arguments every step (~12 scalar loads per step, each followed by
-    // a wait with nothing else resident on the SIMD to cover it).  Vector registers are plentiful at
-    // one wave per SIMD, so they are parked there once.
-    RolloutArgs a = a_;
-    PandaScene sc = sc_;
-    if constexpr (!GENERAL) { a.sampling_random = 0; a.mode_simple = 0; a.full_sigma = 0; a.noise_abs_cost = 0; }
-#pragma unroll
-    for (int j = 0; j < 9; ++j) {
-        a.u_min[j] = in_vgpr(a_.u_min[j]); a.u_max[j] = in_vgpr(a_.u_max[j]);
-        // (update_cov rewrites the scale on the device after every command: mppi.py:516)
-        a.scale_tril[j] = in_vgpr(a_.scale_dev ? a_.scale_dev[j] : a_.scale_tril[j]);
-        sc.a[j] = in_vgpr(sc_.a[j]); sc.rden[j] = in_vgpr(sc_.rden[j]); sc.dv[j] = in_vgpr(sc_.dv[j]);
-    }
-    const int Kl = a.Kl, T = a.T;
-    const int k = a.k0 + i;
-    PandaWorld w;
-    if (a.sim_dof) panda_world_from_sim(a.sim_dof, a.sim_root, pa.cubeA_actor, pa.cubeB_actor, pa.obs_actor, w);
-    else panda_world_from_raw(pa.world0, w);
-    float hp[3], trav = 0.0f;   // hand origin at the last evaluated kinematics, joint travel since (panda_step)
-    panda_infer_held(sc, w, hp);
-
-    const bool is_last = (k == a.Kg - 1);
-    const bool first_half = k < pa.cp.half_K;
-    const bool halton = !a.mode_simple;
-    const float* mptr = a.mean;
-    if (a.multi_modal && halton) mptr = first_half ? a.mean1 : a.mean2;
-
-    // inputs of step t+1 are fetched before step t is simulated (one wavefront per SIMD: nothing
-    // else hides the latency of a load that is consumed at once)
-    const bool use_best = halton && a.multi_modal && (k == 0 || k == pa.cp.half_K);
-    const float* bptr = (k == 0) ? a.best1 : a.best2;
-    float nd[9], nm[9];
-    auto fetch = [&](int t) {
-        // _shift_action: mppi.py:266-273; simple mode: torch.roll(U, -1), mppi.py:221
-        const int ts = a.mode_simple ? ((t + 1 == T) ? 0 : t + 1) : ((t + 1 < T) ? t + 1 : T - 1);
-        const float* dptr = a.delta + ((size_t)t * Kl + i) * 9;
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            nd[j] = a.sampling_random ? 0.0f : dptr[j];
-            nm[j] = use_best ? bptr[ts * 9 + j] : mptr[ts * 9 + j];
-        }
-    };
-    fetch(0);
-    FkCarry<LPS> fkc;
-    fkc.valid = false;
-    fkc.near_lane_substeps = 0;
-    float J = 0.0f, g = 1.0f, S = 0.0f, pc = 0.0f;
-#ifdef M3_PABL_PROF
-    PandaProf prof = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    long long prof_step = 0;
-    const long long prof_start = __builtin_readcyclecounter();
-#endif
-    for (int t = 0; t < T; ++t) {
-        float cd[9], cm[9];
-#pragma unroll
-        for (int j = 0; j < 9; ++j) { cd[j] = nd[j]; cm[j] = nm[j]; }
-        if (t + 1 < T) fetch(t + 1);
-        if constexpr (GENERAL) {
-            if (a.sampling_random) {   // N(noise_mu, noise_sigma) = mu + L z (noise_stream.hpp; order as the oracle)
-                float z[10];
-#pragma unroll
-                for (int p = 0; p < 5; ++p) gauss_pair(a.seed, a.call, (unsigned)k, (unsigned)t, (unsigned)p, z[2 * p], z[2 * p + 1]);
-#pragma unroll
-                for (int j = 0; j < 9; ++j) {
-                    float acc;
-                    if (a.full_sigma) {
-                        acc = a.noise_mats[j * 9 + 0] * z[0];
-#pragma unroll
-                        for (int q = 1; q <= j; ++q) acc = acc + a.noise_mats[j * 9 + q] * z[q];
-                    } else acc = z[j] * a_.scale_tril[j];   // (the configured scale, not update_cov's)
-                    cd[j] = a.noise_mu[j] + acc;
-                }
-            }
-        }
-        float u[9], e[9];
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            float aj;
-            if (GENERAL && a.mode_simple) {
-                aj = fmaxf(fminf(cm[j] + cd[j], a.u_max[j]), a.u_min[j]);             // mppi.py:341-345
-            } else {
-                const float d = is_last ? 0.0f : cd[j];                                // mppi.py:392
-                aj = fmaxf(fminf(cm[j] + d * a.scale_tril[j], a.u_max[j]), a.u_min[j]);
-                if (use_best) aj = cm[j];                                              // :407-409
-            }
-            if (j >= 7) {                                                              // :412-416 / :346-350
-                if (a.gripper_cmd == 1) aj = 1.5f;
-                else if (a.gripper_cmd == 2) aj = -1.5f;
-            }
-            float uj = a.u_scale * aj;                                                 // :297
-            if (a.sample_null_action && is_last) uj = 0.0f;                            // :300-302
-            u[j] = uj;
-            e[j] = uj;                                     // :313 (the update consumes the scaled stack)
-        }
-        PandaObs obs;
-#ifdef M3_PABL_PROF
-        const long long prof_s0 = __builtin_readcyclecounter();
-        panda_step<FORCES, true, LPS>(sc, w, u, obs, cs, hp, &trav, &fkc, &prof);
-        prof_step += __builtin_readcyclecounter() - prof_s0;
-#else
-        panda_step<FORCES, true, LPS>(sc, w, u, obs, cs, hp, &trav, &fkc);
-#endif
-        float cube0[3], qh0[4];
-        if (deferred) {
-            // the reach cost of this step is formed by k_panda_reach_cost (below) from what it reads of the sample -- and of
-            // samples 0 and K / 2, whose cube it is measured against (quirk Q8): no shadow slots in this launch
-            if (writer) {
-                float* r = pa.reach_rec + (size_t)t * REACH_REC * Kl + i;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) { r[(0 + j) * Kl] = obs.left[j]; r[(3 + j) * Kl] = obs.right[j]; r[(14 + j) * Kl] = w.A.p[j]; }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { r[(6 + j) * Kl] = obs.left_q[j]; r[(10 + j) * Kl] = w.A.q[j]; }
-            }
-#pragma unroll
-            for (int j = 0; j < 3; ++j) cube0[j] = w.A.p[j];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) qh0[j] = w.A.q[j];
-        } else if (pa.shadows) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) cube0[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w.A.p[j]), 63));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float q0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w.A.q[j]), 63));
-                const float q1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w.A.q[j]), 63 - LPS));
-                qh0[j] = first_half ? q0 : q1;     // (one shadow: single mode, the tilt term does not read it)
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) cube0[j] = w.A.p[j];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) qh0[j] = w.A.q[j];
-        }
-        const float c = deferred ? 0.0f : panda_cost(pa.cp, w, obs, k, cube0, qh0);
-        if (writer) {
-            *reinterpret_cast<float4*>(a.states + ((size_t)t * Kl + i) * 4) =
-                make_float4(w.q[0], w.qd[0], w.q[1], w.qd[1]);                   // reactive_tamp.py:66-69
-            if (!deferred) a.cost_h[(size_t)t * Kl + i] = c;
-        }
-        if constexpr (LPS == 1) {
-            if (!shadow) {
-                float* ap = a.actions + ((size_t)t * Kl + i) * 9;
-#pragma unroll
-                for (int j = 0; j < 9; ++j) ap[j] = e[j];
-            }
-        } else {          // the sample's lanes store one control each
-            const Gen<LPS> eo = gen_from9<LPS>(e);
-#pragma unroll
-            for (int el = 0; el < Gen<LPS>::N; ++el) {
-                const int cj = gen_coord<LPS>(el);
-                if (!shadow && cj < 9) a.actions[((size_t)t * Kl + i) * 9 + cj] = eo.a[el];
-            }
-        }
-        J = J + g * c;
-        g = g * a.gamma;
-        if constexpr (GENERAL) {
-            if (a.mode_simple) {   // mppi.py:309 and the perturbation cost :355-372: sum U * ((lambda * noise) @ Sigma^-1)
-                S = S + c;
-                float ln[9];
-#pragma unroll
-                for (int j = 0; j < 9; ++j) {
-                    float n = e[j] - cm[j];
-                    if (a.noise_abs_cost) n = fabsf(n);
-                    ln[j] = a.lambda_ * n;
-                }
-#pragma unroll
-                for (int j = 0; j < 9; ++j) {
-                    float ac;
-                    if (a.full_sigma) {
-                        ac = ln[0] * a.noise_mats[81 + 0 * 9 + j];
-#pragma unroll
-                        for (int q = 1; q < 9; ++q) ac = ac + ln[q] * a.noise_mats[81 + q * 9 + j];
-                    } else ac = ln[j] * a.sigma_inv[j];
-                    pc = pc + cm[j] * ac;
-                }
-            }
-        }
-    }
-#ifdef M3_PABL_PROF     // (cost_horizon rows 0-5 of the sample: total / solver / near-path clocks, substeps with gripper rows / body rows / near)
-    if (writer && T >= 6) {
-        a.cost_h[(size_t)0 * Kl + i] = (float)(__builtin_readcyclecounter() - prof_start);
-        a.cost_h[(size_t)1 * Kl + i] = (float)prof.solve_clk;
-        a.cost_h[(size_t)2 * Kl + i] = (float)prof.near_clk;
-        a.cost_h[(size_t)3 * Kl + i] = (float)prof.n_robot;
-        a.cost_h[(size_t)4 * Kl + i] = (float)prof.n_body;
-        a.cost_h[(size_t)5 * Kl + i] = (float)prof.n_near;
-        if (T >= 10) {
-            a.cost_h[(size_t)6 * Kl + i] = (float)prof.detect_clk;
-            a.cost_h[(size_t)7 * Kl + i] = (float)prof.post_clk;
-            a.cost_h[(size_t)8 * Kl + i] = (float)prof.n_act;
-            a.cost_h[(size_t)9 * Kl + i] = (float)prof.n_fk;
-        }
-        if (T >= 14) {
-            a.cost_h[(size_t)10 * Kl + i] = (float)prof.pre_clk;
-            a.cost_h[(size_t)11 * Kl + i] = (float)prof.mid_clk;
-            a.cost_h[(size_t)12 * Kl + i] = (float)prof.wake_clk;
-            a.cost_h[(size_t)13 * Kl + i] = (float)prof_step;
-        }
-    }
-#endif
-    if (!deferred) {      // (else: k_panda_reach_cost writes the costs and leaves the minima behind)
-        if (writer) a.J[i] = (GENERAL && a.mode_simple) ? (S + pc) : J;
-        if (a.wave_min) wave_min_store(a.wave_min, J, first_half, writer);
-    }
-    // What the NEXT reach commands' kernel form is chosen by (panda_lps_for): the share of (sample, substep) pairs of this launch
-    // in which the gripper was within reach of a box or a cube was awake, in 1/1000.  Every wavefront adds its count; the last one to finish (the
-    // same atomic is its ticket) turns the sum into the share, stores it into a word of mapped host memory and clears the counters for the next
-    // launch.  A hint: results do not depend on the form.
-    if (pa.busy_hint != nullptr && threadIdx.x == 0) {
-        // ONE atomic carries both: bits 0-23 wavefronts finished, bits 24-63 the sum of their counts
-        const unsigned long long mine = ((unsigned long long)(unsigned)(fkc.near_lane_substeps / LPS) << 24) | 1ull;
-        const unsigned long long old = atomicAdd(pa.busy_count, mine);
-        if ((old & 0xffffffull) == (unsigned long long)(gridDim.x - 1u)) {
-            const unsigned long long total = (old + mine) >> 24;
-            *pa.busy_count = 0ull;
-            const unsigned long long all = (unsigned long long)Kl * (unsigned long long)(T * sc.substeps);
-            *(volatile int*)pa.busy_hint = (int)((total * 1000ull) / (all ? all : 1ull)) + 1;    // (+ 1: 0 = nothing reported yet)
-        }
-    }
+#include "rollout_panda_body.inc"
 }
 
 // The reach cost of a launch that ran WITHOUT shadow slots (PandaArgs::reach_rec): quirk Q8 measures every rollout against the
@@ -331,42 +95,7 @@ __global__ __launch_bounds__(64) void k_rollout_panda(const RolloutArgs a_, cons
 // (16 -> 7 us at C4: profiles/r06).
 constexpr int RC_TS = 4, RC_CH = 32;      // time slices per workgroup; steps per LDS chunk
 __global__ __launch_bounds__(64 * RC_TS) void k_panda_reach_cost(const RolloutArgs a, const PandaArgs pa) {
-    __shared__ float s_c[RC_CH][64];
-    const int Kl = a.Kl, T = a.T;
-    const int lane = (int)threadIdx.x & 63, slice = (int)threadIdx.x >> 6;
-    const int i0 = blockIdx.x * 64 + lane;
-    const bool mine = i0 < Kl;
-    const int i = mine ? i0 : 0;          // (every lane stays for the barriers)
-    const int k = a.k0 + i;
-    const bool first_half = k < pa.cp.half_K;
-    const int h = (pa.cp.multi_modal && !first_half) ? pa.cp.half_K : 0;    // whose cube orientation the tilt term reads
-    float J = 0.0f, g = 1.0f;
-    for (int t0 = 0; t0 < T; t0 += RC_CH) {
-        for (int tt = slice; tt < RC_CH && t0 + tt < T; tt += RC_TS) {
-            const int t = t0 + tt;
-            const float* r = pa.reach_rec + (size_t)t * REACH_REC * Kl;
-            PandaObs o;
-            PandaWorld w;
-            float cube0[3], qh0[4];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) { o.left[j] = r[(0 + j) * Kl + i]; o.right[j] = r[(3 + j) * Kl + i]; cube0[j] = r[(14 + j) * Kl]; }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { o.left_q[j] = r[(6 + j) * Kl + i]; w.A.q[j] = r[(10 + j) * Kl + i]; qh0[j] = r[(10 + j) * Kl + h]; }
-            const float c = panda_cost(pa.cp, w, o, k, cube0, qh0);
-            if (mine) a.cost_h[(size_t)t * Kl + i] = c;
-            s_c[tt][lane] = c;
-        }
-        __syncthreads();
-        if (slice == 0) {
-            for (int tt = 0; tt < RC_CH && t0 + tt < T; ++tt) {
-                J = J + g * s_c[tt][lane];
-                g = g * a.gamma;
-            }
-        }
-        __syncthreads();
-    }
-    if (slice == 0 && mine) a.J[i] = J;
-    if (a.wave_min) wave_min_store(a.wave_min, J, first_half, mine && slice == 0);
+#include "panda_reach_cost_body.inc"
 }
 
 // Lanes per sample, by what was measured at C4's size (profiles/r05/panda_lps_bench.json, panda_reach_mid_bench.json; K = 4000,
@@ -397,24 +126,12 @@ static int panda_lps_for(const RolloutArgs& a, const PandaArgs& pa) {
     if (waves(8) <= 1024) return 8;
     return 1;
 }
-template <int LPS>
-static int launch_rollout_panda_lps(const RolloutArgs& a_in, const PandaArgs& pa, const PandaScene& sc, hipStream_t s) {
-    constexpr int SPW = 64 / LPS;
-    int lanes = (a_in.lanes >= 1 && a_in.lanes <= SPW) ? a_in.lanes : SPW;
-    if (lanes > SPW - pa.shadows) lanes = SPW - pa.shadows;
-    RolloutArgs a = a_in;
-    a.lanes = lanes;
-    const dim3 grid((a.Kl + lanes - 1) / lanes), block(64);
-    if (a.sampling_random || a.mode_simple) {
-        if (pa.cp.task == 5) hipLaunchKernelGGL((k_rollout_panda<true, true, LPS>), grid, block, 0, s, a, pa, sc);
-        else hipLaunchKernelGGL((k_rollout_panda<false, true, LPS>), grid, block, 0, s, a, pa, sc);
-    } else if (pa.cp.task == 5) hipLaunchKernelGGL((k_rollout_panda<true, false, LPS>), grid, block, 0, s, a, pa, sc);
-    else hipLaunchKernelGGL((k_rollout_panda<false, false, LPS>), grid, block, 0, s, a, pa, sc);
-    return (int)grid.x;
-}
-// returns the number of workgroups (= rows of the wave_min table)
-int launch_rollout_panda(const RolloutArgs& a, const PandaArgs& pa_in, const PandaScene& sc, hipStream_t s, int* lps_used) {
-    PandaArgs pa = pa_in;
+// The form of a launch: the lanes per sample, the instance, the lanes per wavefront adjusted for the shadow slots and the grid;
+// pa becomes what the kernels receive (no shadow slots with the record buffer; without it, and with the shadow slots again,
+// when the one-lane form is chosen).  Launches nothing: launch_rollout_panda launches it at once, m3_batch_command groups the
+// handles by it.
+PandaRolloutPlan plan_rollout_panda(const RolloutArgs& a, PandaArgs& pa) {
+    const PandaArgs pa_in = pa;
     // reach without shadow slots (k_panda_reach_cost): when the handle holds the record buffer (m3_api.hip: K up to 8192), the
     // sampler is the default one and a many-lane form is what the launch
     // sixteen (eight) lanes per sample run in; automatic choice: while few of the last command's (sample, substep) pairs had the
@@ -435,16 +152,77 @@ int launch_rollout_panda(const RolloutArgs& a, const PandaArgs& pa_in, const Pan
         if (lps == 1) pa = pa_in, pa.reach_rec = nullptr;
     }
     if (pa.reach_rec == nullptr) lps = panda_lps_for(a, pa);
-    if (lps_used) *lps_used = lps;
-    if (pa.reach_rec != nullptr) {
-        if (lps == 16) (void)launch_rollout_panda_lps<16>(a, pa, sc, s);
-        else (void)launch_rollout_panda_lps<8>(a, pa, sc, s);
+    PandaRolloutPlan p;
+    p.lps = lps;
+    p.forces = pa.cp.task == 5 ? 1 : 0;
+    p.general = (a.sampling_random || a.mode_simple) ? 1 : 0;
+    p.rec = pa.reach_rec != nullptr ? 1 : 0;
+    const int spw = 64 / lps;
+    int lanes = (a.lanes >= 1 && a.lanes <= spw) ? a.lanes : spw;
+    if (lanes > spw - pa.shadows) lanes = spw - pa.shadows;
+    p.lanes = lanes;
+    p.blocks = (a.Kl + lanes - 1) / lanes;
+    p.rows = p.rec ? (a.Kl + 63) / 64 : p.blocks;
+    return p;
+}
+template <int LPS>
+static void launch_rollout_panda_lps(const RolloutArgs& a_in, const PandaArgs& pa, const PandaScene& sc, const PandaRolloutPlan& p,
+                                     hipStream_t s) {
+    RolloutArgs a = a_in;
+    a.lanes = p.lanes;
+    const dim3 grid(p.blocks), block(64);
+    if (p.general) {
+        if (p.forces) hipLaunchKernelGGL((k_rollout_panda<true, true, LPS>), grid, block, 0, s, a, pa, sc);
+        else hipLaunchKernelGGL((k_rollout_panda<false, true, LPS>), grid, block, 0, s, a, pa, sc);
+    } else if (p.forces) hipLaunchKernelGGL((k_rollout_panda<true, false, LPS>), grid, block, 0, s, a, pa, sc);
+    else hipLaunchKernelGGL((k_rollout_panda<false, false, LPS>), grid, block, 0, s, a, pa, sc);
+}
+// returns the number of workgroups (= rows of the wave_min table)
+int launch_rollout_panda(const RolloutArgs& a, const PandaArgs& pa_in, const PandaScene& sc, hipStream_t s, int* lps_used) {
+    PandaArgs pa = pa_in;
+    const PandaRolloutPlan p = plan_rollout_panda(a, pa);
+    if (lps_used) *lps_used = p.lps;
+    if (p.lps == 16) launch_rollout_panda_lps<16>(a, pa, sc, p, s);
+    else if (p.lps == 8) launch_rollout_panda_lps<8>(a, pa, sc, p, s);
+    else launch_rollout_panda_lps<1>(a, pa, sc, p, s);
+    if (p.rec) {
         const dim3 grid((a.Kl + 63) / 64), block(64 * RC_TS);
         hipLaunchKernelGGL(k_panda_reach_cost, grid, block, 0, s, a, pa);
-        return (int)grid.x;
     }
-    return lps == 16 ? launch_rollout_panda_lps<16>(a, pa, sc, s) : lps == 8 ? launch_rollout_panda_lps<8>(a, pa, sc, s)
-                                                                              : launch_rollout_panda_lps<1>(a, pa, sc, s);
+    return p.rows;
+}
+
+// ---- batched command (m3_batch_command) ---------------------------------------------------------------------------
+// One workgroup of the handle tab[blockIdx.y], its own grid's workgroup blockIdx.x: the unchanged body.  The table is
+// read-only during the launch (`__restrict__`).  A group's handles share K and the adjusted lanes, so gridDim.x is every
+// handle's own grid -- which the busy report's last-wavefront ticket counts against (each handle has its own counter).
+template <bool FORCES, bool GENERAL, int LPS>
+__global__ __launch_bounds__(64) void kb_rollout_panda(const BatchPandaEntry* __restrict__ tab) {
+    const RolloutArgs& a_ = tab[blockIdx.y].a;
+    const PandaArgs& pa = tab[blockIdx.y].pa;
+    const PandaScene& sc_ = tab[blockIdx.y].sc;
+#include "rollout_panda_body.inc"
+}
+__global__ __launch_bounds__(64 * RC_TS) void kb_panda_reach_cost(const BatchPandaEntry* __restrict__ tab) {
+    const RolloutArgs& a = tab[blockIdx.y].a;
+    const PandaArgs& pa = tab[blockIdx.y].pa;
+#include "panda_reach_cost_body.inc"
+}
+void launch_rollout_panda_batch(const BatchPandaEntry* tab, int n, const PandaRolloutPlan& p, int Kl, hipStream_t s) {
+    const dim3 grid(p.blocks, n), block(64);
+#define M3_LAUNCH_PBATCH(LPS_)                                                                                             \
+    do {                                                                                                                   \
+        if (p.general) {                                                                                                   \
+            if (p.forces) hipLaunchKernelGGL((kb_rollout_panda<true, true, LPS_>), grid, block, 0, s, tab);                \
+            else hipLaunchKernelGGL((kb_rollout_panda<false, true, LPS_>), grid, block, 0, s, tab);                        \
+        } else if (p.forces) hipLaunchKernelGGL((kb_rollout_panda<true, false, LPS_>), grid, block, 0, s, tab);            \
+        else hipLaunchKernelGGL((kb_rollout_panda<false, false, LPS_>), grid, block, 0, s, tab);                           \
+    } while (0)
+    if (p.lps == 16) M3_LAUNCH_PBATCH(16);
+    else if (p.lps == 8) M3_LAUNCH_PBATCH(8);
+    else M3_LAUNCH_PBATCH(1);
+#undef M3_LAUNCH_PBATCH
+    if (p.rec) hipLaunchKernelGGL(kb_panda_reach_cost, dim3((Kl + 63) / 64, n), dim3(64 * RC_TS), 0, s, tab);
 }
 
 // ======================= step mode ======================================================

@@ -119,8 +119,32 @@ int update_small_batch_blocks_per_cu(const SmallUpdateInstance& in) {
     return 4;                     // <true, 8 | 16, 256>: 73 / 126 VGPRs, 106 SGPRs -> 6 / 4 waves per SIMD, 4 at most
 }
 
+// The nu = 9 (panda_env) twin: a kernel of its own name, so that kb_update_small keeps exactly its instances.
+template <bool MULTI, int JR>
+__global__ __launch_bounds__(256) void kb_update_small9(const UpdateArgs* __restrict__ tab) {
+    constexpr int NU = 9, WT = 256;
+    const UpdateArgs& a = tab[blockIdx.y];
+#include "update_small_body.inc"
+}
+
+// The same bound for kb_update_small9<true, JR> (the rule above; the plan in LDS is up to T * nu = 2048 floats, 8 KB):
+// tests/test_batch_panda_cpu.py re-derives it from the built library.
+int update_small9_batch_blocks_per_cu(const SmallUpdateInstance& in) {
+    if (in.jr == 16) return 2;    // <true, 16>: 238 VGPRs -> 2 waves per SIMD
+    return 4;                     // <true, 8>: 127 VGPRs -> 4 waves per SIMD
+}
+
 void launch_update_small_batch(const UpdateArgs* tab, int n, const SmallUpdateInstance& in, int T, hipStream_t s) {
     const dim3 grid(T + in.n_cand, n);
+    if (in.nu == 9) {
+        const size_t lds9 = (size_t)T * 9 * sizeof(float);
+        if (in.multi) {
+            if (in.jr == 8) hipLaunchKernelGGL((kb_update_small9<true, 8>), grid, dim3(256), lds9, s, tab);
+            else hipLaunchKernelGGL((kb_update_small9<true, 16>), grid, dim3(256), lds9, s, tab);
+        } else if (in.jr == 8) hipLaunchKernelGGL((kb_update_small9<false, 8>), grid, dim3(256), lds9, s, tab);
+        else hipLaunchKernelGGL((kb_update_small9<false, 16>), grid, dim3(256), lds9, s, tab);
+        return;
+    }
     const size_t lds = (size_t)T * 2 * sizeof(float);
 #define M3_LAUNCH_BATCH(MULTI_, JR_, WT_) hipLaunchKernelGGL((kb_update_small<MULTI_, JR_, WT_>), grid, dim3(WT_), lds, s, tab)
     if (in.multi) {

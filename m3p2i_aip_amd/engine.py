@@ -502,9 +502,10 @@ class HipEngine:
 
 
 class HipBatch:
-    """One command() of each of several HipEngines (unsharded point_env handles) in one rollout launch and one update
-    launch per group of handles that run the same kernel instance (``m3_batch_command``, include/m3p2i_hip.h).  Each
-    engine's results are bit-identical to its own ``command()``; the batch holds no planner state, only the device
+    """One command() of each of several HipEngines (unsharded handles of one environment per call: point_env or
+    panda_env, as the first engine's) in one rollout launch and one update launch per group of handles that run the same
+    kernel instance (``m3_batch_command``, include/m3p2i_hip.h).  Each engine's results are bit-identical to its own
+    ``command()``, a panda_env engine's automatic kernel form included; the batch holds no planner state, only the device
     workspace of its argument table (allocated here, for up to ``max_handles`` engines per call)."""
 
     def __init__(self, max_handles, device=0):

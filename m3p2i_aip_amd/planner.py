@@ -586,13 +586,14 @@ _BATCHES = {}   # device index -> the HipBatch command_batch uses (grown when a 
 
 
 def command_batch(planners, states):
-    """``[p.command(s) for p, s in zip(planners, states)]`` with ONE batched library call (m3_batch_command): the
-    planners' rollouts and updates run in one launch per group of planners that use the same kernel instance.  Each
+    """``[p.command(s) for p, s in zip(planners, states)]`` with one batched library call (m3_batch_command) per
+    environment in the list: the planners' rollouts and updates run in one launch per group of planners that use the
+    same kernel instance (point_env and panda_env planners alike; a list that mixes them makes one call for each).  Each
     planner does its own preparation (noise, objective, world binding, action slot) and keeps all of its state; the
-    returned tensors are the ones its own command() would have returned, bit for bit.  A planner whose fused / step
-    decision is still pending gets that first command on its own.  Unsharded fused-path point_env planners on the current
-    torch stream only: step-mode or sharded planners and planners with collectives installed raise ValueError (the
-    library refuses the rest, e.g. panda_env, with M3Error)."""
+    returned tensors are the ones its own command() would have returned, bit for bit -- for a panda_env planner with the
+    same automatic kernel form.  A planner whose fused / step decision is still pending gets that first command on its
+    own.  Unsharded fused-path planners on the current torch stream only: step-mode or sharded planners and planners with
+    collectives installed raise ValueError (the library refuses the rest, e.g. panda_env with K > 4096, with M3Error)."""
     planners, states = list(planners), list(states)
     if len(planners) != len(states):
         raise ValueError("command_batch: one state per planner")
@@ -626,7 +627,8 @@ def command_batch(planners, states):
             if b is not None:
                 b.close()
             b = _BATCHES[dev] = HipBatch(max(64, len(batched)), device=dev)
-        b.command(batched)
+        for env in sorted({e.cfg.env_type for e in batched}):     # (the library takes one environment per call)
+            b.command([e for e in batched if e.cfg.env_type == env])
     return outs
 
 

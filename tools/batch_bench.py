@@ -1,5 +1,7 @@
-"""Batched command (m3_batch_command) vs the best a caller can do without it: n independent point_env planners, each with its
-own jittered world (tools/band_stats.py: jitter_of), commanded
+"""Batched command (m3_batch_command) vs the best a caller can do without it: n independent planners, each with its own
+jittered world (point_env: tools/band_stats.py's jitter_of; panda_env: cubeA's start displaced by up to 2 cm as
+band_stats.panda_episodes does, then the product's own closed loop, tools/closed_loop.py, run into the scene measured),
+commanded
   batched        ONE m3_batch_command per iteration (one rollout + one update launch per group; multi-modal groups in
                  residency chunks)
   back_to_back   n m3_command calls per iteration on the same stream, no host synchronisation in between
@@ -28,6 +30,34 @@ CONFIGS = {
     "shipped_push": ("case2_halton_push_coll", "push", (-3.0, 3.0), 200, 15, False, (1, 16, 64)),
     "c3_push_pull": ("corner1_hybrid", "push_pull", (-3.75, -3.75), 4000, 30, True, (1, 4, 16)),
 }
+# panda_env: name -> (task, the closed-loop phase the scene is taken from + ticks into it, K, T, the n to measure)
+PANDA_CONFIGS = {
+    "c4_reach": ("reach", ("reach", 40), 4000, 20, (1, 4, 16)),
+    "c4_pick": ("pick", ("pick", 12), 4000, 20, (1, 4, 16)),
+    "shipped_pick": ("pick", ("pick", 6), 200, 12, (1, 16, 64)),
+}
+
+
+def panda_world_of(task_phase, K, T, episode, device):
+    """57 floats (q9 qd9 | cubeA | cubeB | dyn-obs) and the goal: the world the closed loop (planner K, T) of an episode whose
+    cubeA starts displaced (tools/band_stats.py: panda_episodes; episode 0 the reference scene) is in `ticks` ticks into
+    `phase`"""
+    import closed_loop
+    from m3p2i_aip_amd import scenes
+    rng = np.random.default_rng([77, episode])
+    cube = (0.0, 0.0) if episode == 0 else tuple(rng.uniform(-0.02, 0.02, 2).tolist())
+    phase, ticks = task_phase
+    res = closed_loop.run("config_panda", [f"mppi.num_samples={K}", f"mppi.horizon={T}", f"mppi.device={device}"], ticks=400,
+                          until_task=phase, extra_ticks=ticks, jitter=dict(cube=cube))
+    cap = res.get("captured")
+    if cap is None or cap["task"] != phase:
+        raise RuntimeError(f"episode {episode}: no {phase} scene: {res.get('timeline')}")
+    dof, root = np.asarray(cap["dof_state"], np.float32).reshape(-1), np.asarray(cap["root_state"], np.float32)
+    w = np.zeros(57, np.float32)
+    w[0:9], w[9:18] = dof[0::2], dof[1::2]
+    for o, name in ((18, "cubeA"), (31, "cubeB"), (44, "dyn-obs")):
+        w[o:o + 13] = root[scenes.actor_index("panda_env", name)]
+    return w, cap["goal"]
 
 
 def world_of(scenario, episode):
@@ -47,18 +77,33 @@ def measure(name, iters, warmup, repeats):
     import torch
     from m3p2i_aip_amd import sampling
     from m3p2i_aip_amd.engine import HipBatch, HipEngine, make_config
-    scenario, task, goal, K, T, mm, ns = CONFIGS[name]
-    pk = dict(u_min=[-3, -3], u_max=[3, 3], noise_sigma_diag=[3, 3], lambda_=0.5)
-    n_max = max(ns)
-    knots = sampling.halton_knots(K, T, 2, 4, 2, 0, K, scramble="none")
     engs = []
-    for e_i in range(n_max):
-        e = HipEngine(make_config(K=K, T=T, nu=2, multi_modal=mm, **pk))
-        e.set_noise_knots(knots, 2, 0.5)
-        e.relabel_samples()
-        e.set_objective(task, goal)
-        e.set_world_point_raw(world_of(scenario, e_i))
-        engs.append(e)
+    if name in PANDA_CONFIGS:
+        task, phase, K, T, ns = PANDA_CONFIGS[name]
+        mm = False
+        n_max = max(ns)
+        pk = dict(u_min=[-2.0] * 7 + [-1.5] * 2, u_max=[2.0] * 7 + [1.5] * 2, noise_sigma_diag=[10.0] * 7 + [0.8] * 2,
+                  lambda_=0.05, pre_height_diff=0.05, dt=0.01)
+        knots = sampling.halton_knots(K, T, 9, 4, 2, 0, K, scramble="none")
+        worlds = [panda_world_of(phase, K, T, e_i, "cuda:0") for e_i in range(n_max)]
+        for w, goal in worlds:
+            e = HipEngine(make_config(K=K, T=T, nu=9, env_type="panda_env", **pk))
+            e.set_noise_knots(knots, 2, 0.5)
+            e.set_objective(task, goal, gripper_cmd=1 if task == "reach" else 2)
+            e.set_world_panda_raw(w)
+            engs.append(e)
+    else:
+        scenario, task, goal, K, T, mm, ns = CONFIGS[name]
+        pk = dict(u_min=[-3, -3], u_max=[3, 3], noise_sigma_diag=[3, 3], lambda_=0.5)
+        n_max = max(ns)
+        knots = sampling.halton_knots(K, T, 2, 4, 2, 0, K, scramble="none")
+        for e_i in range(n_max):
+            e = HipEngine(make_config(K=K, T=T, nu=2, multi_modal=mm, **pk))
+            e.set_noise_knots(knots, 2, 0.5)
+            e.relabel_samples()
+            e.set_objective(task, goal)
+            e.set_world_point_raw(world_of(scenario, e_i))
+            engs.append(e)
     lib = engs[0].lib
     batch = HipBatch(n_max)
     stream = torch.cuda.current_stream()
@@ -99,6 +144,7 @@ def measure(name, iters, warmup, repeats):
         s_ms, s_all = timed(back_to_back)
         rows.append(dict(n=n, batched_ms=round(b_ms, 4), back_to_back_ms=round(s_ms, 4),
                          speedup=round(s_ms / b_ms, 3), rollout_launches=r_launch, update_launches=u_launch,
+                         panda_lanes_per_sample=sorted({e.panda_lanes_per_sample_used() for e in sel}) if name in PANDA_CONFIGS else None,
                          batched_repeats_ms=[round(x, 4) for x in b_all], back_to_back_repeats_ms=[round(x, 4) for x in s_all],
                          wall_s=round(time.perf_counter() - t0, 2)))
     batch.close()
@@ -114,14 +160,14 @@ def main(argv):
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--timeout", type=float, default=240.0, help="seconds per configuration")
+    ap.add_argument("--timeout", type=float, default=400.0, help="seconds per configuration")
     ap.add_argument("--json", default=None)
     a = ap.parse_args(argv)
     if a.one:
         print("RESULT" + json.dumps(measure(a.one, a.iters, a.warmup, a.repeats)), flush=True)
         return 0
     from m3p2i_aip_amd import _lib as L
-    names = a.only.split(",") if a.only else list(CONFIGS)
+    names = a.only.split(",") if a.only else list(CONFIGS) + list(PANDA_CONFIGS)
     res = dict(tool="batch_bench", build_id=L.load().m3_build_id().decode(), iters=a.iters, warmup=a.warmup,
                repeats=a.repeats, configs=[])
     rc = 0
