@@ -479,6 +479,52 @@ int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float* actions_ho
 /* rollout-kernel and update launches of the last successful m3_batch_command (panda reach-cost launches not counted) */
 int m3_batch_launches(const m3_batch* b, int* rollout_launches, int* update_launches);
 
+/* ---- batched closed-loop episodes (point_env): N episodes of tools/closed_loop.run in lockstep --------------------------
+ * One N-env "real world" (a sim_only point_env handle with K_local == n and bound views: the engine of an
+ * IsaacGymWrapper(num_envs=n)), row e the 1-env world of episode e, planned by planners[e].  m3_episodes_tick runs one tick
+ * of every episode: a pre-command kernel (dyn-obs walk with the episode's phase, success test, suction-gate snapshot), one
+ * m3_batch_command of the planners whose episodes were still running after the last tick, a post-command kernel (trace
+ * row, suction, step, collision count), one copy of the status words to pinned memory and ONE host synchronisation.
+ * Before every batched command each planner is bound (m3_bind_sim_point) to its row of the world.  An episode ends at its
+ * success tick (before its command, as closed_loop.run) or after the step of tick max_ticks - 1; an ended episode's
+ * metrics are frozen and its planner leaves the next tick's batch (its world row keeps evolving, unrecorded).
+ * A planner's first command (the fused / step probe) is the caller's: m3_episodes_begin (pre kernel + status, synchronises)
+ * and m3_episodes_end (post kernel + status, synchronises) frame a tick whose commands the caller issues itself.
+ * Each planner's m3_set_action_out destination is read at create and must stay the same at every tick.
+ * m3_episodes_create refuses, before any launch and leaving every handle as it was: a world that is not a sim_only
+ * point_env handle with bound views or whose K_local differs from n (M3_ERR_STATE), a panda_env planner (M3_ERR_UNSUPPORTED),
+ * a planner m3_batch_command would refuse (its code), a handle on another stream than the world's, a handle listed twice,
+ * a planner without an action-out destination, n <= 0, max_ticks <= 0, a bad spec (M3_ERR_BAD_ARG / M3_ERR_STATE).
+ * All device and pinned memory is allocated by m3_episodes_create; a tick allocates nothing beyond what the planners' own
+ * first commands allocate. */
+typedef enum { M3_SUCTION_OFF = 0, M3_SUCTION_ON = 1, M3_SUCTION_PULL_PREFERENCE = 2 } m3_suction_mode;
+typedef struct {
+    int task;            /* M3_TASK_NAVIGATION .. M3_TASK_PUSH_PULL: what PLANNER_SIMPLE checks for success */
+    float goal[2];
+    int dyn_phase;       /* the dyn-obs walk of tick i is that of tick i + dyn_phase (>= 0) */
+    int suction;         /* m3_suction_mode: push / navigation off, pull on, push_pull the previous pull preference */
+    float kp_suction;
+} m3_episode_spec;
+typedef struct {
+    int done_tick;       /* -1 while running; else the success tick or max_ticks - 1 */
+    int success;
+    int collision_ticks; /* ticks with |Fx| + |Fy| > 0.1 on the dyn-obs after the step */
+    float final_pos[2];  /* box x, y (robot x, y for navigation) at the end, f32 */
+} m3_episode_status;
+typedef struct m3_episodes m3_episodes;
+int m3_episodes_create(m3_handle* world, m3_handle* const* planners, const m3_episode_spec* specs, int n, int max_ticks,
+                       int trace, m3_episodes** out);
+int m3_episodes_tick(m3_episodes* eps, m3_batch* batch);
+int m3_episodes_begin(m3_episodes* eps);
+int m3_episodes_end(m3_episodes* eps);
+/* status_out [n] (host); trace_out (host, may be NULL) [max_ticks][n][10] floats: robot x, y, box x, y, qz, qw, dyn-obs x,
+ * y, action x, y -- rows of ticks an episode did not trace are undefined.  Synchronises. */
+int m3_episodes_status(m3_episodes* eps, m3_episode_status* status_out, float* trace_out);
+int m3_episodes_ticks_done(const m3_episodes* eps);
+int m3_episodes_running(const m3_episodes* eps);   /* episodes not ended as of the last status copy (no synchronisation) */
+void m3_episodes_destroy(m3_episodes* eps);
+const char* m3_episodes_last_error(const m3_episodes* eps);   /* eps may be NULL: the last failed create on this thread */
+
 int m3_get_buffer(m3_handle* h, int which, void** dev_ptr, long long* nbytes);
 int m3_reduce_len(const m3_handle* h);
 int m3_record_len(const m3_handle* h);

@@ -61,6 +61,18 @@ INFO_WORDS = C.sizeof(Info) // 4
 INFO_PULL_PREFERENCE = Info.pull_preference.offset // 4   # index of the field in an int32 view of M3_BUF_INFO
 
 
+class EpisodeSpec(C.Structure):
+    _fields_ = [("task", C.c_int), ("goal", C.c_float * 2), ("dyn_phase", C.c_int), ("suction", C.c_int),
+                ("kp_suction", C.c_float)]
+
+
+class EpisodeStatus(C.Structure):
+    _fields_ = [("done_tick", C.c_int), ("success", C.c_int), ("collision_ticks", C.c_int), ("final_pos", C.c_float * 2)]
+
+
+SUCTION_OFF, SUCTION_ON, SUCTION_PULL_PREFERENCE = 0, 1, 2
+
+
 class Timing(C.Structure):
     _fields_ = [("rollout_ms", C.c_float), ("update_ms", C.c_float),
                 ("finalize_ms", C.c_float), ("total_ms", C.c_float)]
@@ -133,6 +145,15 @@ SYMBOLS = [
     ("m3_batch_last_error", C.c_char_p, [_H]),
     ("m3_batch_command", C.c_int, [_H, C.POINTER(_H), C.c_int, _FP]),
     ("m3_batch_launches", C.c_int, [_H, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("m3_episodes_create", C.c_int, [_H, C.POINTER(_H), C.POINTER(EpisodeSpec), C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
+    ("m3_episodes_tick", C.c_int, [_H, _H]),
+    ("m3_episodes_begin", C.c_int, [_H]),
+    ("m3_episodes_end", C.c_int, [_H]),
+    ("m3_episodes_status", C.c_int, [_H, C.POINTER(EpisodeStatus), C.c_void_p]),
+    ("m3_episodes_ticks_done", C.c_int, [_H]),
+    ("m3_episodes_running", C.c_int, [_H]),
+    ("m3_episodes_destroy", None, [_H]),
+    ("m3_episodes_last_error", C.c_char_p, [_H]),
     ("m3_get_buffer", C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]),
     ("m3_reduce_len", C.c_int, [_H]),
     ("m3_record_len", C.c_int, [_H]),

@@ -2059,3 +2059,244 @@ extern "C" int m3_cost(m3_handle* h, float* cost) {
     HIPCHK(h, hipGetLastError());
     return M3_OK;
 }
+
+// ---------------------------------- batched closed-loop episodes ------------------------------------
+// N episodes of tools/closed_loop.run (point_env) in lockstep: the world handle's N rows are the episodes' 1-env worlds
+// (DESIGN.md §7c).  Per tick: k_episodes_pre, m3_batch_command of the running episodes' planners, k_episodes_post, one
+// copy of the status words, one synchronisation.
+static thread_local std::string g_eps_err;
+
+struct m3_episodes {
+    m3_handle* world = nullptr;
+    int n = 0, max_ticks = 0, tick = 0;
+    bool mid_tick = false;           // between m3_episodes_begin and m3_episodes_end
+    std::string err;
+    std::vector<m3_handle*> planners;
+    std::vector<const float*> plan;  // each planner's action-out, fixed at create
+    std::vector<m3_handle*> live;    // scratch: this tick's batch
+    char* dev = nullptr;             // lanes | status | gates
+    float* trace = nullptr;
+    m3_episode_status* host = nullptr;   // pinned copy of the status words
+    m3::EpisodeArgs args{};
+};
+
+extern "C" const char* m3_episodes_last_error(const m3_episodes* eps) { return eps ? eps->err.c_str() : g_eps_err.c_str(); }
+
+extern "C" void m3_episodes_destroy(m3_episodes* eps) {
+    if (!eps) return;
+    if (eps->world) (void)hipStreamSynchronize(eps->world->stream);   // (kernels may still use the memory)
+    if (eps->dev) (void)hipFree(eps->dev);
+    if (eps->trace) (void)hipFree(eps->trace);
+    if (eps->host) (void)hipHostFree(eps->host);
+    delete eps;
+}
+
+static int eps_refuse(int code, int i, const std::string& msg) {
+    char head[64];
+    if (i >= 0) std::snprintf(head, sizeof(head), "m3_episodes_create: planner %d: ", i);
+    else std::snprintf(head, sizeof(head), "m3_episodes_create: ");
+    g_eps_err = std::string(head) + msg;
+    return code;
+}
+
+extern "C" int m3_episodes_create(m3_handle* world, m3_handle* const* planners, const m3_episode_spec* specs, int n,
+                                  int max_ticks, int trace, m3_episodes** out) {
+    if (!out) return eps_refuse(M3_ERR_BAD_ARG, -1, "null argument");
+    *out = nullptr;
+    // ---- every check before any allocation or launch ----
+    if (!world || !planners || !specs) return eps_refuse(M3_ERR_BAD_ARG, -1, "null argument");
+    if (n <= 0 || n > 65535) return eps_refuse(M3_ERR_BAD_ARG, -1, "n must be in 1 .. 65535");
+    if (max_ticks <= 0) return eps_refuse(M3_ERR_BAD_ARG, -1, "max_ticks must be > 0");
+    const m3_config& wc = world->cfg;
+    if (wc.env_type != M3_ENV_POINT || !wc.sim_only || !world->views_bound || !world->sim_world || !world->views.dof_state ||
+        !world->views.root_state || !world->views.rigid_body_state || !world->views.net_contact_force)
+        return eps_refuse(M3_ERR_STATE, -1, "the world must be a sim_only point_env handle with all four views bound");
+    if (wc.K_local != n || wc.K_global != n) return eps_refuse(M3_ERR_STATE, -1, "the world's K_local must equal n (one row per episode)");
+    for (int i = 0; i < n; ++i) {
+        m3_handle* h = planners[i];
+        if (!h) return eps_refuse(M3_ERR_BAD_ARG, i, "null handle");
+        if (h == world) return eps_refuse(M3_ERR_BAD_ARG, i, "the world handle is listed as a planner");
+        for (int j = 0; j < i; ++j)
+            if (planners[j] == h) return eps_refuse(M3_ERR_BAD_ARG, i, "handle listed twice");
+        const m3_config& c = h->cfg;
+        if (c.env_type != M3_ENV_POINT) return eps_refuse(M3_ERR_UNSUPPORTED, i, "panda_env planner (point_env episodes only)");
+        if (c.device != wc.device) return eps_refuse(M3_ERR_BAD_ARG, i, "handle on another device than the world");
+        if (h->stream != world->stream) return eps_refuse(M3_ERR_STATE, i, "its stream differs from the world's");
+        // what m3_batch_command would refuse
+        if (c.K_local != c.K_global) return eps_refuse(M3_ERR_STATE, i, "sharded handle (K_local != K_global)");
+        if (c.sim_only) return eps_refuse(M3_ERR_STATE, i, "handle was created sim_only");
+        if (const char* why = rollout_refusal(h)) return eps_refuse(M3_ERR_STATE, i, why);
+        UpdateArgs ua;
+        fill_update_args(h, ua);
+        ua.fuse_finalize = 1;
+        ua.Jall = (const float*)h->buf[M3_BUF_TRAJ_COST];
+        if (!can_fuse_finalize(h) || !update_small_applies(ua))
+            return eps_refuse(M3_ERR_UNSUPPORTED, i, "its command does not take the one-launch update (nu = 2: K <= 16384; "
+                                                     "multi-modal K <= 8192)");
+        if (!h->action_out) return eps_refuse(M3_ERR_STATE, i, "no action-out destination (m3_set_action_out)");
+        const m3_episode_spec& sp = specs[i];
+        if (sp.task < M3_TASK_NAVIGATION || sp.task > M3_TASK_PUSH_PULL) return eps_refuse(M3_ERR_BAD_ARG, i, "spec: task is not a point_env task");
+        if (sp.suction < M3_SUCTION_OFF || sp.suction > M3_SUCTION_PULL_PREFERENCE) return eps_refuse(M3_ERR_BAD_ARG, i, "spec: unknown suction mode");
+        if (sp.suction == M3_SUCTION_PULL_PREFERENCE && !c.multi_modal)
+            return eps_refuse(M3_ERR_STATE, i, "spec: suction from the pull preference needs a multi-modal planner");
+        if (sp.dyn_phase < 0) return eps_refuse(M3_ERR_BAD_ARG, i, "spec: dyn_phase must be >= 0");
+    }
+    // ---- allocations: all of the set's memory, here ----
+    m3_episodes* eps = new (std::nothrow) m3_episodes();
+    if (!eps) return eps_refuse(M3_ERR_HIP, -1, "out of host memory");
+    try {
+        eps->planners.assign(planners, planners + n);
+        eps->plan.resize(n);
+        eps->live.reserve(n);
+    } catch (...) {
+        delete eps;
+        return eps_refuse(M3_ERR_HIP, -1, "out of host memory");
+    }
+    eps->world = world;
+    eps->n = n;
+    eps->max_ticks = max_ticks;
+    const size_t lane_b = align16((size_t)n * sizeof(m3::EpisodeLane));
+    const size_t st_b = align16((size_t)n * sizeof(m3_episode_status));
+    const size_t gate_b = align16((size_t)n * sizeof(int));
+    std::vector<m3::EpisodeLane> lanes(n);
+    std::vector<m3_episode_status> st0(n);
+    for (int i = 0; i < n; ++i) {
+        m3_handle* h = planners[i];
+        const m3_episode_spec& sp = specs[i];
+        m3::EpisodeLane& L = lanes[i];
+        L.task = sp.task; L.phase = sp.dyn_phase; L.suction = sp.suction;
+        L.gx = sp.goal[0]; L.gy = sp.goal[1]; L.kp = sp.kp_suction;
+        L.pref = sp.suction == M3_SUCTION_PULL_PREFERENCE
+                     ? (const int*)((const char*)h->buf[M3_BUF_INFO] + offsetof(m3_info, pull_preference)) : nullptr;
+        L.plan = eps->plan[i] = h->action_out;
+        st0[i].done_tick = -1; st0[i].success = 0; st0[i].collision_ticks = 0;
+        st0[i].final_pos[0] = st0[i].final_pos[1] = 0.0f;
+    }
+    const hipStream_t s = world->stream;
+    hipError_t e = hipMalloc((void**)&eps->dev, lane_b + st_b + gate_b);
+    if (e == hipSuccess && trace) e = hipMalloc((void**)&eps->trace, (size_t)max_ticks * n * 10 * sizeof(float));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&eps->host, (size_t)n * sizeof(m3_episode_status), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMemcpyAsync(eps->dev, lanes.data(), (size_t)n * sizeof(m3::EpisodeLane), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(eps->dev + lane_b, st0.data(), (size_t)n * sizeof(m3_episode_status), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(eps->dev + lane_b + st_b, 0, gate_b, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // (the host vectors above go out of scope)
+    if (e != hipSuccess) {
+        m3_episodes_destroy(eps);
+        return eps_refuse(M3_ERR_HIP, -1, hipGetErrorString(e));
+    }
+    std::memcpy(eps->host, st0.data(), (size_t)n * sizeof(m3_episode_status));
+    m3::EpisodeArgs& a = eps->args;
+    a.v = world->views;
+    a.world = world->sim_world;
+    a.n = n;
+    a.last_tick = max_ticks - 1;
+    a.lane = reinterpret_cast<const m3::EpisodeLane*>(eps->dev);
+    a.st = reinterpret_cast<m3_episode_status*>(eps->dev + lane_b);
+    a.gate = reinterpret_cast<int*>(eps->dev + lane_b + st_b);
+    a.trace = eps->trace;
+    *out = eps;
+    return M3_OK;
+}
+
+#define EPSK(eps, expr)                                                                  \
+    do {                                                                                 \
+        hipError_t e_ = (expr);                                                          \
+        if (e_ != hipSuccess) {                                                          \
+            (eps)->err = std::string(#expr) + ": " + hipGetErrorString(e_);              \
+            return M3_ERR_HIP;                                                           \
+        }                                                                                \
+    } while (0)
+
+static int eps_ready(m3_episodes* eps, const char* who) {
+    if (eps->tick >= eps->max_ticks) { eps->err = std::string(who) + ": all max_ticks ticks are done"; return M3_ERR_STATE; }
+    for (int i = 0; i < eps->n; ++i)
+        if (eps->planners[i]->action_out != eps->plan[i]) {
+            eps->err = std::string(who) + ": planner " + std::to_string(i) + "'s action-out destination changed since create";
+            return M3_ERR_STATE;
+        }
+    return M3_OK;
+}
+
+static int eps_status_sync(m3_episodes* eps) {
+    const hipStream_t s = eps->world->stream;
+    EPSK(eps, hipMemcpyAsync(eps->host, eps->args.st, (size_t)eps->n * sizeof(m3_episode_status), hipMemcpyDeviceToHost, s));
+    EPSK(eps, hipStreamSynchronize(s));
+    return M3_OK;
+}
+
+extern "C" int m3_episodes_begin(m3_episodes* eps) {
+    if (!eps) return M3_ERR_BAD_ARG;
+    if (eps->mid_tick) { eps->err = "m3_episodes_begin: the tick was begun already"; return M3_ERR_STATE; }
+    int rc = eps_ready(eps, "m3_episodes_begin");
+    if (rc != M3_OK) return rc;
+    m3::launch_episodes_pre(eps->args, eps->tick, eps->world->stream);
+    EPSK(eps, hipGetLastError());
+    eps->mid_tick = true;
+    return eps_status_sync(eps);
+}
+
+extern "C" int m3_episodes_end(m3_episodes* eps) {
+    if (!eps) return M3_ERR_BAD_ARG;
+    if (!eps->mid_tick) { eps->err = "m3_episodes_end: no tick begun"; return M3_ERR_STATE; }
+    int rc = eps_ready(eps, "m3_episodes_end");
+    if (rc != M3_OK) return rc;
+    m3::launch_episodes_post(eps->world->scene, eps->args, eps->tick, eps->world->stream);
+    EPSK(eps, hipGetLastError());
+    eps->mid_tick = false;
+    eps->tick += 1;
+    return eps_status_sync(eps);
+}
+
+extern "C" int m3_episodes_tick(m3_episodes* eps, m3_batch* batch) {
+    if (!eps) return M3_ERR_BAD_ARG;
+    if (!batch) { eps->err = "m3_episodes_tick: null batch"; return M3_ERR_BAD_ARG; }
+    if (eps->mid_tick) { eps->err = "m3_episodes_tick: inside m3_episodes_begin / m3_episodes_end"; return M3_ERR_STATE; }
+    int rc = eps_ready(eps, "m3_episodes_tick");
+    if (rc != M3_OK) return rc;
+    // the batch: episodes still running after the last tick's status (one that succeeds in this tick's pre kernel is
+    // commanded once more -- its plan is never recorded)
+    eps->live.clear();
+    const m3_handle* w = eps->world;
+    for (int i = 0; i < eps->n; ++i) {
+        if (eps->host[i].done_tick >= 0) continue;
+        m3_handle* h = eps->planners[i];
+        // (f) planner i reads row i of the world: the rollout takes row 0 of its bound views
+        // (rollout_point_kernel.hpp), so it sees the floats closed_loop.run copies into its K-env sim
+        rc = m3_bind_sim_point(h, w->views.dof_state + (size_t)i * 4, w->views.root_state + (size_t)i * w->views.n_actors * 13,
+                               w->views.n_actors, w->views.box_actor, w->views.dyn_actor);
+        if (rc != M3_OK) { eps->err = "m3_episodes_tick: " + h->err; return rc; }
+        eps->live.push_back(h);
+    }
+    m3::launch_episodes_pre(eps->args, eps->tick, w->stream);
+    EPSK(eps, hipGetLastError());
+    if (!eps->live.empty()) {
+        rc = m3_batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr);
+        if (rc != M3_OK) { eps->err = std::string("m3_episodes_tick: ") + m3_batch_last_error(batch); return rc; }
+    }
+    m3::launch_episodes_post(w->scene, eps->args, eps->tick, w->stream);
+    EPSK(eps, hipGetLastError());
+    eps->tick += 1;
+    return eps_status_sync(eps);
+}
+
+extern "C" int m3_episodes_ticks_done(const m3_episodes* eps) { return eps ? eps->tick : M3_ERR_BAD_ARG; }
+
+extern "C" int m3_episodes_running(const m3_episodes* eps) {
+    if (!eps) return M3_ERR_BAD_ARG;
+    int r = 0;
+    for (int i = 0; i < eps->n; ++i) r += eps->host[i].done_tick < 0;
+    return r;
+}
+
+extern "C" int m3_episodes_status(m3_episodes* eps, m3_episode_status* status_out, float* trace_out) {
+    if (!eps || !status_out) return M3_ERR_BAD_ARG;
+    const hipStream_t s = eps->world->stream;
+    EPSK(eps, hipMemcpyAsync(status_out, eps->args.st, (size_t)eps->n * sizeof(m3_episode_status), hipMemcpyDeviceToHost, s));
+    if (trace_out) {
+        if (!eps->trace) { eps->err = "m3_episodes_status: the set was created without a trace"; return M3_ERR_STATE; }
+        EPSK(eps, hipMemcpyAsync(trace_out, eps->trace, (size_t)eps->max_ticks * eps->n * 10 * sizeof(float),
+                                 hipMemcpyDeviceToHost, s));
+    }
+    EPSK(eps, hipStreamSynchronize(s));
+    return M3_OK;
+}

@@ -278,6 +278,25 @@ void launch_sim_cost(const CostParams& cp, float* world, int Kl, int k0, float* 
 void launch_sim_suction(const SimViews& v, float* world, int Kl, float kp, float thresh, float reach,
                         const float* action, int apply, float* forces, int* flags, const int* gate, hipStream_t s);
 
+// batched closed-loop episodes (m3_episodes_*): one lane per episode of an N-env point_env world
+struct EpisodeLane {          // per episode, uploaded once by m3_episodes_create
+    int task, phase, suction; // M3_TASK_*, dyn-obs phase, EP_SUCTION_* (episode_lane.hpp)
+    float gx, gy, kp;         // goal, kp_suction
+    const int* pref;          // its planner's m3_info.pull_preference (device)
+    const float* plan;        // its planner's action-out (device): row 0 is the velocity target
+};
+struct EpisodeArgs {
+    SimViews v;               // the world's views, [n] rows
+    float* world;             // the world's SoA state [NW][n]
+    int n, last_tick;         // episodes, max_ticks - 1
+    const EpisodeLane* lane;  // [n]
+    m3_episode_status* st;    // [n]
+    int* gate;                // [n] suction gate of the current tick
+    float* trace;             // [max_ticks][n][10] or null
+};
+void launch_episodes_pre(const EpisodeArgs& a, int tick, hipStream_t s);
+void launch_episodes_post(const PointScene& sc, const EpisodeArgs& a, int tick, hipStream_t s);
+
 constexpr int NW = 28;  // floats per env in the step-mode SoA world (PointWorld fields)
 constexpr int NWP = 77; // same for the panda_env (PandaWorld fields, rollout_panda.hip)
 

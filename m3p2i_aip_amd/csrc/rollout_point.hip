@@ -1,6 +1,7 @@
 // rollout_point.hip -- point_env rollout: launch dispatch, the all-modes instance of the kernel
 // (rollout_point_kernel.hpp), the noise transpose and the step-mode (IsaacGymWrapper-like) kernels.
 #include "rollout_point_kernel.hpp"
+#include "episode_lane.hpp"
 
 namespace m3 {
 
@@ -277,6 +278,107 @@ void launch_sim_suction(const SimViews& v, float* world, int Kl, float kp, float
                         const float* action, int apply, float* forces, int* flags, const int* gate, hipStream_t s) {
     hipLaunchKernelGGL(k_sim_suction, dim3((Kl + 255) / 256), dim3(256), 0, s, v, world, Kl, kp, thresh, reach,
                        action, apply, forces, flags, gate);
+}
+
+// ======================= batched closed-loop episodes (m3_episodes_*) =======================
+// One lane per episode e of an N-env world; lane e does for row e exactly what tools/closed_loop.run does for its 1-env
+// world at one tick, in the same order.  The expressions shared with k_sim_shift_pull / k_sim_suction / k_sim_step are
+// the same code or the same text in this translation unit, so they compile to the same arithmetic.
+
+// before the command: dyn-obs walk with the episode's phase, success test, suction-gate snapshot
+__global__ __launch_bounds__(64) void k_episodes_pre(const EpisodeArgs a, int tick) {
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= a.n) return;
+    const SimViews& v = a.v;
+    const EpisodeLane L = a.lane[e];
+    // update_dyn_obs(tick + phase): k_sim_shift_pull on row e, with this episode's own phase
+    const float d = ep_walk_forth(tick + L.phase) ? 0.01f : -0.01f;
+    float* r = v.root_state + ((size_t)e * v.n_actors + v.dyn_actor) * 13;
+    r[0] = r[0] + d; r[1] = r[1] + d; r[2] = r[2] + 0.0f;
+    pull_env(v, a.world, a.n, e);
+    m3_episode_status& st = a.st[e];
+    if (st.done_tick < 0) {
+        // check_task_success on the wrapper's views: robot_pos (dof_state x, y) for navigation, else the box's root x, y.
+        // A success ends the episode before its command; its metrics freeze here.
+        float px, py;
+        if (L.task == 0) {
+            px = v.dof_state[(size_t)e * 4 + 0]; py = v.dof_state[(size_t)e * 4 + 2];
+        } else {
+            const float* b = v.root_state + ((size_t)e * v.n_actors + v.box_actor) * 13;
+            px = b[0]; py = b[1];
+        }
+        if (ep_success(L.task, px, py, L.gx, L.gy)) {
+            // (d) the final error is taken on the host from these f32 positions, as closed_loop.run does with CPU torch
+            st.done_tick = tick; st.success = 1; st.final_pos[0] = px; st.final_pos[1] = py;
+        }
+    }
+    // (b) gate of this tick = the previous command's pull preference: read it before this tick's command rewrites it
+    a.gate[e] = ep_gate(L.suction, L.pref ? *L.pref : 0);
+}
+void launch_episodes_pre(const EpisodeArgs& a, int tick, hipStream_t s) {
+    hipLaunchKernelGGL(k_episodes_pre, dim3((a.n + 63) / 64), dim3(64), 0, s, a, tick);
+}
+
+// after the command: trace row, suction, step + views, collision count, the last tick's end
+// (g) not masked: an episode that is done keeps its row evolving (on its last plan); nothing of it is recorded any more
+__global__ __launch_bounds__(64) void k_episodes_post(const PointScene sc, const EpisodeArgs a, int tick) {
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= a.n) return;
+    const SimViews& v = a.v;
+    const EpisodeLane L = a.lane[e];
+    m3_episode_status& st = a.st[e];
+    const bool live = st.done_tick < 0;
+    const float* action = L.plan;            // row 0 of the plan: the velocity target of the 1-env world
+    const float ux = action[0], uy = action[1];
+    if (live && a.trace) {   // closed_loop.run(trace=True): robot x, y | box body x, y, qz, qw | dyn-obs root x, y | action
+        float* o = a.trace + ((size_t)tick * a.n + e) * 10;
+        const float* rb = v.rigid_body_state + ((size_t)e * v.n_bodies + v.box_body) * 13;
+        const float* dy = v.root_state + ((size_t)e * v.n_actors + v.dyn_actor) * 13;
+        o[0] = v.dof_state[(size_t)e * 4 + 0]; o[1] = v.dof_state[(size_t)e * 4 + 2];
+        o[2] = rb[0]; o[3] = rb[1]; o[4] = rb[5]; o[5] = rb[6];
+        o[6] = dy[0]; o[7] = dy[1];
+        o[8] = ux; o[9] = uy;
+    }
+    const int Kl = a.n;
+    float* p = a.world + e;
+    if (L.suction != EP_SUCTION_OFF) {
+        // check_and_apply_suction: k_sim_suction's action path with apply = 1, its expressions verbatim, and
+        // (b) a gate per episode instead of one scalar for all environments.
+        // (a) threshold 1.5: each episode is a 1-env "real world" (skill_utils.py: num_envs == 1), although this
+        //     world's K_local is N -- m3_sim_check_and_apply_suction on it would pick 1.8.
+        const float thresh = 1.5f, reach = 0.6f, kp = L.kp;
+        const bool enabled = a.gate[e] != 0;
+        const float ex = p[4 * Kl] - p[0 * Kl], ey = p[5 * Kl] - p[1 * Kl];   // robot -> box
+        const float len = sqrtf(ex * ex + ey * ey);
+        const float inv = 1.0f / len;
+        float fx = 0.0f, fy = 0.0f;                                          // force on the robot
+        if (inv > thresh) {
+            fx = clamp500(kp * (ex * inv));
+            fy = clamp500(kp * (ey * inv));
+        }
+        const float along = action[0] * (-ex) + action[1] * (-ey);   // action . (robot - box)
+        const bool pulling = enabled && len < reach && along > 0.0f;
+        if (pulling) {
+            p[18 * Kl] = fx; p[19 * Kl] = fy; p[20 * Kl] = -fx; p[21 * Kl] = -fy;
+        }
+    }
+    // step(): k_sim_step's body on row e (set_dof_velocity_target_tensor(action) in front of it)
+    PointWorld w;
+    soa_load(a.world, Kl, e, w);
+    point_step<true>(sc, w, ux, uy);
+    soa_store(a.world, Kl, e, w);
+    push_views(v, e, w);
+    if (!live) return;
+    // (c) the dyn-obs contact force of the views after the step, as closed_loop.run reads it
+    if (ep_collision(w.fcDx, w.fcDy)) st.collision_ticks += 1;
+    if (tick == a.last_tick) {   // out of ticks: the episode ends unsuccessful with the state after this step
+        st.done_tick = tick; st.success = 0;
+        st.final_pos[0] = L.task == 0 ? w.rx : w.B.x;
+        st.final_pos[1] = L.task == 0 ? w.ry : w.B.y;
+    }
+}
+void launch_episodes_post(const PointScene& sc, const EpisodeArgs& a, int tick, hipStream_t s) {
+    hipLaunchKernelGGL(k_episodes_post, dim3((a.n + 63) / 64), dim3(64), 0, s, sc, a, tick);
 }
 
 }  // namespace m3

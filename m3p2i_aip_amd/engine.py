@@ -565,3 +565,74 @@ class HipBatch:
         r, u = C.c_int(), C.c_int()
         self._ck(self.lib.m3_batch_launches(self._b, C.byref(r), C.byref(u)))
         return r.value, u.value
+
+
+class HipEpisodes:
+    """N closed-loop point_env episodes in lockstep (``m3_episodes_*``, include/m3p2i_hip.h): row e of the
+    N-env world engine (an ``IsaacGymWrapper(num_envs=N)``'s) is episode e's 1-env world, planned by ``engines[e]``.
+    ``specs``: one ``(task, goal, dyn_phase, suction, kp_suction)`` per episode, task a name or M3_TASK_* id, suction one of
+    ``L.SUCTION_*``.  Each engine's ``set_action_out`` tensor is read here and must stay the same.  The set owns its
+    device state and pinned status words; a tick allocates nothing."""
+
+    def __init__(self, world, engines, specs, max_ticks, trace=False):
+        self.lib = L.load()
+        self.world, self.engines = world, list(engines)
+        self.n, self.max_ticks, self.trace_on = len(self.engines), int(max_ticks), bool(trace)
+        arr = (C.c_void_p * max(self.n, 1))(*[e._h.value for e in self.engines])
+        sp = (L.EpisodeSpec * max(self.n, 1))()
+        for i, (task, goal, phase, suction, kp) in enumerate(specs):
+            sp[i].task = L.TASKS[task] if isinstance(task, str) else int(task)
+            sp[i].goal[0], sp[i].goal[1] = float(goal[0]), float(goal[1])
+            sp[i].dyn_phase, sp[i].suction, sp[i].kp_suction = int(phase), int(suction), float(kp)
+        self._eps = C.c_void_p()
+        rc = self.lib.m3_episodes_create(world._h, arr, sp, self.n, self.max_ticks, int(self.trace_on), C.byref(self._eps))
+        if rc != 0:
+            msg = self.lib.m3_episodes_last_error(None)
+            raise L.M3Error(f"m3p2i_hip error {rc}: {msg.decode() if msg else ''}")
+        self._status = (L.EpisodeStatus * self.n)()
+
+    def close(self):
+        if getattr(self, "_eps", None) is not None and self._eps:
+            self.lib.m3_episodes_destroy(self._eps)
+            self._eps = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc != 0:
+            msg = self.lib.m3_episodes_last_error(self._eps)
+            raise L.M3Error(f"m3p2i_hip error {rc}: {msg.decode() if msg else ''}")
+
+    def tick(self, batch):
+        """One tick of every episode: pre kernel, one batched command of the running episodes' planners, post kernel,
+        one synchronisation."""
+        self._ck(self.lib.m3_episodes_tick(self._eps, batch._b))
+
+    def begin(self):
+        """The pre-command half of a tick whose commands the caller issues itself (a planner's first command)."""
+        self._ck(self.lib.m3_episodes_begin(self._eps))
+
+    def end(self):
+        self._ck(self.lib.m3_episodes_end(self._eps))
+
+    @property
+    def running(self):
+        """Episodes not ended as of the last tick (host copy, no synchronisation)."""
+        return int(self.lib.m3_episodes_running(self._eps))
+
+    @property
+    def ticks_done(self):
+        return int(self.lib.m3_episodes_ticks_done(self._eps))
+
+    def status(self, with_trace=False):
+        """[dict(done_tick, success, collision_ticks, final_pos)] per episode, and with_trace the trace as a
+        [max_ticks, n, 10] float32 array."""
+        tr = np.empty((self.max_ticks, self.n, 10), np.float32) if with_trace else None
+        self._ck(self.lib.m3_episodes_status(self._eps, self._status, tr.ctypes.data if tr is not None else None))
+        st = [dict(done_tick=s.done_tick, success=bool(s.success), collision_ticks=s.collision_ticks,
+                   final_pos=(s.final_pos[0], s.final_pos[1])) for s in self._status]
+        return (st, tr) if with_trace else st

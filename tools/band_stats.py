@@ -2,7 +2,10 @@
 (deterministic seeds): statistics of what the reference logged per run (plot/plot_point.py:26-34) -- final
 block-to-goal error, task time, dyn-obs collisions -- next to the logged statistics (tests/golden/behaviour_band.json).
 
-    python tools/band_stats.py [--n 20] [--json out.json] [--size baseline|default] [--avoid] [scenario ...]
+    python tools/band_stats.py [--n 20] [--json out.json] [--size baseline|default] [--avoid] [--batched] [scenario ...]
+
+--batched: all episodes of all named scenarios in lockstep, one library call per tick (m3p2i_aip_amd/episodes.py,
+DESIGN.md §7c): the same per-episode results as the serial runs, bit for bit.
 
 --size default: the reference's shipped planner size, K=200 samples, T=15 (config/mppi/point.yaml) -- the size the
 logged runs were most plausibly made with (it is not recorded); baseline (default here): K, T of the BASELINE configs.
@@ -14,6 +17,7 @@ its 100-tick period) and +-5 cm on the start positions of box and robot.
 tests/test_behaviour_band_gpu.py asserts on the output of `episodes()`.
 """
 import json
+import math
 import os
 import sys
 
@@ -64,6 +68,16 @@ def jitter_of(scenario, episode):
     return j
 
 
+def fisher_one_sided(a, b, c, d, alternative="less"):
+    """One-sided Fisher exact test of the 2x2 table [[a, b], [c, d]] (rows: this build, the logged runs; columns: event,
+    no event): the probability, with all margins fixed, of a top-left count <= a ("less") or >= a ("greater")."""
+    r1, c1, n = a + b, a + c, a + b + c + d
+    lo, hi = max(0, r1 + c1 - n), min(r1, c1)
+    tot = math.comb(n, r1)
+    xs = range(lo, a + 1) if alternative == "less" else range(a, hi + 1)
+    return sum(math.comb(c1, x) * math.comb(n - c1, r1 - x) for x in xs) / tot
+
+
 def stats(x):
     x = np.asarray(x, np.float64)
     return {"mean": float(x.mean()), "std": float(x.std()), "min": float(x.min()), "max": float(x.max()), "n": int(x.size)}
@@ -99,6 +113,39 @@ def episodes(scenario, n=20, max_sim_time_s=40.0, size="baseline"):
                 command_ms_p50=stats([r["command_ms_p50"] for r in runs]), runs=runs)
 
 
+def _summary(scenario, n, size, runs):
+    ok = [r for r in runs if r["success"]]
+    return dict(scenario=scenario, n=n, size=size, overrides=overrides(scenario, size), successes=len(ok),
+                final_pos_error_m=stats([r["final_pos_error_m"] for r in ok]) if ok else None,
+                task_time_s=stats([r["task_time_s"] for r in ok]) if ok else None,
+                dyn_obs_collided_episodes=int(sum(r["dyn_obs_collision_ticks"] > 0 for r in runs)),
+                dyn_obs_collision_ticks=stats([r["dyn_obs_collision_ticks"] for r in runs]),
+                command_ms_p50=stats([r["command_ms_p50"] for r in runs]), runs=runs)
+
+
+def band_batched(pairs, n=20, max_sim_time_s=40.0):
+    """episodes() of every (scenario, size) in `pairs` at once: all n * len(pairs) episodes in lockstep
+    (m3p2i_aip_amd.episodes.run_point_episodes).  Returns {(scenario, size): the dict episodes() returns}; each run's
+    command_ms_p50 is the set's tick time."""
+    from m3p2i_aip_amd.episodes import run_point_episodes
+    items = [(sc, size, e, jitter_of(sc, e)) for sc, size in pairs for e in range(n)]
+    reps = run_point_episodes([("config_point", overrides(sc, size), j) for sc, size, _, j in items],
+                              max_ticks=int(max_sim_time_s / 0.05))
+    out = {}
+    for (sc, size, e, j), r in zip(items, reps):
+        out.setdefault((sc, size), []).append(dict(episode=e, jitter=j, success=r["success"], final_pos_error_m=r["final_pos_error"],
+                                                   task_time_s=r["sim_time_s"], dyn_obs_collision_ticks=r["dyn_obs_collision_ticks"],
+                                                   command_ms_p50=r["tick_ms_p50"]))
+    return {k: _summary(k[0], n, k[1], runs) for k, runs in out.items()}
+
+
+def episodes_batched(scenario, n=20, max_sim_time_s=40.0, size="baseline"):
+    """episodes() with the n episodes in lockstep: the same dict, the same per-episode results (SETTLE_TICKS = 0)."""
+    if SETTLE_TICKS:
+        raise ValueError("episodes_batched: the batched runner takes the final error at the success tick (SETTLE_TICKS = 0)")
+    return band_batched([(scenario, size)], n, max_sim_time_s)[(scenario, size)]
+
+
 def panda_episodes(n=20, overrides=("mppi.num_samples=4000", "mppi.horizon=20"), ticks=600):
     """Panda reactive pick-and-place (config_panda), cubeA's start jittered by +-2 cm (episode 0: the reference scene)."""
     import closed_loop
@@ -116,10 +163,12 @@ def panda_episodes(n=20, overrides=("mppi.num_samples=4000", "mppi.horizon=20"),
 
 
 def main(argv):
-    n, out, names, size = 20, None, [], "baseline"
+    n, out, names, size, batched = 20, None, [], "baseline", False
     it = iter(argv)
     for a in it:
-        if a == "--n":
+        if a == "--batched":
+            batched = True
+        elif a == "--n":
             n = int(next(it))
         elif a == "--json":
             out = next(it)
@@ -150,8 +199,9 @@ def main(argv):
             if out:
                 json.dump(res, open(out, "w"), indent=1)
             return
+    pre = band_batched([(sc, size) for sc in names or list(SCENARIOS)], n) if batched else {}
     for sc in names or list(SCENARIOS):
-        r = episodes(sc, n, size=size)
+        r = pre[(sc, size)] if batched else episodes(sc, n, size=size)
         r["logged"] = {k: band[sc][k] for k in ("final_pos_error_m", "task_time_s", "dyn_obs_collisions")}
         res[sc] = r
         lg = r["logged"]
