@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <tuple>
 #include <vector>
 #include <new>
 
@@ -16,11 +17,13 @@ using namespace m3;
 
 static thread_local std::string g_create_err;
 
-#define HIPCHK(h, expr)                                                                  \
+// on a HIP error: "<expr>: <error>" into (o)->err -- the error string of a handle, a batch (m3_batch) or an episode set
+// (m3_episodes) -- and return M3_ERR_HIP
+#define HIPCHK(o, expr)                                                                  \
     do {                                                                                 \
         hipError_t e_ = (expr);                                                          \
         if (e_ != hipSuccess) {                                                          \
-            (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                \
+            (o)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                \
             return M3_ERR_HIP;                                                           \
         }                                                                                \
     } while (0)
@@ -871,7 +874,7 @@ extern "C" int m3_bind_sim_panda(m3_handle* h, const float* dof, const float* ro
 // 842: 0.784 / 0.450, 60 ticks 993: 1.530 / 0.831 -- the forms cross near 240; the eight-lane form's own count runs ~10 % higher,
 // its shadow slots included)
 
-// the conditions under which m3_rollout refuses (M3_ERR_STATE; nullptr: none) -- m3_batch_command checks them too
+// the conditions under which m3_rollout refuses (M3_ERR_STATE; nullptr: none) -- batch_refusal checks them too
 static const char* rollout_refusal(const m3_handle* h) {
     const m3_config& c = h->cfg;
     if (c.sim_only) return "m3_rollout: handle was created sim_only";
@@ -929,11 +932,10 @@ static int prepare_rollout(m3_handle* h, RolloutArgs& a) {
     a.cost_h = (float*)h->buf[M3_BUF_COST_HORIZON];
     a.J = (float*)h->buf[M3_BUF_TRAJ_COST];
     a.wave_min = h->wave_min;   // (null unless the handle's update is the three-launch one)
-    h->wave_min_rows = 0;
     return M3_OK;
 }
 
-// the panda part of a rollout's arguments (m3_rollout, m3_batch_command): world, objective, quirk Q8's shadow slots, the
+// the panda part of a rollout's arguments (plan_rollout): world, objective, quirk Q8's shadow slots, the
 // record buffer of k_panda_reach_cost, and the handle's reading of its last busy report (hysteresis: updates h->panda_reach_busy)
 static void fill_panda_args(m3_handle* h, const RolloutArgs& a, PandaArgs& pa) {
     std::memcpy(pa.world0, h->pworld0, sizeof(pa.world0));
@@ -962,26 +964,44 @@ static void fill_panda_args(m3_handle* h, const RolloutArgs& a, PandaArgs& pa) {
     }
 }
 
-extern "C" int m3_rollout(m3_handle* h) {
-    if (!h) return M3_ERR_BAD_ARG;
-    const m3_config& c = h->cfg;
-    if (const char* why = rollout_refusal(h)) return fail(h, M3_ERR_STATE, why);
-    RolloutArgs a;
+// a handle's rollout, as m3_rollout launches it and m3_batch_command groups it: the arguments (prepare_rollout), for panda_env
+// the panda part (fill_panda_args), and the form (p; a and pa become what the kernels receive).  Keeps the handle's record of
+// what the launch leaves: the rows of minima (wave_min_rows), the panda form (panda_lps_used)
+static int plan_rollout(m3_handle* h, RolloutArgs& a, PandaArgs& pa, RolloutPlan& p) {
     const int rc = prepare_rollout(h, a);
     if (rc != M3_OK) return rc;
-    if (h->timing) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    if (c.env_type == M3_ENV_POINT) {
-        if (launch_rollout_point(a, h->scene, h->stream)) h->wave_min_rows = (a.Kl + a.lanes - 1) / a.lanes;
+    if (h->cfg.env_type == M3_ENV_POINT) {
+        p = plan_rollout_point(a, h->scene);
     } else {
-        PandaArgs pa;
         fill_panda_args(h, a, pa);
-        const int wgs = launch_rollout_panda(a, pa, h->pscene, h->stream, &h->panda_lps_used);
-        if (a.wave_min) h->wave_min_rows = wgs;
+        p = plan_rollout_panda(a, pa);
+        h->panda_lps_used = p.lps;
     }
+    a.lanes = p.lanes;
+    h->wave_min_rows = p.rows;
+    return M3_OK;
+}
+
+extern "C" int m3_rollout(m3_handle* h) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (const char* why = rollout_refusal(h)) return fail(h, M3_ERR_STATE, why);
+    RolloutArgs a;
+    PandaArgs pa;
+    RolloutPlan p;
+    const int rc = plan_rollout(h, a, pa, p);
+    if (rc != M3_OK) return rc;
+    if (h->timing) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+    if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, p, h->stream);
+    else launch_rollout_panda(a, pa, h->pscene, p, h->stream);
     HIPCHK(h, hipGetLastError());
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     return M3_OK;
 }
+
+// where a command leaves its plan: the caller's destination (m3_set_action_out) or M3_BUF_ACTION_OUT
+static float* plan_dst(const m3_handle* h) { return h->action_out ? h->action_out : (float*)h->buf[M3_BUF_ACTION_OUT]; }
+// floats of that plan: [u_per_command][nu] in simple mode, else [T][nu]
+static size_t plan_floats(const m3_config& c) { return (size_t)(c.mode_simple ? c.u_per_command : c.T) * c.nu; }
 
 static void fill_update_args(m3_handle* h, UpdateArgs& a) {
     const m3_config& c = h->cfg;
@@ -1019,7 +1039,7 @@ static void fill_update_args(m3_handle* h, UpdateArgs& a) {
     a.best = (float*)h->buf[M3_BUF_BEST];
     a.best1 = (float*)h->buf[M3_BUF_BEST_1];
     a.best2 = (float*)h->buf[M3_BUF_BEST_2];
-    a.action_out = h->action_out ? h->action_out : (float*)h->buf[M3_BUF_ACTION_OUT];
+    a.action_out = plan_dst(h);
     a.top_trajs = (float*)h->buf[M3_BUF_TOP_TRAJS];
     a.top_dst = (c.K_local == c.K_global) ? a.top_trajs : a.reduce + reduce_off_top(c.T, c.nu);
     a.kbase = 0;
@@ -1056,14 +1076,20 @@ static bool can_fuse_finalize(const m3_handle* h) {
     return c.K_local == c.K_global && (long long)c.T * c.nu <= 2048;  // plan staged in 8 KB of LDS
 }
 
+// the arguments update_impl launches with (fuse: m3_command's update, the finalize fused in -- also what m3_batch_command
+// launches for every handle and batch_refusal checks)
+static void fill_update_impl_args(m3_handle* h, UpdateArgs& a, bool fuse) {
+    fill_update_args(h, a);
+    a.fuse_finalize = fuse ? 1 : 0;
+    if (h->cfg.K_local == h->cfg.K_global)  // unsharded: the local costs ARE the global costs (no copy)
+        a.Jall = (const float*)h->buf[M3_BUF_TRAJ_COST];
+}
+
 static int update_impl(m3_handle* h, bool fuse) {
     const m3_config& c = h->cfg;
     if (c.sim_only) return fail(h, M3_ERR_STATE, "m3_update: handle was created sim_only");
     UpdateArgs a;
-    fill_update_args(h, a);
-    a.fuse_finalize = fuse ? 1 : 0;
-    if (c.K_local == c.K_global)  // unsharded: the local costs ARE the global costs (no copy)
-        a.Jall = (const float*)h->buf[M3_BUF_TRAJ_COST];
+    fill_update_impl_args(h, a, fuse);
     if (h->regen) {
         // one-collective multi-modal sharding, phase before the all-gather: the rollout left the shard's
         // costs at the head of the record; add the shard's own top-k (costs, global indices, trajectories)
@@ -1227,6 +1253,16 @@ static int after_finalize(m3_handle* h) {
                       (const float*)h->buf[M3_BUF_MEAN], h->wpart, (float*)h->buf[M3_BUF_COV], c.K_local, c.T, c.nu,
                       h->stream);
     HIPCHK(h, hipGetLastError());
+    return M3_OK;
+}
+
+// the end of a command whose finalize has been enqueued (m3_finalize, m3_update_finalize, m3_batch_command): the covariance
+// step, the end-of-command timing event (timed: not in a batch), the call count
+static int finish_command(m3_handle* h, bool timed) {
+    const int rc = after_finalize(h);
+    if (rc != M3_OK) return rc;
+    if (timed && h->timing) HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
+    h->calls += 1;
     return M3_OK;
 }
 
@@ -1480,11 +1516,7 @@ extern "C" int m3_finalize(m3_handle* h) {
     if (mix_mode(h)) launch_mix(a, h->stream);  // records -> the REDUCE buffer an all-reduce would hold, + finalize
     else launch_finalize(a, h->stream);
     HIPCHK(h, hipGetLastError());
-    const int rc = after_finalize(h);
-    if (rc != M3_OK) return rc;
-    if (h->timing) HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
-    h->calls += 1;
-    return M3_OK;
+    return finish_command(h, true);
 }
 
 extern "C" int m3_update_finalize(m3_handle* h) {
@@ -1495,12 +1527,8 @@ extern "C" int m3_update_finalize(m3_handle* h) {
         const int rc = m3_update(h);
         return rc != M3_OK ? rc : m3_finalize(h);
     }
-    int rc = update_impl(h, true);
-    if (rc == M3_OK) rc = after_finalize(h);
-    if (rc != M3_OK) return rc;
-    if (h->timing) HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
-    h->calls += 1;
-    return M3_OK;
+    const int rc = update_impl(h, true);
+    return rc != M3_OK ? rc : finish_command(h, true);
 }
 
 extern "C" int m3_command(m3_handle* h, float* action_host) {
@@ -1517,9 +1545,7 @@ extern "C" int m3_command(m3_handle* h, float* action_host) {
     h->use_wave_min = false;
     if (rc != M3_OK) return rc;
     if (action_host) {
-        const m3_config& c = h->cfg;
-        const int rows = c.mode_simple ? c.u_per_command : c.T;
-        HIPCHK(h, hipMemcpyAsync(action_host, h->action_out ? h->action_out : (float*)h->buf[M3_BUF_ACTION_OUT], (size_t)rows * c.nu * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(action_host, plan_dst(h), plan_floats(h->cfg) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     return M3_OK;
@@ -1538,39 +1564,26 @@ constexpr int BATCH_SLOTS = 4;
 
 namespace {
 struct BatchKey {
-    int instance, ref, K, T, lanes;   // rollout: rollout_point_instance, reference scene compiled in, sizes (panda: 0, 0,
-                                      // K, T, the plan's lanes per wavefront)
-    int lps, forces, general, shadows, rec;   // panda_env: the plan's form (PandaRolloutPlan; point_env: all 0)
-    SmallUpdateInstance upd;          // update: k_update_small's template arguments, width, top-k workgroups
+    RolloutPlan roll;          // rollout: the handle's plan (plan_rollout) ...
+    int K, T;                  // ... and sizes
+    SmallUpdateInstance upd;   // update: k_update_small's template arguments, width, top-k workgroups
 };
-bool same_rollout(const BatchKey& x, const BatchKey& y) {
-    return x.instance == y.instance && x.ref == y.ref && x.K == y.K && x.T == y.T && x.lanes == y.lanes && x.lps == y.lps &&
-           x.forces == y.forces && x.general == y.general && x.shadows == y.shadows && x.rec == y.rec;
+// the fields a group shares, in the order the groups are sorted by
+auto rollout_fields(const BatchKey& k) {
+    const RolloutPlan& p = k.roll;
+    return std::tie(p.instance, p.ref, p.lps, p.forces, p.general, p.shadows, p.rec, k.K, k.T, p.lanes);
 }
-bool less_rollout(const BatchKey& x, const BatchKey& y) {
-    if (x.instance != y.instance) return x.instance < y.instance;
-    if (x.ref != y.ref) return x.ref < y.ref;
-    if (x.lps != y.lps) return x.lps < y.lps;
-    if (x.forces != y.forces) return x.forces < y.forces;
-    if (x.general != y.general) return x.general < y.general;
-    if (x.shadows != y.shadows) return x.shadows < y.shadows;
-    if (x.rec != y.rec) return x.rec < y.rec;
-    if (x.K != y.K) return x.K < y.K;
-    if (x.T != y.T) return x.T < y.T;
-    return x.lanes < y.lanes;
-}
-bool same_update(const BatchKey& x, const BatchKey& y) {
-    return x.upd.nu == y.upd.nu && x.upd.multi == y.upd.multi && x.upd.jr == y.upd.jr && x.upd.wt == y.upd.wt &&
-           x.upd.n_cand == y.upd.n_cand && x.T == y.T;
-}
-bool less_update(const BatchKey& x, const BatchKey& y) {
-    if (x.upd.nu != y.upd.nu) return x.upd.nu < y.upd.nu;
-    if (x.upd.multi != y.upd.multi) return x.upd.multi < y.upd.multi;
-    if (x.upd.jr != y.upd.jr) return x.upd.jr < y.upd.jr;
-    if (x.upd.wt != y.upd.wt) return x.upd.wt < y.upd.wt;
-    if (x.upd.n_cand != y.upd.n_cand) return x.upd.n_cand < y.upd.n_cand;
-    return x.T < y.T;
-}
+auto update_fields(const BatchKey& k) { return std::tie(k.upd.nu, k.upd.multi, k.upd.jr, k.upd.wt, k.upd.n_cand, k.T); }
+bool same_rollout(const BatchKey& x, const BatchKey& y) { return rollout_fields(x) == rollout_fields(y); }
+bool less_rollout(const BatchKey& x, const BatchKey& y) { return rollout_fields(x) < rollout_fields(y); }
+bool same_update(const BatchKey& x, const BatchKey& y) { return update_fields(x) == update_fields(y); }
+bool less_update(const BatchKey& x, const BatchKey& y) { return update_fields(x) < update_fields(y); }
+struct BatchHandle {   // one handle's command as planned, in call order (copied into the table by group)
+    RolloutArgs a;
+    PandaArgs pa;      // (panda_env only)
+    UpdateArgs u;
+    BatchKey key;
+};
 size_t align16(size_t n) { return (n + 15) / 16 * 16; }
 }  // namespace
 
@@ -1587,20 +1600,9 @@ struct m3_batch {
     int rollout_launches = 0, update_launches = 0;   // of the last successful m3_batch_command
     // host scratch, sized by m3_batch_create
     std::vector<m3_handle*> seen;
-    std::vector<BatchKey> key;
+    std::vector<BatchHandle> hd;
     std::vector<int> by_roll, by_upd;
-    std::vector<BatchPandaEntry> pent;      // panda_env: the rollout entries in call order (copied into the slot by group)
-    std::vector<PandaRolloutPlan> plan;
 };
-
-#define BATCHK(b, expr)                                                                  \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess) {                                                          \
-            (b)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                \
-            return M3_ERR_HIP;                                                           \
-        }                                                                                \
-    } while (0)
 
 extern "C" const char* m3_batch_last_error(const m3_batch* b) { return b ? b->err.c_str() : g_batch_err.c_str(); }
 
@@ -1638,11 +1640,9 @@ extern "C" int m3_batch_create(int device, int max_handles, m3_batch** out) {
     b->slot_bytes = b->upd_off + (size_t)max_handles * sizeof(UpdateArgs);
     try {
         b->seen.resize(max_handles);
-        b->key.resize(max_handles);
+        b->hd.resize(max_handles);
         b->by_roll.resize(max_handles);
         b->by_upd.resize(max_handles);
-        b->pent.resize(max_handles);
-        b->plan.resize(max_handles);
     } catch (...) {
         delete b;
         g_batch_err = "m3_batch_create: out of host memory";
@@ -1673,6 +1673,24 @@ extern "C" int m3_batch_launches(const m3_batch* b, int* rollout_launches, int* 
     return M3_OK;
 }
 
+// the conditions under which m3_batch_command refuses a handle of the call's environment, device and stream (nullptr: none;
+// code: the return code) -- m3_episodes_create checks them too.  u: the arguments of the handle's update, as m3_command
+// launches it
+static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code) {
+    const m3_config& c = h->cfg;
+    code = M3_ERR_STATE;
+    if (c.K_local != c.K_global) return "sharded handle (K_local != K_global)";
+    if (c.sim_only) return "handle was created sim_only";
+    if (const char* why = rollout_refusal(h)) return why;
+    fill_update_impl_args(h, u, true);
+    code = M3_ERR_UNSUPPORTED;
+    if (!can_fuse_finalize(h) || !update_small_applies(u))
+        return c.env_type == M3_ENV_PANDA
+                   ? "its command does not take the one-launch update (nu = 9: K <= 4096, T * nu <= 2048)"
+                   : "its command does not take the one-launch update (nu = 2: K <= 16384; multi-modal K <= 8192)";
+    return nullptr;
+}
+
 static int batch_refuse(m3_batch* b, int code, int i, const char* msg) {
     char head[64];
     if (i >= 0) std::snprintf(head, sizeof(head), "m3_batch_command: handle %d: ", i);
@@ -1699,72 +1717,38 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
     }
     const hipStream_t s = hs[0]->stream;
     const bool panda = hs[0]->cfg.env_type == M3_ENV_PANDA;   // one environment per call: handle 0's
+    BatchHandle* hd = b->hd.data();
     for (int i = 0; i < n; ++i) {
         m3_handle* h = hs[i];
-        const m3_config& c = h->cfg;
-        if (c.env_type != hs[0]->cfg.env_type)
+        if (h->cfg.env_type != hs[0]->cfg.env_type)
             return batch_refuse(b, M3_ERR_UNSUPPORTED, i, panda ? "point_env handle in a batch of panda_env handles (one environment per call)"
                                                                 : "panda_env handle in a batch of point_env handles (one environment per call)");
-        if (c.K_local != c.K_global) return batch_refuse(b, M3_ERR_STATE, i, "sharded handle (K_local != K_global)");
-        if (c.sim_only) return batch_refuse(b, M3_ERR_STATE, i, "handle was created sim_only");
         if (h->stream != s) return batch_refuse(b, M3_ERR_STATE, i, "its stream differs from handle 0's");
-        if (const char* why = rollout_refusal(h)) return batch_refuse(b, M3_ERR_STATE, i, why);
-        UpdateArgs ua;   // (what m3_command's update would be handed: update_impl with the finalize fused in)
-        fill_update_args(h, ua);
-        ua.fuse_finalize = 1;
-        ua.Jall = (const float*)h->buf[M3_BUF_TRAJ_COST];
-        if (!can_fuse_finalize(h) || !update_small_applies(ua))
-            return batch_refuse(b, M3_ERR_UNSUPPORTED, i, panda ? "its command does not take the one-launch update (nu = 9: "
-                                                                  "K <= 4096, T * nu <= 2048)"
-                                                                : "its command does not take the one-launch update (nu = 2: K <= "
-                                                                  "16384; multi-modal K <= 8192)");
-        BatchKey& k = b->key[i];
-        k.upd = update_small_instance(ua);
+        int code;
+        if (const char* why = batch_refusal(h, hd[i].u, code)) return batch_refuse(b, code, i, why);
+        BatchKey& k = hd[i].key;
+        k.upd = update_small_instance(hd[i].u);
+        hd[i].u.n_cand = k.upd.n_cand;   // (what launch_update_small hands its instance)
+        k.K = h->cfg.K_local; k.T = h->cfg.T;
         b->by_roll[i] = b->by_upd[i] = i;
-        if (panda) continue;   // (the rollout's form is planned below, after every check)
-        RolloutArgs ka;   // (the fields the rollout's instance depends on, as prepare_rollout sets them)
-        std::memset(&ka, 0, sizeof(ka));
-        ka.multi_modal = c.multi_modal; ka.mode_simple = c.mode_simple; ka.sampling_random = c.sampling_random;
-        ka.scale_dev = h->cov_active ? (const float*)h->buf[M3_BUF_COV] + c.nu : nullptr;
-        fill_cost_params(h, ka.cp);
-        k.instance = rollout_point_instance(ka);
-        k.ref = point_scene_is_reference(h->scene) ? 1 : 0;
-        k.K = c.K_local; k.T = c.T;
-        k.lanes = h->lanes_override > 0 ? h->lanes_override : rollout_lanes_for(c.K_local);
-        k.lps = k.forces = k.general = k.shadows = k.rec = 0;
     }
-    // ---- panda_env: each handle's rollout form, as m3_rollout would choose it (its own busy report and hysteresis) ----
-    if (panda) {
-        for (int i = 0; i < n; ++i) {
-            m3_handle* h = hs[i];
-            BatchPandaEntry& e = b->pent[i];
-            const int rc = prepare_rollout(h, e.a);
-            if (rc != M3_OK) { b->err = "m3_batch_command: " + h->err; return rc; }
-            fill_panda_args(h, e.a, e.pa);
-            const PandaRolloutPlan pl = plan_rollout_panda(e.a, e.pa);
-            e.a.lanes = pl.lanes;
-            e.sc = h->pscene;
-            b->plan[i] = pl;
-            h->panda_lps_used = pl.lps;
-            if (e.a.wave_min) h->wave_min_rows = pl.rows;
-            BatchKey& k = b->key[i];
-            k.instance = k.ref = 0;
-            k.K = h->cfg.K_local; k.T = h->cfg.T; k.lanes = pl.lanes;
-            k.lps = pl.lps; k.forces = pl.forces; k.general = pl.general; k.shadows = e.pa.shadows; k.rec = pl.rec;
-        }
+    // ---- each handle's rollout, as m3_rollout plans it, in call order (+ its wave-order refresh when it is due: its own
+    // launch on the stream, ahead of the batched rollout) ----
+    for (int i = 0; i < n; ++i) {
+        const int rc = plan_rollout(hs[i], hd[i].a, hd[i].pa, hd[i].key.roll);
+        if (rc != M3_OK) { b->err = "m3_batch_command: " + hs[i]->err; return rc; }
     }
     // ---- groups: handles in key order (ties in call order) ----
-    const BatchKey* key = b->key.data();
-    std::sort(b->by_roll.begin(), b->by_roll.begin() + n, [key](int x, int y) {
-        return less_rollout(key[x], key[y]) || (!less_rollout(key[y], key[x]) && x < y);
+    std::sort(b->by_roll.begin(), b->by_roll.begin() + n, [hd](int x, int y) {
+        return less_rollout(hd[x].key, hd[y].key) || (!less_rollout(hd[y].key, hd[x].key) && x < y);
     });
-    std::sort(b->by_upd.begin(), b->by_upd.begin() + n, [key](int x, int y) {
-        return less_update(key[x], key[y]) || (!less_update(key[y], key[x]) && x < y);
+    std::sort(b->by_upd.begin(), b->by_upd.begin() + n, [hd](int x, int y) {
+        return less_update(hd[x].key, hd[y].key) || (!less_update(hd[y].key, hd[x].key) && x < y);
     });
     // ---- the argument table: a free ring slot, filled on the host, ONE copy ----
     const int slot = b->next;
     if (b->in_flight[slot]) {
-        BATCHK(b, hipEventSynchronize(b->done[slot]));
+        HIPCHK(b, hipEventSynchronize(b->done[slot]));
         b->in_flight[slot] = false;
     }
     BatchRolloutEntry* hr = reinterpret_cast<BatchRolloutEntry*>(b->host[slot]);
@@ -1772,53 +1756,34 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
     const size_t upd_off = align16((size_t)n * (panda ? sizeof(BatchPandaEntry) : sizeof(BatchRolloutEntry)));
     UpdateArgs* hu = reinterpret_cast<UpdateArgs*>(b->host[slot] + upd_off);
     for (int p = 0; p < n; ++p) {
-        if (panda) {
-            hp[p] = b->pent[b->by_roll[p]];
-            continue;
-        }
-        m3_handle* h = hs[b->by_roll[p]];
-        const int rc = prepare_rollout(h, hr[p].a);   // (+ the handle's wave-order refresh when it is due: its own launch)
-        if (rc != M3_OK) { b->err = "m3_batch_command: " + h->err; return rc; }
-        hr[p].sc = h->scene;
+        const int i = b->by_roll[p];
+        if (panda) { hp[p].a = hd[i].a; hp[p].pa = hd[i].pa; hp[p].sc = hs[i]->pscene; }
+        else { hr[p].a = hd[i].a; hr[p].sc = hs[i]->scene; }
     }
-    for (int p = 0; p < n; ++p) {
-        const int i = b->by_upd[p];
-        m3_handle* h = hs[i];
-        fill_update_args(h, hu[p]);
-        hu[p].fuse_finalize = 1;
-        hu[p].Jall = (const float*)h->buf[M3_BUF_TRAJ_COST];
-        hu[p].n_cand = key[i].upd.n_cand;   // (what launch_update_small hands its instance)
-    }
+    for (int p = 0; p < n; ++p) hu[p] = hd[b->by_upd[p]].u;
     char* dslot = b->dev[slot];
-    BATCHK(b, hipMemcpyAsync(dslot, b->host[slot], upd_off + (size_t)n * sizeof(UpdateArgs), hipMemcpyHostToDevice, s));
+    HIPCHK(b, hipMemcpyAsync(dslot, b->host[slot], upd_off + (size_t)n * sizeof(UpdateArgs), hipMemcpyHostToDevice, s));
     const BatchRolloutEntry* dr = reinterpret_cast<const BatchRolloutEntry*>(dslot);
     const BatchPandaEntry* dp = reinterpret_cast<const BatchPandaEntry*>(dslot);
     const UpdateArgs* du = reinterpret_cast<const UpdateArgs*>(dslot + upd_off);
-    // ---- one rollout launch per group ----
+    // ---- one rollout launch per group (panda_env: + one k_panda_reach_cost launch when the group keeps the record buffer,
+    // not counted) ----
     int n_roll = 0, n_upd = 0;
     for (int p = 0; p < n;) {
-        const BatchKey& k = key[b->by_roll[p]];
+        const BatchKey& k = hd[b->by_roll[p]].key;
         int q = p + 1;
-        while (q < n && same_rollout(key[b->by_roll[q]], k)) ++q;
-        if (panda) {   // (+ one k_panda_reach_cost launch when the group keeps the record buffer: not counted)
-            launch_rollout_panda_batch(dp + p, q - p, b->plan[b->by_roll[p]], k.K, s);
-            ++n_roll;
-            p = q;
-            continue;
-        }
-        const int blocks = (k.K + k.lanes - 1) / k.lanes;
-        launch_rollout_point_batch(dr + p, q - p, k.instance, blocks, k.ref != 0, s);
+        while (q < n && same_rollout(hd[b->by_roll[q]].key, k)) ++q;
+        if (panda) launch_rollout_panda_batch(dp + p, q - p, k.roll, k.K, s);
+        else launch_rollout_point_batch(dr + p, q - p, k.roll, s);
         ++n_roll;
-        for (int r = p; r < q; ++r)   // (as m3_rollout: the instances that can leave the workgroups' minima)
-            hs[b->by_roll[r]]->wave_min_rows = (hr[r].a.wave_min && (k.instance == -1 || k.instance == 3)) ? blocks : 0;
         p = q;
     }
-    BATCHK(b, hipGetLastError());
+    HIPCHK(b, hipGetLastError());
     // ---- one update launch per group; multi-modal groups in chunks whose whole grid is resident ----
     for (int p = 0; p < n;) {
-        const BatchKey& k = key[b->by_upd[p]];
+        const BatchKey& k = hd[b->by_upd[p]].key;
         int q = p + 1;
-        while (q < n && same_update(key[b->by_upd[q]], k)) ++q;
+        while (q < n && same_update(hd[b->by_upd[q]].key, k)) ++q;
         int chunk = q - p;
         if (k.upd.multi) {
             const int per_cu = k.upd.nu == 9 ? update_small9_batch_blocks_per_cu(k.upd) : update_small_batch_blocks_per_cu(k.upd);
@@ -1830,30 +1795,25 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
         }
         p = q;
     }
-    BATCHK(b, hipGetLastError());
-    // ---- per handle, as m3_update_finalize: the covariance step, the call count ----
+    HIPCHK(b, hipGetLastError());
+    // ---- per handle, as m3_update_finalize (without its timing events): the covariance step, the call count ----
     for (int i = 0; i < n; ++i) {
-        m3_handle* h = hs[i];
-        const int rc = after_finalize(h);
-        if (rc != M3_OK) { b->err = "m3_batch_command: " + h->err; return rc; }
-        h->calls += 1;
+        const int rc = finish_command(hs[i], false);
+        if (rc != M3_OK) { b->err = "m3_batch_command: " + hs[i]->err; return rc; }
     }
-    BATCHK(b, hipEventRecord(b->done[slot], s));
+    HIPCHK(b, hipEventRecord(b->done[slot], s));
     b->in_flight[slot] = true;
     b->next = (slot + 1) % BATCH_SLOTS;
     b->rollout_launches = n_roll;
     b->update_launches = n_upd;
-    if (actions_host) {   // the plans one after the other: [rows_i][nu] each (rows = u_per_command in simple mode, else T)
+    if (actions_host) {   // the plans one after the other
         size_t off = 0;
         for (int i = 0; i < n; ++i) {
-            const m3_handle* h = hs[i];
-            const m3_config& c = h->cfg;
-            const size_t len = (size_t)(c.mode_simple ? c.u_per_command : c.T) * c.nu;
-            BATCHK(b, hipMemcpyAsync(actions_host + off, h->action_out ? h->action_out : (float*)h->buf[M3_BUF_ACTION_OUT],
-                                     len * sizeof(float), hipMemcpyDeviceToHost, s));
+            const size_t len = plan_floats(hs[i]->cfg);
+            HIPCHK(b, hipMemcpyAsync(actions_host + off, plan_dst(hs[i]), len * sizeof(float), hipMemcpyDeviceToHost, s));
             off += len;
         }
-        BATCHK(b, hipStreamSynchronize(s));
+        HIPCHK(b, hipStreamSynchronize(s));
     }
     return M3_OK;
 }
@@ -2122,17 +2082,9 @@ extern "C" int m3_episodes_create(m3_handle* world, m3_handle* const* planners, 
         if (c.env_type != M3_ENV_POINT) return eps_refuse(M3_ERR_UNSUPPORTED, i, "panda_env planner (point_env episodes only)");
         if (c.device != wc.device) return eps_refuse(M3_ERR_BAD_ARG, i, "handle on another device than the world");
         if (h->stream != world->stream) return eps_refuse(M3_ERR_STATE, i, "its stream differs from the world's");
-        // what m3_batch_command would refuse
-        if (c.K_local != c.K_global) return eps_refuse(M3_ERR_STATE, i, "sharded handle (K_local != K_global)");
-        if (c.sim_only) return eps_refuse(M3_ERR_STATE, i, "handle was created sim_only");
-        if (const char* why = rollout_refusal(h)) return eps_refuse(M3_ERR_STATE, i, why);
-        UpdateArgs ua;
-        fill_update_args(h, ua);
-        ua.fuse_finalize = 1;
-        ua.Jall = (const float*)h->buf[M3_BUF_TRAJ_COST];
-        if (!can_fuse_finalize(h) || !update_small_applies(ua))
-            return eps_refuse(M3_ERR_UNSUPPORTED, i, "its command does not take the one-launch update (nu = 2: K <= 16384; "
-                                                     "multi-modal K <= 8192)");
+        UpdateArgs u;
+        int code;
+        if (const char* why = batch_refusal(h, u, code)) return eps_refuse(code, i, why);
         if (!h->action_out) return eps_refuse(M3_ERR_STATE, i, "no action-out destination (m3_set_action_out)");
         const m3_episode_spec& sp = specs[i];
         if (sp.task < M3_TASK_NAVIGATION || sp.task > M3_TASK_PUSH_PULL) return eps_refuse(M3_ERR_BAD_ARG, i, "spec: task is not a point_env task");
@@ -2198,15 +2150,6 @@ extern "C" int m3_episodes_create(m3_handle* world, m3_handle* const* planners, 
     return M3_OK;
 }
 
-#define EPSK(eps, expr)                                                                  \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess) {                                                          \
-            (eps)->err = std::string(#expr) + ": " + hipGetErrorString(e_);              \
-            return M3_ERR_HIP;                                                           \
-        }                                                                                \
-    } while (0)
-
 static int eps_ready(m3_episodes* eps, const char* who) {
     if (eps->tick >= eps->max_ticks) { eps->err = std::string(who) + ": all max_ticks ticks are done"; return M3_ERR_STATE; }
     for (int i = 0; i < eps->n; ++i)
@@ -2219,8 +2162,8 @@ static int eps_ready(m3_episodes* eps, const char* who) {
 
 static int eps_status_sync(m3_episodes* eps) {
     const hipStream_t s = eps->world->stream;
-    EPSK(eps, hipMemcpyAsync(eps->host, eps->args.st, (size_t)eps->n * sizeof(m3_episode_status), hipMemcpyDeviceToHost, s));
-    EPSK(eps, hipStreamSynchronize(s));
+    HIPCHK(eps, hipMemcpyAsync(eps->host, eps->args.st, (size_t)eps->n * sizeof(m3_episode_status), hipMemcpyDeviceToHost, s));
+    HIPCHK(eps, hipStreamSynchronize(s));
     return M3_OK;
 }
 
@@ -2230,7 +2173,7 @@ extern "C" int m3_episodes_begin(m3_episodes* eps) {
     int rc = eps_ready(eps, "m3_episodes_begin");
     if (rc != M3_OK) return rc;
     m3::launch_episodes_pre(eps->args, eps->tick, eps->world->stream);
-    EPSK(eps, hipGetLastError());
+    HIPCHK(eps, hipGetLastError());
     eps->mid_tick = true;
     return eps_status_sync(eps);
 }
@@ -2241,7 +2184,7 @@ extern "C" int m3_episodes_end(m3_episodes* eps) {
     int rc = eps_ready(eps, "m3_episodes_end");
     if (rc != M3_OK) return rc;
     m3::launch_episodes_post(eps->world->scene, eps->args, eps->tick, eps->world->stream);
-    EPSK(eps, hipGetLastError());
+    HIPCHK(eps, hipGetLastError());
     eps->mid_tick = false;
     eps->tick += 1;
     return eps_status_sync(eps);
@@ -2268,13 +2211,13 @@ extern "C" int m3_episodes_tick(m3_episodes* eps, m3_batch* batch) {
         eps->live.push_back(h);
     }
     m3::launch_episodes_pre(eps->args, eps->tick, w->stream);
-    EPSK(eps, hipGetLastError());
+    HIPCHK(eps, hipGetLastError());
     if (!eps->live.empty()) {
         rc = m3_batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr);
         if (rc != M3_OK) { eps->err = std::string("m3_episodes_tick: ") + m3_batch_last_error(batch); return rc; }
     }
     m3::launch_episodes_post(w->scene, eps->args, eps->tick, w->stream);
-    EPSK(eps, hipGetLastError());
+    HIPCHK(eps, hipGetLastError());
     eps->tick += 1;
     return eps_status_sync(eps);
 }
@@ -2291,12 +2234,12 @@ extern "C" int m3_episodes_running(const m3_episodes* eps) {
 extern "C" int m3_episodes_status(m3_episodes* eps, m3_episode_status* status_out, float* trace_out) {
     if (!eps || !status_out) return M3_ERR_BAD_ARG;
     const hipStream_t s = eps->world->stream;
-    EPSK(eps, hipMemcpyAsync(status_out, eps->args.st, (size_t)eps->n * sizeof(m3_episode_status), hipMemcpyDeviceToHost, s));
+    HIPCHK(eps, hipMemcpyAsync(status_out, eps->args.st, (size_t)eps->n * sizeof(m3_episode_status), hipMemcpyDeviceToHost, s));
     if (trace_out) {
         if (!eps->trace) { eps->err = "m3_episodes_status: the set was created without a trace"; return M3_ERR_STATE; }
-        EPSK(eps, hipMemcpyAsync(trace_out, eps->trace, (size_t)eps->max_ticks * eps->n * 10 * sizeof(float),
+        HIPCHK(eps, hipMemcpyAsync(trace_out, eps->trace, (size_t)eps->max_ticks * eps->n * 10 * sizeof(float),
                                  hipMemcpyDeviceToHost, s));
     }
-    EPSK(eps, hipStreamSynchronize(s));
+    HIPCHK(eps, hipStreamSynchronize(s));
     return M3_OK;
 }

@@ -162,7 +162,8 @@ struct BatchRolloutEntry {   // one point_env handle's rollout (the scene is not
     RolloutArgs a;
     PointScene sc;
 };
-// the k_update_small instance (template arguments, workgroup width, top-k workgroups) an unsharded command takes
+// the k_update_small instance (template arguments, workgroup width, top-k workgroups) an unsharded command takes:
+// launch_update_small launches it, m3_batch_command groups the handles by it
 struct SmallUpdateInstance {
     int nu, multi, jr, wt, n_cand;
 };
@@ -173,17 +174,27 @@ int update_small_batch_blocks_per_cu(const SmallUpdateInstance& in);
 int update_small9_batch_blocks_per_cu(const SmallUpdateInstance& in);
 // one launch of k_update_small's body for n handles whose entries (tab[0 .. n-1], device) share `in` and T (and nu)
 void launch_update_small_batch(const UpdateArgs* tab, int n, const SmallUpdateInstance& in, int T, hipStream_t s);
-// -1: the general instance of the point_env rollout; 0..3: the per-task instance of that task (launch_rollout_point)
-int rollout_point_instance(const RolloutArgs& a);
-// one launch of the instance for n handles of K_local = a.Kl and the same lanes (tab: device, n entries)
-void launch_rollout_point_batch(const BatchRolloutEntry* tab, int n, int instance, int blocks, bool ref, hipStream_t s);
+// the form a rollout launch takes (plan_rollout_point, plan_rollout_panda); launches nothing: m3_rollout launches it at once,
+// m3_batch_command groups the handles by it
+struct RolloutPlan {
+    int instance, ref;   // point_env: -1 the general instance, 0..3 the per-task instance of that task; the reference's
+                         // solver settings compiled in (panda_env: 0, 0)
+    int lps, forces, general, shadows, rec;   // panda_env: lanes per sample, FORCES = pick / place, GENERAL = random sampler
+                                              // or simple mode, quirk Q8's shadow slots, k_panda_reach_cost behind it
+                                              // (point_env: all 0)
+    int lanes, blocks;   // active lanes per wavefront, rollout workgroups
+    int rows;            // rows of minima the launch leaves in a.wave_min (wave_min.hpp; 0: none)
+};
+RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc);
+// one launch of the plan's instance for n handles of K_local = a.Kl and the same plan (tab: device, n entries)
+void launch_rollout_point_batch(const BatchRolloutEntry* tab, int n, const RolloutPlan& p, hipStream_t s);
 void launch_rollout_point_nav_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
 void launch_rollout_point_push_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
 void launch_rollout_point_pull_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
 void launch_rollout_point_pushpull_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
 
 // ---- launchers (defined in the .hip files) ---------------------------------------------
-bool launch_rollout_point(const RolloutArgs& a, const PointScene& sc, hipStream_t s);
+void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const RolloutPlan& p, hipStream_t s);
 void launch_rollout_point_nav(const RolloutArgs& a, const PointScene& sc, int blocks, hipStream_t s);
 void launch_rollout_point_push(const RolloutArgs& a, const PointScene& sc, int blocks, hipStream_t s);
 void launch_rollout_point_pull(const RolloutArgs& a, const PointScene& sc, int blocks, hipStream_t s);
@@ -314,15 +325,9 @@ struct PandaArgs {
     unsigned long long* busy_count;   // device scratch of that: bits 0-23 wavefronts finished, bits 24-63 the sum so far
     int reach_busy;              // the host's reading of the last reports, with hysteresis: the reach command runs with 8 lanes per sample
 };
-int launch_rollout_panda(const RolloutArgs& a, const PandaArgs& pa, const PandaScene& sc, hipStream_t s,
-                         int* lps_used = nullptr);   // returns its workgroups; *lps_used = the kernel form it chose
-// the kernel form a panda rollout launch takes (rollout_panda.hip: plan_rollout_panda): lanes per sample, instance
-// (FORCES = pick / place, GENERAL = random sampler or simple mode), k_panda_reach_cost behind it, active lanes per
-// wavefront, rollout workgroups, and the rows of minima the launch leaves (the reach-cost kernel's workgroups with it)
-struct PandaRolloutPlan {
-    int lps, forces, general, rec, lanes, blocks, rows;
-};
-PandaRolloutPlan plan_rollout_panda(const RolloutArgs& a, PandaArgs& pa);
+// the plan of a panda rollout launch; pa becomes what the kernels receive (rows: the reach-cost kernel's workgroups with it)
+RolloutPlan plan_rollout_panda(const RolloutArgs& a, PandaArgs& pa);
+void launch_rollout_panda(const RolloutArgs& a, const PandaArgs& pa, const PandaScene& sc, const RolloutPlan& p, hipStream_t s);
 struct BatchPandaEntry {     // one panda_env handle's rollout in m3_batch_command's table (a.lanes: the plan's)
     RolloutArgs a;
     PandaArgs pa;
@@ -330,7 +335,7 @@ struct BatchPandaEntry {     // one panda_env handle's rollout in m3_batch_comma
 };
 // one launch of the plan's instance for n handles of K_local = Kl and the same plan (tab: device, n entries), + one launch
 // of the reach-cost kernel when the plan keeps the record buffer
-void launch_rollout_panda_batch(const BatchPandaEntry* tab, int n, const PandaRolloutPlan& p, int Kl, hipStream_t s);
+void launch_rollout_panda_batch(const BatchPandaEntry* tab, int n, const RolloutPlan& p, int Kl, hipStream_t s);
 void launch_psim_step(const PandaScene& sc, const SimViews& v, float* world, const float* u, float* u_keep, int Kl,
                       hipStream_t s);
 void launch_psim_pull(const PandaScene& sc, const SimViews& v, float* world, int Kl, hipStream_t s);

@@ -74,7 +74,7 @@ __device__ __forceinline__ float in_vgpr(float v) {   // keep a uniform value in
 // 16 -- the sixteen lanes of a DPP row simulate ONE sample together: everything but the contact solver's generalized vectors
 // is replicated in them, the joint-space rows of the gripper contacts run across them.  Four samples per wavefront, so K = 4000
 // is 1000 wavefronts, one per SIMD, instead of 63: the launch is as long as its slowest wavefront either way, and a wavefront's
-// velocity passes are ~2.3x shorter (tools/ubench/coop_panda_rows.hip).  Chosen by launch_rollout_panda.
+// velocity passes are ~2.3x shorter (tools/ubench/coop_panda_rows.hip).  Chosen by plan_rollout_panda.
 template <bool FORCES, bool GENERAL, int LPS>
 __global__ __launch_bounds__(64) void k_rollout_panda(const RolloutArgs a_, const PandaArgs pa,
                                                       const PandaScene sc_) {
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(64 * RC_TS) void k_panda_reach_cost(const RolloutAr
 //   reach (quirk Q8): with the arm away from everything nothing touches anything, the time is the replicated part of the step,
 //     which more lanes per sample only repeat in more wavefronts -- one lane with its shadow slots, 0.167 ms with the cubes asleep;
 //     once the rollouts are next to the cube (most of an episode's reach phase) the many-lane forms win by up to 2x: sixteen lanes
-//     WITHOUT shadow slots + k_panda_reach_cost where launch_rollout_panda has the record buffer, else eight lanes with them (sixteen
+//     WITHOUT shadow slots + k_panda_reach_cost where the launch has the record buffer, else eight lanes with them (sixteen
 //     would lose 1-2 of 4 sample slots and need two rounds of wavefronts).  pa.reach_busy says which (m3_api.hip).
 // Beyond 1024 wavefronts the launch is throughput-bound and the replicated work (16x / 8x more instructions per sample
 // outside the solver) decides: one lane.  pa.lps (m3_set_panda_lanes_per_sample) forces a form.
@@ -128,9 +128,8 @@ static int panda_lps_for(const RolloutArgs& a, const PandaArgs& pa) {
 }
 // The form of a launch: the lanes per sample, the instance, the lanes per wavefront adjusted for the shadow slots and the grid;
 // pa becomes what the kernels receive (no shadow slots with the record buffer; without it, and with the shadow slots again,
-// when the one-lane form is chosen).  Launches nothing: launch_rollout_panda launches it at once, m3_batch_command groups the
-// handles by it.
-PandaRolloutPlan plan_rollout_panda(const RolloutArgs& a, PandaArgs& pa) {
+// when the one-lane form is chosen).
+RolloutPlan plan_rollout_panda(const RolloutArgs& a, PandaArgs& pa) {
     const PandaArgs pa_in = pa;
     // reach without shadow slots (k_panda_reach_cost): when the handle holds the record buffer (m3_api.hip: K up to 8192), the
     // sampler is the default one and a many-lane form is what the launch
@@ -152,21 +151,22 @@ PandaRolloutPlan plan_rollout_panda(const RolloutArgs& a, PandaArgs& pa) {
         if (lps == 1) pa = pa_in, pa.reach_rec = nullptr;
     }
     if (pa.reach_rec == nullptr) lps = panda_lps_for(a, pa);
-    PandaRolloutPlan p;
+    RolloutPlan p{};
     p.lps = lps;
     p.forces = pa.cp.task == 5 ? 1 : 0;
     p.general = (a.sampling_random || a.mode_simple) ? 1 : 0;
+    p.shadows = pa.shadows;
     p.rec = pa.reach_rec != nullptr ? 1 : 0;
     const int spw = 64 / lps;
     int lanes = (a.lanes >= 1 && a.lanes <= spw) ? a.lanes : spw;
     if (lanes > spw - pa.shadows) lanes = spw - pa.shadows;
     p.lanes = lanes;
     p.blocks = (a.Kl + lanes - 1) / lanes;
-    p.rows = p.rec ? (a.Kl + 63) / 64 : p.blocks;
+    p.rows = !a.wave_min ? 0 : p.rec ? (a.Kl + 63) / 64 : p.blocks;
     return p;
 }
 template <int LPS>
-static void launch_rollout_panda_lps(const RolloutArgs& a_in, const PandaArgs& pa, const PandaScene& sc, const PandaRolloutPlan& p,
+static void launch_rollout_panda_lps(const RolloutArgs& a_in, const PandaArgs& pa, const PandaScene& sc, const RolloutPlan& p,
                                      hipStream_t s) {
     RolloutArgs a = a_in;
     a.lanes = p.lanes;
@@ -177,11 +177,8 @@ static void launch_rollout_panda_lps(const RolloutArgs& a_in, const PandaArgs& p
     } else if (p.forces) hipLaunchKernelGGL((k_rollout_panda<true, false, LPS>), grid, block, 0, s, a, pa, sc);
     else hipLaunchKernelGGL((k_rollout_panda<false, false, LPS>), grid, block, 0, s, a, pa, sc);
 }
-// returns the number of workgroups (= rows of the wave_min table)
-int launch_rollout_panda(const RolloutArgs& a, const PandaArgs& pa_in, const PandaScene& sc, hipStream_t s, int* lps_used) {
-    PandaArgs pa = pa_in;
-    const PandaRolloutPlan p = plan_rollout_panda(a, pa);
-    if (lps_used) *lps_used = p.lps;
+// pa: as plan_rollout_panda left it
+void launch_rollout_panda(const RolloutArgs& a, const PandaArgs& pa, const PandaScene& sc, const RolloutPlan& p, hipStream_t s) {
     if (p.lps == 16) launch_rollout_panda_lps<16>(a, pa, sc, p, s);
     else if (p.lps == 8) launch_rollout_panda_lps<8>(a, pa, sc, p, s);
     else launch_rollout_panda_lps<1>(a, pa, sc, p, s);
@@ -189,7 +186,6 @@ int launch_rollout_panda(const RolloutArgs& a, const PandaArgs& pa_in, const Pan
         const dim3 grid((a.Kl + 63) / 64), block(64 * RC_TS);
         hipLaunchKernelGGL(k_panda_reach_cost, grid, block, 0, s, a, pa);
     }
-    return p.rows;
 }
 
 // ---- batched command (m3_batch_command) ---------------------------------------------------------------------------
@@ -208,7 +204,7 @@ __global__ __launch_bounds__(64 * RC_TS) void kb_panda_reach_cost(const BatchPan
     const PandaArgs& pa = tab[blockIdx.y].pa;
 #include "panda_reach_cost_body.inc"
 }
-void launch_rollout_panda_batch(const BatchPandaEntry* tab, int n, const PandaRolloutPlan& p, int Kl, hipStream_t s) {
+void launch_rollout_panda_batch(const BatchPandaEntry* tab, int n, const RolloutPlan& p, int Kl, hipStream_t s) {
     const dim3 grid(p.blocks, n), block(64);
 #define M3_LAUNCH_PBATCH(LPS_)                                                                                             \
     do {                                                                                                                   \

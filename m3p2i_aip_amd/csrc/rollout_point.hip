@@ -16,9 +16,10 @@ int rollout_lanes_for(int Kl) {
     return 64;
 }
 
-// -1: the general instance (every sampler mode, task at run time); 0..3: the instance with the reference's default sampler
-// and that task compiled in (rollout_point_task*.hip)
-int rollout_point_instance(const RolloutArgs& a) {
+// The form of a launch.  Instance -1: the general instance (every sampler mode, task at run time); 0..3: the instance with
+// the reference's default sampler and that task compiled in (rollout_point_task*.hip).  Only the general and the push_pull
+// instances carry the epilogue that leaves the workgroups' cost minima (rollout_point_kernel.hpp).
+RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc) {
 #if defined(M3_ABL_GENERAL_ONLY) || defined(M3_ABL_COUNT) || defined(M3_ABL_PHASES)   // (experiments: one kernel for all modes;
     // the instrumented builds keep their counters in this translation unit)
     const bool general = true;
@@ -28,29 +29,33 @@ int rollout_point_instance(const RolloutArgs& a) {
                          (a.cp.task == 3 && !a.multi_modal) || a.scale_dev != nullptr /* update_cov */ ||
                          a.cp.avoid_dyn_obs != 0 /* the extension: the dyn-obs contact force must be formed */;
 #endif
-    return general ? -1 : a.cp.task;
+    RolloutPlan p{};
+    p.instance = general ? -1 : a.cp.task;
+    p.ref = point_scene_is_reference(sc) ? 1 : 0;
+    p.lanes = a.lanes;
+    p.blocks = (a.Kl + a.lanes - 1) / a.lanes;
+    p.rows = (a.wave_min && (p.instance == -1 || p.instance == 3)) ? p.blocks : 0;
+    return p;
 }
 
-// returns whether the instance launched leaves the workgroups' cost minima in a.wave_min (wave_min.hpp)
-bool launch_rollout_point(const RolloutArgs& a, const PointScene& sc, hipStream_t s) {
-    const int blocks = (a.Kl + a.lanes - 1) / a.lanes;
-    switch (rollout_point_instance(a)) {   // the reference's default sampler: one instance per task (rollout_point_task*.hip)
-        case -1: launch_rollout_point_instance<true, -1>(a, sc, blocks, s); return a.wave_min != nullptr;
-        case 0: launch_rollout_point_nav(a, sc, blocks, s); break;
-        case 1: launch_rollout_point_push(a, sc, blocks, s); break;
-        case 2: launch_rollout_point_pull(a, sc, blocks, s); break;
-        default: launch_rollout_point_pushpull(a, sc, blocks, s); return a.wave_min != nullptr;
+void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const RolloutPlan& p, hipStream_t s) {
+    switch (p.instance) {
+        case -1: launch_rollout_point_instance<true, -1>(a, sc, p.blocks, s); break;
+        case 0: launch_rollout_point_nav(a, sc, p.blocks, s); break;
+        case 1: launch_rollout_point_push(a, sc, p.blocks, s); break;
+        case 2: launch_rollout_point_pull(a, sc, p.blocks, s); break;
+        default: launch_rollout_point_pushpull(a, sc, p.blocks, s); break;
     }
-    return false;
 }
 
-void launch_rollout_point_batch(const BatchRolloutEntry* tab, int n, int instance, int blocks, bool ref, hipStream_t s) {
-    switch (instance) {
-        case -1: launch_rollout_point_batch_instance<true, -1>(tab, blocks, n, ref, s); break;
-        case 0: launch_rollout_point_nav_batch(tab, blocks, n, ref, s); break;
-        case 1: launch_rollout_point_push_batch(tab, blocks, n, ref, s); break;
-        case 2: launch_rollout_point_pull_batch(tab, blocks, n, ref, s); break;
-        default: launch_rollout_point_pushpull_batch(tab, blocks, n, ref, s); break;
+void launch_rollout_point_batch(const BatchRolloutEntry* tab, int n, const RolloutPlan& p, hipStream_t s) {
+    const bool ref = p.ref != 0;
+    switch (p.instance) {
+        case -1: launch_rollout_point_batch_instance<true, -1>(tab, p.blocks, n, ref, s); break;
+        case 0: launch_rollout_point_nav_batch(tab, p.blocks, n, ref, s); break;
+        case 1: launch_rollout_point_push_batch(tab, p.blocks, n, ref, s); break;
+        case 2: launch_rollout_point_pull_batch(tab, p.blocks, n, ref, s); break;
+        default: launch_rollout_point_pushpull_batch(tab, p.blocks, n, ref, s); break;
     }
 }
 

@@ -186,7 +186,7 @@ __device__ __forceinline__ void rollout_point_body(const RolloutArgs& a_, const 
 #endif
     a.J[i] = a.mode_simple ? (S + pc) : J;
     // (only the instances a multi-modal command can run carry this epilogue: compiled into the push instance too it cost
-    // the headline 2 us -- 316 instead of 312 VGPRs -- without ever running there; launch_rollout_point says who wrote)
+    // the headline 2 us -- 316 instead of 312 VGPRs -- without ever running there; plan_rollout_point says who wrote)
     if constexpr (GENERAL || TASK == 3) {
         if (a.wave_min) wave_min_store(a.wave_min, J, first_half, true);
     }

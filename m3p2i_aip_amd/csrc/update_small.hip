@@ -23,43 +23,54 @@ template <int NU, bool MULTI, int JR, int WT = 256>
 __global__ __launch_bounds__(WT) void k_update_small(const UpdateArgs a) {
 #include "update_small_body.inc"
 }
+// The instance of a's command: template arguments (JR: register rows of 256 costs), workgroup width and top-k workgroups.
+// n_cand is what the launched copy of the arguments holds.
+SmallUpdateInstance update_small_instance(const UpdateArgs& a) {
+    const bool multi = a.multi_modal && !a.mode_simple;
+    const int rows = (a.Kg + 255) / 256;
+    SmallUpdateInstance in{a.nu, multi ? 1 : 0, rows <= 8 ? 8 : 16, 256, a.n_cand};
+    if (a.nu != 2) return in;
+    // multi-modal with more than 2048 costs: 512-thread workgroups (half the register rows per thread: every per-row loop of
+    // the kernel -- loads, ladder points, weights, sums -- halves; C3 24.2 -> 22.4 us, K = 8000 33 -> 27.7 us), ONE top-k
+    // workgroup (32 rows of 256 costs).  Single mode measured no gain (panda -1 %) or a loss (C2: +10 us on the command
+    // although the kernel itself is not slower -- the wider workgroups delay the next rollout's dispatch).
+#ifdef M3_EXP_UPDATE_WT256   // (experiment build: the 256-thread instances)
+    constexpr bool wide = false;
+#else
+    constexpr bool wide = true;
+#endif
+    if (multi && wide && rows > 8) { in.wt = 512; in.n_cand = 1; in.jr = rows > 16 ? 16 : 8; }
+    else if (multi && rows > 16) in.jr = 32;
+    else if (multi) {}
+    else if (rows <= 16) {}
+    else if (rows <= 32) in.jr = 32;
+    else in.jr = 64;
+    return in;
+}
 void launch_update_small(const UpdateArgs& a_, hipStream_t s) {
     // (a.ladder_spins: bounded wait of the in-launch ladder exchange, ~20 ms; m3_set_ladder_spins(h, 0) makes every
     // workgroup give up at once and run all its passes itself -- tests/test_hip_edge_cases.py: same decisions)
+    const SmallUpdateInstance in = update_small_instance(a_);
     UpdateArgs a = a_;
-    const dim3 grid(a.T + a.n_cand);
+    a.n_cand = in.n_cand;
+    const dim3 grid(a.T + in.n_cand);
     const size_t lds = (size_t)a.T * a.nu * sizeof(float);
-    const bool multi = a.multi_modal && !a.mode_simple;
-    const int rows = (a.Kg + 255) / 256;
-#define M3_LAUNCH_SMALL(NU_, MULTI_)                                                                         \
-    do {                                                                                                     \
-        if (rows <= 8) hipLaunchKernelGGL((k_update_small<NU_, MULTI_, 8>), grid, dim3(256), lds, s, a);     \
-        else hipLaunchKernelGGL((k_update_small<NU_, MULTI_, 16>), grid, dim3(256), lds, s, a);              \
-    } while (0)
-    if (a.nu == 2) {
-        // multi-modal with more than 2048 costs: 512-thread workgroups (half the register rows per thread: every
-        // per-row loop of the kernel -- loads, ladder points, weights, sums -- halves; C3 24.2 -> 22.4 us, K = 8000
-        // 33 -> 27.7 us).  Single mode measured no gain (panda -1 %) or a loss (C2: +10 us on the command although
-        // the kernel itself is not slower -- the wider workgroups delay the next rollout's dispatch).
-#ifdef M3_EXP_UPDATE_WT256   // (experiment build: the 256-thread instances)
-        constexpr bool wide = false;
-#else
-        constexpr bool wide = true;
-#endif
-        if (multi && wide && rows > 8) {   // 512 threads per workgroup, ONE top-k workgroup (32 rows of 256 costs)
-            a.n_cand = 1;
-            const dim3 grid1(a.T + 1);
-            if (rows > 16) hipLaunchKernelGGL((k_update_small<2, true, 16, 512>), grid1, dim3(512), lds, s, a);
-            else hipLaunchKernelGGL((k_update_small<2, true, 8, 512>), grid1, dim3(512), lds, s, a);
-        }
-        else if (multi && rows > 16) hipLaunchKernelGGL((k_update_small<2, true, 32>), grid, dim3(256), lds, s, a);
-        else if (multi) M3_LAUNCH_SMALL(2, true);
-        else if (rows <= 16) M3_LAUNCH_SMALL(2, false);
-        else if (rows <= 32) hipLaunchKernelGGL((k_update_small<2, false, 32>), grid, dim3(256), lds, s, a);
-        else hipLaunchKernelGGL((k_update_small<2, false, 64>), grid, dim3(256), lds, s, a);
-    } else {
-        if (multi) M3_LAUNCH_SMALL(9, true); else M3_LAUNCH_SMALL(9, false);
-    }
+#define M3_LAUNCH_SMALL(NU_, MULTI_, JR_, WT_) hipLaunchKernelGGL((k_update_small<NU_, MULTI_, JR_, WT_>), grid, dim3(WT_), lds, s, a)
+    // (the instances in the order they were first written here: their code keeps its place in the code object)
+    if (in.nu == 2 && in.multi) {
+        if (in.wt == 512) { if (in.jr == 16) M3_LAUNCH_SMALL(2, true, 16, 512); else M3_LAUNCH_SMALL(2, true, 8, 512); }
+        else if (in.jr == 32) M3_LAUNCH_SMALL(2, true, 32, 256);
+        else if (in.jr == 8) M3_LAUNCH_SMALL(2, true, 8, 256);
+        else M3_LAUNCH_SMALL(2, true, 16, 256);
+    } else if (in.nu == 2) {
+        if (in.jr == 8) M3_LAUNCH_SMALL(2, false, 8, 256);
+        else if (in.jr == 16) M3_LAUNCH_SMALL(2, false, 16, 256);
+        else if (in.jr == 32) M3_LAUNCH_SMALL(2, false, 32, 256);
+        else M3_LAUNCH_SMALL(2, false, 64, 256);
+    } else if (in.multi) {
+        if (in.jr == 8) M3_LAUNCH_SMALL(9, true, 8, 256); else M3_LAUNCH_SMALL(9, true, 16, 256);
+    } else if (in.jr == 8) M3_LAUNCH_SMALL(9, false, 8, 256);
+    else M3_LAUNCH_SMALL(9, false, 16, 256);
 #undef M3_LAUNCH_SMALL
 }
 bool update_small_applies(const UpdateArgs& a) {
@@ -76,26 +87,6 @@ bool update_small_applies(const UpdateArgs& a) {
 }
 
 // ---- batched command (m3_batch_command) ---------------------------------------------------------------------------
-// The instance launch_update_small picks (same rules, same order); n_cand is what the launched copy of the arguments holds.
-SmallUpdateInstance update_small_instance(const UpdateArgs& a) {
-    const bool multi = a.multi_modal && !a.mode_simple;
-    const int rows = (a.Kg + 255) / 256;
-    SmallUpdateInstance in{a.nu, multi ? 1 : 0, rows <= 8 ? 8 : 16, 256, a.n_cand};
-    if (a.nu != 2) return in;
-#ifdef M3_EXP_UPDATE_WT256
-    constexpr bool wide = false;
-#else
-    constexpr bool wide = true;
-#endif
-    if (multi && wide && rows > 8) { in.wt = 512; in.n_cand = 1; in.jr = rows > 16 ? 16 : 8; }
-    else if (multi && rows > 16) in.jr = 32;
-    else if (multi) {}
-    else if (rows <= 16) {}
-    else if (rows <= 32) in.jr = 32;
-    else in.jr = 64;
-    return in;
-}
-
 // One workgroup of the handle tab[blockIdx.y], its own grid's workgroup blockIdx.x: the unchanged body.  The table is
 // read-only during the launch (`__restrict__`); a handle's workgroups only ever meet through that handle's own counters
 // and buffers (wcount, lad, cand), exactly as in its own launch.
