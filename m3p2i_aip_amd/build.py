@@ -24,7 +24,8 @@ CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
           "-Wno-unused-function"]
 # per-source flags, measured on the bench configs (tools/time_variants_cfg.sh; later flags win; none of them changes
 # floating-point semantics): the point rollout kernels are ~2 % faster at -O2 than at -O3, the panda rollout
-# faster without the SLP vectoriser (the point kernels ~2 % slower without it) and at -O2
+# faster without the SLP vectoriser (the point kernels ~2 % slower without it -- measured again with the predicated rows of the
+# lean substep instances, profiles/lean_rows: +2.4 % without it) and at -O2
 PER_SOURCE = {
     "rollout_point.hip": ["-O2"], "rollout_point_task0.hip": ["-O2"], "rollout_point_task1.hip": ["-O2"],
     "rollout_point_task2.hip": ["-O2"], "rollout_point_task3.hip": ["-O2"],

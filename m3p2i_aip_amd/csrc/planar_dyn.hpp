@@ -135,12 +135,18 @@ __device__ __forceinline__ float spec_rsqrt(float a) {
 // factors of the linear / torsion rows' limits from the velocities a substep starts its passes with.  A patch that
 // slides fast hardly resists turning -- the independent torsion row of spec v1.4 resisted it in full, which is what
 // wedged the box behind the goal at the reference's shipped planner size (profiles/r04/ab_default_size_push.json).
+template <bool PRED = false>
 __device__ __forceinline__ void friction_coupling(float vx, float vy, float w, float R, float& cl, float& ca) {
     const float s2 = mad(vx, vx, vy * vy);
     const float v = ((__float_as_uint(s2) & 0x7f800000u) == 0u) ? 0.0f : s2 * spec_rsqrt(s2);
     auto zero = [](float x) { return (__float_as_uint(x) & 0x7f800000u) == 0u; };   // (below the smallest normal number)
     const float u = zero(w) ? 0.0f : R * fabsf(w);
     cl = 1.0f; ca = 1.0f;
+    if constexpr (PRED) {   // (both factors for all lanes, selected: no per-lane branch)
+        const float fl = v * spec_rcp(mad(0.8488264f, u, v)), fa = u * spec_rcp(mad(2.9452431f, v, u));
+        cl = zero(v) ? 1.0f : fl; ca = zero(u) ? 1.0f : fa;
+        return;
+    }
     if (!zero(v)) cl = v * spec_rcp(mad(0.8488264f, u, v));
     if (!zero(u)) ca = u * spec_rcp(mad(2.9452431f, v, u));
 }
@@ -199,8 +205,9 @@ __device__ __forceinline__ void apply(const PointScene& sc, Vel& v, float dl, fl
     }
 }
 
-// spec: prepare (effective masses, bias) of one contact
-template <int A, int B>
+// spec: prepare (effective masses, bias) of one contact.  PRED: the same values without a per-lane branch (both sides of the
+// bias are formed and one is selected) -- for the predicated rows of the lean substep instances, see point_substep.
+template <int A, int B, bool PRED = false>
 __device__ __forceinline__ void prepare(const PointScene& sc, Slot& c, float nx, float ny,
                                         float rax, float ray, float rbx, float rby, float sep) {
     const float tx = -ny, ty = nx;
@@ -221,7 +228,11 @@ __device__ __forceinline__ void prepare(const PointScene& sc, Slot& c, float nx,
     }
     c.mn = spec_rcp(kn);
     c.mt = spec_rcp(kt);
-    if (sep > 0.0f) {
+    if constexpr (PRED) {
+        const float pen = clamp_lo0(-sep - sc.slop);
+        const float push = clamp_hi((sc.baumgarte * pen) * sc.inv_h, sc.max_bias);
+        c.bias = (sep > 0.0f) ? sep * sc.inv_h : -push;
+    } else if (sep > 0.0f) {
         c.bias = sep * sc.inv_h;
     } else {
         float pen = -sep - sc.slop;
@@ -264,15 +275,60 @@ __device__ __forceinline__ void solve(const PointScene& sc, Vel& v, Slot& c, flo
     apply<B, +1>(sc, v, dl, tx, ty, c.rtb);
 }
 
+// The same row for ALL lanes, merged by a select on the slot's flag: lanes without the contact compute on whatever their
+// slot holds (anything, inf / NaN included) and keep their old velocities.  No exec-mask region, so the row sits in one
+// basic block with its neighbours (point_substep's lean passes).  The slot's accumulated impulses need no select: a slot
+// is prepared anew in every substep, its flag does not change within one, and nobody reads ln / lt of a slot that is off.
+template <int A, int B>
+__device__ __forceinline__ void solve_sel(const PointScene& sc, Vel& v, Slot& c, float mu) {
+    Vel n = v;
+    solve<A, B>(sc, n, c, mu);
+    const bool on = c.on;
+    if constexpr (A == ROBOT || B == ROBOT) { v.rvx = on ? n.rvx : v.rvx; v.rvy = on ? n.rvy : v.rvy; }
+    if constexpr (A == BOXB || B == BOXB) { v.bvx = on ? n.bvx : v.bvx; v.bvy = on ? n.bvy : v.bvy; v.bw = on ? n.bw : v.bw; }
+    if constexpr (A == BOXD || B == BOXD) { v.dvx = on ? n.dvx : v.dvx; v.dvy = on ? n.dvy : v.dvy; v.dw = on ? n.dw : v.dw; }
+}
+
 // ---- narrow phase ---------------------------------------------------------------------
 // robot disc (A) vs box (B, possibly static)
-template <int B>
+// PRED: every lane runs the whole narrow phase and `on` is the conjunction of the tests the branches of the plain form
+// return on; every field of the slot is defined (lanes out of range hold values nobody uses).
+template <int B, bool PRED = false>
 __device__ __forceinline__ void detect_disc_box(const PointScene& sc, Slot& c, float px, float py,
                                                 float qx, float qy, float bc, float bs, float hx,
                                                 float hy, float rad) {
     c.on = false;
     const float r = sc.robot_r;
     const float dx = px - qx, dy = py - qy;
+    if constexpr (PRED) {
+        const float lim = r + rad + sc.contact_offset + 1e-3f;
+        const bool in_range = !(mad(dx, dx, dy * dy) > lim * lim);
+        const float lx = mad(bc, dx, bs * dy);
+        const float ly = mad(bc, dy, -(bs * dx));
+        const float kx = fminf(fmaxf(lx, -hx), hx);
+        const float ky = fminf(fmaxf(ly, -hy), hy);
+        const float ex = lx - kx, ey = ly - ky;
+        const float d2 = mad(ex, ex, ey * ey);
+        const bool outside = d2 > 0.0f;
+        const float rd = spec_rsqrt(d2);
+        const float d = d2 * rd;
+        // (the disc's centre inside the box: the face of least penetration)
+        const float ppx = hx - fabsf(lx), ppy = hy - fabsf(ly);
+        const bool xface = ppx < ppy;
+        const float sgx = (lx >= 0.0f) ? 1.0f : -1.0f, sgy = (ly >= 0.0f) ? 1.0f : -1.0f;
+        const float nlx = outside ? ex * rd : (xface ? sgx : 0.0f);
+        const float nly = outside ? ey * rd : (xface ? 0.0f : sgy);
+        const float cx = outside ? kx : (xface ? sgx * hx : lx);
+        const float cy = outside ? ky : (xface ? ly : sgy * hy);
+        const float sep = outside ? d - r : (xface ? -ppx - r : -ppy - r);
+        const float wx = mad(bc, nlx, -(bs * nly));
+        const float wy = mad(bs, nlx, bc * nly);
+        const float rbx = mad(bc, cx, -(bs * cy));
+        const float rby = mad(bs, cx, bc * cy);
+        prepare<ROBOT, B, true>(sc, c, -wx, -wy, 0.0f, 0.0f, rbx, rby, sep);
+        c.on = in_range && (sep < sc.contact_offset);
+        return;
+    }
     {   // conservative broad phase (does not change results)
         const float lim = r + rad + sc.contact_offset + 1e-3f;
         if (mad(dx, dx, dy * dy) > lim * lim) return;
@@ -451,20 +507,18 @@ struct Fric {
     float lx, ly, la;
 };
 
-// (A branch-free version of this row -- selects instead of the two exec-mask regions, so that the
-// scheduler could overlap it with the drive rows and the other box's row -- was measured 9 %
-// SLOWER: the disc clamp's IEEE sqrt + divide chain then sits on every pass's critical path, also
-// for bodies at rest or inside the friction disc, and the compiler does not interleave two such
-// expanded chains anyway: tools/ubench/valu_chain.hip, "2 independent div/sqrt".)
+// spec: a body at rest (v = 0 and w = 0) has no friction row in this pass.  v1.4: "zero" = below the smallest normal
+// number -- 1 / I is a rounded reciprocal, so an angular friction row leaves ~1e-8 of the spin, which the next
+// passes shrink by that factor each until it is subnormal, where it can stay (-I * 1e-45 rounds to 0): such a
+// body IS at rest.  (one v_or3 + v_and + compare on the bit patterns: the exponent fields of all three are zero
+// -- instead of three float compares joined through scalar registers)
+template <int ID> __device__ __forceinline__ bool body_rests(const Vel& v) {
+    return ((__float_as_uint(gvx<ID>(v)) | __float_as_uint(gvy<ID>(v)) | __float_as_uint(gw<ID>(v))) & 0x7f800000u) == 0u;
+}
+// the friction row of a body that moves
 template <int ID>
-__device__ __forceinline__ void solve_ground_friction(const PointScene& sc, Vel& v, Fric& f,
-                                                      float m, float I, float Llin, float Lang) {
-    // spec: a body at rest (v = 0 and w = 0) has no friction row in this pass.  v1.4: "zero" = below the smallest normal
-    // number -- 1 / I is a rounded reciprocal, so an angular friction row leaves ~1e-8 of the spin, which the next
-    // passes shrink by that factor each until it is subnormal, where it can stay (-I * 1e-45 rounds to 0): such a
-    // body IS at rest.  (one v_or3 + v_and + compare on the bit patterns: the exponent fields of all three are zero
-    // -- instead of three float compares joined through scalar registers)
-    if (((__float_as_uint(gvx<ID>(v)) | __float_as_uint(gvy<ID>(v)) | __float_as_uint(gw<ID>(v))) & 0x7f800000u) == 0u) return;
+__device__ __forceinline__ void solve_ground_friction_row(const PointScene& sc, Vel& v, Fric& f,
+                                                          float m, float I, float Llin, float Lang) {
     float nlx = mad(-m, gvx<ID>(v), f.lx);
     float nly = mad(-m, gvy<ID>(v), f.ly);
     const float mag2 = mad(nlx, nlx, nly * nly);
@@ -490,11 +544,35 @@ __device__ __forceinline__ void solve_ground_friction(const PointScene& sc, Vel&
     else v.dw = mad(sc.invI_d, nla - f.la, v.dw);
     f.la = nla;
 }
+// ... behind the rest test as an exec-mask region (the general instances' rolled passes, step mode) ...
+template <int ID>
+__device__ __forceinline__ void solve_ground_friction(const PointScene& sc, Vel& v, Fric& f,
+                                                      float m, float I, float Llin, float Lang) {
+    if (body_rests<ID>(v)) return;
+    solve_ground_friction_row<ID>(sc, v, f, m, I, Llin, Lang);
+}
+// ... and for ALL lanes with the rest test as a select: lanes whose body rests keep their velocities and impulses, and the
+// row shares a basic block with the drive rows and the other body's rows (point_substep's lean passes).  (When the disc
+// clamp still was an IEEE sqrt + divide chain, a branch-free row was 9 % SLOWER -- that chain then sat on every pass's
+// critical path; with spec_rsqrt and the clamp a select it is the faster form: DESIGN.md section 6.)
+template <int ID>
+__device__ __forceinline__ void solve_ground_friction_sel(const PointScene& sc, Vel& v, Fric& f,
+                                                          float m, float I, float Llin, float Lang) {
+    const bool rests = body_rests<ID>(v);
+    Vel n = v;
+    Fric g = f;
+    solve_ground_friction_row<ID>(sc, n, g, m, I, Llin, Lang);
+    f.lx = rests ? f.lx : g.lx; f.ly = rests ? f.ly : g.ly; f.la = rests ? f.la : g.la;
+    if constexpr (ID == BOXB) { v.bvx = rests ? v.bvx : n.bvx; v.bvy = rests ? v.bvy : n.bvy; v.bw = rests ? v.bw : n.bw; }
+    else { v.dvx = rests ? v.dvx : n.dvx; v.dvy = rests ? v.dvy : n.dvy; v.dw = rests ? v.dw : n.dw; }
+}
 
+template <bool PRED = false>
 __device__ __forceinline__ void integrate_box(Box& X, float h) {
     X.x = mad(h, X.vx, X.x);
     X.y = mad(h, X.vy, X.y);
-    if ((__float_as_uint(X.w) & 0x7f800000u) == 0u) return;  // spec: orientation is only touched when w != 0 (v1.4: subnormal = 0)
+    const bool still = (__float_as_uint(X.w) & 0x7f800000u) == 0u;  // spec: orientation is only touched when w != 0 (v1.4: subnormal = 0)
+    if constexpr (!PRED) { if (still) return; }
     const float a = 0.5f * (h * X.w);
     const float a2 = a * a;
     const float den = 1.0f + a2;
@@ -504,8 +582,8 @@ __device__ __forceinline__ void integrate_box(Box& X, float h) {
     const float c = mad(X.c, cd, -(X.s * sd));
     const float s = mad(X.s, cd, X.c * sd);
     const float rn = spec_rsqrt(mad(c, c, s * s));
-    X.c = c * rn;
-    X.s = s * rn;
+    X.c = (PRED && still) ? X.c : c * rn;   // (PRED: all lanes run the update, lanes that do not turn keep their orientation)
+    X.s = (PRED && still) ? X.s : s * rn;
 }
 
 // impulse of slot c on its body b (+) / a (-), accumulated in slot order like the oracle
@@ -591,7 +669,10 @@ struct PhaseClock {};
 
 struct RowOn { static constexpr bool value = true; };     // compile-time flags of point_substep's pass versions
 struct RowOff { static constexpr bool value = false; };
-template <bool ALL_FORCES, unsigned M>
+// LONE: the build runs as ONE wavefront per SIMD (every BASELINE size), where the wave's own instruction stream is the
+// command's time: predicated rows and the two-level broad phase below.  The builds for two / three resident waves per
+// SIMD (saturated launches, VALU throughput-bound: predication ADDS vector instructions) keep the branches.
+template <bool ALL_FORCES, unsigned M, bool LONE = true>
 __device__ __forceinline__ void point_substep(const PointScene& sc, PointWorld& w, float ux, float uy,
                                               bool form_dyn_force, PhaseClock* pc_ = nullptr) {
     M3_PH(1);
@@ -618,11 +699,20 @@ __device__ __forceinline__ void point_substep(const PointScene& sc, PointWorld& 
     s_rd.on = s_ro.on = s_rwx.on = s_rwy.on = false;
     s_bx1.on = s_bx2.on = s_by1.on = s_by2.on = s_dx1.on = s_dx2.on = s_dy1.on = s_dy2.on = false;
     s_bd1.on = s_bd2.on = s_bo1.on = s_bo2.on = s_do1.on = s_do2.on = false;
+    // The three lean instances (see below) run WITHOUT per-lane branches: narrow phase, friction coupling, solver rows and
+    // orientation update are computed for all lanes and merged by selects on the lanes' flags (PRED).  Same operations in
+    // the same order on every lane that has the row, so identical bits; lanes without it compute values nobody reads.
+    constexpr bool LEAN = !ALL_FORCES && (M == 0u || M == G_RB || M == (G_RB | G_RD));
+#ifdef M3_ABL_BRANCHY_ROWS
+    constexpr bool PRED = false;
+#else
+    constexpr bool PRED = LEAN && LONE;
+#endif
     if constexpr (RB)
-        detect_disc_box<BOXB>(sc, s_rb, w.rx, w.ry, w.B.x, w.B.y, w.B.c, w.B.s, sc.box_hx,
+        detect_disc_box<BOXB, PRED>(sc, s_rb, w.rx, w.ry, w.B.x, w.B.y, w.B.c, w.B.s, sc.box_hx,
                               sc.box_hy, sc.rad_b);
     if constexpr (RD)
-        detect_disc_box<BOXD>(sc, s_rd, w.rx, w.ry, w.D.x, w.D.y, w.D.c, w.D.s, sc.dyn_hx,
+        detect_disc_box<BOXD, PRED>(sc, s_rd, w.rx, w.ry, w.D.x, w.D.y, w.D.c, w.D.s, sc.dyn_hx,
                               sc.dyn_hy, sc.rad_d);
     if constexpr (RO)
         detect_disc_box<STATIC>(sc, s_ro, w.rx, w.ry, sc.obs_x, sc.obs_y, 1.0f, 0.0f, sc.obs_hx,
@@ -660,12 +750,12 @@ __device__ __forceinline__ void point_substep(const PointScene& sc, PointWorld& 
     float LlinBe = sc.LlinB, LangBe = sc.LangB, LlinDe = sc.LlinD, LangDe = sc.LangD;
     if (__builtin_amdgcn_ballot_w64(((__float_as_uint(v.bvx) | __float_as_uint(v.bvy) | __float_as_uint(v.bw)) & 0x7f800000u) != 0u) != 0ull) {
         float cl, ca;
-        friction_coupling(v.bvx, v.bvy, v.bw, sc.RcB, cl, ca);
+        friction_coupling<PRED>(v.bvx, v.bvy, v.bw, sc.RcB, cl, ca);
         LlinBe = sc.LlinB * cl; LangBe = sc.LangB * ca;
     }
     if (__builtin_amdgcn_ballot_w64(((__float_as_uint(v.dvx) | __float_as_uint(v.dvy) | __float_as_uint(v.dw)) & 0x7f800000u) != 0u) != 0ull) {
         float cl, ca;
-        friction_coupling(v.dvx, v.dvy, v.dw, sc.RcD, cl, ca);
+        friction_coupling<PRED>(v.dvx, v.dvy, v.dw, sc.RcD, cl, ca);
         LlinDe = sc.LlinD * cl; LangDe = sc.LangD * ca;
     }
     // A body that no slot of this instance touches and that is at rest now stays at rest for the
@@ -679,15 +769,15 @@ __device__ __forceinline__ void point_substep(const PointScene& sc, PointWorld& 
         skipD = __builtin_amdgcn_ballot_w64(((__float_as_uint(v.dvx) | __float_as_uint(v.dvy) | __float_as_uint(v.dw)) & 0x7f800000u) != 0u) == 0ull;
     // The three lean instances (no pair at all / robot-box / + robot-dyn-obs: nearly every substep of the planned
     // rollouts) run their passes in VERSIONS chosen once per substep by wave-uniform flags -- with / without the
-    // box's and the dyn-obs' friction rows and the robot-dyn-obs row -- and, for the reference's six iterations,
+    // box's and the dyn-obs' friction rows, the robot-dyn-obs row and the robot-box row (a row exists in a version
+    // when a ballot finds a lane that has it; inside, the rows are predicated) -- and, for the reference's six iterations,
     // fully unrolled: inside the generic loop below every pass paid two or three TAKEN scalar branches (rows of
     // bodies at rest and of contacts no lane has are skipped) and the loop's own -- a taken branch refills the lone
     // wavefront's instruction buffer, ~30 cycles against a drive-row pass of ~120 -- and the straight-line form lets
     // the scheduler interleave the independent rows.  Same operations in the same order: identical bits.
     // (C2 0.144 -> 0.136 ms, C3 0.182 -> 0.170, north-star 0.173 -> 0.163.)
-    constexpr bool LEAN = !ALL_FORCES && (M == 0u || M == G_RB || M == (G_RB | G_RD));
     if constexpr (LEAN) {
-        auto pass = [&](auto with_b, auto with_d, auto with_rd) {
+        auto pass = [&](auto with_b, auto with_d, auto with_rd, auto with_rb) {
             {
                 float dl = -(mad(sc.gam, ldx, v.rvx - ux) * sc.md);
                 float l1 = ldx + dl;
@@ -700,23 +790,31 @@ __device__ __forceinline__ void point_substep(const PointScene& sc, PointWorld& 
                 v.rvy = mad(sc.invm_r, l1 - ldy, v.rvy);
                 ldy = l1;
             }
-            if constexpr (decltype(with_b)::value) solve_ground_friction<BOXB>(sc, v, fB, sc.box_m, sc.box_I, LlinBe, LangBe);
-            if constexpr (RB) {
-                if (s_rb.on) solve<ROBOT, BOXB>(sc, v, s_rb, sc.mu_rb);
-            }
-            if constexpr (decltype(with_d)::value) solve_ground_friction<BOXD>(sc, v, fD, sc.dyn_m, sc.dyn_I, LlinDe, LangDe);
-            if constexpr (RD && decltype(with_rd)::value) {
-                if (s_rd.on) solve<ROBOT, BOXD>(sc, v, s_rd, sc.mu_rd);
+            // predicated rows (-DM3_ABL_BRANCHY_ROWS: the per-lane exec-mask regions they replaced, for A/B runs)
+            if constexpr (PRED) {
+                if constexpr (decltype(with_b)::value) solve_ground_friction_sel<BOXB>(sc, v, fB, sc.box_m, sc.box_I, LlinBe, LangBe);
+                if constexpr (RB && decltype(with_rb)::value) solve_sel<ROBOT, BOXB>(sc, v, s_rb, sc.mu_rb);
+                if constexpr (decltype(with_d)::value) solve_ground_friction_sel<BOXD>(sc, v, fD, sc.dyn_m, sc.dyn_I, LlinDe, LangDe);
+                if constexpr (RD && decltype(with_rd)::value) solve_sel<ROBOT, BOXD>(sc, v, s_rd, sc.mu_rd);
+            } else {
+                if constexpr (decltype(with_b)::value) solve_ground_friction<BOXB>(sc, v, fB, sc.box_m, sc.box_I, LlinBe, LangBe);
+                if constexpr (RB) {
+                    if (s_rb.on) solve<ROBOT, BOXB>(sc, v, s_rb, sc.mu_rb);
+                }
+                if constexpr (decltype(with_d)::value) solve_ground_friction<BOXD>(sc, v, fD, sc.dyn_m, sc.dyn_I, LlinDe, LangDe);
+                if constexpr (RD && decltype(with_rd)::value) {
+                    if (s_rd.on) solve<ROBOT, BOXD>(sc, v, s_rd, sc.mu_rd);
+                }
             }
         };
         // (a version runs to the end of the substep: the integration of a body whose rows it does not have is skipped
         // with them -- x + h * 0 == x -- without a branch of its own)
-        auto passes = [&](auto with_b, auto with_d, auto with_rd) {
+        auto passes_rb = [&](auto with_b, auto with_d, auto with_rd, auto with_rb) {
             if (sc.iters == 6) {
-                pass(with_b, with_d, with_rd); pass(with_b, with_d, with_rd); pass(with_b, with_d, with_rd);
-                pass(with_b, with_d, with_rd); pass(with_b, with_d, with_rd); pass(with_b, with_d, with_rd);
+                pass(with_b, with_d, with_rd, with_rb); pass(with_b, with_d, with_rd, with_rb); pass(with_b, with_d, with_rd, with_rb);
+                pass(with_b, with_d, with_rd, with_rb); pass(with_b, with_d, with_rd, with_rb); pass(with_b, with_d, with_rd, with_rb);
             } else {
-                for (int it = 0; it < sc.iters; ++it) pass(with_b, with_d, with_rd);
+                for (int it = 0; it < sc.iters; ++it) pass(with_b, with_d, with_rd, with_rb);
             }
             w.rvx = v.rvx; w.rvy = v.rvy;
             w.B.vx = v.bvx; w.B.vy = v.bvy; w.B.w = v.bw;
@@ -730,9 +828,18 @@ __device__ __forceinline__ void point_substep(const PointScene& sc, PointWorld& 
             }
             w.rx = mad(h, w.rvx, w.rx);
             w.ry = mad(h, w.rvy, w.ry);
-            if constexpr (decltype(with_b)::value) integrate_box(w.B, h);
-            if constexpr (decltype(with_d)::value) integrate_box(w.D, h);
+            if constexpr (decltype(with_b)::value) integrate_box<PRED>(w.B, h);
+            if constexpr (decltype(with_d)::value) integrate_box<PRED>(w.D, h);
             M3_PH(4);
+        };
+        // (predicated rows: the robot-box row exists in a version only when a lane of the wave has the contact)
+        auto passes = [&](auto with_b, auto with_d, auto with_rd) {
+            if constexpr (RB && PRED) {
+                if (__builtin_amdgcn_ballot_w64(s_rb.on) != 0ull) passes_rb(with_b, with_d, with_rd, RowOn{});
+                else passes_rb(with_b, with_d, with_rd, RowOff{});
+            } else {
+                passes_rb(with_b, with_d, with_rd, RowOn{});
+            }
         };
         if constexpr (RD) {
             // (the dyn-obs is in reach of the robot: usually no lane touches it, and then a dyn-obs that rests in
@@ -881,7 +988,7 @@ static __device__ unsigned int g_cyc[64 * 16];
 #endif
 
 // one sim.step(): substeps x (forces, detect, solve, integrate)
-template <bool ALL_FORCES>
+template <bool ALL_FORCES, bool LONE = true>
 __device__ __forceinline__ void point_step(const PointScene& sc, PointWorld& w, float ux, float uy,
                                            bool need_dyn_force = true, PhaseClock* pc_ = nullptr) {
     for (int sub = 0; sub < sc.substeps; ++sub) {
@@ -892,15 +999,28 @@ __device__ __forceinline__ void point_step(const PointScene& sc, PointWorld& w, 
             // wave-uniform mask of the pair groups with any lane inside its broad-phase range
             unsigned m = 0u;
 #define M3_NEAR(bit, expr) if (__builtin_amdgcn_ballot_w64(expr) != 0ull) m |= (bit);
+            // Two levels (LONE builds; -DM3_ABL_FLAT_BROAD: nine ballots as in the other builds): the robot-box group on its
+            // own, the other eight first as ONE ballot of their OR -- in the planned rollouts' common case (nothing but the
+            // robot-box pair in range) two scalar round trips instead of nine; only a wave with a lane near one of the
+            // eight looks at them one by one.  Same predicates, same m.
+#ifdef M3_ABL_FLAT_BROAD
+            constexpr bool TWO_LEVEL = false;
+#else
+            constexpr bool TWO_LEVEL = LONE;
+#endif
+            const bool n_rd = near_centres(sc, w.D.x, w.D.y, w.rx, w.ry, sc.robot_r, sc.rad_d);
+            const bool n_ro = near_centres(sc, sc.obs_x, sc.obs_y, w.rx, w.ry, sc.robot_r, sc.rad_o);
+            const bool n_rw = near_walls_disc(sc, w.rx, w.ry);
+            const bool n_bw = near_walls_box(sc, w.B, sc.rad_b);
+            const bool n_dw = near_walls_box(sc, w.D, sc.rad_d);
+            const bool n_bd = near_centres(sc, w.B.x, w.B.y, w.D.x, w.D.y, sc.rad_b, sc.rad_d);
+            const bool n_bo = near_centres(sc, w.B.x, w.B.y, sc.obs_x, sc.obs_y, sc.rad_b, sc.rad_o);
+            const bool n_do = near_centres(sc, w.D.x, w.D.y, sc.obs_x, sc.obs_y, sc.rad_d, sc.rad_o);
             M3_NEAR(G_RB, near_centres(sc, w.B.x, w.B.y, w.rx, w.ry, sc.robot_r, sc.rad_b))
-            M3_NEAR(G_RD, near_centres(sc, w.D.x, w.D.y, w.rx, w.ry, sc.robot_r, sc.rad_d))
-            M3_NEAR(G_RO, near_centres(sc, sc.obs_x, sc.obs_y, w.rx, w.ry, sc.robot_r, sc.rad_o))
-            M3_NEAR(G_RW, near_walls_disc(sc, w.rx, w.ry))
-            M3_NEAR(G_BW, near_walls_box(sc, w.B, sc.rad_b))
-            M3_NEAR(G_DW, near_walls_box(sc, w.D, sc.rad_d))
-            M3_NEAR(G_BD, near_centres(sc, w.B.x, w.B.y, w.D.x, w.D.y, sc.rad_b, sc.rad_d))
-            M3_NEAR(G_BO, near_centres(sc, w.B.x, w.B.y, sc.obs_x, sc.obs_y, sc.rad_b, sc.rad_o))
-            M3_NEAR(G_DO, near_centres(sc, w.D.x, w.D.y, sc.obs_x, sc.obs_y, sc.rad_d, sc.rad_o))
+            if (!TWO_LEVEL || __builtin_amdgcn_ballot_w64(n_rd | n_ro | n_rw | n_bw | n_dw | n_bd | n_bo | n_do) != 0ull) {
+                M3_NEAR(G_RD, n_rd) M3_NEAR(G_RO, n_ro) M3_NEAR(G_RW, n_rw) M3_NEAR(G_BW, n_bw)
+                M3_NEAR(G_DW, n_dw) M3_NEAR(G_BD, n_bd) M3_NEAR(G_BO, n_bo) M3_NEAR(G_DO, n_do)
+            }
 #undef M3_NEAR
 #ifdef M3_ABL_COUNT
             atomicAdd(&g_lvl[m], 1u);   // (every active lane: the tools normalise the histogram)
@@ -913,15 +1033,15 @@ __device__ __forceinline__ void point_step(const PointScene& sc, PointWorld& w, 
 #endif
             // the leanest instance that covers the mask
 #define M3_COVERS(set) ((m & ~(set)) == 0u)
-            if (m == 0u) point_substep<false, 0u>(sc, w, ux, uy, form, pc_);
-            else if (M3_COVERS(G_RB)) point_substep<false, G_RB>(sc, w, ux, uy, form, pc_);
-            else if (M3_COVERS(G_RB | G_RD)) point_substep<false, G_RB | G_RD>(sc, w, ux, uy, form, pc_);
-            else if (M3_COVERS(G_RB | G_RD | G_BD)) point_substep<false, G_RB | G_RD | G_BD>(sc, w, ux, uy, form, pc_);
+            if (m == 0u) point_substep<false, 0u, LONE>(sc, w, ux, uy, form, pc_);
+            else if (M3_COVERS(G_RB)) point_substep<false, G_RB, LONE>(sc, w, ux, uy, form, pc_);
+            else if (M3_COVERS(G_RB | G_RD)) point_substep<false, G_RB | G_RD, LONE>(sc, w, ux, uy, form, pc_);
+            else if (M3_COVERS(G_RB | G_RD | G_BD)) point_substep<false, G_RB | G_RD | G_BD, LONE>(sc, w, ux, uy, form, pc_);
 #ifndef M3_ABL_NO_CORNER
-            else if (M3_COVERS(G_CORNER)) point_substep<false, G_CORNER>(sc, w, ux, uy, form, pc_);
+            else if (M3_COVERS(G_CORNER)) point_substep<false, G_CORNER, LONE>(sc, w, ux, uy, form, pc_);
 #endif
-            else if (M3_COVERS(G_NO_BOX_STATICS)) point_substep<false, G_NO_BOX_STATICS>(sc, w, ux, uy, form, pc_);
-            else point_substep<false, G_ALL>(sc, w, ux, uy, form, pc_);
+            else if (M3_COVERS(G_NO_BOX_STATICS)) point_substep<false, G_NO_BOX_STATICS, LONE>(sc, w, ux, uy, form, pc_);
+            else point_substep<false, G_ALL, LONE>(sc, w, ux, uy, form, pc_);
 #if defined(M3_ABL_COUNT) && defined(M3_ABL_COUNT_CYCLES)
             {
                 const unsigned long long dt_ = wall_clock64() - t0_;

@@ -55,7 +55,8 @@ __device__ __forceinline__ void load_world_from_sim(const float* dof, const floa
 // suction bookkeeping of the tasks that have none and the dyn-obs contact force of the tasks that do not read
 // it disappear from the instance.  Measured at C2: one kernel for everything 0.1555 ms per command, sampler
 // mode compiled in 0.1530, task compiled in as well 0.143 (same results bit for bit: only which code exists).
-template <bool GENERAL, int TASK>
+// LONE: a build for one resident wavefront per SIMD (planar_dyn.hpp: predicated rows, two-level broad phase)
+template <bool GENERAL, int TASK, bool LONE = true>
 __device__ __forceinline__ void rollout_point_body(const RolloutArgs& a_, const PointScene& sc) {
     RolloutArgs a = a_;
     if constexpr (!GENERAL) {
@@ -152,7 +153,7 @@ __device__ __forceinline__ void rollout_point_body(const RolloutArgs& a_, const 
 
         M3_PH(0);
         // ---- A6: one sim.step() ----
-        point_step<false>(sc, w, u0, u1, /*need_dyn_force=*/a.cp.task == 0 || a.cp.avoid_dyn_obs != 0, pc_);
+        point_step<false, LONE>(sc, w, u0, u1, /*need_dyn_force=*/a.cp.task == 0 || a.cp.avoid_dyn_obs != 0, pc_);
 
         // ---- A7/A8: running cost on the post-step state ----
         const float c = point_cost(a.cp, w, k);
@@ -213,7 +214,7 @@ __global__ __launch_bounds__(64) void k_rollout_point_ref(const RolloutArgs a) {
 template <bool GENERAL, int TASK>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_rollout_point_occ2(const RolloutArgs a,
                                                                                                       const PointScene sc) {
-    rollout_point_body<GENERAL, TASK>(a, sc);
+    rollout_point_body<GENERAL, TASK, false>(a, sc);
 }
 // ... and THREE resident waves (170 VGPRs) from four wavefronts per SIMD on: with the fused multiply-adds of spec v1.4 the
 // two-wave build spills only ~60 values, the three-wave build about what the two-wave build used to -- K = 524 288
@@ -221,7 +222,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 template <bool GENERAL, int TASK>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_rollout_point_occ3(const RolloutArgs a,
                                                                                                       const PointScene sc) {
-    rollout_point_body<GENERAL, TASK>(a, sc);
+    rollout_point_body<GENERAL, TASK, false>(a, sc);
 }
 template <bool GENERAL, int TASK>
 inline void launch_rollout_point_instance(const RolloutArgs& a, const PointScene& sc, int blocks, hipStream_t s) {
@@ -247,12 +248,12 @@ __global__ __launch_bounds__(64) void kb_rollout_point_ref(const BatchRolloutEnt
 template <bool GENERAL, int TASK>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void kb_rollout_point_occ2(
     const BatchRolloutEntry* __restrict__ tab) {
-    rollout_point_body<GENERAL, TASK>(tab[blockIdx.y].a, tab[blockIdx.y].sc);
+    rollout_point_body<GENERAL, TASK, false>(tab[blockIdx.y].a, tab[blockIdx.y].sc);
 }
 template <bool GENERAL, int TASK>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void kb_rollout_point_occ3(
     const BatchRolloutEntry* __restrict__ tab) {
-    rollout_point_body<GENERAL, TASK>(tab[blockIdx.y].a, tab[blockIdx.y].sc);
+    rollout_point_body<GENERAL, TASK, false>(tab[blockIdx.y].a, tab[blockIdx.y].sc);
 }
 // blocks: workgroups of ONE handle (all handles of the group have the same); n: handles; ref: the group runs the
 // reference's solver settings

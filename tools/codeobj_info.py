@@ -2,8 +2,10 @@
 rocprofv3's kernel-trace CSV, whose VGPR column is the granulated ARCH count only): per kernel the AMDGPU
 metadata -- .vgpr_count (arch + acc), .agpr_count, .sgpr_count, spills, LDS, scratch -- and, with --isa
 <kernel substring>, the static instruction histogram of that kernel (s_nop, v_mov, v_readlane/v_writelane ...).
+--opcodes <kernel substring> prints the full opcode histogram of the FIRST kernel whose demangled name contains the
+substring (one "count opcode" line each, most frequent first), to set two builds side by side.
 
-    python tools/codeobj_info.py [--isa k_rollout_point] [--json out.json] [lib.so]
+    python tools/codeobj_info.py [--isa k_rollout_point] [--opcodes 'k_rollout_point_ref<false, 1>'] [--json out.json] [lib.so]
 """
 import collections
 import json
@@ -63,23 +65,28 @@ def isa_hist(co, symbol):
 
 
 def main(argv):
-    lib, want_isa, out_json = os.path.join(ROOT, "m3p2i_aip_amd", "lib", "libm3p2i_hip.so"), None, None
+    lib, want_isa, out_json, want_ops = os.path.join(ROOT, "m3p2i_aip_amd", "lib", "libm3p2i_hip.so"), None, None, None
     it = iter(argv)
     for a in it:
         if a == "--isa":
             want_isa = next(it)
+        elif a == "--opcodes":
+            want_ops = next(it)
         elif a == "--json":
             out_json = next(it)
         else:
             lib = a
     tmp, cos = extract(lib)
-    report = {"kernels": [], "isa": {}}
+    report = {"kernels": [], "isa": {}, "opcodes": {}}
     try:
         for co in cos:
             ks = kernels(co)
             for k, d in zip(ks, demangle([k["name"] for k in ks])):
                 k["demangled"] = re.sub(r"\(.*$", "", d)
                 report["kernels"].append(k)
+                if want_ops and want_ops in k["demangled"] and not report["opcodes"]:
+                    n, h = isa_hist(co, k["name"])
+                    report["opcodes"][k["demangled"]] = dict(h.most_common())
                 if want_isa and want_isa in k["demangled"]:
                     n, h = isa_hist(co, k["name"])
                     def pre(*ps):
@@ -103,6 +110,10 @@ def main(argv):
                          k.get("private_segment_fixed_size")))
     for name, g in report["isa"].items():
         print("ISA", name, g)
+    for name, h in report["opcodes"].items():
+        print("OPCODES", name, "total", sum(h.values()), "vgpr", next(k["vgpr_count"] for k in report["kernels"] if k["demangled"] == name))
+        for op, c in h.items():
+            print("%7d %s" % (c, op))
     if out_json:
         json.dump(report, open(out_json, "w"), indent=1)
 
