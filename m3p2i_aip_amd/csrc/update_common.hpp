@@ -583,7 +583,8 @@ __device__ __forceinline__ void search_body(const UpdateArgs& a, SearchOut& out,
             float t = 0.0f;
             for (int r = 0; r < N; ++r) {
                 const float* rec = a.records_all + (size_t)r * a.rec_len;
-                t += m3_exp(nib * (rec[om + sx] - m)) * rec[ot + o];
+                // (a shard whose costs of this set are all +inf has m_r = +inf and NaN sums (inf - inf): no weight)
+                if (rec[om + sx] != INF) t += m3_exp(nib * (rec[om + sx] - m)) * rec[ot + o];
             }
             s_tab[o] = t;
         }

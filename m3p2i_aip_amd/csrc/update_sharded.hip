@@ -442,16 +442,19 @@ __global__ __launch_bounds__(256) void k_mix(const UpdateArgs a) {
     const float* R = a.records_all;
     if (tid == 0) {
         float m = __builtin_inff();
-        int br = 0;
-        for (int r = 0; r < N; ++r) {
-            const float mr = R[(size_t)r * L + 0];
-            if (mr < m) { m = mr; br = r; }  // first rank on ties = lowest sample index
-        }
+        for (int r = 0; r < N; ++r) m = fminf(m, R[(size_t)r * L + 0]);
         const float beta = a.mode_simple ? a.lambda_ : a.info->beta;
         const float nib = -1.0f / beta;
-        float Z = 0.0f;
+        // g_r = the unnormalised global weight of rank r's best sample.  The best rank is the one with the largest g_r,
+        // the first on ties (costs that differ but whose binary32 weights are equal: the lowest index wins, as
+        // torch.argmax over the unsharded weights).  A rank whose costs are all +inf has m_r = +inf, g_r = 0 and a NaN
+        // local softmin (inf - inf): it carries no weight, and none of its sums may enter (0 * NaN).
+        float Z = 0.0f, gbest = -1.0f;
+        int br = 0;
         for (int r = 0; r < N; ++r) {
-            const float sr = m3_exp(nib * (R[(size_t)r * L + 0] - m)) * R[(size_t)r * L + 1];
+            const float g = m3_exp(nib * (R[(size_t)r * L + 0] - m));
+            const float sr = R[(size_t)r * L + 0] == __builtin_inff() ? 0.0f : g * R[(size_t)r * L + 1];   // (a NaN record still poisons)
+            if (g > gbest) { gbest = g; br = r; }
             s_rho[r] = sr;
             Z += sr;
         }
@@ -460,8 +463,10 @@ __global__ __launch_bounds__(256) void k_mix(const UpdateArgs a) {
         float h0 = 0.0f, h1 = 0.0f;
         for (int r = 0; r < N; ++r) {
             s_rho[r] = s_rho[r] * iz;
-            h0 += s_rho[r] * R[(size_t)r * L + 2];
-            h1 += s_rho[r] * R[(size_t)r * L + 3];
+            if (s_rho[r] != 0.0f) {
+                h0 += s_rho[r] * R[(size_t)r * L + 2];
+                h1 += s_rho[r] * R[(size_t)r * L + 3];
+            }
         }
         s_best_rank = br;
         m3_info* f = a.info;
@@ -492,7 +497,8 @@ __global__ __launch_bounds__(256) void k_mix(const UpdateArgs a) {
     const int n = T * nu, br = s_best_rank;
     for (int o = tid; o < n; o += blockDim.x) {
         float acc = 0.0f;
-        for (int r = 0; r < N; ++r) acc += s_rho[r] * R[(size_t)r * L + REC_HDR + reduce_off_psum(0, T, nu) + o];
+        for (int r = 0; r < N; ++r)
+            if (s_rho[r] != 0.0f) acc += s_rho[r] * R[(size_t)r * L + REC_HDR + reduce_off_psum(0, T, nu) + o];
         a.reduce[reduce_off_psum(0, T, nu) + o] = acc;
         a.reduce[reduce_off_best(0, T, nu) + o] = R[(size_t)br * L + REC_HDR + reduce_off_best(0, T, nu) + o];
     }
@@ -520,7 +526,7 @@ __global__ __launch_bounds__(256) void k_mix(const UpdateArgs a) {
     }
     // this rank's weights were normalised by its own eta_r: rescale to the global normalisation
     const float rho = s_rho[a.rank];
-    for (int i = tid; i < a.Kl; i += blockDim.x) a.w[a.k0 + i] *= rho;
+    for (int i = tid; i < a.Kl; i += blockDim.x) a.w[a.k0 + i] = rho != 0.0f ? a.w[a.k0 + i] * rho : 0.0f;
     // ... and the usual finalize on the buffer just formed, in the same launch (one dependent
     // launch less on the critical path after the collective): stores out to L2, then
     // finalize_body reads them back with L2-coherent loads

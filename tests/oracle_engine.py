@@ -157,7 +157,8 @@ class OracleEngine:
         J = n[L.BUF_TRAJ_COST]
         beta = f(c.lambda_ if c.mode_simple else self.beta)
         m_r = J.min()
-        e = np.exp((f(-1.0) / beta) * (J - m_r)).astype(f)
+        with np.errstate(invalid="ignore"):
+            e = np.exp((f(-1.0) / beta) * (J - m_r)).astype(f)
         eta_r = e.sum(dtype=f)
         w = (e * (f(1.0) / eta_r)).astype(f)
         n[L.BUF_WEIGHTS][k0:k1] = w
@@ -165,7 +166,7 @@ class OracleEngine:
         rec = n[L.BUF_RECORD]
         rec[...] = 0
         kk = np.arange(k0, k1)
-        best = int(np.argmin(J))
+        best = int(np.argmax(w))                                    # first index of the largest weight (mppi.py:494)
         rec[0], rec[1] = m_r, eta_r
         rec[2], rec[3] = w[kk < self.Kg // 2].sum(dtype=f), w[kk >= self.Kg // 2].sum(dtype=f)
         rec[4:5] = np.array([k0 + best], np.int32).view(f)
@@ -184,13 +185,19 @@ class OracleEngine:
         N = R.shape[0]
         beta = f(c.lambda_ if c.mode_simple else self.beta)
         m = R[:, 0].min()
-        s = (np.exp((f(-1.0) / beta) * (R[:, 0] - m)).astype(f) * R[:, 1]).astype(f)
-        rho = (s / s.sum(dtype=f)).astype(f)
-        br = int(np.argmin(R[:, 0]))
+        with np.errstate(invalid="ignore"):
+            g = np.exp((f(-1.0) / beta) * (R[:, 0] - m)).astype(f)       # a rank's best sample, unnormalised
+            # (a rank whose costs are all +inf has m_r = +inf and a NaN local softmin: it carries no weight)
+            s = np.where(np.isposinf(R[:, 0]), f(0.0), (g * R[:, 1]).astype(f)).astype(f)
+        Z = s.sum(dtype=f)
+        rho = (s / Z).astype(f)
+        br = int(np.argmax(np.where(g > 0, g, f(-1.0))))                 # largest weight, first rank on ties = lowest index
         red = n[L.BUF_REDUCE]
         red[...] = 0
         B = R[:, self.HDR:]
-        red[:T * nu] = (rho[:, None] * B[:, :T * nu]).sum(axis=0, dtype=f)
+        live = rho != 0
+        with np.errstate(invalid="ignore"):
+            red[:T * nu] = np.where(live[:, None], rho[:, None] * B[:, :T * nu], f(0.0)).sum(axis=0, dtype=f)
         red[3 * T * nu:4 * T * nu] = B[br, 3 * T * nu:4 * T * nu]
         Jc = R[:, 8:28].reshape(-1)
         Ic = R[:, 28:48].copy().view(np.int32).reshape(-1)
@@ -199,14 +206,22 @@ class OracleEngine:
         top = red[6 * T * nu:].reshape(L.TOPK, T, 2)
         for slot, cnd in enumerate(order):
             top[slot] = B[cnd // L.TOPK, 6 * T * nu:].reshape(L.TOPK, T, 2)[cnd % L.TOPK]
-        n[L.BUF_WEIGHTS][self.k0:self.k0 + self.Kl] *= rho[self.k0 // self.Kl]
+            gi = int(Ic[cnd])
+            if not (self.k0 <= gi < self.k0 + self.Kl):   # the top-k samples of other ranks get their global weight too
+                n[L.BUF_WEIGHTS][gi] = f(np.exp((f(-1.0) / beta) * (Jc[cnd] - m))) * (f(1.0) / Z)
+        me = self.k0 // self.Kl
+        own = n[L.BUF_WEIGHTS][self.k0:self.k0 + self.Kl]
+        own[...] = (own * rho[me]) if live[me] else f(0.0)
 
         class _I:
             pass
         i = _I()
-        i.wsum_push = float((rho * R[:, 2]).sum(dtype=f))
-        i.wsum_pull = float((rho * R[:, 3]).sum(dtype=f))
+        with np.errstate(invalid="ignore"):
+            i.wsum_push = float(np.where(live, rho * R[:, 2], f(0.0)).sum(dtype=f))
+            i.wsum_pull = float(np.where(live, rho * R[:, 3], f(0.0)).sum(dtype=f))
         i.beta = float(self.beta)
+        i.eta, i.eta_1, i.eta_2, i.iters, i.iters_1, i.iters_2 = float(Z), 0.0, 0.0, 1, 1, 1
+        i.best_idx, i.best_idx_1, i.best_idx_2 = int(R[br, 4:5].copy().view(np.int32)[0]), -1, -1
         self._info = i
 
     def _update_regen(self):
@@ -234,6 +249,7 @@ class OracleEngine:
         sh = np.minimum(np.arange(1, T + 1), T - 1)
         act = O.assemble_actions(cfg, self.delta_all, n[L.BUF_MEAN][sh], n[L.BUF_MEAN_1][sh], n[L.BUF_MEAN_2][sh],
                                  n[L.BUF_BEST_1][sh], n[L.BUF_BEST_2][sh], 0, Kg)
+        act = (np.float32(cfg.u_scale) * act).astype(np.float32)   # the rollout stores the SCALED controls (mppi.py:297, :313)
         if cfg.sample_null_action:
             act[Kg - 1] = 0.0                     # what the rollout stores for the null sample
         ps = O.partial_sums(cfg, w, w1, w2, act, 0, Kg)
@@ -385,6 +401,16 @@ class OracleEngine:
         if s is not None:
             i.wsum_push, i.wsum_pull, i.beta = s.wsum_push, s.wsum_pull, s.beta
             i.pull_preference = int(s.wsum_pull > s.wsum_push)
+            for field in ("eta", "eta_1", "eta_2", "iters", "iters_1", "iters_2", "best_idx", "best_idx_1", "best_idx_2",
+                          "beta_1", "beta_2"):
+                if hasattr(s, field):
+                    setattr(i, field, getattr(s, field))
+            if self.cfg.multi_modal and not self.mix:
+                i.best_idx_2 = self.Kg // 2 + s.best_idx_2          # global index, as the library reports it
+                J = self.np[L.BUF_TRAJ_COST_ALL] if not self.regen else \
+                    np.ascontiguousarray(self.np[L.BUF_RECORDS_ALL][:, :self.Kl].reshape(-1))
+                i.beta_1 = O.beta_search(J[:self.Kg // 2])[3]        # (the oracle's update_weights does not report them)
+                i.beta_2 = O.beta_search(J[self.Kg // 2:])[3]
         return i
 
     @property

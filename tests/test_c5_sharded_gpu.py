@@ -503,7 +503,8 @@ def test_one_collective_fast_protocol_on_synthetic_costs(Kt, Nt, scale, level):
     as the reference's rule evaluated in float64 on the whole cost vector."""
     from m3p2i_aip_amd import _lib as L
     from m3p2i_aip_amd.engine import HipEngine, make_config
-    from tests.test_update_on_synthetic_costs_gpu import search
+    from tests import update_ref as R
+    from tests.update_f64_checks import search_like_kernel
     kl, Ts = Kt // Nt, 12
     kw = dict(T=Ts, nu=2, multi_modal=True, u_min=[-3, -3], u_max=[3, 3], noise_sigma_diag=[3, 3])
     shards = [HipEngine(make_config(K=Kt, K_local=kl, k_offset=r * kl, shard_mix=level, **kw)) for r in range(Nt)]
@@ -528,10 +529,11 @@ def test_one_collective_fast_protocol_on_synthetic_costs(Kt, Nt, scale, level):
                 shards[0].buffer(buf)[lo:hi].copy_(e.buffer(buf)[lo:hi])
     for buf, JJ, eta, iters in ((L.BUF_WEIGHTS, J, info.eta, info.iters), (L.BUF_WEIGHTS_1, J[:half], info.eta_1, info.iters_1),
                                 (L.BUF_WEIGHTS_2, J[half:], info.eta_2, info.iters_2)):
-        w_ref, eta_ref, beta_ref, it_ref = search(JJ)
-        assert 3.0 <= eta <= 10.0 and abs(iters - it_ref) <= 1, (eta, iters, it_ref)
-        if iters == it_ref:
-            np.testing.assert_allclose(shards[0].buffer(buf).cpu().numpy(), w_ref, rtol=5e-3, atol=1e-7)
+        # (a pass count other than the float64 search's is right only where the deciding eta grazes a bound; the weights are
+        # then compared with the reference that took that decision the other way: update_f64_checks.search_like_kernel)
+        r = search_like_kernel(JJ, iters, f"K {Kt} N {Nt} scale {scale} level {level}")
+        assert 3.0 <= eta <= 10.0, (eta, iters)
+        np.testing.assert_allclose(shards[0].buffer(buf).cpu().numpy(), R.weights_at(JJ, r["beta32"])[0], rtol=5e-3, atol=1e-7)
     if scale != 1.0:     # beyond the 0.9-ladder (64 points) / the 1.2-ladder (32 points): the fallback passes ran
         assert info.iters > (65 if scale < 1.0 else 34), info.iters
     for e in shards[1:]:

@@ -1,0 +1,166 @@
+"""The sharded update protocols against the float64 restatement of the reference (tests/update_ref.py) evaluated on the
+WHOLE cost vector, at shard edges: the sharded twin of tests/test_update_forms_f64_gpu.py.  One process, one GPU, N shard
+handles in lock step, every collective a copy between the handles' buffers (tests/sharded_update_driver.py); the same
+driver runs on the float32 NumPy emulation without a GPU (tests/test_sharded_update_f64_cpu.py).
+
+  kernel / host branch                                          reached by (case ids)
+  k_weights / k_wsum with k_offset != 0, owner-only rows,       gr_* (unequal shards 300 / 251 / 450: offsets 300 and 551)
+    the packed M3_BUF_REDUCE (shard_mix = 0)
+  update_impl mix_mode: k_update_small on the local shard       mix_* with K_local <= 16384 (Panda: <= 4096)
+  update_impl mix_mode: k_weights + k_wsum on the local shard   mix_single_N2_Kl16386_*, mix_panda_N2_Kl4098_*
+  k_mix (single, simple, Panda's persisted beta)                mix_single_*, mix_simple_*, mix_panda_*
+  k_local_topk<16> / <32>, one workgroup                        regen*/p3* with K_local <= 4096 / 4098..8192
+  k_local_topk<16>, several workgroups + stage B                regen1_multi_N2_Kl8194_*, regen1_multi_N2_Kl65538_T9 (no ladder
+                                                                  workgroups); regen2_* / p3_* with Kl8194 / Kl65536 / Kl65538
+  k_local_topk's ladder-table workgroups (registers / memory)   regen2_* / p3_* (K_local <= 8192 / above)
+  regen_finalize, shard_mix = 1: k_mins / k_ladder / k_weights  regen1_*
+    / k_wsum<REGEN> (+ k_finalize: T * nu > 2048)               regen1_multi_N2_Kl40_T1030
+  regen_finalize, shard_mix = 2: k_regen_part / k_regen_done    regen2_* (<2>), regen2_panda_* (<9>); chunk length above
+    (search_body on the mixed tables, topk_merge_records)         K_global = 131072: regen2_multi_N2_Kl65538, regen2_multi_N4_Kl65536
+  search_body's fallback passes over the gathered costs         *_fallback (info.iters beyond the ladder asserted)
+  m3_update_b: k_search's second workgroup, local weights,      p3_*
+    k_wsum into record B; k_p3_done                             p3_* (<2>), p3_panda_* (<9>)
+  refusals: shard_mix = 3 with T * nu > 2048 (m3_create),       test_long_horizons_are_refused_where_documented
+    shard_mix = 2 with T * nu > 2048 (m3_finalize)
+
+Tolerances: those of tests/test_update_forms_f64_gpu.py (its docstring derives them) plus one term for the mixture,
+derived here from the kernels' arithmetic, not from their output.  u = 2^-24.
+A mixed weight is w_k = [e_k / eta_r] * [s_r / Z] with e_k = exp(-(J_k - m_r) / beta), s_r = exp(-(m_r - m) / beta) * eta_r,
+Z = sum_r s_r (k_mix; the ladder-table protocols form eta(beta_j) = sum_r exp(-(m_r - m) / beta_j) * eta_r(beta_j) the same way
+and then evaluate every weight with the global m, beta, eta as the unsharded kernels do).
+ * The exponent x = (J_k - m) / beta is split into x1 = (J_k - m_r) / beta and x2 = (m_r - m) / beta, both >= 0 with
+   x1 + x2 = x: 3u x1 + 3u x2 = 3u |x|, what the unsharded bound already carries, and one more exp (2 ulp = 4u).
+ * eta_r cancels between e_k / eta_r and s_r up to the roundings of 1 / eta_r, the two products and s_r / Z: <= 6u.
+ * Z inherits the local blocked sums' error (inside the 1e-5 the unsharded bound grants eta), the error of every
+   exp(-x2_r): 3u x2_r weighted with s_r / Z <= min(1, K_local exp(-x2_r)), i.e. at most 3u (ln K_local + 1) <= 3u (ln 2^24 + 1),
+   and N - 1 <= 31 sequential additions (<= 32u with the final 1 / Z).
+ Sum, rounded up: extra = (3 (ln 2^24 + 1) + 32 + 16) u = 6.1e-6 relative, added to 2e-5 + 4u|x| on the weights, to 2e-5
+ on the etas and the half sums, and (times the actions' scale) to 1e-5 on the means and the plan -- for k_mix (shard_mix = 1,
+ single and simple mode) and for shard_mix = 2 / 3 (of which only the eta part applies: still an upper bound).  Gather +
+ reduce and shard_mix = 1 multi-modal (regen_finalize: k_mins / k_ladder / k_weights / k_wsum on the gathered costs) form
+ every weight with the unsharded kernels on all K costs: no extra term, the unsharded bounds as they are.
+Every protocol meets every edge of tests/test_sharded_update_f64_cpu.EDGES once (that module's matrix, run here on the
+kernels), except: shift1e8 under a multi-modal search (whole halves tie at their minimum in float32: the search has no
+end, in the reference too), inf24 under shard_mix (K_local >= 20 is required: a 24-sample vector is gather + reduce only),
+mode_inf in single mode (there are no per-mode sets).
+The best sample of the mixture (k_mix) cannot be "the first index of the maximum of the returned weights", which are
+products rounded per rank; it is the first index among the samples whose float32 weight exp(-x) rounds to the maximum's
+value (sharded_update_driver._mix_best).  Everything else -- beta chains bit-equal to `beta32`, grazing decisions by
+search_like_kernel, top-k = argsort(J, stable)[:20] in GLOBAL indices, best rows and top trajectories bit-equal to the
+ranks' own action / state buffers (which for the re-generating protocols are what each rank's rollout stored) -- is as
+in the unsharded module, and every plan buffer, TOP_IDX and m3_info field is bit-identical across the ranks, every call.
+Nothing is skipped; every case asserts what its id claims about its cost vector."""
+import numpy as np
+import pytest
+
+from tests.sharded_update_driver import Case, HipBackend, run_sharded_case
+from tests.test_sharded_update_f64_cpu import CASES as SMALL_CASES
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+P9 = dict(nu=9, T=20)
+CASES = SMALL_CASES + [
+    # ---- gather + reduce ----
+    Case("gr_simple_unequal_300_251_450_3calls", 0, "simple", [300, 251, 450], "s1", calls=3),
+    Case("gr_panda_single_unequal_300_251_450_cycle_3calls", 0, "single", [300, 251, 450], "cycle", calls=3, **P9),
+    Case("gr_single_N2_Kl131072_K262144_T9", 0, "single", [131072, 131072], "lastmin", T=9),
+    Case("gr_single_N3_Kl100_T1030_unfused_finalize", 0, "single", [100, 100, 100], "s1", T=1030),
+    Case("gr_multi_N2_Kl8194_spread1e8_fallback", 0, "multi", [8194, 8194], "s1e8", min_iters=34),
+    Case("gr_multi_N5_negative", 0, "multi", [100] * 5, "neg"),
+    # ---- shard_mix = 1: k_mix, K_local at the local update's dispatch boundaries ----
+    Case("mix_single_N2_Kl2048_offset", 1, "single", [2048, 2048], "offset"),
+    Case("mix_single_N2_Kl2050_negative", 1, "single", [2050, 2050], "neg"),
+    Case("mix_single_N2_Kl4096_stageA", 1, "single", [4096, 4096], "stageA"),
+    Case("mix_single_N2_Kl4098_dupmin", 1, "single", [4098, 4098], "dupmin"),
+    Case("mix_single_N2_Kl8192_spread1e-5", 1, "single", [8192, 8192], "s1e-5"),
+    Case("mix_single_N2_Kl8194_spread1e8", 1, "single", [8194, 8194], "s1e8"),
+    Case("mix_single_N2_Kl16384_argmax_tie", 1, "single", [16384, 16384], "tie"),
+    Case("mix_single_N2_Kl16386_zeros", 1, "single", [16386, 16386], "zeros"),
+    Case("mix_single_N4_Kl65536_K262144_T9", 1, "single", [65536] * 4, "s1", T=9),
+    Case("mix_single_N2_Kl262144_T9_stageB_in_every_rank", 1, "single", [262144] * 2, "stageB", T=9),
+    Case("mix_single_N2_Kl100_T1030", 1, "single", [100, 100], "s1", T=1030),
+    Case("mix_single_N5_inf", 1, "single", [100] * 5, "inf"),
+    Case("mix_simple_N3_3calls", 1, "simple", [100, 100, 100], "s1", calls=3),
+    Case("mix_simple_N32_Kl20_top20_spread", 1, "simple", [20] * 32, "top20_spread"),
+    Case("mix_simple_N3_rank_all_inf", 1, "simple", [40, 40, 40], "rank_inf"),
+    Case("mix_simple_N5_shift1e8", 1, "simple", [30] * 5, "shift1e8"),
+    Case("mix_panda_N3_cycle_3calls", 1, "single", [100, 100, 100], "cycle", calls=3, **P9),
+    Case("mix_panda_N2_Kl4096_cycle_3calls", 1, "single", [4096, 4096], "cycle", calls=3, **P9),
+    Case("mix_panda_N2_Kl4098_cycle_3calls", 1, "single", [4098, 4098], "cycle", calls=3, **P9),
+    Case("mix_panda_N3_rank_all_inf", 1, "single", [40, 40, 40], "rank_inf", **P9),
+    # ---- gather + reduce at the dispatch boundaries of K_global and of the owner's K_local ----
+    Case("gr_single_N2_Kl8192_K16384_argmax_tie", 0, "single", [8192, 8192], "tie"),
+    Case("gr_single_N2_Kl8194_K16388_zeros", 0, "single", [8194, 8194], "zeros"),
+    Case("gr_single_N32_Kl20_top20_spread_T9", 0, "single", [20] * 32, "top20_spread", T=9),
+    Case("gr_multi_N2_Kl2048_K4096_dupmin", 0, "multi", [2048, 2048], "dupmin"),
+    Case("gr_multi_N2_Kl2050_K4100", 0, "multi", [2050, 2050], "lastmin"),
+    Case("gr_multi_N2_Kl4096_K8192_stageA", 0, "multi", [4096, 4096], "stageA"),
+    Case("gr_multi_N2_Kl4098_K8196_edge_tie_in_top20", 0, "multi", [4098, 4098], "edge_in"),
+    Case("gr_multi_N2_Kl65536_K131072_T9", 0, "multi", [65536, 65536], "s1", T=9),
+    Case("gr_multi_N2_Kl65538_K131076_T9_inf", 0, "multi", [65538, 65538], "inf", T=9),
+    Case("gr_panda_multi_N3_Kl40", 0, "multi", [40, 40, 40], "s1", **P9),
+    # ---- shard_mix = 1, multi-modal: the unsharded kernels on the gathered costs, actions re-generated ----
+    Case("regen1_multi_N2_Kl4096_K8192", 1, "multi", [4096, 4096], "s1"),
+    Case("regen1_multi_N2_Kl4098", 1, "multi", [4098, 4098], "dupmin"),
+    Case("regen1_multi_N2_Kl40_T1030_unfused_finalize", 1, "multi", [40, 40], "s1", T=1030),
+    Case("regen1_multi_N2_Kl2048_K4096", 1, "multi", [2048, 2048], "lastmin"),
+    Case("regen1_multi_N2_Kl2050", 1, "multi", [2050, 2050], "dup2ranks"),
+    Case("regen1_multi_N2_Kl8192_negative", 1, "multi", [8192, 8192], "neg"),
+    Case("regen1_multi_N2_Kl8194_inf", 1, "multi", [8194, 8194], "inf"),
+    Case("regen1_multi_N2_Kl65536_K131072_T9", 1, "multi", [65536, 65536], "s1", T=9),
+    Case("regen1_multi_N2_Kl65538_T9", 1, "multi", [65538, 65538], "s1", T=9),
+    Case("regen1_panda_multi_N3_Kl40", 1, "multi", [40, 40, 40], "s1", **P9),
+    Case("regen1_panda_multi_N3_no_null_action", 1, "multi", [40, 40, 40], "s1", null_action=False, **P9),
+    Case("regen2_panda_multi_N3_no_null_action", 2, "multi", [40, 40, 40], "s1", null_action=False, **P9),
+    Case("regen2_panda_multi_N3_mode_inf", 2, "multi", [40, 40, 40], "mode_inf", **P9),
+    Case("p3_panda_multi_N3_mode_inf", 3, "multi", [40, 40, 40], "mode_inf", **P9),
+    # ---- shard_mix = 2 ----
+    Case("regen2_multi_N2_Kl2048_K4096", 2, "multi", [2048, 2048], "lastmin"),
+    Case("regen2_multi_N2_Kl2050", 2, "multi", [2050, 2050], "dup2ranks"),
+    Case("regen2_multi_N2_Kl4096_K8192_stageA", 2, "multi", [4096, 4096], "stageA"),
+    Case("regen2_multi_N2_Kl4098_edge_tie_in_top20", 2, "multi", [4098, 4098], "edge_in"),
+    Case("regen2_multi_N2_Kl8192_negative", 2, "multi", [8192, 8192], "neg"),
+    Case("regen2_multi_N2_Kl8194_inf", 2, "multi", [8194, 8194], "inf"),
+    Case("regen2_multi_N2_Kl65536_K131072_T9", 2, "multi", [65536, 65536], "s1", T=9),
+    Case("regen2_multi_N2_Kl65538_T9", 2, "multi", [65538, 65538], "s1", T=9),
+    Case("regen2_multi_N4_Kl65536_K262144_T9", 2, "multi", [65536] * 4, "s1", T=9),
+    Case("regen2_multi_N3_cov_noop_3calls", 2, "multi", [40, 40, 40], "s1", calls=3, cov=True),
+    Case("regen2_panda_multi_N3_Kl40", 2, "multi", [40, 40, 40], "s1", **P9),
+    Case("regen2_panda_multi_N3_rank_all_inf", 2, "multi", [40, 40, 40], "rank_inf", **P9),
+    # ---- shard_mix = 3 ----
+    Case("p3_multi_N2_Kl2048_K4096", 3, "multi", [2048, 2048], "lastmin"),
+    Case("p3_multi_N2_Kl2050", 3, "multi", [2050, 2050], "dup2ranks"),
+    Case("p3_multi_N2_Kl4096_stageA", 3, "multi", [4096, 4096], "stageA"),
+    Case("p3_multi_N2_Kl4098_edge_tie_in_top20", 3, "multi", [4098, 4098], "edge_in"),
+    Case("p3_multi_N2_Kl65538_T9", 3, "multi", [65538, 65538], "s1", T=9),
+    Case("p3_multi_N2_Kl8192_top20_one_rank", 3, "multi", [8192, 8192], "top20_one_rank"),
+    Case("p3_multi_N2_Kl8194_spread1e-5_fallback", 3, "multi", [8194, 8194], "s1e-5", min_iters=65),
+    Case("p3_multi_N5_shift1e3", 3, "multi", [24] * 5, "shift1e3"),
+    Case("p3_multi_N4_Kl65536_K262144_T9", 3, "multi", [65536] * 4, "s1", T=9),
+    Case("p3_panda_multi_N3_Kl40", 3, "multi", [40, 40, 40], "s1", **P9),
+    Case("p3_panda_multi_N3_rank_all_inf", 3, "multi", [40, 40, 40], "rank_inf", **P9),
+]
+assert len({c.id for c in CASES}) == len(CASES)
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
+def test_sharded_update_against_float64_reference(case):
+    run_sharded_case(HipBackend(), case, seed=sum(map(ord, case.id)))
+
+
+def test_long_horizons_are_refused_where_documented():
+    """T * nu > 2048: shard_mix = 3 is refused by m3_create, shard_mix = 2 by m3_finalize (shard_mix = 0 / 1 take the unfused
+    finalize: gr_single_N3_Kl100_T1030_unfused_finalize, regen1_multi_N2_Kl40_T1030_unfused_finalize; k_mix always runs the
+    finalize in its own launch: mix_single_N2_Kl100_T1030 only shows that it does so at that size)."""
+    from m3p2i_aip_amd import _lib as L
+    from m3p2i_aip_amd.engine import HipEngine, make_config
+    kw = dict(K=80, K_local=40, k_offset=0, T=1030, nu=2, multi_modal=True, u_min=[-3, -3], u_max=[3, 3], noise_sigma_diag=[3, 3])
+    with pytest.raises(L.M3Error):
+        HipEngine(make_config(shard_mix=3, **kw))
+    e = HipEngine(make_config(shard_mix=2, **kw))
+    try:
+        with pytest.raises(L.M3Error):
+            e.finalize()
+    finally:
+        e.close()

@@ -40,17 +40,10 @@ step), and the comparison continues against the reference with that one decision
 import numpy as np
 import pytest
 
-from tests import update_ref as R
+from tests.update_f64_checks import check_call, make_costs, new_state
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
-
-U32 = 2.0 ** -24
-
-
-def _sg_gain():
-    import scipy.signal
-    return max(np.abs(np.array([scipy.signal.savgol_coeffs(9, 2, pos=p, use="dot") for p in range(9)])).sum(1))
 
 
 # (id, K, T, nu, mode, dist, entry, calls, update_cov): the form each is meant to reach is in the id
@@ -119,108 +112,6 @@ CASES = [
 ]
 
 
-def stage_a_layout(K):
-    """Costs that overflow top-k stage A's candidate list (TK_CAP = 1024) in every 4096-cost workgroup, all distinct:
-    local index i = e * 256 + tid (tid = 64 * wave + lane, e < 16 register rows) holds lane * 1e-3 + e * 1e-5 +
-    wave * 1e-6 (+ 0.1 per workgroup).  Each wave's threshold is its lanes' 20th smallest minimum, lane 19's
-    row 0; every cost of lanes 0..18 lies below it: 19 * 16 * 4 > 1024 survivors."""
-    i = np.arange(K)
-    blk, loc = i // 4096, i % 4096
-    e, tid = loc // 256, loc % 256
-    return (0.1 * blk + (tid % 64) * 1e-3 + e * 1e-5 + (tid // 64) * 1e-6).astype(np.float32)
-
-
-def stage_a_survivors(J):
-    """What the kernel's stage A keeps of the first workgroup (update_common.hpp: topk_stage_a), counted on the host."""
-    blk = np.full(4096, np.inf, np.float32)
-    blk[:min(4096, len(J))] = J[:4096]
-    rv = blk.reshape(16, 4, 64)                  # [row e][wave][lane]
-    lane_min = rv.min(axis=0)                    # [wave][lane]
-    tau = np.sort(lane_min, axis=1)[:, 19].min()
-    return int((blk <= tau).sum())
-
-
-def make_costs(dist, K, rng, call=0):
-    a = np.abs(rng.standard_normal(K))
-    if dist == "s1":
-        return a.astype(np.float32)
-    if dist in ("s1e-5", "s1e8"):
-        return (float("1" + dist[2:]) * a).astype(np.float32)
-    if dist == "cycle":   # Panda: eta > 20 and < 10 in turn, so the beta step goes both ways
-        return ((1.0, 1e3, 0.03)[call % 3] * a).astype(np.float32)
-    if dist == "offset":
-        return (1e6 + rng.uniform(0, 1, K)).astype(np.float32)
-    if dist == "neg":
-        return (-50.0 - 3.0 * rng.standard_normal(K)).astype(np.float32)
-    J = a.astype(np.float32) + np.float32(0.5)
-    if dist == "dupmin":   # the minimum twice, on both sides of a 4096-sample workgroup boundary (of each half)
-        for p in ((4095, 4096) if K > 4096 else (K // 3, K - 2)):
-            J[p] = -1.0
-        if K // 2 + 4097 < K:
-            J[K // 2 + 4095] = J[K // 2 + 4096] = -1.0
-        return J
-    if dist == "tie":      # distinct costs whose float32 weights are equal: the first index of the max wins (3 and
-        h = K // 2         # 3 + 256 share a thread in every form, 9 is another thread's)
-        for base in (0, h):
-            J[base + 3], J[base + (259 if h > 300 else 5)], J[base + 9] = 3e-9, 1e-9, 0.0
-        return J
-    if dist == "zeros":    # -0.0 and +0.0 (equal costs, ordered by index), three per half
-        h = K // 2
-        for base in (0, h):
-            J[base + 2], J[base + 7], J[base + min(h - 1, 20)] = 0.0, -0.0, 0.0
-        J[1] = -0.0
-        return J
-    if dist == "inf":
-        J[rng.choice(K, 5, replace=False)] = np.inf
-        return J
-    if dist == "inf24":    # more than 4 of 24 at +inf: the top-20 holds +inf rows
-        J[[1, 4, 9, 13, 17, 22]] = np.inf
-        return J
-    if dist == "stageA":
-        J = stage_a_layout(K)
-        assert stage_a_survivors(J) > 1024
-        return J
-    if dist == "stageB":   # every workgroup: 19 copies of F and 40 of C > F at its 20th place; the lists' first elements
-        # are all F, so > 1024 of the 64 x 20 candidates pass stage B's bounds
-        J = (10.0 + a).astype(np.float32)
-        for b in range(K // 4096):
-            pos = b * 4096 + rng.choice(4096, 59, replace=False)
-            J[pos[:19]] = 1.0
-            J[pos[19:]] = 2.0
-        return J
-    raise ValueError(dist)
-
-
-def check_weights(w, J, beta, what):
-    """w (kernel, float32) against the float64 weights at `beta` with the bound of the module docstring."""
-    w_ref, eta_ref = R.weights_at(J, beta)
-    J64 = J.astype(np.float64)
-    with np.errstate(invalid="ignore"):
-        x = np.abs(J64 - J64.min()) / beta
-    big = w_ref >= 1e-30
-    err = np.abs(w.astype(np.float64) - w_ref)
-    bad = big & (err > (2e-5 + 4 * U32 * np.where(big, x, 0.0)) * w_ref)
-    assert not bad.any(), f"{what}: {int(bad.sum())} weights off, first at {np.flatnonzero(bad)[:5]}: " \
-                          f"{w[bad][:3]} vs {w_ref[bad][:3]}"
-    assert np.all(err[~big] <= 1e-30), f"{what}: tiny weights off by {err[~big].max()}"
-    return w_ref, eta_ref
-
-
-def search_like_kernel(JJ, iters, what):
-    """The float64 search of m3p2i.py:24-44; if the kernel made a different number of passes, the deciding pass must
-    graze 3 or 10 and the reference is re-run with that decision reversed."""
-    r = R.update_infinite_beta(JJ - JJ.astype(np.float64).min(), 1.0, 10, 3)
-    if r["iters"] != iters:
-        p = min(r["iters"], iters)
-        eta_p = r["etas"][p - 1]
-        assert min(abs(eta_p - 3.0) / 3.0, abs(eta_p - 10.0) / 10.0) <= 1e-5, \
-            f"{what}: {iters} passes, reference {r['iters']}, eta at pass {p} = {eta_p!r}"
-        r = R.update_infinite_beta(JJ - JJ.astype(np.float64).min(), 1.0, 10, 3, flip_at=p)
-        assert r["iters"] == iters, (what, iters, r["iters"])
-    assert abs(r["beta32"] - r["beta"]) <= r["iters"] * U32 * r["beta"] * 1.01
-    return r
-
-
 def run_case(K, T, nu, mode, dist, entry, calls, cov, seed):
     from m3p2i_aip_amd import _lib as L
     from m3p2i_aip_amd.engine import HipEngine, make_config
@@ -234,14 +125,10 @@ def run_case(K, T, nu, mode, dist, entry, calls, cov, seed):
         if entry == "five":
             eng.set_update_launches(5)
         rng = np.random.default_rng(seed)
-        half = K // 2
         ss = float(eng.cfg.step_size_mean)
-        sg_gain = _sg_gain()
         mean = rng.uniform(-1, 1, (T, nu)).astype(np.float32)
         eng.buffer(L.BUF_MEAN).copy_(torch.from_numpy(mean))
-        mean_ref = mean.astype(np.float64)
-        beta64, beta32 = 1.0, np.float32(1.0)
-        cov_ref = np.array(list(eng.cfg.noise_sigma_diag)[:nu], np.float64)
+        st = new_state(mean, list(eng.cfg.noise_sigma_diag)[:nu])
         for call in range(calls):
             J = make_costs(dist, K, rng, call)
             A = rng.uniform(-3, 3, (T, K, nu)).astype(np.float32)
@@ -255,90 +142,8 @@ def run_case(K, T, nu, mode, dist, entry, calls, cov, seed):
             else:
                 eng.update_finalize()
             torch.cuda.synchronize()
-            info = eng.info()
-            out = {b: eng.buffer(b).cpu().numpy() for b in (L.BUF_WEIGHTS, L.BUF_MEAN, L.BUF_ACTION_OUT, L.BUF_TOP_IDX,
-                                                             L.BUF_TOP_TRAJS, L.BUF_BEST, L.BUF_COV)}
-            Akt = A.transpose(1, 0, 2)                         # [K, T, nu] (reference layout)
-            tag = f"call {call}"
-            w = out[L.BUF_WEIGHTS]
-            # ---- weights, eta, beta, iters ----
-            if mode == "multi":
-                r = [search_like_kernel(J, info.iters, tag + " all"),
-                     search_like_kernel(J[:half], info.iters_1, tag + " mode 1"),
-                     search_like_kernel(J[half:], info.iters_2, tag + " mode 2")]
-                assert np.float32(info.beta_1) == np.float32(r[1]["beta32"]) and \
-                    np.float32(info.beta_2) == np.float32(r[2]["beta32"]), (info.beta_1, info.beta_2, r[1]["beta32"], r[2]["beta32"])
-                w1, w2 = eng.buffer(L.BUF_WEIGHTS_1).cpu().numpy(), eng.buffer(L.BUF_WEIGHTS_2).cpu().numpy()
-                wr, er = check_weights(w, J, r[0]["beta32"], tag + " weights")
-                w1r, e1r = check_weights(w1, J[:half], r[1]["beta32"], tag + " weights_1")
-                w2r, e2r = check_weights(w2, J[half:], r[2]["beta32"], tag + " weights_2")
-                for got, want in ((info.eta, er), (info.eta_1, e1r), (info.eta_2, e2r)):
-                    assert abs(got - want) <= 2e-5 * want, (tag, got, want)
-                assert np.float32(info.beta) == np.float32(1.0)          # the persistent beta is never written
-            else:
-                b_used = (float(eng.cfg.lambda_) if mode == "simple" else float(beta32))
-                wr, er = check_weights(w, J, b_used, tag + " weights")
-                assert abs(info.eta - er) <= 2e-5 * er, (tag, info.eta, er)
-                if mode == "single":
-                    # mppi.py:446-454: panda_env adapts beta after use; point_env keeps it
-                    _, eta64, nb64 = R.exp_util(J, beta64, panda)
-                    step = nb64 / beta64
-                    if panda and (abs(eta64 - 20) <= 2e-5 * 20 or abs(eta64 - 10) <= 2e-5 * 10):
-                        step = info.beta / float(beta32)               # a grazing eta: either side is right
-                    beta64 *= step
-                    beta32 = np.float32(beta32 * np.float32(step)) if step != 1.0 else beta32
-                    assert np.float32(info.beta) == beta32, (tag, info.beta, beta32)
-                    assert abs(beta64 - float(beta32)) <= (call + 1) * 2 * U32 * beta64
-            # ---- argmax (first index of the max of the returned weights), best rows ----
-            bi = R.argmax_first(w)
-            assert info.best_idx == bi, (tag, info.best_idx, bi)
-            assert wr[bi] >= wr.max() * (1 - 1e-6)
-            if mode == "multi":
-                b1, b2 = R.argmax_first(w1), half + R.argmax_first(w2)
-                assert (info.best_idx_1, info.best_idx_2) == (b1, b2), (tag, info.best_idx_1, info.best_idx_2, b1, b2)
-                assert w1r[b1] >= w1r.max() * (1 - 1e-6) and w2r[b2 - half] >= w2r.max() * (1 - 1e-6)
-                assert np.array_equal(eng.buffer(L.BUF_BEST_1).cpu().numpy(), A[:, b1])
-                assert np.array_equal(eng.buffer(L.BUF_BEST_2).cpu().numpy(), A[:, b2])
-            elif mode == "single":
-                assert np.array_equal(out[L.BUF_BEST], A[:, bi])
-            # ---- sums of the halves, pull preference (m3p2i.py:16-21) ----
-            hp, hq = wr[:half].sum(), wr[half:].sum()
-            assert abs(info.wsum_push - hp) <= 2e-5 and abs(info.wsum_pull - hq) <= 2e-5, (tag, info.wsum_push, hp, info.wsum_pull, hq)
-            assert info.pull_preference == int(info.wsum_pull > info.wsum_push)
-            if abs(hq - hp) > 1e-4:
-                assert info.pull_preference == R.pull_preference(wr, half)
-            # ---- top-k: the 20 largest reference weights, and the project's rule (ascending J, ties by index,
-            # -0.0 == +0.0, as torch.argsort(J, stable=True)) ----
-            ti = out[L.BUF_TOP_IDX].astype(np.int64)
-            assert np.all((ti >= 0) & (ti < K)), ti
-            _, vals = R.topk(wr)
-            np.testing.assert_allclose(wr[ti], vals, rtol=1e-12, atol=0, err_msg=tag + " top-k weights")
-            assert np.all(np.diff(wr[ti]) <= 0)
-            want_ti = np.argsort(J, kind="stable")[:R.TOPK]
-            assert np.array_equal(ti, want_ti), (tag, ti, want_ti)
-            np.testing.assert_array_equal(out[L.BUF_TOP_TRAJS], S[:, ti][:, :, [0, 2]].transpose(1, 0, 2))
-            # ---- means, filtered plan, covariance ----
-            scale = float(np.abs(A).max())
-            if mode == "simple":
-                noise = Akt.astype(np.float64) - np.roll(mean_ref, -1, axis=0)[None]
-                s = R.simple_update(J, noise, mean_ref, float(eng.cfg.lambda_))
-                mean_ref = s["U"]
-            elif mode == "multi":
-                m = R.update_multi_modal_distribution([dict(w=wr), dict(w=w1r), dict(w=w2r)], Akt, R.shift_action(mean_ref), ss, half)
-                np.testing.assert_allclose(eng.buffer(L.BUF_MEAN_1).cpu().numpy(), m["mean_1"], rtol=0, atol=1e-5 * scale, err_msg=tag)
-                np.testing.assert_allclose(eng.buffer(L.BUF_MEAN_2).cpu().numpy(), m["mean_2"], rtol=0, atol=1e-5 * scale, err_msg=tag)
-                mean_ref = m["mean"]
-            else:
-                m = R.update_distribution(wr, Akt, R.shift_action(mean_ref), ss, cov_ref if cov else None)
-                mean_ref = m["mean"]
-                if cov:
-                    cov_ref = m["cov"]
-                    c = out[L.BUF_COV]
-                    np.testing.assert_allclose(c[0], m["cov"], rtol=0, atol=1e-5 * m["cov"].max(), err_msg=tag + " cov")
-                    np.testing.assert_allclose(c[1], m["scale_tril"], rtol=0, atol=1e-5 * m["scale_tril"].max(), err_msg=tag + " scale_tril")
-            np.testing.assert_allclose(out[L.BUF_MEAN], mean_ref, rtol=0, atol=1e-5 * scale, err_msg=tag + " mean")
-            np.testing.assert_allclose(out[L.BUF_ACTION_OUT], R.savgol(mean_ref), rtol=0, atol=sg_gain * 1e-5 * scale,
-                                       err_msg=tag + " action_out")
+            check_call(L, lambda b: eng.buffer(b).cpu().numpy(), eng.info(), J, A, S, st, K=K, nu=nu, mode=mode, cov=cov,
+                       lambda_=float(eng.cfg.lambda_), ss=ss, call=call)
     finally:
         eng.close()
 
