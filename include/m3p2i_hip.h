@@ -525,6 +525,53 @@ int m3_episodes_running(const m3_episodes* eps);   /* episodes not ended as of t
 void m3_episodes_destroy(m3_episodes* eps);
 const char* m3_episodes_last_error(const m3_episodes* eps);   /* eps may be NULL: the last failed create on this thread */
 
+/* ---- batched closed-loop episodes (panda_env): N reactive pick-and-place episodes in lockstep -----
+ * world: a sim_only panda_env handle with K_local == n and bound views, row e the 1-env world of episode e, planned by
+ * planners[e].  The task planner stays on the host and decides per tick, so a tick is TWO calls with the host in between:
+ *   m3_panda_episodes_observe: the pre kernel -- per running episode, row e of the world's views advanced by one step of
+ *     the planner's own simulator (under the targets that simulator kept since tick 0) into row e of the set's planning
+ *     view (dof, root and rigid-body state) -- then ONE copy of the planning view's rigid-body rows to pinned host memory
+ *     (*rb_host: [n][17][13] floats, valid until the next observe) and one synchronisation;
+ *   the host: its n task planners on those rows, m3_set_objective on every planner that goes on, ended[e] != 0 for every
+ *     episode whose task is done at this tick;
+ *   m3_panda_episodes_act: every running, not-ended planner bound (m3_bind_sim_panda) to its row of the planning view, ONE
+ *     m3_batch_command, the post kernel (running: trace row, step under row 0 of the planner's action-out; ended: up to
+ *     settle_ticks steps under zero targets, one per tick, after which its row of the world is not stepped any more -- the
+ *     cubeA / cubeB positions of the status are frozen from there on; an episode
+ *     still running at tick max_ticks - 1 ends unsuccessful after that step).  No synchronisation.
+ * Tick 0 is the caller's (each planner's first command is the fused / step probe on its own simulator):
+ * m3_panda_episodes_act_first launches no command; sims[e] is planner e's K-env simulator handle, whose kept velocity
+ * targets of row 0 become episode e's for every later observe.
+ * m3_panda_episodes_create refuses, before any launch and leaving every handle as it was: a world that is not a sim_only
+ * panda_env handle with bound views or whose K_local differs from n (M3_ERR_STATE), a point_env planner
+ * (M3_ERR_UNSUPPORTED), a planner m3_batch_command would refuse (its code), a handle on another stream or device than the
+ * world's, a handle listed twice, a planner without an action-out destination, n <= 0, max_ticks <= 0, settle_ticks < 0.
+ * All device and pinned memory comes from create; observe / act allocate nothing. */
+typedef struct {
+    int phase;           /* 0 running, 1 ended and settling, 2 ended and settled: cubeA / cubeB are valid */
+    int done_tick;       /* -1 while running; else the success tick or max_ticks - 1 */
+    int success;
+    int settle_left;     /* settle steps still to take */
+    float cubeA[3];      /* rigid-body position of cubeA / cubeB in the episode's row of the world, f32: filled by */
+    float cubeB[3];      /* m3_panda_episodes_status; with phase 2 the positions after the episode's last step, for good */
+} m3_panda_episode_status;
+#define M3_PANDA_EPISODE_TRACE_FLOATS 132   /* dof_state 18 | root_state 91 | action 9 | panda_hand pose 7 | cubeA body pose 7 */
+typedef struct m3_panda_episodes m3_panda_episodes;
+int m3_panda_episodes_create(m3_handle* world, m3_handle* const* planners, int n, int max_ticks, int settle_ticks, int trace,
+                             m3_panda_episodes** out);
+int m3_panda_episodes_observe(m3_panda_episodes* eps, const float** rb_host);
+int m3_panda_episodes_act(m3_panda_episodes* eps, m3_batch* batch, const int* ended_host /* [n] */);
+int m3_panda_episodes_act_first(m3_panda_episodes* eps, m3_handle* const* sims /* [n] */, const int* ended_host /* [n] */);
+/* status_out [n] (host); trace_out (host, may be NULL) [max_ticks][n][M3_PANDA_EPISODE_TRACE_FLOATS], rows of ticks an
+ * episode did not step while running are undefined.  Synchronises; not between observe and act (it reuses the pinned
+ * host copy, which also ends the validity of the last observe's rows). */
+int m3_panda_episodes_status(m3_panda_episodes* eps, m3_panda_episode_status* status_out, float* trace_out);
+int m3_panda_episodes_ticks_done(const m3_panda_episodes* eps);
+int m3_panda_episodes_running(const m3_panda_episodes* eps);   /* episodes the host has not ended (host mirror, no synchronisation) */
+int m3_panda_episodes_active(const m3_panda_episodes* eps);    /* ... plus those still settling */
+void m3_panda_episodes_destroy(m3_panda_episodes* eps);
+const char* m3_panda_episodes_last_error(const m3_panda_episodes* eps);   /* eps may be NULL: the last failed create on this thread */
+
 int m3_get_buffer(m3_handle* h, int which, void** dev_ptr, long long* nbytes);
 int m3_reduce_len(const m3_handle* h);
 int m3_record_len(const m3_handle* h);

@@ -73,6 +73,17 @@ class EpisodeStatus(C.Structure):
 SUCTION_OFF, SUCTION_ON, SUCTION_PULL_PREFERENCE = 0, 1, 2
 
 
+class PandaEpisodeStatus(C.Structure):
+    _fields_ = [("phase", C.c_int), ("done_tick", C.c_int), ("success", C.c_int), ("settle_left", C.c_int),
+                ("cubeA", C.c_float * 3), ("cubeB", C.c_float * 3)]
+
+
+PE_RUNNING, PE_SETTLING, PE_FROZEN = 0, 1, 2
+PANDA_EPISODE_TRACE_FLOATS = 132
+# offsets inside a trace row: dof_state 18 | root_state 91 | action 9 | panda_hand pose 7 | cubeA body pose 7
+PE_TR_DOF, PE_TR_ROOT, PE_TR_ACTION, PE_TR_HAND, PE_TR_CUBE = 0, 18, 109, 118, 125
+
+
 class Timing(C.Structure):
     _fields_ = [("rollout_ms", C.c_float), ("update_ms", C.c_float),
                 ("finalize_ms", C.c_float), ("total_ms", C.c_float)]
@@ -154,6 +165,16 @@ SYMBOLS = [
     ("m3_episodes_running", C.c_int, [_H]),
     ("m3_episodes_destroy", None, [_H]),
     ("m3_episodes_last_error", C.c_char_p, [_H]),
+    ("m3_panda_episodes_create", C.c_int, [_H, C.POINTER(_H), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
+    ("m3_panda_episodes_observe", C.c_int, [_H, C.POINTER(C.POINTER(C.c_float))]),
+    ("m3_panda_episodes_act", C.c_int, [_H, _H, C.POINTER(C.c_int)]),
+    ("m3_panda_episodes_act_first", C.c_int, [_H, C.POINTER(_H), C.POINTER(C.c_int)]),
+    ("m3_panda_episodes_status", C.c_int, [_H, C.POINTER(PandaEpisodeStatus), C.c_void_p]),
+    ("m3_panda_episodes_ticks_done", C.c_int, [_H]),
+    ("m3_panda_episodes_running", C.c_int, [_H]),
+    ("m3_panda_episodes_active", C.c_int, [_H]),
+    ("m3_panda_episodes_destroy", None, [_H]),
+    ("m3_panda_episodes_last_error", C.c_char_p, [_H]),
     ("m3_get_buffer", C.c_int, [_H, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]),
     ("m3_reduce_len", C.c_int, [_H]),
     ("m3_record_len", C.c_int, [_H]),

@@ -12,6 +12,7 @@
 #include <new>
 
 #include "m3_internal.hpp"
+#include "panda_episode_lane.hpp"
 
 using namespace m3;
 
@@ -2241,5 +2242,292 @@ extern "C" int m3_episodes_status(m3_episodes* eps, m3_episode_status* status_ou
                                  hipMemcpyDeviceToHost, s));
     }
     HIPCHK(eps, hipStreamSynchronize(s));
+    return M3_OK;
+}
+
+// ---------------------------------- batched closed-loop episodes, panda_env ------------------------------------
+// N reactive pick-and-place episodes of tools/closed_loop.run in lockstep.  The task planner stays on the
+// host, so a tick is two calls: m3_panda_episodes_observe (pre kernel, one copy, one synchronisation), the host's task
+// planners, m3_panda_episodes_act (bind, one batched command, post kernel; no synchronisation).
+static thread_local std::string g_peps_err;
+
+struct m3_panda_episodes {
+    m3_handle* world = nullptr;
+    int n = 0, max_ticks = 0, settle_ticks = 0, tick = 0;
+    bool observed = false;           // between observe and act
+    std::string err;
+    std::vector<m3_handle*> planners;
+    std::vector<const float*> plan;  // each planner's action-out, fixed at create
+    std::vector<m3_handle*> live;    // scratch: this tick's batch
+    std::vector<m3_panda_episode_status> mirror;   // the device's status words, advanced on the host by the same pe_advance
+    char* dev = nullptr;             // status | plan pointers | kept targets | ended | planning view: dof, root, rigid bodies
+    float* trace = nullptr;
+    char* pinned = nullptr;          // rigid-body rows of the planning view | ended
+    size_t rb_bytes = 0;
+    int* ended_pinned = nullptr;
+    int* ended_dev = nullptr;
+    float* kept_dev = nullptr;
+    m3::PandaEpisodeArgs args{};
+};
+
+extern "C" const char* m3_panda_episodes_last_error(const m3_panda_episodes* eps) {
+    return eps ? eps->err.c_str() : g_peps_err.c_str();
+}
+
+extern "C" void m3_panda_episodes_destroy(m3_panda_episodes* eps) {
+    if (!eps) return;
+    if (eps->world) (void)hipStreamSynchronize(eps->world->stream);   // (kernels may still use the memory)
+    if (eps->dev) (void)hipFree(eps->dev);
+    if (eps->trace) (void)hipFree(eps->trace);
+    if (eps->pinned) (void)hipHostFree(eps->pinned);
+    delete eps;
+}
+
+static int peps_refuse(int code, int i, const std::string& msg) {
+    char head[64];
+    if (i >= 0) std::snprintf(head, sizeof(head), "m3_panda_episodes_create: planner %d: ", i);
+    else std::snprintf(head, sizeof(head), "m3_panda_episodes_create: ");
+    g_peps_err = std::string(head) + msg;
+    return code;
+}
+
+extern "C" int m3_panda_episodes_create(m3_handle* world, m3_handle* const* planners, int n, int max_ticks, int settle_ticks,
+                                        int trace, m3_panda_episodes** out) {
+    if (!out) return peps_refuse(M3_ERR_BAD_ARG, -1, "null argument");
+    *out = nullptr;
+    // ---- every check before any allocation or launch ----
+    if (!world || !planners) return peps_refuse(M3_ERR_BAD_ARG, -1, "null argument");
+    if (n <= 0 || n > 65535) return peps_refuse(M3_ERR_BAD_ARG, -1, "n must be in 1 .. 65535");
+    if (max_ticks <= 0) return peps_refuse(M3_ERR_BAD_ARG, -1, "max_ticks must be > 0");
+    if (settle_ticks < 0) return peps_refuse(M3_ERR_BAD_ARG, -1, "settle_ticks must be >= 0");
+    const m3_config& wc = world->cfg;
+    if (wc.env_type != M3_ENV_PANDA || !wc.sim_only || !world->views_bound || !world->sim_world || !world->views.dof_state ||
+        !world->views.root_state || !world->views.rigid_body_state)
+        return peps_refuse(M3_ERR_STATE, -1, "the world must be a sim_only panda_env handle with its views bound");
+    if (wc.K_local != n || wc.K_global != n) return peps_refuse(M3_ERR_STATE, -1, "the world's K_local must equal n (one row per episode)");
+    for (int i = 0; i < n; ++i) {
+        m3_handle* h = planners[i];
+        if (!h) return peps_refuse(M3_ERR_BAD_ARG, i, "null handle");
+        if (h == world) return peps_refuse(M3_ERR_BAD_ARG, i, "the world handle is listed as a planner");
+        for (int j = 0; j < i; ++j)
+            if (planners[j] == h) return peps_refuse(M3_ERR_BAD_ARG, i, "handle listed twice");
+        const m3_config& c = h->cfg;
+        if (c.env_type != M3_ENV_PANDA) return peps_refuse(M3_ERR_UNSUPPORTED, i, "point_env planner (panda_env episodes only)");
+        if (c.device != wc.device) return peps_refuse(M3_ERR_BAD_ARG, i, "handle on another device than the world");
+        if (h->stream != world->stream) return peps_refuse(M3_ERR_STATE, i, "its stream differs from the world's");
+        UpdateArgs u;
+        int code;
+        if (const char* why = batch_refusal(h, u, code)) return peps_refuse(code, i, why);
+        if (!h->action_out) return peps_refuse(M3_ERR_STATE, i, "no action-out destination (m3_set_action_out)");
+    }
+    // ---- allocations: all of the set's memory, here ----
+    m3_panda_episodes* eps = new (std::nothrow) m3_panda_episodes();
+    if (!eps) return peps_refuse(M3_ERR_HIP, -1, "out of host memory");
+    m3_panda_episode_status st0;
+    std::memset(&st0, 0, sizeof(st0));
+    st0.phase = m3::PE_RUNNING; st0.done_tick = -1;
+    try {
+        eps->planners.assign(planners, planners + n);
+        eps->plan.resize(n);
+        eps->live.reserve(n);
+        eps->mirror.assign(n, st0);
+    } catch (...) {
+        delete eps;
+        return peps_refuse(M3_ERR_HIP, -1, "out of host memory");
+    }
+    for (int i = 0; i < n; ++i) eps->plan[i] = planners[i]->action_out;
+    eps->world = world;
+    eps->n = n;
+    eps->max_ticks = max_ticks;
+    eps->settle_ticks = settle_ticks;
+    const SimViews& wv = world->views;
+    const size_t st_b = align16((size_t)n * sizeof(m3_panda_episode_status));
+    const size_t plan_b = align16((size_t)n * sizeof(const float*));
+    const size_t kept_b = align16((size_t)n * 9 * sizeof(float));
+    const size_t end_b = align16((size_t)n * sizeof(int));
+    const size_t dof_b = align16((size_t)n * 18 * sizeof(float));
+    const size_t root_b = align16((size_t)n * wv.n_actors * 13 * sizeof(float));
+    const size_t rb_b = align16((size_t)n * wv.n_bodies * 13 * sizeof(float));
+    eps->rb_bytes = (size_t)n * wv.n_bodies * 13 * sizeof(float);
+    const hipStream_t s = world->stream;
+    hipError_t e = hipMalloc((void**)&eps->dev, st_b + plan_b + kept_b + end_b + dof_b + root_b + rb_b);
+    if (e == hipSuccess && trace)
+        e = hipMalloc((void**)&eps->trace, (size_t)max_ticks * n * m3::PE_TRACE_FLOATS * sizeof(float));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&eps->pinned, rb_b + end_b, hipHostMallocDefault);
+    char* d_st = eps->dev;
+    char* d_plan = d_st + st_b;
+    char* d_kept = d_plan + plan_b;
+    char* d_end = d_kept + kept_b;
+    char* d_dof = d_end + end_b;
+    char* d_root = d_dof + dof_b;
+    char* d_rb = d_root + root_b;
+    if (e == hipSuccess) e = hipMemcpyAsync(d_st, eps->mirror.data(), (size_t)n * sizeof(m3_panda_episode_status), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_plan, eps->plan.data(), (size_t)n * sizeof(const float*), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_kept, 0, kept_b + end_b, s);   // (a simulator's targets are zero until its first step_with_target)
+    // the planning view starts as a copy of the world's views: the rows panda_push_views never writes (table, stands) are
+    // the scene's, as in a planner's own simulator
+    if (e == hipSuccess) e = hipMemcpyAsync(d_dof, wv.dof_state, (size_t)n * 18 * sizeof(float), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_root, wv.root_state, (size_t)n * wv.n_actors * 13 * sizeof(float), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rb, wv.rigid_body_state, eps->rb_bytes, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        m3_panda_episodes_destroy(eps);
+        return peps_refuse(M3_ERR_HIP, -1, hipGetErrorString(e));
+    }
+    eps->ended_pinned = reinterpret_cast<int*>(eps->pinned + rb_b);
+    eps->ended_dev = reinterpret_cast<int*>(d_end);
+    eps->kept_dev = reinterpret_cast<float*>(d_kept);
+    m3::PandaEpisodeArgs& a = eps->args;
+    a.v = wv;
+    a.pv = wv;
+    a.pv.dof_state = reinterpret_cast<float*>(d_dof);
+    a.pv.root_state = reinterpret_cast<float*>(d_root);
+    a.pv.rigid_body_state = reinterpret_cast<float*>(d_rb);
+    a.pv.net_contact_force = nullptr;
+    a.world = world->sim_world;
+    a.n = n;
+    a.last_tick = max_ticks - 1;
+    a.settle_ticks = settle_ticks;
+    a.plan = reinterpret_cast<const float* const*>(d_plan);
+    a.kept = eps->kept_dev;
+    a.ended = eps->ended_dev;
+    a.st = reinterpret_cast<m3_panda_episode_status*>(d_st);
+    a.trace = eps->trace;
+    *out = eps;
+    return M3_OK;
+}
+
+static int peps_active(const m3_panda_episodes* eps) {
+    int r = 0;
+    for (int i = 0; i < eps->n; ++i) r += eps->mirror[i].phase != m3::PE_FROZEN;
+    return r;
+}
+
+static int peps_ready(m3_panda_episodes* eps, const char* who) {
+    if (peps_active(eps) == 0) { eps->err = std::string(who) + ": every episode has ended and settled"; return M3_ERR_STATE; }
+    for (int i = 0; i < eps->n; ++i)
+        if (eps->planners[i]->action_out != eps->plan[i]) {
+            eps->err = std::string(who) + ": planner " + std::to_string(i) + "'s action-out destination changed since create";
+            return M3_ERR_STATE;
+        }
+    return M3_OK;
+}
+
+extern "C" int m3_panda_episodes_observe(m3_panda_episodes* eps, const float** rb_host) {
+    if (!eps) return M3_ERR_BAD_ARG;
+    if (!rb_host) { eps->err = "m3_panda_episodes_observe: null argument"; return M3_ERR_BAD_ARG; }
+    if (eps->observed) { eps->err = "m3_panda_episodes_observe: the tick was observed already"; return M3_ERR_STATE; }
+    int rc = peps_ready(eps, "m3_panda_episodes_observe");
+    if (rc != M3_OK) return rc;
+    const hipStream_t s = eps->world->stream;
+    m3::launch_panda_episodes_pre(eps->world->pscene, eps->args, s);
+    HIPCHK(eps, hipGetLastError());
+    HIPCHK(eps, hipMemcpyAsync(eps->pinned, eps->args.pv.rigid_body_state, eps->rb_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(eps, hipStreamSynchronize(s));
+    eps->observed = true;
+    *rb_host = reinterpret_cast<const float*>(eps->pinned);
+    return M3_OK;
+}
+
+// the post kernel of the current tick under the host's word, and the host mirror's same step.  The pinned `ended` words are
+// free to rewrite: the observe of this tick synchronised after the last tick's copy (tick 0: nothing was in flight)
+static int peps_post(m3_panda_episodes* eps, const int* ended_host) {
+    const hipStream_t s = eps->world->stream;
+    for (int i = 0; i < eps->n; ++i) eps->ended_pinned[i] = ended_host[i] != 0;
+    HIPCHK(eps, hipMemcpyAsync(eps->ended_dev, eps->ended_pinned, (size_t)eps->n * sizeof(int), hipMemcpyHostToDevice, s));
+    m3::launch_panda_episodes_post(eps->world->pscene, eps->args, eps->tick, s);
+    HIPCHK(eps, hipGetLastError());
+    for (int i = 0; i < eps->n; ++i)
+        (void)m3::pe_advance(eps->mirror[i], eps->ended_pinned[i], eps->tick, eps->args.last_tick, eps->settle_ticks);
+    eps->tick += 1;
+    eps->observed = false;
+    return M3_OK;
+}
+
+extern "C" int m3_panda_episodes_act(m3_panda_episodes* eps, m3_batch* batch, const int* ended_host) {
+    if (!eps) return M3_ERR_BAD_ARG;
+    if (!batch || !ended_host) { eps->err = "m3_panda_episodes_act: null argument"; return M3_ERR_BAD_ARG; }
+    if (eps->tick == 0) { eps->err = "m3_panda_episodes_act: tick 0 is m3_panda_episodes_act_first's"; return M3_ERR_STATE; }
+    if (!eps->observed) { eps->err = "m3_panda_episodes_act: the tick was not observed (m3_panda_episodes_observe)"; return M3_ERR_STATE; }
+    int rc = peps_ready(eps, "m3_panda_episodes_act");
+    if (rc != M3_OK) return rc;
+    eps->live.clear();
+    const SimViews& pv = eps->args.pv;
+    for (int i = 0; i < eps->n; ++i) {
+        if (eps->mirror[i].phase != m3::PE_RUNNING || ended_host[i]) continue;
+        m3_handle* h = eps->planners[i];
+        // planner i plans from row i of the planning view: the rollout takes row 0 of its bound views, so it sees the floats
+        // row 0 of its own simulator would hold after update_plan's step
+        rc = m3_bind_sim_panda(h, pv.dof_state + (size_t)i * 18, pv.root_state + (size_t)i * pv.n_actors * 13, pv.n_actors,
+                               pv.box_actor, pv.dyn_actor, pv.obs_actor);
+        if (rc != M3_OK) { eps->err = "m3_panda_episodes_act: " + h->err; return rc; }
+        eps->live.push_back(h);
+    }
+    if (!eps->live.empty()) {
+        rc = m3_batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr);
+        if (rc != M3_OK) { eps->err = std::string("m3_panda_episodes_act: ") + m3_batch_last_error(batch); return rc; }
+    }
+    return peps_post(eps, ended_host);
+}
+
+extern "C" int m3_panda_episodes_act_first(m3_panda_episodes* eps, m3_handle* const* sims, const int* ended_host) {
+    if (!eps) return M3_ERR_BAD_ARG;
+    if (!sims || !ended_host) { eps->err = "m3_panda_episodes_act_first: null argument"; return M3_ERR_BAD_ARG; }
+    if (eps->tick != 0) { eps->err = "m3_panda_episodes_act_first: tick 0 is done"; return M3_ERR_STATE; }
+    int rc = peps_ready(eps, "m3_panda_episodes_act_first");
+    if (rc != M3_OK) return rc;
+    const m3_handle* w = eps->world;
+    for (int i = 0; i < eps->n; ++i) {
+        if (ended_host[i]) continue;
+        const m3_handle* sh = sims[i];
+        const char* why = nullptr;
+        if (!sh) why = "null handle";
+        else if (sh->cfg.env_type != M3_ENV_PANDA || !sh->cfg.sim_only || !sh->sim_u) why = "not a sim_only panda_env handle with bound views";
+        else if (sh->cfg.device != w->cfg.device || sh->stream != w->stream) why = "its device or stream differs from the world's";
+        else if (sh->cfg.dt != w->cfg.dt || sh->cfg.substeps != w->cfg.substeps) why = "its dt / substeps differ from the world's";
+        if (why) { eps->err = "m3_panda_episodes_act_first: simulator " + std::to_string(i) + ": " + why; return M3_ERR_STATE; }
+    }
+    // the targets planner i's simulator keeps from here on (row 0: the only row ever read again)
+    for (int i = 0; i < eps->n; ++i) {
+        if (ended_host[i]) continue;
+        HIPCHK(eps, hipMemcpyAsync(eps->kept_dev + (size_t)i * 9, sims[i]->sim_u, 9 * sizeof(float), hipMemcpyDeviceToDevice, w->stream));
+    }
+    return peps_post(eps, ended_host);
+}
+
+extern "C" int m3_panda_episodes_ticks_done(const m3_panda_episodes* eps) { return eps ? eps->tick : M3_ERR_BAD_ARG; }
+
+extern "C" int m3_panda_episodes_running(const m3_panda_episodes* eps) {
+    if (!eps) return M3_ERR_BAD_ARG;
+    int r = 0;
+    for (int i = 0; i < eps->n; ++i) r += eps->mirror[i].phase == m3::PE_RUNNING;
+    return r;
+}
+
+extern "C" int m3_panda_episodes_active(const m3_panda_episodes* eps) { return eps ? peps_active(eps) : M3_ERR_BAD_ARG; }
+
+extern "C" int m3_panda_episodes_status(m3_panda_episodes* eps, m3_panda_episode_status* status_out, float* trace_out) {
+    if (!eps || !status_out) return M3_ERR_BAD_ARG;
+    if (eps->observed) { eps->err = "m3_panda_episodes_status: between observe and act (the host copy is in use)"; return M3_ERR_STATE; }
+    const hipStream_t s = eps->world->stream;
+    const SimViews& v = eps->args.v;
+    HIPCHK(eps, hipMemcpyAsync(status_out, eps->args.st, (size_t)eps->n * sizeof(m3_panda_episode_status), hipMemcpyDeviceToHost, s));
+    // an ended and settled episode's row of the world is not stepped any more: its rigid-body rows hold the cubes as the
+    // episode's last step left them (through the set's pinned buffer: nothing is allocated here either)
+    HIPCHK(eps, hipMemcpyAsync(eps->pinned, v.rigid_body_state, eps->rb_bytes, hipMemcpyDeviceToHost, s));
+    if (trace_out) {
+        if (!eps->trace) { eps->err = "m3_panda_episodes_status: the set was created without a trace"; return M3_ERR_STATE; }
+        HIPCHK(eps, hipMemcpyAsync(trace_out, eps->trace, (size_t)eps->max_ticks * eps->n * m3::PE_TRACE_FLOATS * sizeof(float),
+                                 hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(eps, hipStreamSynchronize(s));
+    const float* rb = reinterpret_cast<const float*>(eps->pinned);
+    for (int i = 0; i < eps->n; ++i) {
+        const float* row = rb + (size_t)i * v.n_bodies * 13;
+        for (int j = 0; j < 3; ++j) {
+            status_out[i].cubeA[j] = row[v.box_body * 13 + j];
+            status_out[i].cubeB[j] = row[v.dyn_body * 13 + j];
+        }
+    }
     return M3_OK;
 }

@@ -343,6 +343,21 @@ void launch_psim_push(const PandaScene& sc, const SimViews& v, const float* worl
 void launch_psim_cost(const PandaScene& sc, const PandaCostParams& cp, const float* world, int Kl, int k0, bool env0_cube,
                       float* cost, hipStream_t s);
 
+// batched closed-loop episodes of the panda_env (m3_panda_episodes_*): one lane per episode of an N-env world
+struct PandaEpisodeArgs {
+    SimViews v;                    // the world's views, [n] rows
+    SimViews pv;                   // the set's planning view, [n] rows (no contact forces): what the planners and the host read
+    float* world;                  // the world's SoA state [NWP][n]
+    int n, last_tick, settle_ticks;
+    const float* const* plan;      // [n] each planner's action-out (device): row 0 is the velocity target
+    const float* kept;             // [n][9] the targets each planner's own simulator kept since tick 0
+    const int* ended;              // [n] the host's word for the current tick
+    m3_panda_episode_status* st;   // [n]
+    float* trace;                  // [max_ticks][n][PE_TRACE_FLOATS] or null
+};
+void launch_panda_episodes_pre(const PandaScene& sc, const PandaEpisodeArgs& a, hipStream_t s);
+void launch_panda_episodes_post(const PandaScene& sc, const PandaEpisodeArgs& a, int tick, hipStream_t s);
+
 }  // namespace m3
 
 struct m3_handle {

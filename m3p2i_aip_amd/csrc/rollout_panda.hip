@@ -9,6 +9,7 @@
 #include "m3_internal.hpp"
 #include "noise_stream.hpp"
 #include "panda_dyn.hpp"
+#include "panda_episode_lane.hpp"
 #include "wave_min.hpp"
 
 #include <cstdlib>
@@ -392,6 +393,88 @@ __global__ __launch_bounds__(64) void k_psim_cost(const PandaScene sc, const Pan
 void launch_psim_cost(const PandaScene& sc, const PandaCostParams& cp, const float* world, int Kl, int k0, bool env0_cube,
                       float* cost, hipStream_t s) {
     hipLaunchKernelGGL(k_psim_cost, dim3((Kl + 63) / 64), dim3(64), 0, s, sc, cp, world, Kl, k0, env0_cube ? 1 : 0, cost);
+}
+
+// ======================= batched closed-loop episodes (m3_panda_episodes_*) =======================
+// One lane per episode e of an N-env world.  Both kernels live in this translation unit so that panda_world_from_sim,
+// panda_infer_held, panda_step and panda_push_views are the same text under the same flags as in k_psim_pull / k_psim_step,
+// whose sequence on a 1-env world (and on row 0 of a planner's K-env simulator) they reproduce: same arithmetic, same bits.
+
+// before the command: what run_tamp's state upload and update_plan's sim.step() leave in row 0 of the planner's simulator
+__global__ __launch_bounds__(64) void k_panda_episodes_pre(const PandaScene sc, const PandaEpisodeArgs a) {
+    PANDA_CORNER_LDS(1);
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= a.n) return;
+    if (a.st[e].phase != PE_RUNNING) return;      // (an ended episode's planner is not asked any more)
+    const SimViews& v = a.v;
+    PandaWorld w;
+    // (1) set_dof_state_tensor / set_actor_root_state_tensor of the world's row: k_psim_pull.  Everything derived (sleep flags,
+    //     warm-started impulses, contact forces) is cleared and the held latch inferred from geometry there, so NOTHING of the
+    //     planner's simulator survives the upload but the velocity targets of (2)
+    panda_world_from_sim(v.dof_state + (size_t)e * 18, v.root_state + (size_t)e * v.n_actors * 13,
+                         v.box_actor, v.dyn_actor, v.obs_actor, w);
+    panda_infer_held(sc, w);
+    // (2) update_plan's sim.step(): k_psim_step under the targets that simulator holds -- on the fused path the ones the probe's
+    //     step leg set last at tick 0 (m3_panda_episodes_act_first), zero before
+    float uu[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) uu[j] = a.kept[(size_t)e * 9 + j];
+    PandaObs obs;
+    panda_step(sc, w, uu, obs, cs);
+    // (3) the views after that step: what PLANNER_AIF_PANDA reads (rigid-body rows) and the fused rollout starts from (dof and
+    //     root rows, m3_bind_sim_panda)
+    panda_push_views(sc, a.pv, e, w);
+}
+void launch_panda_episodes_pre(const PandaScene& sc, const PandaEpisodeArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_panda_episodes_pre, dim3((a.n + 63) / 64), dim3(64), 0, s, sc, a);
+}
+
+// after the command: trace row, the 1-env world's step (k_psim_step's body on row e), the end of an episode
+__global__ __launch_bounds__(64) void k_panda_episodes_post(const PandaScene sc, const PandaEpisodeArgs a, int tick) {
+    PANDA_CORNER_LDS(1);
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    const SimViews& v = a.v;
+    // everything that is not the step itself comes first and leaves nothing in registers across panda_step: from the second exit
+    // on the kernel is k_psim_step
+    if (e >= a.n) return;
+    int op;
+    {
+        m3_panda_episode_status st = a.st[e];
+        op = pe_advance(st, a.ended[e], tick, a.last_tick, a.settle_ticks);   // (4) panda_episode_lane.hpp
+        if (op != 0) a.st[e] = st;
+    }
+    if (!(op & PE_OP_STEP)) return;
+    float uu[9];
+    {
+        const float* plan = a.plan[e];
+#pragma unroll
+        for (int j = 0; j < 9; ++j) uu[j] = pe_target(op, plan, j);
+    }
+    if ((op & PE_OP_TRACE) && a.trace) {   // (5) the views BEFORE the step, the action the step runs under
+        float* o = a.trace + ((size_t)tick * a.n + e) * PE_TRACE_FLOATS;
+        const float* d = v.dof_state + (size_t)e * 18;
+        const float* r = v.root_state + (size_t)e * v.n_actors * 13;
+        const float* rb = v.rigid_body_state + (size_t)e * v.n_bodies * 13;
+        for (int j = 0; j < 18; ++j) o[PE_TR_DOF + j] = d[j];
+        for (int j = 0; j < PE_TR_ACTION - PE_TR_ROOT; ++j) o[PE_TR_ROOT + j] = r[j];
+        for (int j = 0; j < 9; ++j) o[PE_TR_ACTION + j] = uu[j];
+        for (int j = 0; j < 7; ++j) {
+            o[PE_TR_HAND + j] = rb[(v.robot_body + 8) * 13 + j];     // panda_hand: link 8 of the robot's 11
+            o[PE_TR_CUBE + j] = rb[v.box_body * 13 + j];
+        }
+    }
+    // set_dof_velocity_target_tensor(action) + step(): k_psim_step on row e
+    PandaWorld w;
+    psoa_load(a.world, a.n, e, w);
+    PandaObs obs;
+    panda_step(sc, w, uu, obs, cs);
+    psoa_store(a.world, a.n, e, w);
+    panda_push_views(sc, v, e, w);
+    // (6) no lane steps after its episode's last step (op == 0 from then on): row e of the views KEEPS the cubes' positions the
+    // serial loop reads after its loops -- m3_panda_episodes_status takes them from there
+}
+void launch_panda_episodes_post(const PandaScene& sc, const PandaEpisodeArgs& a, int tick, hipStream_t s) {
+    hipLaunchKernelGGL(k_panda_episodes_post, dim3((a.n + 63) / 64), dim3(64), 0, s, sc, a, tick);
 }
 
 }  // namespace m3

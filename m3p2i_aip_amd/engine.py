@@ -636,3 +636,88 @@ class HipEpisodes:
         st = [dict(done_tick=s.done_tick, success=bool(s.success), collision_ticks=s.collision_ticks,
                    final_pos=(s.final_pos[0], s.final_pos[1])) for s in self._status]
         return (st, tr) if with_trace else st
+
+
+class HipPandaEpisodes:
+    """N closed-loop panda_env episodes in lockstep (``m3_panda_episodes_*``, include/m3p2i_hip.h): row e of
+    the N-env world engine (an ``IsaacGymWrapper(..., "panda_env", num_envs=N)``'s) is episode e's 1-env world, planned by
+    ``engines[e]``.  The task planners stay on the host: a tick is ``observe()`` (the link rows they read, one copy, one
+    synchronisation), their decisions, ``act(batch, ended)``.  Each engine's ``set_action_out`` tensor is read here and must
+    stay the same.  The set owns its device state, planning views and pinned host copy; a tick allocates nothing."""
+
+    def __init__(self, world, engines, max_ticks, settle_ticks=0, trace=False):
+        self.lib = L.load()
+        self.world, self.engines = world, list(engines)
+        self.n, self.max_ticks, self.settle_ticks, self.trace_on = len(self.engines), int(max_ticks), int(settle_ticks), bool(trace)
+        arr = (C.c_void_p * max(self.n, 1))(*[e._h.value for e in self.engines])
+        self._eps = C.c_void_p()
+        rc = self.lib.m3_panda_episodes_create(world._h, arr, self.n, self.max_ticks, self.settle_ticks, int(self.trace_on),
+                                               C.byref(self._eps))
+        if rc != 0:
+            msg = self.lib.m3_panda_episodes_last_error(None)
+            raise L.M3Error(f"m3p2i_hip error {rc}: {msg.decode() if msg else ''}")
+        self._status = (L.PandaEpisodeStatus * self.n)()
+        self._ended = (C.c_int * self.n)()
+        self._rb = C.POINTER(C.c_float)()
+        self.bodies = int(world._simviews[2].shape[1])
+
+    def close(self):
+        if getattr(self, "_eps", None) is not None and self._eps:
+            self.lib.m3_panda_episodes_destroy(self._eps)
+            self._eps = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc != 0:
+            msg = self.lib.m3_panda_episodes_last_error(self._eps)
+            raise L.M3Error(f"m3p2i_hip error {rc}: {msg.decode() if msg else ''}")
+
+    def observe(self):
+        """Pre kernel, one device-to-host copy, one synchronisation.  Returns the planning view's rigid-body rows as an
+        [n, bodies, 13] float32 array over the set's pinned memory: valid until the next observe()."""
+        self._ck(self.lib.m3_panda_episodes_observe(self._eps, C.byref(self._rb)))
+        return np.ctypeslib.as_array(self._rb, shape=(self.n, self.bodies, 13))
+
+    def _flags(self, ended):
+        for i in range(self.n):
+            self._ended[i] = int(bool(ended[i]))
+        return self._ended
+
+    def act(self, batch, ended):
+        """ended[e]: episode e's task is done at this tick (the host's check_task_success).  Binds the planners that go on
+        to their rows, one batched command, post kernel; no synchronisation."""
+        self._ck(self.lib.m3_panda_episodes_act(self._eps, batch._b, self._flags(ended)))
+
+    def act_first(self, sims, ended):
+        """Tick 0, after each planner's own first command: no command here; sims[e] is planner e's K-env simulator engine,
+        whose kept velocity targets (row 0) become episode e's."""
+        arr = (C.c_void_p * self.n)(*[s._h.value for s in sims])
+        self._ck(self.lib.m3_panda_episodes_act_first(self._eps, arr, self._flags(ended)))
+
+    @property
+    def running(self):
+        """Episodes the host has not ended (host mirror, no synchronisation)."""
+        return int(self.lib.m3_panda_episodes_running(self._eps))
+
+    @property
+    def active(self):
+        """Episodes running or still settling."""
+        return int(self.lib.m3_panda_episodes_active(self._eps))
+
+    @property
+    def ticks_done(self):
+        return int(self.lib.m3_panda_episodes_ticks_done(self._eps))
+
+    def status(self, with_trace=False):
+        """[dict(phase, done_tick, success, cubeA, cubeB)] per episode (positions as float32 arrays), and with_trace the
+        trace as a [max_ticks, n, 132] float32 array (L.PE_TR_* offsets)."""
+        tr = np.empty((self.max_ticks, self.n, L.PANDA_EPISODE_TRACE_FLOATS), np.float32) if with_trace else None
+        self._ck(self.lib.m3_panda_episodes_status(self._eps, self._status, tr.ctypes.data if tr is not None else None))
+        st = [dict(phase=s.phase, done_tick=s.done_tick, success=bool(s.success),
+                   cubeA=np.array(s.cubeA[:], np.float32), cubeB=np.array(s.cubeB[:], np.float32)) for s in self._status]
+        return (st, tr) if with_trace else st

@@ -1,4 +1,5 @@
-"""Batched closed-loop episodes (point_env): N episodes of tools/closed_loop.run in lockstep.
+"""Batched closed-loop episodes: N episodes of tools/closed_loop.run in lockstep -- point_env (below) and
+panda_env (§7d: run_panda_episodes / PandaEpisodeSet at the end of this module).
 
     from m3p2i_aip_amd.episodes import run_point_episodes
     reports = run_point_episodes([("config_point", ["task=push", "goal=[-3,3]"], dict(dyn_phase=30)), ...], max_ticks=800)
@@ -18,7 +19,8 @@ import torch
 
 from . import _lib as L
 from . import compat
-from .engine import HipBatch, HipEpisodes
+from . import scenes
+from .engine import HipBatch, HipEpisodes, HipPandaEpisodes
 
 
 class _PlannerSide:
@@ -229,6 +231,263 @@ def run_point_episodes(episodes, max_ticks=800, trace=False):
     out = [None] * len(episodes)
     for members in groups.values():
         es = PointEpisodeSet([m for _, m in members], int(max_ticks), bool(trace))
+        try:
+            es.run()
+            reps = es.reports()
+        finally:
+            es.close()
+        for (idx, _), r in zip(members, reps):
+            out[idx] = r
+    return out
+
+
+# ---------------------------------------------- panda_env ----------------------------------------------
+class RowSim:
+    """What PLANNER_AIF_PANDA touches of a simulator -- step(), env0_link_states_host(), link_row() -- served from one
+    episode's row of the set's host copy of the planning view (HipPandaEpisodes.observe): the step update_plan asks for
+    was taken by the pre kernel, for all episodes at once."""
+
+    def __init__(self, env_type="panda_env"):
+        self.env_type = env_type
+        self.rows = None        # [bodies, 13] float32: this tick's rigid-body rows of the episode
+
+    def step(self):
+        pass
+
+    def env0_link_states_host(self):
+        return self.rows
+
+    def link_row(self, actor_name, link_name):
+        return scenes.body_index(self.env_type, actor_name, link_name)
+
+
+class _PandaSide(_PlannerSide):
+    """The planner side of one panda_env episode: Tamp.run_tamp split where the set takes over."""
+
+    def __init__(self, cfg):
+        super().__init__(cfg)
+        self.row_sim = RowSim(cfg.env_type)
+        self.rb0 = None
+
+    def first(self, dof_state, root_state):
+        """Tamp.run_tamp of tick 0 on the planner's own K-env simulator: the state upload, the task planner (its step
+        included), then the first command -- the fused / step probe, whose step leg rolls that simulator on and leaves the
+        velocity targets it keeps from then on.  Returns the whole plan, or None when the task is done already."""
+        self.sim._dof_state[:] = dof_state
+        self.sim._root_state[:] = root_state
+        self.sim.set_dof_state_tensor(self.sim._dof_state)
+        self.sim.set_actor_root_state_tensor(self.sim._root_state)
+        self.task_planner.update_plan(self.sim)
+        self.rb0 = self.sim.env0_link_states_host().copy()      # (the copy update_plan just read: no further read-back)
+        self.motion_planner.update_gripper_command(self.task_planner.task)
+        self.objective.update_objective(self.task_planner.task, self.task_planner.curr_goal)
+        self.task_success = bool(self.task_planner.check_task_success(self.sim))
+        if self.task_success:
+            return None
+        return self.motion_planner.command(self.sim._dof_state[0])
+
+    def decide(self, rows):
+        """Ticks 1..: run_tamp up to its command on this tick's rows; the objective goes to the handle as _push_objective
+        sends it inside command().  (get_pull_preference() is not read: nothing in a panda_env tick uses it.)"""
+        self.row_sim.rows = rows
+        tp = self.task_planner
+        tp.update_plan(self.row_sim)
+        self.motion_planner.update_gripper_command(tp.task)
+        self.objective.update_objective(tp.task, tp.curr_goal)
+        self.task_success = bool(tp.check_task_success(self.row_sim))
+        if not self.task_success:
+            self.motion_planner._push_objective()
+
+
+class PandaEpisodeSet:
+    """One set of config_panda episodes in lockstep: built by the constructor, tick 0 by start() (each planner's first
+    command on its own), then tick() while `active`; reports() afterwards.  items: [(config name, overrides, config,
+    jitter)] of one world (same dt, substeps, device, cube_on_shelf); jitter: dict(cube=(dx, dy)) or None."""
+
+    def __init__(self, items, max_ticks, settle_ticks=0, trace=False):
+        import m3p2i_aip.utils.isaacgym_utils.isaacgym_wrapper as wrapper
+        t0 = time.perf_counter()
+        self.items, self.max_ticks, self.settle_ticks, self.trace = list(items), int(max_ticks), int(settle_ticks), bool(trace)
+        cfgs = [cfg for _, _, cfg, _ in self.items]
+        self.sides = [_PandaSide(cfg) for cfg in cfgs]
+        c0, n = cfgs[0], len(self.items)
+        self.real = real = wrapper.IsaacGymWrapper(c0.isaacgym, c0.env_type, num_envs=n, viewer=False, device=c0.mppi.device,
+                                                   cube_on_shelf=c0.cube_on_shelf)
+        # closed_loop.run's jitter of its 1-env world, the same torch ops on row e
+        ia = int(real._get_actor_index_by_name("cubeA"))
+        jittered = False
+        for e, (*_, jitter) in enumerate(self.items):
+            if jitter and "cube" in jitter:
+                real._root_state[e, ia, 0] += float(jitter["cube"][0])
+                real._root_state[e, ia, 1] += float(jitter["cube"][1])
+                jittered = True
+        if jittered:
+            real.set_actor_root_state_tensor(real._root_state)
+        self.outs = []
+        for side in self.sides:
+            mp = side.motion_planner
+            mp._engine.use_torch_stream()
+            mp._ensure_noise()
+            out = torch.zeros(mp.T, mp.nu, device=mp.device, dtype=torch.float32)
+            mp._engine.set_action_out(out)
+            self.outs.append(out)
+        real._engine.use_torch_stream()
+        self.eps = HipPandaEpisodes(real._engine, [s.motion_planner._engine for s in self.sides], self.max_ticks,
+                                    settle_ticks=self.settle_ticks, trace=self.trace)
+        self.batch = HipBatch(n, device=torch.device(c0.mppi.device).index or 0)
+        self.alive = [True] * n
+        self.timelines = [[] for _ in range(n)]
+        self.tasks = [[] for _ in range(n)]          # per running tick, for the trace rows
+        self.lat, self.split = [], []                # per tick 1..: whole tick; (observe, host planners, act) seconds
+        self.build_s = time.perf_counter() - t0
+        self.first_s = self.loop_s = 0.0
+
+    def _note(self, e, tick):
+        side = self.sides[e]
+        task = side.task_planner.task
+        if not self.timelines[e] or self.timelines[e][-1][1] != task:
+            self.timelines[e].append((tick, task))
+        if side.task_success:
+            self.alive[e] = False
+        else:
+            self.tasks[e].append(task)
+
+    def start(self):
+        """Tick 0: each planner's first command on its own simulator (the probe), between observe and act_first."""
+        t0 = time.perf_counter()
+        rb = self.eps.observe().copy()
+        for e, side in enumerate(self.sides):
+            plan = side.first(self.real._dof_state[e:e + 1], self.real._root_state[e:e + 1])
+            # the pre kernel's row against the planner's own simulator after update_plan's step: the same bits, or the set
+            # does not reproduce the serial loop
+            if side.rb0.tobytes() != rb[e].tobytes():
+                raise RuntimeError(f"run_panda_episodes: episode {e}: the planning view differs from the planner's own "
+                                   "simulator at tick 0")
+            self._note(e, 0)
+            if plan is None:
+                continue
+            if side.motion_planner._fused is not True:
+                raise RuntimeError(f"run_panda_episodes: episode {e}'s planner chose the step path at its probe; "
+                                   "the batched command runs the fused path only")
+            self.outs[e].copy_(plan)
+            side.motion_planner._engine.set_action_out(self.outs[e])
+        self.eps.act_first([s.sim._engine for s in self.sides], [not a for a in self.alive])
+        self._after_act()
+        self.first_s = time.perf_counter() - t0
+
+    def _after_act(self):
+        if self.eps.ticks_done >= self.max_ticks:        # (the post kernel ended whoever was still running)
+            self.alive = [False] * len(self.alive)
+
+    @property
+    def active(self):
+        return self.eps.active
+
+    def tick(self):
+        t0 = time.perf_counter()
+        rb = self.eps.observe()
+        t1 = time.perf_counter()
+        tick = self.eps.ticks_done
+        for e, side in enumerate(self.sides):
+            if self.alive[e]:
+                side.decide(rb[e])
+                self._note(e, tick)
+        t2 = time.perf_counter()
+        self.eps.act(self.batch, [not a for a in self.alive])
+        self._after_act()
+        t3 = time.perf_counter()
+        self.lat.append(t3 - t0)
+        self.split.append((t1 - t0, t2 - t1, t3 - t2))
+
+    def run(self):
+        self.start()
+        t = time.perf_counter()
+        while self.active:
+            self.tick()
+        self.loop_s = time.perf_counter() - t
+
+    def reports(self):
+        st, tr = self.eps.status(with_trace=True) if self.trace else (self.eps.status(), None)
+        p50 = float(np.percentile(self.lat, 50) * 1e3) if self.lat else 0.0
+        p99 = float(np.percentile(self.lat, 99) * 1e3) if self.lat else 0.0
+        sp = np.percentile(np.array(self.split), 50, axis=0) * 1e3 if self.split else np.zeros(3)
+        reports = []
+        for e, ((cn, ov, cfg, _), side) in enumerate(zip(self.items, self.sides)):
+            s = st[e]
+            if s["phase"] != L.PE_FROZEN:
+                raise RuntimeError(f"run_panda_episodes: episode {e} has not ended (reports() before the set ran out)")
+            i = s["done_tick"]
+            # CPU torch on the f32 positions, as closed_loop.run
+            cube, goal = torch.from_numpy(s["cubeA"]), torch.from_numpy(s["cubeB"])
+            r = dict(config=cn, overrides=list(ov), K=cfg.mppi.num_samples, T=cfg.mppi.horizon, ticks=i + 1,
+                     success=s["success"], transport="batched", sim_time_s=(i + 1) * cfg.isaacgym.dt,
+                     timeline=list(self.timelines[e]), tick_ms_p50=p50, tick_ms_p99=p99,
+                     observe_ms_p50=float(sp[0]), host_ms_p50=float(sp[1]), act_ms_p50=float(sp[2]),
+                     build_s=self.build_s, first_s=self.first_s, loop_s=self.loop_s,
+                     cube_to_goal_xy=float(torch.norm(cube[:2] - goal[:2])), cube_height_above_goal=float(cube[2] - goal[2]),
+                     lanes_per_sample_used=side.motion_planner._engine.panda_lanes_per_sample_used())
+            if self.trace:
+                rows = i if s["success"] else i + 1      # (no row for the success tick: the serial loop ends before it)
+                path, full = [], []
+                for t in range(rows):
+                    row, task = tr[t, e], self.tasks[e][t]
+                    dof = row[L.PE_TR_DOF:L.PE_TR_ROOT]
+                    act = row[L.PE_TR_ACTION:L.PE_TR_HAND]
+                    path.append([task] + row[L.PE_TR_HAND:L.PE_TR_CUBE].tolist() + row[L.PE_TR_CUBE:L.PE_TR_CUBE + 7].tolist() +
+                                dof[[14, 16]].tolist() + act[7:9].tolist())
+                    full.append(dict(tick=t, task=task, dof_state=dof.tolist(),
+                                     root_state=row[L.PE_TR_ROOT:L.PE_TR_ACTION].reshape(-1, 13).tolist(), action=act.tolist()))
+                r["trace"] = path
+                if full:
+                    r["full"] = full
+            reports.append(r)
+        return reports
+
+    def close(self):
+        for x in (getattr(self, "eps", None), getattr(self, "batch", None)):
+            if x is not None:
+                x.close()
+        if getattr(self, "real", None) is not None:
+            self.real.stop_sim()
+        for side in getattr(self, "sides", []):
+            side.close()
+
+
+def _panda_groups(episodes, who):
+    compat.install(force_standins=True)
+    groups = {}
+    for idx, (cn, ov, jitter) in enumerate(episodes):
+        cfg = compat.make_config(cn, list(ov))
+        if cfg.env_type != "panda_env":
+            raise ValueError(f"{who}: episode {idx} is {cfg.env_type} (panda_env only)")
+        key = (float(cfg.isaacgym.dt), int(cfg.isaacgym.substeps), cfg.mppi.device, bool(cfg.cube_on_shelf))
+        groups.setdefault(key, []).append((idx, (cn, list(ov), cfg, jitter)))
+    return groups
+
+
+def build_panda_set(episodes, max_ticks=600, settle_ticks=0, trace=False):
+    """A PandaEpisodeSet of episodes [(config name, overrides, jitter)] that share one world."""
+    groups = _panda_groups(episodes, "build_panda_set")
+    if len(groups) != 1:
+        raise ValueError("build_panda_set: the episodes' worlds differ (dt, substeps, device, cube_on_shelf)")
+    return PandaEpisodeSet([m for _, m in next(iter(groups.values()))], max_ticks, settle_ticks, trace)
+
+
+def run_panda_episodes(episodes, max_ticks=600, settle_ticks=0, trace=False):
+    """episodes: [("config_panda", overrides, jitter)] as closed_loop.run takes them (jitter: dict(cube=(dx, dy)) or None).
+    Returns one report per episode, in order: what closed_loop.run(cn, overrides, ticks=max_ticks, jitter=jitter,
+    settle_ticks=settle_ticks, trace=trace) returns, bit for bit (ticks, success, sim_time_s, timeline, cube_to_goal_xy,
+    cube_height_above_goal, trace and full rows if asked), with the set's tick_ms_p50 / tick_ms_p99 in place of the
+    per-episode command_ms_*, their split (observe_ms_p50, host_ms_p50, act_ms_p50), build_s / first_s / loop_s of the set
+    (construction, tick 0, ticks 1..) and lanes_per_sample_used (the kernel form of the planner's last command).  Episodes
+    whose worlds differ run as separate sets, one after the other.  A lone episode is better served by closed_loop.run."""
+    if int(max_ticks) <= 0:
+        raise ValueError("run_panda_episodes: max_ticks must be > 0")
+    if int(settle_ticks) < 0:
+        raise ValueError("run_panda_episodes: settle_ticks must be >= 0")
+    out = [None] * len(episodes)
+    for members in _panda_groups(episodes, "run_panda_episodes").values():
+        es = PandaEpisodeSet([m for _, m in members], int(max_ticks), int(settle_ticks), bool(trace))
         try:
             es.run()
             reps = es.reports()

@@ -5,7 +5,8 @@ block-to-goal error, task time, dyn-obs collisions -- next to the logged statist
     python tools/band_stats.py [--n 20] [--json out.json] [--size baseline|default] [--avoid] [--batched] [scenario ...]
 
 --batched: all episodes of all named scenarios in lockstep, one library call per tick (m3p2i_aip_amd/episodes.py,
-DESIGN.md §7c): the same per-episode results as the serial runs, bit for bit.
+DESIGN.md §7c): the same per-episode results as the serial runs, bit for bit.  The `panda` rows likewise, the n episodes
+of each row in lockstep (two library calls per tick with the host's task planners in between, §7d).
 
 --size default: the reference's shipped planner size, K=200 samples, T=15 (config/mppi/point.yaml) -- the size the
 logged runs were most plausibly made with (it is not recorded); baseline (default here): K, T of the BASELINE configs.
@@ -162,6 +163,24 @@ def panda_episodes(n=20, overrides=("mppi.num_samples=4000", "mppi.horizon=20"),
                 ticks_to_success=stats([r["ticks"] for r in ok]) if ok else None, runs=runs)
 
 
+def panda_episodes_batched(n=20, overrides=("mppi.num_samples=4000", "mppi.horizon=20"), ticks=600):
+    """panda_episodes() with the n episodes in lockstep (m3p2i_aip_amd.episodes.run_panda_episodes): the same
+    dict, the same per-episode results bit for bit."""
+    from m3p2i_aip_amd.episodes import run_panda_episodes
+    jit = []
+    for e in range(n):
+        rng = np.random.default_rng([77, e])
+        jit.append(dict(cube=(0.0, 0.0) if e == 0 else tuple(rng.uniform(-0.02, 0.02, 2).tolist())))
+    reps = run_panda_episodes([("config_panda", list(overrides), j) for j in jit], max_ticks=ticks, settle_ticks=SETTLE_TICKS)
+    runs = [dict(episode=e, jitter=j, success=r["success"], ticks=r["ticks"], timeline=r["timeline"],
+                 cube_to_goal_xy=r["cube_to_goal_xy"], cube_height_above_goal=r["cube_height_above_goal"])
+            for e, (j, r) in enumerate(zip(jit, reps))]
+    ok = [r for r in runs if r["success"]]
+    return dict(n=n, overrides=list(overrides), successes=len(ok),
+                final_xy_error_m=stats([r["cube_to_goal_xy"] for r in ok]) if ok else None,
+                ticks_to_success=stats([r["ticks"] for r in ok]) if ok else None, runs=runs)
+
+
 def main(argv):
     n, out, names, size, batched = 20, None, [], "baseline", False
     it = iter(argv)
@@ -188,7 +207,7 @@ def main(argv):
                         ("panda_pick_faure", ["mppi.num_samples=4000", "mppi.horizon=20", "mppi.halton_scramble=faure"]),
                         ("panda_pick_default_size", ["mppi.num_samples=200", "mppi.horizon=12"]),
                         ("panda_pick_default_size_faure", ["mppi.num_samples=200", "mppi.horizon=12", "mppi.halton_scramble=faure"])):
-            r = panda_episodes(n, ov)
+            r = panda_episodes_batched(n, ov) if batched else panda_episodes(n, ov)
             r["logged"] = allband["panda"]["reactive_pick"]["final_xy_error_m"]
             res[tag] = r
             e = r["final_xy_error_m"]
