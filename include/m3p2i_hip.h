@@ -331,6 +331,33 @@ int m3_set_objective(m3_handle* h, int task, const float* goal, int goal_len, in
  * blind to the dyn-obs; its logged experiments `plot/point/case2_halton_{push,pull}_coll.npy` show 3 / 60 and 1 / 60
  * collisions, i.e. were made with the term active.  point_env only.  The rollout then runs its general instance. */
 int m3_set_avoid_dyn_obs(m3_handle* h, int on);
+/* EXTENSION, point_env only: the literal WEIGHTS of the four point tasks' costs as per-handle state (the defaults = the
+ * reference's literals, cost_functions.py:38-89,158-169).  Thresholds and values that are not weights stay literals: the 0.1
+ * contact-force threshold, the 0.5 radius and the 0.6 value of the pull's velocity term, the suction constants. */
+typedef struct m3_point_cost_weights {
+    float nav_dist;      /* 1    :39       navigation: |robot - goal| */
+    float collision;     /* 1000 :158-169  the penalty of get_motion_cost (navigation; push / pull with avoid_dyn_obs) */
+    float robot_box;     /* 1    :49       calculate_dist: |robot - box| */
+    float box_goal;      /* 10   :49       calculate_dist: |box - goal| */
+    float push_dist;     /* 3    :60 */
+    float push_align;    /* 1    :60 */
+    float pull_dist;     /* 3    :89 */
+    float pull_vel;      /* 3    :89 */
+    float pull_align;    /* 7    :89 */
+} m3_point_cost_weights;
+void m3_default_point_cost_weights(m3_point_cost_weights* w);
+/* Applies from the next command / rollout / cost call (fused rollout, batched command, episodes, step-mode m3_cost alike);
+ * survives m3_reset; no allocation, no synchronisation.  w == NULL: back to the defaults.  Negative and zero weights are
+ * legal; a NaN or infinite one is M3_ERR_BAD_ARG (the message names the field); a panda_env handle M3_ERR_UNSUPPORTED.
+ * A handle whose nine floats equal the defaults bit for bit runs exactly the kernels it ran before this call existed; any
+ * other handle runs the weighted build of the general rollout instance (and of the step-mode cost), in which each literal
+ * is replaced by its weight one for one -- at the default weights the same bits.  Sharded handles: set the same weights
+ * on every rank. */
+int m3_set_point_cost_weights(m3_handle* h, const m3_point_cost_weights* w);
+int m3_get_point_cost_weights(const m3_handle* h, m3_point_cost_weights* out);
+/* Test and A/B switch: -1 the automatic choice above (default), 1 the weighted build whatever the weights, 0 never -- with
+ * weights other than the defaults the next command / rollout / cost call is then refused (M3_ERR_STATE). */
+int m3_set_weighted_cost_instance(m3_handle* h, int on);
 /* Objective.multi_modal (cost_functions.py:9) for a sim_only handle, whose config does not
  * come from an MPPI object; refused on planner handles (fixed at m3_create) */
 int m3_set_multi_modal(m3_handle* h, int multi_modal);

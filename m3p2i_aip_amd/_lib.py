@@ -48,6 +48,14 @@ class PointWorld(C.Structure):
     _fields_ = [("robot", C.c_float * 4), ("box", C.c_float * 7), ("dyn_obs", C.c_float * 7)]
 
 
+COST_WEIGHT_DEFAULTS = dict(nav_dist=1.0, collision=1000.0, robot_box=1.0, box_goal=10.0, push_dist=3.0, push_align=1.0,
+                            pull_dist=3.0, pull_vel=3.0, pull_align=7.0)   # m3_point_cost_weights, in field order
+
+
+class PointCostWeights(C.Structure):
+    _fields_ = [(n, C.c_float) for n in COST_WEIGHT_DEFAULTS]
+
+
 class Info(C.Structure):
     _fields_ = [("eta", C.c_float), ("eta_1", C.c_float), ("eta_2", C.c_float),
                 ("beta", C.c_float), ("beta_1", C.c_float), ("beta_2", C.c_float),
@@ -120,6 +128,10 @@ SYMBOLS = [
     ("m3_set_call_count", C.c_int, [_H, C.c_uint]),
     ("m3_set_objective", C.c_int, [_H, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int]),
     ("m3_set_avoid_dyn_obs", C.c_int, [_H, C.c_int]),
+    ("m3_default_point_cost_weights", None, [C.POINTER(PointCostWeights)]),
+    ("m3_set_point_cost_weights", C.c_int, [_H, C.POINTER(PointCostWeights)]),
+    ("m3_get_point_cost_weights", C.c_int, [_H, C.POINTER(PointCostWeights)]),
+    ("m3_set_weighted_cost_instance", C.c_int, [_H, C.c_int]),
     ("m3_set_multi_modal", C.c_int, [_H, C.c_int]),
     ("m3_set_plan", C.c_int, [_H, C.c_int, _FP]),
     ("m3_set_action_out", C.c_int, [_H, C.c_void_p]),

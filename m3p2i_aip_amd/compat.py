@@ -25,7 +25,7 @@ import sys
 import time
 import types
 from dataclasses import dataclass, field
-from typing import List
+from typing import Dict, List, Optional
 
 import torch
 
@@ -122,6 +122,8 @@ class ExampleConfig:
     n_steps: int = 0
     nx: int = 4
     avoid_dyn_obs: bool = False     # EXTENSION (not a key of the reference's config_store.py): cost_functions.Objective
+    cost_weights: Optional[Dict[str, float]] = None   # EXTENSION, point_env: e.g. `cost_weights={push_align: 2.5}`; None = the
+                                                      # reference's literals (cost_functions.Objective, _lib.COST_WEIGHT_DEFAULTS)
 
 
 def make_config(config_name="config_point", overrides=()):

@@ -52,7 +52,48 @@ class Objective(object):
         # EXTENSION, off by default: `avoid_dyn_obs: True` in the config makes push / pull / push_pull add
         # get_motion_cost (:158-169) as navigation does; the shipped compute_cost returns before it (:23-29 vs :36)
         self.avoid_dyn_obs = bool(getattr(cfg, "avoid_dyn_obs", False)) and getattr(cfg, "env_type", "point_env") == "point_env"
+        # EXTENSION, off by default: `cost_weights: {push_align: 2.5, ...}` in the config replaces literal weights of the
+        # point_env costs (keys: _lib.COST_WEIGHT_DEFAULTS, the fields of m3_point_cost_weights; missing keys keep the
+        # reference's literal).  With every weight at its default the handle runs the kernels it always ran.
+        self._cost_weights = dict(L.COST_WEIGHT_DEFAULTS)
+        given = getattr(cfg, "cost_weights", None)
+        if given:
+            if getattr(cfg, "env_type", "point_env") != "point_env":
+                raise ValueError("cost_weights: point_env only")
+            self.set_cost_weights(**dict(given))
         _LIVE.add(self)
+
+    @property
+    def cost_weights(self):
+        """The nine weights of the point_env costs (a copy; change them with set_cost_weights)."""
+        return dict(self._cost_weights)
+
+    @property
+    def has_default_cost_weights(self):
+        return self._cost_weights == L.COST_WEIGHT_DEFAULTS
+
+    def set_cost_weights(self, **kw):
+        """Replace some of the weights (the others keep their value); they apply from the next command / compute_cost."""
+        unknown = sorted(set(kw) - set(L.COST_WEIGHT_DEFAULTS))
+        if unknown:
+            raise ValueError(f"unknown cost weight(s) {unknown}: one of {list(L.COST_WEIGHT_DEFAULTS)}")
+        for k, v in kw.items():
+            v = float(np.float32(v))          # (the library's value: a float)
+            if not np.isfinite(v):
+                raise ValueError(f"cost weight {k} is not finite")
+            self._cost_weights[k] = v
+
+    def push_cost_weights(self, eng):
+        """Hand the weights to an engine that does not hold them yet.  With default weights on an engine that never held
+        others the call is not made at all (an engine without set_point_cost_weights serves such an Objective)."""
+        w = self._cost_weights
+        if getattr(eng, "_cost_weights_pushed", L.COST_WEIGHT_DEFAULTS) == w:
+            return
+        if not hasattr(eng, "set_point_cost_weights"):
+            raise TypeError(f"{type(eng).__name__} has no set_point_cost_weights: non-default cost_weights need the HIP library's "
+                            "engine (m3p2i_aip_amd.engine.HipEngine)")
+        eng.set_point_cost_weights(w)
+        eng._cost_weights_pushed = dict(w)
 
     def update_objective(self, task, goal):
         self.task = task
@@ -91,6 +132,7 @@ class Objective(object):
         if self.avoid_dyn_obs or getattr(eng, "_avoid_dyn_obs", False):
             eng.set_avoid_dyn_obs(self.avoid_dyn_obs)
             eng._avoid_dyn_obs = self.avoid_dyn_obs
+        self.push_cost_weights(eng)
         return eng.cost()
 
 

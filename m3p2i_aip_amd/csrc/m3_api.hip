@@ -729,6 +729,58 @@ extern "C" int m3_set_avoid_dyn_obs(m3_handle* h, int on) {
     return M3_OK;
 }
 
+// ---- the point_env cost weights (extension; per-handle state like the objective: no allocation, no synchronisation) ----
+static const char* const COST_WEIGHT_NAMES[9] = {"nav_dist", "collision", "robot_box", "box_goal", "push_dist",
+                                                 "push_align", "pull_dist", "pull_vel", "pull_align"};
+static_assert(sizeof(m3_point_cost_weights) == 9 * sizeof(float) && sizeof(PointCostWeights) == sizeof(m3_point_cost_weights),
+              "m3_point_cost_weights: nine floats, the layout of PointCostWeights");
+
+extern "C" void m3_default_point_cost_weights(m3_point_cost_weights* w) {
+    if (w) std::memcpy(w, &POINT_COST_WEIGHTS_DEFAULT, sizeof(*w));
+}
+
+extern "C" int m3_set_point_cost_weights(m3_handle* h, const m3_point_cost_weights* w) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_point_cost_weights: point_env only");
+    if (!w) { h->cost_weights = POINT_COST_WEIGHTS_DEFAULT; return M3_OK; }
+    const float* f = reinterpret_cast<const float*>(w);
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(f[i]))
+            return fail(h, M3_ERR_BAD_ARG, (std::string("m3_set_point_cost_weights: ") + COST_WEIGHT_NAMES[i] + " is not finite").c_str());
+    std::memcpy(&h->cost_weights, w, sizeof(*w));
+    return M3_OK;
+}
+
+extern "C" int m3_get_point_cost_weights(const m3_handle* h, m3_point_cost_weights* out) {
+    if (!h || !out) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_POINT) return M3_ERR_UNSUPPORTED;
+    std::memcpy(out, &h->cost_weights, sizeof(*out));
+    return M3_OK;
+}
+
+extern "C" int m3_set_weighted_cost_instance(m3_handle* h, int on) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_weighted_cost_instance: point_env only");
+    if (on < -1 || on > 1) return fail(h, M3_ERR_BAD_ARG, "m3_set_weighted_cost_instance: -1 (by the weights), 0 or 1");
+    h->weighted_instance = on;
+    return M3_OK;
+}
+
+// the handle's weights are the defaults bit for bit (-0.0f is not 0.0f here: the kernels multiply by them)
+static bool default_cost_weights(const m3_handle* h) {
+    return std::memcmp(&h->cost_weights, &POINT_COST_WEIGHTS_DEFAULT, sizeof(PointCostWeights)) == 0;
+}
+// the one owner of "does this handle's cost code take the weights" (rollout instance, batch group, step-mode cost)
+static bool weighted_cost(const m3_handle* h) {
+    if (h->cfg.env_type != M3_ENV_POINT) return false;
+    return h->weighted_instance < 0 ? !default_cost_weights(h) : h->weighted_instance != 0;
+}
+static const char* weighted_refusal(const m3_handle* h) {
+    if (h->cfg.env_type == M3_ENV_POINT && h->weighted_instance == 0 && !default_cost_weights(h))
+        return "the weighted cost instance is forced off (m3_set_weighted_cost_instance 0) but the handle's cost weights are not the defaults";
+    return nullptr;
+}
+
 extern "C" int m3_set_multi_modal(m3_handle* h, int mm) {
     if (!h) return M3_ERR_BAD_ARG;
     if (!h->cfg.sim_only && (mm != 0) != (h->cfg.multi_modal != 0))
@@ -884,6 +936,7 @@ static const char* rollout_refusal(const m3_handle* h) {
     if (c.mode_simple && !c.sampling_random && !h->have_noise)
         return "m3_rollout: simple mode needs m3_set_noise or sampling_random";
     if (h->task == M3_TASK_PUSH_PULL && !c.multi_modal) return "m3_rollout: push_pull needs multi_modal";
+    if (const char* why = weighted_refusal(h)) return why;
     return nullptr;
 }
 
@@ -972,7 +1025,7 @@ static int plan_rollout(m3_handle* h, RolloutArgs& a, PandaArgs& pa, RolloutPlan
     const int rc = prepare_rollout(h, a);
     if (rc != M3_OK) return rc;
     if (h->cfg.env_type == M3_ENV_POINT) {
-        p = plan_rollout_point(a, h->scene);
+        p = plan_rollout_point(a, h->scene, weighted_cost(h));
     } else {
         fill_panda_args(h, a, pa);
         p = plan_rollout_panda(a, pa);
@@ -992,7 +1045,7 @@ extern "C" int m3_rollout(m3_handle* h) {
     const int rc = plan_rollout(h, a, pa, p);
     if (rc != M3_OK) return rc;
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, p, h->stream);
+    if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->cost_weights, p, h->stream);
     else launch_rollout_panda(a, pa, h->pscene, p, h->stream);
     HIPCHK(h, hipGetLastError());
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
@@ -1572,7 +1625,8 @@ struct BatchKey {
 // the fields a group shares, in the order the groups are sorted by
 auto rollout_fields(const BatchKey& k) {
     const RolloutPlan& p = k.roll;
-    return std::tie(p.instance, p.ref, p.lps, p.forces, p.general, p.shadows, p.rec, k.K, k.T, p.lanes);
+    // (weighted first: the weighted groups' entries, of their own type, lie behind all the others in the table)
+    return std::tie(p.weighted, p.instance, p.ref, p.lps, p.forces, p.general, p.shadows, p.rec, k.K, k.T, p.lanes);
 }
 auto update_fields(const BatchKey& k) { return std::tie(k.upd.nu, k.upd.multi, k.upd.jr, k.upd.wt, k.upd.n_cand, k.T); }
 bool same_rollout(const BatchKey& x, const BatchKey& y) { return rollout_fields(x) == rollout_fields(y); }
@@ -1591,8 +1645,8 @@ size_t align16(size_t n) { return (n + 15) / 16 * 16; }
 struct m3_batch {
     int device = 0, max_handles = 0;
     std::string err;
-    size_t upd_off = 0, slot_bytes = 0;   // a slot: [max_handles] BatchRolloutEntry or BatchPandaEntry (from 0) |
-                                          // [max_handles] UpdateArgs
+    size_t upd_off = 0, slot_bytes = 0;   // a slot: [max_handles] BatchRolloutEntry (then, 16-aligned, the weighted groups'
+                                          // BatchRolloutEntryW) or BatchPandaEntry (from 0) | [max_handles] UpdateArgs
     char* host[BATCH_SLOTS] = {};
     char* dev[BATCH_SLOTS] = {};
     hipEvent_t done[BATCH_SLOTS] = {};
@@ -1636,8 +1690,8 @@ extern "C" int m3_batch_create(int device, int max_handles, m3_batch** out) {
     if (!b) { g_batch_err = "m3_batch_create: out of host memory"; return M3_ERR_HIP; }
     b->device = device;
     b->max_handles = max_handles;
-    constexpr size_t entry = std::max(sizeof(BatchRolloutEntry), sizeof(BatchPandaEntry));
-    b->upd_off = align16((size_t)max_handles * entry);
+    constexpr size_t entry = std::max(std::max(sizeof(BatchRolloutEntry), sizeof(BatchRolloutEntryW)), sizeof(BatchPandaEntry));
+    b->upd_off = align16((size_t)max_handles * entry) + 16;   // (+ 16: the alignment gap in front of the weighted entries)
     b->slot_bytes = b->upd_off + (size_t)max_handles * sizeof(UpdateArgs);
     try {
         b->seen.resize(max_handles);
@@ -1752,19 +1806,30 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
         HIPCHK(b, hipEventSynchronize(b->done[slot]));
         b->in_flight[slot] = false;
     }
+    // point_env: the first n_plain handles in key order are the unweighted ones (rollout_fields), the weighted ones follow
+    int n_plain = n;
+    if (!panda) {
+        n_plain = 0;
+        while (n_plain < n && !hd[b->by_roll[n_plain]].key.roll.weighted) ++n_plain;
+    }
+    const size_t w_off = align16((size_t)n_plain * sizeof(BatchRolloutEntry));
     BatchRolloutEntry* hr = reinterpret_cast<BatchRolloutEntry*>(b->host[slot]);
+    BatchRolloutEntryW* hw = reinterpret_cast<BatchRolloutEntryW*>(b->host[slot] + w_off);
     BatchPandaEntry* hp = reinterpret_cast<BatchPandaEntry*>(b->host[slot]);
-    const size_t upd_off = align16((size_t)n * (panda ? sizeof(BatchPandaEntry) : sizeof(BatchRolloutEntry)));
+    const size_t upd_off = panda ? align16((size_t)n * sizeof(BatchPandaEntry))
+                                 : align16(w_off + (size_t)(n - n_plain) * sizeof(BatchRolloutEntryW));
     UpdateArgs* hu = reinterpret_cast<UpdateArgs*>(b->host[slot] + upd_off);
     for (int p = 0; p < n; ++p) {
         const int i = b->by_roll[p];
         if (panda) { hp[p].a = hd[i].a; hp[p].pa = hd[i].pa; hp[p].sc = hs[i]->pscene; }
-        else { hr[p].a = hd[i].a; hr[p].sc = hs[i]->scene; }
+        else if (p < n_plain) { hr[p].a = hd[i].a; hr[p].sc = hs[i]->scene; }
+        else { BatchRolloutEntryW& e = hw[p - n_plain]; e.a = hd[i].a; e.sc = hs[i]->scene; e.wt = hs[i]->cost_weights; }
     }
     for (int p = 0; p < n; ++p) hu[p] = hd[b->by_upd[p]].u;
     char* dslot = b->dev[slot];
     HIPCHK(b, hipMemcpyAsync(dslot, b->host[slot], upd_off + (size_t)n * sizeof(UpdateArgs), hipMemcpyHostToDevice, s));
     const BatchRolloutEntry* dr = reinterpret_cast<const BatchRolloutEntry*>(dslot);
+    const BatchRolloutEntryW* dw = reinterpret_cast<const BatchRolloutEntryW*>(dslot + w_off);
     const BatchPandaEntry* dp = reinterpret_cast<const BatchPandaEntry*>(dslot);
     const UpdateArgs* du = reinterpret_cast<const UpdateArgs*>(dslot + upd_off);
     // ---- one rollout launch per group (panda_env: + one k_panda_reach_cost launch when the group keeps the record buffer,
@@ -1775,6 +1840,7 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
         int q = p + 1;
         while (q < n && same_rollout(hd[b->by_roll[q]].key, k)) ++q;
         if (panda) launch_rollout_panda_batch(dp + p, q - p, k.roll, k.K, s);
+        else if (k.roll.weighted) launch_rollout_point_batch_w(dw + (p - n_plain), q - p, k.roll, s);
         else launch_rollout_point_batch(dr + p, q - p, k.roll, s);
         ++n_roll;
         p = q;
@@ -2007,9 +2073,11 @@ extern "C" int m3_cost(m3_handle* h, float* cost) {
     if (!h || !cost) return M3_ERR_BAD_ARG;
     if (!h->sim_world) return fail(h, M3_ERR_STATE, "m3_cost: step-mode state not initialised");
     if (h->cfg.env_type == M3_ENV_POINT) {
+        if (const char* why = weighted_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_cost: ") + why).c_str());
         CostParams cp;
         fill_cost_params(h, cp);
-        launch_sim_cost(cp, h->sim_world, h->cfg.K_local, h->cfg.k_offset, cost, h->stream);
+        if (weighted_cost(h)) launch_sim_cost_w(cp, h->cost_weights, h->sim_world, h->cfg.K_local, h->cfg.k_offset, cost, h->stream);
+        else launch_sim_cost(cp, h->sim_world, h->cfg.K_local, h->cfg.k_offset, cost, h->stream);
     } else {
         PandaCostParams cp;
         fill_panda_cost_params(h, cp);

@@ -162,6 +162,11 @@ struct BatchRolloutEntry {   // one point_env handle's rollout (the scene is not
     RolloutArgs a;
     PointScene sc;
 };
+struct BatchRolloutEntryW {  // ... of the weighted group (kb_rollout_point_w): the same with the handle's cost weights behind it
+    RolloutArgs a;
+    PointScene sc;
+    PointCostWeights wt;
+};
 // the k_update_small instance (template arguments, workgroup width, top-k workgroups) an unsharded command takes:
 // launch_update_small launches it, m3_batch_command groups the handles by it
 struct SmallUpdateInstance {
@@ -184,17 +189,20 @@ struct RolloutPlan {
                                               // (point_env: all 0)
     int lanes, blocks;   // active lanes per wavefront, rollout workgroups
     int rows;            // rows of minima the launch leaves in a.wave_min (wave_min.hpp; 0: none)
+    int weighted;        // point_env: the weighted build of the general instance (m3_set_point_cost_weights; instance == -1)
 };
-RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc);
+RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, bool weighted);
 // one launch of the plan's instance for n handles of K_local = a.Kl and the same plan (tab: device, n entries)
 void launch_rollout_point_batch(const BatchRolloutEntry* tab, int n, const RolloutPlan& p, hipStream_t s);
+void launch_rollout_point_batch_w(const BatchRolloutEntryW* tab, int n, const RolloutPlan& p, hipStream_t s);   // p.weighted
 void launch_rollout_point_nav_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
 void launch_rollout_point_push_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
 void launch_rollout_point_pull_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
 void launch_rollout_point_pushpull_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
 
 // ---- launchers (defined in the .hip files) ---------------------------------------------
-void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const RolloutPlan& p, hipStream_t s);
+void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const PointCostWeights& wt /* read if p.weighted */,
+                          const RolloutPlan& p, hipStream_t s);
 void launch_rollout_point_nav(const RolloutArgs& a, const PointScene& sc, int blocks, hipStream_t s);
 void launch_rollout_point_push(const RolloutArgs& a, const PointScene& sc, int blocks, hipStream_t s);
 void launch_rollout_point_pull(const RolloutArgs& a, const PointScene& sc, int blocks, hipStream_t s);
@@ -286,6 +294,8 @@ void launch_sim_forces(const SimViews& v, float* world, const float* f /*[Kl][nB
                        hipStream_t s);
 void launch_sim_cost(const CostParams& cp, float* world, int Kl, int k0, float* cost,
                      hipStream_t s);
+void launch_sim_cost_w(const CostParams& cp, const PointCostWeights& wt, float* world, int Kl, int k0, float* cost,
+                       hipStream_t s);
 void launch_sim_suction(const SimViews& v, float* world, int Kl, float kp, float thresh, float reach,
                         const float* action, int apply, float* forces, int* flags, const int* gate, hipStream_t s);
 
@@ -383,6 +393,8 @@ struct m3_handle {
     float goal[7] = {0, 0, 0, 0, 0, 0, 1};
     int gripper_cmd = 0;
     int avoid_dyn_obs = 0;             // m3_set_avoid_dyn_obs (extension; 0 = the reference's compute_cost)
+    m3::PointCostWeights cost_weights = m3::POINT_COST_WEIGHTS_DEFAULT;   // m3_set_point_cost_weights (extension, point_env)
+    int weighted_instance = -1;        // m3_set_weighted_cost_instance: -1 by the weights (not the defaults bit for bit), 0 / 1 forced
     // world
     float world0[18];
     const float* world0_bound = nullptr;  // device, 18 floats (filled by world_from_sim)

@@ -16,10 +16,66 @@ int rollout_lanes_for(int Kl) {
     return 64;
 }
 
+// ---- weighted cost (m3_set_point_cost_weights): the general instance with point_cost_w, the nine weights a kernel argument
+// of their own (wave-uniform: scalar registers, loaded once) -- RolloutArgs and every other instance are untouched.  The same
+// four builds, picked by the same rule.
+__global__ __launch_bounds__(64) void k_rollout_point_w(const RolloutArgs a, const PointScene sc, const PointCostWeights wt) {
+    rollout_point_body<true, -1, true, true>(a, sc, &wt);
+}
+__global__ __launch_bounds__(64) void k_rollout_point_w_ref(const RolloutArgs a, const PointCostWeights wt) {
+    constexpr PointScene sc = POINT_SCENE_REFERENCE;
+    rollout_point_body<true, -1, true, true>(a, sc, &wt);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_rollout_point_w_occ2(
+    const RolloutArgs a, const PointScene sc, const PointCostWeights wt) {
+    rollout_point_body<true, -1, false, true>(a, sc, &wt);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_rollout_point_w_occ3(
+    const RolloutArgs a, const PointScene sc, const PointCostWeights wt) {
+    rollout_point_body<true, -1, false, true>(a, sc, &wt);
+}
+static void launch_rollout_point_weighted(const RolloutArgs& a, const PointScene& sc, const PointCostWeights& wt, int blocks,
+                                          hipStream_t s) {
+    switch (rollout_point_build(blocks, point_scene_is_reference(sc))) {
+        case BUILD_OCC3: hipLaunchKernelGGL(k_rollout_point_w_occ3, dim3(blocks), dim3(64), 0, s, a, sc, wt); break;
+        case BUILD_OCC2: hipLaunchKernelGGL(k_rollout_point_w_occ2, dim3(blocks), dim3(64), 0, s, a, sc, wt); break;
+        case BUILD_LONE_REF: hipLaunchKernelGGL(k_rollout_point_w_ref, dim3(blocks), dim3(64), 0, s, a, wt); break;
+        default: hipLaunchKernelGGL(k_rollout_point_w, dim3(blocks), dim3(64), 0, s, a, sc, wt); break;
+    }
+}
+// ... and the weighted group's twin: its own entry type (BatchRolloutEntryW: the entry + the handle's weights), so that handles
+// with different weights share one launch and the entries of the other kernels keep their size
+__global__ __launch_bounds__(64) void kb_rollout_point_w(const BatchRolloutEntryW* __restrict__ tab) {
+    rollout_point_body<true, -1, true, true>(tab[blockIdx.y].a, tab[blockIdx.y].sc, &tab[blockIdx.y].wt);
+}
+__global__ __launch_bounds__(64) void kb_rollout_point_w_ref(const BatchRolloutEntryW* __restrict__ tab) {
+    constexpr PointScene sc = POINT_SCENE_REFERENCE;
+    rollout_point_body<true, -1, true, true>(tab[blockIdx.y].a, sc, &tab[blockIdx.y].wt);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void kb_rollout_point_w_occ2(
+    const BatchRolloutEntryW* __restrict__ tab) {
+    rollout_point_body<true, -1, false, true>(tab[blockIdx.y].a, tab[blockIdx.y].sc, &tab[blockIdx.y].wt);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void kb_rollout_point_w_occ3(
+    const BatchRolloutEntryW* __restrict__ tab) {
+    rollout_point_body<true, -1, false, true>(tab[blockIdx.y].a, tab[blockIdx.y].sc, &tab[blockIdx.y].wt);
+}
+static void launch_rollout_point_weighted_batch(const BatchRolloutEntryW* tab, int blocks, int n, bool ref, hipStream_t s) {
+    const dim3 grid(blocks, n);
+    switch (rollout_point_build(blocks * n, ref)) {
+        case BUILD_OCC3: hipLaunchKernelGGL(kb_rollout_point_w_occ3, grid, dim3(64), 0, s, tab); break;
+        case BUILD_OCC2: hipLaunchKernelGGL(kb_rollout_point_w_occ2, grid, dim3(64), 0, s, tab); break;
+        case BUILD_LONE_REF: hipLaunchKernelGGL(kb_rollout_point_w_ref, grid, dim3(64), 0, s, tab); break;
+        default: hipLaunchKernelGGL(kb_rollout_point_w, grid, dim3(64), 0, s, tab); break;
+    }
+}
+
 // The form of a launch.  Instance -1: the general instance (every sampler mode, task at run time); 0..3: the instance with
 // the reference's default sampler and that task compiled in (rollout_point_task*.hip).  Only the general and the push_pull
 // instances carry the epilogue that leaves the workgroups' cost minima (rollout_point_kernel.hpp).
-RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc) {
+// weighted: the handle's cost weights are not the defaults (or the weighted instance is forced on): the general instance with
+// point_cost_w, whatever the sampler and the task.
+RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, bool weighted) {
 #if defined(M3_ABL_GENERAL_ONLY) || defined(M3_ABL_COUNT) || defined(M3_ABL_PHASES)   // (experiments: one kernel for all modes;
     // the instrumented builds keep their counters in this translation unit)
     const bool general = true;
@@ -27,9 +83,11 @@ RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc) {
     // push_pull without multi_modal is refused upstream (m3_rollout); a task outside 0..3 cannot reach here
     const bool general = a.sampling_random || a.mode_simple || a.cp.task < 0 || a.cp.task > 3 ||
                          (a.cp.task == 3 && !a.multi_modal) || a.scale_dev != nullptr /* update_cov */ ||
-                         a.cp.avoid_dyn_obs != 0 /* the extension: the dyn-obs contact force must be formed */;
+                         a.cp.avoid_dyn_obs != 0 /* the extension: the dyn-obs contact force must be formed */ ||
+                         weighted /* the extension: only the general instance has a weighted build */;
 #endif
     RolloutPlan p{};
+    p.weighted = weighted ? 1 : 0;
     p.instance = general ? -1 : a.cp.task;
     p.ref = point_scene_is_reference(sc) ? 1 : 0;
     p.lanes = a.lanes;
@@ -38,7 +96,9 @@ RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc) {
     return p;
 }
 
-void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const RolloutPlan& p, hipStream_t s) {
+void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const PointCostWeights& wt, const RolloutPlan& p,
+                          hipStream_t s) {
+    if (p.weighted) { launch_rollout_point_weighted(a, sc, wt, p.blocks, s); return; }
     switch (p.instance) {
         case -1: launch_rollout_point_instance<true, -1>(a, sc, p.blocks, s); break;
         case 0: launch_rollout_point_nav(a, sc, p.blocks, s); break;
@@ -57,6 +117,10 @@ void launch_rollout_point_batch(const BatchRolloutEntry* tab, int n, const Rollo
         case 2: launch_rollout_point_pull_batch(tab, p.blocks, n, ref, s); break;
         default: launch_rollout_point_pushpull_batch(tab, p.blocks, n, ref, s); break;
     }
+}
+
+void launch_rollout_point_batch_w(const BatchRolloutEntryW* tab, int n, const RolloutPlan& p, hipStream_t s) {
+    launch_rollout_point_weighted_batch(tab, p.blocks, n, p.ref != 0, s);
 }
 
 // delta [K][T][nu] (reference layout) -> [T][K][nu]
@@ -175,6 +239,20 @@ __global__ void k_sim_cost(const CostParams cp, float* wd, int Kl, int k0, float
 void launch_sim_cost(const CostParams& cp, float* world, int Kl, int k0, float* cost,
                      hipStream_t s) {
     hipLaunchKernelGGL(k_sim_cost, dim3((Kl + 255) / 256), dim3(256), 0, s, cp, world, Kl, k0, cost);
+}
+// ... with the handle's cost weights (m3_set_point_cost_weights): what k_rollout_point_w evaluates after each step
+__global__ void k_sim_cost_w(const CostParams cp, const PointCostWeights wt, float* wd, int Kl, int k0, float* cost) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= Kl) return;
+    PointWorld w;
+    soa_load(wd, Kl, i, w);
+    cost[i] = point_cost_w(cp, wt, w, k0 + i);
+    float* p = wd + i;  // only the pending force changes
+    p[18 * Kl] = w.fRx; p[19 * Kl] = w.fRy; p[20 * Kl] = w.fBx; p[21 * Kl] = w.fBy;
+}
+void launch_sim_cost_w(const CostParams& cp, const PointCostWeights& wt, float* world, int Kl, int k0, float* cost,
+                       hipStream_t s) {
+    hipLaunchKernelGGL(k_sim_cost_w, dim3((Kl + 255) / 256), dim3(256), 0, s, cp, wt, world, Kl, k0, cost);
 }
 
 // wrapper views (AoS, torch-owned) -> SoA world.  dof_state row = [x, vx, y, vy]

@@ -56,8 +56,10 @@ __device__ __forceinline__ void load_world_from_sim(const float* dof, const floa
 // it disappear from the instance.  Measured at C2: one kernel for everything 0.1555 ms per command, sampler
 // mode compiled in 0.1530, task compiled in as well 0.143 (same results bit for bit: only which code exists).
 // LONE: a build for one resident wavefront per SIMD (planar_dyn.hpp: predicated rows, two-level broad phase)
-template <bool GENERAL, int TASK, bool LONE = true>
-__device__ __forceinline__ void rollout_point_body(const RolloutArgs& a_, const PointScene& sc) {
+// WEIGHTED: the running cost is point_cost_w with *wt (k_rollout_point_w below; wt is not read otherwise)
+template <bool GENERAL, int TASK, bool LONE = true, bool WEIGHTED = false>
+__device__ __forceinline__ void rollout_point_body(const RolloutArgs& a_, const PointScene& sc,
+                                                   const PointCostWeights* wt = nullptr) {
     RolloutArgs a = a_;
     if constexpr (!GENERAL) {
         a.sampling_random = 0; a.mode_simple = 0;
@@ -156,7 +158,9 @@ __device__ __forceinline__ void rollout_point_body(const RolloutArgs& a_, const 
         point_step<false, LONE>(sc, w, u0, u1, /*need_dyn_force=*/a.cp.task == 0 || a.cp.avoid_dyn_obs != 0, pc_);
 
         // ---- A7/A8: running cost on the post-step state ----
-        const float c = point_cost(a.cp, w, k);
+        float c;
+        if constexpr (WEIGHTED) c = point_cost_w(a.cp, *wt, w, k);
+        else c = point_cost(a.cp, w, k);
         M3_PH(5);
 
         // ---- outputs, time-major ----
@@ -224,12 +228,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
                                                                                                       const PointScene sc) {
     rollout_point_body<GENERAL, TASK, false>(a, sc);
 }
+// which of the builds a launch of `waves` wavefronts takes -- the one rule of every launcher below
+enum RolloutBuild { BUILD_LONE, BUILD_LONE_REF, BUILD_OCC2, BUILD_OCC3 };
+inline RolloutBuild rollout_point_build(int waves, bool ref) {
+    if (rollout_three_waves(waves)) return BUILD_OCC3;
+    if (rollout_two_waves(waves)) return BUILD_OCC2;
+    return ref ? BUILD_LONE_REF : BUILD_LONE;
+}
 template <bool GENERAL, int TASK>
 inline void launch_rollout_point_instance(const RolloutArgs& a, const PointScene& sc, int blocks, hipStream_t s) {
-    if (rollout_three_waves(blocks)) hipLaunchKernelGGL((k_rollout_point_occ3<GENERAL, TASK>), dim3(blocks), dim3(64), 0, s, a, sc);
-    else if (rollout_two_waves(blocks)) hipLaunchKernelGGL((k_rollout_point_occ2<GENERAL, TASK>), dim3(blocks), dim3(64), 0, s, a, sc);
-    else if (point_scene_is_reference(sc)) hipLaunchKernelGGL((k_rollout_point_ref<GENERAL, TASK>), dim3(blocks), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((k_rollout_point<GENERAL, TASK>), dim3(blocks), dim3(64), 0, s, a, sc);
+    switch (rollout_point_build(blocks, point_scene_is_reference(sc))) {
+        case BUILD_OCC3: hipLaunchKernelGGL((k_rollout_point_occ3<GENERAL, TASK>), dim3(blocks), dim3(64), 0, s, a, sc); break;
+        case BUILD_OCC2: hipLaunchKernelGGL((k_rollout_point_occ2<GENERAL, TASK>), dim3(blocks), dim3(64), 0, s, a, sc); break;
+        case BUILD_LONE_REF: hipLaunchKernelGGL((k_rollout_point_ref<GENERAL, TASK>), dim3(blocks), dim3(64), 0, s, a); break;
+        default: hipLaunchKernelGGL((k_rollout_point<GENERAL, TASK>), dim3(blocks), dim3(64), 0, s, a, sc); break;
+    }
 }
 
 // ---- batched command (m3_batch_command): one launch for a group of handles that share the instance, K, T and lanes.
@@ -260,12 +273,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
 template <bool GENERAL, int TASK>
 inline void launch_rollout_point_batch_instance(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s) {
     const dim3 grid(blocks, n);
-    const int waves = blocks * n;
-    if (rollout_three_waves(waves)) hipLaunchKernelGGL((kb_rollout_point_occ3<GENERAL, TASK>), grid, dim3(64), 0, s, tab);
-    else if (rollout_two_waves(waves)) hipLaunchKernelGGL((kb_rollout_point_occ2<GENERAL, TASK>), grid, dim3(64), 0, s, tab);
-    else if (ref) hipLaunchKernelGGL((kb_rollout_point_ref<GENERAL, TASK>), grid, dim3(64), 0, s, tab);
-    else hipLaunchKernelGGL((kb_rollout_point<GENERAL, TASK>), grid, dim3(64), 0, s, tab);
+    switch (rollout_point_build(blocks * n, ref)) {
+        case BUILD_OCC3: hipLaunchKernelGGL((kb_rollout_point_occ3<GENERAL, TASK>), grid, dim3(64), 0, s, tab); break;
+        case BUILD_OCC2: hipLaunchKernelGGL((kb_rollout_point_occ2<GENERAL, TASK>), grid, dim3(64), 0, s, tab); break;
+        case BUILD_LONE_REF: hipLaunchKernelGGL((kb_rollout_point_ref<GENERAL, TASK>), grid, dim3(64), 0, s, tab); break;
+        default: hipLaunchKernelGGL((kb_rollout_point<GENERAL, TASK>), grid, dim3(64), 0, s, tab); break;
+    }
 }
-
 
 }  // namespace m3

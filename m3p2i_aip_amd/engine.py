@@ -221,6 +221,27 @@ class HipEngine:
         """Extension (off = the reference): push / pull / push_pull add get_motion_cost like navigation does."""
         self._ck(self.lib.m3_set_avoid_dyn_obs(self._h, int(bool(on))))
 
+    def set_point_cost_weights(self, weights=None):
+        """Extension, point_env: the weights of the task costs (a mapping with keys of _lib.COST_WEIGHT_DEFAULTS, missing keys =
+        the reference's literal; None = all defaults).  They apply from the next command / rollout / cost call."""
+        if weights is None:
+            self._ck(self.lib.m3_set_point_cost_weights(self._h, None))
+            return
+        unknown = sorted(set(weights) - set(L.COST_WEIGHT_DEFAULTS))
+        if unknown:
+            raise ValueError(f"unknown cost weight(s) {unknown}: one of {list(L.COST_WEIGHT_DEFAULTS)}")
+        w = L.PointCostWeights(**{**L.COST_WEIGHT_DEFAULTS, **{k: float(v) for k, v in weights.items()}})
+        self._ck(self.lib.m3_set_point_cost_weights(self._h, C.byref(w)))
+
+    def point_cost_weights(self):
+        w = L.PointCostWeights()
+        self._ck(self.lib.m3_get_point_cost_weights(self._h, C.byref(w)))
+        return {n: getattr(w, n) for n in L.COST_WEIGHT_DEFAULTS}
+
+    def set_weighted_cost_instance(self, on=-1):
+        """-1: the weighted kernels exactly when the weights are not the defaults (default); 1 / 0 forced (tests, A/B)."""
+        self._ck(self.lib.m3_set_weighted_cost_instance(self._h, int(on)))
+
     def set_multi_modal(self, mm):
         self._ck(self.lib.m3_set_multi_modal(self._h, int(bool(mm))))
 

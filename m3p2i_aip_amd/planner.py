@@ -364,6 +364,8 @@ class MPPI():
         if avoid != getattr(self, "_avoid_dyn_obs", False):     # (extension, off by default: cost_functions.Objective)
             self._engine.set_avoid_dyn_obs(avoid)
             self._avoid_dyn_obs = avoid
+        if hasattr(o, "push_cost_weights"):     # (extension, off by default: no call while the weights are the defaults)
+            o.push_cost_weights(self._engine)
 
     def _bind_world(self):
         s = self._sim

@@ -1,0 +1,88 @@
+"""What the weighted cost instances (m3_set_point_cost_weights) cost: m3_command at C2 (push, K = 2000, T = 30) on
+  per_task           the default handle: the push instance (what bench.py's headline runs)
+  general            the same handle with avoid_dyn_obs: the general instance, the weighted build's twin
+  weighted_default   the weighted build forced on at the default weights (m3_set_weighted_cost_instance 1)
+  weighted           push_align = 2.5: the weighted build by the automatic choice
+  general_avoid_w    avoid_dyn_obs + weights: the weighted build with the dyn-obs term (compare with `general`)
+HIP events around `--iters` commands after `--warmup`, ms per command, median of `--repeats`; one JSON line.  A library
+without the entry points (an older build, to set next to this one: run this file from that tree) measures the first two.
+
+    python tools/cost_weights_bench.py [--json out.json] [--iters 50] [--warmup 10] [--repeats 5]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+K, T = 2000, 30
+WORLD = np.array([0.1, 1.5, 0, 0, 0.0, 2.0, 1, 0, 0, 0, 0, -2.0, 2.0, 1, 0, 0, 0, 0], np.float32)
+
+
+def noise(torch):
+    g = torch.Generator().manual_seed(3)
+    knots = torch.randn(K, 2, T // 4, generator=g)
+    return torch.nn.functional.interpolate(knots, size=T, mode="linear", align_corners=True).permute(0, 2, 1).contiguous().numpy()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--json")
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=5)
+    a = ap.parse_args()
+    import torch
+    from m3p2i_aip_amd import _lib as L
+    from m3p2i_aip_amd.engine import HipEngine, make_config
+    has = hasattr(HipEngine, "set_point_cost_weights")
+    variants = [("per_task", {}), ("general", dict(avoid=True))]
+    if has:
+        variants += [("weighted_default", dict(force=1)), ("weighted", dict(w=dict(push_align=2.5))),
+                     ("general_avoid_w", dict(avoid=True, w=dict(push_align=2.5)))]
+    delta = noise(torch)
+    engines = {}
+    for name, v in variants:
+        e = HipEngine(make_config(K=K, T=T, nu=2, u_min=[-3, -3], u_max=[3, 3], noise_sigma_diag=[3, 3]))
+        e.set_noise(delta)
+        e.set_objective("push", (-3.75, -3.75))
+        e.set_world_point_raw(WORLD)
+        if v.get("avoid"):
+            e.set_avoid_dyn_obs(True)
+        if v.get("w"):
+            e.set_point_cost_weights(v["w"])
+        if v.get("force") is not None:
+            e.set_weighted_cost_instance(v["force"])
+        engines[name] = e
+    samples = {name: [] for name, _ in variants}
+    for _ in range(a.repeats):          # the variants interleaved inside every repeat
+        for name, _ in variants:
+            e = engines[name]
+            e.reset()
+            for _ in range(a.warmup):
+                e.command()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.iters):
+                e.command()
+            e1.record()
+            e1.synchronize()
+            samples[name].append(e0.elapsed_time(e1) / a.iters)
+    out = dict(tool="cost_weights_bench", build_id=L.load().m3_build_id().decode(), device=torch.cuda.get_device_name(0),
+               K=K, T=T, task="push", iters=a.iters, warmup=a.warmup, repeats=a.repeats,
+               ms_per_command={n: dict(median=float(np.median(s)), min=float(min(s)), max=float(max(s))) for n, s in samples.items()})
+    for e in engines.values():
+        e.close()
+    line = json.dumps(out)
+    print(line)
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
