@@ -128,6 +128,7 @@ def load():
     lib.m3o_noise_fill.argtypes = [C.POINTER(Cfg), C.c_ulonglong, C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_float)]
     lib.m3o_gauss_fill.argtypes = [C.c_ulonglong, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int,
                                    FP]
+    lib.m3o_stream_raw.argtypes = [C.c_ulonglong, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
     lib.m3o_ori_cube2goal.argtypes = [FP, FP]
     lib.m3o_ori_cube2goal.restype = C.c_float
     lib.m3o_ori_ee2cube.argtypes = [FP, FP, C.c_float, FP]

@@ -188,6 +188,7 @@ void m3o_simple_update(const m3o_cfg* cfg, const float* S, const float* perturbe
 /* xoshiro128++ / Box-Muller stream shared with the kernels (spec in DESIGN.md) */
 float m3o_gauss(unsigned long long seed, unsigned call, unsigned k, unsigned t, unsigned j);
 
+void m3o_stream_raw(unsigned long long seed, unsigned call, unsigned k, unsigned t, unsigned pair, unsigned* r0, unsigned* r1);
 void m3o_gauss_fill(unsigned long long seed, unsigned call, int k0, int n, int T, int nu,
                     float* out);
 void m3o_noise_fill(const m3o_cfg* cfg, unsigned long long seed, unsigned call, int k0, int n, float* out);

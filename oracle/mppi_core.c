@@ -454,12 +454,19 @@ static unsigned xoshiro128pp(unsigned s[4]) {
     s[3] = rotl32(s[3], 11);
     return result;
 }
-float m3o_gauss(unsigned long long seed, unsigned call, unsigned k, unsigned t, unsigned j) {
+/* the two 32-bit outputs behind the pair's uniforms (exported for tests/test_noise_stream_cpu.py; a copy of the header's
+ * key line like this whole stream: agreement with it shows the twins agree, not that either is right) */
+void m3o_stream_raw(unsigned long long seed, unsigned call, unsigned k, unsigned t, unsigned pair, unsigned* r0, unsigned* r1) {
     unsigned long long x = seed ^ (0xD1B54A32D192ED03ULL * (unsigned long long)(call + 1u));
-    x ^= ((unsigned long long)k << 32) | ((unsigned long long)t << 8) | (unsigned long long)(j >> 1);
+    x ^= ((unsigned long long)k << 32) | ((unsigned long long)t << 8) | (unsigned long long)pair;
     unsigned long long a = splitmix64(&x), b = splitmix64(&x);
     unsigned s[4] = {(unsigned)a, (unsigned)(a >> 32), (unsigned)b, (unsigned)(b >> 32)};
-    unsigned r0 = xoshiro128pp(s), r1 = xoshiro128pp(s);
+    *r0 = xoshiro128pp(s);
+    *r1 = xoshiro128pp(s);
+}
+float m3o_gauss(unsigned long long seed, unsigned call, unsigned k, unsigned t, unsigned j) {
+    unsigned r0, r1;
+    m3o_stream_raw(seed, call, k, t, j >> 1, &r0, &r1);
     /* (0,1] and [0,1) uniforms from the top 24 bits */
     float u0 = ((float)(r0 >> 8) + 1.0f) * (1.0f / 16777216.0f);
     float u1 = (float)(r1 >> 8) * (1.0f / 16777216.0f);
