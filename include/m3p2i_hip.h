@@ -241,6 +241,16 @@ int m3_enable_timing(m3_handle* h, int on);
  * a power of two in 1..64, or 0 = choose from K_local so that the waves fill the chip
  * (DESIGN.md "Lanes per wavefront").  Results do not depend on it. */
 int m3_set_rollout_lanes(m3_handle* h, int lanes);
+/* point_env: wavefronts per 64 samples in the rollout kernel of the navigation and push tasks (default sampler, default cost
+ * weights, at most as many wavefronts as the chip has SIMDs, T <= 31) -- 0 = one wavefront does everything, 1 = two: one runs
+ * the dynamics alone, its companion assembles the actions ahead of it and forms costs, stores and sums behind it (hand-over
+ * through LDS), wherever that form exists; -1 (default) = automatic: 1 where it exists and was measured not slower.  Every
+ * other rollout (pull, push_pull, the other samplers, weighted costs, m3_batch_command, episodes) keeps one wavefront whatever
+ * the value.  Results do not depend on it.  A hand-over wait that runs out (bounded) invalidates that rollout's results and
+ * makes the handle's NEXT m3_rollout / m3_command fail with M3_ERR_HIP.  DESIGN.md section 6. */
+int m3_set_point_rollout_form(m3_handle* h, int form);
+/* the form of the last rollout launch of m3_rollout / m3_command (0, 1); -1 before the first */
+int m3_point_rollout_form_used(m3_handle* h);
 /* panda_env: lanes that simulate ONE sample in the rollout kernel -- 1 (a lane per sample, 64 samples per wavefront), 8 or
  * 16 (the lanes of a DPP row share a sample: the contact solver's joint-space rows run across them; eight / four sample
  * slots per wavefront), 0 = automatic: by size (16 while the launch has no more wavefronts than the chip has SIMDs, then 8,

@@ -110,6 +110,8 @@ SYMBOLS = [
     ("m3_set_stream", C.c_int, [_H, C.c_void_p]),
     ("m3_enable_timing", C.c_int, [_H, C.c_int]),
     ("m3_set_rollout_lanes", C.c_int, [_H, C.c_int]),
+    ("m3_set_point_rollout_form", C.c_int, [_H, C.c_int]),
+    ("m3_point_rollout_form_used", C.c_int, [_H]),
     ("m3_set_panda_lanes_per_sample", C.c_int, [_H, C.c_int]),
     ("m3_panda_lanes_per_sample_used", C.c_int, [_H]),
     ("m3_panda_near_share", C.c_int, [_H]),

@@ -305,6 +305,21 @@ extern "C" int m3_create(const m3_config* c, m3_handle** out) {
         if (rc == M3_OK && Kl == Kg && Kg >= 2 && Kl <= PANDA_REACH_REC_MAX_K &&
             hipMalloc((void**)&h->panda_reach_rec, (size_t)T * REACH_REC * (size_t)Kl * f) != hipSuccess) rc = M3_ERR_HIP;
     }
+    if (rc == M3_OK && c->env_type == M3_ENV_POINT && !c->sim_only) {
+        // the word the two-wavefront rollout form reports a hand-over wait that ran out into (mapped host memory: m3_rollout
+        // reads it without a synchronisation, so it refuses the rollout AFTER the one that failed)
+        void* p = nullptr;
+        void* d = nullptr;
+        if (hipHostMalloc(&p, sizeof(int), hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&d, p, 0) != hipSuccess) {
+            if (p) (void)hipHostFree(p);
+            h->err = "m3_create: the point rollout's error word (mapped host memory) could not be allocated";
+            rc = M3_ERR_HIP;
+        } else {
+            h->rollout_err = (int*)p;
+            h->rollout_err_dev = (int*)d;
+            *h->rollout_err = 0;
+        }
+    }
     if (rc == M3_OK && hipMalloc((void**)&h->wcount, (size_t)(T + 2) * sizeof(int)) != hipSuccess) rc = M3_ERR_HIP;
     if (rc == M3_OK && hipMemset(h->wcount, 0, (size_t)(T + 2) * sizeof(int)) != hipSuccess) rc = M3_ERR_HIP;
     if (rc == M3_OK) {
@@ -350,6 +365,7 @@ extern "C" void m3_destroy(m3_handle* h) {
         if (h->peer_ipc[p] && h->peer_base[p]) (void)hipIpcCloseMemHandle(h->peer_base[p]);
     if (h->xb) (void)hipFree(h->xb);
     if (h->panda_busy_hint) (void)hipHostFree(h->panda_busy_hint);
+    if (h->rollout_err) (void)hipHostFree(h->rollout_err);
     if (h->panda_busy_count) (void)hipFree(h->panda_busy_count);
     if (h->panda_reach_rec) (void)hipFree(h->panda_reach_rec);
     for (auto& ev : h->ev)
@@ -374,6 +390,17 @@ extern "C" int m3_set_rollout_lanes(m3_handle* h, int lanes) {
         return fail(h, M3_ERR_BAD_ARG, "m3_set_rollout_lanes: lanes must be 0 (auto) or a power of two in 1..64");
     h->lanes_override = lanes;
     return M3_OK;
+}
+
+extern "C" int m3_set_point_rollout_form(m3_handle* h, int form) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (form < -1 || form > 1) return fail(h, M3_ERR_BAD_ARG, "m3_set_point_rollout_form: 0 (one wavefront), 1 (two) or -1 (automatic)");
+    h->point_form = form;
+    return M3_OK;
+}
+
+extern "C" int m3_point_rollout_form_used(m3_handle* h) {
+    return h ? h->point_form_used : -1;
 }
 
 extern "C" int m3_set_panda_lanes_per_sample(m3_handle* h, int lps) {
@@ -1021,11 +1048,12 @@ static void fill_panda_args(m3_handle* h, const RolloutArgs& a, PandaArgs& pa) {
 // a handle's rollout, as m3_rollout launches it and m3_batch_command groups it: the arguments (prepare_rollout), for panda_env
 // the panda part (fill_panda_args), and the form (p; a and pa become what the kernels receive).  Keeps the handle's record of
 // what the launch leaves: the rows of minima (wave_min_rows), the panda form (panda_lps_used)
-static int plan_rollout(m3_handle* h, RolloutArgs& a, PandaArgs& pa, RolloutPlan& p) {
+static int plan_rollout(m3_handle* h, RolloutArgs& a, PandaArgs& pa, RolloutPlan& p, bool own_launch = false) {
     const int rc = prepare_rollout(h, a);
     if (rc != M3_OK) return rc;
     if (h->cfg.env_type == M3_ENV_POINT) {
-        p = plan_rollout_point(a, h->scene, weighted_cost(h));
+        // (the two-wavefront form: m3_rollout's own launch only, and only with the error word to report into)
+        p = plan_rollout_point(a, h->scene, weighted_cost(h), (own_launch && h->rollout_err_dev) ? h->point_form : 0);
     } else {
         fill_panda_args(h, a, pa);
         p = plan_rollout_panda(a, pa);
@@ -1042,10 +1070,14 @@ extern "C" int m3_rollout(m3_handle* h) {
     RolloutArgs a;
     PandaArgs pa;
     RolloutPlan p;
-    const int rc = plan_rollout(h, a, pa, p);
+    if (h->rollout_err && *(volatile const int*)h->rollout_err != 0)
+        return fail(h, M3_ERR_HIP, "m3_rollout: a hand-over wait between the two wavefronts of an earlier rollout launch ran out "
+                                   "(its results are invalid); m3_set_point_rollout_form(h, 0) avoids the form");
+    const int rc = plan_rollout(h, a, pa, p, true);
     if (rc != M3_OK) return rc;
+    if (h->cfg.env_type == M3_ENV_POINT) h->point_form_used = p.form;
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->cost_weights, p, h->stream);
+    if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->cost_weights, p, h->stream, h->rollout_err_dev);
     else launch_rollout_panda(a, pa, h->pscene, p, h->stream);
     HIPCHK(h, hipGetLastError());
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));

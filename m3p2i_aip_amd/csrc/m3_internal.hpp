@@ -190,8 +190,11 @@ struct RolloutPlan {
     int lanes, blocks;   // active lanes per wavefront, rollout workgroups
     int rows;            // rows of minima the launch leaves in a.wave_min (wave_min.hpp; 0: none)
     int weighted;        // point_env: the weighted build of the general instance (m3_set_point_cost_weights; instance == -1)
+    int form;            // point_env: 0 one wavefront per 64 samples, 1 dynamics + companion wavefront (rollout_point_kernel.hpp:
+                         // rollout_point_body2); m3_rollout only -- the batched and episode paths plan with form_request 0
 };
-RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, bool weighted);
+// form_request: m3_set_point_rollout_form's value (0 one wavefront, 1 two wherever available, -1 by rollout_companion_pays)
+RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, bool weighted, int form_request = 0);
 // one launch of the plan's instance for n handles of K_local = a.Kl and the same plan (tab: device, n entries)
 void launch_rollout_point_batch(const BatchRolloutEntry* tab, int n, const RolloutPlan& p, hipStream_t s);
 void launch_rollout_point_batch_w(const BatchRolloutEntryW* tab, int n, const RolloutPlan& p, hipStream_t s);   // p.weighted
@@ -202,7 +205,10 @@ void launch_rollout_point_pushpull_batch(const BatchRolloutEntry* tab, int block
 
 // ---- launchers (defined in the .hip files) ---------------------------------------------
 void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const PointCostWeights& wt /* read if p.weighted */,
-                          const RolloutPlan& p, hipStream_t s);
+                          const RolloutPlan& p, hipStream_t s, int* err = nullptr /* p.form == 1: the hand-over's error word */);
+// the two-wavefront form of the navigation / push instances (p.form == 1)
+void launch_rollout_point_nav2(const RolloutArgs& a, const PointScene& sc, int blocks, int* err, hipStream_t s);
+void launch_rollout_point_push2(const RolloutArgs& a, const PointScene& sc, int blocks, int* err, hipStream_t s);
 void launch_rollout_point_nav(const RolloutArgs& a, const PointScene& sc, int blocks, hipStream_t s);
 void launch_rollout_point_push(const RolloutArgs& a, const PointScene& sc, int blocks, hipStream_t s);
 void launch_rollout_point_pull(const RolloutArgs& a, const PointScene& sc, int blocks, hipStream_t s);
@@ -247,6 +253,17 @@ constexpr int M3_CUS = 256;
 constexpr int M3_SIMDS = 1024;
 inline bool rollout_two_waves(int wavefronts) { return wavefronts > M3_SIMDS; }
 inline bool rollout_three_waves(int wavefronts) { return wavefronts > 4 * M3_SIMDS; }   // (measured: equal at 4 per SIMD, -11 % at 8)
+// The two-wavefront form (dynamics + companion, rollout_point_kernel.hpp) puts two wavefronts of > 256 VGPRs on two SIMDs of
+// one CU: up to M3_SIMDS / 2 workgroups every wavefront still has a SIMD of its own.  The automatic rule takes the form up to
+// ROLLOUT_COMPANION_MAX_BLOCKS workgroups: the largest count at which it was not slower than the one-wavefront form in the
+// K sweep of profiles/companion_wave/k_sweep_push.json ("Companion wavefront").
+constexpr int ROLLOUT_COMPANION_MAX_BLOCKS = M3_SIMDS / 2;
+inline bool rollout_companion_pays(int blocks) { return blocks <= ROLLOUT_COMPANION_MAX_BLOCKS; }
+// its LDS: 16 bytes of progress words, then per step [8][64] floats (six of the record, the two scaled controls)
+constexpr int R2_COMPS = 8;
+constexpr size_t R2_LDS_MAX = 64 * 1024;   // what a launch gets without a function attribute
+inline size_t rollout_point2_lds_bytes(int T) { return 16 + (size_t)T * R2_COMPS * 64 * sizeof(float); }
+inline bool rollout_point2_fits(int T) { return T >= 1 && rollout_point2_lds_bytes(T) <= R2_LDS_MAX; }
 int mins_workgroups(int Kg);
 int topk_workgroups(int Kg);
 int ladder_workgroups(int Kg);
@@ -413,6 +430,10 @@ struct m3_handle {
     int* local_top_idx = nullptr;  // regen: top_idx of the local pre-gather selection (scratch)
     unsigned calls = 0;
     int lanes_override = 0;  // 0 = automatic (rollout_lanes_for)
+    int point_form = -1;          // m3_set_point_rollout_form: 0, 1, -1 = automatic
+    int point_form_used = -1;     // the form of the last rollout launch (m3_point_rollout_form_used)
+    int* rollout_err = nullptr;   // mapped host word (m3_create, point_env): a hand-over wait of the two-wavefront form ran out
+    int* rollout_err_dev = nullptr;
     int* panda_busy_hint = nullptr;   // hipHostMalloc (m3_create, panda_env): see PandaArgs::busy_hint
     int* panda_busy_hint_dev = nullptr;   // the same word as the device sees it
     unsigned long long* panda_busy_count = nullptr;

@@ -75,7 +75,10 @@ static void launch_rollout_point_weighted_batch(const BatchRolloutEntryW* tab, i
 // instances carry the epilogue that leaves the workgroups' cost minima (rollout_point_kernel.hpp).
 // weighted: the handle's cost weights are not the defaults (or the weighted instance is forced on): the general instance with
 // point_cost_w, whatever the sampler and the task.
-RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, bool weighted) {
+// form_request: the two-wavefront form (RolloutPlan::form = 1) exists for the navigation and push instances in the builds with
+// one resident wavefront per SIMD, with the default weights and a horizon whose tables fit its LDS; 1 takes it wherever it
+// exists, -1 where rollout_companion_pays as well, 0 never (m3_batch_command, the episode paths).
+RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, bool weighted, int form_request) {
 #if defined(M3_ABL_GENERAL_ONLY) || defined(M3_ABL_COUNT) || defined(M3_ABL_PHASES)   // (experiments: one kernel for all modes;
     // the instrumented builds keep their counters in this translation unit)
     const bool general = true;
@@ -93,12 +96,21 @@ RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, bool 
     p.lanes = a.lanes;
     p.blocks = (a.Kl + a.lanes - 1) / a.lanes;
     p.rows = (a.wave_min && (p.instance == -1 || p.instance == 3)) ? p.blocks : 0;
+    const RolloutBuild build = rollout_point_build(p.blocks, p.ref != 0);
+    const bool exists = (p.instance == 0 || p.instance == 1) && !weighted && (build == BUILD_LONE || build == BUILD_LONE_REF) &&
+                        rollout_point2_fits(a.T);
+    p.form = (exists && (form_request == 1 || (form_request < 0 && rollout_companion_pays(p.blocks)))) ? 1 : 0;
     return p;
 }
 
 void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const PointCostWeights& wt, const RolloutPlan& p,
-                          hipStream_t s) {
+                          hipStream_t s, int* err) {
     if (p.weighted) { launch_rollout_point_weighted(a, sc, wt, p.blocks, s); return; }
+    if (p.form == 1) {
+        if (p.instance == 0) launch_rollout_point_nav2(a, sc, p.blocks, err, s);
+        else launch_rollout_point_push2(a, sc, p.blocks, err, s);
+        return;
+    }
     switch (p.instance) {
         case -1: launch_rollout_point_instance<true, -1>(a, sc, p.blocks, s); break;
         case 0: launch_rollout_point_nav(a, sc, p.blocks, s); break;

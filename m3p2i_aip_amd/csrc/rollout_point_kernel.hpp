@@ -245,6 +245,154 @@ inline void launch_rollout_point_instance(const RolloutArgs& a, const PointScene
     }
 }
 
+// ---- the two-wavefront form of the lone builds (navigation and push; plan_rollout_point: RolloutPlan::form == 1) ----
+// For tasks 0 and 1 point_cost writes nothing back into the world, so everything of the loop body but point_step is either
+// a function of (delta, mean, k, t) alone or a pure consumer of the post-step state.  A 128-thread workgroup splits it:
+//   wave 0, dynamics:  world + pend in, per step { controls of its lane from LDS, point_step, six floats of the record into
+//                      LDS }, pend out.  No global access inside the loop.
+//   wave 1, companion: first the action side of all T steps (loads, clamp, scale, null action, `actions` store, controls
+//                      into LDS), then, trailing the dynamics wave, per recorded step { point_cost on a world filled from the
+//                      record, `states` / `cost_h` stores, J / S / g in step order }, finally J.
+// Same expressions in the same order per sample as rollout_point_body<false, TASK>: same bits.
+// Hand-over: dynamic LDS, [0] "steps of controls ready" (writer: companion), [1] "steps recorded" (writer: dynamics), both
+// monotonic, stored with workgroup-scope release behind the data they cover and polled relaxed with one workgroup-scope
+// acquire behind the poll; tables [t][component][lane] (every ds access of a wave conflict-free).  Both polls are bounded:
+// a wait that runs out sets *err (the host refuses the handle's next rollout) and the wave leaves its loop.
+constexpr unsigned R2_SPINS_DYN = 1u << 16;    // polls of "controls ready" (~100 clocks each; the companion waits on memory only)
+constexpr unsigned R2_SPINS_COMP = 1u << 16;   // polls of "steps recorded", an s_sleep of ~256 clocks between two
+__device__ __forceinline__ unsigned r2_peek(const unsigned* word) {
+    return __builtin_amdgcn_readfirstlane(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+}
+template <int TASK>
+__device__ __forceinline__ void rollout_point_body2(const RolloutArgs& a_, const PointScene& sc, int* err) {
+    static_assert(TASK == 0 || TASK == 1, "the cost of pull / push_pull stages the suction force of the next step");
+    extern __shared__ __attribute__((aligned(16))) float r2_lds[];
+    RolloutArgs a = a_;
+    a.sampling_random = 0; a.mode_simple = 0;
+    a.noise_abs_cost = 0; a.full_sigma = 0; a.scale_dev = nullptr;
+    a.cp.avoid_dyn_obs = 0;
+    a.cp.task = TASK;
+    unsigned* const words = reinterpret_cast<unsigned*>(r2_lds);
+    float* const tab = r2_lds + 4;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int lane = (int)threadIdx.x & 63;
+    if (threadIdx.x == 0) { words[0] = 0u; words[1] = 0u; }
+    __syncthreads();   // (the only barrier: before any lane leaves, outside the step loop)
+    const int slot = blockIdx.x * a.lanes + lane;
+    if (lane >= a.lanes || slot >= a.Kl) return;
+    const int i = a.order ? a.order[slot] : slot;
+    const int Kl = a.Kl, T = a.T;
+    const int k = a.k0 + i;
+#define M3_R2(t, c) tab[((t) * R2_COMPS + (c)) * 64 + lane]
+    if (wave == 0) {
+        PointWorld w;
+        if (a.sim_dof) load_world_from_sim(a.sim_dof, a.sim_root, a.sim_box, a.sim_dyn, w);
+        else load_world(a.world0, w);
+        w.fRx = a.pend[0 * Kl + i]; w.fRy = a.pend[1 * Kl + i];
+        w.fBx = a.pend[2 * Kl + i]; w.fBy = a.pend[3 * Kl + i];
+        unsigned ready = 0u;   // cached copy of words[0]
+        bool ok = true;
+        auto controls = [&](int t, float& u0, float& u1) {
+            if (ready < (unsigned)(t + 1)) {
+                for (unsigned spins = 0u; (ready = r2_peek(&words[0])) < (unsigned)(t + 1);)
+                    if (++spins > R2_SPINS_DYN) { *err = 1; ok = false; break; }
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            }
+            u0 = M3_R2(t, 6); u1 = M3_R2(t, 7);
+        };
+        float n0, n1;
+        controls(0, n0, n1);
+        for (int t = 0; t < T && ok; ++t) {
+            const float u0 = n0, u1 = n1;
+            if (t + 1 < T) controls(t + 1, n0, n1);   // (issued before step t is simulated, as fetch() is)
+            point_step<false, true>(sc, w, u0, u1, /*need_dyn_force=*/TASK == 0);
+            M3_R2(t, 0) = w.rx; M3_R2(t, 1) = w.rvx; M3_R2(t, 2) = w.ry; M3_R2(t, 3) = w.rvy;
+            if constexpr (TASK == 0) { M3_R2(t, 4) = w.fcDx; M3_R2(t, 5) = w.fcDy; }
+            else { M3_R2(t, 4) = w.B.x; M3_R2(t, 5) = w.B.y; }
+            __hip_atomic_store(&words[1], (unsigned)(t + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        a.pend[0 * Kl + i] = w.fRx; a.pend[1 * Kl + i] = w.fRy;
+        a.pend[2 * Kl + i] = w.fBx; a.pend[3 * Kl + i] = w.fBy;
+    } else {
+        const bool is_last = (k == a.Kg - 1);
+        const bool first_half = k < a.cp.half_K;
+        const float* mptr = a.mean;
+        if (a.multi_modal) mptr = first_half ? a.mean1 : a.mean2;
+        struct StepIn { float d0, d1, m0, m1, b0, b1; };
+        const bool use_best = a.multi_modal && (k == 0 || k == a.cp.half_K);
+        const float* bptr = (k == 0) ? a.best1 : a.best2;
+        auto fetch = [&](int t) {
+            StepIn in;
+            in.b0 = in.b1 = 0.0f;
+            const float2 dd = *reinterpret_cast<const float2*>(a.delta + ((size_t)t * Kl + slot) * 2);
+            in.d0 = dd.x; in.d1 = dd.y;
+            const int ts = (t + 1 < T) ? t + 1 : T - 1;   // _shift_action: mppi.py:266-273
+            in.m0 = mptr[ts * 2 + 0]; in.m1 = mptr[ts * 2 + 1];
+            if (use_best) { in.b0 = bptr[ts * 2 + 0]; in.b1 = bptr[ts * 2 + 1]; }
+            return in;
+        };
+        // ---- the action side, all T steps ahead of the dynamics ----
+        StepIn nxt = fetch(0);
+        for (int t = 0; t < T; ++t) {
+            const StepIn in = nxt;
+            if (t + 1 < T) nxt = fetch(t + 1);
+            float d0 = in.d0, d1 = in.d1;
+            if (is_last) { d0 = 0.0f; d1 = 0.0f; }      // mppi.py:392
+            float a0 = fmaxf(fminf(in.m0 + d0 * a.scale_tril[0], a.u_max[0]), a.u_min[0]);  // :394-405
+            float a1 = fmaxf(fminf(in.m1 + d1 * a.scale_tril[1], a.u_max[1]), a.u_min[1]);
+            if (use_best) { a0 = in.b0; a1 = in.b1; }  // mppi.py:407-409
+            float u0 = a.u_scale * a0, u1 = a.u_scale * a1;                 // mppi.py:297
+            if (a.sample_null_action && is_last) { u0 = 0.0f; u1 = 0.0f; }  // mppi.py:300-302
+            M3_R2(t, 6) = u0; M3_R2(t, 7) = u1;
+            __hip_atomic_store(&words[0], (unsigned)(t + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            *reinterpret_cast<float2*>(a.actions + ((size_t)t * Kl + i) * 2) = make_float2(u0, u1);   // mppi.py:313
+        }
+        // ---- the cost side, behind the dynamics ----
+        float J = 0.0f, S = 0.0f, g = 1.0f;
+        unsigned recorded = 0u;   // cached copy of words[1]
+        PointWorld w = {};
+        for (int t = 0; t < T; ++t) {
+            if (recorded < (unsigned)(t + 1)) {
+                bool ok = true;
+                for (unsigned spins = 0u; (recorded = r2_peek(&words[1])) < (unsigned)(t + 1);) {
+                    if (++spins > R2_SPINS_COMP) { *err = 2; ok = false; break; }
+                    __builtin_amdgcn_s_sleep(4);
+                }
+                if (!ok) break;
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            }
+            w.rx = M3_R2(t, 0); w.rvx = M3_R2(t, 1); w.ry = M3_R2(t, 2); w.rvy = M3_R2(t, 3);
+            if constexpr (TASK == 0) { w.fcDx = M3_R2(t, 4); w.fcDy = M3_R2(t, 5); }
+            else { w.B.x = M3_R2(t, 4); w.B.y = M3_R2(t, 5); }
+            const float c = point_cost(a.cp, w, k);
+            *reinterpret_cast<float4*>(a.states + ((size_t)t * Kl + i) * 4) =
+                make_float4(w.rx, w.rvx, w.ry, w.rvy);                      // reactive_tamp.py:66-69
+            a.cost_h[(size_t)t * Kl + i] = c;                               // mppi.py:310
+            J = J + g * c;                                                  // mppi_utils.py:106-113
+            S = S + c;                                                      // mppi.py:309
+            g = g * a.gamma;
+        }
+        a.J[i] = J;
+    }
+#undef M3_R2
+}
+// (both use more than 256 VGPRs like the one-wavefront builds, so the two waves of a workgroup take a SIMD each)
+template <int TASK>
+__global__ __launch_bounds__(128) void k_rollout_point2(const RolloutArgs a, const PointScene sc, int* err) {
+    rollout_point_body2<TASK>(a, sc, err);
+}
+template <int TASK>
+__global__ __launch_bounds__(128) void k_rollout_point2_ref(const RolloutArgs a, int* err) {
+    constexpr PointScene sc = POINT_SCENE_REFERENCE;
+    rollout_point_body2<TASK>(a, sc, err);
+}
+template <int TASK>
+inline void launch_rollout_point2_instance(const RolloutArgs& a, const PointScene& sc, int blocks, int* err, hipStream_t s) {
+    const size_t lds = rollout_point2_lds_bytes(a.T);
+    if (point_scene_is_reference(sc)) hipLaunchKernelGGL((k_rollout_point2_ref<TASK>), dim3(blocks), dim3(128), lds, s, a, err);
+    else hipLaunchKernelGGL((k_rollout_point2<TASK>), dim3(blocks), dim3(128), lds, s, a, sc, err);
+}
+
 // ---- batched command (m3_batch_command): one launch for a group of handles that share the instance, K, T and lanes.
 // blockIdx.y picks the handle's entry of the argument table (BatchRolloutEntry, m3_internal.hpp; read-only, so
 // `__restrict__`: nothing the body stores can alias it) and the unchanged body runs on it.  The same four builds with the same

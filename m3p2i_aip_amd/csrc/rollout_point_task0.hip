@@ -7,6 +7,9 @@ namespace m3 {
 void launch_rollout_point_nav(const RolloutArgs& a, const PointScene& sc, int blocks, hipStream_t s) {
     launch_rollout_point_instance<false, 0>(a, sc, blocks, s);
 }
+void launch_rollout_point_nav2(const RolloutArgs& a, const PointScene& sc, int blocks, int* err, hipStream_t s) {
+    launch_rollout_point2_instance<0>(a, sc, blocks, err, s);
+}
 void launch_rollout_point_nav_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s) {
     launch_rollout_point_batch_instance<false, 0>(tab, blocks, n, ref, s);
 }

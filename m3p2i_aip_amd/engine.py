@@ -97,6 +97,8 @@ class HipEngine:
             self.set_wave_order(False)
         if os.environ.get("M3P2I_ROLLOUT_LANES"):            # experiments (tools/panda_lanes_sweep.py)
             self.set_rollout_lanes(int(os.environ["M3P2I_ROLLOUT_LANES"]))
+        if os.environ.get("M3P2I_POINT_ROLLOUT_FORM"):       # experiments (tools/fuzz_parity.py, A/B runs)
+            self.set_point_rollout_form(int(os.environ["M3P2I_POINT_ROLLOUT_FORM"]))
 
     # ---- lifetime ----
     def close(self):
@@ -121,6 +123,15 @@ class HipEngine:
 
     def set_rollout_lanes(self, lanes=0):
         self._ck(self.lib.m3_set_rollout_lanes(self._h, int(lanes)))
+
+    def set_point_rollout_form(self, form=-1):
+        """point_env rollout of navigation / push: 0 = one wavefront per 64 samples, 1 = dynamics + companion wavefront wherever
+        that form exists, -1 = automatic; same results bit for bit."""
+        self._ck(self.lib.m3_set_point_rollout_form(self._h, int(form)))
+
+    def point_rollout_form_used(self):
+        """The form of the last rollout launch (0, 1; -1 before the first)."""
+        return int(self.lib.m3_point_rollout_form_used(self._h))
 
     def set_panda_lanes_per_sample(self, lps=0):
         """panda_env rollout: 1 = a lane per sample, 16 = the sixteen lanes of a DPP row share a sample (the contact rows run
