@@ -368,6 +368,40 @@ int m3_get_point_cost_weights(const m3_handle* h, m3_point_cost_weights* out);
 /* Test and A/B switch: -1 the automatic choice above (default), 1 the weighted build whatever the weights, 0 never -- with
  * weights other than the defaults the next command / rollout / cost call is then refused (M3_ERR_STATE). */
 int m3_set_weighted_cost_instance(m3_handle* h, int on);
+/* EXTENSION, point_env only: the ARENA as per-handle state -- what a user of the reference edits in the yaml files of config/point_env
+ * (5_obs, 1..4_wall, 7_box, 6_dyn_obs) and pointRobot.urdf.  The physical fields of the dynamics' scene, one for one; g, the
+ * velocity drive, the solver constants and the spec switches are not part of it.  The defaults are the reference's arena. */
+typedef struct m3_point_scene {
+    float robot_r, robot_m;                                  /* the robot disc: radius, mass */
+    float box_hx, box_hy, box_m, box_I, box_mu_g, box_req;   /* the pushable box: half extents, mass, inertia, ground friction,
+                                                              * mean lever arm of its footprint */
+    float dyn_hx, dyn_hy, dyn_m, dyn_I, dyn_mu_g, dyn_req;   /* the dynamic obstacle, likewise */
+    float obs_x, obs_y, obs_hx, obs_hy;                      /* the fixed obstacle: centre, half extents */
+    float wall;                                              /* inner face of the four walls, a square centred at the origin */
+    float mu_rb, mu_rd, mu_ro, mu_rw, mu_bw, mu_dw, mu_bd, mu_bo, mu_do;   /* pair frictions: r robot, b box, d dyn-obs,
+                                                                            * o obstacle, w walls */
+} m3_point_scene;
+void m3_default_point_scene(m3_point_scene* sc);
+/* Applies from the next command / rollout / step / episode tick; survives m3_reset; no allocation, no synchronisation.
+ * sc == NULL: back to the defaults.  Allowed on planner, sharded and sim_only handles; a world handle and its planners may
+ * carry different scenes (each handle uses its own).  Sharded handles: set the same scene on every rank.  A NaN or infinite
+ * field, a size / mass / inertia / *_req / robot_r <= 0, a negative friction or wall <= robot_r is M3_ERR_BAD_ARG (the message
+ * names the field); a panda_env handle M3_ERR_UNSUPPORTED.  A handle whose fields equal the defaults bit for bit runs exactly
+ * the kernels it ran before this call existed; any other handle runs the run-time-scene build of the general rollout instance
+ * (which is also its weighted build), of the batched rollout, of the step and of the episode tick. */
+int m3_set_point_scene(m3_handle* h, const m3_point_scene* sc);
+int m3_get_point_scene(const m3_handle* h, m3_point_scene* out);
+/* Test and A/B switch: -1 the automatic choice above (default), 1 the run-time-scene build whatever the values, 0 never --
+ * with a scene other than the default the next command / rollout / step is then refused (M3_ERR_STATE). */
+int m3_set_point_scene_instance(m3_handle* h, int on);
+/* Diagnostic, host only (no device call, no handle): the kernel form a point_env rollout with these settings takes -- what
+ * m3_rollout / m3_batch_command would launch for a handle configured so.  weighted / scene: what the handle's cost weights and
+ * scene (or their switches) amount to; form_request: m3_set_point_rollout_form's value; want_minima: the command keeps the
+ * workgroups' cost minima.  out: instance (-1 general, 0..3 the task's), ref (solver settings compiled in), form (1: two
+ * wavefronts), weighted, scene, workgroups, rows of minima, lanes. */
+int m3_point_rollout_plan(int task, int multi_modal, int mode_simple, int sampling_random, int avoid_dyn_obs, int K_local, int T,
+                          int lanes, float dt, int substeps, int solver_iters, int weighted, int scene, int form_request,
+                          int want_minima, int out[8]);
 /* Objective.multi_modal (cost_functions.py:9) for a sim_only handle, whose config does not
  * come from an MPPI object; refused on planner handles (fixed at m3_create) */
 int m3_set_multi_modal(m3_handle* h, int multi_modal);

@@ -56,6 +56,26 @@ class PointCostWeights(C.Structure):
     _fields_ = [(n, C.c_float) for n in COST_WEIGHT_DEFAULTS]
 
 
+# m3_point_scene, in field order, with the values of m3_default_point_scene (the reference's arena; the oracle's
+# m3o_point_scene_default): box_I / dyn_I = 16 * (0.4^2 + 0.4^2) / 12 and *_req = 0.3825978 * 0.4 are formed in binary32 there
+def _f32(x):
+    return C.c_float(x).value
+
+
+_I_DEFAULT = _f32(_f32(_f32(16.0) * _f32(_f32(_f32(0.4) * _f32(0.4)) + _f32(_f32(0.4) * _f32(0.4)))) / 12.0)
+_REQ_DEFAULT = _f32(_f32(0.3825978) * _f32(0.4))
+POINT_SCENE_DEFAULTS = dict(
+    robot_r=0.2, robot_m=10.0,
+    box_hx=0.2, box_hy=0.2, box_m=16.0, box_I=_I_DEFAULT, box_mu_g=0.75, box_req=_REQ_DEFAULT,
+    dyn_hx=0.2, dyn_hy=0.2, dyn_m=16.0, dyn_I=_I_DEFAULT, dyn_mu_g=1.0, dyn_req=_REQ_DEFAULT,
+    obs_x=2.0, obs_y=2.0, obs_hx=0.15, obs_hy=0.2, wall=3.95,
+    mu_rb=0.275, mu_rd=0.525, mu_ro=0.525, mu_rw=0.525, mu_bw=0.75, mu_dw=1.0, mu_bd=0.75, mu_bo=0.75, mu_do=1.0)
+
+
+class PointSceneFields(C.Structure):
+    _fields_ = [(n, C.c_float) for n in POINT_SCENE_DEFAULTS]
+
+
 class Info(C.Structure):
     _fields_ = [("eta", C.c_float), ("eta_1", C.c_float), ("eta_2", C.c_float),
                 ("beta", C.c_float), ("beta_1", C.c_float), ("beta_2", C.c_float),
@@ -134,6 +154,11 @@ SYMBOLS = [
     ("m3_set_point_cost_weights", C.c_int, [_H, C.POINTER(PointCostWeights)]),
     ("m3_get_point_cost_weights", C.c_int, [_H, C.POINTER(PointCostWeights)]),
     ("m3_set_weighted_cost_instance", C.c_int, [_H, C.c_int]),
+    ("m3_default_point_scene", None, [C.POINTER(PointSceneFields)]),
+    ("m3_set_point_scene", C.c_int, [_H, C.POINTER(PointSceneFields)]),
+    ("m3_get_point_scene", C.c_int, [_H, C.POINTER(PointSceneFields)]),
+    ("m3_set_point_scene_instance", C.c_int, [_H, C.c_int]),
+    ("m3_point_rollout_plan", C.c_int, [C.c_int] * 8 + [C.c_float] + [C.c_int] * 6 + [C.POINTER(C.c_int)]),
     ("m3_set_multi_modal", C.c_int, [_H, C.c_int]),
     ("m3_set_plan", C.c_int, [_H, C.c_int, _FP]),
     ("m3_set_action_out", C.c_int, [_H, C.c_void_p]),

@@ -124,6 +124,10 @@ class ExampleConfig:
     avoid_dyn_obs: bool = False     # EXTENSION (not a key of the reference's config_store.py): cost_functions.Objective
     cost_weights: Optional[Dict[str, float]] = None   # EXTENSION, point_env: e.g. `cost_weights={push_align: 2.5}`; None = the
                                                       # reference's literals (cost_functions.Objective, _lib.COST_WEIGHT_DEFAULTS)
+    point_scene: Optional[Dict[str, float]] = None    # EXTENSION, point_env: field overrides of the arena, e.g.
+                                                      # `point_scene={obs_x: -1.0, wall: 2.95}` (_lib.POINT_SCENE_DEFAULTS); the
+                                                      # wrappers built from cfg.isaacgym set it on their engines, the planners
+                                                      # that attach to them take it over
 
 
 def make_config(config_name="config_point", overrides=()):
@@ -161,6 +165,10 @@ def make_config(config_name="config_point", overrides=()):
         if not hasattr(obj, parts[-1]):
             raise AttributeError(f"unknown config key {key!r}")
         setattr(obj, parts[-1], yaml.safe_load(val))
+    if cfg.point_scene:
+        if cfg.env_type != "point_env":
+            raise ValueError("point_scene: point_env only")
+        cfg.isaacgym.point_scene = dict(cfg.point_scene)   # (the wrappers are built from cfg.isaacgym)
     return cfg
 
 

@@ -207,6 +207,7 @@ extern "C" int m3_create(const m3_config* c, m3_handle** out) {
         return M3_ERR_HIP;
     }
     build_point_scene(*c, h->scene);
+    h->scene_rt = make_point_scene_rt(h->point_scene, c->dt, c->substeps, c->solver_iters);
     default_world(h->world0);
     build_panda_scene(*c, h->pscene);
     default_panda_world(h->pworld0, c->cube_on_shelf);
@@ -463,7 +464,7 @@ static int order_block(m3_handle* h, float* block, int k_offset, bool relabel, b
     std::memset(&os, 0, sizeof(os));
     if (h->bind_dof) { os.sim_root = h->bind_root; os.sim_box = h->bind_box; os.sim_dyn = h->bind_dyn; }
     os.bx = h->world0[4]; os.by = h->world0[5]; os.dx = h->world0[11]; os.dy = h->world0[12];
-    os.ox = h->scene.obs_x; os.oy = h->scene.obs_y;
+    os.ox = h->point_scene.obs_x; os.oy = h->point_scene.obs_y;   // (the handle's arena; the default: PointScene's constants)
     // relabelling keeps the samples with a role of their own at their index
     const int specials[3] = {0 - k_offset, c.K_global / 2 - k_offset, c.K_global - 1 - k_offset};
     hipError_t e = launch_wave_order(block, c.K_local, c.T, c.nu,
@@ -808,6 +809,66 @@ static const char* weighted_refusal(const m3_handle* h) {
     return nullptr;
 }
 
+// ---- the point_env arena (extension; per-handle state like the cost weights: no allocation, no synchronisation) ----
+static const char* const SCENE_FIELD_NAMES[28] = {
+    "robot_r", "robot_m", "box_hx", "box_hy", "box_m", "box_I", "box_mu_g", "box_req", "dyn_hx", "dyn_hy", "dyn_m", "dyn_I",
+    "dyn_mu_g", "dyn_req", "obs_x", "obs_y", "obs_hx", "obs_hy", "wall", "mu_rb", "mu_rd", "mu_ro", "mu_rw", "mu_bw", "mu_dw",
+    "mu_bd", "mu_bo", "mu_do"};
+// what a field must satisfy: 0 any finite value (a position), 1 > 0 (size, mass, inertia, lever arm), 2 >= 0 (friction)
+static const int SCENE_FIELD_RULE[28] = {1, 1, 1, 1, 1, 1, 2, 1, 1, 1, 1, 1, 2, 1, 0, 0, 1, 1, 1, 2, 2, 2, 2, 2, 2, 2, 2, 2};
+static_assert(sizeof(m3_point_scene) == 28 * sizeof(float), "m3_point_scene: twenty-eight floats");
+
+extern "C" void m3_default_point_scene(m3_point_scene* sc) {
+    if (sc) std::memcpy(sc, &POINT_SCENE_DEFAULT, sizeof(*sc));
+}
+
+extern "C" int m3_set_point_scene(m3_handle* h, const m3_point_scene* sc) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_point_scene: point_env only");
+    const m3_point_scene& src = sc ? *sc : POINT_SCENE_DEFAULT;
+    const float* f = reinterpret_cast<const float*>(&src);
+    for (int i = 0; i < 28; ++i) {
+        const char* what = !std::isfinite(f[i]) ? " is not finite"
+                           : (SCENE_FIELD_RULE[i] == 1 && !(f[i] > 0.0f)) ? " must be > 0"
+                           : (SCENE_FIELD_RULE[i] == 2 && f[i] < 0.0f) ? " must be >= 0" : nullptr;
+        if (what) return fail(h, M3_ERR_BAD_ARG, (std::string("m3_set_point_scene: ") + SCENE_FIELD_NAMES[i] + what).c_str());
+    }
+    if (!(src.wall > src.robot_r)) return fail(h, M3_ERR_BAD_ARG, "m3_set_point_scene: wall must be > robot_r");
+    std::memcpy(&h->point_scene, &src, sizeof(src));
+    h->scene_rt = make_point_scene_rt(h->point_scene, h->cfg.dt, h->cfg.substeps, h->cfg.solver_iters);
+    return M3_OK;
+}
+
+extern "C" int m3_get_point_scene(const m3_handle* h, m3_point_scene* out) {
+    if (!h || !out) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_POINT) return M3_ERR_UNSUPPORTED;
+    std::memcpy(out, &h->point_scene, sizeof(*out));
+    return M3_OK;
+}
+
+extern "C" int m3_set_point_scene_instance(m3_handle* h, int on) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_point_scene_instance: point_env only");
+    if (on < -1 || on > 1) return fail(h, M3_ERR_BAD_ARG, "m3_set_point_scene_instance: -1 (by the values), 0 or 1");
+    h->scene_instance = on;
+    return M3_OK;
+}
+
+// the handle's arena is the default bit for bit (-0.0f is not 0.0f here)
+static bool default_point_scene(const m3_handle* h) {
+    return std::memcmp(&h->point_scene, &POINT_SCENE_DEFAULT, sizeof(m3_point_scene)) == 0;
+}
+// the one owner of "does this handle run the run-time-scene kernels" (rollout instance, batch group, step, episode tick)
+static bool runtime_scene(const m3_handle* h) {
+    if (h->cfg.env_type != M3_ENV_POINT) return false;
+    return h->scene_instance < 0 ? !default_point_scene(h) : h->scene_instance != 0;
+}
+static const char* scene_refusal(const m3_handle* h) {
+    if (h->cfg.env_type == M3_ENV_POINT && h->scene_instance == 0 && !default_point_scene(h))
+        return "the run-time-scene instance is forced off (m3_set_point_scene_instance 0) but the handle's scene is not the default";
+    return nullptr;
+}
+
 extern "C" int m3_set_multi_modal(m3_handle* h, int mm) {
     if (!h) return M3_ERR_BAD_ARG;
     if (!h->cfg.sim_only && (mm != 0) != (h->cfg.multi_modal != 0))
@@ -964,6 +1025,7 @@ static const char* rollout_refusal(const m3_handle* h) {
         return "m3_rollout: simple mode needs m3_set_noise or sampling_random";
     if (h->task == M3_TASK_PUSH_PULL && !c.multi_modal) return "m3_rollout: push_pull needs multi_modal";
     if (const char* why = weighted_refusal(h)) return why;
+    if (const char* why = scene_refusal(h)) return why;
     return nullptr;
 }
 
@@ -1053,7 +1115,7 @@ static int plan_rollout(m3_handle* h, RolloutArgs& a, PandaArgs& pa, RolloutPlan
     if (rc != M3_OK) return rc;
     if (h->cfg.env_type == M3_ENV_POINT) {
         // (the two-wavefront form: m3_rollout's own launch only, and only with the error word to report into)
-        p = plan_rollout_point(a, h->scene, weighted_cost(h), (own_launch && h->rollout_err_dev) ? h->point_form : 0);
+        p = plan_rollout_point(a, h->scene, weighted_cost(h), (own_launch && h->rollout_err_dev) ? h->point_form : 0, runtime_scene(h));
     } else {
         fill_panda_args(h, a, pa);
         p = plan_rollout_panda(a, pa);
@@ -1077,7 +1139,8 @@ extern "C" int m3_rollout(m3_handle* h) {
     if (rc != M3_OK) return rc;
     if (h->cfg.env_type == M3_ENV_POINT) h->point_form_used = p.form;
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->cost_weights, p, h->stream, h->rollout_err_dev);
+    if (h->cfg.env_type == M3_ENV_POINT && p.scene) launch_rollout_point_scene(a, h->scene_rt, h->cost_weights, p, h->stream);
+    else if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->cost_weights, p, h->stream, h->rollout_err_dev);
     else launch_rollout_panda(a, pa, h->pscene, p, h->stream);
     HIPCHK(h, hipGetLastError());
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
@@ -1657,8 +1720,9 @@ struct BatchKey {
 // the fields a group shares, in the order the groups are sorted by
 auto rollout_fields(const BatchKey& k) {
     const RolloutPlan& p = k.roll;
-    // (weighted first: the weighted groups' entries, of their own type, lie behind all the others in the table)
-    return std::tie(p.weighted, p.instance, p.ref, p.lps, p.forces, p.general, p.shadows, p.rec, k.K, k.T, p.lanes);
+    // (scene, then weighted, first: the weighted groups' entries, of their own type, lie behind the plain ones in the table, the
+    // run-time-scene groups' -- always weighted -- behind those)
+    return std::tie(p.scene, p.weighted, p.instance, p.ref, p.lps, p.forces, p.general, p.shadows, p.rec, k.K, k.T, p.lanes);
 }
 auto update_fields(const BatchKey& k) { return std::tie(k.upd.nu, k.upd.multi, k.upd.jr, k.upd.wt, k.upd.n_cand, k.T); }
 bool same_rollout(const BatchKey& x, const BatchKey& y) { return rollout_fields(x) == rollout_fields(y); }
@@ -1677,8 +1741,9 @@ size_t align16(size_t n) { return (n + 15) / 16 * 16; }
 struct m3_batch {
     int device = 0, max_handles = 0;
     std::string err;
-    size_t upd_off = 0, slot_bytes = 0;   // a slot: [max_handles] BatchRolloutEntry (then, 16-aligned, the weighted groups'
-                                          // BatchRolloutEntryW) or BatchPandaEntry (from 0) | [max_handles] UpdateArgs
+    size_t upd_off = 0, slot_bytes = 0;   // a slot: [max_handles] BatchRolloutEntry (then, 16-aligned each, the weighted groups'
+                                          // BatchRolloutEntryW and the run-time-scene groups' BatchRolloutEntryS) or
+                                          // BatchPandaEntry (from 0) | [max_handles] UpdateArgs
     char* host[BATCH_SLOTS] = {};
     char* dev[BATCH_SLOTS] = {};
     hipEvent_t done[BATCH_SLOTS] = {};
@@ -1722,8 +1787,9 @@ extern "C" int m3_batch_create(int device, int max_handles, m3_batch** out) {
     if (!b) { g_batch_err = "m3_batch_create: out of host memory"; return M3_ERR_HIP; }
     b->device = device;
     b->max_handles = max_handles;
-    constexpr size_t entry = std::max(std::max(sizeof(BatchRolloutEntry), sizeof(BatchRolloutEntryW)), sizeof(BatchPandaEntry));
-    b->upd_off = align16((size_t)max_handles * entry) + 16;   // (+ 16: the alignment gap in front of the weighted entries)
+    constexpr size_t entry = std::max(std::max(std::max(sizeof(BatchRolloutEntry), sizeof(BatchRolloutEntryW)), sizeof(BatchRolloutEntryS)),
+                                      sizeof(BatchPandaEntry));
+    b->upd_off = align16((size_t)max_handles * entry) + 32;   // (+ 32: the alignment gaps in front of the weighted and the scene entries)
     b->slot_bytes = b->upd_off + (size_t)max_handles * sizeof(UpdateArgs);
     try {
         b->seen.resize(max_handles);
@@ -1838,30 +1904,37 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
         HIPCHK(b, hipEventSynchronize(b->done[slot]));
         b->in_flight[slot] = false;
     }
-    // point_env: the first n_plain handles in key order are the unweighted ones (rollout_fields), the weighted ones follow
-    int n_plain = n;
+    // point_env: the first n_plain handles in key order are the unweighted ones (rollout_fields), the weighted ones follow, the
+    // run-time-scene ones (from n_ws on) come last
+    int n_plain = n, n_ws = n;
     if (!panda) {
         n_plain = 0;
         while (n_plain < n && !hd[b->by_roll[n_plain]].key.roll.weighted) ++n_plain;
+        n_ws = n_plain;
+        while (n_ws < n && !hd[b->by_roll[n_ws]].key.roll.scene) ++n_ws;
     }
     const size_t w_off = align16((size_t)n_plain * sizeof(BatchRolloutEntry));
+    const size_t s_off = align16(w_off + (size_t)(n_ws - n_plain) * sizeof(BatchRolloutEntryW));
+    BatchRolloutEntryS* hsn = reinterpret_cast<BatchRolloutEntryS*>(b->host[slot] + s_off);
     BatchRolloutEntry* hr = reinterpret_cast<BatchRolloutEntry*>(b->host[slot]);
     BatchRolloutEntryW* hw = reinterpret_cast<BatchRolloutEntryW*>(b->host[slot] + w_off);
     BatchPandaEntry* hp = reinterpret_cast<BatchPandaEntry*>(b->host[slot]);
     const size_t upd_off = panda ? align16((size_t)n * sizeof(BatchPandaEntry))
-                                 : align16(w_off + (size_t)(n - n_plain) * sizeof(BatchRolloutEntryW));
+                                 : align16(s_off + (size_t)(n - n_ws) * sizeof(BatchRolloutEntryS));
     UpdateArgs* hu = reinterpret_cast<UpdateArgs*>(b->host[slot] + upd_off);
     for (int p = 0; p < n; ++p) {
         const int i = b->by_roll[p];
         if (panda) { hp[p].a = hd[i].a; hp[p].pa = hd[i].pa; hp[p].sc = hs[i]->pscene; }
         else if (p < n_plain) { hr[p].a = hd[i].a; hr[p].sc = hs[i]->scene; }
-        else { BatchRolloutEntryW& e = hw[p - n_plain]; e.a = hd[i].a; e.sc = hs[i]->scene; e.wt = hs[i]->cost_weights; }
+        else if (p < n_ws) { BatchRolloutEntryW& e = hw[p - n_plain]; e.a = hd[i].a; e.sc = hs[i]->scene; e.wt = hs[i]->cost_weights; }
+        else { BatchRolloutEntryS& e = hsn[p - n_ws]; e.a = hd[i].a; e.sc = hs[i]->scene_rt; e.wt = hs[i]->cost_weights; }
     }
     for (int p = 0; p < n; ++p) hu[p] = hd[b->by_upd[p]].u;
     char* dslot = b->dev[slot];
     HIPCHK(b, hipMemcpyAsync(dslot, b->host[slot], upd_off + (size_t)n * sizeof(UpdateArgs), hipMemcpyHostToDevice, s));
     const BatchRolloutEntry* dr = reinterpret_cast<const BatchRolloutEntry*>(dslot);
     const BatchRolloutEntryW* dw = reinterpret_cast<const BatchRolloutEntryW*>(dslot + w_off);
+    const BatchRolloutEntryS* dsn = reinterpret_cast<const BatchRolloutEntryS*>(dslot + s_off);
     const BatchPandaEntry* dp = reinterpret_cast<const BatchPandaEntry*>(dslot);
     const UpdateArgs* du = reinterpret_cast<const UpdateArgs*>(dslot + upd_off);
     // ---- one rollout launch per group (panda_env: + one k_panda_reach_cost launch when the group keeps the record buffer,
@@ -1872,6 +1945,7 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
         int q = p + 1;
         while (q < n && same_rollout(hd[b->by_roll[q]].key, k)) ++q;
         if (panda) launch_rollout_panda_batch(dp + p, q - p, k.roll, k.K, s);
+        else if (k.roll.scene) launch_rollout_point_batch_s(dsn + (p - n_ws), q - p, k.roll, s);
         else if (k.roll.weighted) launch_rollout_point_batch_w(dw + (p - n_plain), q - p, k.roll, s);
         else launch_rollout_point_batch(dr + p, q - p, k.roll, s);
         ++n_roll;
@@ -2060,7 +2134,9 @@ extern "C" int m3_sim_apply_body_forces(m3_handle* h, const float* f) {
 static int sim_step_impl(m3_handle* h, const float* u) {
     if (!h->views_bound) return fail(h, M3_ERR_STATE, "m3_sim_step: views not bound");
     if (h->cfg.env_type == M3_ENV_POINT) {
-        launch_sim_step(h->scene, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
+        if (const char* why = scene_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_sim_step: ") + why).c_str());
+        if (runtime_scene(h)) launch_sim_step_s(h->scene_rt, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
+        else launch_sim_step(h->scene, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
     } else {
         launch_psim_step(h->pscene, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
     }
@@ -2261,6 +2337,12 @@ static int eps_ready(m3_episodes* eps, const char* who) {
     return M3_OK;
 }
 
+// the step of the world's rows with the WORLD handle's scene (the planners plan with their own)
+static void episodes_post(const m3_handle* w, const m3::EpisodeArgs& a, int tick) {
+    if (runtime_scene(w)) m3::launch_episodes_post_s(w->scene_rt, a, tick, w->stream);
+    else m3::launch_episodes_post(w->scene, a, tick, w->stream);
+}
+
 static int eps_status_sync(m3_episodes* eps) {
     const hipStream_t s = eps->world->stream;
     HIPCHK(eps, hipMemcpyAsync(eps->host, eps->args.st, (size_t)eps->n * sizeof(m3_episode_status), hipMemcpyDeviceToHost, s));
@@ -2284,7 +2366,8 @@ extern "C" int m3_episodes_end(m3_episodes* eps) {
     if (!eps->mid_tick) { eps->err = "m3_episodes_end: no tick begun"; return M3_ERR_STATE; }
     int rc = eps_ready(eps, "m3_episodes_end");
     if (rc != M3_OK) return rc;
-    m3::launch_episodes_post(eps->world->scene, eps->args, eps->tick, eps->world->stream);
+    if (const char* why = scene_refusal(eps->world)) { eps->err = std::string("m3_episodes_end: world: ") + why; return M3_ERR_STATE; }
+    episodes_post(eps->world, eps->args, eps->tick);
     HIPCHK(eps, hipGetLastError());
     eps->mid_tick = false;
     eps->tick += 1;
@@ -2297,6 +2380,7 @@ extern "C" int m3_episodes_tick(m3_episodes* eps, m3_batch* batch) {
     if (eps->mid_tick) { eps->err = "m3_episodes_tick: inside m3_episodes_begin / m3_episodes_end"; return M3_ERR_STATE; }
     int rc = eps_ready(eps, "m3_episodes_tick");
     if (rc != M3_OK) return rc;
+    if (const char* why = scene_refusal(eps->world)) { eps->err = std::string("m3_episodes_tick: world: ") + why; return M3_ERR_STATE; }
     // the batch: episodes still running after the last tick's status (one that succeeds in this tick's pre kernel is
     // commanded once more -- its plan is never recorded)
     eps->live.clear();
@@ -2317,7 +2401,7 @@ extern "C" int m3_episodes_tick(m3_episodes* eps, m3_batch* batch) {
         rc = m3_batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr);
         if (rc != M3_OK) { eps->err = std::string("m3_episodes_tick: ") + m3_batch_last_error(batch); return rc; }
     }
-    m3::launch_episodes_post(w->scene, eps->args, eps->tick, w->stream);
+    episodes_post(w, eps->args, eps->tick);
     HIPCHK(eps, hipGetLastError());
     eps->tick += 1;
     return eps_status_sync(eps);

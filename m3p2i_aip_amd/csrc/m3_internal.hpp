@@ -167,6 +167,11 @@ struct BatchRolloutEntryW {  // ... of the weighted group (kb_rollout_point_w): 
     PointScene sc;
     PointCostWeights wt;
 };
+struct BatchRolloutEntryS {  // ... of the run-time-scene group (kb_rollout_point_s): the handle's own arena and its weights
+    RolloutArgs a;
+    PointSceneRT sc;
+    PointCostWeights wt;
+};
 // the k_update_small instance (template arguments, workgroup width, top-k workgroups) an unsharded command takes:
 // launch_update_small launches it, m3_batch_command groups the handles by it
 struct SmallUpdateInstance {
@@ -192,12 +197,19 @@ struct RolloutPlan {
     int weighted;        // point_env: the weighted build of the general instance (m3_set_point_cost_weights; instance == -1)
     int form;            // point_env: 0 one wavefront per 64 samples, 1 dynamics + companion wavefront (rollout_point_kernel.hpp:
                          // rollout_point_body2); m3_rollout only -- the batched and episode paths plan with form_request 0
+    int scene;           // point_env: the run-time-scene build of the general instance (m3_set_point_scene; instance == -1,
+                         // weighted == 1, ref == 0, form == 0)
 };
 // form_request: m3_set_point_rollout_form's value (0 one wavefront, 1 two wherever available, -1 by rollout_companion_pays)
-RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, bool weighted, int form_request = 0);
+RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, bool weighted, int form_request = 0,
+                               bool scene = false /* the handle runs the run-time-scene build */);
 // one launch of the plan's instance for n handles of K_local = a.Kl and the same plan (tab: device, n entries)
 void launch_rollout_point_batch(const BatchRolloutEntry* tab, int n, const RolloutPlan& p, hipStream_t s);
 void launch_rollout_point_batch_w(const BatchRolloutEntryW* tab, int n, const RolloutPlan& p, hipStream_t s);   // p.weighted
+void launch_rollout_point_batch_s(const BatchRolloutEntryS* tab, int n, const RolloutPlan& p, hipStream_t s);   // p.scene
+// one handle's launch of the run-time-scene build (p.scene)
+void launch_rollout_point_scene(const RolloutArgs& a, const PointSceneRT& sc, const PointCostWeights& wt, const RolloutPlan& p,
+                                hipStream_t s);
 void launch_rollout_point_nav_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
 void launch_rollout_point_push_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
 void launch_rollout_point_pull_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
@@ -307,6 +319,8 @@ void launch_sim_shift_pull(const SimViews& v, float* world, int Kl, int actor, f
 void launch_sim_push(const SimViews& v, const float* world, int Kl, hipStream_t s);
 void launch_sim_step(const PointScene& sc, const SimViews& v, float* world, const float* u /*[Kl][2]*/, float* u_keep,
                      int Kl, hipStream_t s);   // step + refresh of the views
+void launch_sim_step_s(const PointSceneRT& sc, const SimViews& v, float* world, const float* u, float* u_keep, int Kl,
+                       hipStream_t s);   // ... of a handle with a run-time scene
 void launch_sim_forces(const SimViews& v, float* world, const float* f /*[Kl][nB][3]*/, int Kl,
                        hipStream_t s);
 void launch_sim_cost(const CostParams& cp, float* world, int Kl, int k0, float* cost,
@@ -334,6 +348,7 @@ struct EpisodeArgs {
 };
 void launch_episodes_pre(const EpisodeArgs& a, int tick, hipStream_t s);
 void launch_episodes_post(const PointScene& sc, const EpisodeArgs& a, int tick, hipStream_t s);
+void launch_episodes_post_s(const PointSceneRT& sc, const EpisodeArgs& a, int tick, hipStream_t s);
 
 constexpr int NW = 28;  // floats per env in the step-mode SoA world (PointWorld fields)
 constexpr int NWP = 77; // same for the panda_env (PandaWorld fields, rollout_panda.hip)
@@ -412,6 +427,9 @@ struct m3_handle {
     int avoid_dyn_obs = 0;             // m3_set_avoid_dyn_obs (extension; 0 = the reference's compute_cost)
     m3::PointCostWeights cost_weights = m3::POINT_COST_WEIGHTS_DEFAULT;   // m3_set_point_cost_weights (extension, point_env)
     int weighted_instance = -1;        // m3_set_weighted_cost_instance: -1 by the weights (not the defaults bit for bit), 0 / 1 forced
+    m3_point_scene point_scene = m3::POINT_SCENE_DEFAULT;   // m3_set_point_scene (extension, point_env); survives m3_reset
+    m3::PointSceneRT scene_rt = {};    // ... with the handle's dt / substeps / iterations (make_point_scene_rt; m3_create, m3_set_point_scene)
+    int scene_instance = -1;           // m3_set_point_scene_instance: -1 by the values (not the defaults bit for bit), 0 / 1 forced
     // world
     float world0[18];
     const float* world0_bound = nullptr;  // device, 18 floats (filled by world_from_sim)

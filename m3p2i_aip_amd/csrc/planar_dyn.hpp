@@ -1,4 +1,4 @@
-// planar_dyn.hpp -- device-side "Planar contact dynamics spec" (currently v1.5).
+// planar_dyn.hpp -- device-side "Planar contact dynamics spec" (currently v1.7).
 //
 // Replaces, for the point_env scene, what the reference delegates to Isaac Gym / PhysX:
 //   IsaacGymWrapper.step()                    isaacgym_wrapper.py:354-360
@@ -16,6 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/m3p2i_hip.h"
 #include "spec_fma.hpp"
 
 namespace m3 {
@@ -79,6 +80,86 @@ inline bool point_scene_is_reference(const PointScene& s) {
     return s.substeps == r.substeps && s.iters == r.iters && same(s.h, r.h) && same(s.inv_h, r.inv_h) && same(s.gam, r.gam) &&
            same(s.md, r.md) && same(s.dmax, r.dmax) && same(s.LlinB, r.LlinB) && same(s.LangB, r.LangB) && same(s.LlinD, r.LlinD) &&
            same(s.LangD, r.LangD) && same(s.RcB, r.RcB) && same(s.RcD, r.RcD);
+}
+
+// ---- the scene at RUN TIME (m3_set_point_scene; extension) ----
+// The thirteen run-time fields of PointScene and, as ordinary members under the same names, everything that is a compile-time
+// constant there.  Every function below that reads a scene is a template on the scene type (`SC`): the PointScene instantiations
+// are what they were (a constant folds into the instruction stream), the PointSceneRT instantiations run the same operations in
+// the same order on values that arrive as kernel arguments.  Only the kernels of a handle whose scene is not the default
+// (k_rollout_point_s, kb_rollout_point_s, k_sim_step_s, k_episodes_post_s) are instantiated with it.
+struct PointSceneRT {
+    float h, inv_h;
+    int substeps, iters;
+    float gam, md, dmax;
+    float LlinB, LangB, LlinD, LangD;
+    float RcB, RcD;
+    float robot_r, invm_r;
+    float box_hx, box_hy, box_m, box_I, invm_b, invI_b;
+    float dyn_hx, dyn_hy, dyn_m, dyn_I, invm_d, invI_d;
+    float obs_x, obs_y, obs_hx, obs_hy;
+    float wall;
+    float mu_rb, mu_rd, mu_ro, mu_rw, mu_bw, mu_dw, mu_bd, mu_bo, mu_do;
+    float contact_offset, baumgarte, slop, max_bias, face_tol;
+    float rad_b, rad_d, rad_o;
+};
+
+// the reference's arena as m3_point_scene (m3_default_point_scene): the constants of PointScene and of point_scene_for, the same
+// expressions as the oracle's m3o_point_scene_default -- same bits
+constexpr m3_point_scene POINT_SCENE_DEFAULT = {
+    PointScene::robot_r, 10.0f,
+    PointScene::box_hx, PointScene::box_hy, PointScene::box_m, PointScene::box_I, 0.75f, 0.3825978f * 0.4f,
+    PointScene::dyn_hx, PointScene::dyn_hy, PointScene::dyn_m, PointScene::dyn_I, 1.0f, 0.3825978f * 0.4f,
+    PointScene::obs_x, PointScene::obs_y, PointScene::obs_hx, PointScene::obs_hy,
+    PointScene::wall,
+    PointScene::mu_rb, PointScene::mu_rd, PointScene::mu_ro, PointScene::mu_rw, PointScene::mu_bw, PointScene::mu_dw,
+    PointScene::mu_bd, PointScene::mu_bo, PointScene::mu_do};
+
+// Bounding radius of a box for the broad phase.  The oracle has no broad phase: every pair goes through its narrow phase, and
+// a pair is a contact when the narrow phase finds sep < contact_offset.  The device skips the narrow phase of a pair whose
+// centres are farther apart than the sum of the bounding radii (+ contact_offset + 1e-3).  A radius that is TOO LARGE only
+// sends more pairs through the narrow phase, which then decides by itself exactly as the oracle does: no bit can change.  A
+// radius that is TOO SMALL skips a pair the oracle finds in contact: the contact is lost.  So the radius is an upper bound of
+// sqrt(hx^2 + hy^2): formed in binary64, rounded UP to binary32, plus POINT_RAD_MARGIN (far above the rounding of the sum and
+// of the binary32 narrow phase, far below anything that would cost time).
+constexpr float POINT_RAD_MARGIN = 1e-4f;
+inline float point_bounding_radius(float hx, float hy) {
+    const double d = __builtin_sqrt((double)hx * (double)hx + (double)hy * (double)hy);
+    float f = (float)d;
+    if ((double)f < d) f = __builtin_nextafterf(f, __builtin_inff());
+    return f + POINT_RAD_MARGIN;
+}
+
+// Host side (m3_set_point_scene, the host build in tests/native/): the derived constants in binary32 in exactly the order the
+// oracle forms them (oracle/planar_world.c, m3o_point_step); g, the drive constants and the solver constants are not part of
+// m3_point_scene and keep the values of point_scene_for / PointScene.
+inline PointSceneRT make_point_scene_rt(const m3_point_scene& p, float dt, int substeps, int iters) {
+    PointSceneRT s{};
+    const float h = dt / (float)substeps;
+    s.h = h; s.inv_h = 1.0f / h; s.substeps = substeps; s.iters = iters;
+    const float g = 9.8f;
+    s.robot_r = p.robot_r;
+    s.invm_r = 1.0f / p.robot_m;
+    s.box_hx = p.box_hx; s.box_hy = p.box_hy; s.box_m = p.box_m; s.box_I = p.box_I;
+    s.invm_b = 1.0f / p.box_m; s.invI_b = 1.0f / p.box_I;
+    s.dyn_hx = p.dyn_hx; s.dyn_hy = p.dyn_hy; s.dyn_m = p.dyn_m; s.dyn_I = p.dyn_I;
+    s.invm_d = 1.0f / p.dyn_m; s.invI_d = 1.0f / p.dyn_I;
+    s.gam = 1.0f / (h * 600.0f);
+    s.md = 1.0f / (s.invm_r + s.gam);
+    s.dmax = 1000.0f * h;
+    s.LlinB = ((p.box_mu_g * p.box_m) * g) * h; s.LangB = s.LlinB * p.box_req;
+    s.LlinD = ((p.dyn_mu_g * p.dyn_m) * g) * h; s.LangD = s.LlinD * p.dyn_req;
+    s.RcB = 1.5f * p.box_req; s.RcD = 1.5f * p.dyn_req;
+    s.obs_x = p.obs_x; s.obs_y = p.obs_y; s.obs_hx = p.obs_hx; s.obs_hy = p.obs_hy;
+    s.wall = p.wall;
+    s.mu_rb = p.mu_rb; s.mu_rd = p.mu_rd; s.mu_ro = p.mu_ro; s.mu_rw = p.mu_rw; s.mu_bw = p.mu_bw; s.mu_dw = p.mu_dw;
+    s.mu_bd = p.mu_bd; s.mu_bo = p.mu_bo; s.mu_do = p.mu_do;
+    s.contact_offset = PointScene::contact_offset; s.baumgarte = PointScene::baumgarte; s.slop = PointScene::slop;
+    s.max_bias = PointScene::max_bias; s.face_tol = PointScene::face_tol;
+    s.rad_b = point_bounding_radius(p.box_hx, p.box_hy);
+    s.rad_d = point_bounding_radius(p.dyn_hx, p.dyn_hy);
+    s.rad_o = point_bounding_radius(p.obs_hx, p.obs_hy);
+    return s;
 }
 
 struct Box {
@@ -174,13 +255,13 @@ template <int ID> __device__ __forceinline__ float gw(const Vel& v) {
     else if constexpr (ID == BOXD) return v.dw;
     else return 0.0f;
 }
-template <int ID> __device__ __forceinline__ float invm(const PointScene& sc) {
+template <int ID, class SC> __device__ __forceinline__ float invm(const SC& sc) {
     if constexpr (ID == ROBOT) return sc.invm_r;
     else if constexpr (ID == BOXB) return sc.invm_b;
     else if constexpr (ID == BOXD) return sc.invm_d;
     else return 0.0f;
 }
-template <int ID> __device__ __forceinline__ float invI(const PointScene& sc) {
+template <int ID, class SC> __device__ __forceinline__ float invI(const SC& sc) {
     if constexpr (ID == BOXB) return sc.invI_b;
     else if constexpr (ID == BOXD) return sc.invI_d;
     else return 0.0f;
@@ -189,8 +270,8 @@ template <int ID> constexpr bool rotates() { return ID == BOXB || ID == BOXD; }
 template <int ID> constexpr bool moves() { return ID != STATIC; }
 
 // apply impulse dl along (dx,dy) with angular arm ra to body ID, sign sg (-1 for a, +1 for b)
-template <int ID, int SG>
-__device__ __forceinline__ void apply(const PointScene& sc, Vel& v, float dl, float dx, float dy,
+template <int ID, int SG, class SC>
+__device__ __forceinline__ void apply(const SC& sc, Vel& v, float dl, float dx, float dy,
                                       float arm) {
     if constexpr (!moves<ID>()) return;
     const float im = (SG < 0) ? -(invm<ID>(sc) * dl) : invm<ID>(sc) * dl;
@@ -207,8 +288,8 @@ __device__ __forceinline__ void apply(const PointScene& sc, Vel& v, float dl, fl
 
 // spec: prepare (effective masses, bias) of one contact.  PRED: the same values without a per-lane branch (both sides of the
 // bias are formed and one is selected) -- for the predicated rows of the lean substep instances, see point_substep.
-template <int A, int B, bool PRED = false>
-__device__ __forceinline__ void prepare(const PointScene& sc, Slot& c, float nx, float ny,
+template <int A, int B, bool PRED = false, class SC>
+__device__ __forceinline__ void prepare(const SC& sc, Slot& c, float nx, float ny,
                                         float rax, float ray, float rbx, float rby, float sep) {
     const float tx = -ny, ty = nx;
     c.nx = nx; c.ny = ny;
@@ -245,8 +326,8 @@ __device__ __forceinline__ void prepare(const PointScene& sc, Slot& c, float nx,
     c.on = true;
 }
 
-template <int A, int B>
-__device__ __forceinline__ void solve(const PointScene& sc, Vel& v, Slot& c, float mu) {
+template <int A, int B, class SC>
+__device__ __forceinline__ void solve(const SC& sc, Vel& v, Slot& c, float mu) {
     const float tx = -c.ny, ty = c.nx;
     float dvx = gvx<B>(v) - gvx<A>(v), dvy = gvy<B>(v) - gvy<A>(v);
     float vn = mad(dvx, c.nx, dvy * c.ny);
@@ -279,8 +360,8 @@ __device__ __forceinline__ void solve(const PointScene& sc, Vel& v, Slot& c, flo
 // slot holds (anything, inf / NaN included) and keep their old velocities.  No exec-mask region, so the row sits in one
 // basic block with its neighbours (point_substep's lean passes).  The slot's accumulated impulses need no select: a slot
 // is prepared anew in every substep, its flag does not change within one, and nobody reads ln / lt of a slot that is off.
-template <int A, int B>
-__device__ __forceinline__ void solve_sel(const PointScene& sc, Vel& v, Slot& c, float mu) {
+template <int A, int B, class SC>
+__device__ __forceinline__ void solve_sel(const SC& sc, Vel& v, Slot& c, float mu) {
     Vel n = v;
     solve<A, B>(sc, n, c, mu);
     const bool on = c.on;
@@ -293,8 +374,8 @@ __device__ __forceinline__ void solve_sel(const PointScene& sc, Vel& v, Slot& c,
 // robot disc (A) vs box (B, possibly static)
 // PRED: every lane runs the whole narrow phase and `on` is the conjunction of the tests the branches of the plain form
 // return on; every field of the slot is defined (lanes out of range hold values nobody uses).
-template <int B, bool PRED = false>
-__device__ __forceinline__ void detect_disc_box(const PointScene& sc, Slot& c, float px, float py,
+template <int B, bool PRED = false, class SC>
+__device__ __forceinline__ void detect_disc_box(const SC& sc, Slot& c, float px, float py,
                                                 float qx, float qy, float bc, float bs, float hx,
                                                 float hy, float rad) {
     c.on = false;
@@ -363,7 +444,8 @@ __device__ __forceinline__ void detect_disc_box(const PointScene& sc, Slot& c, f
     prepare<ROBOT, B>(sc, c, -wx, -wy, 0.0f, 0.0f, rbx, rby, sep);
 }
 
-__device__ __forceinline__ void detect_disc_walls(const PointScene& sc, Slot& cx_, Slot& cy_,
+template <class SC>
+__device__ __forceinline__ void detect_disc_walls(const SC& sc, Slot& cx_, Slot& cy_,
                                                   float px, float py) {
     cx_.on = false; cy_.on = false;
     float sg = (px >= 0.0f) ? 1.0f : -1.0f;
@@ -374,8 +456,8 @@ __device__ __forceinline__ void detect_disc_walls(const PointScene& sc, Slot& cx
     if (sep < sc.contact_offset) prepare<ROBOT, STATIC>(sc, cy_, 0.0f, sg, 0.f, 0.f, 0.f, 0.f, sep);
 }
 
-template <int A>
-__device__ __forceinline__ void detect_box_walls(const PointScene& sc, Slot& x1, Slot& x2,
+template <int A, class SC>
+__device__ __forceinline__ void detect_box_walls(const SC& sc, Slot& x1, Slot& x2,
                                                  Slot& y1, Slot& y2, const Box& X, float hx,
                                                  float hy, float rad) {
     x1.on = x2.on = y1.on = y2.on = false;
@@ -416,8 +498,8 @@ __device__ __forceinline__ void detect_box_walls(const PointScene& sc, Slot& x1,
 }
 
 // box A vs box B: SAT over the 4 face axes, reference face + clipped incident edge
-template <int A, int B>
-__device__ __forceinline__ void detect_box_box(const PointScene& sc, Slot& c1, Slot& c2, float ax,
+template <int A, int B, class SC>
+__device__ __forceinline__ void detect_box_box(const SC& sc, Slot& c1, Slot& c2, float ax,
                                                float ay, float ca, float sa, float hax, float hay,
                                                float rada, float bx, float by, float cb, float sb,
                                                float hbx, float hby, float radb) {
@@ -516,8 +598,8 @@ template <int ID> __device__ __forceinline__ bool body_rests(const Vel& v) {
     return ((__float_as_uint(gvx<ID>(v)) | __float_as_uint(gvy<ID>(v)) | __float_as_uint(gw<ID>(v))) & 0x7f800000u) == 0u;
 }
 // the friction row of a body that moves
-template <int ID>
-__device__ __forceinline__ void solve_ground_friction_row(const PointScene& sc, Vel& v, Fric& f,
+template <int ID, class SC>
+__device__ __forceinline__ void solve_ground_friction_row(const SC& sc, Vel& v, Fric& f,
                                                           float m, float I, float Llin, float Lang) {
     float nlx = mad(-m, gvx<ID>(v), f.lx);
     float nly = mad(-m, gvy<ID>(v), f.ly);
@@ -545,8 +627,8 @@ __device__ __forceinline__ void solve_ground_friction_row(const PointScene& sc, 
     f.la = nla;
 }
 // ... behind the rest test as an exec-mask region (the general instances' rolled passes, step mode) ...
-template <int ID>
-__device__ __forceinline__ void solve_ground_friction(const PointScene& sc, Vel& v, Fric& f,
+template <int ID, class SC>
+__device__ __forceinline__ void solve_ground_friction(const SC& sc, Vel& v, Fric& f,
                                                       float m, float I, float Llin, float Lang) {
     if (body_rests<ID>(v)) return;
     solve_ground_friction_row<ID>(sc, v, f, m, I, Llin, Lang);
@@ -555,8 +637,8 @@ __device__ __forceinline__ void solve_ground_friction(const PointScene& sc, Vel&
 // row shares a basic block with the drive rows and the other body's rows (point_substep's lean passes).  (When the disc
 // clamp still was an IEEE sqrt + divide chain, a branch-free row was 9 % SLOWER -- that chain then sat on every pass's
 // critical path; with spec_rsqrt and the clamp a select it is the faster form: DESIGN.md section 6.)
-template <int ID>
-__device__ __forceinline__ void solve_ground_friction_sel(const PointScene& sc, Vel& v, Fric& f,
+template <int ID, class SC>
+__device__ __forceinline__ void solve_ground_friction_sel(const SC& sc, Vel& v, Fric& f,
                                                           float m, float I, float Llin, float Lang) {
     const bool rests = body_rests<ID>(v);
     Vel n = v;
@@ -597,17 +679,20 @@ __device__ __forceinline__ void integrate_box(Box& X, float h) {
 
 // Broad-phase predicates: the same expressions as the early-outs inside the detect functions, so
 // "not near" here implies that the corresponding slots come out `on = false`.
-__device__ __forceinline__ bool near_centres(const PointScene& sc, float ax, float ay, float bx, float by,
+template <class SC>
+__device__ __forceinline__ bool near_centres(const SC& sc, float ax, float ay, float bx, float by,
                                              float ra, float rb) {
     const float dx = bx - ax, dy = by - ay;
     const float lim = ra + rb + sc.contact_offset + 1e-3f;
     return !(mad(dx, dx, dy * dy) > lim * lim);
 }
-__device__ __forceinline__ bool near_walls_disc(const PointScene& sc, float px, float py) {
+template <class SC>
+__device__ __forceinline__ bool near_walls_disc(const SC& sc, float px, float py) {
     return ((sc.wall - fabsf(px)) - sc.robot_r < sc.contact_offset) ||
            ((sc.wall - fabsf(py)) - sc.robot_r < sc.contact_offset);
 }
-__device__ __forceinline__ bool near_walls_box(const PointScene& sc, const Box& X, float rad) {
+template <class SC>
+__device__ __forceinline__ bool near_walls_box(const SC& sc, const Box& X, float rad) {
     const float lim = rad + sc.contact_offset + 1e-3f;
     return ((sc.wall - fabsf(X.x)) <= lim) || ((sc.wall - fabsf(X.y)) <= lim);
 }
@@ -672,8 +757,8 @@ struct RowOff { static constexpr bool value = false; };
 // LONE: the build runs as ONE wavefront per SIMD (every BASELINE size), where the wave's own instruction stream is the
 // command's time: predicated rows and the two-level broad phase below.  The builds for two / three resident waves per
 // SIMD (saturated launches, VALU throughput-bound: predication ADDS vector instructions) keep the branches.
-template <bool ALL_FORCES, unsigned M, bool LONE = true>
-__device__ __forceinline__ void point_substep(const PointScene& sc, PointWorld& w, float ux, float uy,
+template <bool ALL_FORCES, unsigned M, bool LONE = true, class SC>
+__device__ __forceinline__ void point_substep(const SC& sc, PointWorld& w, float ux, float uy,
                                               bool form_dyn_force, PhaseClock* pc_ = nullptr) {
     M3_PH(1);
     constexpr bool RB = M & G_RB, RD = M & G_RD, RO = M & G_RO, RW = M & G_RW, BW = M & G_BW,
@@ -988,8 +1073,8 @@ static __device__ unsigned int g_cyc[64 * 16];
 #endif
 
 // one sim.step(): substeps x (forces, detect, solve, integrate)
-template <bool ALL_FORCES, bool LONE = true>
-__device__ __forceinline__ void point_step(const PointScene& sc, PointWorld& w, float ux, float uy,
+template <bool ALL_FORCES, bool LONE = true, class SC>
+__device__ __forceinline__ void point_step(const SC& sc, PointWorld& w, float ux, float uy,
                                            bool need_dyn_force = true, PhaseClock* pc_ = nullptr) {
     for (int sub = 0; sub < sc.substeps; ++sub) {
         const bool form = need_dyn_force && sub == sc.substeps - 1;

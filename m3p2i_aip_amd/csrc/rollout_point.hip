@@ -2,6 +2,7 @@
 // (rollout_point_kernel.hpp), the noise transpose and the step-mode (IsaacGymWrapper-like) kernels.
 #include "rollout_point_kernel.hpp"
 #include "episode_lane.hpp"
+#include "point_step_mode.hpp"
 
 namespace m3 {
 
@@ -70,6 +71,52 @@ static void launch_rollout_point_weighted_batch(const BatchRolloutEntryW* tab, i
     }
 }
 
+// ---- run-time scene (m3_set_point_scene): the general, weighted instance on PointSceneRT -- the arena arrives as a kernel
+// argument instead of being compiled in.  Three builds picked by the same rule; no _ref build: the compile-time solver scene is
+// a property of the default-scene kernels.  At the default values the same bits as k_rollout_point_w (same operations in the same
+// order; the broad-phase radii are conservative, planar_dyn.hpp).
+__global__ __launch_bounds__(64) void k_rollout_point_s(const RolloutArgs a, const PointSceneRT sc, const PointCostWeights wt) {
+    rollout_point_body<true, -1, true, true>(a, sc, &wt);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_rollout_point_s_occ2(
+    const RolloutArgs a, const PointSceneRT sc, const PointCostWeights wt) {
+    rollout_point_body<true, -1, false, true>(a, sc, &wt);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_rollout_point_s_occ3(
+    const RolloutArgs a, const PointSceneRT sc, const PointCostWeights wt) {
+    rollout_point_body<true, -1, false, true>(a, sc, &wt);
+}
+void launch_rollout_point_scene(const RolloutArgs& a, const PointSceneRT& sc, const PointCostWeights& wt, const RolloutPlan& p,
+                                hipStream_t s) {
+    const int blocks = p.blocks;
+    switch (rollout_point_build(blocks, false)) {
+        case BUILD_OCC3: hipLaunchKernelGGL(k_rollout_point_s_occ3, dim3(blocks), dim3(64), 0, s, a, sc, wt); break;
+        case BUILD_OCC2: hipLaunchKernelGGL(k_rollout_point_s_occ2, dim3(blocks), dim3(64), 0, s, a, sc, wt); break;
+        default: hipLaunchKernelGGL(k_rollout_point_s, dim3(blocks), dim3(64), 0, s, a, sc, wt); break;
+    }
+}
+// ... and the scene group's batched twin: its own entry type (BatchRolloutEntryS: arguments + the handle's scene + its weights),
+// so that handles with different scenes share one launch and the entries of the other kernels keep their size
+__global__ __launch_bounds__(64) void kb_rollout_point_s(const BatchRolloutEntryS* __restrict__ tab) {
+    rollout_point_body<true, -1, true, true>(tab[blockIdx.y].a, tab[blockIdx.y].sc, &tab[blockIdx.y].wt);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void kb_rollout_point_s_occ2(
+    const BatchRolloutEntryS* __restrict__ tab) {
+    rollout_point_body<true, -1, false, true>(tab[blockIdx.y].a, tab[blockIdx.y].sc, &tab[blockIdx.y].wt);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void kb_rollout_point_s_occ3(
+    const BatchRolloutEntryS* __restrict__ tab) {
+    rollout_point_body<true, -1, false, true>(tab[blockIdx.y].a, tab[blockIdx.y].sc, &tab[blockIdx.y].wt);
+}
+void launch_rollout_point_batch_s(const BatchRolloutEntryS* tab, int n, const RolloutPlan& p, hipStream_t s) {
+    const dim3 grid(p.blocks, n);
+    switch (rollout_point_build(p.blocks * n, false)) {
+        case BUILD_OCC3: hipLaunchKernelGGL(kb_rollout_point_s_occ3, grid, dim3(64), 0, s, tab); break;
+        case BUILD_OCC2: hipLaunchKernelGGL(kb_rollout_point_s_occ2, grid, dim3(64), 0, s, tab); break;
+        default: hipLaunchKernelGGL(kb_rollout_point_s, grid, dim3(64), 0, s, tab); break;
+    }
+}
+
 // The form of a launch.  Instance -1: the general instance (every sampler mode, task at run time); 0..3: the instance with
 // the reference's default sampler and that task compiled in (rollout_point_task*.hip).  Only the general and the push_pull
 // instances carry the epilogue that leaves the workgroups' cost minima (rollout_point_kernel.hpp).
@@ -78,7 +125,18 @@ static void launch_rollout_point_weighted_batch(const BatchRolloutEntryW* tab, i
 // form_request: the two-wavefront form (RolloutPlan::form = 1) exists for the navigation and push instances in the builds with
 // one resident wavefront per SIMD, with the default weights and a horizon whose tables fit its LDS; 1 takes it wherever it
 // exists, -1 where rollout_companion_pays as well, 0 never (m3_batch_command, the episode paths).
-RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, bool weighted, int form_request) {
+// scene: the handle's arena is not the default (or the run-time-scene build is forced on): the general instance on PointSceneRT,
+// which is always the weighted build as well -- instance -1, form 0, ref 0, whatever the sampler, the task and the weights.
+RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, bool weighted, int form_request, bool scene) {
+    if (scene) {
+        RolloutPlan p{};
+        p.scene = 1; p.weighted = 1;
+        p.instance = -1; p.ref = 0; p.form = 0;
+        p.lanes = a.lanes;
+        p.blocks = (a.Kl + a.lanes - 1) / a.lanes;
+        p.rows = a.wave_min ? p.blocks : 0;
+        return p;
+    }
 #if defined(M3_ABL_GENERAL_ONLY) || defined(M3_ABL_COUNT) || defined(M3_ABL_PHASES)   // (experiments: one kernel for all modes;
     // the instrumented builds keep their counters in this translation unit)
     const bool general = true;
@@ -156,83 +214,9 @@ void launch_transpose_noise(const float* src, float* dst, int K, int T, int nu, 
 }
 
 // ======================= step mode (IsaacGymWrapper-like surface) =======================
-__device__ __forceinline__ void soa_load(const float* wd, int Kl, int i, PointWorld& w) {
-    const float* p = wd + i;
-    w.rx = p[0 * Kl]; w.ry = p[1 * Kl]; w.rvx = p[2 * Kl]; w.rvy = p[3 * Kl];
-    w.B.x = p[4 * Kl]; w.B.y = p[5 * Kl]; w.B.c = p[6 * Kl]; w.B.s = p[7 * Kl];
-    w.B.vx = p[8 * Kl]; w.B.vy = p[9 * Kl]; w.B.w = p[10 * Kl];
-    w.D.x = p[11 * Kl]; w.D.y = p[12 * Kl]; w.D.c = p[13 * Kl]; w.D.s = p[14 * Kl];
-    w.D.vx = p[15 * Kl]; w.D.vy = p[16 * Kl]; w.D.w = p[17 * Kl];
-    w.fRx = p[18 * Kl]; w.fRy = p[19 * Kl]; w.fBx = p[20 * Kl]; w.fBy = p[21 * Kl];
-    w.fcDx = p[22 * Kl]; w.fcDy = p[23 * Kl]; w.fcBx = p[24 * Kl]; w.fcBy = p[25 * Kl];
-    w.fcRx = p[26 * Kl]; w.fcRy = p[27 * Kl];
-}
-__device__ __forceinline__ void soa_store(float* wd, int Kl, int i, const PointWorld& w) {
-    float* p = wd + i;
-    p[0 * Kl] = w.rx; p[1 * Kl] = w.ry; p[2 * Kl] = w.rvx; p[3 * Kl] = w.rvy;
-    p[4 * Kl] = w.B.x; p[5 * Kl] = w.B.y; p[6 * Kl] = w.B.c; p[7 * Kl] = w.B.s;
-    p[8 * Kl] = w.B.vx; p[9 * Kl] = w.B.vy; p[10 * Kl] = w.B.w;
-    p[11 * Kl] = w.D.x; p[12 * Kl] = w.D.y; p[13 * Kl] = w.D.c; p[14 * Kl] = w.D.s;
-    p[15 * Kl] = w.D.vx; p[16 * Kl] = w.D.vy; p[17 * Kl] = w.D.w;
-    p[18 * Kl] = w.fRx; p[19 * Kl] = w.fRy; p[20 * Kl] = w.fBx; p[21 * Kl] = w.fBy;
-    p[22 * Kl] = w.fcDx; p[23 * Kl] = w.fcDy; p[24 * Kl] = w.fcBx; p[25 * Kl] = w.fcBy;
-    p[26 * Kl] = w.fcRx; p[27 * Kl] = w.fcRy;
-}
-
-__device__ __forceinline__ void write_body13(float* r, float x, float y, float c, float s,
-                                             float vx, float vy, float wz) {
-    // yaw (c, s) -> quaternion (0, 0, sin(th/2), cos(th/2)) with cos(th/2) >= 0
-    float qw = sqrtf(fmaxf(0.5f * (1.0f + c), 0.0f));
-    float qz;
-    if (qw > 1e-4f) qz = s / (2.0f * qw);
-    else { qz = 1.0f; qw = 0.0f; }
-    r[0] = x; r[1] = y;  // r[2] (z) is left as set at init
-    r[3] = 0.0f; r[4] = 0.0f; r[5] = qz; r[6] = qw;
-    r[7] = vx; r[8] = vy; r[9] = 0.0f;
-    r[10] = 0.0f; r[11] = 0.0f; r[12] = wz;
-}
-
-// SoA world of environment i -> the wrapper's views (what a refresh_*_tensor call of Isaac Gym does)
-__device__ __forceinline__ void push_views(const SimViews& v, int i, const PointWorld& w) {
-    if (v.dof_state) {
-        *reinterpret_cast<float4*>(v.dof_state + (size_t)i * 4) = make_float4(w.rx, w.rvx, w.ry, w.rvy);
-    }
-    if (v.root_state) {
-        float* base = v.root_state + (size_t)i * v.n_actors * 13;
-        write_body13(base + v.box_actor * 13, w.B.x, w.B.y, w.B.c, w.B.s, w.B.vx, w.B.vy, w.B.w);
-        write_body13(base + v.dyn_actor * 13, w.D.x, w.D.y, w.D.c, w.D.s, w.D.vx, w.D.vy, w.D.w);
-        // (fixed base of the robot: stays at its init pose)
-    }
-    if (v.rigid_body_state) {
-        float* base = v.rigid_body_state + (size_t)i * v.n_bodies * 13;
-        write_body13(base + v.box_body * 13, w.B.x, w.B.y, w.B.c, w.B.s, w.B.vx, w.B.vy, w.B.w);
-        write_body13(base + v.dyn_body * 13, w.D.x, w.D.y, w.D.c, w.D.s, w.D.vx, w.D.vy, w.D.w);
-        // robot links: plane (fixed), link_x (x only), link_y (x, y)
-        write_body13(base + (v.robot_body - 1) * 13, w.rx, 0.0f, 1.0f, 0.0f, w.rvx, 0.0f, 0.0f);
-        write_body13(base + v.robot_body * 13, w.rx, w.ry, 1.0f, 0.0f, w.rvx, w.rvy, 0.0f);
-    }
-    if (v.net_contact_force) {
-        float* f = v.net_contact_force + (size_t)i * v.n_bodies * 3;
-        f[v.box_body * 3 + 0] = w.fcBx; f[v.box_body * 3 + 1] = w.fcBy;
-        f[v.dyn_body * 3 + 0] = w.fcDx; f[v.dyn_body * 3 + 1] = w.fcDy;
-        f[v.robot_body * 3 + 0] = w.fcRx; f[v.robot_body * 3 + 1] = w.fcRy;
-    }
-}
-
-// one sim.step() of every environment and the refresh of the wrapper's views in the same launch
-// (u_keep != u: the targets come from the caller's tensor and are kept for the steps after this one, as a
-// set_dof_velocity_target_tensor in front of the step would have done)
 __global__ __launch_bounds__(64) void k_sim_step(const PointScene sc, const SimViews v, float* wd, const float* u,
                                                  float* u_keep, int Kl) {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= Kl) return;
-    PointWorld w;
-    soa_load(wd, Kl, i, w);
-    const float2 uu = *reinterpret_cast<const float2*>(u + (size_t)i * 2);
-    if (u_keep != u) *reinterpret_cast<float2*>(u_keep + (size_t)i * 2) = uu;
-    point_step<true>(sc, w, uu.x, uu.y);
-    soa_store(wd, Kl, i, w);
-    push_views(v, i, w);
+    sim_step_body(sc, v, wd, u, u_keep, Kl);
 }
 void launch_sim_step(const PointScene& sc, const SimViews& v, float* world, const float* u, float* u_keep, int Kl,
                      hipStream_t s) {
@@ -417,66 +401,33 @@ void launch_episodes_pre(const EpisodeArgs& a, int tick, hipStream_t s) {
 // after the command: trace row, suction, step + views, collision count, the last tick's end
 // (g) not masked: an episode that is done keeps its row evolving (on its last plan); nothing of it is recorded any more
 __global__ __launch_bounds__(64) void k_episodes_post(const PointScene sc, const EpisodeArgs a, int tick) {
-    const int e = blockIdx.x * 64 + threadIdx.x;
-    if (e >= a.n) return;
-    const SimViews& v = a.v;
-    const EpisodeLane L = a.lane[e];
-    m3_episode_status& st = a.st[e];
-    const bool live = st.done_tick < 0;
-    const float* action = L.plan;            // row 0 of the plan: the velocity target of the 1-env world
-    const float ux = action[0], uy = action[1];
-    if (live && a.trace) {   // closed_loop.run(trace=True): robot x, y | box body x, y, qz, qw | dyn-obs root x, y | action
-        float* o = a.trace + ((size_t)tick * a.n + e) * 10;
-        const float* rb = v.rigid_body_state + ((size_t)e * v.n_bodies + v.box_body) * 13;
-        const float* dy = v.root_state + ((size_t)e * v.n_actors + v.dyn_actor) * 13;
-        o[0] = v.dof_state[(size_t)e * 4 + 0]; o[1] = v.dof_state[(size_t)e * 4 + 2];
-        o[2] = rb[0]; o[3] = rb[1]; o[4] = rb[5]; o[5] = rb[6];
-        o[6] = dy[0]; o[7] = dy[1];
-        o[8] = ux; o[9] = uy;
-    }
-    const int Kl = a.n;
-    float* p = a.world + e;
-    if (L.suction != EP_SUCTION_OFF) {
-        // check_and_apply_suction: k_sim_suction's action path with apply = 1, its expressions verbatim, and
-        // (b) a gate per episode instead of one scalar for all environments.
-        // (a) threshold 1.5: each episode is a 1-env "real world" (skill_utils.py: num_envs == 1), although this
-        //     world's K_local is N -- m3_sim_check_and_apply_suction on it would pick 1.8.
-        const float thresh = 1.5f, reach = 0.6f, kp = L.kp;
-        const bool enabled = a.gate[e] != 0;
-        const float ex = p[4 * Kl] - p[0 * Kl], ey = p[5 * Kl] - p[1 * Kl];   // robot -> box
-        const float len = sqrtf(ex * ex + ey * ey);
-        const float inv = 1.0f / len;
-        float fx = 0.0f, fy = 0.0f;                                          // force on the robot
-        if (inv > thresh) {
-            fx = clamp500(kp * (ex * inv));
-            fy = clamp500(kp * (ey * inv));
-        }
-        const float along = action[0] * (-ex) + action[1] * (-ey);   // action . (robot - box)
-        const bool pulling = enabled && len < reach && along > 0.0f;
-        if (pulling) {
-            p[18 * Kl] = fx; p[19 * Kl] = fy; p[20 * Kl] = -fx; p[21 * Kl] = -fy;
-        }
-    }
-    // step(): k_sim_step's body on row e (set_dof_velocity_target_tensor(action) in front of it)
-    PointWorld w;
-    soa_load(a.world, Kl, e, w);
-    point_step<true>(sc, w, ux, uy);
-    soa_store(a.world, Kl, e, w);
-    push_views(v, e, w);
-    if (!live) return;
-    // (c) the dyn-obs contact force of the views after the step, as closed_loop.run reads it
-    if (ep_collision(w.fcDx, w.fcDy)) st.collision_ticks += 1;
-    if (tick == a.last_tick) {   // out of ticks: the episode ends unsuccessful with the state after this step
-        st.done_tick = tick; st.success = 0;
-        st.final_pos[0] = L.task == 0 ? w.rx : w.B.x;
-        st.final_pos[1] = L.task == 0 ? w.ry : w.B.y;
-    }
+    episodes_post_body(sc, a, tick);
 }
 void launch_episodes_post(const PointScene& sc, const EpisodeArgs& a, int tick, hipStream_t s) {
     hipLaunchKernelGGL(k_episodes_post, dim3((a.n + 63) / 64), dim3(64), 0, s, sc, a, tick);
 }
 
 }  // namespace m3
+
+// Diagnostic (host only, no device call): the form plan_rollout_point gives a point_env rollout with these settings -- what
+// m3_rollout / m3_batch_command would launch.  out: instance, ref, form, weighted, scene, blocks, rows, lanes.
+extern "C" int m3_point_rollout_plan(int task, int multi_modal, int mode_simple, int sampling_random, int avoid_dyn_obs,
+                                     int K_local, int T, int lanes, float dt, int substeps, int solver_iters, int weighted,
+                                     int scene, int form_request, int want_minima, int out[8]) {
+    if (!out || K_local < 1 || T < 1 || lanes < 1 || lanes > 64 || substeps < 1) return M3_ERR_BAD_ARG;
+    m3::RolloutArgs a{};
+    a.Kl = a.Kg = K_local; a.T = T; a.nu = 2; a.lanes = lanes;
+    a.multi_modal = multi_modal; a.mode_simple = mode_simple; a.sampling_random = sampling_random;
+    a.cp.task = task; a.cp.multi_modal = multi_modal; a.cp.avoid_dyn_obs = avoid_dyn_obs;
+    static float minima_stand_in[3];
+    a.wave_min = want_minima ? minima_stand_in : nullptr;   // (only tested against null)
+    m3::PointScene sc;
+    m3::make_point_scene(sc, dt, substeps, solver_iters);
+    const m3::RolloutPlan p = m3::plan_rollout_point(a, sc, weighted != 0, form_request, scene != 0);
+    out[0] = p.instance; out[1] = p.ref; out[2] = p.form; out[3] = p.weighted; out[4] = p.scene; out[5] = p.blocks;
+    out[6] = p.rows; out[7] = p.lanes;
+    return M3_OK;
+}
 
 #ifdef M3_ABL_PHASES
 extern "C" void m3_dbg_phases(unsigned long long* out, int reset) {

@@ -57,8 +57,10 @@ __device__ __forceinline__ void load_world_from_sim(const float* dof, const floa
 // mode compiled in 0.1530, task compiled in as well 0.143 (same results bit for bit: only which code exists).
 // LONE: a build for one resident wavefront per SIMD (planar_dyn.hpp: predicated rows, two-level broad phase)
 // WEIGHTED: the running cost is point_cost_w with *wt (k_rollout_point_w below; wt is not read otherwise)
-template <bool GENERAL, int TASK, bool LONE = true, bool WEIGHTED = false>
-__device__ __forceinline__ void rollout_point_body(const RolloutArgs& a_, const PointScene& sc,
+// SC: the scene type -- PointScene (the reference's arena compiled in) or PointSceneRT (m3_set_point_scene: k_rollout_point_s in
+// rollout_point.hip, always GENERAL and WEIGHTED)
+template <bool GENERAL, int TASK, bool LONE = true, bool WEIGHTED = false, class SC = PointScene>
+__device__ __forceinline__ void rollout_point_body(const RolloutArgs& a_, const SC& sc,
                                                    const PointCostWeights* wt = nullptr) {
     RolloutArgs a = a_;
     if constexpr (!GENERAL) {

@@ -253,6 +253,29 @@ class HipEngine:
         """-1: the weighted kernels exactly when the weights are not the defaults (default); 1 / 0 forced (tests, A/B)."""
         self._ck(self.lib.m3_set_weighted_cost_instance(self._h, int(on)))
 
+    def set_point_scene(self, scene=None, **overrides):
+        """Extension, point_env: the arena (a mapping with keys of _lib.POINT_SCENE_DEFAULTS, missing keys = the reference's
+        arena; keyword arguments override single fields; nothing at all = the defaults).  Applies from the next command /
+        rollout / step / episode tick.  scenes.point_scene_from_actors derives the mapping from an actor list."""
+        fields = {**(scene or {}), **overrides}
+        if not fields:
+            self._ck(self.lib.m3_set_point_scene(self._h, None))
+            return
+        unknown = sorted(set(fields) - set(L.POINT_SCENE_DEFAULTS))
+        if unknown:
+            raise ValueError(f"unknown point scene field(s) {unknown}: one of {list(L.POINT_SCENE_DEFAULTS)}")
+        sc = L.PointSceneFields(**{**L.POINT_SCENE_DEFAULTS, **{k: float(v) for k, v in fields.items()}})
+        self._ck(self.lib.m3_set_point_scene(self._h, C.byref(sc)))
+
+    def point_scene(self):
+        sc = L.PointSceneFields()
+        self._ck(self.lib.m3_get_point_scene(self._h, C.byref(sc)))
+        return {n: getattr(sc, n) for n in L.POINT_SCENE_DEFAULTS}
+
+    def set_point_scene_instance(self, on=-1):
+        """-1: the run-time-scene kernels exactly when the scene is not the default (default); 1 / 0 forced (tests, A/B)."""
+        self._ck(self.lib.m3_set_point_scene_instance(self._h, int(on)))
+
     def set_multi_modal(self, mm):
         self._ck(self.lib.m3_set_multi_modal(self._h, int(bool(mm))))
 

@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import weakref
 from dataclasses import dataclass, field
-from typing import List
+from typing import List, Optional
 
 import torch
 
@@ -44,12 +44,15 @@ class IsaacGymConfig:
     spacing: float = 10
     camera_pos: List[float] = field(default_factory=lambda: [1.5, 6, 8])
     camera_target: List[float] = field(default_factory=lambda: [1.5, 0, 0])
+    point_scene: Optional[dict] = None   # EXTENSION, point_env: field overrides of the arena (_lib.POINT_SCENE_DEFAULTS), e.g.
+                                         # {obs_x: -1.0, wall: 2.95}; None = the reference's arena (compat copies the top-level
+                                         # `point_scene` config key here)
 
 
 class IsaacGymWrapper:
     def __init__(self, cfg: IsaacGymConfig, env_type: str = "point_env", num_envs: int = 1,
                  viewer: bool = False, device: str = "cuda:0", cube_on_shelf: bool = False,
-                 k_offset: int = 0, num_envs_global: int | None = None):
+                 k_offset: int = 0, num_envs_global: int | None = None, actors=None):
         if viewer or getattr(cfg, "viewer", False):
             # scripts/sim.py:19-27 asks for the viewer of its 1-env world; this build has none: the world
             # runs headless (visualize_trajs / play_with_cube are no-ops), keyboard_control raises
@@ -60,6 +63,36 @@ class IsaacGymWrapper:
         self.cfg = cfg
         self.env_type = env_type
         self.env_cfg = [scenes.Actor(**vars(a)) for a in scenes.ENVS[env_type]]
+        # EXTENSION, point_env: another arena -- `actors` (a list shaped like scenes.POINT_ENV: same names, same order) and / or
+        # the config's `point_scene` field overrides on top of it.  self.point_scene: the resulting field overrides of
+        # m3_point_scene, None while the arena is the reference's (planners that attach to this wrapper take them over)
+        self.point_scene = None
+        if actors is not None or getattr(cfg, "point_scene", None):
+            if env_type != "point_env":
+                raise ValueError("actors / point_scene: point_env only")
+            sc = dict(L.POINT_SCENE_DEFAULTS)
+            if actors is not None:
+                if [a.name for a in actors] != [a.name for a in self.env_cfg]:
+                    raise ValueError("actors: the names and the order of scenes.POINT_ENV are fixed")
+                self.env_cfg = [scenes.Actor(**vars(a)) for a in actors]
+                sc = scenes.point_scene_from_actors(self.env_cfg)
+            given = dict(getattr(cfg, "point_scene", None) or {})
+            unknown = sorted(set(given) - set(sc))
+            if unknown:
+                raise ValueError(f"point_scene: unknown field(s) {unknown}: one of {list(sc)}")
+            sc.update({k: float(v) for k, v in given.items()})
+            if sc != L.POINT_SCENE_DEFAULTS:
+                self.point_scene = sc
+            for a in self.env_cfg:      # the rows of `obs` and the walls carry the scene's positions
+                if a.name == "obs":
+                    a.init_pos = [sc["obs_x"], sc["obs_y"], a.init_pos[2]]
+                    a.size = [2 * sc["obs_hx"], 2 * sc["obs_hy"], a.size[2]]
+                elif a.name.startswith("wall-"):
+                    ax = 0 if a.name in ("wall-1", "wall-2") else 1
+                    sign = 1.0 if a.name in ("wall-1", "wall-3") else -1.0
+                    pos = list(a.init_pos)
+                    pos[ax] = sign * (sc["wall"] + 0.5 * a.size[0])
+                    a.init_pos = pos
         for i, a in enumerate(self.env_cfg):
             a.handle = i
         self.device = device
@@ -84,6 +117,8 @@ class IsaacGymWrapper:
             K=num_envs_global or K, K_local=K, k_offset=k_offset, T=1,
             nu=self.dofs_per_robot, env_type=env_type, dt=cfg.dt, substeps=cfg.substeps,
             device=dev.index or 0, sim_only=True, filter_u=False, cube_on_shelf=cube_on_shelf))
+        if self.point_scene is not None:
+            self._engine.set_point_scene(self.point_scene)
 
         # initial scene (start_sim / set_initial_joint_pose / acquire_states: :68-118,222-240)
         root = torch.zeros(nA, 13)

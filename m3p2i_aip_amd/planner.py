@@ -371,6 +371,15 @@ class MPPI():
         s = self._sim
         if s is None:
             raise RuntimeError("fused command() needs the HIP IsaacGymWrapper; use planner.attach(sim, objective)")
+        # (extension, off by default: the planner's own handle plans in the arena of the wrapper it is attached to; no call
+        # while both are the reference's)
+        # Precedence: while `follow_sim_scene` is True (the default) the wrapper's arena wins -- it is pushed whenever it differs
+        # from what this planner pushed last, which also overwrites an arena set by hand on self._engine.  A planner whose
+        # model is to differ from its world on purpose sets `planner.follow_sim_scene = False` and owns its engine's arena.
+        arena = getattr(s, "point_scene", None)
+        if getattr(self, "follow_sim_scene", True) and arena != getattr(self, "_point_scene_pushed", None):
+            self._engine.set_point_scene(arena)
+            self._point_scene_pushed = None if arena is None else dict(arena)
         if getattr(self, "_bound_sim", None) is not s:
             if self.env_type == "point_env":
                 self._engine.bind_sim_point(s._dof_state, s._root_state,

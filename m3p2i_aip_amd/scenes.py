@@ -87,3 +87,72 @@ def body_index(env_type: str, actor: str, link: str) -> int:
 
 def num_bodies(env_type: str) -> int:
     return sum(len(a.links) for a in ENVS[env_type])
+
+
+# ---- the point_env arena as the dynamics see it (m3_point_scene; HipEngine.set_point_scene) ----
+def mean_footprint_radius(a: float, b: float) -> float:
+    """Mean distance of the points of an a x b rectangle from its centre (the lever arm of a box's ground friction, `*_req`):
+    d/6 + a^2/(12 b) asinh(b/a) + b^2/(12 a) asinh(a/b) with d = sqrt(a^2 + b^2), in binary64."""
+    import math
+    d = math.hypot(a, b)
+    return d / 6.0 + a * a / (12.0 * b) * math.asinh(b / a) + b * b / (12.0 * a) * math.asinh(a / b)
+
+
+def point_scene_from_actors(actors) -> dict:
+    """The fields of m3_point_scene (keys and order of _lib.POINT_SCENE_DEFAULTS) from an actor list shaped like POINT_ENV, by
+    the rules the dynamics' scene constants were derived with:
+      * half extents from `size`; the fixed obstacle's centre from `init_pos`;
+      * `wall`: the inner face of the walls, |position| - half thickness -- the four walls must be symmetric about the origin
+        (the dynamics know one `wall`), otherwise ValueError;
+      * mass = 1000 kg/m^3 x volume (the yaml mass is not applied: isaacgym_wrapper.py:293-300), I = m ((2hx)^2 + (2hy)^2) / 12;
+      * pair frictions: the average of the two actors' `friction`; the ground and the fixed actors are at 1.0;
+      * `*_req` = mean_footprint_radius of the footprint.
+    The robot's radius and mass come from its urdf, which an actor list does not carry: they keep their defaults.
+    Every value is formed in binary64 and rounded once to binary32.  A derived value within two units in the last place of the
+    literal default (the oracle forms box_I, dyn_I and *_req of the shipped arena in binary32, which can differ from the
+    rounded binary64 value in the last bit) is PINNED to the literal, so that point_scene_from_actors(POINT_ENV) is the default
+    arena bit for bit and the shipped scene stays on the default-scene kernels."""
+    import numpy as np
+    from ._lib import POINT_SCENE_DEFAULTS
+    by = {a.name: a for a in actors}
+    for need in ("box", "dyn-obs", "obs", "point_robot", "wall-1", "wall-2", "wall-3", "wall-4"):
+        if need not in by:
+            raise ValueError(f"point_scene_from_actors: no actor {need!r}")
+    faces = []
+    for name, axis in (("wall-1", 0), ("wall-2", 0), ("wall-3", 1), ("wall-4", 1)):
+        w = by[name]
+        if abs(w.init_pos[1 - axis]) > 1e-9:
+            raise ValueError(f"point_scene_from_actors: {name} is not centred on its axis (the dynamics know one centred square)")
+        faces.append(abs(w.init_pos[axis]) - 0.5 * w.size[0])
+    signs = [by["wall-1"].init_pos[0] * by["wall-2"].init_pos[0], by["wall-3"].init_pos[1] * by["wall-4"].init_pos[1]]
+    if max(faces) - min(faces) > 1e-9 or any(s >= 0 for s in signs):
+        raise ValueError(f"point_scene_from_actors: the four walls are not symmetric about the origin (inner faces {faces}); "
+                         "the dynamics know one `wall`")
+    d = dict(POINT_SCENE_DEFAULTS)
+    d["wall"] = faces[0]
+    robot_mu = by["point_robot"].friction
+
+    def pair(x, y):
+        return 0.5 * (x + y)
+
+    for key, name in (("box", "box"), ("dyn", "dyn-obs")):
+        a = by[name]
+        sx, sy, sz = a.size
+        m = 1000.0 * sx * sy * sz
+        d[f"{key}_hx"], d[f"{key}_hy"], d[f"{key}_m"] = 0.5 * sx, 0.5 * sy, m
+        d[f"{key}_I"] = m * (sx * sx + sy * sy) / 12.0
+        d[f"{key}_mu_g"] = pair(a.friction, 1.0)
+        d[f"{key}_req"] = mean_footprint_radius(sx, sy)
+    obs = by["obs"]
+    d["obs_x"], d["obs_y"] = obs.init_pos[0], obs.init_pos[1]
+    d["obs_hx"], d["obs_hy"] = 0.5 * obs.size[0], 0.5 * obs.size[1]
+    fb, fd = by["box"].friction, by["dyn-obs"].friction
+    d["mu_rb"], d["mu_rd"], d["mu_ro"], d["mu_rw"] = pair(robot_mu, fb), pair(robot_mu, fd), pair(robot_mu, 1.0), pair(robot_mu, 1.0)
+    d["mu_bw"], d["mu_dw"], d["mu_bd"], d["mu_bo"], d["mu_do"] = pair(fb, 1.0), pair(fd, 1.0), pair(fb, fd), pair(fb, 1.0), pair(fd, 1.0)
+    out = {}
+    for n, lit in POINT_SCENE_DEFAULTS.items():
+        v = float(np.float32(d[n]))
+        if abs(v - lit) <= 2.0 * float(np.spacing(np.float32(abs(lit)))):
+            v = lit
+        out[n] = v
+    return out
