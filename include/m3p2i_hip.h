@@ -394,6 +394,25 @@ int m3_get_point_scene(const m3_handle* h, m3_point_scene* out);
 /* Test and A/B switch: -1 the automatic choice above (default), 1 the run-time-scene build whatever the values, 0 never --
  * with a scene other than the default the next command / rollout / step is then refused (M3_ERR_STATE). */
 int m3_set_point_scene_instance(m3_handle* h, int on);
+/* EXTENSION, sim_only point_env handles: one arena PER ENVIRONMENT -- environment i steps in scenes[i] (the N independent "real
+ * worlds" of a wrapper with num_envs = N, the world handle of m3_episodes_*).  n must equal the handle's K_local.  Applies from
+ * the next m3_sim_step, m3_sim_step_with_target or episode tick / half-tick; survives m3_reset; may be called between ticks of a
+ * running m3_episodes set, and m3_episodes_create accepts a world with rows set.  scenes == NULL clears the rows (n is not
+ * read): the handle is back on its single scene and runs exactly the kernels it ran before.  Every row gets the checks of
+ * m3_set_point_scene; a failing one is M3_ERR_BAD_ARG and the message names the row and the field ("row 2: box_m is not
+ * finite").  A panda_env handle is M3_ERR_UNSUPPORTED, a handle that is not sim_only M3_ERR_STATE (a planner's rollouts share
+ * one model: m3_set_point_scene), n != K_local M3_ERR_SHAPE.  Every check runs before any state changes: after a refusal the
+ * rows and the single scene are what they were.
+ * With m3_set_point_scene: the LAST call wins -- m3_set_point_scene on a handle with rows set clears the rows; while rows are
+ * set m3_get_point_scene keeps returning the single scene (which no step reads), and m3_set_point_scene_instance(h, 0) refuses
+ * the next step as it does for a non-default single scene.
+ * Memory: the first call on a handle allocates a device table, its pinned host mirror and a host copy of the rows; later calls
+ * reuse them (and wait for the handle's stream before they rewrite the mirror).  The upload is one hipMemcpyAsync on the
+ * handle's stream.  m3_sim_step* and m3_episodes_tick / _begin / _end allocate nothing because of the rows. */
+int m3_set_point_scene_rows(m3_handle* h, const m3_point_scene* scenes, int n);
+/* row `row` as it was set; M3_ERR_STATE while no rows are set, M3_ERR_BAD_ARG for a row outside 0 .. K_local - 1 */
+int m3_get_point_scene_row(const m3_handle* h, int row, m3_point_scene* out);
+int m3_point_scene_rows_set(const m3_handle* h);   /* 0 / 1 */
 /* Diagnostic, host only (no device call, no handle): the kernel form a point_env rollout with these settings takes -- what
  * m3_rollout / m3_batch_command would launch for a handle configured so.  weighted / scene: what the handle's cost weights and
  * scene (or their switches) amount to; form_request: m3_set_point_rollout_form's value; want_minima: the command keeps the

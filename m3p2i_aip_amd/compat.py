@@ -128,6 +128,9 @@ class ExampleConfig:
                                                       # `point_scene={obs_x: -1.0, wall: 2.95}` (_lib.POINT_SCENE_DEFAULTS); the
                                                       # wrappers built from cfg.isaacgym set it on their engines, the planners
                                                       # that attach to them take it over
+    world_point_scene: Optional[Dict[str, float]] = None   # EXTENSION, point_env: field overrides of the REAL world only, on top
+                                                           # of point_scene (model mismatch: the planner and its K-env simulator
+                                                           # keep point_scene); world_isaacgym_config applies it
 
 
 def make_config(config_name="config_point", overrides=()):
@@ -169,7 +172,26 @@ def make_config(config_name="config_point", overrides=()):
         if cfg.env_type != "point_env":
             raise ValueError("point_scene: point_env only")
         cfg.isaacgym.point_scene = dict(cfg.point_scene)   # (the wrappers are built from cfg.isaacgym)
+    if cfg.world_point_scene:
+        if cfg.env_type != "point_env":
+            raise ValueError("world_point_scene: point_env only")
+        cfg.world_point_scene = dict(cfg.world_point_scene)
     return cfg
+
+
+def world_point_scene(cfg):
+    """The field overrides of the arena of cfg's REAL world: `point_scene` with `world_point_scene` on top ({} = the
+    reference's arena)."""
+    return {**(getattr(cfg, "point_scene", None) or {}), **(getattr(cfg, "world_point_scene", None) or {})}
+
+
+def world_isaacgym_config(cfg):
+    """cfg.isaacgym as the 1-env or N-env REAL world is built from it: cfg.isaacgym itself unless `world_point_scene` is set,
+    else a copy whose point_scene carries those overrides too.  The planner's K-env simulator is built from cfg.isaacgym."""
+    if not getattr(cfg, "world_point_scene", None):
+        return cfg.isaacgym
+    import dataclasses
+    return dataclasses.replace(cfg.isaacgym, point_scene=world_point_scene(cfg))
 
 
 def _hydra_standin():

@@ -13,6 +13,7 @@
 
 #include "m3_internal.hpp"
 #include "panda_episode_lane.hpp"
+#include "point_scene_rows.hpp"
 
 using namespace m3;
 
@@ -367,6 +368,9 @@ extern "C" void m3_destroy(m3_handle* h) {
     if (h->xb) (void)hipFree(h->xb);
     if (h->panda_busy_hint) (void)hipHostFree(h->panda_busy_hint);
     if (h->rollout_err) (void)hipHostFree(h->rollout_err);
+    if (h->scene_rows_dev) (void)hipFree(h->scene_rows_dev);
+    if (h->scene_rows_host) (void)hipHostFree(h->scene_rows_host);
+    std::free(h->scene_rows);
     if (h->panda_busy_count) (void)hipFree(h->panda_busy_count);
     if (h->panda_reach_rec) (void)hipFree(h->panda_reach_rec);
     for (auto& ev : h->ev)
@@ -822,22 +826,88 @@ extern "C" void m3_default_point_scene(m3_point_scene* sc) {
     if (sc) std::memcpy(sc, &POINT_SCENE_DEFAULT, sizeof(*sc));
 }
 
-extern "C" int m3_set_point_scene(m3_handle* h, const m3_point_scene* sc) {
-    if (!h) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_point_scene: point_env only");
-    const m3_point_scene& src = sc ? *sc : POINT_SCENE_DEFAULT;
+// the per-field checks of an arena, shared by m3_set_point_scene and every row of m3_set_point_scene_rows: empty if it passes,
+// else "<field> <what is wrong>"
+static std::string point_scene_fault(const m3_point_scene& src) {
     const float* f = reinterpret_cast<const float*>(&src);
     for (int i = 0; i < 28; ++i) {
         const char* what = !std::isfinite(f[i]) ? " is not finite"
                            : (SCENE_FIELD_RULE[i] == 1 && !(f[i] > 0.0f)) ? " must be > 0"
                            : (SCENE_FIELD_RULE[i] == 2 && f[i] < 0.0f) ? " must be >= 0" : nullptr;
-        if (what) return fail(h, M3_ERR_BAD_ARG, (std::string("m3_set_point_scene: ") + SCENE_FIELD_NAMES[i] + what).c_str());
+        if (what) return std::string(SCENE_FIELD_NAMES[i]) + what;
     }
-    if (!(src.wall > src.robot_r)) return fail(h, M3_ERR_BAD_ARG, "m3_set_point_scene: wall must be > robot_r");
+    if (!(src.wall > src.robot_r)) return "wall must be > robot_r";
+    return std::string();
+}
+
+extern "C" int m3_set_point_scene(m3_handle* h, const m3_point_scene* sc) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_point_scene: point_env only");
+    const m3_point_scene& src = sc ? *sc : POINT_SCENE_DEFAULT;
+    const std::string fault = point_scene_fault(src);
+    if (!fault.empty()) return fail(h, M3_ERR_BAD_ARG, ("m3_set_point_scene: " + fault).c_str());
     std::memcpy(&h->point_scene, &src, sizeof(src));
     h->scene_rt = make_point_scene_rt(h->point_scene, h->cfg.dt, h->cfg.substeps, h->cfg.solver_iters);
+    h->scene_rows_on = false;   // the last call wins: the handle is on its single scene (the rows' memory is kept for a later call)
     return M3_OK;
 }
+
+// One arena per environment of a sim_only handle.  Every check before any state changes.
+extern "C" int m3_set_point_scene_rows(m3_handle* h, const m3_point_scene* scenes, int n) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_point_scene_rows: point_env only");
+    if (!h->cfg.sim_only)
+        return fail(h, M3_ERR_STATE, "m3_set_point_scene_rows: sim_only handles only (a planner's rollouts share one model: m3_set_point_scene)");
+    if (!scenes) {   // back on the single scene: exactly the kernels of a handle that never had rows (n is not read)
+        h->scene_rows_on = false;
+        return M3_OK;
+    }
+    const int Kl = h->cfg.K_local;
+    if (n != Kl)
+        return fail(h, M3_ERR_SHAPE, ("m3_set_point_scene_rows: n is " + std::to_string(n) + ", the handle's K_local " + std::to_string(Kl)).c_str());
+    for (int i = 0; i < n; ++i) {
+        const std::string fault = point_scene_fault(scenes[i]);
+        if (!fault.empty()) return fail(h, M3_ERR_BAD_ARG, ("m3_set_point_scene_rows: row " + std::to_string(i) + ": " + fault).c_str());
+    }
+    const size_t table_bytes = (size_t)POINT_SCENE_ROW_WORDS * Kl * sizeof(float);
+    // THE allocation of this feature: the first call on a handle; later calls reuse the three blocks (K_local is fixed at
+    // m3_create).  m3_sim_step*, m3_episodes_tick / _begin / _end allocate nothing because of the rows -- they read
+    // scene_rows_dev and scene_rt, nothing else.
+    if (!h->scene_rows_dev) {
+        m3_point_scene* rows = static_cast<m3_point_scene*>(std::malloc((size_t)Kl * sizeof(m3_point_scene)));
+        float* host = nullptr;
+        float* dev = nullptr;
+        hipError_t e = rows ? hipSuccess : hipErrorOutOfMemory;
+        if (e == hipSuccess) e = hipHostMalloc((void**)&host, table_bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc((void**)&dev, table_bytes);
+        if (e != hipSuccess) {
+            if (host) (void)hipHostFree(host);
+            std::free(rows);
+            return fail(h, M3_ERR_HIP, (std::string("m3_set_point_scene_rows: ") + hipGetErrorString(e)).c_str());
+        }
+        h->scene_rows = rows; h->scene_rows_host = host; h->scene_rows_dev = dev;
+    } else {
+        // the pinned mirror is the source of the previous call's asynchronous upload: that copy is over before it is rewritten
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    std::memcpy(h->scene_rows, scenes, (size_t)Kl * sizeof(m3_point_scene));
+    for (int i = 0; i < Kl; ++i)
+        point_scene_row_pack(make_point_scene_rt(scenes[i], h->cfg.dt, h->cfg.substeps, h->cfg.solver_iters), h->scene_rows_host, Kl, i);
+    HIPCHK(h, hipMemcpyAsync(h->scene_rows_dev, h->scene_rows_host, table_bytes, hipMemcpyHostToDevice, h->stream));
+    h->scene_rows_on = true;
+    return M3_OK;
+}
+
+extern "C" int m3_get_point_scene_row(const m3_handle* h, int row, m3_point_scene* out) {
+    if (!h || !out) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_POINT) return M3_ERR_UNSUPPORTED;
+    if (!h->scene_rows_on) return M3_ERR_STATE;
+    if (row < 0 || row >= h->cfg.K_local) return M3_ERR_BAD_ARG;
+    std::memcpy(out, &h->scene_rows[row], sizeof(*out));
+    return M3_OK;
+}
+
+extern "C" int m3_point_scene_rows_set(const m3_handle* h) { return h ? (h->scene_rows_on ? 1 : 0) : M3_ERR_BAD_ARG; }
 
 extern "C" int m3_get_point_scene(const m3_handle* h, m3_point_scene* out) {
     if (!h || !out) return M3_ERR_BAD_ARG;
@@ -864,6 +934,8 @@ static bool runtime_scene(const m3_handle* h) {
     return h->scene_instance < 0 ? !default_point_scene(h) : h->scene_instance != 0;
 }
 static const char* scene_refusal(const m3_handle* h) {
+    if (h->cfg.env_type == M3_ENV_POINT && h->scene_instance == 0 && h->scene_rows_on)
+        return "the run-time-scene instance is forced off (m3_set_point_scene_instance 0) but the handle has an arena per environment (m3_set_point_scene_rows)";
     if (h->cfg.env_type == M3_ENV_POINT && h->scene_instance == 0 && !default_point_scene(h))
         return "the run-time-scene instance is forced off (m3_set_point_scene_instance 0) but the handle's scene is not the default";
     return nullptr;
@@ -2135,7 +2207,9 @@ static int sim_step_impl(m3_handle* h, const float* u) {
     if (!h->views_bound) return fail(h, M3_ERR_STATE, "m3_sim_step: views not bound");
     if (h->cfg.env_type == M3_ENV_POINT) {
         if (const char* why = scene_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_sim_step: ") + why).c_str());
-        if (runtime_scene(h)) launch_sim_step_s(h->scene_rt, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
+        if (h->scene_rows_on)
+            launch_sim_step_sv(h->scene_rt, h->scene_rows_dev, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
+        else if (runtime_scene(h)) launch_sim_step_s(h->scene_rt, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
         else launch_sim_step(h->scene, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
     } else {
         launch_psim_step(h->pscene, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
@@ -2339,7 +2413,8 @@ static int eps_ready(m3_episodes* eps, const char* who) {
 
 // the step of the world's rows with the WORLD handle's scene (the planners plan with their own)
 static void episodes_post(const m3_handle* w, const m3::EpisodeArgs& a, int tick) {
-    if (runtime_scene(w)) m3::launch_episodes_post_s(w->scene_rt, a, tick, w->stream);
+    if (w->scene_rows_on) m3::launch_episodes_post_sv(w->scene_rt, w->scene_rows_dev, a, tick, w->stream);   // a scene per episode
+    else if (runtime_scene(w)) m3::launch_episodes_post_s(w->scene_rt, a, tick, w->stream);
     else m3::launch_episodes_post(w->scene, a, tick, w->stream);
 }
 

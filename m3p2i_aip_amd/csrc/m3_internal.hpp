@@ -321,6 +321,9 @@ void launch_sim_step(const PointScene& sc, const SimViews& v, float* world, cons
                      int Kl, hipStream_t s);   // step + refresh of the views
 void launch_sim_step_s(const PointSceneRT& sc, const SimViews& v, float* world, const float* u, float* u_keep, int Kl,
                        hipStream_t s);   // ... of a handle with a run-time scene
+// ... of a sim_only handle with an arena per environment (m3_set_point_scene_rows; point_scene_rows.hpp: uni, rows)
+void launch_sim_step_sv(const PointSceneRT& uni, const float* rows, const SimViews& v, float* world, const float* u,
+                        float* u_keep, int Kl, hipStream_t s);
 void launch_sim_forces(const SimViews& v, float* world, const float* f /*[Kl][nB][3]*/, int Kl,
                        hipStream_t s);
 void launch_sim_cost(const CostParams& cp, float* world, int Kl, int k0, float* cost,
@@ -349,6 +352,7 @@ struct EpisodeArgs {
 void launch_episodes_pre(const EpisodeArgs& a, int tick, hipStream_t s);
 void launch_episodes_post(const PointScene& sc, const EpisodeArgs& a, int tick, hipStream_t s);
 void launch_episodes_post_s(const PointSceneRT& sc, const EpisodeArgs& a, int tick, hipStream_t s);
+void launch_episodes_post_sv(const PointSceneRT& uni, const float* rows, const EpisodeArgs& a, int tick, hipStream_t s);
 
 constexpr int NW = 28;  // floats per env in the step-mode SoA world (PointWorld fields)
 constexpr int NWP = 77; // same for the panda_env (PandaWorld fields, rollout_panda.hip)
@@ -430,6 +434,12 @@ struct m3_handle {
     m3_point_scene point_scene = m3::POINT_SCENE_DEFAULT;   // m3_set_point_scene (extension, point_env); survives m3_reset
     m3::PointSceneRT scene_rt = {};    // ... with the handle's dt / substeps / iterations (make_point_scene_rt; m3_create, m3_set_point_scene)
     int scene_instance = -1;           // m3_set_point_scene_instance: -1 by the values (not the defaults bit for bit), 0 / 1 forced
+    // m3_set_point_scene_rows (extension, sim_only point_env): one arena per environment; survive m3_reset.  All three are
+    // allocated by the first m3_set_point_scene_rows on the handle and freed by m3_destroy; nothing else allocates them.
+    bool scene_rows_on = false;        // the step and the episode tick take the per-row kernels
+    m3_point_scene* scene_rows = nullptr;   // host [Kl]: what was set (m3_get_point_scene_row)
+    float* scene_rows_host = nullptr;  // pinned host [POINT_SCENE_ROW_WORDS][Kl]: the table as uploaded (point_scene_rows.hpp)
+    float* scene_rows_dev = nullptr;   // device, the same
     // world
     float world0[18];
     const float* world0_bound = nullptr;  // device, 18 floats (filled by world_from_sim)

@@ -272,6 +272,32 @@ class HipEngine:
         self._ck(self.lib.m3_get_point_scene(self._h, C.byref(sc)))
         return {n: getattr(sc, n) for n in L.POINT_SCENE_DEFAULTS}
 
+    def set_point_scene_rows(self, rows=None):
+        """Extension, sim_only point_env engines: one arena per environment -- rows[i] the field overrides of environment i
+        over _lib.POINT_SCENE_DEFAULTS (None: the reference's arena); len(rows) == K_local.  rows=None clears: the engine is
+        back on its single scene.  Applies from the next step / episode tick; set_point_scene afterwards clears the rows."""
+        if rows is None:
+            self._ck(self.lib.m3_set_point_scene_rows(self._h, None, 0))
+            return
+        rows = list(rows)
+        arr = (L.PointSceneFields * max(len(rows), 1))()
+        for i, fields in enumerate(rows):
+            fields = dict(fields or {})
+            unknown = sorted(set(fields) - set(L.POINT_SCENE_DEFAULTS))
+            if unknown:
+                raise ValueError(f"row {i}: unknown point scene field(s) {unknown}: one of {list(L.POINT_SCENE_DEFAULTS)}")
+            arr[i] = L.PointSceneFields(**{**L.POINT_SCENE_DEFAULTS, **{k: float(v) for k, v in fields.items()}})
+        self._ck(self.lib.m3_set_point_scene_rows(self._h, arr, len(rows)))
+
+    def point_scene_row(self, i):
+        """environment i's arena as set by set_point_scene_rows (all fields)"""
+        sc = L.PointSceneFields()
+        self._ck(self.lib.m3_get_point_scene_row(self._h, int(i), C.byref(sc)))
+        return {n: getattr(sc, n) for n in L.POINT_SCENE_DEFAULTS}
+
+    def point_scene_rows_set(self):
+        return self.lib.m3_point_scene_rows_set(self._h) == 1
+
     def set_point_scene_instance(self, on=-1):
         """-1: the run-time-scene kernels exactly when the scene is not the default (default); 1 / 0 forced (tests, A/B)."""
         self._ck(self.lib.m3_set_point_scene_instance(self._h, int(on)))

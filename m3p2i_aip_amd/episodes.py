@@ -8,7 +8,8 @@ One N-env "real world" (an IsaacGymWrapper(num_envs=N)) holds the episodes' 1-en
 its own planner, Objective and task planner, built as tools/closed_loop.Tamp builds them.  Every tick is one library call
 for all episodes (m3_episodes_tick: pre-command kernel, one batched command of the running planners, post-command kernel,
 one synchronisation).  Each episode's report equals what closed_loop.run(cn, overrides, ticks=max_ticks, jitter=jitter)
-returns, bit for bit: ticks, success, final error, collision ticks, trace rows.
+returns, bit for bit: ticks, success, final error, collision ticks, trace rows.  Episodes may differ in their arena
+(`point_scene`, `world_point_scene` overrides): each planner plans in its own, each row of the world is stepped in its own.
 """
 from __future__ import annotations
 
@@ -112,8 +113,12 @@ class PointEpisodeSet:
         cfgs = [cfg for _, _, cfg, _ in self.items]
         self.sides = [_PlannerSide(cfg) for cfg in cfgs]
         c0, n = cfgs[0], len(self.items)
-        self.real = real = wrapper.IsaacGymWrapper(c0.isaacgym, c0.env_type, num_envs=n, viewer=False, device=c0.mppi.device,
-                                                   cube_on_shelf=c0.cube_on_shelf)
+        # each episode's world arena: its `point_scene` with its `world_point_scene` on top.  All the same: the single-arena
+        # world as before; otherwise one arena per row (m3_set_point_scene_rows) -- the planners keep their own `point_scene`
+        arenas = [compat.world_point_scene(cfg) for cfg in cfgs]
+        rows = None if all(a == arenas[0] for a in arenas) else arenas
+        self.real = real = wrapper.IsaacGymWrapper(compat.world_isaacgym_config(c0), c0.env_type, num_envs=n, viewer=False,
+                                                   device=c0.mppi.device, cube_on_shelf=c0.cube_on_shelf, point_scenes=rows)
         phases = [_apply_jitter(real, e, jitter) if jitter else 0 for e, (*_, jitter) in enumerate(self.items)]
         if any(jitter for *_, jitter in self.items):
             real.set_dof_state_tensor(real._dof_state)

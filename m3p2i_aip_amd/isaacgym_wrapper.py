@@ -52,7 +52,7 @@ class IsaacGymConfig:
 class IsaacGymWrapper:
     def __init__(self, cfg: IsaacGymConfig, env_type: str = "point_env", num_envs: int = 1,
                  viewer: bool = False, device: str = "cuda:0", cube_on_shelf: bool = False,
-                 k_offset: int = 0, num_envs_global: int | None = None, actors=None):
+                 k_offset: int = 0, num_envs_global: int | None = None, actors=None, point_scenes=None):
         if viewer or getattr(cfg, "viewer", False):
             # scripts/sim.py:19-27 asks for the viewer of its 1-env world; this build has none: the world
             # runs headless (visualize_trajs / play_with_cube are no-ops), keyboard_control raises
@@ -93,6 +93,25 @@ class IsaacGymWrapper:
                     pos = list(a.init_pos)
                     pos[ax] = sign * (sc["wall"] + 0.5 * a.size[0])
                     a.init_pos = pos
+        # EXTENSION, point_env: one arena PER ENVIRONMENT (the N independent "real worlds" of num_envs = N) -- point_scenes[i] the
+        # field overrides of environment i over _lib.POINT_SCENE_DEFAULTS, None the reference's arena.  self.point_scenes: the
+        # rows (all fields); self.point_scene stays the single arena above, which is what a planner attached to this wrapper
+        # follows, and which the engine is back on after set_point_scene_rows(None).
+        self.point_scenes = None
+        if point_scenes is not None:
+            if env_type != "point_env":
+                raise ValueError("point_scenes: point_env only")
+            point_scenes = list(point_scenes)
+            if len(point_scenes) != int(num_envs):
+                raise ValueError(f"point_scenes: {len(point_scenes)} entries for num_envs = {int(num_envs)}")
+            rows = []
+            for i, given in enumerate(point_scenes):
+                given = dict(given or {})
+                unknown = sorted(set(given) - set(L.POINT_SCENE_DEFAULTS))
+                if unknown:
+                    raise ValueError(f"point_scenes[{i}]: unknown field(s) {unknown}: one of {list(L.POINT_SCENE_DEFAULTS)}")
+                rows.append({**L.POINT_SCENE_DEFAULTS, **{k: float(v) for k, v in given.items()}})
+            self.point_scenes = rows
         for i, a in enumerate(self.env_cfg):
             a.handle = i
         self.device = device
@@ -119,6 +138,8 @@ class IsaacGymWrapper:
             device=dev.index or 0, sim_only=True, filter_u=False, cube_on_shelf=cube_on_shelf))
         if self.point_scene is not None:
             self._engine.set_point_scene(self.point_scene)
+        if self.point_scenes is not None:
+            self._engine.set_point_scene_rows(self.point_scenes)
 
         # initial scene (start_sim / set_initial_joint_pose / acquire_states: :68-118,222-240)
         root = torch.zeros(nA, 13)
@@ -130,14 +151,21 @@ class IsaacGymWrapper:
                 pos[2] = a.size[2] / 2  # rests on the ground plane
             root[i, 0:3] = torch.tensor(pos)
             root[i, 3:7] = torch.tensor(a.init_ori)
-        self._root_state = root.unsqueeze(0).repeat(K, 1, 1).to(dev).contiguous()
-        rb = torch.zeros(self.bodies_per_env, 13)
-        b = 0
-        for i, a in enumerate(self.env_cfg):
-            for _ in a.links:
-                rb[b] = root[i]
-                b += 1
-        self._rigid_body_state = rb.unsqueeze(0).repeat(K, 1, 1).to(dev).contiguous()
+        root = root.unsqueeze(0).repeat(K, 1, 1)
+        if self.point_scenes is not None:
+            # row i shows arena i wherever the single-arena path above writes the arena into every row: the obstacle's pose, the
+            # walls' (an arena moves neither the box nor the dyn-obs; the views hold no sizes)
+            for i, a in enumerate(self.env_cfg):
+                for e, sc in enumerate(self.point_scenes):
+                    if a.name == "obs":
+                        root[e, i, 0:2] = torch.tensor([sc["obs_x"], sc["obs_y"]])
+                    elif a.name.startswith("wall-"):
+                        ax = 0 if a.name in ("wall-1", "wall-2") else 1
+                        sign = 1.0 if a.name in ("wall-1", "wall-3") else -1.0
+                        root[e, i, ax] = sign * (sc["wall"] + 0.5 * a.size[0])
+        self._root_state = root.to(dev).contiguous()
+        body_actor = [i for i, a in enumerate(self.env_cfg) for _ in a.links]   # (a link starts at its actor's root pose)
+        self._rigid_body_state = root[:, body_actor, :].to(dev).contiguous()
         dof = torch.zeros(2 * self.dofs_per_robot)
         robot = [a for a in self.env_cfg if a.type == "robot"][0]
         if robot.init_joint_pose:

@@ -2,11 +2,16 @@
 (deterministic seeds): statistics of what the reference logged per run (plot/plot_point.py:26-34) -- final
 block-to-goal error, task time, dyn-obs collisions -- next to the logged statistics (tests/golden/behaviour_band.json).
 
-    python tools/band_stats.py [--n 20] [--json out.json] [--size baseline|default] [--avoid] [--batched] [scenario ...]
+    python tools/band_stats.py [--n 20] [--json out.json] [--size baseline|default] [--avoid] [--batched]
+                               [--world-arena-spread S] [scenario ...]
 
 --batched: all episodes of all named scenarios in lockstep, one library call per tick (m3p2i_aip_amd/episodes.py,
 DESIGN.md §7c): the same per-episode results as the serial runs, bit for bit.  The `panda` rows likewise, the n episodes
 of each row in lockstep (two library calls per tick with the host's task planners in between, §7d).
+
+--world-arena-spread S (with --batched): a randomised band -- each episode's REAL world gets its own box mass, box ground
+friction and robot-box friction, the nominal value times a factor drawn from [1 - S, 1 + S] (world_arena_of; the config key
+`world_point_scene`); the planners keep the nominal arena.  0 (default): the runs as without the option, byte for byte.
 
 --size default: the reference's shipped planner size, K=200 samples, T=15 (config/mppi/point.yaml) -- the size the
 logged runs were most plausibly made with (it is not recorded); baseline (default here): K, T of the BASELINE configs.
@@ -69,6 +74,35 @@ def jitter_of(scenario, episode):
     return j
 
 
+def world_arena_of(scenario, episode, spread):
+    """--world-arena-spread: the `world_point_scene` overrides of an episode, or None (spread 0, and episode 0: the nominal
+    world).  Factors in [1 - spread, 1 + spread] for box_m, box_mu_g and mu_rb from the episode's jitter seed (its own stream:
+    the jitter's draws are what they were); box_I scales with box_m."""
+    if not spread or episode == 0:
+        return None
+    if not 0.0 < spread < 1.0:
+        raise ValueError("--world-arena-spread: a share in [0, 1)")
+    from m3p2i_aip_amd._lib import POINT_SCENE_DEFAULTS as D
+    order = sorted(k for k in SCENARIOS if not k.startswith("corner2")) + sorted(k for k in SCENARIOS if k.startswith("corner2"))
+    rng = np.random.default_rng([order.index(scenario), episode, 1])
+    fm, fg, fr = (float(f) for f in rng.uniform(1.0 - spread, 1.0 + spread, 3))
+    return dict(box_m=D["box_m"] * fm, box_I=D["box_I"] * fm, box_mu_g=D["box_mu_g"] * fg, mu_rb=D["mu_rb"] * fr)
+
+
+def batched_episode_list(pairs, n=20, world_arena_spread=0.0):
+    """What band_batched runs: [(scenario, size, episode, jitter)] and the [(config name, overrides, jitter)] of
+    run_point_episodes, in the same order."""
+    items = [(sc, size, e, jitter_of(sc, e)) for sc, size in pairs for e in range(n)]
+    eps = []
+    for sc, size, e, j in items:
+        ov = overrides(sc, size)
+        arena = world_arena_of(sc, e, world_arena_spread)
+        if arena:
+            ov.append("world_point_scene={" + ", ".join(f"{k}: {v!r}" for k, v in arena.items()) + "}")
+        eps.append(("config_point", ov, j))
+    return items, eps
+
+
 def fisher_one_sided(a, b, c, d, alternative="less"):
     """One-sided Fisher exact test of the 2x2 table [[a, b], [c, d]] (rows: this build, the logged runs; columns: event,
     no event): the probability, with all margins fixed, of a top-left count <= a ("less") or >= a ("greater")."""
@@ -124,14 +158,13 @@ def _summary(scenario, n, size, runs):
                 command_ms_p50=stats([r["command_ms_p50"] for r in runs]), runs=runs)
 
 
-def band_batched(pairs, n=20, max_sim_time_s=40.0):
+def band_batched(pairs, n=20, max_sim_time_s=40.0, world_arena_spread=0.0):
     """episodes() of every (scenario, size) in `pairs` at once: all n * len(pairs) episodes in lockstep
     (m3p2i_aip_amd.episodes.run_point_episodes).  Returns {(scenario, size): the dict episodes() returns}; each run's
     command_ms_p50 is the set's tick time."""
     from m3p2i_aip_amd.episodes import run_point_episodes
-    items = [(sc, size, e, jitter_of(sc, e)) for sc, size in pairs for e in range(n)]
-    reps = run_point_episodes([("config_point", overrides(sc, size), j) for sc, size, _, j in items],
-                              max_ticks=int(max_sim_time_s / 0.05))
+    items, eps = batched_episode_list(pairs, n, world_arena_spread)
+    reps = run_point_episodes(eps, max_ticks=int(max_sim_time_s / 0.05))
     out = {}
     for (sc, size, e, j), r in zip(items, reps):
         out.setdefault((sc, size), []).append(dict(episode=e, jitter=j, success=r["success"], final_pos_error_m=r["final_pos_error"],
@@ -182,7 +215,7 @@ def panda_episodes_batched(n=20, overrides=("mppi.num_samples=4000", "mppi.horiz
 
 
 def main(argv):
-    n, out, names, size, batched = 20, None, [], "baseline", False
+    n, out, names, size, batched, spread = 20, None, [], "baseline", False, 0.0
     it = iter(argv)
     for a in it:
         if a == "--batched":
@@ -193,11 +226,15 @@ def main(argv):
             out = next(it)
         elif a == "--size":
             size = next(it)
+        elif a == "--world-arena-spread":
+            spread = float(next(it))
         elif a == "--avoid":
             global AVOID
             AVOID = True
         else:
             names.append(a)
+    if spread and not batched:
+        raise SystemExit("--world-arena-spread: with --batched (the serial runs keep the nominal world)")
     allband = json.load(open(os.path.join(ROOT, "tests", "golden", "behaviour_band.json")))
     band = allband["point"]
     res = {}
@@ -218,7 +255,7 @@ def main(argv):
             if out:
                 json.dump(res, open(out, "w"), indent=1)
             return
-    pre = band_batched([(sc, size) for sc in names or list(SCENARIOS)], n) if batched else {}
+    pre = band_batched([(sc, size) for sc in names or list(SCENARIOS)], n, world_arena_spread=spread) if batched else {}
     for sc in names or list(SCENARIOS):
         r = pre[(sc, size)] if batched else episodes(sc, n, size=size)
         r["logged"] = {k: band[sc][k] for k in ("final_pos_error_m", "task_time_s", "dyn_obs_collisions")}

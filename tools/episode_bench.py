@@ -2,6 +2,13 @@
 of the 8-scenario band (tools/band_stats.py) per size, batched against serial, planner construction shown separately.
 
     python tools/episode_bench.py [--json out.json] [--n 60] [--serial-n 4] [--ticks 100]
+    python tools/episode_bench.py --arena-rows [--json out.json] [--rows 64] [--repeats 5] [--ticks 8]
+
+--arena-rows: what an arena per world row costs (m3_set_point_scene_rows, k_episodes_post_sv).  Three sets of --rows case2 push
+episodes at BASELINE size whose planners all plan in the reference's arena (the batched command is the same work in all three):
+`single` -- one custom arena on the world handle (m3_set_point_scene: k_episodes_post_s, the kernel of the parent commit),
+`rows_same` -- the same arena as --rows identical rows, `rows_distinct` -- --rows different arenas.  The variants alternate
+inside each of --repeats repeats of --ticks ticks; p50 ms per m3_episodes_tick of each and the ratios to `single`.
 
 The serial band time is measured on --serial-n episodes per scenario and scaled to --n (the serial loop's cost is linear
 in the number of episodes); construction of the serial runs is timed by building their planners alone.
@@ -38,6 +45,51 @@ def tick_times(n, ticks):
         es.close()
 
 
+def arena_rows_times(n=64, repeats=5, ticks=8):
+    import band_stats as bs
+    from m3p2i_aip_amd._lib import POINT_SCENE_DEFAULTS as D
+    from m3p2i_aip_amd.episodes import build_set
+    sc = "case2_halton_push_coll"
+
+    def arena(f):      # the box heavier / lighter by the factor f, its frictions moved with it
+        return dict(box_m=D["box_m"] * f, box_I=D["box_I"] * f, box_mu_g=D["box_mu_g"] * (2.0 - f), mu_rb=D["mu_rb"] * f)
+
+    def world(a):
+        return "world_point_scene={" + ", ".join(f"{k}: {v!r}" for k, v in a.items()) + "}"
+
+    one = arena(1.125)
+    distinct = [arena(0.8 + 0.4 * e / max(n - 1, 1)) for e in range(n)]
+    plans = dict(single=[one] * n, rows_same=[one] * n, rows_distinct=distinct)
+    sets = {}
+    try:
+        for name, arenas in plans.items():
+            eps = [("config_point", bs.overrides(sc, "baseline") + [world(arenas[e])], bs.jitter_of(sc, e % 60)) for e in range(n)]
+            es = sets[name] = build_set(eps, max_ticks=repeats * ticks + 4)
+            if name == "rows_same":      # (episodes that agree build the single-arena world: give it the rows by hand)
+                es.real._engine.set_point_scene_rows(arenas)
+            assert es.real._engine.point_scene_rows_set() == (name != "single")
+            es.start()
+            for _ in range(3):           # warm-up ticks, not counted
+                es.tick()
+            es.lat.clear()
+        for _ in range(repeats):         # the variants interleaved inside every repeat
+            for es in sets.values():
+                for _ in range(ticks):
+                    if es.running:
+                        es.tick()
+        out = dict(n=n, K=2000, T=30, repeats=repeats, ticks_per_repeat=ticks, tick_ms_p50={}, tick_ms_min={}, ticks={})
+        for name, es in sets.items():
+            lat = np.array(es.lat) * 1e3
+            out["tick_ms_p50"][name] = float(np.percentile(lat, 50))
+            out["tick_ms_min"][name] = float(lat.min())
+            out["ticks"][name] = len(lat)
+        out["ratio_to_single"] = {k: v / out["tick_ms_p50"]["single"] for k, v in out["tick_ms_p50"].items()}
+        return out
+    finally:
+        for es in sets.values():
+            es.close()
+
+
 def serial_band(size, n):
     import band_stats as bs
     import closed_loop
@@ -71,6 +123,14 @@ def batched_band(size, n):
 
 def main(argv):
     out, n, serial_n, ticks = None, 60, 4, 100
+    if "--arena-rows" in argv:
+        opt = dict(zip(argv, argv[1:]))
+        res = dict(arena_rows=arena_rows_times(int(opt.get("--rows", 64)), int(opt.get("--repeats", 5)), int(opt.get("--ticks", 8))))
+        print(json.dumps(res), flush=True)
+        if opt.get("--json"):
+            os.makedirs(os.path.dirname(opt["--json"]) or ".", exist_ok=True)
+            json.dump(res, open(opt["--json"], "w"), indent=1)
+        return
     it = iter(argv)
     for a in it:
         if a == "--json":
