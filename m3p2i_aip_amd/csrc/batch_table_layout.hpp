@@ -1,0 +1,62 @@
+// batch_table_layout.hpp -- where the sections of m3_batch_command's argument table lie (host only; no HIP dependency, so that
+// tests/native/batch_table_layout_host.cpp can run it on its own).
+//
+// A point_env table: one section of rollout entries per variant (PointVariant: plain, weighted, scene -- each variant has an
+// entry type of its own), in that order, then the handles' UpdateArgs.  A panda_env table: its single section of rollout
+// entries, then the UpdateArgs.  Every section starts on a multiple of 16 bytes; a section without handles takes no room.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+
+namespace m3 {
+
+constexpr int BATCH_ROLLOUT_SECTIONS = 3;   // (POINT_VARIANTS, m3_internal.hpp)
+struct BatchTableSizes {
+    size_t entry[BATCH_ROLLOUT_SECTIONS];   // bytes of one rollout entry of each point_env variant
+    size_t panda_entry, update;             // ... of a panda_env rollout entry, of one UpdateArgs
+};
+struct BatchTableLayout {
+    size_t off[BATCH_ROLLOUT_SECTIONS];   // start of each rollout section
+    size_t upd_off;                       // start of the update section
+    size_t total;                         // bytes of the table (what is copied to the device)
+};
+constexpr size_t align16(size_t n) { return (n + 15) / 16 * 16; }
+
+// n[v]: handles of variant v in this call
+inline BatchTableLayout batch_table_layout(const BatchTableSizes& z, const int n[BATCH_ROLLOUT_SECTIONS]) {
+    BatchTableLayout l{};
+    size_t end = 0, handles = 0;
+    for (int v = 0; v < BATCH_ROLLOUT_SECTIONS; ++v) {
+        l.off[v] = align16(end);
+        end = l.off[v] + (size_t)n[v] * z.entry[v];
+        handles += (size_t)n[v];
+    }
+    l.upd_off = align16(end);
+    l.total = l.upd_off + handles * z.update;
+    return l;
+}
+inline BatchTableLayout batch_table_layout_panda(const BatchTableSizes& z, int n) {
+    BatchTableLayout l{};
+    l.upd_off = align16((size_t)n * z.panda_entry);
+    l.total = l.upd_off + (size_t)n * z.update;
+    return l;
+}
+
+// The largest total of any call with up to max_handles handles: what m3_batch_create gives a slot.  A handle more never makes
+// a table smaller, so only the splits of exactly max_handles count.  Moving 16 handles from a section into the one with the
+// largest entries keeps every alignment gap (16 entries are a multiple of 16 bytes) and does not shrink the table: the worst
+// split has fewer than 16 handles in each of the other sections.
+inline size_t batch_table_capacity(const BatchTableSizes& z, int max_handles) {
+    const int big = (int)(std::max_element(z.entry, z.entry + BATCH_ROLLOUT_SECTIONS) - z.entry);
+    const int o1 = (big + 1) % BATCH_ROLLOUT_SECTIONS, o2 = (big + 2) % BATCH_ROLLOUT_SECTIONS;
+    size_t worst = batch_table_layout_panda(z, max_handles).total;
+    for (int a = 0; a < 16 && a <= max_handles; ++a)
+        for (int b = 0; b < 16 && a + b <= max_handles; ++b) {
+            int n[BATCH_ROLLOUT_SECTIONS];
+            n[o1] = a; n[o2] = b; n[big] = max_handles - a - b;
+            worst = std::max(worst, batch_table_layout(z, n).total);
+        }
+    return worst;
+}
+
+}  // namespace m3

@@ -12,6 +12,7 @@
 #include <new>
 
 #include "m3_internal.hpp"
+#include "batch_table_layout.hpp"
 #include "panda_episode_lane.hpp"
 #include "point_scene_rows.hpp"
 
@@ -802,16 +803,6 @@ extern "C" int m3_set_weighted_cost_instance(m3_handle* h, int on) {
 static bool default_cost_weights(const m3_handle* h) {
     return std::memcmp(&h->cost_weights, &POINT_COST_WEIGHTS_DEFAULT, sizeof(PointCostWeights)) == 0;
 }
-// the one owner of "does this handle's cost code take the weights" (rollout instance, batch group, step-mode cost)
-static bool weighted_cost(const m3_handle* h) {
-    if (h->cfg.env_type != M3_ENV_POINT) return false;
-    return h->weighted_instance < 0 ? !default_cost_weights(h) : h->weighted_instance != 0;
-}
-static const char* weighted_refusal(const m3_handle* h) {
-    if (h->cfg.env_type == M3_ENV_POINT && h->weighted_instance == 0 && !default_cost_weights(h))
-        return "the weighted cost instance is forced off (m3_set_weighted_cost_instance 0) but the handle's cost weights are not the defaults";
-    return nullptr;
-}
 
 // ---- the point_env arena (extension; per-handle state like the cost weights: no allocation, no synchronisation) ----
 static const char* const SCENE_FIELD_NAMES[28] = {
@@ -928,15 +919,33 @@ extern "C" int m3_set_point_scene_instance(m3_handle* h, int on) {
 static bool default_point_scene(const m3_handle* h) {
     return std::memcmp(&h->point_scene, &POINT_SCENE_DEFAULT, sizeof(m3_point_scene)) == 0;
 }
-// the one owner of "does this handle run the run-time-scene kernels" (rollout instance, batch group, step, episode tick)
-static bool runtime_scene(const m3_handle* h) {
-    if (h->cfg.env_type != M3_ENV_POINT) return false;
-    return h->scene_instance < 0 ? !default_point_scene(h) : h->scene_instance != 0;
+
+// ---- which point_env kernels a handle runs: decided here and nowhere else ----
+// what a caller is about to launch: the step-mode cost reads the weights only, the step and the episode tick the arena only,
+// a rollout both
+enum PointSide { SIDE_COST = 1, SIDE_STEP = 2, SIDE_ROLLOUT = SIDE_COST | SIDE_STEP };
+// the variant of the rollout kernels (SIDE_ROLLOUT: m3_rollout, m3_batch_command) or of the step-mode cost (SIDE_COST: the
+// arena is no input of the cost, so never POINT_SCENE)
+static PointVariant point_variant(const m3_handle* h, PointSide side) {
+    if (h->cfg.env_type != M3_ENV_POINT) return POINT_PLAIN;
+    if ((side & SIDE_STEP) && (h->scene_instance < 0 ? !default_point_scene(h) : h->scene_instance != 0)) return POINT_SCENE;
+    return (h->weighted_instance < 0 ? !default_cost_weights(h) : h->weighted_instance != 0) ? POINT_WEIGHTED : POINT_PLAIN;
 }
-static const char* scene_refusal(const m3_handle* h) {
-    if (h->cfg.env_type == M3_ENV_POINT && h->scene_instance == 0 && h->scene_rows_on)
+// the variant of the step-mode kernels (m3_sim_step, the episode tick): the arena compiled in, the handle's arena a kernel
+// argument (m3_set_point_scene), or one arena per environment (m3_set_point_scene_rows)
+enum PointStepVariant { STEP_COMPILED, STEP_RUNTIME, STEP_ROWS };
+static PointStepVariant point_step_variant(const m3_handle* h) {
+    if (h->scene_rows_on) return STEP_ROWS;
+    return point_variant(h, SIDE_STEP) == POINT_SCENE ? STEP_RUNTIME : STEP_COMPILED;
+}
+// why the handle cannot run that side's kernels (M3_ERR_STATE; nullptr: it can)
+static const char* point_variant_refusal(const m3_handle* h, PointSide side) {
+    if (h->cfg.env_type != M3_ENV_POINT) return nullptr;
+    if ((side & SIDE_COST) && h->weighted_instance == 0 && !default_cost_weights(h))
+        return "the weighted cost instance is forced off (m3_set_weighted_cost_instance 0) but the handle's cost weights are not the defaults";
+    if ((side & SIDE_STEP) && h->scene_instance == 0 && h->scene_rows_on)
         return "the run-time-scene instance is forced off (m3_set_point_scene_instance 0) but the handle has an arena per environment (m3_set_point_scene_rows)";
-    if (h->cfg.env_type == M3_ENV_POINT && h->scene_instance == 0 && !default_point_scene(h))
+    if ((side & SIDE_STEP) && h->scene_instance == 0 && !default_point_scene(h))
         return "the run-time-scene instance is forced off (m3_set_point_scene_instance 0) but the handle's scene is not the default";
     return nullptr;
 }
@@ -1096,9 +1105,7 @@ static const char* rollout_refusal(const m3_handle* h) {
     if (c.mode_simple && !c.sampling_random && !h->have_noise)
         return "m3_rollout: simple mode needs m3_set_noise or sampling_random";
     if (h->task == M3_TASK_PUSH_PULL && !c.multi_modal) return "m3_rollout: push_pull needs multi_modal";
-    if (const char* why = weighted_refusal(h)) return why;
-    if (const char* why = scene_refusal(h)) return why;
-    return nullptr;
+    return point_variant_refusal(h, SIDE_ROLLOUT);
 }
 
 // the rollout's arguments; refreshes the wavefront order when it is due (a stream-ordered launch)
@@ -1187,7 +1194,7 @@ static int plan_rollout(m3_handle* h, RolloutArgs& a, PandaArgs& pa, RolloutPlan
     if (rc != M3_OK) return rc;
     if (h->cfg.env_type == M3_ENV_POINT) {
         // (the two-wavefront form: m3_rollout's own launch only, and only with the error word to report into)
-        p = plan_rollout_point(a, h->scene, weighted_cost(h), (own_launch && h->rollout_err_dev) ? h->point_form : 0, runtime_scene(h));
+        p = plan_rollout_point(a, h->scene, point_variant(h, SIDE_ROLLOUT), (own_launch && h->rollout_err_dev) ? h->point_form : 0);
     } else {
         fill_panda_args(h, a, pa);
         p = plan_rollout_panda(a, pa);
@@ -1211,8 +1218,7 @@ extern "C" int m3_rollout(m3_handle* h) {
     if (rc != M3_OK) return rc;
     if (h->cfg.env_type == M3_ENV_POINT) h->point_form_used = p.form;
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    if (h->cfg.env_type == M3_ENV_POINT && p.scene) launch_rollout_point_scene(a, h->scene_rt, h->cost_weights, p, h->stream);
-    else if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->cost_weights, p, h->stream, h->rollout_err_dev);
+    if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->scene_rt, h->cost_weights, p, h->stream, h->rollout_err_dev);
     else launch_rollout_panda(a, pa, h->pscene, p, h->stream);
     HIPCHK(h, hipGetLastError());
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
@@ -1792,8 +1798,7 @@ struct BatchKey {
 // the fields a group shares, in the order the groups are sorted by
 auto rollout_fields(const BatchKey& k) {
     const RolloutPlan& p = k.roll;
-    // (scene, then weighted, first: the weighted groups' entries, of their own type, lie behind the plain ones in the table, the
-    // run-time-scene groups' -- always weighted -- behind those)
+    // (scene, then weighted, first: that is the order of PointVariant, by which the table's sections lie)
     return std::tie(p.scene, p.weighted, p.instance, p.ref, p.lps, p.forces, p.general, p.shadows, p.rec, k.K, k.T, p.lanes);
 }
 auto update_fields(const BatchKey& k) { return std::tie(k.upd.nu, k.upd.multi, k.upd.jr, k.upd.wt, k.upd.n_cand, k.T); }
@@ -1807,15 +1812,14 @@ struct BatchHandle {   // one handle's command as planned, in call order (copied
     UpdateArgs u;
     BatchKey key;
 };
-size_t align16(size_t n) { return (n + 15) / 16 * 16; }
+constexpr BatchTableSizes BATCH_TABLE_SIZES = {{sizeof(BatchRolloutEntry), sizeof(BatchRolloutEntryW), sizeof(BatchRolloutEntryS)},
+                                               sizeof(BatchPandaEntry), sizeof(UpdateArgs)};
 }  // namespace
 
 struct m3_batch {
     int device = 0, max_handles = 0;
     std::string err;
-    size_t upd_off = 0, slot_bytes = 0;   // a slot: [max_handles] BatchRolloutEntry (then, 16-aligned each, the weighted groups'
-                                          // BatchRolloutEntryW and the run-time-scene groups' BatchRolloutEntryS) or
-                                          // BatchPandaEntry (from 0) | [max_handles] UpdateArgs
+    size_t slot_bytes = 0;   // of a slot: the largest table of max_handles handles (batch_table_layout.hpp)
     char* host[BATCH_SLOTS] = {};
     char* dev[BATCH_SLOTS] = {};
     hipEvent_t done[BATCH_SLOTS] = {};
@@ -1859,10 +1863,7 @@ extern "C" int m3_batch_create(int device, int max_handles, m3_batch** out) {
     if (!b) { g_batch_err = "m3_batch_create: out of host memory"; return M3_ERR_HIP; }
     b->device = device;
     b->max_handles = max_handles;
-    constexpr size_t entry = std::max(std::max(std::max(sizeof(BatchRolloutEntry), sizeof(BatchRolloutEntryW)), sizeof(BatchRolloutEntryS)),
-                                      sizeof(BatchPandaEntry));
-    b->upd_off = align16((size_t)max_handles * entry) + 32;   // (+ 32: the alignment gaps in front of the weighted and the scene entries)
-    b->slot_bytes = b->upd_off + (size_t)max_handles * sizeof(UpdateArgs);
+    b->slot_bytes = batch_table_capacity(BATCH_TABLE_SIZES, max_handles);
     try {
         b->seen.resize(max_handles);
         b->hd.resize(max_handles);
@@ -1976,39 +1977,34 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
         HIPCHK(b, hipEventSynchronize(b->done[slot]));
         b->in_flight[slot] = false;
     }
-    // point_env: the first n_plain handles in key order are the unweighted ones (rollout_fields), the weighted ones follow, the
-    // run-time-scene ones (from n_ws on) come last
-    int n_plain = n, n_ws = n;
-    if (!panda) {
-        n_plain = 0;
-        while (n_plain < n && !hd[b->by_roll[n_plain]].key.roll.weighted) ++n_plain;
-        n_ws = n_plain;
-        while (n_ws < n && !hd[b->by_roll[n_ws]].key.roll.scene) ++n_ws;
-    }
-    const size_t w_off = align16((size_t)n_plain * sizeof(BatchRolloutEntry));
-    const size_t s_off = align16(w_off + (size_t)(n_ws - n_plain) * sizeof(BatchRolloutEntryW));
-    BatchRolloutEntryS* hsn = reinterpret_cast<BatchRolloutEntryS*>(b->host[slot] + s_off);
-    BatchRolloutEntry* hr = reinterpret_cast<BatchRolloutEntry*>(b->host[slot]);
-    BatchRolloutEntryW* hw = reinterpret_cast<BatchRolloutEntryW*>(b->host[slot] + w_off);
-    BatchPandaEntry* hp = reinterpret_cast<BatchPandaEntry*>(b->host[slot]);
-    const size_t upd_off = panda ? align16((size_t)n * sizeof(BatchPandaEntry))
-                                 : align16(s_off + (size_t)(n - n_ws) * sizeof(BatchRolloutEntryS));
-    UpdateArgs* hu = reinterpret_cast<UpdateArgs*>(b->host[slot] + upd_off);
+    // point_env: in key order the handles come by variant (rollout_fields), as the table's sections do
+    int count[POINT_VARIANTS] = {};
+    if (!panda)
+        for (int i = 0; i < n; ++i) ++count[point_variant(hd[i].key.roll)];
+    const BatchTableLayout lay = panda ? batch_table_layout_panda(BATCH_TABLE_SIZES, n) : batch_table_layout(BATCH_TABLE_SIZES, count);
+    // byte offset of the rollout entry of the p-th handle in key order
+    auto entry_off = [&](int p) {
+        if (panda) return (size_t)p * sizeof(BatchPandaEntry);
+        int v = 0;
+        for (; p >= count[v]; ++v) p -= count[v];
+        return lay.off[v] + (size_t)p * BATCH_TABLE_SIZES.entry[v];
+    };
     for (int p = 0; p < n; ++p) {
         const int i = b->by_roll[p];
-        if (panda) { hp[p].a = hd[i].a; hp[p].pa = hd[i].pa; hp[p].sc = hs[i]->pscene; }
-        else if (p < n_plain) { hr[p].a = hd[i].a; hr[p].sc = hs[i]->scene; }
-        else if (p < n_ws) { BatchRolloutEntryW& e = hw[p - n_plain]; e.a = hd[i].a; e.sc = hs[i]->scene; e.wt = hs[i]->cost_weights; }
-        else { BatchRolloutEntryS& e = hsn[p - n_ws]; e.a = hd[i].a; e.sc = hs[i]->scene_rt; e.wt = hs[i]->cost_weights; }
+        const m3_handle* h = hs[i];
+        char* e = b->host[slot] + entry_off(p);
+        if (panda) { *reinterpret_cast<BatchPandaEntry*>(e) = {hd[i].a, hd[i].pa, h->pscene}; continue; }
+        switch (point_variant(hd[i].key.roll)) {
+            case POINT_SCENE: *reinterpret_cast<BatchRolloutEntryS*>(e) = {hd[i].a, h->scene_rt, h->cost_weights}; break;
+            case POINT_WEIGHTED: *reinterpret_cast<BatchRolloutEntryW*>(e) = {hd[i].a, h->scene, h->cost_weights}; break;
+            default: *reinterpret_cast<BatchRolloutEntry*>(e) = {hd[i].a, h->scene}; break;
+        }
     }
+    UpdateArgs* hu = reinterpret_cast<UpdateArgs*>(b->host[slot] + lay.upd_off);
     for (int p = 0; p < n; ++p) hu[p] = hd[b->by_upd[p]].u;
     char* dslot = b->dev[slot];
-    HIPCHK(b, hipMemcpyAsync(dslot, b->host[slot], upd_off + (size_t)n * sizeof(UpdateArgs), hipMemcpyHostToDevice, s));
-    const BatchRolloutEntry* dr = reinterpret_cast<const BatchRolloutEntry*>(dslot);
-    const BatchRolloutEntryW* dw = reinterpret_cast<const BatchRolloutEntryW*>(dslot + w_off);
-    const BatchRolloutEntryS* dsn = reinterpret_cast<const BatchRolloutEntryS*>(dslot + s_off);
-    const BatchPandaEntry* dp = reinterpret_cast<const BatchPandaEntry*>(dslot);
-    const UpdateArgs* du = reinterpret_cast<const UpdateArgs*>(dslot + upd_off);
+    HIPCHK(b, hipMemcpyAsync(dslot, b->host[slot], lay.total, hipMemcpyHostToDevice, s));
+    const UpdateArgs* du = reinterpret_cast<const UpdateArgs*>(dslot + lay.upd_off);
     // ---- one rollout launch per group (panda_env: + one k_panda_reach_cost launch when the group keeps the record buffer,
     // not counted) ----
     int n_roll = 0, n_upd = 0;
@@ -2016,10 +2012,8 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
         const BatchKey& k = hd[b->by_roll[p]].key;
         int q = p + 1;
         while (q < n && same_rollout(hd[b->by_roll[q]].key, k)) ++q;
-        if (panda) launch_rollout_panda_batch(dp + p, q - p, k.roll, k.K, s);
-        else if (k.roll.scene) launch_rollout_point_batch_s(dsn + (p - n_ws), q - p, k.roll, s);
-        else if (k.roll.weighted) launch_rollout_point_batch_w(dw + (p - n_plain), q - p, k.roll, s);
-        else launch_rollout_point_batch(dr + p, q - p, k.roll, s);
+        if (panda) launch_rollout_panda_batch(reinterpret_cast<const BatchPandaEntry*>(dslot + entry_off(p)), q - p, k.roll, k.K, s);
+        else launch_rollout_point_batch(dslot + entry_off(p), q - p, k.roll, s);
         ++n_roll;
         p = q;
     }
@@ -2206,11 +2200,13 @@ extern "C" int m3_sim_apply_body_forces(m3_handle* h, const float* f) {
 static int sim_step_impl(m3_handle* h, const float* u) {
     if (!h->views_bound) return fail(h, M3_ERR_STATE, "m3_sim_step: views not bound");
     if (h->cfg.env_type == M3_ENV_POINT) {
-        if (const char* why = scene_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_sim_step: ") + why).c_str());
-        if (h->scene_rows_on)
-            launch_sim_step_sv(h->scene_rt, h->scene_rows_dev, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
-        else if (runtime_scene(h)) launch_sim_step_s(h->scene_rt, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
-        else launch_sim_step(h->scene, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
+        if (const char* why = point_variant_refusal(h, SIDE_STEP)) return fail(h, M3_ERR_STATE, (std::string("m3_sim_step: ") + why).c_str());
+        const int Kl = h->cfg.K_local;
+        switch (point_step_variant(h)) {
+            case STEP_ROWS: launch_sim_step_sv(h->scene_rt, h->scene_rows_dev, h->views, h->sim_world, u, h->sim_u, Kl, h->stream); break;
+            case STEP_RUNTIME: launch_sim_step_s(h->scene_rt, h->views, h->sim_world, u, h->sim_u, Kl, h->stream); break;
+            default: launch_sim_step(h->scene, h->views, h->sim_world, u, h->sim_u, Kl, h->stream); break;
+        }
     } else {
         launch_psim_step(h->pscene, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
     }
@@ -2255,11 +2251,11 @@ extern "C" int m3_cost(m3_handle* h, float* cost) {
     if (!h || !cost) return M3_ERR_BAD_ARG;
     if (!h->sim_world) return fail(h, M3_ERR_STATE, "m3_cost: step-mode state not initialised");
     if (h->cfg.env_type == M3_ENV_POINT) {
-        if (const char* why = weighted_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_cost: ") + why).c_str());
+        if (const char* why = point_variant_refusal(h, SIDE_COST)) return fail(h, M3_ERR_STATE, (std::string("m3_cost: ") + why).c_str());
         CostParams cp;
         fill_cost_params(h, cp);
-        if (weighted_cost(h)) launch_sim_cost_w(cp, h->cost_weights, h->sim_world, h->cfg.K_local, h->cfg.k_offset, cost, h->stream);
-        else launch_sim_cost(cp, h->sim_world, h->cfg.K_local, h->cfg.k_offset, cost, h->stream);
+        const PointCostWeights* wt = point_variant(h, SIDE_COST) == POINT_WEIGHTED ? &h->cost_weights : nullptr;
+        launch_sim_cost(cp, wt, h->sim_world, h->cfg.K_local, h->cfg.k_offset, cost, h->stream);
     } else {
         PandaCostParams cp;
         fill_panda_cost_params(h, cp);
@@ -2413,9 +2409,11 @@ static int eps_ready(m3_episodes* eps, const char* who) {
 
 // the step of the world's rows with the WORLD handle's scene (the planners plan with their own)
 static void episodes_post(const m3_handle* w, const m3::EpisodeArgs& a, int tick) {
-    if (w->scene_rows_on) m3::launch_episodes_post_sv(w->scene_rt, w->scene_rows_dev, a, tick, w->stream);   // a scene per episode
-    else if (runtime_scene(w)) m3::launch_episodes_post_s(w->scene_rt, a, tick, w->stream);
-    else m3::launch_episodes_post(w->scene, a, tick, w->stream);
+    switch (point_step_variant(w)) {
+        case STEP_ROWS: m3::launch_episodes_post_sv(w->scene_rt, w->scene_rows_dev, a, tick, w->stream); break;   // a scene per episode
+        case STEP_RUNTIME: m3::launch_episodes_post_s(w->scene_rt, a, tick, w->stream); break;
+        default: m3::launch_episodes_post(w->scene, a, tick, w->stream); break;
+    }
 }
 
 static int eps_status_sync(m3_episodes* eps) {
@@ -2441,7 +2439,7 @@ extern "C" int m3_episodes_end(m3_episodes* eps) {
     if (!eps->mid_tick) { eps->err = "m3_episodes_end: no tick begun"; return M3_ERR_STATE; }
     int rc = eps_ready(eps, "m3_episodes_end");
     if (rc != M3_OK) return rc;
-    if (const char* why = scene_refusal(eps->world)) { eps->err = std::string("m3_episodes_end: world: ") + why; return M3_ERR_STATE; }
+    if (const char* why = point_variant_refusal(eps->world, SIDE_STEP)) { eps->err = std::string("m3_episodes_end: world: ") + why; return M3_ERR_STATE; }
     episodes_post(eps->world, eps->args, eps->tick);
     HIPCHK(eps, hipGetLastError());
     eps->mid_tick = false;
@@ -2455,7 +2453,7 @@ extern "C" int m3_episodes_tick(m3_episodes* eps, m3_batch* batch) {
     if (eps->mid_tick) { eps->err = "m3_episodes_tick: inside m3_episodes_begin / m3_episodes_end"; return M3_ERR_STATE; }
     int rc = eps_ready(eps, "m3_episodes_tick");
     if (rc != M3_OK) return rc;
-    if (const char* why = scene_refusal(eps->world)) { eps->err = std::string("m3_episodes_tick: world: ") + why; return M3_ERR_STATE; }
+    if (const char* why = point_variant_refusal(eps->world, SIDE_STEP)) { eps->err = std::string("m3_episodes_tick: world: ") + why; return M3_ERR_STATE; }
     // the batch: episodes still running after the last tick's status (one that succeeds in this tick's pre kernel is
     // commanded once more -- its plan is never recorded)
     eps->live.clear();

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <string>
 
 #include "../../include/m3p2i_hip.h"
@@ -158,20 +159,34 @@ __host__ __device__ inline int regen_off_table(int Kls, int T) { return regen_of
 __host__ __device__ inline int regen_record_length(int Kls, int T) { return (regen_off_table(Kls, T) + LAD_N * 3 + 3) / 4 * 4; }
 
 // ---- batched command (m3_batch_command): the per-handle entries of the device argument table ----------------------
-struct BatchRolloutEntry {   // one point_env handle's rollout (the scene is not read by the _ref build)
+// The variant of the point_env rollout kernels a handle runs, decided in one place (m3_api.hip: point_variant): the reference's
+// arena and cost weights compiled in; the handle's cost weights a kernel argument (m3_set_point_cost_weights); the handle's
+// arena a kernel argument as well (m3_set_point_scene -- always with the weights).  Also the order of the table's sections.
+enum PointVariant { POINT_PLAIN = 0, POINT_WEIGHTED = 1, POINT_SCENE = 2, POINT_VARIANTS = 3 };
+// one point_env handle's rollout: the arguments, the variant's scene (not read by the _ref build) and, for the variants that
+// carry them, the handle's cost weights behind it
+template <class SC, bool WEIGHTED>
+struct BatchRolloutEntryT {
+    static constexpr bool weighted = true;
     RolloutArgs a;
-    PointScene sc;
-};
-struct BatchRolloutEntryW {  // ... of the weighted group (kb_rollout_point_w): the same with the handle's cost weights behind it
-    RolloutArgs a;
-    PointScene sc;
+    SC sc;
     PointCostWeights wt;
 };
-struct BatchRolloutEntryS {  // ... of the run-time-scene group (kb_rollout_point_s): the handle's own arena and its weights
+template <class SC>
+struct BatchRolloutEntryT<SC, false> {
+    static constexpr bool weighted = false;
     RolloutArgs a;
-    PointSceneRT sc;
-    PointCostWeights wt;
+    SC sc;
 };
+using BatchRolloutEntry = BatchRolloutEntryT<PointScene, false>;
+using BatchRolloutEntryW = BatchRolloutEntryT<PointScene, true>;
+using BatchRolloutEntryS = BatchRolloutEntryT<PointSceneRT, true>;
+// (the kernels read the table by these offsets: they are what they were when the three were written out by hand)
+static_assert(sizeof(RolloutArgs) == 528 && sizeof(BatchRolloutEntry) == 584 && offsetof(BatchRolloutEntry, sc) == 528, "");
+static_assert(sizeof(BatchRolloutEntryW) == 616 && offsetof(BatchRolloutEntryW, sc) == 528 &&
+              offsetof(BatchRolloutEntryW, wt) == 580, "");
+static_assert(sizeof(BatchRolloutEntryS) == 760 && offsetof(BatchRolloutEntryS, sc) == 528 &&
+              offsetof(BatchRolloutEntryS, wt) == 724, "");
 // the k_update_small instance (template arguments, workgroup width, top-k workgroups) an unsharded command takes:
 // launch_update_small launches it, m3_batch_command groups the handles by it
 struct SmallUpdateInstance {
@@ -194,29 +209,27 @@ struct RolloutPlan {
                                               // (point_env: all 0)
     int lanes, blocks;   // active lanes per wavefront, rollout workgroups
     int rows;            // rows of minima the launch leaves in a.wave_min (wave_min.hpp; 0: none)
-    int weighted;        // point_env: the weighted build of the general instance (m3_set_point_cost_weights; instance == -1)
+    int weighted;        // point_env: the build of the general instance that takes the cost weights (POINT_WEIGHTED, POINT_SCENE;
+                         // instance == -1)
     int form;            // point_env: 0 one wavefront per 64 samples, 1 dynamics + companion wavefront (rollout_point_kernel.hpp:
                          // rollout_point_body2); m3_rollout only -- the batched and episode paths plan with form_request 0
-    int scene;           // point_env: the run-time-scene build of the general instance (m3_set_point_scene; instance == -1,
+    int scene;           // point_env: the run-time-scene build of the general instance (POINT_SCENE; instance == -1,
                          // weighted == 1, ref == 0, form == 0)
 };
+inline PointVariant point_variant(const RolloutPlan& p) { return p.scene ? POINT_SCENE : p.weighted ? POINT_WEIGHTED : POINT_PLAIN; }
 // form_request: m3_set_point_rollout_form's value (0 one wavefront, 1 two wherever available, -1 by rollout_companion_pays)
-RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, bool weighted, int form_request = 0,
-                               bool scene = false /* the handle runs the run-time-scene build */);
-// one launch of the plan's instance for n handles of K_local = a.Kl and the same plan (tab: device, n entries)
-void launch_rollout_point_batch(const BatchRolloutEntry* tab, int n, const RolloutPlan& p, hipStream_t s);
-void launch_rollout_point_batch_w(const BatchRolloutEntryW* tab, int n, const RolloutPlan& p, hipStream_t s);   // p.weighted
-void launch_rollout_point_batch_s(const BatchRolloutEntryS* tab, int n, const RolloutPlan& p, hipStream_t s);   // p.scene
-// one handle's launch of the run-time-scene build (p.scene)
-void launch_rollout_point_scene(const RolloutArgs& a, const PointSceneRT& sc, const PointCostWeights& wt, const RolloutPlan& p,
-                                hipStream_t s);
+RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, PointVariant variant, int form_request = 0);
+// one launch of the plan's instance for n handles of K_local = a.Kl and the same plan (tab: device, n entries of the type of
+// the plan's variant)
+void launch_rollout_point_batch(const void* tab, int n, const RolloutPlan& p, hipStream_t s);
 void launch_rollout_point_nav_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
 void launch_rollout_point_push_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
 void launch_rollout_point_pull_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
 void launch_rollout_point_pushpull_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
 
 // ---- launchers (defined in the .hip files) ---------------------------------------------
-void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const PointCostWeights& wt /* read if p.weighted */,
+// one handle's launch of the plan; the plan's variant says which of sc / rt and whether wt is read
+void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const PointSceneRT& rt, const PointCostWeights& wt,
                           const RolloutPlan& p, hipStream_t s, int* err = nullptr /* p.form == 1: the hand-over's error word */);
 // the two-wavefront form of the navigation / push instances (p.form == 1)
 void launch_rollout_point_nav2(const RolloutArgs& a, const PointScene& sc, int blocks, int* err, hipStream_t s);
@@ -326,10 +339,8 @@ void launch_sim_step_sv(const PointSceneRT& uni, const float* rows, const SimVie
                         float* u_keep, int Kl, hipStream_t s);
 void launch_sim_forces(const SimViews& v, float* world, const float* f /*[Kl][nB][3]*/, int Kl,
                        hipStream_t s);
-void launch_sim_cost(const CostParams& cp, float* world, int Kl, int k0, float* cost,
-                     hipStream_t s);
-void launch_sim_cost_w(const CostParams& cp, const PointCostWeights& wt, float* world, int Kl, int k0, float* cost,
-                       hipStream_t s);
+// wt: the handle's cost weights, or null for the reference's (compiled in)
+void launch_sim_cost(const CostParams& cp, const PointCostWeights* wt, float* world, int Kl, int k0, float* cost, hipStream_t s);
 void launch_sim_suction(const SimViews& v, float* world, int Kl, float kp, float thresh, float reach,
                         const float* action, int apply, float* forces, int* flags, const int* gate, hipStream_t s);
 

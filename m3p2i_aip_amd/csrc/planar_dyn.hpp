@@ -87,7 +87,7 @@ inline bool point_scene_is_reference(const PointScene& s) {
 // constant there.  Every function below that reads a scene is a template on the scene type (`SC`): the PointScene instantiations
 // are what they were (a constant folds into the instruction stream), the PointSceneRT instantiations run the same operations in
 // the same order on values that arrive as kernel arguments.  Only the kernels of a handle whose scene is not the default
-// (k_rollout_point_s, kb_rollout_point_s, k_sim_step_s, k_episodes_post_s) are instantiated with it.
+// (k_rollout_point / kb_rollout_point on PointSceneRT, k_sim_step_s, k_episodes_post_s) are instantiated with it.
 struct PointSceneRT {
     float h, inv_h;
     int substeps, iters;

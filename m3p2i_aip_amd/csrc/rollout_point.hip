@@ -17,118 +17,19 @@ int rollout_lanes_for(int Kl) {
     return 64;
 }
 
-// ---- weighted cost (m3_set_point_cost_weights): the general instance with point_cost_w, the nine weights a kernel argument
-// of their own (wave-uniform: scalar registers, loaded once) -- RolloutArgs and every other instance are untouched.  The same
-// four builds, picked by the same rule.
-__global__ __launch_bounds__(64) void k_rollout_point_w(const RolloutArgs a, const PointScene sc, const PointCostWeights wt) {
-    rollout_point_body<true, -1, true, true>(a, sc, &wt);
-}
-__global__ __launch_bounds__(64) void k_rollout_point_w_ref(const RolloutArgs a, const PointCostWeights wt) {
-    constexpr PointScene sc = POINT_SCENE_REFERENCE;
-    rollout_point_body<true, -1, true, true>(a, sc, &wt);
-}
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_rollout_point_w_occ2(
-    const RolloutArgs a, const PointScene sc, const PointCostWeights wt) {
-    rollout_point_body<true, -1, false, true>(a, sc, &wt);
-}
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_rollout_point_w_occ3(
-    const RolloutArgs a, const PointScene sc, const PointCostWeights wt) {
-    rollout_point_body<true, -1, false, true>(a, sc, &wt);
-}
-static void launch_rollout_point_weighted(const RolloutArgs& a, const PointScene& sc, const PointCostWeights& wt, int blocks,
-                                          hipStream_t s) {
-    switch (rollout_point_build(blocks, point_scene_is_reference(sc))) {
-        case BUILD_OCC3: hipLaunchKernelGGL(k_rollout_point_w_occ3, dim3(blocks), dim3(64), 0, s, a, sc, wt); break;
-        case BUILD_OCC2: hipLaunchKernelGGL(k_rollout_point_w_occ2, dim3(blocks), dim3(64), 0, s, a, sc, wt); break;
-        case BUILD_LONE_REF: hipLaunchKernelGGL(k_rollout_point_w_ref, dim3(blocks), dim3(64), 0, s, a, wt); break;
-        default: hipLaunchKernelGGL(k_rollout_point_w, dim3(blocks), dim3(64), 0, s, a, sc, wt); break;
-    }
-}
-// ... and the weighted group's twin: its own entry type (BatchRolloutEntryW: the entry + the handle's weights), so that handles
-// with different weights share one launch and the entries of the other kernels keep their size
-__global__ __launch_bounds__(64) void kb_rollout_point_w(const BatchRolloutEntryW* __restrict__ tab) {
-    rollout_point_body<true, -1, true, true>(tab[blockIdx.y].a, tab[blockIdx.y].sc, &tab[blockIdx.y].wt);
-}
-__global__ __launch_bounds__(64) void kb_rollout_point_w_ref(const BatchRolloutEntryW* __restrict__ tab) {
-    constexpr PointScene sc = POINT_SCENE_REFERENCE;
-    rollout_point_body<true, -1, true, true>(tab[blockIdx.y].a, sc, &tab[blockIdx.y].wt);
-}
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void kb_rollout_point_w_occ2(
-    const BatchRolloutEntryW* __restrict__ tab) {
-    rollout_point_body<true, -1, false, true>(tab[blockIdx.y].a, tab[blockIdx.y].sc, &tab[blockIdx.y].wt);
-}
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void kb_rollout_point_w_occ3(
-    const BatchRolloutEntryW* __restrict__ tab) {
-    rollout_point_body<true, -1, false, true>(tab[blockIdx.y].a, tab[blockIdx.y].sc, &tab[blockIdx.y].wt);
-}
-static void launch_rollout_point_weighted_batch(const BatchRolloutEntryW* tab, int blocks, int n, bool ref, hipStream_t s) {
-    const dim3 grid(blocks, n);
-    switch (rollout_point_build(blocks * n, ref)) {
-        case BUILD_OCC3: hipLaunchKernelGGL(kb_rollout_point_w_occ3, grid, dim3(64), 0, s, tab); break;
-        case BUILD_OCC2: hipLaunchKernelGGL(kb_rollout_point_w_occ2, grid, dim3(64), 0, s, tab); break;
-        case BUILD_LONE_REF: hipLaunchKernelGGL(kb_rollout_point_w_ref, grid, dim3(64), 0, s, tab); break;
-        default: hipLaunchKernelGGL(kb_rollout_point_w, grid, dim3(64), 0, s, tab); break;
-    }
-}
-
-// ---- run-time scene (m3_set_point_scene): the general, weighted instance on PointSceneRT -- the arena arrives as a kernel
-// argument instead of being compiled in.  Three builds picked by the same rule; no _ref build: the compile-time solver scene is
-// a property of the default-scene kernels.  At the default values the same bits as k_rollout_point_w (same operations in the same
-// order; the broad-phase radii are conservative, planar_dyn.hpp).
-__global__ __launch_bounds__(64) void k_rollout_point_s(const RolloutArgs a, const PointSceneRT sc, const PointCostWeights wt) {
-    rollout_point_body<true, -1, true, true>(a, sc, &wt);
-}
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_rollout_point_s_occ2(
-    const RolloutArgs a, const PointSceneRT sc, const PointCostWeights wt) {
-    rollout_point_body<true, -1, false, true>(a, sc, &wt);
-}
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_rollout_point_s_occ3(
-    const RolloutArgs a, const PointSceneRT sc, const PointCostWeights wt) {
-    rollout_point_body<true, -1, false, true>(a, sc, &wt);
-}
-void launch_rollout_point_scene(const RolloutArgs& a, const PointSceneRT& sc, const PointCostWeights& wt, const RolloutPlan& p,
-                                hipStream_t s) {
-    const int blocks = p.blocks;
-    switch (rollout_point_build(blocks, false)) {
-        case BUILD_OCC3: hipLaunchKernelGGL(k_rollout_point_s_occ3, dim3(blocks), dim3(64), 0, s, a, sc, wt); break;
-        case BUILD_OCC2: hipLaunchKernelGGL(k_rollout_point_s_occ2, dim3(blocks), dim3(64), 0, s, a, sc, wt); break;
-        default: hipLaunchKernelGGL(k_rollout_point_s, dim3(blocks), dim3(64), 0, s, a, sc, wt); break;
-    }
-}
-// ... and the scene group's batched twin: its own entry type (BatchRolloutEntryS: arguments + the handle's scene + its weights),
-// so that handles with different scenes share one launch and the entries of the other kernels keep their size
-__global__ __launch_bounds__(64) void kb_rollout_point_s(const BatchRolloutEntryS* __restrict__ tab) {
-    rollout_point_body<true, -1, true, true>(tab[blockIdx.y].a, tab[blockIdx.y].sc, &tab[blockIdx.y].wt);
-}
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void kb_rollout_point_s_occ2(
-    const BatchRolloutEntryS* __restrict__ tab) {
-    rollout_point_body<true, -1, false, true>(tab[blockIdx.y].a, tab[blockIdx.y].sc, &tab[blockIdx.y].wt);
-}
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void kb_rollout_point_s_occ3(
-    const BatchRolloutEntryS* __restrict__ tab) {
-    rollout_point_body<true, -1, false, true>(tab[blockIdx.y].a, tab[blockIdx.y].sc, &tab[blockIdx.y].wt);
-}
-void launch_rollout_point_batch_s(const BatchRolloutEntryS* tab, int n, const RolloutPlan& p, hipStream_t s) {
-    const dim3 grid(p.blocks, n);
-    switch (rollout_point_build(p.blocks * n, false)) {
-        case BUILD_OCC3: hipLaunchKernelGGL(kb_rollout_point_s_occ3, grid, dim3(64), 0, s, tab); break;
-        case BUILD_OCC2: hipLaunchKernelGGL(kb_rollout_point_s_occ2, grid, dim3(64), 0, s, tab); break;
-        default: hipLaunchKernelGGL(kb_rollout_point_s, grid, dim3(64), 0, s, tab); break;
-    }
-}
-
 // The form of a launch.  Instance -1: the general instance (every sampler mode, task at run time); 0..3: the instance with
 // the reference's default sampler and that task compiled in (rollout_point_task*.hip).  Only the general and the push_pull
 // instances carry the epilogue that leaves the workgroups' cost minima (rollout_point_kernel.hpp).
-// weighted: the handle's cost weights are not the defaults (or the weighted instance is forced on): the general instance with
-// point_cost_w, whatever the sampler and the task.
+// variant POINT_WEIGHTED: the handle's cost weights are not the defaults (or the weighted instance is forced on): the general
+// instance with point_cost_w, whatever the sampler and the task.
 // form_request: the two-wavefront form (RolloutPlan::form = 1) exists for the navigation and push instances in the builds with
 // one resident wavefront per SIMD, with the default weights and a horizon whose tables fit its LDS; 1 takes it wherever it
 // exists, -1 where rollout_companion_pays as well, 0 never (m3_batch_command, the episode paths).
-// scene: the handle's arena is not the default (or the run-time-scene build is forced on): the general instance on PointSceneRT,
-// which is always the weighted build as well -- instance -1, form 0, ref 0, whatever the sampler, the task and the weights.
-RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, bool weighted, int form_request, bool scene) {
-    if (scene) {
+// variant POINT_SCENE: the handle's arena is not the default (or the run-time-scene build is forced on): the general instance on
+// PointSceneRT, which always takes the weights as well -- instance -1, form 0, ref 0, whatever the sampler, the task and the weights.
+RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, PointVariant variant, int form_request) {
+    const bool weighted = variant != POINT_PLAIN;
+    if (variant == POINT_SCENE) {
         RolloutPlan p{};
         p.scene = 1; p.weighted = 1;
         p.instance = -1; p.ref = 0; p.form = 0;
@@ -161,9 +62,13 @@ RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, bool 
     return p;
 }
 
-void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const PointCostWeights& wt, const RolloutPlan& p,
-                          hipStream_t s, int* err) {
-    if (p.weighted) { launch_rollout_point_weighted(a, sc, wt, p.blocks, s); return; }
+void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const PointSceneRT& rt, const PointCostWeights& wt,
+                          const RolloutPlan& p, hipStream_t s, int* err) {
+    switch (point_variant(p)) {
+        case POINT_SCENE: launch_rollout_point_instance<true, -1>(a, rt, p.blocks, s, wt); return;
+        case POINT_WEIGHTED: launch_rollout_point_instance<true, -1>(a, sc, p.blocks, s, wt); return;
+        default: break;
+    }
     if (p.form == 1) {
         if (p.instance == 0) launch_rollout_point_nav2(a, sc, p.blocks, err, s);
         else launch_rollout_point_push2(a, sc, p.blocks, err, s);
@@ -178,19 +83,25 @@ void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const Poin
     }
 }
 
-void launch_rollout_point_batch(const BatchRolloutEntry* tab, int n, const RolloutPlan& p, hipStream_t s) {
+void launch_rollout_point_batch(const void* tab, int n, const RolloutPlan& p, hipStream_t s) {
     const bool ref = p.ref != 0;
-    switch (p.instance) {
-        case -1: launch_rollout_point_batch_instance<true, -1>(tab, p.blocks, n, ref, s); break;
-        case 0: launch_rollout_point_nav_batch(tab, p.blocks, n, ref, s); break;
-        case 1: launch_rollout_point_push_batch(tab, p.blocks, n, ref, s); break;
-        case 2: launch_rollout_point_pull_batch(tab, p.blocks, n, ref, s); break;
-        default: launch_rollout_point_pushpull_batch(tab, p.blocks, n, ref, s); break;
+    switch (point_variant(p)) {
+        case POINT_SCENE:
+            launch_rollout_point_batch_instance<true, -1>(static_cast<const BatchRolloutEntryS*>(tab), p.blocks, n, ref, s);
+            return;
+        case POINT_WEIGHTED:
+            launch_rollout_point_batch_instance<true, -1>(static_cast<const BatchRolloutEntryW*>(tab), p.blocks, n, ref, s);
+            return;
+        default: break;
     }
-}
-
-void launch_rollout_point_batch_w(const BatchRolloutEntryW* tab, int n, const RolloutPlan& p, hipStream_t s) {
-    launch_rollout_point_weighted_batch(tab, p.blocks, n, p.ref != 0, s);
+    const BatchRolloutEntry* plain = static_cast<const BatchRolloutEntry*>(tab);
+    switch (p.instance) {
+        case -1: launch_rollout_point_batch_instance<true, -1>(plain, p.blocks, n, ref, s); break;
+        case 0: launch_rollout_point_nav_batch(plain, p.blocks, n, ref, s); break;
+        case 1: launch_rollout_point_push_batch(plain, p.blocks, n, ref, s); break;
+        case 2: launch_rollout_point_pull_batch(plain, p.blocks, n, ref, s); break;
+        default: launch_rollout_point_pushpull_batch(plain, p.blocks, n, ref, s); break;
+    }
 }
 
 // delta [K][T][nu] (reference layout) -> [T][K][nu]
@@ -223,6 +134,7 @@ void launch_sim_step(const PointScene& sc, const SimViews& v, float* world, cons
     hipLaunchKernelGGL(k_sim_step, dim3((Kl + 63) / 64), dim3(64), 0, s, sc, v, world, u, u_keep, Kl);
 }
 
+// (two hand-written kernels: as instances of one templated body, k_sim_cost came out with the operands of one v_add_f32 swapped)
 __global__ void k_sim_cost(const CostParams cp, float* wd, int Kl, int k0, float* cost) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Kl) return;
@@ -232,11 +144,7 @@ __global__ void k_sim_cost(const CostParams cp, float* wd, int Kl, int k0, float
     float* p = wd + i;  // only the pending force changes
     p[18 * Kl] = w.fRx; p[19 * Kl] = w.fRy; p[20 * Kl] = w.fBx; p[21 * Kl] = w.fBy;
 }
-void launch_sim_cost(const CostParams& cp, float* world, int Kl, int k0, float* cost,
-                     hipStream_t s) {
-    hipLaunchKernelGGL(k_sim_cost, dim3((Kl + 255) / 256), dim3(256), 0, s, cp, world, Kl, k0, cost);
-}
-// ... with the handle's cost weights (m3_set_point_cost_weights): what k_rollout_point_w evaluates after each step
+// ... with the handle's cost weights (m3_set_point_cost_weights): what the weighted rollout evaluates after each step
 __global__ void k_sim_cost_w(const CostParams cp, const PointCostWeights wt, float* wd, int Kl, int k0, float* cost) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Kl) return;
@@ -246,9 +154,10 @@ __global__ void k_sim_cost_w(const CostParams cp, const PointCostWeights wt, flo
     float* p = wd + i;  // only the pending force changes
     p[18 * Kl] = w.fRx; p[19 * Kl] = w.fRy; p[20 * Kl] = w.fBx; p[21 * Kl] = w.fBy;
 }
-void launch_sim_cost_w(const CostParams& cp, const PointCostWeights& wt, float* world, int Kl, int k0, float* cost,
-                       hipStream_t s) {
-    hipLaunchKernelGGL(k_sim_cost_w, dim3((Kl + 255) / 256), dim3(256), 0, s, cp, wt, world, Kl, k0, cost);
+void launch_sim_cost(const CostParams& cp, const PointCostWeights* wt, float* world, int Kl, int k0, float* cost, hipStream_t s) {
+    const dim3 grid((Kl + 255) / 256), wg(256);
+    if (wt) hipLaunchKernelGGL(k_sim_cost_w, grid, wg, 0, s, cp, *wt, world, Kl, k0, cost);
+    else hipLaunchKernelGGL(k_sim_cost, grid, wg, 0, s, cp, world, Kl, k0, cost);
 }
 
 // wrapper views (AoS, torch-owned) -> SoA world.  dof_state row = [x, vx, y, vy]
@@ -423,7 +332,8 @@ extern "C" int m3_point_rollout_plan(int task, int multi_modal, int mode_simple,
     a.wave_min = want_minima ? minima_stand_in : nullptr;   // (only tested against null)
     m3::PointScene sc;
     m3::make_point_scene(sc, dt, substeps, solver_iters);
-    const m3::RolloutPlan p = m3::plan_rollout_point(a, sc, weighted != 0, form_request, scene != 0);
+    const m3::PointVariant variant = scene ? m3::POINT_SCENE : weighted ? m3::POINT_WEIGHTED : m3::POINT_PLAIN;
+    const m3::RolloutPlan p = m3::plan_rollout_point(a, sc, variant, form_request);
     out[0] = p.instance; out[1] = p.ref; out[2] = p.form; out[3] = p.weighted; out[4] = p.scene; out[5] = p.blocks;
     out[6] = p.rows; out[7] = p.lanes;
     return M3_OK;

@@ -15,6 +15,8 @@
 // Algorithmic traffic per state-step (nu = 2): read delta 8 B, write state 16 B + action
 // 8 B + cost 4 B = 36 B (28 B with in-kernel noise); the update pass re-reads actions (8 B).
 #pragma once
+#include <type_traits>
+
 #include "m3_internal.hpp"
 #include "noise_stream.hpp"
 #include "wave_min.hpp"
@@ -56,8 +58,8 @@ __device__ __forceinline__ void load_world_from_sim(const float* dof, const floa
 // it disappear from the instance.  Measured at C2: one kernel for everything 0.1555 ms per command, sampler
 // mode compiled in 0.1530, task compiled in as well 0.143 (same results bit for bit: only which code exists).
 // LONE: a build for one resident wavefront per SIMD (planar_dyn.hpp: predicated rows, two-level broad phase)
-// WEIGHTED: the running cost is point_cost_w with *wt (k_rollout_point_w below; wt is not read otherwise)
-// SC: the scene type -- PointScene (the reference's arena compiled in) or PointSceneRT (m3_set_point_scene: k_rollout_point_s in
+// WEIGHTED: the running cost is point_cost_w with *wt (the shells with WT = PointCostWeights below; wt is not read otherwise)
+// SC: the scene type -- PointScene (the reference's arena compiled in) or PointSceneRT (m3_set_point_scene: instantiated in
 // rollout_point.hip, always GENERAL and WEIGHTED)
 template <bool GENERAL, int TASK, bool LONE = true, bool WEIGHTED = false, class SC = PointScene>
 __device__ __forceinline__ void rollout_point_body(const RolloutArgs& a_, const SC& sc,
@@ -201,34 +203,36 @@ __device__ __forceinline__ void rollout_point_body(const RolloutArgs& a_, const 
     a.pend[2 * Kl + i] = w.fBx; a.pend[3 * Kl + i] = w.fBy;
 }
 
-// Three builds of every instance.  k_rollout_point: no register limit -- 312 VGPRs (256 + 56 AGPR), ONE resident wave
-// per SIMD: the fastest build while the launch has no more wavefronts than the chip has SIMDs (K_local <= 65536:
-// every BASELINE config).  k_rollout_point_occ2: `amdgpu_waves_per_eu(2, 2)` -- 256 VGPRs, ~60 values spilled to
-// scratch, TWO resident waves per SIMD whose instruction streams interleave: 2-3 % slower below 65536 samples, but
-// K = 131072: 0.22 -> 0.162 ms.  k_rollout_point_occ3 (below) from four wavefronts per SIMD on.  The host picks by the
-// number of wavefronts (rollout_two_waves / rollout_three_waves).  Same arithmetic, same bits.
-template <bool GENERAL, int TASK>
-__global__ __launch_bounds__(64) void k_rollout_point(const RolloutArgs a, const PointScene sc) {
-    rollout_point_body<GENERAL, TASK>(a, sc);
+// Four builds of every instance.  Lone: no register limit -- 312 VGPRs (256 + 56 AGPR), ONE resident wave per SIMD: the
+// fastest build while the launch has no more wavefronts than the chip has SIMDs (K_local <= 65536: every BASELINE config);
+// k_rollout_point_ref is the same build with the reference's solver settings compiled in (planar_dyn.hpp:
+// POINT_SCENE_REFERENCE).  k_rollout_point_occ<2>: `amdgpu_waves_per_eu(2, 2)` -- 256 VGPRs, ~60 values spilled to scratch,
+// TWO resident waves per SIMD whose instruction streams interleave: 2-3 % slower below 65536 samples, but K = 131072:
+// 0.22 -> 0.162 ms.  k_rollout_point_occ<3>: THREE resident waves (170 VGPRs) from four wavefronts per SIMD on: with the fused
+// multiply-adds of spec v1.4 the two-wave build spills only ~60 values, the three-wave build about what the two-wave build used
+// to -- K = 524 288 0.557 -> 0.497 ms, 1 M 1.08 -> 0.95 ms; equal at 262 144, slower below (a third wave that is not there does
+// not help).  The host picks by the number of wavefronts (rollout_point_build).  Same arithmetic, same bits.
+//
+// One family of shells for every variant (PointVariant, m3_internal.hpp) of every instance: SC is the variant's scene type, WT...
+// is PointCostWeights for the variants that carry the handle's cost weights (m3_set_point_cost_weights: the nine weights a
+// kernel argument of their own -- wave-uniform: scalar registers, loaded once) and empty for the plain one, whose kernels
+// keep the arguments they always had.  On PointSceneRT (m3_set_point_scene) the arena arrives as a kernel argument instead of
+// being compiled in; at the default values the same bits (same operations in the same order; the broad-phase radii are
+// conservative, planar_dyn.hpp).  The lone builds carry no amdgpu_waves_per_eu attribute, hence a shell of their own.
+template <bool GENERAL, int TASK, class SC = PointScene, class... WT>
+__global__ __launch_bounds__(64) void k_rollout_point(const RolloutArgs a, const SC sc, const WT... wt) {
+    rollout_point_body<GENERAL, TASK, true, sizeof...(WT) != 0>(a, sc, &wt...);
 }
-// ... and the same build with the reference's solver settings compiled in (planar_dyn.hpp: POINT_SCENE_REFERENCE)
-template <bool GENERAL, int TASK>
-__global__ __launch_bounds__(64) void k_rollout_point_ref(const RolloutArgs a) {
+template <bool GENERAL, int TASK, class... WT>
+__global__ __launch_bounds__(64) void k_rollout_point_ref(const RolloutArgs a, const WT... wt) {
     constexpr PointScene sc = POINT_SCENE_REFERENCE;
-    rollout_point_body<GENERAL, TASK>(a, sc);
+    rollout_point_body<GENERAL, TASK, true, sizeof...(WT) != 0>(a, sc, &wt...);
 }
-template <bool GENERAL, int TASK>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_rollout_point_occ2(const RolloutArgs a,
-                                                                                                      const PointScene sc) {
-    rollout_point_body<GENERAL, TASK, false>(a, sc);
-}
-// ... and THREE resident waves (170 VGPRs) from four wavefronts per SIMD on: with the fused multiply-adds of spec v1.4 the
-// two-wave build spills only ~60 values, the three-wave build about what the two-wave build used to -- K = 524 288
-// 0.557 -> 0.497 ms, 1 M 1.08 -> 0.95 ms; equal at 262 144, slower below (a third wave that is not there does not help).
-template <bool GENERAL, int TASK>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_rollout_point_occ3(const RolloutArgs a,
-                                                                                                      const PointScene sc) {
-    rollout_point_body<GENERAL, TASK, false>(a, sc);
+template <int OCC, bool GENERAL, int TASK, class SC = PointScene, class... WT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void k_rollout_point_occ(const RolloutArgs a,
+                                                                                                         const SC sc,
+                                                                                                         const WT... wt) {
+    rollout_point_body<GENERAL, TASK, false, sizeof...(WT) != 0>(a, sc, &wt...);
 }
 // which of the builds a launch of `waves` wavefronts takes -- the one rule of every launcher below
 enum RolloutBuild { BUILD_LONE, BUILD_LONE_REF, BUILD_OCC2, BUILD_OCC3 };
@@ -237,13 +241,20 @@ inline RolloutBuild rollout_point_build(int waves, bool ref) {
     if (rollout_two_waves(waves)) return BUILD_OCC2;
     return ref ? BUILD_LONE_REF : BUILD_LONE;
 }
-template <bool GENERAL, int TASK>
-inline void launch_rollout_point_instance(const RolloutArgs& a, const PointScene& sc, int blocks, hipStream_t s) {
-    switch (rollout_point_build(blocks, point_scene_is_reference(sc))) {
-        case BUILD_OCC3: hipLaunchKernelGGL((k_rollout_point_occ3<GENERAL, TASK>), dim3(blocks), dim3(64), 0, s, a, sc); break;
-        case BUILD_OCC2: hipLaunchKernelGGL((k_rollout_point_occ2<GENERAL, TASK>), dim3(blocks), dim3(64), 0, s, a, sc); break;
-        case BUILD_LONE_REF: hipLaunchKernelGGL((k_rollout_point_ref<GENERAL, TASK>), dim3(blocks), dim3(64), 0, s, a); break;
-        default: hipLaunchKernelGGL((k_rollout_point<GENERAL, TASK>), dim3(blocks), dim3(64), 0, s, a, sc); break;
+// Only the compile-time scene has a _ref build: the reference's solver settings are a property of the default-scene kernels.
+template <class SC> constexpr bool scene_has_ref_build = std::is_same<SC, PointScene>::value;
+template <bool GENERAL, int TASK, class SC, class... WT>
+inline void launch_rollout_point_instance(const RolloutArgs& a, const SC& sc, int blocks, hipStream_t s, const WT&... wt) {
+    bool ref = false;
+    if constexpr (scene_has_ref_build<SC>) ref = point_scene_is_reference(sc);
+    const dim3 grid(blocks), wg(64);
+    switch (rollout_point_build(blocks, ref)) {
+        case BUILD_OCC3: hipLaunchKernelGGL((k_rollout_point_occ<3, GENERAL, TASK, SC, WT...>), grid, wg, 0, s, a, sc, wt...); break;
+        case BUILD_OCC2: hipLaunchKernelGGL((k_rollout_point_occ<2, GENERAL, TASK, SC, WT...>), grid, wg, 0, s, a, sc, wt...); break;
+        case BUILD_LONE_REF:
+            if constexpr (scene_has_ref_build<SC>) hipLaunchKernelGGL((k_rollout_point_ref<GENERAL, TASK, WT...>), grid, wg, 0, s, a, wt...);
+            break;
+        default: hipLaunchKernelGGL((k_rollout_point<GENERAL, TASK, SC, WT...>), grid, wg, 0, s, a, sc, wt...); break;
     }
 }
 
@@ -395,39 +406,43 @@ inline void launch_rollout_point2_instance(const RolloutArgs& a, const PointScen
     else hipLaunchKernelGGL((k_rollout_point2<TASK>), dim3(blocks), dim3(128), lds, s, a, sc, err);
 }
 
-// ---- batched command (m3_batch_command): one launch for a group of handles that share the instance, K, T and lanes.
-// blockIdx.y picks the handle's entry of the argument table (BatchRolloutEntry, m3_internal.hpp; read-only, so
+// ---- batched command (m3_batch_command): one launch for a group of handles that share the variant, the instance, K, T and
+// lanes.  blockIdx.y picks the handle's entry of the argument table (BatchRolloutEntryT, m3_internal.hpp; read-only, so
 // `__restrict__`: nothing the body stores can alias it) and the unchanged body runs on it.  The same four builds with the same
-// attributes, picked by the GROUP's wavefront count (rollout_two_waves / rollout_three_waves): same bits.
-template <bool GENERAL, int TASK>
-__global__ __launch_bounds__(64) void kb_rollout_point(const BatchRolloutEntry* __restrict__ tab) {
-    rollout_point_body<GENERAL, TASK>(tab[blockIdx.y].a, tab[blockIdx.y].sc);
+// attributes, picked by the GROUP's wavefront count (rollout_point_build): same bits.  An entry type per variant, so that
+// handles with different weights or scenes share one launch and the entries of the other variants keep their size.
+template <class E>
+__device__ __forceinline__ const PointCostWeights* entry_weights(const E& e) {
+    if constexpr (E::weighted) return &e.wt;
+    else return nullptr;
 }
-template <bool GENERAL, int TASK>
-__global__ __launch_bounds__(64) void kb_rollout_point_ref(const BatchRolloutEntry* __restrict__ tab) {
-    constexpr PointScene sc = POINT_SCENE_REFERENCE;
-    rollout_point_body<GENERAL, TASK>(tab[blockIdx.y].a, sc);
+template <bool GENERAL, int TASK, bool REF, class E>
+__global__ __launch_bounds__(64) void kb_rollout_point(const E* __restrict__ tab) {
+    if constexpr (REF) {
+        constexpr PointScene sc = POINT_SCENE_REFERENCE;
+        rollout_point_body<GENERAL, TASK, true, E::weighted>(tab[blockIdx.y].a, sc, entry_weights(tab[blockIdx.y]));
+    } else {
+        rollout_point_body<GENERAL, TASK, true, E::weighted>(tab[blockIdx.y].a, tab[blockIdx.y].sc, entry_weights(tab[blockIdx.y]));
+    }
 }
-template <bool GENERAL, int TASK>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void kb_rollout_point_occ2(
-    const BatchRolloutEntry* __restrict__ tab) {
-    rollout_point_body<GENERAL, TASK, false>(tab[blockIdx.y].a, tab[blockIdx.y].sc);
-}
-template <bool GENERAL, int TASK>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void kb_rollout_point_occ3(
-    const BatchRolloutEntry* __restrict__ tab) {
-    rollout_point_body<GENERAL, TASK, false>(tab[blockIdx.y].a, tab[blockIdx.y].sc);
+template <int OCC, bool GENERAL, int TASK, class E>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void kb_rollout_point_occ(
+    const E* __restrict__ tab) {
+    rollout_point_body<GENERAL, TASK, false, E::weighted>(tab[blockIdx.y].a, tab[blockIdx.y].sc, entry_weights(tab[blockIdx.y]));
 }
 // blocks: workgroups of ONE handle (all handles of the group have the same); n: handles; ref: the group runs the
-// reference's solver settings
-template <bool GENERAL, int TASK>
-inline void launch_rollout_point_batch_instance(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s) {
-    const dim3 grid(blocks, n);
-    switch (rollout_point_build(blocks * n, ref)) {
-        case BUILD_OCC3: hipLaunchKernelGGL((kb_rollout_point_occ3<GENERAL, TASK>), grid, dim3(64), 0, s, tab); break;
-        case BUILD_OCC2: hipLaunchKernelGGL((kb_rollout_point_occ2<GENERAL, TASK>), grid, dim3(64), 0, s, tab); break;
-        case BUILD_LONE_REF: hipLaunchKernelGGL((kb_rollout_point_ref<GENERAL, TASK>), grid, dim3(64), 0, s, tab); break;
-        default: hipLaunchKernelGGL((kb_rollout_point<GENERAL, TASK>), grid, dim3(64), 0, s, tab); break;
+// reference's solver settings (never set for a scene type without a _ref build)
+template <bool GENERAL, int TASK, class E>
+inline void launch_rollout_point_batch_instance(const E* tab, int blocks, int n, bool ref, hipStream_t s) {
+    constexpr bool has_ref = scene_has_ref_build<decltype(E::sc)>;
+    const dim3 grid(blocks, n), wg(64);
+    switch (rollout_point_build(blocks * n, has_ref && ref)) {
+        case BUILD_OCC3: hipLaunchKernelGGL((kb_rollout_point_occ<3, GENERAL, TASK, E>), grid, wg, 0, s, tab); break;
+        case BUILD_OCC2: hipLaunchKernelGGL((kb_rollout_point_occ<2, GENERAL, TASK, E>), grid, wg, 0, s, tab); break;
+        case BUILD_LONE_REF:
+            if constexpr (has_ref) hipLaunchKernelGGL((kb_rollout_point<GENERAL, TASK, true, E>), grid, wg, 0, s, tab);
+            break;
+        default: hipLaunchKernelGGL((kb_rollout_point<GENERAL, TASK, false, E>), grid, wg, 0, s, tab); break;
     }
 }
 

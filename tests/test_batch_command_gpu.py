@@ -201,6 +201,26 @@ def test_multi_modal_group_larger_than_one_residency_chunk(twins, spins):
     assert rl == 1 and ul == math.ceil(n / (256 // 31))
 
 
+@pytest.mark.parametrize("counts", [(1, 1, 1), (3, 1, 2)])
+def test_all_three_variants_in_one_call(twins, counts):
+    """plain / tuned cost weights in the default arena / custom arena in ONE m3_batch_command: the table then holds all three
+    kinds of entry, with both alignment gaps between its sections (584-byte plain and 616-byte weighted entries: an odd number
+    of either leaves the next section 8 bytes further).  K = 128: two workgroups per handle.  Every handle's states, actions,
+    costs and plan (all of BUFS, m3_info) are the bits of its own twin's m3_command; one rollout launch per variant."""
+    from tests.point_scene_fixture import CUSTOM
+    kinds = [k for k, c in enumerate(counts) for _ in range(c)]
+    kinds = kinds[::-1][1:] + kinds[::-1][:1]   # (not in the order of the table's sections)
+    for i, kind in enumerate(kinds):
+        t = Twin(i, K=128, T=5, task="push", goal=(-1.0, -1.0), filter_u=False)   # (T = 5 is below the filter's window)
+        twins.append(t)
+        for e in t.engs:
+            if kind == 1:
+                e.set_point_cost_weights(dict(push_align=2.5, push_dist=1.5))
+            if kind == 2:
+                e.set_point_scene(CUSTOM)
+    assert _run(twins, calls=2)[0] == 3
+
+
 def _calls_and_mean(e):
     return e.info().calls, e.buffer(L.BUF_MEAN).cpu().numpy().tobytes()
 

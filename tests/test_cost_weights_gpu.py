@@ -101,7 +101,7 @@ def test_weighted_instance_at_default_weights_is_the_ordinary_command(twins):
 
 
 def test_weighted_batch_group_at_default_weights_is_the_ordinary_command(twins):
-    """... and the same through m3_batch_command: kb_rollout_point_w against each twin's own ordinary m3_command."""
+    """... and the same through m3_batch_command: the weighted kb_rollout_point against each twin's own ordinary m3_command."""
     twins += [_weights(Twin(i, **s), force_A=1) for i, s in enumerate(IDENTITY)]
     rl, _ = _run(twins, calls=6)
     assert rl == 4          # every forced handle runs the general weighted instance: groups by (K, T) only

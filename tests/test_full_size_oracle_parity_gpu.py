@@ -22,10 +22,10 @@ POINT = {
     "C5shard_hybrid_K8000": dict(K=8000, task="push_pull", goal=(-3.75, -3.75), mm=True),
     "C5_hybrid_K64000": dict(K=64000, task="push_pull", goal=(-3.75, -3.75), mm=True),
     # more wavefronts (1094) than the chip has SIMDs (1024): the two-waves-per-SIMD build of the rollout kernel
-    # (k_rollout_point_occ2: 256 VGPRs, ~175 values in scratch) -- same bits as the oracle
+    # (k_rollout_point_occ<2>: 256 VGPRs, ~175 values in scratch) -- same bits as the oracle
     "occ2_push_K70016": dict(K=70016, task="push", goal=(-1.0, -1.0), mm=False),
     "occ2_hybrid_K70016": dict(K=70016, task="push_pull", goal=(-3.75, -3.75), mm=True),
-    # more than four wavefronts per SIMD (8192 > 4096): the THREE-waves build (k_rollout_point_occ3: 170 VGPRs, the rest
+    # more than four wavefronts per SIMD (8192 > 4096): the THREE-waves build (k_rollout_point_occ<3>: 170 VGPRs, the rest
     # in scratch) and the saturated update (k_mins / k_ladder / k_search / k_apply_weights / k_wsum with the top-k
     # stage B) against the full oracle command -- every state, action, cost and J of the 524 288 rollouts bit for bit
     "occ3_push_K524288": dict(K=524288, task="push", goal=(-1.0, -1.0), mm=False, calls=2),

@@ -271,7 +271,7 @@ ARENA_EP = "point_scene={obs_x: 0.0, obs_y: 0.9, obs_hx: 0.3, obs_hy: 0.1, wall:
 
 def test_episodes_in_a_custom_arena_equal_the_serial_loop():
     """run_point_episodes with n = 4 (the arena on the world handle and, through planner._bind_world, on the four planners'
-    handles: kb_rollout_point_s + k_episodes_post_s) against the serial closed_loop.run loop, report and trace bit for bit"""
+    handles: kb_rollout_point on PointSceneRT + k_episodes_post_s) against the serial closed_loop.run loop, report and trace bit for bit"""
     import band_stats as bs
     import closed_loop
     from m3p2i_aip_amd.episodes import run_point_episodes

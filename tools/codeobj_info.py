@@ -40,7 +40,7 @@ def kernels(co):
             cur = {}
             res.append(cur)
         if cur is not None and k in ("agpr_count", "vgpr_count", "sgpr_count", "sgpr_spill_count", "vgpr_spill_count",
-                                     "group_segment_fixed_size", "private_segment_fixed_size", "name",
+                                     "group_segment_fixed_size", "private_segment_fixed_size", "kernarg_segment_size", "name",
                                      "max_flat_workgroup_size", "wavefront_size"):
             cur[k] = int(v) if re.fullmatch(r"-?\d+", v) else v
     return [k for k in res if "name" in k]

@@ -43,7 +43,7 @@ tools/pmc_rollout.sh final 2000 0 push > $O/pmc_final.txt 2>&1
 tools/pmc_rollout.sh pandaf 4000 0 reach > $O/pmc_panda.txt 2>&1
 # dynamic instruction mix of the rollout kernels (the thread-trace decoder is not in this image: tools/att_rollout.sh)
 tools/pmc_mix.sh push_K2000 2000 push > $O/pmc_mix_push.log 2>&1
-python tools/codeobj_info.py --isa "k_rollout_point<false, 1>" --json $O/codeobj_info.json > $O/codeobj_info.txt 2>&1
+python tools/codeobj_info.py --isa "k_rollout_point<false, 1," --json $O/codeobj_info.json > $O/codeobj_info.txt 2>&1
 # behaviour: N = 20 jittered episodes per scenario (tests/test_behaviour_band_gpu.py asserts on the first and the last)
 python tools/band_stats.py --n 20 --json $O/behaviour_stats_baseline.json > $O/behaviour_stats_baseline.log 2>&1
 python tools/band_stats.py --n 20 --size default --json $O/behaviour_stats_default_size.json > $O/behaviour_stats_default_size.log 2>&1
