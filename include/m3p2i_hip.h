@@ -400,8 +400,8 @@ int m3_set_point_scene_instance(m3_handle* h, int on);
  * running m3_episodes set, and m3_episodes_create accepts a world with rows set.  scenes == NULL clears the rows (n is not
  * read): the handle is back on its single scene and runs exactly the kernels it ran before.  Every row gets the checks of
  * m3_set_point_scene; a failing one is M3_ERR_BAD_ARG and the message names the row and the field ("row 2: box_m is not
- * finite").  A panda_env handle is M3_ERR_UNSUPPORTED, a handle that is not sim_only M3_ERR_STATE (a planner's rollouts share
- * one model: m3_set_point_scene), n != K_local M3_ERR_SHAPE.  Every check runs before any state changes: after a refusal the
+ * finite").  A panda_env handle is M3_ERR_UNSUPPORTED, a handle that is not sim_only M3_ERR_STATE (a planner's samples get
+ * their arenas from m3_set_point_rollout_scenes below), n != K_local M3_ERR_SHAPE.  Every check runs before any state changes: after a refusal the
  * rows and the single scene are what they were.
  * With m3_set_point_scene: the LAST call wins -- m3_set_point_scene on a handle with rows set clears the rows; while rows are
  * set m3_get_point_scene keeps returning the single scene (which no step reads), and m3_set_point_scene_instance(h, 0) refuses
@@ -413,11 +413,39 @@ int m3_set_point_scene_rows(m3_handle* h, const m3_point_scene* scenes, int n);
 /* row `row` as it was set; M3_ERR_STATE while no rows are set, M3_ERR_BAD_ARG for a row outside 0 .. K_local - 1 */
 int m3_get_point_scene_row(const m3_handle* h, int row, m3_point_scene* out);
 int m3_point_scene_rows_set(const m3_handle* h);   /* 0 / 1 */
+/* EXTENSION, point_env PLANNER handles (unsharded or sharded): one arena PER SAMPLE of the fused rollout -- sample i of the handle
+ * rolls out in scenes[i], so a planner can spread its K rollouts over K models of a world it knows only roughly (the reference
+ * gets this from a simulator with num_envs = K whose environments carry their own actor properties).  n must equal the
+ * handle's K_local.  Sample i is row i of every per-sample buffer (M3_BUF_TRAJ_COST[i], states[:, i], the pending force); its
+ * global index is k_offset + i.  The row follows the sample, not the wavefront slot: m3_set_wave_order, m3_relabel_samples
+ * and m3_set_rollout_lanes do not change which arena a sample gets.  dt, substeps, solver iterations and the solver constants
+ * stay the handle's.  Applies from the next m3_rollout / m3_command; survives m3_reset.  scenes == NULL clears the rows (n is
+ * not read): the handle is back on its single scene and launches exactly the kernels it launched before.
+ * Every row gets the checks of m3_set_point_scene; a failing one is M3_ERR_BAD_ARG and the message names the row and the field
+ * ("row 3: box_m is not finite").  A panda_env handle is M3_ERR_UNSUPPORTED, a sim_only handle M3_ERR_STATE (its environments:
+ * m3_set_point_scene_rows), n != K_local M3_ERR_SHAPE.  Every check runs before any state changes.
+ * With m3_set_point_scene: the LAST call wins, as on sim_only handles; m3_set_point_scene_instance(h, 0) with rows set refuses
+ * the next rollout (M3_ERR_STATE).
+ * While rows are set m3_rollout / m3_command run the per-sample build of the general, weighted rollout instance (all tasks,
+ * multi_modal, both mppi modes, both samplers, avoid_dyn_obs, update_cov; tuned cost weights keep working); the two-wavefront
+ * form is never taken (m3_point_rollout_form_used = 0); m3_point_rollout_plan(..., scene = 2, ...) reports the launch.
+ * The special samples are the caller's business: the zero-noise / null-action sample K - 1 and, in multi-modal mode, the two
+ * best-trajectory samples 0 and K / 2 get their rows like any other sample -- give them the nominal arena to keep them nominal.
+ * NOT batched: m3_batch_command with such a handle and m3_episodes_create / m3_episodes_tick with such a planner return
+ * M3_ERR_UNSUPPORTED (the message names this call and the index of the handle); nothing is launched.
+ * Memory: the first call on a handle allocates a device table, its pinned host mirror and a host copy of the rows; later calls
+ * reuse them (and wait for the handle's stream before they rewrite the mirror).  The upload is one hipMemcpyAsync on the
+ * handle's stream.  m3_rollout and m3_command allocate nothing because of the rows. */
+int m3_set_point_rollout_scenes(m3_handle* h, const m3_point_scene* scenes, int n);
+/* row `row` as it was set; M3_ERR_STATE while no rows are set, M3_ERR_BAD_ARG for a row outside 0 .. K_local - 1 */
+int m3_get_point_rollout_scene(const m3_handle* h, int row, m3_point_scene* out);
+int m3_point_rollout_scenes_set(const m3_handle* h);   /* 0 / 1 */
 /* Diagnostic, host only (no device call, no handle): the kernel form a point_env rollout with these settings takes -- what
  * m3_rollout / m3_batch_command would launch for a handle configured so.  weighted / scene: what the handle's cost weights and
  * scene (or their switches) amount to; form_request: m3_set_point_rollout_form's value; want_minima: the command keeps the
  * workgroups' cost minima.  out: instance (-1 general, 0..3 the task's), ref (solver settings compiled in), form (1: two
- * wavefronts), weighted, scene, workgroups, rows of minima, lanes. */
+ * wavefronts), weighted, scene, workgroups, rows of minima, lanes.  scene = 2: the handle has an arena per sample
+ * (m3_set_point_rollout_scenes): instance -1, ref 0, form 0, weighted 1, out[4] = 2. */
 int m3_point_rollout_plan(int task, int multi_modal, int mode_simple, int sampling_random, int avoid_dyn_obs, int K_local, int T,
                           int lanes, float dt, int substeps, int solver_iters, int weighted, int scene, int form_request,
                           int want_minima, int out[8]);

@@ -161,6 +161,9 @@ SYMBOLS = [
     ("m3_set_point_scene_rows", C.c_int, [_H, C.POINTER(PointSceneFields), C.c_int]),
     ("m3_get_point_scene_row", C.c_int, [_H, C.c_int, C.POINTER(PointSceneFields)]),
     ("m3_point_scene_rows_set", C.c_int, [_H]),
+    ("m3_set_point_rollout_scenes", C.c_int, [_H, C.POINTER(PointSceneFields), C.c_int]),
+    ("m3_get_point_rollout_scene", C.c_int, [_H, C.c_int, C.POINTER(PointSceneFields)]),
+    ("m3_point_rollout_scenes_set", C.c_int, [_H]),
     ("m3_point_rollout_plan", C.c_int, [C.c_int] * 8 + [C.c_float] + [C.c_int] * 6 + [C.POINTER(C.c_int)]),
     ("m3_set_multi_modal", C.c_int, [_H, C.c_int]),
     ("m3_set_plan", C.c_int, [_H, C.c_int, _FP]),

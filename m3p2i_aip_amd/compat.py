@@ -131,6 +131,11 @@ class ExampleConfig:
     world_point_scene: Optional[Dict[str, float]] = None   # EXTENSION, point_env: field overrides of the REAL world only, on top
                                                            # of point_scene (model mismatch: the planner and its K-env simulator
                                                            # keep point_scene); world_isaacgym_config applies it
+    rollout_arena_spread: Optional[Dict[str, object]] = None   # EXTENSION, point_env: `rollout_arena_spread={spread: 0.3, seed: 1,
+                                                               # fields: [box_m, box_mu_g, mu_rb]}` -- the planner's K rollouts
+                                                               # each in an arena of their own around point_scene (the samples
+                                                               # 0, K / 2 and K - 1 stay nominal); rollout_point_scenes builds
+                                                               # the rows the planner's K-env simulator carries
 
 
 def make_config(config_name="config_point", overrides=()):
@@ -176,7 +181,44 @@ def make_config(config_name="config_point", overrides=()):
         if cfg.env_type != "point_env":
             raise ValueError("world_point_scene: point_env only")
         cfg.world_point_scene = dict(cfg.world_point_scene)
+    if cfg.rollout_arena_spread:
+        cfg.rollout_arena_spread = dict(cfg.rollout_arena_spread)
+        _check_rollout_arena_spread(cfg)
     return cfg
+
+
+ROLLOUT_ARENA_SPREAD_KEYS = ("spread", "seed", "fields")
+
+
+def _check_rollout_arena_spread(cfg):
+    """the parsed `rollout_arena_spread` key as (spread, seed, fields); ValueError for what it cannot mean"""
+    given = dict(cfg.rollout_arena_spread)
+    if cfg.env_type != "point_env":
+        raise ValueError("rollout_arena_spread: point_env only")
+    unknown = sorted(set(given) - set(ROLLOUT_ARENA_SPREAD_KEYS))
+    if unknown or "spread" not in given:
+        raise ValueError(f"rollout_arena_spread: {{spread: S, seed: n, fields: [...]}} (unknown key(s) {unknown})")
+    spread = float(given["spread"])
+    if not 0.0 <= spread < 1.0:
+        raise ValueError(f"rollout_arena_spread: spread {spread!r} is not a share in [0, 1)")
+    fields = tuple(given.get("fields") or ("box_m", "box_mu_g", "mu_rb"))
+    return spread, int(given.get("seed", 0) or 0), fields
+
+
+def rollout_point_scenes(cfg, k_offset=0, n=None):
+    """The arenas of the planner's samples under the `rollout_arena_spread` key, or None without it: the rows
+    [k_offset, k_offset + n) (all K by default) of scenes.spread_point_scenes(K, spread, seed, base=point_scene, fields,
+    nominal_rows=(0, K // 2, K - 1)).  The planner's K-env simulator is built with them (IsaacGymWrapper(point_scenes=...));
+    the planner attached to it takes them over, so its fused path stays the step path on that simulator."""
+    if not getattr(cfg, "rollout_arena_spread", None):
+        return None
+    from . import scenes
+    spread, seed, fields = _check_rollout_arena_spread(cfg)
+    K = int(cfg.mppi.num_samples)
+    rows = scenes.spread_point_scenes(K, spread, seed, base=getattr(cfg, "point_scene", None), fields=fields,
+                                      nominal_rows=(0, K // 2, K - 1))
+    n = K - int(k_offset) if n is None else int(n)
+    return rows[int(k_offset):int(k_offset) + n]
 
 
 def world_point_scene(cfg):

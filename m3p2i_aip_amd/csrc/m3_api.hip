@@ -840,6 +840,39 @@ extern "C" int m3_set_point_scene(m3_handle* h, const m3_point_scene* sc) {
     std::memcpy(&h->point_scene, &src, sizeof(src));
     h->scene_rt = make_point_scene_rt(h->point_scene, h->cfg.dt, h->cfg.substeps, h->cfg.solver_iters);
     h->scene_rows_on = false;   // the last call wins: the handle is on its single scene (the rows' memory is kept for a later call)
+    h->rollout_scenes_on = false;
+    return M3_OK;
+}
+
+// The rows of a handle -- per environment (sim_only: m3_set_point_scene_rows) or per sample (planner:
+// m3_set_point_rollout_scenes) -- into its host copy, pinned mirror and device table: scenes are Kl checked rows.
+// THE allocation of both features: the first call on a handle; later calls reuse the three blocks (K_local is fixed at
+// m3_create).  m3_sim_step*, m3_episodes_tick / _begin / _end, m3_rollout and m3_command allocate nothing because of the rows --
+// they read scene_rows_dev and scene_rt, nothing else.
+static int upload_point_scene_rows(m3_handle* h, const m3_point_scene* scenes, const char* who) {
+    const int Kl = h->cfg.K_local;
+    const size_t table_bytes = (size_t)POINT_SCENE_ROW_WORDS * Kl * sizeof(float);
+    if (!h->scene_rows_dev) {
+        m3_point_scene* rows = static_cast<m3_point_scene*>(std::malloc((size_t)Kl * sizeof(m3_point_scene)));
+        float* host = nullptr;
+        float* dev = nullptr;
+        hipError_t e = rows ? hipSuccess : hipErrorOutOfMemory;
+        if (e == hipSuccess) e = hipHostMalloc((void**)&host, table_bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc((void**)&dev, table_bytes);
+        if (e != hipSuccess) {
+            if (host) (void)hipHostFree(host);
+            std::free(rows);
+            return fail(h, M3_ERR_HIP, (std::string(who) + ": " + hipGetErrorString(e)).c_str());
+        }
+        h->scene_rows = rows; h->scene_rows_host = host; h->scene_rows_dev = dev;
+    } else {
+        // the pinned mirror is the source of the previous call's asynchronous upload: that copy is over before it is rewritten
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    std::memcpy(h->scene_rows, scenes, (size_t)Kl * sizeof(m3_point_scene));
+    for (int i = 0; i < Kl; ++i)
+        point_scene_row_pack(make_point_scene_rt(scenes[i], h->cfg.dt, h->cfg.substeps, h->cfg.solver_iters), h->scene_rows_host, Kl, i);
+    HIPCHK(h, hipMemcpyAsync(h->scene_rows_dev, h->scene_rows_host, table_bytes, hipMemcpyHostToDevice, h->stream));
     return M3_OK;
 }
 
@@ -860,31 +893,8 @@ extern "C" int m3_set_point_scene_rows(m3_handle* h, const m3_point_scene* scene
         const std::string fault = point_scene_fault(scenes[i]);
         if (!fault.empty()) return fail(h, M3_ERR_BAD_ARG, ("m3_set_point_scene_rows: row " + std::to_string(i) + ": " + fault).c_str());
     }
-    const size_t table_bytes = (size_t)POINT_SCENE_ROW_WORDS * Kl * sizeof(float);
-    // THE allocation of this feature: the first call on a handle; later calls reuse the three blocks (K_local is fixed at
-    // m3_create).  m3_sim_step*, m3_episodes_tick / _begin / _end allocate nothing because of the rows -- they read
-    // scene_rows_dev and scene_rt, nothing else.
-    if (!h->scene_rows_dev) {
-        m3_point_scene* rows = static_cast<m3_point_scene*>(std::malloc((size_t)Kl * sizeof(m3_point_scene)));
-        float* host = nullptr;
-        float* dev = nullptr;
-        hipError_t e = rows ? hipSuccess : hipErrorOutOfMemory;
-        if (e == hipSuccess) e = hipHostMalloc((void**)&host, table_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void**)&dev, table_bytes);
-        if (e != hipSuccess) {
-            if (host) (void)hipHostFree(host);
-            std::free(rows);
-            return fail(h, M3_ERR_HIP, (std::string("m3_set_point_scene_rows: ") + hipGetErrorString(e)).c_str());
-        }
-        h->scene_rows = rows; h->scene_rows_host = host; h->scene_rows_dev = dev;
-    } else {
-        // the pinned mirror is the source of the previous call's asynchronous upload: that copy is over before it is rewritten
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    std::memcpy(h->scene_rows, scenes, (size_t)Kl * sizeof(m3_point_scene));
-    for (int i = 0; i < Kl; ++i)
-        point_scene_row_pack(make_point_scene_rt(scenes[i], h->cfg.dt, h->cfg.substeps, h->cfg.solver_iters), h->scene_rows_host, Kl, i);
-    HIPCHK(h, hipMemcpyAsync(h->scene_rows_dev, h->scene_rows_host, table_bytes, hipMemcpyHostToDevice, h->stream));
+    const int rc = upload_point_scene_rows(h, scenes, "m3_set_point_scene_rows");
+    if (rc != M3_OK) return rc;
     h->scene_rows_on = true;
     return M3_OK;
 }
@@ -899,6 +909,40 @@ extern "C" int m3_get_point_scene_row(const m3_handle* h, int row, m3_point_scen
 }
 
 extern "C" int m3_point_scene_rows_set(const m3_handle* h) { return h ? (h->scene_rows_on ? 1 : 0) : M3_ERR_BAD_ARG; }
+
+// One arena per sample of a planner handle's fused rollout.  Every check before any state changes.
+extern "C" int m3_set_point_rollout_scenes(m3_handle* h, const m3_point_scene* scenes, int n) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_point_rollout_scenes: point_env only");
+    if (h->cfg.sim_only)
+        return fail(h, M3_ERR_STATE, "m3_set_point_rollout_scenes: planner handles only (the environments of a sim_only handle: m3_set_point_scene_rows)");
+    if (!scenes) {   // back on the single scene: exactly the kernels of a handle that never had rows (n is not read)
+        h->rollout_scenes_on = false;
+        return M3_OK;
+    }
+    const int Kl = h->cfg.K_local;
+    if (n != Kl)
+        return fail(h, M3_ERR_SHAPE, ("m3_set_point_rollout_scenes: n is " + std::to_string(n) + ", the handle's K_local " + std::to_string(Kl)).c_str());
+    for (int i = 0; i < n; ++i) {
+        const std::string fault = point_scene_fault(scenes[i]);
+        if (!fault.empty()) return fail(h, M3_ERR_BAD_ARG, ("m3_set_point_rollout_scenes: row " + std::to_string(i) + ": " + fault).c_str());
+    }
+    const int rc = upload_point_scene_rows(h, scenes, "m3_set_point_rollout_scenes");
+    if (rc != M3_OK) return rc;
+    h->rollout_scenes_on = true;
+    return M3_OK;
+}
+
+extern "C" int m3_get_point_rollout_scene(const m3_handle* h, int row, m3_point_scene* out) {
+    if (!h || !out) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_POINT) return M3_ERR_UNSUPPORTED;
+    if (!h->rollout_scenes_on) return M3_ERR_STATE;
+    if (row < 0 || row >= h->cfg.K_local) return M3_ERR_BAD_ARG;
+    std::memcpy(out, &h->scene_rows[row], sizeof(*out));
+    return M3_OK;
+}
+
+extern "C" int m3_point_rollout_scenes_set(const m3_handle* h) { return h ? (h->rollout_scenes_on ? 1 : 0) : M3_ERR_BAD_ARG; }
 
 extern "C" int m3_get_point_scene(const m3_handle* h, m3_point_scene* out) {
     if (!h || !out) return M3_ERR_BAD_ARG;
@@ -928,7 +972,9 @@ enum PointSide { SIDE_COST = 1, SIDE_STEP = 2, SIDE_ROLLOUT = SIDE_COST | SIDE_S
 // arena is no input of the cost, so never POINT_SCENE)
 static PointVariant point_variant(const m3_handle* h, PointSide side) {
     if (h->cfg.env_type != M3_ENV_POINT) return POINT_PLAIN;
-    if ((side & SIDE_STEP) && (h->scene_instance < 0 ? !default_point_scene(h) : h->scene_instance != 0)) return POINT_SCENE;
+    // (per-sample arenas are the run-time-scene variant of the rollout; a planner handle's own step keeps its single scene)
+    const bool rows = side == SIDE_ROLLOUT && h->rollout_scenes_on;
+    if ((side & SIDE_STEP) && (h->scene_instance < 0 ? (rows || !default_point_scene(h)) : h->scene_instance != 0)) return POINT_SCENE;
     return (h->weighted_instance < 0 ? !default_cost_weights(h) : h->weighted_instance != 0) ? POINT_WEIGHTED : POINT_PLAIN;
 }
 // the variant of the step-mode kernels (m3_sim_step, the episode tick): the arena compiled in, the handle's arena a kernel
@@ -945,6 +991,8 @@ static const char* point_variant_refusal(const m3_handle* h, PointSide side) {
         return "the weighted cost instance is forced off (m3_set_weighted_cost_instance 0) but the handle's cost weights are not the defaults";
     if ((side & SIDE_STEP) && h->scene_instance == 0 && h->scene_rows_on)
         return "the run-time-scene instance is forced off (m3_set_point_scene_instance 0) but the handle has an arena per environment (m3_set_point_scene_rows)";
+    if (side == SIDE_ROLLOUT && h->scene_instance == 0 && h->rollout_scenes_on)
+        return "the run-time-scene instance is forced off (m3_set_point_scene_instance 0) but the handle has an arena per sample (m3_set_point_rollout_scenes)";
     if ((side & SIDE_STEP) && h->scene_instance == 0 && !default_point_scene(h))
         return "the run-time-scene instance is forced off (m3_set_point_scene_instance 0) but the handle's scene is not the default";
     return nullptr;
@@ -1194,7 +1242,8 @@ static int plan_rollout(m3_handle* h, RolloutArgs& a, PandaArgs& pa, RolloutPlan
     if (rc != M3_OK) return rc;
     if (h->cfg.env_type == M3_ENV_POINT) {
         // (the two-wavefront form: m3_rollout's own launch only, and only with the error word to report into)
-        p = plan_rollout_point(a, h->scene, point_variant(h, SIDE_ROLLOUT), (own_launch && h->rollout_err_dev) ? h->point_form : 0);
+        p = plan_rollout_point(a, h->scene, point_variant(h, SIDE_ROLLOUT), (own_launch && h->rollout_err_dev) ? h->point_form : 0,
+                               h->rollout_scenes_on);
     } else {
         fill_panda_args(h, a, pa);
         p = plan_rollout_panda(a, pa);
@@ -1218,7 +1267,7 @@ extern "C" int m3_rollout(m3_handle* h) {
     if (rc != M3_OK) return rc;
     if (h->cfg.env_type == M3_ENV_POINT) h->point_form_used = p.form;
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->scene_rt, h->cost_weights, p, h->stream, h->rollout_err_dev);
+    if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->scene_rt, h->cost_weights, p, h->stream, h->rollout_err_dev, h->scene_rows_dev);
     else launch_rollout_panda(a, pa, h->pscene, p, h->stream);
     HIPCHK(h, hipGetLastError());
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
@@ -1907,6 +1956,10 @@ static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code) {
     code = M3_ERR_STATE;
     if (c.K_local != c.K_global) return "sharded handle (K_local != K_global)";
     if (c.sim_only) return "handle was created sim_only";
+    if (h->rollout_scenes_on) {   // (the batched form would be a fourth section of the table: not built)
+        code = M3_ERR_UNSUPPORTED;
+        return "it has an arena per sample (m3_set_point_rollout_scenes), which only m3_rollout / m3_command run";
+    }
     if (const char* why = rollout_refusal(h)) return why;
     fill_update_impl_args(h, u, true);
     code = M3_ERR_UNSUPPORTED;
@@ -2461,6 +2514,10 @@ extern "C" int m3_episodes_tick(m3_episodes* eps, m3_batch* batch) {
     for (int i = 0; i < eps->n; ++i) {
         if (eps->host[i].done_tick >= 0) continue;
         m3_handle* h = eps->planners[i];
+        if (h->rollout_scenes_on) {   // (set after m3_episodes_create, which refuses it: nothing of this tick is launched)
+            eps->err = "m3_episodes_tick: planner " + std::to_string(i) + ": it has an arena per sample (m3_set_point_rollout_scenes), which only m3_rollout / m3_command run";
+            return M3_ERR_UNSUPPORTED;
+        }
         // (f) planner i reads row i of the world: the rollout takes row 0 of its bound views
         // (rollout_point_kernel.hpp), so it sees the floats closed_loop.run copies into its K-env sim
         rc = m3_bind_sim_point(h, w->views.dof_state + (size_t)i * 4, w->views.root_state + (size_t)i * w->views.n_actors * 13,

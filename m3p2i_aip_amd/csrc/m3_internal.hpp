@@ -214,11 +214,14 @@ struct RolloutPlan {
     int form;            // point_env: 0 one wavefront per 64 samples, 1 dynamics + companion wavefront (rollout_point_kernel.hpp:
                          // rollout_point_body2); m3_rollout only -- the batched and episode paths plan with form_request 0
     int scene;           // point_env: the run-time-scene build of the general instance (POINT_SCENE; instance == -1,
-                         // weighted == 1, ref == 0, form == 0)
+                         // weighted == 1, ref == 0, form == 0); 2: its per-sample twin (m3_set_point_rollout_scenes) -- a
+                         // property of the single-handle launch, no variant of its own and no section of the batch table
 };
 inline PointVariant point_variant(const RolloutPlan& p) { return p.scene ? POINT_SCENE : p.weighted ? POINT_WEIGHTED : POINT_PLAIN; }
 // form_request: m3_set_point_rollout_form's value (0 one wavefront, 1 two wherever available, -1 by rollout_companion_pays)
-RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, PointVariant variant, int form_request = 0);
+// per_sample: the handle carries one arena per sample (variant POINT_SCENE then): RolloutPlan::scene = 2
+RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, PointVariant variant, int form_request = 0,
+                               bool per_sample = false);
 // one launch of the plan's instance for n handles of K_local = a.Kl and the same plan (tab: device, n entries of the type of
 // the plan's variant)
 void launch_rollout_point_batch(const void* tab, int n, const RolloutPlan& p, hipStream_t s);
@@ -229,8 +232,13 @@ void launch_rollout_point_pushpull_batch(const BatchRolloutEntry* tab, int block
 
 // ---- launchers (defined in the .hip files) ---------------------------------------------
 // one handle's launch of the plan; the plan's variant says which of sc / rt and whether wt is read
+// scene_rows: p.scene == 2 only -- the handle's table of per-sample arenas (point_scene_rows.hpp), rt then its uniform members
 void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const PointSceneRT& rt, const PointCostWeights& wt,
-                          const RolloutPlan& p, hipStream_t s, int* err = nullptr /* p.form == 1: the hand-over's error word */);
+                          const RolloutPlan& p, hipStream_t s, int* err = nullptr /* p.form == 1: the hand-over's error word */,
+                          const float* scene_rows = nullptr);
+// ... of a planner handle with an arena per sample (rollout_point_rollout_scenes.hip; uni, rows: point_scene_rows.hpp)
+void launch_rollout_point_sv(const RolloutArgs& a, const PointSceneRT& uni, const float* rows, const PointCostWeights& wt,
+                             int blocks, hipStream_t s);
 // the two-wavefront form of the navigation / push instances (p.form == 1)
 void launch_rollout_point_nav2(const RolloutArgs& a, const PointScene& sc, int blocks, int* err, hipStream_t s);
 void launch_rollout_point_push2(const RolloutArgs& a, const PointScene& sc, int blocks, int* err, hipStream_t s);
@@ -448,6 +456,10 @@ struct m3_handle {
     // m3_set_point_scene_rows (extension, sim_only point_env): one arena per environment; survive m3_reset.  All three are
     // allocated by the first m3_set_point_scene_rows on the handle and freed by m3_destroy; nothing else allocates them.
     bool scene_rows_on = false;        // the step and the episode tick take the per-row kernels
+    // m3_set_point_rollout_scenes (extension, point_env planner handles): one arena per sample of the fused rollout; survive
+    // m3_reset.  A handle is a planner or sim_only for life, so the rows live in the same three blocks, allocated by the first
+    // m3_set_point_rollout_scenes on the handle.
+    bool rollout_scenes_on = false;    // m3_rollout / m3_command take the per-sample kernels
     m3_point_scene* scene_rows = nullptr;   // host [Kl]: what was set (m3_get_point_scene_row)
     float* scene_rows_host = nullptr;  // pinned host [POINT_SCENE_ROW_WORDS][Kl]: the table as uploaded (point_scene_rows.hpp)
     float* scene_rows_dev = nullptr;   // device, the same

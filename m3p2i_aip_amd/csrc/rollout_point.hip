@@ -27,11 +27,12 @@ int rollout_lanes_for(int Kl) {
 // exists, -1 where rollout_companion_pays as well, 0 never (m3_batch_command, the episode paths).
 // variant POINT_SCENE: the handle's arena is not the default (or the run-time-scene build is forced on): the general instance on
 // PointSceneRT, which always takes the weights as well -- instance -1, form 0, ref 0, whatever the sampler, the task and the weights.
-RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, PointVariant variant, int form_request) {
+// per_sample: the same build with the arena of each lane read from the handle's table (m3_set_point_rollout_scenes): scene = 2.
+RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, PointVariant variant, int form_request, bool per_sample) {
     const bool weighted = variant != POINT_PLAIN;
     if (variant == POINT_SCENE) {
         RolloutPlan p{};
-        p.scene = 1; p.weighted = 1;
+        p.scene = per_sample ? 2 : 1; p.weighted = 1;
         p.instance = -1; p.ref = 0; p.form = 0;
         p.lanes = a.lanes;
         p.blocks = (a.Kl + a.lanes - 1) / a.lanes;
@@ -63,9 +64,12 @@ RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, Point
 }
 
 void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const PointSceneRT& rt, const PointCostWeights& wt,
-                          const RolloutPlan& p, hipStream_t s, int* err) {
+                          const RolloutPlan& p, hipStream_t s, int* err, const float* scene_rows) {
     switch (point_variant(p)) {
-        case POINT_SCENE: launch_rollout_point_instance<true, -1>(a, rt, p.blocks, s, wt); return;
+        case POINT_SCENE:
+            if (p.scene == 2) launch_rollout_point_sv(a, rt, scene_rows, wt, p.blocks, s);
+            else launch_rollout_point_instance<true, -1>(a, rt, p.blocks, s, wt);
+            return;
         case POINT_WEIGHTED: launch_rollout_point_instance<true, -1>(a, sc, p.blocks, s, wt); return;
         default: break;
     }
@@ -332,8 +336,9 @@ extern "C" int m3_point_rollout_plan(int task, int multi_modal, int mode_simple,
     a.wave_min = want_minima ? minima_stand_in : nullptr;   // (only tested against null)
     m3::PointScene sc;
     m3::make_point_scene(sc, dt, substeps, solver_iters);
+    if (scene < 0 || scene > 2) return M3_ERR_BAD_ARG;
     const m3::PointVariant variant = scene ? m3::POINT_SCENE : weighted ? m3::POINT_WEIGHTED : m3::POINT_PLAIN;
-    const m3::RolloutPlan p = m3::plan_rollout_point(a, sc, variant, form_request);
+    const m3::RolloutPlan p = m3::plan_rollout_point(a, sc, variant, form_request, scene == 2);
     out[0] = p.instance; out[1] = p.ref; out[2] = p.form; out[3] = p.weighted; out[4] = p.scene; out[5] = p.blocks;
     out[6] = p.rows; out[7] = p.lanes;
     return M3_OK;

@@ -298,6 +298,34 @@ class HipEngine:
     def point_scene_rows_set(self):
         return self.lib.m3_point_scene_rows_set(self._h) == 1
 
+    def set_point_rollout_scenes(self, rows=None):
+        """Extension, point_env planner engines: one arena per SAMPLE of the fused rollout -- rows[i] the field overrides of
+        local sample i (global k_offset + i) over _lib.POINT_SCENE_DEFAULTS (None: the reference's arena); len(rows) ==
+        K_local.  rows=None clears: the engine is back on its single scene.  Applies from the next rollout / command;
+        set_point_scene afterwards clears the rows.  The special samples (K - 1; multi-modal: 0 and K / 2) get their rows like
+        any other: scenes.spread_point_scenes keeps them nominal."""
+        if rows is None:
+            self._ck(self.lib.m3_set_point_rollout_scenes(self._h, None, 0))
+            return
+        rows = list(rows)
+        arr = (L.PointSceneFields * max(len(rows), 1))()
+        for i, fields in enumerate(rows):
+            fields = dict(fields or {})
+            unknown = sorted(set(fields) - set(L.POINT_SCENE_DEFAULTS))
+            if unknown:
+                raise ValueError(f"row {i}: unknown point scene field(s) {unknown}: one of {list(L.POINT_SCENE_DEFAULTS)}")
+            arr[i] = L.PointSceneFields(**{**L.POINT_SCENE_DEFAULTS, **{k: float(v) for k, v in fields.items()}})
+        self._ck(self.lib.m3_set_point_rollout_scenes(self._h, arr, len(rows)))
+
+    def point_rollout_scene(self, i):
+        """local sample i's arena as set by set_point_rollout_scenes (all fields)"""
+        sc = L.PointSceneFields()
+        self._ck(self.lib.m3_get_point_rollout_scene(self._h, int(i), C.byref(sc)))
+        return {n: getattr(sc, n) for n in L.POINT_SCENE_DEFAULTS}
+
+    def point_rollout_scenes_set(self):
+        return self.lib.m3_point_rollout_scenes_set(self._h) == 1
+
     def set_point_scene_instance(self, on=-1):
         """-1: the run-time-scene kernels exactly when the scene is not the default (default); 1 / 0 forced (tests, A/B)."""
         self._ck(self.lib.m3_set_point_scene_instance(self._h, int(on)))

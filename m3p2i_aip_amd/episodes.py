@@ -213,6 +213,9 @@ def build_set(episodes, max_ticks=800, trace=False):
         cfg = compat.make_config(cn, list(ov))
         if cfg.env_type != "point_env":
             raise ValueError(f"run_point_episodes: episode {idx} is {cfg.env_type} (point_env only)")
+        if getattr(cfg, "rollout_arena_spread", None):
+            raise ValueError(f"run_point_episodes: episode {idx} asks for an arena per sample (rollout_arena_spread), which the "
+                             "batched command does not run (m3_set_point_rollout_scenes: m3_command only); use closed_loop.run")
         items.append((cn, list(ov), cfg, jitter))
     return PointEpisodeSet(items, max_ticks, trace)
 
@@ -231,6 +234,9 @@ def run_point_episodes(episodes, max_ticks=800, trace=False):
         cfg = compat.make_config(cn, list(ov))
         if cfg.env_type != "point_env":
             raise ValueError(f"run_point_episodes: episode {idx} is {cfg.env_type} (point_env only)")
+        if getattr(cfg, "rollout_arena_spread", None):
+            raise ValueError(f"run_point_episodes: episode {idx} asks for an arena per sample (rollout_arena_spread), which the "
+                             "batched command does not run (m3_set_point_rollout_scenes: m3_command only); use closed_loop.run")
         key = (float(cfg.isaacgym.dt), int(cfg.isaacgym.substeps), cfg.mppi.device)
         groups.setdefault(key, []).append((idx, (cn, list(ov), cfg, jitter)))
     out = [None] * len(episodes)

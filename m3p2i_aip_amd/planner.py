@@ -377,9 +377,31 @@ class MPPI():
         # from what this planner pushed last, which also overwrites an arena set by hand on self._engine.  A planner whose
         # model is to differ from its world on purpose sets `planner.follow_sim_scene = False` and owns its engine's arena.
         arena = getattr(s, "point_scene", None)
-        if getattr(self, "follow_sim_scene", True) and arena != getattr(self, "_point_scene_pushed", None):
+        follow = getattr(self, "follow_sim_scene", True)
+        arena_pushed = False
+        if follow and arena != getattr(self, "_point_scene_pushed", None):
             self._engine.set_point_scene(arena)
             self._point_scene_pushed = None if arena is None else dict(arena)
+            arena_pushed = True
+        # (extension, off by default) one arena per SAMPLE: the fused rollout is the step path on a wrapper whose K_local
+        # environments carry their own arenas (IsaacGymWrapper(point_scenes=...)), so while the planner follows its wrapper it
+        # takes those rows over -- once, and again when the wrapper holds another list (or the single arena was pushed, which
+        # clears the library's rows: the last call wins there).  Rows set by hand (set_rollout_scenes) stand wherever no
+        # wrapper's rows are followed.
+        if self.env_type == "point_env":
+            rows = self._followed_sim_rows()
+            if rows is not None:
+                if arena_pushed or not self._same_rows(rows, getattr(self, "_sim_rows_pushed", None)):
+                    self._engine.set_point_rollout_scenes(rows)
+                    self._sim_rows_pushed = rows
+            else:
+                was_following = getattr(self, "_sim_rows_pushed", None) is not None
+                self._sim_rows_pushed = None
+                mine = getattr(self, "_rollout_scenes", None)
+                if mine is not None and (arena_pushed or was_following):
+                    self._engine.set_point_rollout_scenes(mine[self.k_offset:self.k_offset + self.K_local])
+                elif was_following:
+                    self._engine.set_point_rollout_scenes(None)
         if getattr(self, "_bound_sim", None) is not s:
             if self.env_type == "point_env":
                 self._engine.bind_sim_point(s._dof_state, s._root_state,
@@ -391,6 +413,45 @@ class MPPI():
                                             scenes.actor_index(self.env_type, "cubeB"),
                                             scenes.actor_index(self.env_type, "dyn-obs"))
             self._bound_sim = s
+
+    @staticmethod
+    def _same_rows(a, b):
+        """the same list object (the common case, no work per command), or equal rows"""
+        return a is b or (b is not None and len(a) == len(b) and all(x == y for x, y in zip(a, b)))
+
+    def _followed_sim_rows(self):
+        """the per-environment arenas of the attached wrapper this planner's samples take over, or None: only while
+        follow_sim_scene holds and the wrapper has one environment per local sample"""
+        s = self._sim
+        rows = getattr(s, "point_scenes", None) if s is not None else None
+        if rows is None or not getattr(self, "follow_sim_scene", True) or getattr(s, "num_envs", None) != self.K_local:
+            return None
+        return rows
+
+    @property
+    def has_rollout_scenes(self):
+        """the fused rollout runs (or, from its next command on, will run) one arena per sample"""
+        return self.env_type == "point_env" and (getattr(self, "_rollout_scenes", None) is not None
+                                                 or self._followed_sim_rows() is not None)
+
+    def set_rollout_scenes(self, rows):
+        """Extension, point_env: one arena per sample of the fused rollout (m3_set_point_rollout_scenes) -- `rows` the GLOBAL
+        list of K field-override dicts (None entries: the reference's arena), of which this planner pushes its shard's slice;
+        None clears.  scenes.spread_point_scenes builds such a list with the special samples kept nominal.  A wrapper with
+        `point_scenes` that this planner follows (follow_sim_scene) overrides rows set here."""
+        if self.env_type != "point_env":
+            raise ValueError("set_rollout_scenes: point_env only")
+        if rows is None:
+            self._rollout_scenes = None
+            self._sim_rows_pushed = None      # (a followed wrapper's rows are pushed again by the next command)
+            self._engine.set_point_rollout_scenes(None)
+            return
+        rows = list(rows)
+        if len(rows) != self.K:
+            raise ValueError(f"set_rollout_scenes: {len(rows)} rows for num_samples = {self.K} (the global list)")
+        self._engine.set_point_rollout_scenes(rows[self.k_offset:self.k_offset + self.K_local])
+        self._rollout_scenes = rows
+        self._sim_rows_pushed = None
 
     def _exchange(self, phase):
         if self.collective is None:
@@ -613,6 +674,9 @@ def command_batch(planners, states):
             raise ValueError(f"command_batch: planner {i} runs in step mode (user dynamics / running_cost callables)")
         if p.world_size > 1 or p.collective is not None:
             raise ValueError(f"command_batch: planner {i} is sharded or has collectives installed")
+        if p.has_rollout_scenes:
+            raise ValueError(f"command_batch: planner {i} has an arena per sample (set_rollout_scenes / a wrapper with "
+                             "point_scenes): m3_batch_command does not run those, use planner.command")
         if not isinstance(p._engine, HipEngine):
             raise ValueError(f"command_batch: planner {i} does not run on the HIP library")
     if len({id(p) for p in planners}) != len(planners):

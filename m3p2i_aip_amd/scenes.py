@@ -156,3 +156,36 @@ def point_scene_from_actors(actors) -> dict:
             v = lit
         out[n] = v
     return out
+
+
+def spread_point_scenes(n, spread, seed=0, base=None, fields=("box_m", "box_mu_g", "mu_rb"), nominal_rows=()):
+    """n arenas around `base` (field overrides over _lib.POINT_SCENE_DEFAULTS; None: the reference's arena), as override dicts for
+    HipEngine.set_point_rollout_scenes / set_point_scene_rows / IsaacGymWrapper(point_scenes=...): each field of `fields` is
+    base's value times a factor uniform in [1 - spread, 1 + spread]; box_I scales with box_m and dyn_I with dyn_m (the shape
+    stays, as tools/band_stats.world_arena_of does it).  Row i depends on (seed, i) only, so a shard's rows are the slice of
+    the global list.  Rows in `nominal_rows` are `base` unchanged -- a planner keeps its special samples (K - 1; multi-modal: 0
+    and K / 2) on its nominal model that way."""
+    import numpy as np
+    from ._lib import POINT_SCENE_DEFAULTS
+    spread = float(spread)
+    if not 0.0 <= spread < 1.0:
+        raise ValueError(f"spread_point_scenes: spread {spread!r} is not a share in [0, 1)")
+    base = dict(base or {})
+    fields = tuple(fields)
+    unknown = sorted((set(base) | set(fields)) - set(POINT_SCENE_DEFAULTS))
+    if unknown:
+        raise ValueError(f"spread_point_scenes: unknown point scene field(s) {unknown}: one of {list(POINT_SCENE_DEFAULTS)}")
+    full = {**POINT_SCENE_DEFAULTS, **{k: float(v) for k, v in base.items()}}
+    follows = {"box_m": "box_I", "dyn_m": "dyn_I"}
+    nominal = {int(i) % int(n) for i in nominal_rows} if n else set()
+    rows = []
+    for i in range(int(n)):
+        row = dict(base)
+        if i not in nominal and fields:
+            f = np.random.default_rng([int(seed), i]).uniform(1.0 - spread, 1.0 + spread, len(fields))
+            for name, fac in zip(fields, f):
+                row[name] = full[name] * float(fac)
+                if name in follows and follows[name] not in fields:
+                    row[follows[name]] = full[follows[name]] * float(fac)
+        rows.append(row)
+    return rows
