@@ -130,6 +130,13 @@ inline float point_bounding_radius(float hx, float hy) {
     return f + POINT_RAD_MARGIN;
 }
 
+// spec v1.8: floor of the linear ground-friction limit, 2^-63 = sqrt(smallest normal binary32 number).  The friction row's disc
+// clamp selects Llin * spec_rsqrt(mag2) where mag2 > Llin^2, and spec_rsqrt of a SUBNORMAL mag2 is not finite (its second Newton
+// step squares y ~ 2e19): a limit whose square underflows -- a ground friction of 0, a coupling factor of ~1e-20 -- let one
+// through, and 0 * inf was NaN in every word of a box that had come to rest against a wall.  With the floor a selected mag2 is
+// above 2^-126.  (An impulse of 1e-19 N s: a body without ground friction keeps every bit of a velocity above ~1e-12 m/s.)
+constexpr float POINT_LLIN_FLOOR = 0x1p-63f;
+
 // Host side (m3_set_point_scene, the host build in tests/native/): the derived constants in binary32 in exactly the order the
 // oracle forms them (oracle/planar_world.c, m3o_point_step); g, the drive constants and the solver constants are not part of
 // m3_point_scene and keep the values of point_scene_for / PointScene.
@@ -147,8 +154,10 @@ inline PointSceneRT make_point_scene_rt(const m3_point_scene& p, float dt, int s
     s.gam = 1.0f / (h * 600.0f);
     s.md = 1.0f / (s.invm_r + s.gam);
     s.dmax = 1000.0f * h;
-    s.LlinB = ((p.box_mu_g * p.box_m) * g) * h; s.LangB = s.LlinB * p.box_req;
-    s.LlinD = ((p.dyn_mu_g * p.dyn_m) * g) * h; s.LangD = s.LlinD * p.dyn_req;
+    s.LlinB = ((p.box_mu_g * p.box_m) * g) * h; if (s.LlinB < POINT_LLIN_FLOOR) s.LlinB = POINT_LLIN_FLOOR;   // spec v1.8
+    s.LangB = s.LlinB * p.box_req;
+    s.LlinD = ((p.dyn_mu_g * p.dyn_m) * g) * h; if (s.LlinD < POINT_LLIN_FLOOR) s.LlinD = POINT_LLIN_FLOOR;
+    s.LangD = s.LlinD * p.dyn_req;
     s.RcB = 1.5f * p.box_req; s.RcD = 1.5f * p.dyn_req;
     s.obs_x = p.obs_x; s.obs_y = p.obs_y; s.obs_hx = p.obs_hx; s.obs_hy = p.obs_hy;
     s.wall = p.wall;
@@ -607,6 +616,7 @@ __device__ __forceinline__ void solve_ground_friction_row(const SC& sc, Vel& v, 
     {   // disc clamp as a select: a body that moves is almost always sliding (saturated), so the
         // sqrt + divide chain is on the path anyway and the exec-mask region around it only
         // added its ~40-cycle turnaround; unused lanes' inf / NaN are discarded by the select
+        // (spec v1.8: Llin >= POINT_LLIN_FLOOR, so a selected mag2 is a normal number and its spec_rsqrt finite)
         const float scl = Llin * spec_rsqrt(mag2);
         const bool sat = mag2 > Llin * Llin;
         nlx = sat ? nlx * scl : nlx;
@@ -836,12 +846,12 @@ __device__ __forceinline__ void point_substep(const SC& sc, PointWorld& w, float
     if (__builtin_amdgcn_ballot_w64(((__float_as_uint(v.bvx) | __float_as_uint(v.bvy) | __float_as_uint(v.bw)) & 0x7f800000u) != 0u) != 0ull) {
         float cl, ca;
         friction_coupling<PRED>(v.bvx, v.bvy, v.bw, sc.RcB, cl, ca);
-        LlinBe = sc.LlinB * cl; LangBe = sc.LangB * ca;
+        LlinBe = fmaxf(sc.LlinB * cl, POINT_LLIN_FLOOR); LangBe = sc.LangB * ca;   // (spec v1.8: the floor)
     }
     if (__builtin_amdgcn_ballot_w64(((__float_as_uint(v.dvx) | __float_as_uint(v.dvy) | __float_as_uint(v.dw)) & 0x7f800000u) != 0u) != 0ull) {
         float cl, ca;
         friction_coupling<PRED>(v.dvx, v.dvy, v.dw, sc.RcD, cl, ca);
-        LlinDe = sc.LlinD * cl; LangDe = sc.LangD * ca;
+        LlinDe = fmaxf(sc.LlinD * cl, POINT_LLIN_FLOOR); LangDe = sc.LangD * ca;
     }
     // A body that no slot of this instance touches and that is at rest now stays at rest for the
     // whole substep (its friction row is a no-op at rest), so its per-pass rest test -- an exec-mask

@@ -1,7 +1,7 @@
 /*
  * planar_world.c -- CPU ORACLE (test infrastructure, NOT product code).
  *
- * Independent scalar implementation of the "Planar contact dynamics spec" (currently v1.4).
+ * Independent scalar implementation of the "Planar contact dynamics spec" (currently v1.8).
  * It stands where the reference calls Isaac Gym / PhysX (closed binary):
  *   IsaacGymWrapper.step()                      isaacgym_wrapper.py:354-360
  *   set_dof_velocity_target_tensor()            isaacgym_wrapper.py:196
@@ -375,6 +375,13 @@ static inline int is_zero(float x) {
 
 typedef struct { float lx, ly, la; } fric_acc;
 
+/* spec v1.8: floor of the linear ground-friction limit, 2^-63 = sqrt(smallest normal binary32 number).  The disc clamp below
+ * forms Llin * spec_rsqrt(mag2) where mag2 > Llin^2, and spec_rsqrt of a SUBNORMAL mag2 is not finite (its second Newton step
+ * squares y ~ 2e19): a limit whose square underflows -- a ground friction of 0, a coupling factor of ~1e-20 -- let one through,
+ * and 0 * inf was NaN in every word of a box that had come to rest against a wall.  With the floor, mag2 > Llin^2 >= 2^-126. */
+#define LLIN_FLOOR 0x1p-63f
+static inline float llin_floor(float L) { return (L < LLIN_FLOOR) ? LLIN_FLOOR : L; }
+
 static void solve_ground_friction(solver_t* s, int b, float m, float I, float Llin, float Lang,
                                   fric_acc* f) {
     /* spec: a body at rest (v = 0 and w = 0) has no friction row in this pass */
@@ -382,7 +389,7 @@ static void solve_ground_friction(solver_t* s, int b, float m, float I, float Ll
     float nlx = mad(-m, s->vx[b], f->lx);
     float nly = mad(-m, s->vy[b], f->ly);
     float mag2 = mad(nlx, nlx, nly * nly);
-    if (mag2 > Llin * Llin) {
+    if (mag2 > Llin * Llin) {   /* (spec v1.8: Llin >= LLIN_FLOOR, so mag2 is a normal number here and its spec_rsqrt finite) */
         float sc = Llin * spec_rsqrt(mag2); /* spec v1.3 */
         nlx = nlx * sc; nly = nly * sc;
     }
@@ -469,9 +476,9 @@ void m3o_point_step(const m3o_point_scene* sc, m3o_point_world* w, const float u
     const float gam = 1.0f / (h * sc->drive_damping);
     const float md = 1.0f / (s.invm[BR] + gam);
     const float dmax = sc->drive_fmax * h;
-    const float LlinB = ((sc->box_mu_g * sc->box_m) * sc->g) * h;
+    const float LlinB = llin_floor(((sc->box_mu_g * sc->box_m) * sc->g) * h);   /* spec v1.8 */
     const float LangB = LlinB * sc->box_req;
-    const float LlinD = ((sc->dyn_mu_g * sc->dyn_m) * sc->g) * h;
+    const float LlinD = llin_floor(((sc->dyn_mu_g * sc->dyn_m) * sc->g) * h);
     const float LangD = LlinD * sc->dyn_req;
 
     for (int sub = 0; sub < sc->substeps; ++sub) {
@@ -525,7 +532,7 @@ void m3o_point_step(const m3o_point_scene* sc, m3o_point_world* w, const float u
             friction_coupling(s.vx[BB], s.vy[BB], s.w[BB], 1.5f * sc->box_req, cfB);
             friction_coupling(s.vx[BD], s.vy[BD], s.w[BD], 1.5f * sc->dyn_req, cfD);
         }
-        const float LlinBe = LlinB * cfB[0], LangBe = LangB * cfB[1], LlinDe = LlinD * cfD[0], LangDe = LangD * cfD[1];
+        const float LlinBe = llin_floor(LlinB * cfB[0]), LangBe = LangB * cfB[1], LlinDe = llin_floor(LlinD * cfD[0]), LangDe = LangD * cfD[1];
         for (int it = 0; it < sc->iters; ++it) {
             /* velocity drive (soft constraint, implicit damper) */
             {
