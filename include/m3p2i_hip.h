@@ -271,6 +271,46 @@ int m3_panda_lanes_per_sample_used(m3_handle* h);
  * substep) pairs in which the gripper was within reach of a box or a cube was awake (the kernel's last wavefront reports
  * it into mapped host memory; no synchronisation); -1 before the first report */
 int m3_panda_near_share(m3_handle* h);
+/* EXTENSION, panda_env only: the pick-and-place WORKSPACE as per-handle state -- what a user of the reference edits in the
+ * yaml files of config/panda_env (panda, 1_table, 3_shelf_stand, 4_obs, 5_cubeA, 6_cubeB) and the actors' friction.  The
+ * defaults are the reference's workspace.
+ * NOT part of the scene, and why: the cube's SIZE -- the checker the kernels are held to bit for bit carries the cube's
+ * bounding radius as the literal 0.0434 next to its run-time half extent, so another size cannot be verified; the grasp and
+ * gripper geometry, the joint limits, inertias and efforts -- they are the Franka URDF's, and other robots are out of scope
+ * (DESIGN.md section 9); g, the drive, the solver constants, dt, substeps and iterations -- they are the spec, not the room. */
+typedef struct m3_panda_scene {
+    float base[3];      /* robot mount (panda.yaml)                     default -0.45, 0, 1.125 */
+    float table[6];     /* centre xyz, half extents xyz (1_table.yaml)  default 0,0,1.0, 0.6,0.6,0.025 */
+    float shelf[6];     /* shelf_stand likewise                          default 0.5,0,1.175, 0.1,0.1,0.15 */
+    float obs_half[3];  /* the dyn-obs plate's half extents              default 0.1,0.1,0.01 */
+    float obs_m;        /* its mass                                      default 0.8 */
+    float cube_m;       /* mass of cubeA and cubeB                       default 0.125 */
+    float mu;           /* contact friction                              default 1.0 */
+} m3_panda_scene;
+void m3_default_panda_scene(m3_panda_scene* sc);
+/* Applies from the next command / rollout / step / cost call; survives m3_reset.  It writes into fixed members of the handle:
+ * no allocation, no synchronisation.  sc == NULL: back to the defaults.  Allowed on planner, sharded and sim_only handles; a
+ * world handle and its planners may carry different scenes (each handle uses its own).  Sharded handles: set the same scene on
+ * every rank.  Every field is checked before any state changes: a NaN or infinite field, a half extent <= 0, a mass <= 0 or
+ * mu < 0 is M3_ERR_BAD_ARG and the message names the field ("m3_set_panda_scene: table[5] must be > 0"); a point_env handle
+ * is M3_ERR_UNSUPPORTED.  A refused call leaves the handle unchanged.
+ * Which kernels run.  A handle whose 21 floats equal the defaults bit for bit runs exactly the kernels it ran before this call
+ * existed.  So does a handle that differs in cube_m / obs_m alone, on every path (m3_batch_command and m3_panda_episodes_*
+ * included): the masses reach the kernels through values that were kernel arguments already.  Any other handle (base, table,
+ * shelf, obs_half, mu) runs the run-time-scene instances of the rollout (all tasks, both samplers, both mppi modes; 1, 8 or 16
+ * lanes per sample chosen as before; the reach-cost kernel as before), of the step, of m3_cost and of the views' refresh -- at
+ * the default values the same bits.
+ * NOT batched: m3_batch_command with a handle that needs the run-time-scene instance, and m3_panda_episodes_create / _act /
+ * _act_first with such a world or planner, return M3_ERR_UNSUPPORTED (the message names m3_set_panda_scene and the index of
+ * the handle); nothing is launched. */
+int m3_set_panda_scene(m3_handle* h, const m3_panda_scene* sc);
+int m3_get_panda_scene(const m3_handle* h, m3_panda_scene* out);
+/* Test and A/B switch: -1 the automatic choice above (default), 1 the run-time-scene instances whatever the values, 0 never --
+ * with a geometry or friction other than the default the next command / rollout / step / cost call is then refused
+ * (M3_ERR_STATE: "... forced off ..."). */
+int m3_set_panda_scene_instance(m3_handle* h, int on);
+/* 0 / 1: whether the last rollout or step of the handle launched the run-time-scene instance */
+int m3_panda_scene_instance_used(m3_handle* h);
 /* launch structure of the unsharded multi-modal update with K beyond the one-launch kernel's range: 0 (default) = three
  * launches (ladder + search in one grid, weights + sums, combine), 5 = the five launches of round 3 (minima, ladder,
  * search, weights, sums), whose sums are added in the order of the sharded "exact" protocols (tests compare those bit

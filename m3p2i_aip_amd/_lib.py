@@ -76,6 +76,42 @@ class PointSceneFields(C.Structure):
     _fields_ = [(n, C.c_float) for n in POINT_SCENE_DEFAULTS]
 
 
+# m3_panda_scene, in field order, with the values of m3_default_panda_scene (the reference's workspace; the oracle's
+# m3o_panda_scene_default)
+PANDA_SCENE_DEFAULTS = dict(
+    base=(-0.45, 0.0, 1.125), table=(0.0, 0.0, 1.0, 0.6, 0.6, 0.025), shelf=(0.5, 0.0, 1.175, 0.1, 0.1, 0.15),
+    obs_half=(0.1, 0.1, 0.01), obs_m=0.8, cube_m=0.125, mu=1.0)
+
+
+class PandaSceneFields(C.Structure):
+    _fields_ = [(n, C.c_float * len(v) if isinstance(v, tuple) else C.c_float) for n, v in PANDA_SCENE_DEFAULTS.items()]
+
+
+def panda_scene_fields(overrides=None):
+    """PandaSceneFields from field overrides over PANDA_SCENE_DEFAULTS (array fields as sequences of their length); ValueError
+    for an unknown field (with the list of fields) or a wrong length."""
+    overrides = dict(overrides or {})
+    unknown = sorted(set(overrides) - set(PANDA_SCENE_DEFAULTS))
+    if unknown:
+        raise ValueError(f"unknown panda scene field(s) {unknown}: one of {list(PANDA_SCENE_DEFAULTS)}")
+    sc = PandaSceneFields()
+    for n, lit in PANDA_SCENE_DEFAULTS.items():
+        v = overrides.get(n, lit)
+        if isinstance(lit, tuple):
+            v = [float(x) for x in v]
+            if len(v) != len(lit):
+                raise ValueError(f"panda scene field {n!r}: {len(v)} values, it has {len(lit)}")
+            setattr(sc, n, (C.c_float * len(lit))(*v))
+        else:
+            setattr(sc, n, float(v))
+    return sc
+
+
+def panda_scene_dict(sc):
+    """all fields of a PandaSceneFields as a mapping like PANDA_SCENE_DEFAULTS (binary32 values)"""
+    return {n: tuple(getattr(sc, n)) if isinstance(lit, tuple) else getattr(sc, n) for n, lit in PANDA_SCENE_DEFAULTS.items()}
+
+
 class Info(C.Structure):
     _fields_ = [("eta", C.c_float), ("eta_1", C.c_float), ("eta_2", C.c_float),
                 ("beta", C.c_float), ("beta_1", C.c_float), ("beta_2", C.c_float),
@@ -164,6 +200,11 @@ SYMBOLS = [
     ("m3_set_point_rollout_scenes", C.c_int, [_H, C.POINTER(PointSceneFields), C.c_int]),
     ("m3_get_point_rollout_scene", C.c_int, [_H, C.c_int, C.POINTER(PointSceneFields)]),
     ("m3_point_rollout_scenes_set", C.c_int, [_H]),
+    ("m3_default_panda_scene", None, [C.POINTER(PandaSceneFields)]),
+    ("m3_set_panda_scene", C.c_int, [_H, C.POINTER(PandaSceneFields)]),
+    ("m3_get_panda_scene", C.c_int, [_H, C.POINTER(PandaSceneFields)]),
+    ("m3_set_panda_scene_instance", C.c_int, [_H, C.c_int]),
+    ("m3_panda_scene_instance_used", C.c_int, [_H]),
     ("m3_point_rollout_plan", C.c_int, [C.c_int] * 8 + [C.c_float] + [C.c_int] * 6 + [C.POINTER(C.c_int)]),
     ("m3_set_multi_modal", C.c_int, [_H, C.c_int]),
     ("m3_set_plan", C.c_int, [_H, C.c_int, _FP]),

@@ -131,6 +131,11 @@ class ExampleConfig:
     world_point_scene: Optional[Dict[str, float]] = None   # EXTENSION, point_env: field overrides of the REAL world only, on top
                                                            # of point_scene (model mismatch: the planner and its K-env simulator
                                                            # keep point_scene); world_isaacgym_config applies it
+    panda_scene: Optional[Dict[str, object]] = None    # EXTENSION, panda_env: field overrides of the workspace, e.g.
+                                                       # `panda_scene={table: [0, 0, 0.99, 0.6, 0.6, 0.025], mu: 0.5}`
+                                                       # (_lib.PANDA_SCENE_DEFAULTS); wrappers and planners as for point_scene
+    world_panda_scene: Optional[Dict[str, object]] = None   # EXTENSION, panda_env: field overrides of the REAL world only, on
+                                                            # top of panda_scene (the planner keeps panda_scene)
     rollout_arena_spread: Optional[Dict[str, object]] = None   # EXTENSION, point_env: `rollout_arena_spread={spread: 0.3, seed: 1,
                                                                # fields: [box_m, box_mu_g, mu_rb]}` -- the planner's K rollouts
                                                                # each in an arena of their own around point_scene (the samples
@@ -184,6 +189,19 @@ def make_config(config_name="config_point", overrides=()):
     if cfg.rollout_arena_spread:
         cfg.rollout_arena_spread = dict(cfg.rollout_arena_spread)
         _check_rollout_arena_spread(cfg)
+    for key in ("panda_scene", "world_panda_scene"):
+        given = getattr(cfg, key)
+        if given:
+            if cfg.env_type != "panda_env":
+                raise ValueError(f"{key}: panda_env only")
+            from ._lib import panda_scene_fields
+            try:
+                panda_scene_fields(given)     # (unknown fields, wrong lengths)
+            except ValueError as e:
+                raise ValueError(f"{key}: {e}") from None
+            setattr(cfg, key, dict(given))
+    if cfg.panda_scene:
+        cfg.isaacgym.panda_scene = dict(cfg.panda_scene)   # (the wrappers are built from cfg.isaacgym)
     return cfg
 
 
@@ -227,12 +245,21 @@ def world_point_scene(cfg):
     return {**(getattr(cfg, "point_scene", None) or {}), **(getattr(cfg, "world_point_scene", None) or {})}
 
 
+def world_panda_scene(cfg):
+    """The field overrides of the workspace of cfg's REAL world: `panda_scene` with `world_panda_scene` on top ({} = the
+    reference's workspace)."""
+    return {**(getattr(cfg, "panda_scene", None) or {}), **(getattr(cfg, "world_panda_scene", None) or {})}
+
+
 def world_isaacgym_config(cfg):
-    """cfg.isaacgym as the 1-env or N-env REAL world is built from it: cfg.isaacgym itself unless `world_point_scene` is set,
-    else a copy whose point_scene carries those overrides too.  The planner's K-env simulator is built from cfg.isaacgym."""
+    """cfg.isaacgym as the 1-env or N-env REAL world is built from it: cfg.isaacgym itself unless `world_point_scene` /
+    `world_panda_scene` is set, else a copy whose point_scene / panda_scene carries those overrides too.  The planner's
+    K-env simulator is built from cfg.isaacgym."""
+    import dataclasses
+    if getattr(cfg, "world_panda_scene", None):
+        return dataclasses.replace(cfg.isaacgym, panda_scene=world_panda_scene(cfg))
     if not getattr(cfg, "world_point_scene", None):
         return cfg.isaacgym
-    import dataclasses
     return dataclasses.replace(cfg.isaacgym, point_scene=world_point_scene(cfg))
 
 

@@ -74,7 +74,12 @@ static void build_point_scene(const m3_config& c, PointScene& s) { make_point_sc
 
 // "Panda chain spec" constants (sources: franka_panda.urdf limits, config/panda_env/*.yaml,
 // isaacgym_wrapper.py:341-344)
-static void build_panda_scene(const m3_config& c, PandaScene& s) { make_panda_scene(s, c.dt, c.substeps); }
+// the handle's two panda scenes from its workspace (m3_create, m3_set_panda_scene): PandaScene takes the masses, PandaSceneRT
+// everything
+static void build_panda_scenes(const m3_config& c, const m3_panda_scene& ws, PandaScene& s, PandaSceneRT& rt) {
+    make_panda_scene(s, c.dt, c.substeps, 6, ws.cube_m, ws.obs_m);
+    rt = make_panda_scene_rt(ws, c.dt, c.substeps);
+}
 
 static void default_panda_world(float* w, int cube_on_shelf) {
     const float q0[9] = {0, 0, 0, -2.0f, 0, 1.8675f, 0, 0.02f, 0.02f};  // panda.yaml:10
@@ -211,7 +216,7 @@ extern "C" int m3_create(const m3_config* c, m3_handle** out) {
     build_point_scene(*c, h->scene);
     h->scene_rt = make_point_scene_rt(h->point_scene, c->dt, c->substeps, c->solver_iters);
     default_world(h->world0);
-    build_panda_scene(*c, h->pscene);
+    build_panda_scenes(*c, h->panda_scene, h->pscene, h->pscene_rt);
     default_panda_world(h->pworld0, c->cube_on_shelf);
     const long long Kl = c->K_local, Kg = c->K_global, T = c->T, nu = c->nu;
     const long long f = sizeof(float);
@@ -998,6 +1003,61 @@ static const char* point_variant_refusal(const m3_handle* h, PointSide side) {
     return nullptr;
 }
 
+// ---- the panda_env workspace (extension; per-handle state like the point arena: fixed members, no allocation, no
+// synchronisation) ----
+extern "C" void m3_default_panda_scene(m3_panda_scene* sc) {
+    if (sc) std::memcpy(sc, &PANDA_SCENE_DEFAULT, sizeof(*sc));
+}
+
+extern "C" int m3_set_panda_scene(m3_handle* h, const m3_panda_scene* sc) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_PANDA) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_panda_scene: panda_env only");
+    const m3_panda_scene& src = sc ? *sc : PANDA_SCENE_DEFAULT;
+    const std::string fault = panda_scene_fault(src);
+    if (!fault.empty()) return fail(h, M3_ERR_BAD_ARG, ("m3_set_panda_scene: " + fault).c_str());
+    std::memcpy(&h->panda_scene, &src, sizeof(src));
+    build_panda_scenes(h->cfg, h->panda_scene, h->pscene, h->pscene_rt);
+    return M3_OK;
+}
+
+extern "C" int m3_get_panda_scene(const m3_handle* h, m3_panda_scene* out) {
+    if (!h || !out) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_PANDA) return M3_ERR_UNSUPPORTED;
+    std::memcpy(out, &h->panda_scene, sizeof(*out));
+    return M3_OK;
+}
+
+extern "C" int m3_set_panda_scene_instance(m3_handle* h, int on) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_PANDA) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_panda_scene_instance: panda_env only");
+    if (on < -1 || on > 1) return fail(h, M3_ERR_BAD_ARG, "m3_set_panda_scene_instance: -1 (by the values), 0 or 1");
+    h->panda_scene_instance = on;
+    return M3_OK;
+}
+
+extern "C" int m3_panda_scene_instance_used(m3_handle* h) { return h ? h->panda_scene_used : M3_ERR_BAD_ARG; }
+
+// ---- which panda_env kernels a handle runs: decided here and nowhere else ----
+// the run-time-scene instances (rollout_panda_scene.hip): by the values -- anything but the two masses off the defaults -- or
+// as m3_set_panda_scene_instance says
+static bool panda_scene_runtime(const m3_handle* h) {
+    if (h->cfg.env_type != M3_ENV_PANDA) return false;
+    return h->panda_scene_instance < 0 ? !panda_scene_geometry_is_default(h->panda_scene) : h->panda_scene_instance != 0;
+}
+// why the handle cannot run its kernels (M3_ERR_STATE; nullptr: it can)
+static const char* panda_scene_refusal(const m3_handle* h) {
+    if (h->cfg.env_type != M3_ENV_PANDA) return nullptr;
+    if (h->panda_scene_instance == 0 && !panda_scene_geometry_is_default(h->panda_scene))
+        return "the run-time-scene instance is forced off (m3_set_panda_scene_instance 0) but the handle's workspace (m3_set_panda_scene) is not the default";
+    return nullptr;
+}
+// why a path that carries a PandaScene only (m3_batch_command's table, the lockstep episodes' kernels) cannot take the handle
+static const char* panda_scene_unbatched(const m3_handle* h) {
+    return panda_scene_runtime(h) ? "its workspace (m3_set_panda_scene) needs the run-time-scene instance, which only m3_rollout / "
+                                    "m3_command and the handle's own step, cost and views run"
+                                  : nullptr;
+}
+
 extern "C" int m3_set_multi_modal(m3_handle* h, int mm) {
     if (!h) return M3_ERR_BAD_ARG;
     if (!h->cfg.sim_only && (mm != 0) != (h->cfg.multi_modal != 0))
@@ -1153,6 +1213,7 @@ static const char* rollout_refusal(const m3_handle* h) {
     if (c.mode_simple && !c.sampling_random && !h->have_noise)
         return "m3_rollout: simple mode needs m3_set_noise or sampling_random";
     if (h->task == M3_TASK_PUSH_PULL && !c.multi_modal) return "m3_rollout: push_pull needs multi_modal";
+    if (const char* why = panda_scene_refusal(h)) return why;
     return point_variant_refusal(h, SIDE_ROLLOUT);
 }
 
@@ -1268,7 +1329,8 @@ extern "C" int m3_rollout(m3_handle* h) {
     if (h->cfg.env_type == M3_ENV_POINT) h->point_form_used = p.form;
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->scene_rt, h->cost_weights, p, h->stream, h->rollout_err_dev, h->scene_rows_dev);
-    else launch_rollout_panda(a, pa, h->pscene, p, h->stream);
+    else if (panda_scene_runtime(h)) { launch_rollout_panda_s(a, pa, h->pscene_rt, p, h->stream); h->panda_scene_used = 1; }
+    else { launch_rollout_panda(a, pa, h->pscene, p, h->stream); h->panda_scene_used = 0; }
     HIPCHK(h, hipGetLastError());
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     return M3_OK;
@@ -1961,6 +2023,10 @@ static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code) {
         return "it has an arena per sample (m3_set_point_rollout_scenes), which only m3_rollout / m3_command run";
     }
     if (const char* why = rollout_refusal(h)) return why;
+    if (const char* why = panda_scene_unbatched(h)) {   // (the table's entry carries a PandaScene)
+        code = M3_ERR_UNSUPPORTED;
+        return why;
+    }
     fill_update_impl_args(h, u, true);
     code = M3_ERR_UNSUPPORTED;
     if (!can_fuse_finalize(h) || !update_small_applies(u))
@@ -2207,7 +2273,9 @@ extern "C" int m3_sim_bind_views(m3_handle* h, float* dof, float* root, float* r
 extern "C" int m3_sim_pull_state(m3_handle* h) {
     if (!h) return M3_ERR_BAD_ARG;
     if (!h->views_bound || !h->views.dof_state || !h->views.root_state) return fail(h, M3_ERR_STATE, "m3_sim_pull_state: views not bound");
+    if (const char* why = panda_scene_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_sim_pull_state: ") + why).c_str());
     if (h->cfg.env_type == M3_ENV_POINT) launch_sim_pull(h->views, h->sim_world, h->cfg.K_local, h->stream);
+    else if (panda_scene_runtime(h)) launch_psim_pull_s(h->pscene_rt, h->views, h->sim_world, h->cfg.K_local, h->stream);
     else launch_psim_pull(h->pscene, h->views, h->sim_world, h->cfg.K_local, h->stream);
     HIPCHK(h, hipGetLastError());
     return M3_OK;
@@ -2226,7 +2294,9 @@ extern "C" int m3_sim_shift_actor(m3_handle* h, int actor, float dx, float dy, f
 extern "C" int m3_sim_push_state(m3_handle* h) {
     if (!h) return M3_ERR_BAD_ARG;
     if (!h->views_bound) return fail(h, M3_ERR_STATE, "m3_sim_push_state: views not bound");
+    if (const char* why = panda_scene_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_sim_push_state: ") + why).c_str());
     if (h->cfg.env_type == M3_ENV_POINT) launch_sim_push(h->views, h->sim_world, h->cfg.K_local, h->stream);
+    else if (panda_scene_runtime(h)) launch_psim_push_s(h->pscene_rt, h->views, h->sim_world, h->cfg.K_local, h->stream);
     else launch_psim_push(h->pscene, h->views, h->sim_world, h->cfg.K_local, h->stream);
     HIPCHK(h, hipGetLastError());
     return M3_OK;
@@ -2261,7 +2331,10 @@ static int sim_step_impl(m3_handle* h, const float* u) {
             default: launch_sim_step(h->scene, h->views, h->sim_world, u, h->sim_u, Kl, h->stream); break;
         }
     } else {
-        launch_psim_step(h->pscene, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
+        if (const char* why = panda_scene_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_sim_step: ") + why).c_str());
+        h->panda_scene_used = panda_scene_runtime(h) ? 1 : 0;
+        if (h->panda_scene_used) launch_psim_step_s(h->pscene_rt, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
+        else launch_psim_step(h->pscene, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
     }
     HIPCHK(h, hipGetLastError());
     return M3_OK;
@@ -2314,7 +2387,9 @@ extern "C" int m3_cost(m3_handle* h, float* cost) {
         fill_panda_cost_params(h, cp);
         // quirk Q8 exactly where m3_rollout applies it (its shadow lanes): reach on an unsharded handle
         const bool env0_cube = cp.task == 4 && h->cfg.k_offset == 0 && h->cfg.K_local == h->cfg.K_global && h->cfg.K_global >= 2;
-        launch_psim_cost(h->pscene, cp, h->sim_world, h->cfg.K_local, h->cfg.k_offset, env0_cube, cost, h->stream);
+        if (const char* why = panda_scene_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_cost: ") + why).c_str());
+        if (panda_scene_runtime(h)) launch_psim_cost_s(h->pscene_rt, cp, h->sim_world, h->cfg.K_local, h->cfg.k_offset, env0_cube, cost, h->stream);
+        else launch_psim_cost(h->pscene, cp, h->sim_world, h->cfg.K_local, h->cfg.k_offset, env0_cube, cost, h->stream);
     }
     HIPCHK(h, hipGetLastError());
     return M3_OK;
@@ -2619,6 +2694,8 @@ extern "C" int m3_panda_episodes_create(m3_handle* world, m3_handle* const* plan
         !world->views.root_state || !world->views.rigid_body_state)
         return peps_refuse(M3_ERR_STATE, -1, "the world must be a sim_only panda_env handle with its views bound");
     if (wc.K_local != n || wc.K_global != n) return peps_refuse(M3_ERR_STATE, -1, "the world's K_local must equal n (one row per episode)");
+    if (const char* why = panda_scene_refusal(world)) return peps_refuse(M3_ERR_STATE, -1, std::string("the world: ") + why);
+    if (const char* why = panda_scene_unbatched(world)) return peps_refuse(M3_ERR_UNSUPPORTED, -1, std::string("the world: ") + why);
     for (int i = 0; i < n; ++i) {
         m3_handle* h = planners[i];
         if (!h) return peps_refuse(M3_ERR_BAD_ARG, i, "null handle");
@@ -2719,6 +2796,17 @@ static int peps_active(const m3_panda_episodes* eps) {
 
 static int peps_ready(m3_panda_episodes* eps, const char* who) {
     if (peps_active(eps) == 0) { eps->err = std::string(who) + ": every episode has ended and settled"; return M3_ERR_STATE; }
+    // (a workspace set after m3_panda_episodes_create, which refuses it: nothing of this tick is launched)
+    for (int i = -1; i < eps->n; ++i) {
+        const m3_handle* h = i < 0 ? eps->world : eps->planners[i];
+        const char* why = panda_scene_refusal(h);
+        const int code = why ? M3_ERR_STATE : M3_ERR_UNSUPPORTED;
+        if (!why) why = panda_scene_unbatched(h);
+        if (why) {
+            eps->err = std::string(who) + (i < 0 ? ": the world: " : ": planner " + std::to_string(i) + ": ") + why;
+            return code;
+        }
+    }
     for (int i = 0; i < eps->n; ++i)
         if (eps->planners[i]->action_out != eps->plan[i]) {
             eps->err = std::string(who) + ": planner " + std::to_string(i) + "'s action-out destination changed since create";

@@ -9,6 +9,7 @@
 #include "planar_dyn.hpp"
 #include "point_cost.hpp"
 #include "panda_dyn.hpp"
+#include "panda_scene.hpp"
 
 namespace m3 {
 
@@ -408,6 +409,17 @@ void launch_psim_push(const PandaScene& sc, const SimViews& v, const float* worl
 void launch_psim_cost(const PandaScene& sc, const PandaCostParams& cp, const float* world, int Kl, int k0, bool env0_cube,
                       float* cost, hipStream_t s);
 
+// the same for a handle whose workspace is a kernel argument (m3_set_panda_scene; rollout_panda_scene.hip).  The reach-cost
+// kernel takes no scene and serves both.
+void launch_panda_reach_cost(const RolloutArgs& a, const PandaArgs& pa, hipStream_t s);
+void launch_rollout_panda_s(const RolloutArgs& a, const PandaArgs& pa, const PandaSceneRT& sc, const RolloutPlan& p, hipStream_t s);
+void launch_psim_step_s(const PandaSceneRT& sc, const SimViews& v, float* world, const float* u, float* u_keep, int Kl,
+                        hipStream_t s);
+void launch_psim_pull_s(const PandaSceneRT& sc, const SimViews& v, float* world, int Kl, hipStream_t s);
+void launch_psim_push_s(const PandaSceneRT& sc, const SimViews& v, const float* world, int Kl, hipStream_t s);
+void launch_psim_cost_s(const PandaSceneRT& sc, const PandaCostParams& cp, const float* world, int Kl, int k0, bool env0_cube,
+                        float* cost, hipStream_t s);
+
 // batched closed-loop episodes of the panda_env (m3_panda_episodes_*): one lane per episode of an N-env world
 struct PandaEpisodeArgs {
     SimViews v;                    // the world's views, [n] rows
@@ -439,7 +451,12 @@ struct m3_handle {
     bool relabel_pending = false;  // m3_relabel_samples: done by the next m3_rollout
     bool relabelled = false;       // the noise rows ARE in wavefront order (identity order from then on)
     m3::PointScene scene;
-    m3::PandaScene pscene;
+    m3::PandaScene pscene;             // ... with the masses of panda_scene (make_panda_scene; m3_create, m3_set_panda_scene)
+    // m3_set_panda_scene (extension, panda_env): fixed members, written in place -- no allocation; survive m3_reset
+    m3_panda_scene panda_scene = m3::PANDA_SCENE_DEFAULT;
+    m3::PandaSceneRT pscene_rt = {};   // make_panda_scene_rt (m3_create, m3_set_panda_scene)
+    int panda_scene_instance = -1;     // m3_set_panda_scene_instance: -1 by the values (geometry / friction not the defaults), 0 / 1 forced
+    int panda_scene_used = 0;          // what the last rollout or step launched (m3_panda_scene_instance_used)
     float pworld0[57];
     hipStream_t stream = nullptr;
     std::string err;

@@ -1,20 +1,28 @@
-// panda_dyn.hpp -- device-side "Panda chain spec" (currently v1.2) and the panda_env task costs.
+// panda_dyn.hpp -- device-side "Panda world spec" (currently v3.1) and the panda_env task costs.
 //
 // Replaces, for the panda_env scene, what the reference delegates to Isaac Gym / PhysX
 // (IsaacGymWrapper.step(), isaacgym_wrapper.py:354-360) with:
 //   * a velocity-servoed 9-dof chain (drive damping 600, isaacgym_wrapper.py:341-344; effort /
-//     velocity / position limits of franka_panda.urdf:34..240),
+//     velocity / position limits of franka_panda.urdf:34..240), the servos in closed form,
 //   * forward kinematics from the URDF joint origins (franka_panda.urdf:27-242),
-//   * cubeA as a free body with support contact and a position-level two-finger grasp,
-//   * penalty contact forces on table / shelf_stand / cubeB (what get_motion_cost reads).
+//   * cubeA and cubeB as free rigid cubes and the dyn-obs plate as a free body that does not rotate; table and
+//     shelf_stand static; sleeping cubes,
+//   * a velocity-level contact solver: one contact per gripper collision sphere, four-point face-to-face manifolds of the
+//     cubes against table / shelf_stand / each other, rows in generalized coordinates with fixed summation trees
+//     (spec v3), effective masses by spec_rcp (v3.1), friction rows first, warm-started normal rows last,
+//   * the grasp as a latch (pad channel: grasp region inside the pads' region inside the capture volume),
+//   * the net contact forces on table / shelf_stand / cubeB from the solver's impulses (what get_motion_cost reads).
 // Costs follow the reference (pinned by golden group G6b):
 //   get_panda_reach_cost :91-114, get_panda_pick_cost :116-125, get_panda_place_cost :127-136,
 //   get_pick_tilt_cost :138-156, get_motion_cost :158-169 (cost_functions.py);
 //   quaternion_rotation_matrix / get_general_ori_* skill_utils.py:140-180, 224-290.
 //
-// One lane per sample; the whole environment (9+9 joint values, cube pose, grasp state) sits
-// in VGPRs.  Trigonometry uses the spec's own Cody-Waite + polynomial sin/cos (plain f32 ops)
-// so that the CPU oracle agrees bit-for-bit.
+// One, eight or sixteen lanes per sample (LPS); a sample's environment (9+9 joint values, the bodies' poses, grasp state)
+// sits in VGPRs, the solver's per-substep store in LDS.  Trigonometry uses the spec's own Cody-Waite + polynomial sin/cos
+// (plain f32 ops) so that the CPU oracle agrees bit-for-bit.
+//
+// Every function that reads the scene is a template on its type: PandaScene (the reference's workspace compiled in) or
+// PandaSceneRT (the workspace of m3_set_panda_scene as kernel-argument members of the same names).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -56,7 +64,9 @@ struct PandaScene {
 // the run-time part of the scene (host side: m3_create, and the host build in tests/native/), in f32, in the oracle's order.
 // Joint inertias: the diagonal of the joint-space mass matrix at the initial pose, from the collision meshes at the
 // default density (tools/panda_inertia.py).
-inline void make_panda_scene(PandaScene& s, float dt, int substeps, int iters = 6) {
+// cube_m, obs_m: the masses of cubeA / cubeB and of the plate (m3_set_panda_scene; the defaults are the reference's).
+inline void make_panda_scene(PandaScene& s, float dt, int substeps, int iters = 6, float cube_m = PandaScene::cube_m,
+                             float obs_m = 0.8f) {
     const float h = dt / (float)substeps;
     s.h = h; s.inv_h = 1.0f / h; s.substeps = substeps; s.iters = iters;
     const float inertia[9] = {1.32f, 2.12f, 1.30f, 0.918f, 0.0271f, 0.0366f, 0.0030f, 0.022f, 0.022f};
@@ -69,12 +79,23 @@ inline void make_panda_scene(PandaScene& s, float dt, int substeps, int iters = 
         s.pmax[i] = h * effort[i];
         s.dv[i] = s.pmax[i] * s.invI[i];
     }
-    const float cube_half = 0.025f, cube_m = 0.125f;
-    s.invm_cube = 1.0f / cube_m;
+    const float cube_half = 0.025f;
+    s.invm_cube = 1.0f / cube_m;      // (the oracle's order: panda_chain.c, m3o_panda_step)
     s.invI_cube = 1.0f / ((cube_m * ((2.0f * cube_half) * (2.0f * cube_half))) / 6.0f);
-    s.invm_obs = 1.0f / 0.8f;
+    s.invm_obs = 1.0f / obs_m;
     s.sleep_v2 = 0.02f * 0.02f; s.sleep_w2 = 0.4f * 0.4f;
 }
+
+// The scene with the workspace of m3_set_panda_scene as run-time members: the five names below hide PandaScene's
+// constants of the same names, everything else (the run-time part above, the robot, the grasp geometry, the solver
+// constants) is PandaScene's.  Formed on the host by make_panda_scene_rt (panda_scene.hpp).
+struct PandaSceneRT : PandaScene {
+    float base[3];
+    float table[6];
+    float shelf[6];
+    float obs_half[3];
+    float mu;
+};
 
 struct Body {
     float p[3], q[4], v[3], w[3];   // pos, quaternion xyzw, linear / angular velocity
@@ -396,8 +417,8 @@ __device__ __forceinline__ void fk_cross(const float* a, const float* b, float* 
     c[1] = mad(a[2], b[0], -(a[0] * b[2]));
     c[2] = mad(a[0], b[1], -(a[1] * b[0]));
 }
-template <bool STORE, bool JAC = false, int LPS = 1>
-__device__ __forceinline__ void panda_fk(const PandaScene& sc, const float* q, Frame& hand,
+template <bool STORE, bool JAC = false, int LPS = 1, class SC>
+__device__ __forceinline__ void panda_fk(const SC& sc, const float* q, Frame& hand,
                                          float* pl, float* pr, float* out, GripperT<LPS>* gj = nullptr) {
     constexpr int NJ = GripperT<LPS>::NJ;
     float jz[NJ][3], jp[NJ][3];
@@ -544,7 +565,8 @@ __device__ __forceinline__ BoxT<false> box_static(const float* b6) {
     o.R = nullptr;
     return o;
 }
-__device__ __forceinline__ BoxT<true> box_cube(const PandaScene& sc, const float* p, const float* R) {
+template <class SC>
+__device__ __forceinline__ BoxT<true> box_cube(const SC& sc, const float* p, const float* R) {
     BoxT<true> o;
 #pragma unroll
     for (int i = 0; i < 3; ++i) { o.p[i] = p[i]; o.e[i] = sc.cube_half; }
@@ -663,14 +685,16 @@ __device__ __forceinline__ void body_put(PandaWorld& W, int b, const BodyVel& o)
         W.obs_v[i] = (b == 2) ? o.v[i] : +W.obs_v[i];
     }
 }
-__device__ __forceinline__ float body_k(const PandaScene& sc, int b, const float* a) {
+template <class SC>
+__device__ __forceinline__ float body_k(const SC& sc, int b, const float* a) {
     return (b < 2) ? mad(sc.invI_cube, dotm(a, a), sc.invm_cube) : sc.invm_obs;
 }
 __device__ __forceinline__ float bodyvel_along(int b, const BodyVel& o, const float* d, const float* a) {
     const float lin = dotm(d, o.v);
     return (b < 2) ? lin + dotm(a, o.w) : lin;
 }
-__device__ __forceinline__ void bodyvel_apply(const PandaScene& sc, int b, BodyVel& o, const float* d, const float* a, float dl) {
+template <class SC>
+__device__ __forceinline__ void bodyvel_apply(const SC& sc, int b, BodyVel& o, const float* d, const float* a, float dl) {
     const float im = ((b < 2) ? sc.invm_cube : sc.invm_obs) * dl;
 #pragma unroll
     for (int i = 0; i < 3; ++i) o.v[i] = mad(im, d[i], o.v[i]);
@@ -680,7 +704,8 @@ __device__ __forceinline__ void bodyvel_apply(const PandaScene& sc, int b, BodyV
         for (int i = 0; i < 3; ++i) o.w[i] = mad(ia, a[i], o.w[i]);
     }
 }
-__device__ __forceinline__ float contact_bias(const PandaScene& sc, float gap) {
+template <class SC>
+__device__ __forceinline__ float contact_bias(const SC& sc, float gap) {
     if (gap > 0.0f) return gap * sc.inv_h;
     const float pen = fmaxf(-gap - sc.slop, 0.0f);
     const float push = fminf((sc.baumgarte * pen) * sc.inv_h, sc.max_bias);
@@ -755,7 +780,7 @@ template <int LPS> struct GenConst {
     Gen<LPS> invM_cube, invM_obs;    // inverse masses: joints | the touched body's 1/m x 3, 1/I x 3 | 0 (cube / plate)
     Gen<LPS> rden, pmax;             // the drive rows (entries 9-15: 0, so they are no-ops there)
 };
-template <int LPS> __device__ __forceinline__ GenConst<LPS> gen_consts(const PandaScene& sc) {
+template <int LPS, class SC> __device__ __forceinline__ GenConst<LPS> gen_consts(const SC& sc) {
     GenConst<LPS> k;
     k.invM_cube = gen_make<LPS>([&](int c) __attribute__((always_inline)) {
         return (c < 9) ? sc.invI[c < 9 ? c : 0] : (c < 12) ? sc.invm_cube : (c < 15) ? sc.invI_cube : 0.0f; });
@@ -772,8 +797,8 @@ struct Manifold {
     int made, up, down;  // contacts made; of them carrying the cube (n_z >= 0.99, gap < rest_gap) / carried by it
     bool centre_over;
 };
-template <bool ORIENTED, int LPS = 1>
-__device__ __forceinline__ void manifold_detect(const PandaScene& sc, const float* pb, const float* Rb, const BoxT<ORIENTED>& tgt,
+template <bool ORIENTED, int LPS = 1, class SC>
+__device__ __forceinline__ void manifold_detect(const SC& sc, const float* pb, const float* Rb, const BoxT<ORIENTED>& tgt,
                                                 Manifold& m, float (*X)[3], float* gap) {
     m.any = false; m.on = 0u; m.made = 0; m.up = 0; m.down = 0; m.centre_over = false;
 #pragma unroll
@@ -866,7 +891,8 @@ __device__ __forceinline__ void manifold_detect(const PandaScene& sc, const floa
 }
 
 // the static box a cube makes contact with: the nearer to its centre (the table on a tie)
-__device__ __forceinline__ bool nearer_is_table(const PandaScene& sc, const float* pb) {
+template <class SC>
+__device__ __forceinline__ bool nearer_is_table(const SC& sc, const float* pb) {
     float d2[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -881,7 +907,8 @@ __device__ __forceinline__ bool nearer_is_table(const PandaScene& sc, const floa
     }
     return d2[0] <= d2[1];
 }
-__device__ __forceinline__ bool cube_on_static(const PandaScene& sc, const Body& c) {
+template <class SC>
+__device__ __forceinline__ bool cube_on_static(const SC& sc, const Body& c) {
     float R[9], X[4][3], gap[4];
     body_rot(c.q, R);
     Manifold m;
@@ -893,7 +920,8 @@ __device__ __forceinline__ bool cube_on_static(const PandaScene& sc, const Body&
     for (int j = 0; j < 4; ++j) ok = ok && (gap[j] < sc.rest_gap);
     return ok;
 }
-__device__ __forceinline__ bool cube_on_cube(const PandaScene& sc, const Body& up, const Body& lo) {
+template <class SC>
+__device__ __forceinline__ bool cube_on_cube(const SC& sc, const Body& up, const Body& lo) {
     float Ru[9], Rl[9], X[4][3], gap[4];
     body_rot(up.q, Ru);
     body_rot(lo.q, Rl);
@@ -916,7 +944,8 @@ struct GraspGeom {
     bool in_pads;      // spec v2.1: the pads meet the cube's side faces (they cannot enter it, closing pads sweep it)
 };
 constexpr float PADS_DX = 0.035f, PADS_DZ = 0.03f;
-__device__ __forceinline__ void grasp_geom(const PandaScene& sc, const PandaWorld& w, const Frame& hand,
+template <class SC>
+__device__ __forceinline__ void grasp_geom(const SC& sc, const PandaWorld& w, const Frame& hand,
                                            GraspGeom& g) {
     const float d[3] = {w.A.p[0] - hand.p[0], w.A.p[1] - hand.p[1], w.A.p[2] - hand.p[2]};
     g.cx = dot3(d, hand.x); g.cy = dot3(d, hand.y); g.cz = dot3(d, hand.z);
@@ -948,7 +977,8 @@ __device__ __forceinline__ void set_rel_rot(PandaWorld& w, const Frame& hand, co
 
 // A world is loaded from the wrapper's tensors, which carry neither a "held" bit nor the cubes' sleep state: both are
 // inferred from geometry (the oracle's m3o_panda_infer_held).
-__device__ __forceinline__ void panda_infer_held(const PandaScene& sc, PandaWorld& w, float* hand_p = nullptr) {
+template <class SC>
+__device__ __forceinline__ void panda_infer_held(const SC& sc, PandaWorld& w, float* hand_p = nullptr) {
     Frame hand;
     float pl[3], pr[3];
     panda_fk<false>(sc, w.q, hand, pl, pr, nullptr);
@@ -1037,8 +1067,8 @@ struct PandaProf { long long solve_clk, near_clk, detect_clk, post_clk, pre_clk,
 #else
 #define M3_PROF_ARG
 #endif
-template <bool FORCES = true, bool LAZY = false, int LPS = 1>
-__device__ __forceinline__ void panda_step(const PandaScene& sc, PandaWorld& w, const float* u, PandaObs& obs,
+template <bool FORCES = true, bool LAZY = false, int LPS = 1, class SC>
+__device__ __forceinline__ void panda_step(const SC& sc, PandaWorld& w, const float* u, PandaObs& obs,
                                            const CornerStore& cs, float* hp = nullptr, float* trav = nullptr,
                                            FkCarry<LPS>* fkc = nullptr M3_PROF_ARG) {
     constexpr bool CARRY = LAZY, CARRY_JAC = LAZY && LPS != 1;

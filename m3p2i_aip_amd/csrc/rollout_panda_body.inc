@@ -1,7 +1,7 @@
 // rollout_panda_body.inc -- the body of k_rollout_panda (rollout_panda.hip), included by the kernel and by its batched form
 // kb_rollout_panda: the same tokens in both, so that k_rollout_panda compiles to exactly the code it did as a plain kernel
-// (as update_small_body.inc).  In scope where it is included: FORCES, GENERAL, LPS, `const RolloutArgs& a_`,
-// `const PandaArgs& pa` and `const PandaScene& sc_`.
+// (as update_small_body.inc).  In scope where it is included: FORCES, GENERAL, LPS, the scene type `SceneT` (PandaScene, or
+// PandaSceneRT in rollout_panda_scene.hip), `const RolloutArgs& a_`, `const PandaArgs& pa` and `const SceneT& sc_`.
     PANDA_CORNER_LDS(LPS);
     // (a_.lanes samples per 64-wide wavefront: m3_set_rollout_lanes; the idle lanes leave at once)
     // Shadow lanes (quirk Q8, pa.shadows = 1 or 2; reach on an unsharded handle): the reference's reach cost measures every
@@ -25,7 +25,7 @@
     // a wait with nothing else resident on the SIMD to cover it).  Vector registers are plentiful at
     // one wave per SIMD, so they are parked there once.
     RolloutArgs a = a_;
-    PandaScene sc = sc_;
+    SceneT sc = sc_;
     if constexpr (!GENERAL) { a.sampling_random = 0; a.mode_simple = 0; a.full_sigma = 0; a.noise_abs_cost = 0; }
 #pragma unroll
     for (int j = 0; j < 9; ++j) {

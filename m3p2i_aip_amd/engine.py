@@ -330,6 +330,33 @@ class HipEngine:
         """-1: the run-time-scene kernels exactly when the scene is not the default (default); 1 / 0 forced (tests, A/B)."""
         self._ck(self.lib.m3_set_point_scene_instance(self._h, int(on)))
 
+    def set_panda_scene(self, scene=None, **overrides):
+        """Extension, panda_env: the workspace (a mapping with keys of _lib.PANDA_SCENE_DEFAULTS -- base, table, shelf, obs_half
+        as sequences, obs_m, cube_m, mu --, missing keys = the reference's workspace; keyword arguments override single fields;
+        nothing at all = the defaults).  Applies from the next command / rollout / step / cost call.
+        scenes.panda_scene_from_actors derives the mapping from an actor list."""
+        fields = {**(scene or {}), **overrides}
+        self.panda_scene_sets = getattr(self, "panda_scene_sets", 0) + 1     # (what a planner keeps its reading of the scene by)
+        if not fields:
+            self._ck(self.lib.m3_set_panda_scene(self._h, None))
+            return
+        sc = L.panda_scene_fields(fields)
+        self._ck(self.lib.m3_set_panda_scene(self._h, C.byref(sc)))
+
+    def panda_scene(self):
+        sc = L.PandaSceneFields()
+        self._ck(self.lib.m3_get_panda_scene(self._h, C.byref(sc)))
+        return L.panda_scene_dict(sc)
+
+    def set_panda_scene_instance(self, on=-1):
+        """-1: the run-time-scene kernels exactly when geometry or friction are not the defaults (default); 1 / 0 forced
+        (tests, A/B)."""
+        self._ck(self.lib.m3_set_panda_scene_instance(self._h, int(on)))
+
+    def panda_scene_instance_used(self):
+        """whether the last rollout or step launched the run-time-scene instance"""
+        return self.lib.m3_panda_scene_instance_used(self._h) == 1
+
     def set_multi_modal(self, mm):
         self._ck(self.lib.m3_set_multi_modal(self._h, int(bool(mm))))
 

@@ -471,6 +471,12 @@ def _panda_groups(episodes, who):
         cfg = compat.make_config(cn, list(ov))
         if cfg.env_type != "panda_env":
             raise ValueError(f"{who}: episode {idx} is {cfg.env_type} (panda_env only)")
+        # the set's one N-env world is built from its first episode's config and every row steps in that handle's scene: an
+        # episode's own workspace -- its masses included -- would be dropped, so the keys are refused here, not ignored
+        for key in ("panda_scene", "world_panda_scene"):
+            if getattr(cfg, key):
+                raise ValueError(f"{who}: episode {idx}: `{key}` asks for a workspace of its own (m3_set_panda_scene), which the "
+                                 "lockstep panda episodes do not run (one world handle, one scene); use closed_loop.run")
         key = (float(cfg.isaacgym.dt), int(cfg.isaacgym.substeps), cfg.mppi.device, bool(cfg.cube_on_shelf))
         groups.setdefault(key, []).append((idx, (cn, list(ov), cfg, jitter)))
     return groups

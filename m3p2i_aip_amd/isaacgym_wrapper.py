@@ -47,6 +47,40 @@ class IsaacGymConfig:
     point_scene: Optional[dict] = None   # EXTENSION, point_env: field overrides of the arena (_lib.POINT_SCENE_DEFAULTS), e.g.
                                          # {obs_x: -1.0, wall: 2.95}; None = the reference's arena (compat copies the top-level
                                          # `point_scene` config key here)
+    panda_scene: Optional[dict] = None   # EXTENSION, panda_env: field overrides of the workspace (_lib.PANDA_SCENE_DEFAULTS), e.g.
+                                         # {table: [0, 0, 0.99, 0.6, 0.6, 0.025], mu: 0.5}; None = the reference's workspace
+
+
+def panda_workspace(actors=None, overrides=None):
+    """(panda_scene, env_cfg) of a panda_env wrapper built with `actors` (a list shaped like scenes.PANDA_ENV, or None) and the
+    `panda_scene` field overrides on top: the fields of m3_panda_scene as the library will hold them (binary32 values) -- None
+    while they are the reference's workspace bit for bit -- and the actor list whose rows carry the workspace's poses."""
+    env_cfg = [scenes.Actor(**vars(a)) for a in scenes.PANDA_ENV]
+    ws = dict(L.PANDA_SCENE_DEFAULTS)
+    if actors is not None:
+        if [a.name for a in actors] != [a.name for a in env_cfg]:
+            raise ValueError("actors: the names and the order of scenes.PANDA_ENV are fixed")
+        env_cfg = [scenes.Actor(**vars(a)) for a in actors]
+        ws = scenes.panda_scene_from_actors(env_cfg)
+    given = dict(overrides or {})
+    unknown = sorted(set(given) - set(ws))
+    if unknown:
+        raise ValueError(f"panda_scene: unknown field(s) {unknown}: one of {list(ws)}")
+    ws.update(given)
+    ws = L.panda_scene_dict(L.panda_scene_fields(ws))     # (checked lengths; the binary32 values the library holds)
+    ref = L.panda_scene_dict(L.panda_scene_fields(None))
+    for a in env_cfg:      # the rows of the table, the shelf stand, the plate and the robot carry the workspace where it is not
+        key = {"table": "table", "shelf_stand": "shelf", "dyn-obs": "obs_half", "panda": "base"}.get(a.name)   # the reference's
+        if key is None or ws[key] == ref[key]:
+            continue
+        if key in ("table", "shelf"):
+            a.init_pos = list(ws[key][:3])
+            a.size = [2.0 * x for x in ws[key][3:]]
+        elif key == "obs_half":
+            a.size = [2.0 * x for x in ws[key]]
+        else:
+            a.init_pos = list(ws[key])
+    return (None if scenes.panda_scene_is_default(ws) else ws), env_cfg
 
 
 class IsaacGymWrapper:
@@ -67,6 +101,17 @@ class IsaacGymWrapper:
         # the config's `point_scene` field overrides on top of it.  self.point_scene: the resulting field overrides of
         # m3_point_scene, None while the arena is the reference's (planners that attach to this wrapper take them over)
         self.point_scene = None
+        # EXTENSION, panda_env: another workspace -- `actors` (a list shaped like scenes.PANDA_ENV: same names, same order;
+        # table_stand is not part of the dynamics) and / or the config's `panda_scene` field overrides on top of it.
+        # self.panda_scene: the resulting fields of m3_panda_scene, None while the workspace is the reference's (planners that
+        # attach to this wrapper take them over).  The actors' init_pos place the cubes and the plate as they always did.
+        self.panda_scene = None
+        if env_type == "panda_env" and not getattr(cfg, "point_scene", None) and (
+                actors is not None or getattr(cfg, "panda_scene", None)):
+            self.panda_scene, self.env_cfg = panda_workspace(actors, getattr(cfg, "panda_scene", None))
+            actors = None
+        elif env_type != "panda_env" and getattr(cfg, "panda_scene", None):
+            raise ValueError("panda_scene: panda_env only")
         if actors is not None or getattr(cfg, "point_scene", None):
             if env_type != "point_env":
                 raise ValueError("actors / point_scene: point_env only")
@@ -138,6 +183,8 @@ class IsaacGymWrapper:
             device=dev.index or 0, sim_only=True, filter_u=False, cube_on_shelf=cube_on_shelf))
         if self.point_scene is not None:
             self._engine.set_point_scene(self.point_scene)
+        if self.panda_scene is not None:
+            self._engine.set_panda_scene(self.panda_scene)
         if self.point_scenes is not None:
             self._engine.set_point_scene_rows(self.point_scenes)
 

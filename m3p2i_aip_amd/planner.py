@@ -383,6 +383,12 @@ class MPPI():
             self._engine.set_point_scene(arena)
             self._point_scene_pushed = None if arena is None else dict(arena)
             arena_pushed = True
+        # (extension, off by default, panda_env: the wrapper's workspace, by the same rule)
+        if self.env_type == "panda_env":
+            ws = getattr(s, "panda_scene", None)
+            if follow and ws != getattr(self, "_panda_scene_pushed", None):
+                self._engine.set_panda_scene(ws)
+                self._panda_scene_pushed = None if ws is None else dict(ws)
         # (extension, off by default) one arena per SAMPLE: the fused rollout is the step path on a wrapper whose K_local
         # environments carry their own arenas (IsaacGymWrapper(point_scenes=...)), so while the planner follows its wrapper it
         # takes those rows over -- once, and again when the wrapper holds another list (or the single arena was pushed, which
@@ -427,6 +433,34 @@ class MPPI():
         if rows is None or not getattr(self, "follow_sim_scene", True) or getattr(s, "num_envs", None) != self.K_local:
             return None
         return rows
+
+    @property
+    def needs_panda_scene_instance(self):
+        """the fused rollout runs (or, from its next command on, will run) the run-time-scene instance of the panda_env
+        kernels: the workspace it follows, or the one its engine holds, differs from the reference's in more than the masses"""
+        if self.env_type != "panda_env":
+            return False
+        # (asked on every tick of the batched paths: the answer is kept while what it was formed from stands -- the followed
+        # wrapper's fields, or the count of set_panda_scene calls on the engine -- so a tick costs one comparison)
+        following = getattr(self, "follow_sim_scene", True) and self._sim is not None
+        if following:
+            ws = getattr(self._sim, "panda_scene", None)      # what _bind_world pushes; None: the reference's workspace
+            if ws is None:
+                return False
+            key = ("sim", ws)
+        else:
+            key = ("engine", getattr(self._engine, "panda_scene_sets", None))
+        kept = getattr(self, "_needs_panda_scene_kept", None)
+        if kept is not None and kept[0] == key and key[1] is not None:
+            return kept[1]
+        if not following:
+            ws = self._engine.panda_scene() if hasattr(self._engine, "panda_scene") else None
+            if ws is None:
+                return False
+        masses = {k: L.PANDA_SCENE_DEFAULTS[k] for k in ("obs_m", "cube_m")}
+        out = not scenes.panda_scene_is_default({**ws, **masses})
+        self._needs_panda_scene_kept = ((key[0], dict(ws)) if following else key, out)
+        return out
 
     @property
     def has_rollout_scenes(self):
@@ -679,6 +713,10 @@ def command_batch(planners, states):
                              "point_scenes): m3_batch_command does not run those, use planner.command")
         if not isinstance(p._engine, HipEngine):
             raise ValueError(f"command_batch: planner {i} does not run on the HIP library")
+        if p.needs_panda_scene_instance:
+            raise ValueError(f"command_batch: planner {i} plans in a workspace of its own (m3_set_panda_scene: a wrapper with "
+                             "panda_scene / actors, or set_panda_scene by hand): m3_batch_command does not run the run-time-scene "
+                             "instance, use planner.command")
     if len({id(p) for p in planners}) != len(planners):
         raise ValueError("command_batch: a planner is listed twice")
     outs, batched = [None] * len(planners), []

@@ -189,3 +189,60 @@ def spread_point_scenes(n, spread, seed=0, base=None, fields=("box_m", "box_mu_g
                     row[follows[name]] = full[follows[name]] * float(fac)
         rows.append(row)
     return rows
+
+
+# ---- the panda_env workspace as the dynamics see it (m3_panda_scene; HipEngine.set_panda_scene) ----
+PANDA_CUBE_SIZE = 0.05
+
+
+def panda_scene_from_actors(actors) -> dict:
+    """The fields of m3_panda_scene (keys and order of _lib.PANDA_SCENE_DEFAULTS) from an actor list shaped like PANDA_ENV:
+      * `table`, `shelf`: centre from `init_pos`, half extents from `size`; `obs_half` from the plate's `size`;
+      * `base` from the robot's `init_pos`;
+      * masses = 1000 kg/m^3 x volume, as point_scene_from_actors documents (so the plate keeps 0.8 unless its size says
+        otherwise); cubeA and cubeB must agree -- the dynamics know one `cube_m` --, otherwise ValueError;
+      * `mu`: the `friction` of the table, the shelf stand, the plate, the cubes and the robot, which must agree (the dynamics
+        know one contact friction), otherwise ValueError.
+    A cube `size` other than 0.05 is a ValueError: the cube's size is not part of m3_panda_scene, because the CPU oracle the
+    kernels are held to bit for bit carries the cube's bounding radius as a literal, so another size could not be checked.
+    `table_stand` is not part of the dynamics.  Every value is formed in binary64 and rounded once to binary32; a value within
+    two units in the last place of the literal default is PINNED to the literal, so that panda_scene_from_actors(PANDA_ENV)
+    is the default workspace bit for bit and the shipped scene stays on the default-scene kernels."""
+    import numpy as np
+    from ._lib import PANDA_SCENE_DEFAULTS
+    by = {a.name: a for a in actors}
+    for need in ("table", "shelf_stand", "dyn-obs", "cubeA", "cubeB", "panda"):
+        if need not in by:
+            raise ValueError(f"panda_scene_from_actors: no actor {need!r}")
+    for name in ("cubeA", "cubeB"):
+        if any(abs(float(x) - PANDA_CUBE_SIZE) > 1e-12 for x in by[name].size):
+            raise ValueError(f"panda_scene_from_actors: {name} has size {list(by[name].size)}: the cube's size (0.05) is not part "
+                             "of m3_panda_scene -- the oracle the kernels are checked against carries the cube's bounding radius "
+                             "as a literal")
+    vol = {n: float(np.prod([float(x) for x in by[n].size])) for n in ("cubeA", "cubeB", "dyn-obs")}
+    if abs(vol["cubeA"] - vol["cubeB"]) > 1e-15:
+        raise ValueError("panda_scene_from_actors: cubeA and cubeB differ in mass (the dynamics know one cube_m)")
+    frictions = {n: float(by[n].friction) for n in ("table", "shelf_stand", "dyn-obs", "cubeA", "cubeB", "panda")}
+    if len(set(frictions.values())) != 1:
+        raise ValueError(f"panda_scene_from_actors: the actors' frictions differ ({frictions}); the dynamics know one contact "
+                         "friction `mu`")
+
+    def box6(a):
+        return tuple(float(x) for x in a.init_pos) + tuple(0.5 * float(x) for x in a.size)
+
+    d = dict(base=tuple(float(x) for x in by["panda"].init_pos), table=box6(by["table"]), shelf=box6(by["shelf_stand"]),
+             obs_half=tuple(0.5 * float(x) for x in by["dyn-obs"].size), obs_m=1000.0 * vol["dyn-obs"],
+             cube_m=1000.0 * vol["cubeA"], mu=frictions["table"])
+
+    def pin(v, lit):
+        v = float(np.float32(v))
+        return lit if abs(v - lit) <= 2.0 * float(np.spacing(np.float32(abs(lit)))) else v
+
+    return {n: tuple(pin(v, l) for v, l in zip(d[n], lit)) if isinstance(lit, tuple) else pin(d[n], lit)
+            for n, lit in PANDA_SCENE_DEFAULTS.items()}
+
+
+def panda_scene_is_default(scene) -> bool:
+    """whether a mapping of panda scene fields (overrides; None) is the reference's workspace bit for bit in binary32"""
+    from ._lib import PANDA_SCENE_DEFAULTS, panda_scene_fields
+    return bytes(panda_scene_fields(scene)) == bytes(panda_scene_fields(PANDA_SCENE_DEFAULTS))

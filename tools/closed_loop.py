@@ -147,7 +147,8 @@ def run(cn="config_point", overrides=(), ticks=2000, connect=None, until_task=No
     from m3p2i_aip.utils.skill_utils import check_and_apply_suction
     cfg = compat.make_config(cn, overrides)
     tamp = RemoteTamp(connect, cfg.mppi.device) if connect else Tamp(cfg)
-    # (the `world_point_scene` config key: overrides of the real world's arena only -- the planner keeps `point_scene`)
+    # (the `world_point_scene` / `world_panda_scene` config keys: overrides of the real world's arena / workspace only -- the
+    # planner keeps `point_scene` / `panda_scene`)
     real = wrapper.IsaacGymWrapper(compat.world_isaacgym_config(cfg), cfg.env_type, num_envs=1, viewer=False, device=cfg.mppi.device,
                                    cube_on_shelf=cfg.cube_on_shelf)
     nu = real.dofs_per_robot
