@@ -489,6 +489,10 @@ int m3_point_rollout_scenes_set(const m3_handle* h);   /* 0 / 1 */
 int m3_point_rollout_plan(int task, int multi_modal, int mode_simple, int sampling_random, int avoid_dyn_obs, int K_local, int T,
                           int lanes, float dt, int substeps, int solver_iters, int weighted, int scene, int form_request,
                           int want_minima, int out[8]);
+/* Diagnostic, host only (no device call, no handle): the blocks -- device, pinned and host memory, events, peer mappings -- that
+ * the process's handles, batches and episode sets hold right now.  Every object owns its memory through one ledger; an object's
+ * destroy call takes its blocks off the count, so after every object is destroyed the count is what it was before the first. */
+long long m3_owned_blocks_live(void);
 /* Objective.multi_modal (cost_functions.py:9) for a sim_only handle, whose config does not
  * come from an MPPI object; refused on planner handles (fixed at m3_create) */
 int m3_set_multi_modal(m3_handle* h, int multi_modal);

@@ -206,6 +206,7 @@ SYMBOLS = [
     ("m3_set_panda_scene_instance", C.c_int, [_H, C.c_int]),
     ("m3_panda_scene_instance_used", C.c_int, [_H]),
     ("m3_point_rollout_plan", C.c_int, [C.c_int] * 8 + [C.c_float] + [C.c_int] * 6 + [C.POINTER(C.c_int)]),
+    ("m3_owned_blocks_live", C.c_longlong, []),
     ("m3_set_multi_modal", C.c_int, [_H, C.c_int]),
     ("m3_set_plan", C.c_int, [_H, C.c_int, _FP]),
     ("m3_set_action_out", C.c_int, [_H, C.c_void_p]),

@@ -36,6 +36,45 @@ static int fail(m3_handle* h, int code, const char* msg) {
     return code;
 }
 
+// ---- ownership (owned_blocks.hpp): the ledger's release function bound to HIP -- the one place that frees -- and one helper
+// per kind, the only places that allocate: allocate, adopt into the object's ledger, write the object's view ----
+void m3_release_block(BlockKind kind, void* p) {
+    switch (kind) {
+        case BLOCK_DEVICE: (void)hipFree(p); break;
+        case BLOCK_PINNED: (void)hipHostFree(p); break;
+        case BLOCK_HOST: std::free(p); break;
+        case BLOCK_EVENT: (void)hipEventDestroy(static_cast<hipEvent_t>(p)); break;
+        case BLOCK_IPC: (void)hipIpcCloseMemHandle(p); break;
+    }
+}
+extern "C" long long m3_owned_blocks_live(void) { return g_owned_blocks_live.load(); }
+
+// alloc(void**) -> hipError_t; the answer: its error, or out-of-memory if the ledger could not take the block
+template <class T, class F> static hipError_t own_hip(OwnedBlocks& l, BlockKind kind, T*& view, F alloc) {
+    hipError_t e = hipSuccess;
+    const bool ok = own_block(l, kind, view, [&]() -> void* { void* p = nullptr; e = alloc(&p); return e == hipSuccess ? p : nullptr; });
+    return ok ? hipSuccess : e != hipSuccess ? e : hipErrorOutOfMemory;
+}
+// flags 0: hipMalloc; else hipExtMallocWithFlags
+template <class T> static hipError_t own_device(OwnedBlocks& l, T*& view, size_t bytes, unsigned flags = 0) {
+    return own_hip(l, BLOCK_DEVICE, view, [=](void** p) { return flags ? hipExtMallocWithFlags(p, bytes, flags) : hipMalloc(p, bytes); });
+}
+template <class T> static hipError_t own_pinned(OwnedBlocks& l, T*& view, size_t bytes, unsigned flags) {
+    return own_hip(l, BLOCK_PINNED, view, [=](void** p) { return hipHostMalloc(p, bytes, flags); });
+}
+template <class T> static hipError_t own_host(OwnedBlocks& l, T*& view, size_t bytes) {
+    return own_hip(l, BLOCK_HOST, view, [=](void** p) { return (*p = std::malloc(bytes)) ? hipSuccess : hipErrorOutOfMemory; });
+}
+// flags 0: hipEventCreate
+static hipError_t own_event(OwnedBlocks& l, hipEvent_t& view, unsigned flags = 0) {
+    return own_hip(l, BLOCK_EVENT, view, [=](void** p) {
+        return flags ? hipEventCreateWithFlags(reinterpret_cast<hipEvent_t*>(p), flags) : hipEventCreate(reinterpret_cast<hipEvent_t*>(p));
+    });
+}
+static hipError_t own_ipc(OwnedBlocks& l, void*& view, const hipIpcMemHandle_t& ih) {
+    return own_hip(l, BLOCK_IPC, view, [&](void** p) { return hipIpcOpenMemHandle(p, ih, hipIpcMemLazyEnablePeerAccess); });
+}
+
 extern "C" int m3_abi_version(void) { return M3_ABI_VERSION; }
 
 extern "C" const char* m3_last_error(const m3_handle* h) {
@@ -100,7 +139,8 @@ static void default_world(float* w) {
 
 static int alloc_buf(m3_handle* h, int id, long long bytes) {
     if (bytes < 16) bytes = 16;
-    HIPCHK(h, hipMalloc(&h->buf[id], (size_t)bytes));
+    const hipError_t e = own_device(h->mem, h->buf[id], (size_t)bytes);
+    if (e != hipSuccess) { h->err = std::string("hipMalloc(&h->buf[id], (size_t)bytes): ") + hipGetErrorString(e); return M3_ERR_HIP; }
     HIPCHK(h, hipMemsetAsync(h->buf[id], 0, (size_t)bytes, h->stream));
     h->nbytes[id] = bytes;
     return M3_OK;
@@ -253,21 +293,21 @@ extern "C" int m3_create(const m3_config* c, m3_handle** out) {
     if (rc == M3_OK && c->full_sigma) {
         float mats[2 * M3_MAX_NU * M3_MAX_NU];
         for (int i = 0; i < nu * nu; ++i) { mats[i] = (float)chol[i]; mats[nu * nu + i] = (float)sinv[i]; }
-        if (hipMalloc((void**)&h->noise_mats, (size_t)(2 * nu * nu * f)) != hipSuccess ||
+        if (own_device(h->mem, h->noise_mats, (size_t)(2 * nu * nu * f)) != hipSuccess ||
             hipMemcpy(h->noise_mats, mats, (size_t)(2 * nu * nu * f), hipMemcpyHostToDevice) != hipSuccess) rc = M3_ERR_HIP;
     }
     if (h->regen) {
         const long long rl = regen_record_length((int)Kl, (int)T);
         A(M3_BUF_RECORD, rl * f);
         A(M3_BUF_RECORDS_ALL, (Kg / Kl) * rl * f);
-        if (rc == M3_OK && hipMalloc((void**)&h->noise_all, (size_t)(T * Kg * nu * f)) != hipSuccess) rc = M3_ERR_HIP;
+        if (rc == M3_OK && own_device(h->mem, h->noise_all, (size_t)(T * Kg * nu * f)) != hipSuccess) rc = M3_ERR_HIP;
         if (rc == M3_OK && hipMemsetAsync(h->noise_all, 0, (size_t)(T * Kg * nu * f), h->stream) != hipSuccess) rc = M3_ERR_HIP;
-        if (rc == M3_OK && hipMalloc((void**)&h->local_top_idx, M3_TOPK * sizeof(int)) != hipSuccess) rc = M3_ERR_HIP;
+        if (rc == M3_OK && own_device(h->mem, h->local_top_idx, M3_TOPK * sizeof(int)) != hipSuccess) rc = M3_ERR_HIP;
         if (h->p3) {
             A(M3_BUF_RECORD_B, (long long)recb_length((int)T, (int)nu) * f);
             A(M3_BUF_RECORDS_B_ALL, (Kg / Kl) * (long long)recb_length((int)T, (int)nu) * f);
         }
-        if (rc == M3_OK) {   // non-owning aliases (m3_destroy skips them)
+        if (rc == M3_OK) {   // aliases: views of blocks adopted above, no ledger entries of their own
             h->buf[M3_BUF_TRAJ_COST] = h->buf[M3_BUF_RECORD]; h->nbytes[M3_BUF_TRAJ_COST] = Kl * f;
             h->buf[M3_BUF_NOISE] = h->noise_all + (size_t)(c->k_offset / Kl) * T * Kl * nu; h->nbytes[M3_BUF_NOISE] = T * Kl * nu * f;
             h->buf[M3_BUF_NOISE_ALL] = h->noise_all; h->nbytes[M3_BUF_NOISE_ALL] = T * Kg * nu * f;
@@ -276,18 +316,18 @@ extern "C" int m3_create(const m3_config* c, m3_handle** out) {
         A(M3_BUF_RECORD, (long long)record_length((int)T, (int)nu) * f);
         A(M3_BUF_RECORDS_ALL, (Kg / Kl) * (long long)record_length((int)T, (int)nu) * f);
     }
-    if (rc == M3_OK && hipMalloc((void**)&h->world0_dev, 18 * f) != hipSuccess) rc = M3_ERR_HIP;
-    if (rc == M3_OK && hipMalloc((void**)&h->topk_cand, (size_t)topk_workgroups((int)Kg) * M3_TOPK * sizeof(VI)) != hipSuccess) rc = M3_ERR_HIP;
-    if (rc == M3_OK && hipMalloc((void**)&h->part_min, (size_t)mins_workgroups((int)Kg) * 3 * f) != hipSuccess) rc = M3_ERR_HIP;
-    if (rc == M3_OK && hipMalloc((void**)&h->lad, (size_t)ladder_workgroups((int)Kg) * 96 * 3 * f) != hipSuccess) rc = M3_ERR_HIP;
+    if (rc == M3_OK && own_device(h->mem, h->world0_dev, 18 * f) != hipSuccess) rc = M3_ERR_HIP;
+    if (rc == M3_OK && own_device(h->mem, h->topk_cand, (size_t)topk_workgroups((int)Kg) * M3_TOPK * sizeof(VI)) != hipSuccess) rc = M3_ERR_HIP;
+    if (rc == M3_OK && own_device(h->mem, h->part_min, (size_t)mins_workgroups((int)Kg) * 3 * f) != hipSuccess) rc = M3_ERR_HIP;
+    if (rc == M3_OK && own_device(h->mem, h->lad, (size_t)ladder_workgroups((int)Kg) * 96 * 3 * f) != hipSuccess) rc = M3_ERR_HIP;
     // the three-launch update of an unsharded multi-modal handle beyond k_update_small's range (update.hip: k_ladder_search)
     const bool fused_large = Kl == Kg && c->multi_modal && !c->mode_simple && Kg > 4096 && Kg <= 131072 && T * nu <= 2048;
-    if (rc == M3_OK && hipMalloc((void**)&h->wpart, (size_t)((h->regen || fused_large) ? std::max(wsum_chunks((int)Kg), regen_chunks((int)Kg)) : wsum_chunks((int)Kl)) * 3 * T * nu * f) != hipSuccess) rc = M3_ERR_HIP;
-    if (rc == M3_OK && hipMalloc((void**)&h->apart, (size_t)(16 + std::max(apply_workgroups((int)Kg), (h->regen || fused_large) ? regen_chunks((int)Kg) : 0) * 8) * f) != hipSuccess) rc = M3_ERR_HIP;
+    if (rc == M3_OK && own_device(h->mem, h->wpart, (size_t)((h->regen || fused_large) ? std::max(wsum_chunks((int)Kg), regen_chunks((int)Kg)) : wsum_chunks((int)Kl)) * 3 * T * nu * f) != hipSuccess) rc = M3_ERR_HIP;
+    if (rc == M3_OK && own_device(h->mem, h->apart, (size_t)(16 + std::max(apply_workgroups((int)Kg), (h->regen || fused_large) ? regen_chunks((int)Kg) : 0) * 8) * f) != hipSuccess) rc = M3_ERR_HIP;
     if (rc == M3_OK && fused_large) {
         const size_t nl = (size_t)ladder_workgroups((int)Kg);
-        if (hipMalloc((void**)&h->wave_min, (size_t)Kl * 3 * f) != hipSuccess) rc = M3_ERR_HIP;      // (one row per rollout workgroup: <= K_local with one lane per wavefront)
-        if (rc == M3_OK && hipMalloc((void**)&h->lflag, nl * sizeof(int)) != hipSuccess) rc = M3_ERR_HIP;
+        if (own_device(h->mem, h->wave_min, (size_t)Kl * 3 * f) != hipSuccess) rc = M3_ERR_HIP;      // (one row per rollout workgroup: <= K_local with one lane per wavefront)
+        if (rc == M3_OK && own_device(h->mem, h->lflag, nl * sizeof(int)) != hipSuccess) rc = M3_ERR_HIP;
         if (rc == M3_OK && hipMemset(h->lflag, 0, nl * sizeof(int)) != hipSuccess) rc = M3_ERR_HIP;
     }
     if (rc == M3_OK && c->env_type == M3_ENV_PANDA) {
@@ -295,40 +335,32 @@ extern "C" int m3_create(const m3_config* c, m3_handle** out) {
         // mapped host memory the rollout's last wavefront reports its near share into + its counter; and, for a handle
         // whose reach task takes quirk Q8's shadow slots (unsharded), the records between the rollout and
         // k_panda_reach_cost ([T][17][K] floats: 5.4 MB at C4).
-        void* p = nullptr;
-        void* q = nullptr;
         void* d = nullptr;
-        if (hipHostMalloc(&p, sizeof(int), hipHostMallocMapped) != hipSuccess || hipMalloc(&q, sizeof(unsigned long long)) != hipSuccess ||
-            hipMemset(q, 0, sizeof(unsigned long long)) != hipSuccess || hipHostGetDevicePointer(&d, p, 0) != hipSuccess) {
-            if (p) (void)hipHostFree(p);
-            if (q) (void)hipFree(q);
+        if (own_pinned(h->mem, h->panda_busy_hint, sizeof(int), hipHostMallocMapped) != hipSuccess ||
+            own_device(h->mem, h->panda_busy_count, sizeof(unsigned long long)) != hipSuccess ||
+            hipMemset(h->panda_busy_count, 0, sizeof(unsigned long long)) != hipSuccess || hipHostGetDevicePointer(&d, h->panda_busy_hint, 0) != hipSuccess) {
             h->err = "m3_create: the panda rollout's report word (mapped host memory) could not be allocated";
             rc = M3_ERR_HIP;
         } else {
-            h->panda_busy_hint = (int*)p;
             h->panda_busy_hint_dev = (int*)d;
-            h->panda_busy_count = (unsigned long long*)q;
             *h->panda_busy_hint = 0;
         }
         if (rc == M3_OK && Kl == Kg && Kg >= 2 && Kl <= PANDA_REACH_REC_MAX_K &&
-            hipMalloc((void**)&h->panda_reach_rec, (size_t)T * REACH_REC * (size_t)Kl * f) != hipSuccess) rc = M3_ERR_HIP;
+            own_device(h->mem, h->panda_reach_rec, (size_t)T * REACH_REC * (size_t)Kl * f) != hipSuccess) rc = M3_ERR_HIP;
     }
     if (rc == M3_OK && c->env_type == M3_ENV_POINT && !c->sim_only) {
         // the word the two-wavefront rollout form reports a hand-over wait that ran out into (mapped host memory: m3_rollout
         // reads it without a synchronisation, so it refuses the rollout AFTER the one that failed)
-        void* p = nullptr;
         void* d = nullptr;
-        if (hipHostMalloc(&p, sizeof(int), hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&d, p, 0) != hipSuccess) {
-            if (p) (void)hipHostFree(p);
+        if (own_pinned(h->mem, h->rollout_err, sizeof(int), hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&d, h->rollout_err, 0) != hipSuccess) {
             h->err = "m3_create: the point rollout's error word (mapped host memory) could not be allocated";
             rc = M3_ERR_HIP;
         } else {
-            h->rollout_err = (int*)p;
             h->rollout_err_dev = (int*)d;
             *h->rollout_err = 0;
         }
     }
-    if (rc == M3_OK && hipMalloc((void**)&h->wcount, (size_t)(T + 2) * sizeof(int)) != hipSuccess) rc = M3_ERR_HIP;
+    if (rc == M3_OK && own_device(h->mem, h->wcount, (size_t)(T + 2) * sizeof(int)) != hipSuccess) rc = M3_ERR_HIP;
     if (rc == M3_OK && hipMemset(h->wcount, 0, (size_t)(T + 2) * sizeof(int)) != hipSuccess) rc = M3_ERR_HIP;
     if (rc == M3_OK) {
         m3_info init;
@@ -348,39 +380,7 @@ extern "C" int m3_create(const m3_config* c, m3_handle** out) {
 
 extern "C" void m3_destroy(m3_handle* h) {
     if (!h) return;
-    if (h->regen) h->buf[M3_BUF_TRAJ_COST] = h->buf[M3_BUF_NOISE] = h->buf[M3_BUF_NOISE_ALL] = nullptr;   // aliases
-    for (int i = 0; i < M3_BUF_COUNT; ++i)
-        if (h->buf[i]) (void)hipFree(h->buf[i]);
-    if (h->noise_all) (void)hipFree(h->noise_all);
-    if (h->noise_mats) (void)hipFree(h->noise_mats);
-    if (h->local_top_idx) (void)hipFree(h->local_top_idx);
-    if (h->world0_dev) (void)hipFree(h->world0_dev);
-    if (h->topk_cand) (void)hipFree(h->topk_cand);
-    if (h->part_min) (void)hipFree(h->part_min);
-    if (h->lad) (void)hipFree(h->lad);
-    if (h->wpart) (void)hipFree(h->wpart);
-    if (h->apart) (void)hipFree(h->apart);
-    if (h->wcount) (void)hipFree(h->wcount);
-    if (h->wave_min) (void)hipFree(h->wave_min);
-    if (h->lflag) (void)hipFree(h->lflag);
-    if (h->sim_world) (void)hipFree(h->sim_world);
-    if (h->sim_u) (void)hipFree(h->sim_u);
-    if (h->noise_stage) (void)hipFree(h->noise_stage);
-    if (h->order) (void)hipFree(h->order);
-    if (h->order_scratch) (void)hipFree(h->order_scratch);
-    if (h->noise_sorted) (void)hipFree(h->noise_sorted);
-    for (int p = 0; p < MIX_MAX_RANKS; ++p)
-        if (h->peer_ipc[p] && h->peer_base[p]) (void)hipIpcCloseMemHandle(h->peer_base[p]);
-    if (h->xb) (void)hipFree(h->xb);
-    if (h->panda_busy_hint) (void)hipHostFree(h->panda_busy_hint);
-    if (h->rollout_err) (void)hipHostFree(h->rollout_err);
-    if (h->scene_rows_dev) (void)hipFree(h->scene_rows_dev);
-    if (h->scene_rows_host) (void)hipHostFree(h->scene_rows_host);
-    std::free(h->scene_rows);
-    if (h->panda_busy_count) (void)hipFree(h->panda_busy_count);
-    if (h->panda_reach_rec) (void)hipFree(h->panda_reach_rec);
-    for (auto& ev : h->ev)
-        if (ev) (void)hipEventDestroy(ev);
+    h->mem.release_all();
     delete h;
 }
 
@@ -452,8 +452,11 @@ extern "C" int m3_set_ladder_spins(m3_handle* h, int spins) {
 
 extern "C" int m3_enable_timing(m3_handle* h, int on) {
     if (!h) return M3_ERR_BAD_ARG;
-    if (on && !h->ev[0])
-        for (auto& ev : h->ev) HIPCHK(h, hipEventCreate(&ev));
+    if (on && !h->ev[0]) {
+        BlockGroup g(h->mem);   // all four or none
+        for (auto& ev : h->ev) HIPCHK(h, own_event(h->mem, ev));
+        g.keep = true;
+    }
     h->timing = on != 0;
     return M3_OK;
 }
@@ -511,9 +514,11 @@ static int refresh_wave_order(m3_handle* h) {
         return M3_OK;
     if (!h->order) {
         h->order_temp_bytes = wave_order_temp_bytes(c.K_local);
-        HIPCHK(h, hipMalloc((void**)&h->order, sizeof(int) * (size_t)c.K_local));
-        HIPCHK(h, hipMalloc(&h->order_scratch, 3 * sizeof(float) * (size_t)c.K_local + h->order_temp_bytes));
-        HIPCHK(h, hipMalloc((void**)&h->noise_sorted, sizeof(float) * (size_t)c.T * c.K_local * c.nu));
+        BlockGroup g(h->mem);   // all three or none: a failure leaves order null, the next rollout tries again
+        HIPCHK(h, own_device(h->mem, h->order, sizeof(int) * (size_t)c.K_local));
+        HIPCHK(h, own_device(h->mem, h->order_scratch, 3 * sizeof(float) * (size_t)c.K_local + h->order_temp_bytes));
+        HIPCHK(h, own_device(h->mem, h->noise_sorted, sizeof(float) * (size_t)c.T * c.K_local * c.nu));
+        g.keep = true;
     }
     if (relabel && h->regen) {
         // every rank holds every shard's noise block (the other ranks' actions are re-generated from
@@ -571,13 +576,15 @@ static int upload_noise(m3_handle* h, const float* delta, long long n_rows, floa
     (void)who;
     const size_t bytes = (size_t)n_rows * c.T * c.nu * sizeof(float);
     const float* src = delta;
-    float* stage = nullptr;
+    ScopedBlock<float> tmp(h->mem);   // the staging block of a global upload: every exit frees it
     if (!on_device) {
+        float* stage = nullptr;
         if (n_rows == c.K_local) {
-            if (!h->noise_stage) HIPCHK(h, hipMalloc((void**)&h->noise_stage, bytes));
+            if (!h->noise_stage) HIPCHK(h, own_device(h->mem, h->noise_stage, bytes));
             stage = h->noise_stage;
         } else {
-            HIPCHK(h, hipMalloc((void**)&stage, bytes));
+            HIPCHK(h, own_device(h->mem, tmp.p, bytes));
+            stage = tmp.p;
         }
         HIPCHK(h, hipMemcpyAsync(stage, delta, bytes, hipMemcpyHostToDevice, h->stream));
         src = stage;
@@ -587,7 +594,6 @@ static int upload_noise(m3_handle* h, const float* delta, long long n_rows, floa
         launch_transpose_noise(src + r * bl, dst + r * bl, c.K_local, c.T, c.nu, h->stream);
     hipError_t e = hipGetLastError();
     if (!on_device) (void)hipStreamSynchronize(h->stream);  // host buffer may be released
-    if (stage && stage != h->noise_stage) (void)hipFree(stage);
     if (e != hipSuccess) { h->err = std::string("k_transpose_noise: ") + hipGetErrorString(e); return M3_ERR_HIP; }
     note_noise_upload(h);
     return M3_OK;
@@ -619,20 +625,17 @@ static int upload_knots(m3_handle* h, const float* knots, long long n_rows, floa
     if (!(smoothing >= 0.0f)) return fail(h, M3_ERR_BAD_ARG, "m3_set_noise_knots: smoothing must be >= 0");
     const size_t bytes = (size_t)n_rows * c.nu * n_knots * sizeof(float);
     const float* src = knots;
-    float* stage = nullptr;
+    ScopedBlock<float> stage(h->mem);
     if (!on_device) {
-        HIPCHK(h, hipMalloc((void**)&stage, bytes));
-        HIPCHK(h, hipMemcpyAsync(stage, knots, bytes, hipMemcpyHostToDevice, h->stream));
-        src = stage;
+        HIPCHK(h, own_device(h->mem, stage.p, bytes));
+        HIPCHK(h, hipMemcpyAsync(stage.p, knots, bytes, hipMemcpyHostToDevice, h->stream));
+        src = stage.p;
     }
     const size_t bl = (size_t)c.T * c.K_local * c.nu, kl = (size_t)c.K_local * c.nu * n_knots;
     for (long long r = 0; r < n_rows / c.K_local; ++r)
         launch_spline_noise(src + r * kl, dst + r * bl, c.K_local, c.nu, n_knots, c.T, degree, (double)smoothing, h->stream);
     hipError_t e = hipGetLastError();
-    if (stage) {
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipFree(stage);
-    }
+    if (stage.p) (void)hipStreamSynchronize(h->stream);   // (before the block goes)
     if (e != hipSuccess) { h->err = std::string("k_spline_noise: ") + hipGetErrorString(e); return M3_ERR_HIP; }
     note_noise_upload(h);
     return M3_OK;
@@ -697,11 +700,13 @@ extern "C" int m3_set_noise_halton_scrambled(m3_handle* h, int n_knots, int degr
         }
     const long long rows = h->regen ? c.K_global : c.K_local;
     const int k0 = h->regen ? 0 : c.k_offset;
-    float* knots = nullptr;
-    int* tab = nullptr;           // primes | perm offsets | permutations
+    ScopedBlock<float> knots_blk(h->mem);
+    ScopedBlock<int> tab_blk(h->mem);   // primes | perm offsets | permutations
     const size_t ntab = (size_t)ncol + perm_off.size() + perm.size();
-    HIPCHK(h, hipMalloc((void**)&knots, (size_t)rows * ncol * sizeof(float)));
-    if (hipMalloc((void**)&tab, ntab * sizeof(int)) != hipSuccess) { (void)hipFree(knots); return fail(h, M3_ERR_HIP, "m3_set_noise_halton: hipMalloc"); }
+    HIPCHK(h, own_device(h->mem, knots_blk.p, (size_t)rows * ncol * sizeof(float)));
+    if (own_device(h->mem, tab_blk.p, ntab * sizeof(int)) != hipSuccess) return fail(h, M3_ERR_HIP, "m3_set_noise_halton: hipMalloc");
+    float* const knots = knots_blk.p;
+    int* const tab = tab_blk.p;
     std::vector<int> host(primes, primes + ncol);
     host.insert(host.end(), perm_off.begin(), perm_off.end());
     host.insert(host.end(), perm.begin(), perm.end());
@@ -713,9 +718,7 @@ extern "C" int m3_set_noise_halton_scrambled(m3_handle* h, int n_knots, int degr
         // knots [rows][nu][n_knots] == [rows][ncol]: column j * n_knots + q is knot q of control dimension j
         rc = upload_knots(h, knots, rows, h->regen ? h->noise_all : (float*)h->buf[M3_BUF_NOISE], n_knots, degree, smoothing, 1);
     }
-    (void)hipStreamSynchronize(h->stream);     // (also keeps `host` alive until the copy is done)
-    (void)hipFree(knots);
-    (void)hipFree(tab);
+    (void)hipStreamSynchronize(h->stream);     // (also keeps `host` alive until the copy is done; then the two blocks go)
     if (rc != M3_OK && h->err.empty()) h->err = "m3_set_noise_halton failed";
     return rc;
 }
@@ -858,18 +861,12 @@ static int upload_point_scene_rows(m3_handle* h, const m3_point_scene* scenes, c
     const int Kl = h->cfg.K_local;
     const size_t table_bytes = (size_t)POINT_SCENE_ROW_WORDS * Kl * sizeof(float);
     if (!h->scene_rows_dev) {
-        m3_point_scene* rows = static_cast<m3_point_scene*>(std::malloc((size_t)Kl * sizeof(m3_point_scene)));
-        float* host = nullptr;
-        float* dev = nullptr;
-        hipError_t e = rows ? hipSuccess : hipErrorOutOfMemory;
-        if (e == hipSuccess) e = hipHostMalloc((void**)&host, table_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void**)&dev, table_bytes);
-        if (e != hipSuccess) {
-            if (host) (void)hipHostFree(host);
-            std::free(rows);
-            return fail(h, M3_ERR_HIP, (std::string(who) + ": " + hipGetErrorString(e)).c_str());
-        }
-        h->scene_rows = rows; h->scene_rows_host = host; h->scene_rows_dev = dev;
+        BlockGroup g(h->mem);   // all three or none
+        hipError_t e = own_host(h->mem, h->scene_rows, (size_t)Kl * sizeof(m3_point_scene));
+        if (e == hipSuccess) e = own_pinned(h->mem, h->scene_rows_host, table_bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = own_device(h->mem, h->scene_rows_dev, table_bytes);
+        if (e != hipSuccess) return fail(h, M3_ERR_HIP, (std::string(who) + ": " + hipGetErrorString(e)).c_str());
+        g.keep = true;
     } else {
         // the pinned mirror is the source of the previous call's asynchronous upload: that copy is over before it is rewritten
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -881,72 +878,48 @@ static int upload_point_scene_rows(m3_handle* h, const m3_point_scene* scenes, c
     return M3_OK;
 }
 
-// One arena per environment of a sim_only handle.  Every check before any state changes.
-extern "C" int m3_set_point_scene_rows(m3_handle* h, const m3_point_scene* scenes, int n) {
+// m3_set_point_scene_rows (sim_only handles: one arena per environment) and, per_sample, m3_set_point_rollout_scenes (planner
+// handles: one arena per sample of the fused rollout).  Every check before any state changes.
+static int set_point_rows(m3_handle* h, const m3_point_scene* scenes, int n, bool per_sample) {
     if (!h) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_point_scene_rows: point_env only");
-    if (!h->cfg.sim_only)
-        return fail(h, M3_ERR_STATE, "m3_set_point_scene_rows: sim_only handles only (a planner's rollouts share one model: m3_set_point_scene)");
+    const std::string who = per_sample ? "m3_set_point_rollout_scenes" : "m3_set_point_scene_rows";
+    bool& on = per_sample ? h->rollout_scenes_on : h->scene_rows_on;
+    if (h->cfg.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, (who + ": point_env only").c_str());
+    if ((h->cfg.sim_only != 0) == per_sample)
+        return fail(h, M3_ERR_STATE, (who + (per_sample ? ": planner handles only (the environments of a sim_only handle: m3_set_point_scene_rows)"
+                                                        : ": sim_only handles only (a planner's rollouts share one model: m3_set_point_scene)")).c_str());
     if (!scenes) {   // back on the single scene: exactly the kernels of a handle that never had rows (n is not read)
-        h->scene_rows_on = false;
+        on = false;
         return M3_OK;
     }
     const int Kl = h->cfg.K_local;
     if (n != Kl)
-        return fail(h, M3_ERR_SHAPE, ("m3_set_point_scene_rows: n is " + std::to_string(n) + ", the handle's K_local " + std::to_string(Kl)).c_str());
+        return fail(h, M3_ERR_SHAPE, (who + ": n is " + std::to_string(n) + ", the handle's K_local " + std::to_string(Kl)).c_str());
     for (int i = 0; i < n; ++i) {
         const std::string fault = point_scene_fault(scenes[i]);
-        if (!fault.empty()) return fail(h, M3_ERR_BAD_ARG, ("m3_set_point_scene_rows: row " + std::to_string(i) + ": " + fault).c_str());
+        if (!fault.empty()) return fail(h, M3_ERR_BAD_ARG, (who + ": row " + std::to_string(i) + ": " + fault).c_str());
     }
-    const int rc = upload_point_scene_rows(h, scenes, "m3_set_point_scene_rows");
+    const int rc = upload_point_scene_rows(h, scenes, who.c_str());
     if (rc != M3_OK) return rc;
-    h->scene_rows_on = true;
+    on = true;
     return M3_OK;
 }
-
-extern "C" int m3_get_point_scene_row(const m3_handle* h, int row, m3_point_scene* out) {
+// row `row` as it was set, while the feature (`on`: its flag) is on
+static int get_point_row(const m3_handle* h, int row, m3_point_scene* out, bool m3_handle::*on) {
     if (!h || !out) return M3_ERR_BAD_ARG;
     if (h->cfg.env_type != M3_ENV_POINT) return M3_ERR_UNSUPPORTED;
-    if (!h->scene_rows_on) return M3_ERR_STATE;
+    if (!(h->*on)) return M3_ERR_STATE;
     if (row < 0 || row >= h->cfg.K_local) return M3_ERR_BAD_ARG;
     std::memcpy(out, &h->scene_rows[row], sizeof(*out));
     return M3_OK;
 }
 
+extern "C" int m3_set_point_scene_rows(m3_handle* h, const m3_point_scene* scenes, int n) { return set_point_rows(h, scenes, n, false); }
+extern "C" int m3_get_point_scene_row(const m3_handle* h, int row, m3_point_scene* out) { return get_point_row(h, row, out, &m3_handle::scene_rows_on); }
 extern "C" int m3_point_scene_rows_set(const m3_handle* h) { return h ? (h->scene_rows_on ? 1 : 0) : M3_ERR_BAD_ARG; }
 
-// One arena per sample of a planner handle's fused rollout.  Every check before any state changes.
-extern "C" int m3_set_point_rollout_scenes(m3_handle* h, const m3_point_scene* scenes, int n) {
-    if (!h) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_point_rollout_scenes: point_env only");
-    if (h->cfg.sim_only)
-        return fail(h, M3_ERR_STATE, "m3_set_point_rollout_scenes: planner handles only (the environments of a sim_only handle: m3_set_point_scene_rows)");
-    if (!scenes) {   // back on the single scene: exactly the kernels of a handle that never had rows (n is not read)
-        h->rollout_scenes_on = false;
-        return M3_OK;
-    }
-    const int Kl = h->cfg.K_local;
-    if (n != Kl)
-        return fail(h, M3_ERR_SHAPE, ("m3_set_point_rollout_scenes: n is " + std::to_string(n) + ", the handle's K_local " + std::to_string(Kl)).c_str());
-    for (int i = 0; i < n; ++i) {
-        const std::string fault = point_scene_fault(scenes[i]);
-        if (!fault.empty()) return fail(h, M3_ERR_BAD_ARG, ("m3_set_point_rollout_scenes: row " + std::to_string(i) + ": " + fault).c_str());
-    }
-    const int rc = upload_point_scene_rows(h, scenes, "m3_set_point_rollout_scenes");
-    if (rc != M3_OK) return rc;
-    h->rollout_scenes_on = true;
-    return M3_OK;
-}
-
-extern "C" int m3_get_point_rollout_scene(const m3_handle* h, int row, m3_point_scene* out) {
-    if (!h || !out) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_POINT) return M3_ERR_UNSUPPORTED;
-    if (!h->rollout_scenes_on) return M3_ERR_STATE;
-    if (row < 0 || row >= h->cfg.K_local) return M3_ERR_BAD_ARG;
-    std::memcpy(out, &h->scene_rows[row], sizeof(*out));
-    return M3_OK;
-}
-
+extern "C" int m3_set_point_rollout_scenes(m3_handle* h, const m3_point_scene* scenes, int n) { return set_point_rows(h, scenes, n, true); }
+extern "C" int m3_get_point_rollout_scene(const m3_handle* h, int row, m3_point_scene* out) { return get_point_row(h, row, out, &m3_handle::rollout_scenes_on); }
 extern "C" int m3_point_rollout_scenes_set(const m3_handle* h) { return h ? (h->rollout_scenes_on ? 1 : 0) : M3_ERR_BAD_ARG; }
 
 extern "C" int m3_get_point_scene(const m3_handle* h, m3_point_scene* out) {
@@ -1630,10 +1603,11 @@ static int p2p_alloc(m3_handle* h) {
     // uncached: neither the peers' stores nor the owner's loads may be served from a stale L2 line
     // (m3_p2p_set_memory_kind: start further down the fallback chain -- the tests of the fenced paths)
     const int first = h->xb_first_kind;
-    if (first <= 1 && hipExtMallocWithFlags(&h->xb, h->xb_bytes, hipDeviceMallocUncached) == hipSuccess) h->xb_kind = 1;
-    else if ((void)hipGetLastError(), first <= 2 && hipExtMallocWithFlags(&h->xb, h->xb_bytes, hipDeviceMallocFinegrained) == hipSuccess) h->xb_kind = 2;
-    else if ((void)hipGetLastError(), hipMalloc(&h->xb, h->xb_bytes) == hipSuccess) h->xb_kind = 3;
-    else { h->xb = nullptr; return fail(h, M3_ERR_HIP, "m3_p2p: allocation of the exchange block failed"); }
+    // (the ledger holds whichever attempt succeeded, as device memory)
+    if (first <= 1 && own_device(h->mem, h->xb, h->xb_bytes, hipDeviceMallocUncached) == hipSuccess) h->xb_kind = 1;
+    else if ((void)hipGetLastError(), first <= 2 && own_device(h->mem, h->xb, h->xb_bytes, hipDeviceMallocFinegrained) == hipSuccess) h->xb_kind = 2;
+    else if ((void)hipGetLastError(), own_device(h->mem, h->xb, h->xb_bytes) == hipSuccess) h->xb_kind = 3;
+    else return fail(h, M3_ERR_HIP, "m3_p2p: allocation of the exchange block failed");
     HIPCHK(h, hipMemset(h->xb, 0, h->xb_bytes));
     HIPCHK(h, hipDeviceSynchronize());
     const int on = ptr_device(h->xb);
@@ -1702,12 +1676,10 @@ extern "C" int m3_p2p_connect(m3_handle* h, const m3_ipc_handle* all, int n) {
         if (h->peer_ipc[p] && h->peer_base[p]) continue;
         hipIpcMemHandle_t ih;
         std::memcpy(&ih, all[p].bytes, sizeof(ih));
-        void* ptr = nullptr;
-        if (hipIpcOpenMemHandle(&ptr, ih, hipIpcMemLazyEnablePeerAccess) != hipSuccess) {
+        if (own_ipc(h->mem, h->peer_base[p], ih) != hipSuccess) {
             (void)hipGetLastError();
             return fail(h, M3_ERR_HIP, "m3_p2p_connect: hipIpcOpenMemHandle failed (peer block of another process)");
         }
-        h->peer_base[p] = ptr;
         h->peer_ipc[p] = true;
     }
     return p2p_finish_connect(h);
@@ -1931,6 +1903,7 @@ struct m3_batch {
     int device = 0, max_handles = 0;
     std::string err;
     size_t slot_bytes = 0;   // of a slot: the largest table of max_handles handles (batch_table_layout.hpp)
+    OwnedBlocks mem{&m3_release_block, 3 * BATCH_SLOTS};   // owns the slots; the three arrays below are views
     char* host[BATCH_SLOTS] = {};
     char* dev[BATCH_SLOTS] = {};
     hipEvent_t done[BATCH_SLOTS] = {};
@@ -1947,12 +1920,9 @@ extern "C" const char* m3_batch_last_error(const m3_batch* b) { return b ? b->er
 
 extern "C" void m3_batch_destroy(m3_batch* b) {
     if (!b) return;
-    for (int q = 0; q < BATCH_SLOTS; ++q) {
+    for (int q = 0; q < BATCH_SLOTS; ++q)
         if (b->in_flight[q]) (void)hipEventSynchronize(b->done[q]);   // (kernels may still read the device slot)
-        if (b->done[q]) (void)hipEventDestroy(b->done[q]);
-        if (b->dev[q]) (void)hipFree(b->dev[q]);
-        if (b->host[q]) (void)hipHostFree(b->host[q]);
-    }
+    b->mem.release_all();
     delete b;
 }
 
@@ -1989,9 +1959,9 @@ extern "C" int m3_batch_create(int device, int max_handles, m3_batch** out) {
     if (hipGetDevice(&prev) != hipSuccess) prev = -1;
     hipError_t e = hipSetDevice(device);
     for (int q = 0; q < BATCH_SLOTS && e == hipSuccess; ++q) {
-        e = hipHostMalloc((void**)&b->host[q], b->slot_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void**)&b->dev[q], b->slot_bytes);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&b->done[q], hipEventDisableTiming);
+        e = own_pinned(b->mem, b->host[q], b->slot_bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = own_device(b->mem, b->dev[q], b->slot_bytes);
+        if (e == hipSuccess) e = own_event(b->mem, b->done[q], hipEventDisableTiming);
     }
     if (prev >= 0) (void)hipSetDevice(prev);
     if (e != hipSuccess) {
@@ -2233,10 +2203,12 @@ static int ensure_sim(m3_handle* h) {
     const m3_config& c = h->cfg;
     if (!h->sim_world) {
         const size_t nw = (c.env_type == M3_ENV_POINT) ? NW : NWP;
-        HIPCHK(h, hipMalloc((void**)&h->sim_world, nw * c.K_local * sizeof(float)));
+        BlockGroup g(h->mem);   // both or none: a failure leaves sim_world null, the next call tries again
+        HIPCHK(h, own_device(h->mem, h->sim_world, nw * c.K_local * sizeof(float)));
         HIPCHK(h, hipMemsetAsync(h->sim_world, 0, nw * c.K_local * sizeof(float), h->stream));
-        HIPCHK(h, hipMalloc((void**)&h->sim_u, (size_t)c.K_local * c.nu * sizeof(float)));
+        HIPCHK(h, own_device(h->mem, h->sim_u, (size_t)c.K_local * c.nu * sizeof(float)));
         HIPCHK(h, hipMemsetAsync(h->sim_u, 0, (size_t)c.K_local * c.nu * sizeof(float), h->stream));
+        g.keep = true;
     }
     return M3_OK;
 }
@@ -2409,6 +2381,7 @@ struct m3_episodes {
     std::vector<m3_handle*> planners;
     std::vector<const float*> plan;  // each planner's action-out, fixed at create
     std::vector<m3_handle*> live;    // scratch: this tick's batch
+    OwnedBlocks mem{&m3_release_block, 3};   // owns the three blocks; dev, trace and host are views
     char* dev = nullptr;             // lanes | status | gates
     float* trace = nullptr;
     m3_episode_status* host = nullptr;   // pinned copy of the status words
@@ -2420,9 +2393,7 @@ extern "C" const char* m3_episodes_last_error(const m3_episodes* eps) { return e
 extern "C" void m3_episodes_destroy(m3_episodes* eps) {
     if (!eps) return;
     if (eps->world) (void)hipStreamSynchronize(eps->world->stream);   // (kernels may still use the memory)
-    if (eps->dev) (void)hipFree(eps->dev);
-    if (eps->trace) (void)hipFree(eps->trace);
-    if (eps->host) (void)hipHostFree(eps->host);
+    eps->mem.release_all();
     delete eps;
 }
 
@@ -2500,9 +2471,9 @@ extern "C" int m3_episodes_create(m3_handle* world, m3_handle* const* planners, 
         st0[i].final_pos[0] = st0[i].final_pos[1] = 0.0f;
     }
     const hipStream_t s = world->stream;
-    hipError_t e = hipMalloc((void**)&eps->dev, lane_b + st_b + gate_b);
-    if (e == hipSuccess && trace) e = hipMalloc((void**)&eps->trace, (size_t)max_ticks * n * 10 * sizeof(float));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&eps->host, (size_t)n * sizeof(m3_episode_status), hipHostMallocDefault);
+    hipError_t e = own_device(eps->mem, eps->dev, lane_b + st_b + gate_b);
+    if (e == hipSuccess && trace) e = own_device(eps->mem, eps->trace, (size_t)max_ticks * n * 10 * sizeof(float));
+    if (e == hipSuccess) e = own_pinned(eps->mem, eps->host, (size_t)n * sizeof(m3_episode_status), hipHostMallocDefault);
     if (e == hipSuccess) e = hipMemcpyAsync(eps->dev, lanes.data(), (size_t)n * sizeof(m3::EpisodeLane), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(eps->dev + lane_b, st0.data(), (size_t)n * sizeof(m3_episode_status), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(eps->dev + lane_b + st_b, 0, gate_b, s);
@@ -2649,6 +2620,7 @@ struct m3_panda_episodes {
     std::vector<const float*> plan;  // each planner's action-out, fixed at create
     std::vector<m3_handle*> live;    // scratch: this tick's batch
     std::vector<m3_panda_episode_status> mirror;   // the device's status words, advanced on the host by the same pe_advance
+    OwnedBlocks mem{&m3_release_block, 3};   // owns the three blocks; dev, trace and pinned are views (and the three below into them)
     char* dev = nullptr;             // status | plan pointers | kept targets | ended | planning view: dof, root, rigid bodies
     float* trace = nullptr;
     char* pinned = nullptr;          // rigid-body rows of the planning view | ended
@@ -2666,9 +2638,7 @@ extern "C" const char* m3_panda_episodes_last_error(const m3_panda_episodes* eps
 extern "C" void m3_panda_episodes_destroy(m3_panda_episodes* eps) {
     if (!eps) return;
     if (eps->world) (void)hipStreamSynchronize(eps->world->stream);   // (kernels may still use the memory)
-    if (eps->dev) (void)hipFree(eps->dev);
-    if (eps->trace) (void)hipFree(eps->trace);
-    if (eps->pinned) (void)hipHostFree(eps->pinned);
+    eps->mem.release_all();
     delete eps;
 }
 
@@ -2741,10 +2711,10 @@ extern "C" int m3_panda_episodes_create(m3_handle* world, m3_handle* const* plan
     const size_t rb_b = align16((size_t)n * wv.n_bodies * 13 * sizeof(float));
     eps->rb_bytes = (size_t)n * wv.n_bodies * 13 * sizeof(float);
     const hipStream_t s = world->stream;
-    hipError_t e = hipMalloc((void**)&eps->dev, st_b + plan_b + kept_b + end_b + dof_b + root_b + rb_b);
+    hipError_t e = own_device(eps->mem, eps->dev, st_b + plan_b + kept_b + end_b + dof_b + root_b + rb_b);
     if (e == hipSuccess && trace)
-        e = hipMalloc((void**)&eps->trace, (size_t)max_ticks * n * m3::PE_TRACE_FLOATS * sizeof(float));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&eps->pinned, rb_b + end_b, hipHostMallocDefault);
+        e = own_device(eps->mem, eps->trace, (size_t)max_ticks * n * m3::PE_TRACE_FLOATS * sizeof(float));
+    if (e == hipSuccess) e = own_pinned(eps->mem, eps->pinned, rb_b + end_b, hipHostMallocDefault);
     char* d_st = eps->dev;
     char* d_plan = d_st + st_b;
     char* d_kept = d_plan + plan_b;

@@ -10,6 +10,7 @@
 #include "point_cost.hpp"
 #include "panda_dyn.hpp"
 #include "panda_scene.hpp"
+#include "owned_blocks.hpp"
 
 namespace m3 {
 
@@ -437,8 +438,15 @@ void launch_panda_episodes_post(const PandaScene& sc, const PandaEpisodeArgs& a,
 
 }  // namespace m3
 
+// the ledger's release function bound to HIP (m3_api.hip): the one place that frees
+void m3_release_block(m3::BlockKind kind, void* p);
+
 struct m3_handle {
     m3_config cfg;
+    // OWNERSHIP: every block of the handle is an entry of this ledger (owned_blocks.hpp), adopted by one own_* helper call of
+    // m3_api.hip and freed by m3_destroy's release_all().  The named pointers below (buf[], sim_world, order, xb, scene_rows_dev,
+    // ...) are non-owning views the kernels' argument blocks and the getters read; a new buffer is one helper call, nothing else.
+    m3::OwnedBlocks mem{&m3_release_block, 128};
     int* order = nullptr;          // [Kl] lane slot -> local sample (null: identity), sampler.hip
     void* order_scratch = nullptr;
     float* noise_sorted = nullptr; // [T][Kl][nu] noise rows in wavefront order
@@ -470,16 +478,16 @@ struct m3_handle {
     m3_point_scene point_scene = m3::POINT_SCENE_DEFAULT;   // m3_set_point_scene (extension, point_env); survives m3_reset
     m3::PointSceneRT scene_rt = {};    // ... with the handle's dt / substeps / iterations (make_point_scene_rt; m3_create, m3_set_point_scene)
     int scene_instance = -1;           // m3_set_point_scene_instance: -1 by the values (not the defaults bit for bit), 0 / 1 forced
-    // m3_set_point_scene_rows (extension, sim_only point_env): one arena per environment; survive m3_reset.  All three are
-    // allocated by the first m3_set_point_scene_rows on the handle and freed by m3_destroy; nothing else allocates them.
+    // m3_set_point_scene_rows (extension, sim_only point_env): one arena per environment; survive m3_reset.  All three blocks
+    // are allocated as one group by the first m3_set_point_scene_rows on the handle; nothing else allocates them.
     bool scene_rows_on = false;        // the step and the episode tick take the per-row kernels
     // m3_set_point_rollout_scenes (extension, point_env planner handles): one arena per sample of the fused rollout; survive
     // m3_reset.  A handle is a planner or sim_only for life, so the rows live in the same three blocks, allocated by the first
     // m3_set_point_rollout_scenes on the handle.
     bool rollout_scenes_on = false;    // m3_rollout / m3_command take the per-sample kernels
-    m3_point_scene* scene_rows = nullptr;   // host [Kl]: what was set (m3_get_point_scene_row)
-    float* scene_rows_host = nullptr;  // pinned host [POINT_SCENE_ROW_WORDS][Kl]: the table as uploaded (point_scene_rows.hpp)
-    float* scene_rows_dev = nullptr;   // device, the same
+    m3_point_scene* scene_rows = nullptr;   // view, host [Kl]: what was set (m3_get_point_scene_row)
+    float* scene_rows_host = nullptr;  // view, pinned host [POINT_SCENE_ROW_WORDS][Kl]: the table as uploaded (point_scene_rows.hpp)
+    float* scene_rows_dev = nullptr;   // view, device, the same
     // world
     float world0[18];
     const float* world0_bound = nullptr;  // device, 18 floats (filled by world_from_sim)
@@ -510,7 +518,7 @@ struct m3_handle {
     int panda_reach_busy = 0;
     int panda_lps_used = 0;           // the form of the last panda rollout (m3_panda_lanes_per_sample_used)
     int panda_lps = 0;       // 0 = automatic (rollout_panda.hip: panda_lps_for), 1, 16
-    // device buffers
+    // device buffers (views; regen: three of buf[] alias other blocks and are no ledger entries)
     void* buf[M3_BUF_COUNT] = {};
     long long nbytes[M3_BUF_COUNT] = {};
     float* world0_dev = nullptr;
@@ -535,12 +543,12 @@ struct m3_handle {
     m3::SimViews views{};
     bool views_bound = false;
     // device-side exchange (p2p.hip)
-    void* xb = nullptr;                 // own exchange block: header (flags, error word) + [2][n_ranks][rec_len]
+    void* xb = nullptr;                 // view, own exchange block: header (flags, error word) + [2][n_ranks][rec_len]
     size_t xb_bytes = 0;
     int xb_kind = 0;                    // 1 uncached, 2 fine-grained, 3 plain device memory
     int xb_first_kind = 1;              // where the allocation's fallback chain starts (m3_p2p_set_memory_kind)
     void* peer_base[m3::MIX_MAX_RANKS] = {};   // every rank's block as mapped here (own: xb)
-    bool peer_ipc[m3::MIX_MAX_RANKS] = {};     // opened with hipIpcOpenMemHandle (closed in m3_destroy)
+    bool peer_ipc[m3::MIX_MAX_RANKS] = {};     // opened with hipIpcOpenMemHandle: a ledger entry (m3_p2p_connect does not open it twice)
     bool p2p_ready = false;
     int p2p_seq[2] = {0, 0};           // per channel (0: records, 1: second records of shard_mix = 3)
     int p2p_first_ms = 30000, p2p_ms = 500;   // wait time-outs (m3_p2p_set_timeout_ms)

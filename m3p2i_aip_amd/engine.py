@@ -78,7 +78,44 @@ def make_config(K, T, nu=2, env_type="point_env", multi_modal=False, mode_simple
     return c
 
 
-class HipEngine:
+class _CObject:
+    """The lifetime and error reporting of one C object of the library.  A subclass names the attribute that holds its pointer
+    and the library's destroy and last-error functions; the pointer is null until its create call succeeded and after close()."""
+    _ptr = _destroy = _last_error = None
+
+    def close(self):
+        p = getattr(self, self._ptr, None)
+        if p is not None and p:
+            getattr(self.lib, self._destroy)(p)
+            setattr(self, self._ptr, C.c_void_p())
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, rc):
+        if rc != 0:
+            msg = getattr(self.lib, self._last_error)(getattr(self, self._ptr))   # (a null pointer: the create call's error)
+            raise L.M3Error(f"m3p2i_hip error {rc}: {msg.decode() if msg else ''}")
+
+
+def _scene_rows_array(rows):
+    """rows of field overrides over _lib.POINT_SCENE_DEFAULTS (None: the reference's arena) as a PointSceneFields array"""
+    arr = (L.PointSceneFields * max(len(rows), 1))()
+    for i, fields in enumerate(rows):
+        fields = dict(fields or {})
+        unknown = sorted(set(fields) - set(L.POINT_SCENE_DEFAULTS))
+        if unknown:
+            raise ValueError(f"row {i}: unknown point scene field(s) {unknown}: one of {list(L.POINT_SCENE_DEFAULTS)}")
+        arr[i] = L.PointSceneFields(**{**L.POINT_SCENE_DEFAULTS, **{k: float(v) for k, v in fields.items()}})
+    return arr
+
+
+class HipEngine(_CObject):
+    _ptr, _destroy, _last_error = "_h", "m3_destroy", "m3_last_error"
+
     def __init__(self, cfg: L.Config):
         if not torch.cuda.is_available():
             raise L.M3Error("HipEngine needs a HIP device (torch.cuda.is_available() is False); "
@@ -88,7 +125,7 @@ class HipEngine:
         self._h = C.c_void_p()
         torch.cuda.set_device(cfg.device)
         torch.zeros(1, device=f"cuda:{cfg.device}")  # make sure the HIP context exists
-        L.check(self.lib.m3_create(C.byref(cfg), C.byref(self._h)))
+        self._ck(self.lib.m3_create(C.byref(cfg), C.byref(self._h)))
         self.device = torch.device(f"cuda:{cfg.device}")
         self._views = {}
         self._action_out = None
@@ -102,19 +139,8 @@ class HipEngine:
 
     # ---- lifetime ----
     def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._views.clear()
-            self.lib.m3_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, rc):
-        L.check(rc, self._h)
+        getattr(self, "_views", {}).clear()
+        super().close()
 
     # ---- configuration ----
     def use_torch_stream(self, stream=None):
@@ -280,14 +306,7 @@ class HipEngine:
             self._ck(self.lib.m3_set_point_scene_rows(self._h, None, 0))
             return
         rows = list(rows)
-        arr = (L.PointSceneFields * max(len(rows), 1))()
-        for i, fields in enumerate(rows):
-            fields = dict(fields or {})
-            unknown = sorted(set(fields) - set(L.POINT_SCENE_DEFAULTS))
-            if unknown:
-                raise ValueError(f"row {i}: unknown point scene field(s) {unknown}: one of {list(L.POINT_SCENE_DEFAULTS)}")
-            arr[i] = L.PointSceneFields(**{**L.POINT_SCENE_DEFAULTS, **{k: float(v) for k, v in fields.items()}})
-        self._ck(self.lib.m3_set_point_scene_rows(self._h, arr, len(rows)))
+        self._ck(self.lib.m3_set_point_scene_rows(self._h, _scene_rows_array(rows), len(rows)))
 
     def point_scene_row(self, i):
         """environment i's arena as set by set_point_scene_rows (all fields)"""
@@ -308,14 +327,7 @@ class HipEngine:
             self._ck(self.lib.m3_set_point_rollout_scenes(self._h, None, 0))
             return
         rows = list(rows)
-        arr = (L.PointSceneFields * max(len(rows), 1))()
-        for i, fields in enumerate(rows):
-            fields = dict(fields or {})
-            unknown = sorted(set(fields) - set(L.POINT_SCENE_DEFAULTS))
-            if unknown:
-                raise ValueError(f"row {i}: unknown point scene field(s) {unknown}: one of {list(L.POINT_SCENE_DEFAULTS)}")
-            arr[i] = L.PointSceneFields(**{**L.POINT_SCENE_DEFAULTS, **{k: float(v) for k, v in fields.items()}})
-        self._ck(self.lib.m3_set_point_rollout_scenes(self._h, arr, len(rows)))
+        self._ck(self.lib.m3_set_point_rollout_scenes(self._h, _scene_rows_array(rows), len(rows)))
 
     def point_rollout_scene(self, i):
         """local sample i's arena as set by set_point_rollout_scenes (all fields)"""
@@ -637,12 +649,14 @@ class HipEngine:
         return out
 
 
-class HipBatch:
+class HipBatch(_CObject):
     """One command() of each of several HipEngines (unsharded handles of one environment per call: point_env or
     panda_env, as the first engine's) in one rollout launch and one update launch per group of handles that run the same
     kernel instance (``m3_batch_command``, include/m3p2i_hip.h).  Each engine's results are bit-identical to its own
     ``command()``, a panda_env engine's automatic kernel form included; the batch holds no planner state, only the device
     workspace of its argument table (allocated here, for up to ``max_handles`` engines per call)."""
+
+    _ptr, _destroy, _last_error = "_b", "m3_batch_destroy", "m3_batch_last_error"
 
     def __init__(self, max_handles, device=0):
         if not torch.cuda.is_available():
@@ -653,27 +667,8 @@ class HipBatch:
         self._b = C.c_void_p()
         torch.cuda.set_device(self.device)
         torch.zeros(1, device=self.device)  # make sure the HIP context exists
-        rc = self.lib.m3_batch_create(int(device), self.max_handles, C.byref(self._b))
-        if rc != 0:
-            msg = self.lib.m3_batch_last_error(None)
-            raise L.M3Error(f"m3p2i_hip error {rc}: {msg.decode() if msg else ''}")
+        self._ck(self.lib.m3_batch_create(int(device), self.max_handles, C.byref(self._b)))
         self._arr = (C.c_void_p * self.max_handles)()
-
-    def close(self):
-        if getattr(self, "_b", None) is not None and self._b:
-            self.lib.m3_batch_destroy(self._b)
-            self._b = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, rc):
-        if rc != 0:
-            msg = self.lib.m3_batch_last_error(self._b)
-            raise L.M3Error(f"m3p2i_hip error {rc}: {msg.decode() if msg else ''}")
 
     def command(self, engines, sync_host=False):
         """One MPPI iteration of every engine.  Returns each engine's plan tensor (its set_action_out tensor or the
@@ -703,12 +698,14 @@ class HipBatch:
         return r.value, u.value
 
 
-class HipEpisodes:
+class HipEpisodes(_CObject):
     """N closed-loop point_env episodes in lockstep (``m3_episodes_*``, include/m3p2i_hip.h): row e of the
     N-env world engine (an ``IsaacGymWrapper(num_envs=N)``'s) is episode e's 1-env world, planned by ``engines[e]``.
     ``specs``: one ``(task, goal, dyn_phase, suction, kp_suction)`` per episode, task a name or M3_TASK_* id, suction one of
     ``L.SUCTION_*``.  Each engine's ``set_action_out`` tensor is read here and must stay the same.  The set owns its
     device state and pinned status words; a tick allocates nothing."""
+
+    _ptr, _destroy, _last_error = "_eps", "m3_episodes_destroy", "m3_episodes_last_error"
 
     def __init__(self, world, engines, specs, max_ticks, trace=False):
         self.lib = L.load()
@@ -721,27 +718,8 @@ class HipEpisodes:
             sp[i].goal[0], sp[i].goal[1] = float(goal[0]), float(goal[1])
             sp[i].dyn_phase, sp[i].suction, sp[i].kp_suction = int(phase), int(suction), float(kp)
         self._eps = C.c_void_p()
-        rc = self.lib.m3_episodes_create(world._h, arr, sp, self.n, self.max_ticks, int(self.trace_on), C.byref(self._eps))
-        if rc != 0:
-            msg = self.lib.m3_episodes_last_error(None)
-            raise L.M3Error(f"m3p2i_hip error {rc}: {msg.decode() if msg else ''}")
+        self._ck(self.lib.m3_episodes_create(world._h, arr, sp, self.n, self.max_ticks, int(self.trace_on), C.byref(self._eps)))
         self._status = (L.EpisodeStatus * self.n)()
-
-    def close(self):
-        if getattr(self, "_eps", None) is not None and self._eps:
-            self.lib.m3_episodes_destroy(self._eps)
-            self._eps = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, rc):
-        if rc != 0:
-            msg = self.lib.m3_episodes_last_error(self._eps)
-            raise L.M3Error(f"m3p2i_hip error {rc}: {msg.decode() if msg else ''}")
 
     def tick(self, batch):
         """One tick of every episode: pre kernel, one batched command of the running episodes' planners, post kernel,
@@ -774,12 +752,14 @@ class HipEpisodes:
         return (st, tr) if with_trace else st
 
 
-class HipPandaEpisodes:
+class HipPandaEpisodes(_CObject):
     """N closed-loop panda_env episodes in lockstep (``m3_panda_episodes_*``, include/m3p2i_hip.h): row e of
     the N-env world engine (an ``IsaacGymWrapper(..., "panda_env", num_envs=N)``'s) is episode e's 1-env world, planned by
     ``engines[e]``.  The task planners stay on the host: a tick is ``observe()`` (the link rows they read, one copy, one
     synchronisation), their decisions, ``act(batch, ended)``.  Each engine's ``set_action_out`` tensor is read here and must
     stay the same.  The set owns its device state, planning views and pinned host copy; a tick allocates nothing."""
+
+    _ptr, _destroy, _last_error = "_eps", "m3_panda_episodes_destroy", "m3_panda_episodes_last_error"
 
     def __init__(self, world, engines, max_ticks, settle_ticks=0, trace=False):
         self.lib = L.load()
@@ -787,31 +767,12 @@ class HipPandaEpisodes:
         self.n, self.max_ticks, self.settle_ticks, self.trace_on = len(self.engines), int(max_ticks), int(settle_ticks), bool(trace)
         arr = (C.c_void_p * max(self.n, 1))(*[e._h.value for e in self.engines])
         self._eps = C.c_void_p()
-        rc = self.lib.m3_panda_episodes_create(world._h, arr, self.n, self.max_ticks, self.settle_ticks, int(self.trace_on),
-                                               C.byref(self._eps))
-        if rc != 0:
-            msg = self.lib.m3_panda_episodes_last_error(None)
-            raise L.M3Error(f"m3p2i_hip error {rc}: {msg.decode() if msg else ''}")
+        self._ck(self.lib.m3_panda_episodes_create(world._h, arr, self.n, self.max_ticks, self.settle_ticks, int(self.trace_on),
+                                                   C.byref(self._eps)))
         self._status = (L.PandaEpisodeStatus * self.n)()
         self._ended = (C.c_int * self.n)()
         self._rb = C.POINTER(C.c_float)()
         self.bodies = int(world._simviews[2].shape[1])
-
-    def close(self):
-        if getattr(self, "_eps", None) is not None and self._eps:
-            self.lib.m3_panda_episodes_destroy(self._eps)
-            self._eps = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, rc):
-        if rc != 0:
-            msg = self.lib.m3_panda_episodes_last_error(self._eps)
-            raise L.M3Error(f"m3p2i_hip error {rc}: {msg.decode() if msg else ''}")
 
     def observe(self):
         """Pre kernel, one device-to-host copy, one synchronisation.  Returns the planning view's rigid-body rows as an
