@@ -39,10 +39,13 @@ void launch_spline_noise(const float* knots, float* noise, int Kl, int nu, int n
 // c-th prime (mppi_utils.py:69-96, the in-tree use_ghalton=False branch), accumulated in binary32 digit by
 // digit from the least significant one with the scale 1 / base^d carried in binary64 and rounded per digit --
 // the arithmetic of sampling.radical_inverse, bit for bit -- then sqrt(2) * erfinv(2u - 1) (mppi_utils.py:
-// 99-104).  erfinv is the rational approximation + two Newton steps torch's CPU kernel uses, on the device's
-// erff / expf / logf: those differ from glibc's in the last ulp, so the Gaussian values agree with the host
-// sampler to ~1e-6 relative, not bit for bit (which is why the planner's default keeps the host knots,
-// pinned by golden G8; MPPIConfig.device_knots opts in).
+// 99-104).  erfinv is the rational approximation + two Newton steps torch's CPU kernel uses; the start value goes
+// through the device's logf / sqrtf, which differ from glibc's in the last ulp, so the Gaussian values are not
+// promised bit for bit (which is why the planner's default keeps the host knots, pinned by golden G8;
+// MPPIConfig.device_knots opts in).  Measured against a binary64 evaluation of the same float32 argument 2u - 1
+// (tests/test_device_sampler_edges_gpu.py, profiles/sampler_edges/README.md; 64000 x 32 and 16000 x 99 values, plain
+// and Faure): at most 8.9e-8 absolute for |g| < 1, 1.8e-7 in [1,2), 3.4e-7 in [2,3), 3.6e-7 in [3,4) and 4.6e-7 for
+// |g| >= 4 (one ulp at 4.4) -- in every bin within 1.02 x what the host sampler's own float32 arithmetic loses there.
 __device__ __forceinline__ float dev_erfinv(float y) {
     const float a[4] = {0.886226899f, -1.645349621f, 0.914624893f, -0.140543331f};
     const float b[4] = {-2.118377725f, 1.442710462f, -0.329097515f, 0.012229801f};
@@ -63,10 +66,15 @@ __device__ __forceinline__ float dev_erfinv(float y) {
         const float dem = (d[1] * z + d[0]) * z + 1.0f;
         x = copysignf(num, y) / dem;
     }
-    const float two_over_sqrt_pi = 1.1283791670955126f;
-    x = x - (erff(x) - y) / (two_over_sqrt_pi * expf(-x * x));
-    x = x - (erff(x) - y) / (two_over_sqrt_pi * expf(-x * x));
-    return x;
+    // The two Newton steps on erf(x) - y run in binary64 on the float start value and round once at the end.  In binary32
+    // erff(x) - y is quantised to ulp(1) = 6e-8 near |y| -> 1 and multiplied by sqrt(pi)/2 exp(x^2) (6e3 at |g| = 4.2, 1.4e5
+    // at 4.9): measured on the device, up to 3.4e-6 off for 3 <= |g| < 4 and 3.6e-5 for |g| >= 4, 10 and 80 times what the
+    // reference's own float arithmetic loses there (tests/test_device_sampler_edges_gpu.py).  Once per planner: the cost is nil.
+    const double two_over_sqrt_pi = 1.1283791670955126, yd = (double)y;
+    double xd = (double)x;
+    xd = xd - (erf(xd) - yd) / (two_over_sqrt_pi * exp(-xd * xd));
+    xd = xd - (erf(xd) - yd) / (two_over_sqrt_pi * exp(-xd * xd));
+    return (float)xd;
 }
 
 // perm == nullptr: the plain van der Corput radical inverse (the reference's in-tree branch, mppi_utils.py:69-87).

@@ -81,7 +81,7 @@ class MPPIConfig(object):
     relabel_samples: bool = True      # generated noise rows into wavefront-coherent order (same sample set)
     action_ring: int = 0              # 0: command() returns a fresh tensor each call (mppi.py:238-246 does); n > 0:
                                       # slot (call % n) of a ring the planner owns (no allocator call per command)
-    device_knots: bool = False        # Halton + erfinv knots on the device too (~1e-6 from the host sampler's)
+    device_knots: bool = False        # Halton + erfinv knots on the device too (within 4.6e-7 of binary64, like the host sampler's)
     halton_scramble: str = "none"     # "none": plain Halton (mppi_utils.py:81-87, pinned by golden G8); "faure": the
                                       # generalized Halton structure of the ghalton branch the reference's planner
                                       # takes (mppi.py:465-471, mppi_utils.py:89-95) with Faure's (1992) permutations

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests.native_flags import host_flags
+from tests.spline_edge_series import EDGE_CASES, edge_series, rows_for, scipy_rows, set_fixed_series
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -32,31 +33,42 @@ def fit(lib, Y, k, s, T):
     return out, kn
 
 
-def scipy_fit(Y, k, s, T):
-    import scipy.interpolate as si
-    m = Y.shape[1]
-    x, xe = np.linspace(0, m, m), np.linspace(0, m, T)
-    ref, n = np.zeros((Y.shape[0], T)), np.zeros(Y.shape[0], np.int32)
-    for i in range(Y.shape[0]):
-        tck = si.splrep(x, Y[i], k=k, s=s)
-        ref[i], n[i] = si.splev(xe, tck, ext=3), len(tck[0])
-    return ref, n
+scipy_fit = scipy_rows
 
 
-@pytest.mark.parametrize("m,T,k,s", [(7, 30, 2, 0.5), (5, 20, 2, 0.5), (3, 12, 2, 0.5), (16, 64, 2, 0.5),
-                                     (7, 30, 3, 0.5), (7, 30, 1, 0.5), (7, 30, 2, 0.05), (7, 30, 2, 5.0),
-                                     (12, 50, 2, 0.0), (32, 128, 2, 0.5)])
+PLANNER_CASES = [(7, 30, 2, 0.5), (5, 20, 2, 0.5), (3, 12, 2, 0.5), (16, 64, 2, 0.5), (7, 30, 3, 0.5), (7, 30, 1, 0.5),
+                 (7, 30, 2, 0.05), (7, 30, 2, 5.0), (12, 50, 2, 0.0), (32, 128, 2, 0.5)]
+
+
+@pytest.mark.parametrize("m,T,k,s", PLANNER_CASES + EDGE_CASES)
 def test_identical_to_scipy_fitpack(host_lib, m, T, k, s):
-    rng = np.random.default_rng(m * 1000 + T + k)
-    Y = rng.standard_normal((1500, m))
-    Y[0] = 0.0                      # degenerate: constant series
-    Y[1] = np.arange(m)             # exactly polynomial
-    Y[2] *= 1e-3                    # residual far below s: the polynomial is accepted
-    Y[3] *= 30.0                    # residual far above s: interpolating knots, many p iterations
+    """The first eleven series of every case are the fixed ones of tests/spline_edge_series.py (the first four as before).
+    EDGE_CASES: the table k_spline_noise runs on the device (tests/test_device_sampler_edges_gpu.py), on the float32 series
+    the device gets; the other cases keep their binary64 series."""
+    seed = m * 1000 + T + k
+    if (m, T, k, s) in EDGE_CASES:
+        Y = edge_series(m, rows_for(m), seed).astype(np.float64)
+    else:
+        Y = set_fixed_series(np.random.default_rng(seed).standard_normal((rows_for(m), m)))
     out, kn = fit(host_lib, Y, k, s, T)
     ref, nref = scipy_fit(Y, k, s, T)
     np.testing.assert_array_equal(kn, nref)
     np.testing.assert_array_equal(out, ref)
+
+
+@pytest.mark.parametrize("scramble", ["none", "faure"])
+@pytest.mark.parametrize("K,nu,m", [(3000, 2, 16), (3000, 9, 11), (3000, 2, 64), (3000, 2, 2)])
+def test_degree_one_without_smoothing_returns_its_input(host_lib, K, nu, m, scramble):
+    """k = 1, s = 0, T = m: the evaluation abscissae are the data abscissae and the spline interpolates, so the fit -- rounded to
+    float32 like the noise buffer -- IS its float32 input, bit for bit.  This is how tests/test_device_sampler_edges_gpu.py
+    reads the device's Gaussian Halton knots out of the noise buffer.  (k = 2, 3 interpolate to ~1e-11 relative only: an exact 0.0
+    among the knots comes back as 2.6e-18.)"""
+    from m3p2i_aip_amd import sampling
+    g = sampling.halton_gaussian(K, nu * m, scramble).numpy().reshape(K * nu, m)
+    assert g.dtype == np.float32 and np.isfinite(g).all()
+    out, kn = fit(host_lib, g, 1, 0.0, m)
+    np.testing.assert_array_equal(kn, m + 2)                        # the interpolating spline: every interior point a knot
+    np.testing.assert_array_equal(out.astype(np.float32), g)
 
 
 def test_sampler_knots_reproduce_the_host_sampler(host_lib):
