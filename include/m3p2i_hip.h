@@ -411,6 +411,44 @@ int m3_get_point_cost_weights(const m3_handle* h, m3_point_cost_weights* out);
 /* Test and A/B switch: -1 the automatic choice above (default), 1 the weighted build whatever the weights, 0 never -- with
  * weights other than the defaults the next command / rollout / cost call is then refused (M3_ERR_STATE). */
 int m3_set_weighted_cost_instance(m3_handle* h, int on);
+/* EXTENSION, panda_env only: the literal WEIGHTS of the three panda tasks' costs as per-handle state (the defaults = the
+ * reference's literals, cost_functions.py:91-170) -- what a user of the reference tunes pick-and-place with.
+ * What stays a literal, and why: the 0.1 contact-force threshold of the collision test (a threshold, not a weight; shelf_force
+ * scales what is compared with it); the `1 -` of the place cost (an offset: place_grip scales the whole term); the finger-pad
+ * offset (geometry of the gripper).  pre_height_diff and tilt_cos_theta are no weights either: they are config and objective
+ * (m3_config, m3_set_objective). */
+typedef struct m3_panda_cost_weights {
+    float reach_dist;   /* 10    cost_functions.py:114      |ee - pre-pick goal| */
+    float reach_tilt;   /* 3     :156  get_pick_tilt_cost   ee-to-cube orientation */
+    float pick_goal;    /* 10    :125  |pre-place - cubeA| */
+    float pick_ori;     /* 15    :125  cube-to-goal orientation */
+    float collision;    /* 1000  :170  get_motion_cost's penalty (pick) */
+    float shelf_force;  /* 4     :163  weight of the shelf stand's contact force inside the collision test */
+    float place_grip;   /* 2     :134 */
+} m3_panda_cost_weights;
+void m3_default_panda_cost_weights(m3_panda_cost_weights* w);
+/* Applies from the next command / rollout / cost call; survives m3_reset.  It writes into a fixed member of the handle: no
+ * allocation, no synchronisation.  w == NULL: back to the defaults.  Negative and zero weights are legal; a NaN or infinite
+ * field is M3_ERR_BAD_ARG, the message names the field ("m3_set_panda_cost_weights: pick_ori is not finite") and the handle is
+ * left unchanged; a point_env handle is M3_ERR_UNSUPPORTED ("panda_env only").  Allowed on planner, sharded and sim_only
+ * handles.  Sharded handles: set the same weights on every rank.
+ * Which kernels run.  A handle whose seven floats equal the defaults bit for bit runs exactly the kernels it ran before this
+ * call existed, on every path.  Any other handle runs the weighted family: the rollout on the run-time scene (all tasks, both
+ * samplers, both mppi modes; 1, 8 or 16 lanes per sample and shadow slots versus record + reach-cost kernel chosen as before),
+ * the weighted reach-cost kernel and the weighted step-mode cost of m3_cost, in which each literal is replaced by its weight one
+ * for one -- at the default weights the same bits.  Step, pull and push read no cost and stay as they are.
+ * m3_set_panda_scene_instance / m3_panda_scene_instance_used keep their meaning ("used": whether the handle's workspace needed
+ * the run-time scene); scene instance 0 with a geometry other than the default refuses as before, whatever the weights.
+ * NOT batched: m3_batch_command with a planner that needs the weighted family, and m3_panda_episodes_create / _observe / _act /
+ * _act_first with such a planner, return M3_ERR_UNSUPPORTED (the message names m3_set_panda_cost_weights and the index of the
+ * handle); nothing is launched.  A sim_only world handle with weights is accepted there: its step reads no weight. */
+int m3_set_panda_cost_weights(m3_handle* h, const m3_panda_cost_weights* w);
+int m3_get_panda_cost_weights(const m3_handle* h, m3_panda_cost_weights* out);
+/* Test and A/B switch: -1 the automatic choice above (default), 1 the weighted family whatever the weights, 0 never -- with
+ * weights other than the defaults the next command / rollout / m3_cost is then refused (M3_ERR_STATE: "... forced off ..."). */
+int m3_set_panda_weighted_cost_instance(m3_handle* h, int on);
+/* 0 / 1: whether the last rollout or m3_cost of the handle launched the weighted family */
+int m3_panda_weighted_cost_instance_used(m3_handle* h);
 /* EXTENSION, point_env only: the ARENA as per-handle state -- what a user of the reference edits in the yaml files of config/point_env
  * (5_obs, 1..4_wall, 7_box, 6_dyn_obs) and pointRobot.urdf.  The physical fields of the dynamics' scene, one for one; g, the
  * velocity drive, the solver constants and the spec switches are not part of it.  The defaults are the reference's arena. */

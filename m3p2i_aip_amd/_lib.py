@@ -56,6 +56,14 @@ class PointCostWeights(C.Structure):
     _fields_ = [(n, C.c_float) for n in COST_WEIGHT_DEFAULTS]
 
 
+PANDA_COST_WEIGHT_DEFAULTS = dict(reach_dist=10.0, reach_tilt=3.0, pick_goal=10.0, pick_ori=15.0, collision=1000.0,
+                                  shelf_force=4.0, place_grip=2.0)   # m3_panda_cost_weights, in field order
+
+
+class PandaCostWeights(C.Structure):
+    _fields_ = [(n, C.c_float) for n in PANDA_COST_WEIGHT_DEFAULTS]
+
+
 # m3_point_scene, in field order, with the values of m3_default_point_scene (the reference's arena; the oracle's
 # m3o_point_scene_default): box_I / dyn_I = 16 * (0.4^2 + 0.4^2) / 12 and *_req = 0.3825978 * 0.4 are formed in binary32 there
 def _f32(x):
@@ -205,6 +213,11 @@ SYMBOLS = [
     ("m3_get_panda_scene", C.c_int, [_H, C.POINTER(PandaSceneFields)]),
     ("m3_set_panda_scene_instance", C.c_int, [_H, C.c_int]),
     ("m3_panda_scene_instance_used", C.c_int, [_H]),
+    ("m3_default_panda_cost_weights", None, [C.POINTER(PandaCostWeights)]),
+    ("m3_set_panda_cost_weights", C.c_int, [_H, C.POINTER(PandaCostWeights)]),
+    ("m3_get_panda_cost_weights", C.c_int, [_H, C.POINTER(PandaCostWeights)]),
+    ("m3_set_panda_weighted_cost_instance", C.c_int, [_H, C.c_int]),
+    ("m3_panda_weighted_cost_instance_used", C.c_int, [_H]),
     ("m3_point_rollout_plan", C.c_int, [C.c_int] * 8 + [C.c_float] + [C.c_int] * 6 + [C.POINTER(C.c_int)]),
     ("m3_owned_blocks_live", C.c_longlong, []),
     ("m3_set_multi_modal", C.c_int, [_H, C.c_int]),

@@ -124,6 +124,8 @@ class ExampleConfig:
     avoid_dyn_obs: bool = False     # EXTENSION (not a key of the reference's config_store.py): cost_functions.Objective
     cost_weights: Optional[Dict[str, float]] = None   # EXTENSION, point_env: e.g. `cost_weights={push_align: 2.5}`; None = the
                                                       # reference's literals (cost_functions.Objective, _lib.COST_WEIGHT_DEFAULTS)
+    panda_cost_weights: Optional[Dict[str, float]] = None   # EXTENSION, panda_env: e.g. `panda_cost_weights={pick_ori: 25.0}`;
+                                                            # None = the reference's literals (_lib.PANDA_COST_WEIGHT_DEFAULTS)
     point_scene: Optional[Dict[str, float]] = None    # EXTENSION, point_env: field overrides of the arena, e.g.
                                                       # `point_scene={obs_x: -1.0, wall: 2.95}` (_lib.POINT_SCENE_DEFAULTS); the
                                                       # wrappers built from cfg.isaacgym set it on their engines, the planners
@@ -202,6 +204,14 @@ def make_config(config_name="config_point", overrides=()):
             setattr(cfg, key, dict(given))
     if cfg.panda_scene:
         cfg.isaacgym.panda_scene = dict(cfg.panda_scene)   # (the wrappers are built from cfg.isaacgym)
+    if cfg.panda_cost_weights:
+        if cfg.env_type != "panda_env":
+            raise ValueError("panda_cost_weights: panda_env only")
+        from ._lib import PANDA_COST_WEIGHT_DEFAULTS
+        cfg.panda_cost_weights = dict(cfg.panda_cost_weights)
+        unknown = sorted(set(cfg.panda_cost_weights) - set(PANDA_COST_WEIGHT_DEFAULTS))
+        if unknown:
+            raise ValueError(f"panda_cost_weights: unknown panda cost weight(s) {unknown}: one of {list(PANDA_COST_WEIGHT_DEFAULTS)}")
     return cfg
 
 

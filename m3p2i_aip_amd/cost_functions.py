@@ -61,6 +61,14 @@ class Objective(object):
             if getattr(cfg, "env_type", "point_env") != "point_env":
                 raise ValueError("cost_weights: point_env only")
             self.set_cost_weights(**dict(given))
+        # EXTENSION, off by default: `panda_cost_weights: {pick_ori: 25.0, ...}` likewise for the panda_env costs (keys:
+        # _lib.PANDA_COST_WEIGHT_DEFAULTS, the fields of m3_panda_cost_weights)
+        self._panda_cost_weights = dict(L.PANDA_COST_WEIGHT_DEFAULTS)
+        given = getattr(cfg, "panda_cost_weights", None)
+        if given:
+            if getattr(cfg, "env_type", "point_env") != "panda_env":
+                raise ValueError("panda_cost_weights: panda_env only")
+            self.set_panda_cost_weights(**dict(given))
         _LIVE.add(self)
 
     @property
@@ -83,17 +91,41 @@ class Objective(object):
                 raise ValueError(f"cost weight {k} is not finite")
             self._cost_weights[k] = v
 
+    @property
+    def panda_cost_weights(self):
+        """The seven weights of the panda_env costs (a copy; change them with set_panda_cost_weights)."""
+        return dict(self._panda_cost_weights)
+
+    @property
+    def has_default_panda_cost_weights(self):
+        return self._panda_cost_weights == L.PANDA_COST_WEIGHT_DEFAULTS
+
+    def set_panda_cost_weights(self, **kw):
+        """Replace some of the panda_env weights (the others keep their value); they apply from the next command / compute_cost."""
+        unknown = sorted(set(kw) - set(L.PANDA_COST_WEIGHT_DEFAULTS))
+        if unknown:
+            raise ValueError(f"unknown panda cost weight(s) {unknown}: one of {list(L.PANDA_COST_WEIGHT_DEFAULTS)}")
+        for k, v in kw.items():
+            v = float(np.float32(v))          # (the library's value: a float)
+            if not np.isfinite(v):
+                raise ValueError(f"panda cost weight {k} is not finite")
+            self._panda_cost_weights[k] = v
+
     def push_cost_weights(self, eng):
-        """Hand the weights to an engine that does not hold them yet.  With default weights on an engine that never held
-        others the call is not made at all (an engine without set_point_cost_weights serves such an Objective)."""
-        w = self._cost_weights
-        if getattr(eng, "_cost_weights_pushed", L.COST_WEIGHT_DEFAULTS) == w:
-            return
-        if not hasattr(eng, "set_point_cost_weights"):
-            raise TypeError(f"{type(eng).__name__} has no set_point_cost_weights: non-default cost_weights need the HIP library's "
-                            "engine (m3p2i_aip_amd.engine.HipEngine)")
-        eng.set_point_cost_weights(w)
-        eng._cost_weights_pushed = dict(w)
+        """Hand the weights -- the point_env's and the panda_env's -- to an engine that does not hold them yet.  With default
+        weights on an engine that never held others the call is not made at all (an engine without the setter serves such an
+        Objective)."""
+        for w, defaults, kept, setter, key in (
+                (self._cost_weights, L.COST_WEIGHT_DEFAULTS, "_cost_weights_pushed", "set_point_cost_weights", "cost_weights"),
+                (self._panda_cost_weights, L.PANDA_COST_WEIGHT_DEFAULTS, "_panda_cost_weights_pushed", "set_panda_cost_weights",
+                 "panda_cost_weights")):
+            if getattr(eng, kept, defaults) == w:
+                continue
+            if not hasattr(eng, setter):
+                raise TypeError(f"{type(eng).__name__} has no {setter}: non-default {key} need the HIP library's "
+                                "engine (m3p2i_aip_amd.engine.HipEngine)")
+            getattr(eng, setter)(w)
+            setattr(eng, kept, dict(w))
 
     def update_objective(self, task, goal):
         self.task = task

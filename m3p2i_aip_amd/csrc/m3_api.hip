@@ -1031,6 +1031,72 @@ static const char* panda_scene_unbatched(const m3_handle* h) {
                                   : nullptr;
 }
 
+// ---- the panda_env cost weights (extension; per-handle state like the point ones: a fixed member, no allocation, no
+// synchronisation) ----
+static const char* const PANDA_COST_WEIGHT_NAMES[7] = {"reach_dist", "reach_tilt", "pick_goal", "pick_ori", "collision",
+                                                       "shelf_force", "place_grip"};
+static_assert(sizeof(m3_panda_cost_weights) == 7 * sizeof(float) && sizeof(PandaCostWeights) == sizeof(m3_panda_cost_weights),
+              "m3_panda_cost_weights: seven floats, the layout of PandaCostWeights");
+
+extern "C" void m3_default_panda_cost_weights(m3_panda_cost_weights* w) {
+    if (w) std::memcpy(w, &PANDA_COST_WEIGHTS_DEFAULT, sizeof(*w));
+}
+
+extern "C" int m3_set_panda_cost_weights(m3_handle* h, const m3_panda_cost_weights* w) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_PANDA) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_panda_cost_weights: panda_env only");
+    if (!w) { h->panda_cost_weights = PANDA_COST_WEIGHTS_DEFAULT; return M3_OK; }
+    const float* f = reinterpret_cast<const float*>(w);
+    for (int i = 0; i < 7; ++i)
+        if (!std::isfinite(f[i]))
+            return fail(h, M3_ERR_BAD_ARG, (std::string("m3_set_panda_cost_weights: ") + PANDA_COST_WEIGHT_NAMES[i] + " is not finite").c_str());
+    std::memcpy(&h->panda_cost_weights, w, sizeof(*w));
+    return M3_OK;
+}
+
+extern "C" int m3_get_panda_cost_weights(const m3_handle* h, m3_panda_cost_weights* out) {
+    if (!h || !out) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_PANDA) return M3_ERR_UNSUPPORTED;
+    std::memcpy(out, &h->panda_cost_weights, sizeof(*out));
+    return M3_OK;
+}
+
+extern "C" int m3_set_panda_weighted_cost_instance(m3_handle* h, int on) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_PANDA) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_panda_weighted_cost_instance: panda_env only");
+    if (on < -1 || on > 1) return fail(h, M3_ERR_BAD_ARG, "m3_set_panda_weighted_cost_instance: -1 (by the weights), 0 or 1");
+    h->panda_weighted_instance = on;
+    return M3_OK;
+}
+
+extern "C" int m3_panda_weighted_cost_instance_used(m3_handle* h) { return h ? h->panda_weighted_used : M3_ERR_BAD_ARG; }
+
+// the handle's weights are the defaults bit for bit (-0.0f is not 0.0f here: the kernels multiply by them)
+static bool default_panda_cost_weights(const m3_handle* h) {
+    return std::memcmp(&h->panda_cost_weights, &PANDA_COST_WEIGHTS_DEFAULT, sizeof(PandaCostWeights)) == 0;
+}
+// the weighted kernels (rollout_panda_weights.hip: the rollout, the reach-cost kernel, the step-mode cost -- on the run-time
+// scene, whatever panda_scene_runtime says): by the weights, or as m3_set_panda_weighted_cost_instance says
+static bool panda_weighted(const m3_handle* h) {
+    if (h->cfg.env_type != M3_ENV_PANDA) return false;
+    return h->panda_weighted_instance < 0 ? !default_panda_cost_weights(h) : h->panda_weighted_instance != 0;
+}
+// why the handle cannot run a rollout or a cost (M3_ERR_STATE; nullptr: it can)
+static const char* panda_weights_refusal(const m3_handle* h) {
+    if (h->cfg.env_type != M3_ENV_PANDA) return nullptr;
+    if (h->panda_weighted_instance == 0 && !default_panda_cost_weights(h))
+        return "the weighted cost instance is forced off (m3_set_panda_weighted_cost_instance 0) but the handle's cost weights (m3_set_panda_cost_weights) are not the defaults";
+    return nullptr;
+}
+// why a path whose kernels take the literal cost only (m3_batch_command's table, the lockstep episodes' planners) cannot take
+// the handle.  A sim_only handle passes: its step reads no weight
+static const char* panda_weights_unbatched(const m3_handle* h) {
+    return (!h->cfg.sim_only && panda_weighted(h))
+               ? "its cost weights (m3_set_panda_cost_weights) need the weighted cost instance, which only m3_rollout / "
+                 "m3_command and the handle's own m3_cost run"
+               : nullptr;
+}
+
 extern "C" int m3_set_multi_modal(m3_handle* h, int mm) {
     if (!h) return M3_ERR_BAD_ARG;
     if (!h->cfg.sim_only && (mm != 0) != (h->cfg.multi_modal != 0))
@@ -1187,6 +1253,7 @@ static const char* rollout_refusal(const m3_handle* h) {
         return "m3_rollout: simple mode needs m3_set_noise or sampling_random";
     if (h->task == M3_TASK_PUSH_PULL && !c.multi_modal) return "m3_rollout: push_pull needs multi_modal";
     if (const char* why = panda_scene_refusal(h)) return why;
+    if (const char* why = panda_weights_refusal(h)) return why;
     return point_variant_refusal(h, SIDE_ROLLOUT);
 }
 
@@ -1302,8 +1369,12 @@ extern "C" int m3_rollout(m3_handle* h) {
     if (h->cfg.env_type == M3_ENV_POINT) h->point_form_used = p.form;
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->scene_rt, h->cost_weights, p, h->stream, h->rollout_err_dev, h->scene_rows_dev);
-    else if (panda_scene_runtime(h)) { launch_rollout_panda_s(a, pa, h->pscene_rt, p, h->stream); h->panda_scene_used = 1; }
-    else { launch_rollout_panda(a, pa, h->pscene, p, h->stream); h->panda_scene_used = 0; }
+    else if (panda_weighted(h)) {   // (one family on the run-time scene: "used" keeps saying whether the workspace needed it)
+        launch_rollout_panda_w(a, pa, h->pscene_rt, h->panda_cost_weights, p, h->stream);
+        h->panda_scene_used = panda_scene_runtime(h) ? 1 : 0; h->panda_weighted_used = 1;
+    }
+    else if (panda_scene_runtime(h)) { launch_rollout_panda_s(a, pa, h->pscene_rt, p, h->stream); h->panda_scene_used = 1; h->panda_weighted_used = 0; }
+    else { launch_rollout_panda(a, pa, h->pscene, p, h->stream); h->panda_scene_used = 0; h->panda_weighted_used = 0; }
     HIPCHK(h, hipGetLastError());
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     return M3_OK;
@@ -1997,6 +2068,10 @@ static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code) {
         code = M3_ERR_UNSUPPORTED;
         return why;
     }
+    if (const char* why = panda_weights_unbatched(h)) {   // (... and no weights: its kernels form the literal cost)
+        code = M3_ERR_UNSUPPORTED;
+        return why;
+    }
     fill_update_impl_args(h, u, true);
     code = M3_ERR_UNSUPPORTED;
     if (!can_fuse_finalize(h) || !update_small_applies(u))
@@ -2360,7 +2435,11 @@ extern "C" int m3_cost(m3_handle* h, float* cost) {
         // quirk Q8 exactly where m3_rollout applies it (its shadow lanes): reach on an unsharded handle
         const bool env0_cube = cp.task == 4 && h->cfg.k_offset == 0 && h->cfg.K_local == h->cfg.K_global && h->cfg.K_global >= 2;
         if (const char* why = panda_scene_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_cost: ") + why).c_str());
-        if (panda_scene_runtime(h)) launch_psim_cost_s(h->pscene_rt, cp, h->sim_world, h->cfg.K_local, h->cfg.k_offset, env0_cube, cost, h->stream);
+        if (const char* why = panda_weights_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_cost: ") + why).c_str());
+        h->panda_weighted_used = panda_weighted(h) ? 1 : 0;
+        if (h->panda_weighted_used)
+            launch_psim_cost_w(h->pscene_rt, cp, h->panda_cost_weights, h->sim_world, h->cfg.K_local, h->cfg.k_offset, env0_cube, cost, h->stream);
+        else if (panda_scene_runtime(h)) launch_psim_cost_s(h->pscene_rt, cp, h->sim_world, h->cfg.K_local, h->cfg.k_offset, env0_cube, cost, h->stream);
         else launch_psim_cost(h->pscene, cp, h->sim_world, h->cfg.K_local, h->cfg.k_offset, env0_cube, cost, h->stream);
     }
     HIPCHK(h, hipGetLastError());
@@ -2766,12 +2845,14 @@ static int peps_active(const m3_panda_episodes* eps) {
 
 static int peps_ready(m3_panda_episodes* eps, const char* who) {
     if (peps_active(eps) == 0) { eps->err = std::string(who) + ": every episode has ended and settled"; return M3_ERR_STATE; }
-    // (a workspace set after m3_panda_episodes_create, which refuses it: nothing of this tick is launched)
+    // (a workspace or cost weights set after m3_panda_episodes_create, which refuses them: nothing of this tick is launched)
     for (int i = -1; i < eps->n; ++i) {
         const m3_handle* h = i < 0 ? eps->world : eps->planners[i];
         const char* why = panda_scene_refusal(h);
+        if (!why && i >= 0) why = panda_weights_refusal(h);   // (... or weights: the world's step reads none)
         const int code = why ? M3_ERR_STATE : M3_ERR_UNSUPPORTED;
         if (!why) why = panda_scene_unbatched(h);
+        if (!why) why = panda_weights_unbatched(h);
         if (why) {
             eps->err = std::string(who) + (i < 0 ? ": the world: " : ": planner " + std::to_string(i) + ": ") + why;
             return code;

@@ -421,6 +421,14 @@ void launch_psim_push_s(const PandaSceneRT& sc, const SimViews& v, const float* 
 void launch_psim_cost_s(const PandaSceneRT& sc, const PandaCostParams& cp, const float* world, int Kl, int k0, bool env0_cube,
                         float* cost, hipStream_t s);
 
+// the same for a handle whose cost weights are a kernel argument (m3_set_panda_cost_weights; rollout_panda_weights.hip): the
+// rollout on the run-time scene with the weighted cost -- and, when the plan keeps the record buffer, the weighted reach-cost
+// kernel -- and the step-mode cost.  Step, pull and push read no cost.
+void launch_rollout_panda_w(const RolloutArgs& a, const PandaArgs& pa, const PandaSceneRT& sc, const PandaCostWeights& wt,
+                            const RolloutPlan& p, hipStream_t s);
+void launch_psim_cost_w(const PandaSceneRT& sc, const PandaCostParams& cp, const PandaCostWeights& wt, const float* world, int Kl,
+                        int k0, bool env0_cube, float* cost, hipStream_t s);
+
 // batched closed-loop episodes of the panda_env (m3_panda_episodes_*): one lane per episode of an N-env world
 struct PandaEpisodeArgs {
     SimViews v;                    // the world's views, [n] rows
@@ -475,6 +483,10 @@ struct m3_handle {
     int avoid_dyn_obs = 0;             // m3_set_avoid_dyn_obs (extension; 0 = the reference's compute_cost)
     m3::PointCostWeights cost_weights = m3::POINT_COST_WEIGHTS_DEFAULT;   // m3_set_point_cost_weights (extension, point_env)
     int weighted_instance = -1;        // m3_set_weighted_cost_instance: -1 by the weights (not the defaults bit for bit), 0 / 1 forced
+    // m3_set_panda_cost_weights (extension, panda_env): a fixed member, written in place -- no allocation; survives m3_reset
+    m3::PandaCostWeights panda_cost_weights = m3::PANDA_COST_WEIGHTS_DEFAULT;
+    int panda_weighted_instance = -1;  // m3_set_panda_weighted_cost_instance: -1 by the weights (not the defaults bit for bit), 0 / 1 forced
+    int panda_weighted_used = 0;       // what the last rollout or m3_cost launched (m3_panda_weighted_cost_instance_used)
     m3_point_scene point_scene = m3::POINT_SCENE_DEFAULT;   // m3_set_point_scene (extension, point_env); survives m3_reset
     m3::PointSceneRT scene_rt = {};    // ... with the handle's dt / substeps / iterations (make_point_scene_rt; m3_create, m3_set_point_scene)
     int scene_instance = -1;           // m3_set_point_scene_instance: -1 by the values (not the defaults bit for bit), 0 / 1 forced

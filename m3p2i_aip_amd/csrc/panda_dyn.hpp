@@ -1894,4 +1894,58 @@ __device__ __forceinline__ float panda_cost(const PandaCostParams& cp, const Pan
     return panda_cost(cp, w, o, k, w.A.p, w.A.q);
 }
 
+// EXTENSION (m3_set_panda_cost_weights; the defaults = the reference's literals): every literal WEIGHT of the three panda
+// tasks, the same seven floats in the same order as m3_panda_cost_weights of the public header.  The 0.1 force threshold,
+// the `1 -` of the place cost and the finger-pad offset stay literals; pre_height_diff and tilt_cos_theta are the
+// objective's (PandaCostParams).  Not a member of PandaCostParams: only the weighted kernels (rollout_panda_weights.hip)
+// receive it, as an argument of their own.
+struct PandaCostWeights {
+    float reach_dist;    // 10    cost_functions.py:114   |ee - pre-pick goal|
+    float reach_tilt;    // 3     :156  get_pick_tilt_cost: ee-to-cube orientation
+    float pick_goal;     // 10    :125  |pre-place - cubeA|
+    float pick_ori;      // 15    :125  cube-to-goal orientation
+    float collision;     // 1000  :170  get_motion_cost's penalty (pick)
+    float shelf_force;   // 4     :163  the shelf stand's contact force inside the collision test
+    float place_grip;    // 2     :134
+};
+constexpr PandaCostWeights PANDA_COST_WEIGHTS_DEFAULT = {10.0f, 3.0f, 10.0f, 15.0f, 1000.0f, 4.0f, 2.0f};
+
+// The weighted form (an overload: the literal form above keeps serving every kernel it served): panda_cost with each
+// literal weight replaced by its field, one for one -- same operations, same order, so at PANDA_COST_WEIGHTS_DEFAULT it
+// returns panda_cost's bits (tests/test_panda_cost_weights_cpu.py on a host build of this text,
+// tests/test_panda_cost_weights_gpu.py on the kernels).
+__device__ __forceinline__ float panda_cost(const PandaCostParams& cp, const PandaCostWeights& wt, const PandaWorld& w,
+                                            const PandaObs& o, int k, const float* cube0, const float* q_half0) {
+    if (cp.task == 4) {  // reach
+        float goal[3] = {cube0[0], cube0[1], cube0[2]};
+        if (!cp.multi_modal || k < cp.half_K) {
+            goal[2] = goal[2] + cp.pre_height_diff;
+        } else {
+            goal[0] = goal[0] - cp.pre_height_diff * cp.tilt_cos_theta;
+            goal[2] = goal[2] + cp.pre_height_diff * sqrtf(1.0f - cp.tilt_cos_theta * cp.tilt_cos_theta);
+        }
+        const float dx = (o.left[0] + o.right[0]) / 2.0f - goal[0];
+        const float dy = (o.left[1] + o.right[1]) / 2.0f - goal[1];
+        const float dz = (o.left[2] + o.right[2]) / 2.0f - goal[2];
+        const float reach = sqrtf((dx * dx + dy * dy) + dz * dz);
+        const float tilt = (cp.multi_modal && k >= cp.half_K) ? cp.tilt_cos_theta : 0.0f;
+        const float ori = ori_ee2cube(o.left_q, w.A.q, tilt, q_half0);
+        return wt.reach_dist * reach + wt.reach_tilt * ori;
+    }
+    if (cp.task == 5) {  // pick
+        const float dx = cp.goal[0] - w.A.p[0], dy = cp.goal[1] - w.A.p[1], dz = cp.goal[2] - w.A.p[2];
+        const float gc = sqrtf((dx * dx + dy * dy) + dz * dz);
+        const float ori = ori_cube2goal(w.A.q, &cp.goal[3]);
+        const float fx = (w.f_table[0] + wt.shelf_force * w.f_shelf[0]) + w.f_cubeB[0];
+        const float fy = (w.f_table[1] + wt.shelf_force * w.f_shelf[1]) + w.f_cubeB[1];
+        const float coll = fabsf(fx) + fabsf(fy);
+        return (wt.pick_goal * gc + wt.pick_ori * ori) + ((coll > 0.1f) ? wt.collision : 0.0f);
+    }
+    if (cp.task == 6) {  // place
+        const float dx = o.left[0] - o.right[0], dy = o.left[1] - o.right[1], dz = o.left[2] - o.right[2];
+        return wt.place_grip * (1.0f - sqrtf((dx * dx + dy * dy) + dz * dz));
+    }
+    return 0.0f;
+}
+
 }  // namespace m3

@@ -1,6 +1,6 @@
 // panda_reach_cost_body.inc -- the body of k_panda_reach_cost (rollout_panda.hip), included by the kernel and by its
 // batched form kb_panda_reach_cost (as rollout_panda_body.inc).  In scope where it is included: `const RolloutArgs& a` and
-// `const PandaArgs& pa`.
+// `const PandaArgs& pa`; with the weighted cost hook (PANDA_BODY_COST, rollout_panda_common.hpp) also `const PandaCostWeights& wt`.
     __shared__ float s_c[RC_CH][64];
     const int Kl = a.Kl, T = a.T;
     const int lane = (int)threadIdx.x & 63, slice = (int)threadIdx.x >> 6;
@@ -22,7 +22,7 @@
             for (int j = 0; j < 3; ++j) { o.left[j] = r[(0 + j) * Kl + i]; o.right[j] = r[(3 + j) * Kl + i]; cube0[j] = r[(14 + j) * Kl]; }
 #pragma unroll
             for (int j = 0; j < 4; ++j) { o.left_q[j] = r[(6 + j) * Kl + i]; w.A.q[j] = r[(10 + j) * Kl + i]; qh0[j] = r[(10 + j) * Kl + h]; }
-            const float c = panda_cost(pa.cp, w, o, k, cube0, qh0);
+            const float c = PANDA_BODY_COST(w, o, k, cube0, qh0);
             if (mine) a.cost_h[(size_t)t * Kl + i] = c;
             s_c[tt][lane] = c;
         }

@@ -45,7 +45,6 @@ __global__ __launch_bounds__(64) void k_rollout_panda(const RolloutArgs a_, cons
 // wavefronts instead of one lane walking all T x 17 of them --, the costs meet in LDS and the first wavefront adds them in step
 // order with the rollout's own recurrence (J = J + g c; g = g gamma): the same operations on the same values, the same bits
 // (16 -> 7 us at C4: profiles/r06).
-constexpr int RC_TS = 4, RC_CH = 32;      // time slices per workgroup; steps per LDS chunk
 __global__ __launch_bounds__(64 * RC_TS) void k_panda_reach_cost(const RolloutArgs a, const PandaArgs pa) {
 #include "panda_reach_cost_body.inc"
 }

@@ -1,7 +1,8 @@
 // rollout_panda_body.inc -- the body of k_rollout_panda (rollout_panda.hip), included by the kernel and by its batched form
 // kb_rollout_panda: the same tokens in both, so that k_rollout_panda compiles to exactly the code it did as a plain kernel
 // (as update_small_body.inc).  In scope where it is included: FORCES, GENERAL, LPS, the scene type `SceneT` (PandaScene, or
-// PandaSceneRT in rollout_panda_scene.hip), `const RolloutArgs& a_`, `const PandaArgs& pa` and `const SceneT& sc_`.
+// PandaSceneRT in rollout_panda_scene.hip), `const RolloutArgs& a_`, `const PandaArgs& pa` and `const SceneT& sc_`;
+// with the weighted cost hook (PANDA_BODY_COST, rollout_panda_common.hpp) also `const PandaCostWeights& wt`.
     PANDA_CORNER_LDS(LPS);
     // (a_.lanes samples per 64-wide wavefront: m3_set_rollout_lanes; the idle lanes leave at once)
     // Shadow lanes (quirk Q8, pa.shadows = 1 or 2; reach on an unsharded handle): the reference's reach cost measures every
@@ -153,7 +154,7 @@
 #pragma unroll
             for (int j = 0; j < 4; ++j) qh0[j] = w.A.q[j];
         }
-        const float c = deferred ? 0.0f : panda_cost(pa.cp, w, obs, k, cube0, qh0);
+        const float c = deferred ? 0.0f : PANDA_BODY_COST(w, obs, k, cube0, qh0);   // (the cost hook: rollout_panda_common.hpp)
         if (writer) {
             *reinterpret_cast<float4*>(a.states + ((size_t)t * Kl + i) * 4) =
                 make_float4(w.q[0], w.qd[0], w.q[1], w.qd[1]);                   // reactive_tamp.py:66-69

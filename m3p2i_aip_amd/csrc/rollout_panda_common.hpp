@@ -59,6 +59,17 @@ __device__ __forceinline__ float in_vgpr(float v) {   // keep a uniform value in
     return v;
 }
 
+// The cost hook: the one place where the rollout body (rollout_panda_body.inc) and the reach-cost body
+// (panda_reach_cost_body.inc) form a step's cost, selected at compile time.  Every translation unit but
+// rollout_panda_weights.hip takes this default -- panda_cost with the reference's literals, the call the bodies always made.
+// rollout_panda_weights.hip defines the hook before this header, with the kernel argument `wt` (m3_set_panda_cost_weights).
+#ifndef PANDA_BODY_COST
+#define PANDA_BODY_COST(w, o, k, cube0, qh0) panda_cost(pa.cp, w, o, k, cube0, qh0)
+#endif
+
+// k_panda_reach_cost (rollout_panda.hip) and its weighted twin (rollout_panda_weights.hip)
+constexpr int RC_TS = 4, RC_CH = 32;      // time slices per workgroup; steps per LDS chunk
+
 // ======================= step mode ======================================================
 // SoA world rows (NWP = 77): q 0-8 | qd 9-17 | cubeA 18-30 (pos3 quat4 vel3 angvel3) | cubeB 31-43 | plate pos 44-46,
 // vel 47-49 | held 50 | rel_p 51-53 | rel_q 54-57 | awake 58-59 | f_table 60-62 | f_shelf 63-65 | f_cubeB 66-68 |

@@ -369,6 +369,31 @@ class HipEngine(_CObject):
         """whether the last rollout or step launched the run-time-scene instance"""
         return self.lib.m3_panda_scene_instance_used(self._h) == 1
 
+    def set_panda_cost_weights(self, weights=None):
+        """Extension, panda_env: the weights of the task costs (a mapping with keys of _lib.PANDA_COST_WEIGHT_DEFAULTS, missing
+        keys = the reference's literal; None = all defaults).  They apply from the next command / rollout / cost call."""
+        if weights is None:
+            self._ck(self.lib.m3_set_panda_cost_weights(self._h, None))
+            return
+        unknown = sorted(set(weights) - set(L.PANDA_COST_WEIGHT_DEFAULTS))
+        if unknown:
+            raise ValueError(f"unknown panda cost weight(s) {unknown}: one of {list(L.PANDA_COST_WEIGHT_DEFAULTS)}")
+        w = L.PandaCostWeights(**{**L.PANDA_COST_WEIGHT_DEFAULTS, **{k: float(v) for k, v in weights.items()}})
+        self._ck(self.lib.m3_set_panda_cost_weights(self._h, C.byref(w)))
+
+    def panda_cost_weights(self):
+        w = L.PandaCostWeights()
+        self._ck(self.lib.m3_get_panda_cost_weights(self._h, C.byref(w)))
+        return {n: getattr(w, n) for n in L.PANDA_COST_WEIGHT_DEFAULTS}
+
+    def set_panda_weighted_cost_instance(self, on=-1):
+        """-1: the weighted kernels exactly when the weights are not the defaults (default); 1 / 0 forced (tests, A/B)."""
+        self._ck(self.lib.m3_set_panda_weighted_cost_instance(self._h, int(on)))
+
+    def panda_weighted_cost_instance_used(self):
+        """whether the last rollout or cost call launched the weighted kernels"""
+        return self.lib.m3_panda_weighted_cost_instance_used(self._h) == 1
+
     def set_multi_modal(self, mm):
         self._ck(self.lib.m3_set_multi_modal(self._h, int(bool(mm))))
 

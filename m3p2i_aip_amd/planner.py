@@ -717,6 +717,10 @@ def command_batch(planners, states):
             raise ValueError(f"command_batch: planner {i} plans in a workspace of its own (m3_set_panda_scene: a wrapper with "
                              "panda_scene / actors, or set_panda_scene by hand): m3_batch_command does not run the run-time-scene "
                              "instance, use planner.command")
+        if not getattr(getattr(p, "_objective", None), "has_default_panda_cost_weights", True):
+            raise ValueError(f"command_batch: planner {i} has panda cost weights of its own (m3_set_panda_cost_weights: "
+                             "`panda_cost_weights` / set_panda_cost_weights): m3_batch_command does not run the weighted cost "
+                             "instance, use planner.command")
     if len({id(p) for p in planners}) != len(planners):
         raise ValueError("command_batch: a planner is listed twice")
     outs, batched = [None] * len(planners), []
