@@ -362,8 +362,9 @@ PANDA_FINGER_Z = 0.0584
 PANDA_BASE = (-0.45, 0.0, 1.125)              # panda.yaml:8
 
 
-def generic_chain(q):
-    """Textbook forward kinematics in binary64 from the URDF numbers: T = T * Trans(xyz) * Rx(roll) * Rz(q)."""
+def generic_chain(q, base=PANDA_BASE):
+    """Textbook forward kinematics in binary64 from the URDF numbers: T = T * Trans(xyz) * Rx(roll) * Rz(q); `base`: where the
+    arm stands (the default room's, or a workspace's of m3_set_panda_scene)."""
     def rx(a):
         c, s = np.cos(a), np.sin(a)
         return np.array([[1, 0, 0], [0, c, -s], [0, s, c]])
@@ -372,7 +373,7 @@ def generic_chain(q):
         c, s = np.cos(a), np.sin(a)
         return np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]])
 
-    R, p = np.eye(3), np.array(PANDA_BASE, np.float64)
+    R, p = np.eye(3), np.array(base, np.float64)
     for (xyz, roll), qj in zip(PANDA_URDF, q[:7]):
         p = p + R @ np.array(xyz)
         R = R @ rx(roll) @ rz(qj)
