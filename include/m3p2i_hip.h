@@ -311,6 +311,44 @@ int m3_get_panda_scene(const m3_handle* h, m3_panda_scene* out);
 int m3_set_panda_scene_instance(m3_handle* h, int on);
 /* 0 / 1: whether the last rollout or step of the handle launched the run-time-scene instance */
 int m3_panda_scene_instance_used(m3_handle* h);
+/* One workspace PER ENVIRONMENT of a sim_only panda_env handle (extension): scenes[e] is the workspace of
+ * environment e, n must equal K_local.  From the next m3_sim_step*, m3_sim_pull_state / _push_state and m3_cost on, lane e runs
+ * in scenes[e] (the link poses of the views through scenes[e].base); the step is panda_step in that workspace, bit for bit the
+ * single-scene handle's where the rows agree.  A point_env handle is M3_ERR_UNSUPPORTED ("... panda_env only"), a planner
+ * handle M3_ERR_STATE (its samples take their workspaces from m3_set_panda_rollout_scenes below), n != K_local M3_ERR_SHAPE.
+ * Every row is checked as m3_set_panda_scene checks its scene, before any state changes: a bad field is M3_ERR_BAD_ARG,
+ * "m3_set_panda_scene_rows: row 3: table[5] must be > 0".  scenes == NULL switches the rows off (n is not read): the handle is
+ * back on its single workspace and runs exactly the kernels of a handle that never had rows.  Against m3_set_panda_scene the
+ * last call wins.  The rows survive m3_reset.  The first call on a handle allocates the table (22 words per row; host, pinned
+ * and device copies), later calls reuse it; m3_sim_step*, m3_cost and the views' refresh never allocate because of it.
+ * The rows need the run-time scene: with m3_set_panda_scene_instance(h, 0) the next step / cost / view call is M3_ERR_STATE
+ * ("... forced off ... m3_set_panda_scene_rows"); m3_panda_scene_instance_used reports 1 while rows are on.  m3_cost takes the
+ * handle's cost weights as before (m3_panda_weighted_cost_instance_used keeps saying whether the WEIGHTS needed them).
+ * NOT in the lockstep episodes: m3_panda_episodes_create / _observe / _act / _act_first with such a world return
+ * M3_ERR_UNSUPPORTED (the message names m3_set_panda_scene_rows); nothing is launched. */
+int m3_set_panda_scene_rows(m3_handle* h, const m3_panda_scene* scenes, int n);
+/* row `row` as it was set; M3_ERR_STATE while the rows are off */
+int m3_get_panda_scene_row(const m3_handle* h, int row, m3_panda_scene* out);
+/* 0 / 1: whether the handle is on per-environment workspaces */
+int m3_panda_scene_rows_set(const m3_handle* h);
+/* One workspace PER SAMPLE of a panda_env planner handle's fused rollout (extension) -- a planner that
+ * plans over a spread of models: sample i of m3_rollout / m3_command is simulated in scenes[i], all tasks, both samplers, both
+ * mppi modes, 1, 8 or 16 lanes per sample chosen as before.  n must equal K_local; a sharded handle passes the K_local rows of
+ * its own samples (k_offset .. k_offset + K_local - 1 of the global list).  Checks, NULL, last-call-wins against
+ * m3_set_panda_scene, m3_reset and the allocation: as m3_set_panda_scene_rows; a sim_only handle is M3_ERR_STATE.
+ * Quirk Q8: the reach cost of every sample reads the cube of sample 0 AS SIMULATED IN scenes[0] (multi-modal: the orientation
+ * of sample K / 2 in scenes[K / 2]) -- what the reference would see with per-environment actor properties.
+ * The handle's own step, cost and views (m3_sim_*, m3_cost) keep its single workspace.  The rollout always runs the weighted
+ * cost's kernels, which give the literal cost's bits at the default weights; rows that all equal one scene give the bits of
+ * m3_set_panda_scene with that scene.  m3_panda_scene_instance_used reports 1; m3_set_panda_scene_instance(h, 0) makes the next
+ * command / rollout M3_ERR_STATE ("... forced off ... m3_set_panda_rollout_scenes").
+ * NOT batched: m3_batch_command with such a handle, and m3_panda_episodes_create / _observe / _act / _act_first with such a
+ * planner, return M3_ERR_UNSUPPORTED (the message names m3_set_panda_rollout_scenes and the index of the handle); nothing is
+ * launched. */
+int m3_set_panda_rollout_scenes(m3_handle* h, const m3_panda_scene* scenes, int n);
+int m3_get_panda_rollout_scene(const m3_handle* h, int row, m3_panda_scene* out);
+/* 0 / 1: whether the handle's rollout is on per-sample workspaces */
+int m3_panda_rollout_scenes_set(const m3_handle* h);
 /* launch structure of the unsharded multi-modal update with K beyond the one-launch kernel's range: 0 (default) = three
  * launches (ladder + search in one grid, weights + sums, combine), 5 = the five launches of round 3 (minima, ladder,
  * search, weights, sums), whose sums are added in the order of the sharded "exact" protocols (tests compare those bit

@@ -213,6 +213,12 @@ SYMBOLS = [
     ("m3_get_panda_scene", C.c_int, [_H, C.POINTER(PandaSceneFields)]),
     ("m3_set_panda_scene_instance", C.c_int, [_H, C.c_int]),
     ("m3_panda_scene_instance_used", C.c_int, [_H]),
+    ("m3_set_panda_scene_rows", C.c_int, [_H, C.POINTER(PandaSceneFields), C.c_int]),
+    ("m3_get_panda_scene_row", C.c_int, [_H, C.c_int, C.POINTER(PandaSceneFields)]),
+    ("m3_panda_scene_rows_set", C.c_int, [_H]),
+    ("m3_set_panda_rollout_scenes", C.c_int, [_H, C.POINTER(PandaSceneFields), C.c_int]),
+    ("m3_get_panda_rollout_scene", C.c_int, [_H, C.c_int, C.POINTER(PandaSceneFields)]),
+    ("m3_panda_rollout_scenes_set", C.c_int, [_H]),
     ("m3_default_panda_cost_weights", None, [C.POINTER(PandaCostWeights)]),
     ("m3_set_panda_cost_weights", C.c_int, [_H, C.POINTER(PandaCostWeights)]),
     ("m3_get_panda_cost_weights", C.c_int, [_H, C.POINTER(PandaCostWeights)]),

@@ -20,8 +20,8 @@ OBJ = os.path.join(HERE, "_obj")   # object files (git- and gpurun-ignored)
 SOURCES = ["rollout_point.hip", "rollout_point_task0.hip", "rollout_point_task1.hip", "rollout_point_task2.hip",
            "rollout_point_task3.hip", "rollout_point_scene.hip", "rollout_point_scene_rows.hip",
            "rollout_point_rollout_scenes.hip",
-           "rollout_panda.hip", "rollout_panda_scene.hip", "rollout_panda_weights.hip", "update.hip", "update_small.hip", "update_sharded.hip", "sampler.hip",
-           "p2p.hip", "m3_api.hip"]
+           "rollout_panda.hip", "rollout_panda_scene.hip", "rollout_panda_weights.hip", "rollout_panda_rows.hip",
+           "update.hip", "update_small.hip", "update_sharded.hip", "sampler.hip", "p2p.hip", "m3_api.hip"]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall",
           "-Wno-unused-function"]
 # per-source flags, measured on the bench configs (tools/time_variants_cfg.sh; later flags win; none of them changes
@@ -35,6 +35,7 @@ PER_SOURCE = {
     "rollout_panda.hip": ["-fno-slp-vectorize", "-O2"],   # (round 4, world spec v2: -O2 -1.5 % reach / -4.5 % pick; with SLP +18 % / +11 %)
     "rollout_panda_scene.hip": ["-fno-slp-vectorize", "-O2"],   # (rollout_panda.hip's: the same bodies)
     "rollout_panda_weights.hip": ["-fno-slp-vectorize", "-O2"],   # (likewise)
+    "rollout_panda_rows.hip": ["-fno-slp-vectorize", "-O2"],   # (likewise)
 }
 
 

@@ -143,6 +143,11 @@ class ExampleConfig:
                                                                # each in an arena of their own around point_scene (the samples
                                                                # 0, K / 2 and K - 1 stay nominal); rollout_point_scenes builds
                                                                # the rows the planner's K-env simulator carries
+    rollout_workspace_spread: Optional[Dict[str, object]] = None   # EXTENSION, panda_env: `rollout_workspace_spread={spread: 0.3,
+                                                                   # seed: 1, fields: [cube_m, mu, obs_m]}` -- the planner's K
+                                                                   # rollouts each in a workspace of their own around panda_scene
+                                                                   # (the samples 0, K / 2 and K - 1 stay nominal);
+                                                                   # rollout_panda_scenes builds the rows
 
 
 def make_config(config_name="config_point", overrides=()):
@@ -191,6 +196,9 @@ def make_config(config_name="config_point", overrides=()):
     if cfg.rollout_arena_spread:
         cfg.rollout_arena_spread = dict(cfg.rollout_arena_spread)
         _check_rollout_arena_spread(cfg)
+    if cfg.rollout_workspace_spread:
+        cfg.rollout_workspace_spread = dict(cfg.rollout_workspace_spread)
+        _check_rollout_workspace_spread(cfg)
     for key in ("panda_scene", "world_panda_scene"):
         given = getattr(cfg, key)
         if given:
@@ -244,6 +252,41 @@ def rollout_point_scenes(cfg, k_offset=0, n=None):
     spread, seed, fields = _check_rollout_arena_spread(cfg)
     K = int(cfg.mppi.num_samples)
     rows = scenes.spread_point_scenes(K, spread, seed, base=getattr(cfg, "point_scene", None), fields=fields,
+                                      nominal_rows=(0, K // 2, K - 1))
+    n = K - int(k_offset) if n is None else int(n)
+    return rows[int(k_offset):int(k_offset) + n]
+
+
+def _check_rollout_workspace_spread(cfg):
+    """the parsed `rollout_workspace_spread` key as (spread, seed, fields); ValueError for what it cannot mean"""
+    from ._lib import PANDA_SCENE_DEFAULTS
+    given = dict(cfg.rollout_workspace_spread)
+    if cfg.env_type != "panda_env":
+        raise ValueError("rollout_workspace_spread: panda_env only")
+    unknown = sorted(set(given) - set(ROLLOUT_ARENA_SPREAD_KEYS))
+    if unknown or "spread" not in given:
+        raise ValueError(f"rollout_workspace_spread: {{spread: S, seed: n, fields: [...]}} (unknown key(s) {unknown})")
+    spread = float(given["spread"])
+    if not 0.0 <= spread < 1.0:
+        raise ValueError(f"rollout_workspace_spread: spread {spread!r} is not a share in [0, 1)")
+    fields = tuple(given.get("fields") or ("cube_m", "mu", "obs_m"))
+    unknown = sorted(set(fields) - set(PANDA_SCENE_DEFAULTS))
+    if unknown:
+        raise ValueError(f"rollout_workspace_spread: unknown panda scene field(s) {unknown}: one of {list(PANDA_SCENE_DEFAULTS)}")
+    return spread, int(given.get("seed", 0) or 0), fields
+
+
+def rollout_panda_scenes(cfg, k_offset=0, n=None):
+    """The workspaces of the planner's samples under the `rollout_workspace_spread` key, or None without it: the rows
+    [k_offset, k_offset + n) (all K by default) of scenes.spread_panda_scenes(K, spread, seed, base=panda_scene, fields,
+    nominal_rows=(0, K // 2, K - 1)).  The planner's K-env simulator is built with them (IsaacGymWrapper(panda_scenes=...));
+    the planner attached to it takes them over, so its fused path stays the step path on that simulator."""
+    if not getattr(cfg, "rollout_workspace_spread", None):
+        return None
+    from . import scenes
+    spread, seed, fields = _check_rollout_workspace_spread(cfg)
+    K = int(cfg.mppi.num_samples)
+    rows = scenes.spread_panda_scenes(K, spread, seed, base=getattr(cfg, "panda_scene", None), fields=fields,
                                       nominal_rows=(0, K // 2, K - 1))
     n = K - int(k_offset) if n is None else int(n)
     return rows[int(k_offset):int(k_offset) + n]

@@ -15,6 +15,7 @@
 #include "batch_table_layout.hpp"
 #include "panda_episode_lane.hpp"
 #include "point_scene_rows.hpp"
+#include "panda_scene_rows.hpp"
 
 using namespace m3;
 
@@ -990,8 +991,80 @@ extern "C" int m3_set_panda_scene(m3_handle* h, const m3_panda_scene* sc) {
     if (!fault.empty()) return fail(h, M3_ERR_BAD_ARG, ("m3_set_panda_scene: " + fault).c_str());
     std::memcpy(&h->panda_scene, &src, sizeof(src));
     build_panda_scenes(h->cfg, h->panda_scene, h->pscene, h->pscene_rt);
+    h->panda_scene_rows_on = false;   // the last call wins: the handle is on its single workspace (the rows' memory is kept for a later call)
+    h->panda_rollout_scenes_on = false;
     return M3_OK;
 }
+
+// The rows of a handle -- per environment (sim_only: m3_set_panda_scene_rows) or per sample (planner:
+// m3_set_panda_rollout_scenes) -- into its host copy, pinned mirror and device table: scenes are Kl checked rows.
+// THE allocation of both features: the first call on a handle; later calls reuse the three blocks (K_local is fixed at
+// m3_create).  m3_sim_step*, m3_cost, m3_rollout and m3_command allocate nothing because of the rows -- they read panda_rows_dev
+// and pscene_rt, nothing else.
+static int upload_panda_scene_rows(m3_handle* h, const m3_panda_scene* scenes, const char* who) {
+    const int Kl = h->cfg.K_local;
+    const size_t table_bytes = (size_t)PANDA_SCENE_ROW_WORDS * Kl * sizeof(float);
+    if (!h->panda_rows_dev) {
+        BlockGroup g(h->mem);   // all three or none
+        hipError_t e = own_host(h->mem, h->panda_rows, (size_t)Kl * sizeof(m3_panda_scene));
+        if (e == hipSuccess) e = own_pinned(h->mem, h->panda_rows_host, table_bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = own_device(h->mem, h->panda_rows_dev, table_bytes);
+        if (e != hipSuccess) return fail(h, M3_ERR_HIP, (std::string(who) + ": " + hipGetErrorString(e)).c_str());
+        g.keep = true;
+    } else {
+        // the pinned mirror is the source of the previous call's asynchronous upload: that copy is over before it is rewritten
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    std::memcpy(h->panda_rows, scenes, (size_t)Kl * sizeof(m3_panda_scene));
+    for (int i = 0; i < Kl; ++i)
+        panda_scene_row_pack(make_panda_scene_rt(scenes[i], h->cfg.dt, h->cfg.substeps), h->panda_rows_host, Kl, i);
+    HIPCHK(h, hipMemcpyAsync(h->panda_rows_dev, h->panda_rows_host, table_bytes, hipMemcpyHostToDevice, h->stream));
+    return M3_OK;
+}
+
+// m3_set_panda_scene_rows (sim_only handles: one workspace per environment) and, per_sample, m3_set_panda_rollout_scenes
+// (planner handles: one workspace per sample of the fused rollout).  Every check before any state changes.
+static int set_panda_rows(m3_handle* h, const m3_panda_scene* scenes, int n, bool per_sample) {
+    if (!h) return M3_ERR_BAD_ARG;
+    const std::string who = per_sample ? "m3_set_panda_rollout_scenes" : "m3_set_panda_scene_rows";
+    bool& on = per_sample ? h->panda_rollout_scenes_on : h->panda_scene_rows_on;
+    if (h->cfg.env_type != M3_ENV_PANDA) return fail(h, M3_ERR_UNSUPPORTED, (who + ": panda_env only").c_str());
+    if ((h->cfg.sim_only != 0) == per_sample)
+        return fail(h, M3_ERR_STATE, (who + (per_sample ? ": planner handles only (the environments of a sim_only handle: m3_set_panda_scene_rows)"
+                                                        : ": sim_only handles only (the samples of a planner's rollout: m3_set_panda_rollout_scenes)")).c_str());
+    if (!scenes) {   // back on the single workspace: exactly the kernels of a handle that never had rows (n is not read)
+        on = false;
+        return M3_OK;
+    }
+    const int Kl = h->cfg.K_local;
+    if (n != Kl)
+        return fail(h, M3_ERR_SHAPE, (who + ": n is " + std::to_string(n) + ", the handle's K_local " + std::to_string(Kl)).c_str());
+    for (int i = 0; i < n; ++i) {
+        const std::string fault = panda_scene_fault(scenes[i]);
+        if (!fault.empty()) return fail(h, M3_ERR_BAD_ARG, (who + ": row " + std::to_string(i) + ": " + fault).c_str());
+    }
+    const int rc = upload_panda_scene_rows(h, scenes, who.c_str());
+    if (rc != M3_OK) return rc;
+    on = true;
+    return M3_OK;
+}
+// row `row` as it was set, while the feature (`on`: its flag) is on
+static int get_panda_row(const m3_handle* h, int row, m3_panda_scene* out, bool m3_handle::*on) {
+    if (!h || !out) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_PANDA) return M3_ERR_UNSUPPORTED;
+    if (!(h->*on)) return M3_ERR_STATE;
+    if (row < 0 || row >= h->cfg.K_local) return M3_ERR_BAD_ARG;
+    std::memcpy(out, &h->panda_rows[row], sizeof(*out));
+    return M3_OK;
+}
+
+extern "C" int m3_set_panda_scene_rows(m3_handle* h, const m3_panda_scene* scenes, int n) { return set_panda_rows(h, scenes, n, false); }
+extern "C" int m3_get_panda_scene_row(const m3_handle* h, int row, m3_panda_scene* out) { return get_panda_row(h, row, out, &m3_handle::panda_scene_rows_on); }
+extern "C" int m3_panda_scene_rows_set(const m3_handle* h) { return h ? (h->panda_scene_rows_on ? 1 : 0) : M3_ERR_BAD_ARG; }
+
+extern "C" int m3_set_panda_rollout_scenes(m3_handle* h, const m3_panda_scene* scenes, int n) { return set_panda_rows(h, scenes, n, true); }
+extern "C" int m3_get_panda_rollout_scene(const m3_handle* h, int row, m3_panda_scene* out) { return get_panda_row(h, row, out, &m3_handle::panda_rollout_scenes_on); }
+extern "C" int m3_panda_rollout_scenes_set(const m3_handle* h) { return h ? (h->panda_rollout_scenes_on ? 1 : 0) : M3_ERR_BAD_ARG; }
 
 extern "C" int m3_get_panda_scene(const m3_handle* h, m3_panda_scene* out) {
     if (!h || !out) return M3_ERR_BAD_ARG;
@@ -1020,6 +1093,11 @@ static bool panda_scene_runtime(const m3_handle* h) {
 // why the handle cannot run its kernels (M3_ERR_STATE; nullptr: it can)
 static const char* panda_scene_refusal(const m3_handle* h) {
     if (h->cfg.env_type != M3_ENV_PANDA) return nullptr;
+    // (the rows' kernels are run-time-scene kernels: rollout_panda_rows.hip)
+    if (h->panda_scene_instance == 0 && h->panda_scene_rows_on)
+        return "the run-time-scene instance is forced off (m3_set_panda_scene_instance 0) but the handle has a workspace per environment (m3_set_panda_scene_rows)";
+    if (h->panda_scene_instance == 0 && h->panda_rollout_scenes_on)
+        return "the run-time-scene instance is forced off (m3_set_panda_scene_instance 0) but the handle has a workspace per sample (m3_set_panda_rollout_scenes)";
     if (h->panda_scene_instance == 0 && !panda_scene_geometry_is_default(h->panda_scene))
         return "the run-time-scene instance is forced off (m3_set_panda_scene_instance 0) but the handle's workspace (m3_set_panda_scene) is not the default";
     return nullptr;
@@ -1029,6 +1107,14 @@ static const char* panda_scene_unbatched(const m3_handle* h) {
     return panda_scene_runtime(h) ? "its workspace (m3_set_panda_scene) needs the run-time-scene instance, which only m3_rollout / "
                                     "m3_command and the handle's own step, cost and views run"
                                   : nullptr;
+}
+// ... or a handle with a workspace per row, whose kernels (rollout_panda_rows.hip) only the handle's own calls launch
+static const char* panda_rows_unbatched(const m3_handle* h) {
+    if (h->panda_rollout_scenes_on)
+        return "it has a workspace per sample (m3_set_panda_rollout_scenes), which only m3_rollout / m3_command run";
+    if (h->panda_scene_rows_on)
+        return "it has a workspace per environment (m3_set_panda_scene_rows), which only the handle's own step, cost and views run";
+    return nullptr;
 }
 
 // ---- the panda_env cost weights (extension; per-handle state like the point ones: a fixed member, no allocation, no
@@ -1369,6 +1455,10 @@ extern "C" int m3_rollout(m3_handle* h) {
     if (h->cfg.env_type == M3_ENV_POINT) h->point_form_used = p.form;
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->scene_rt, h->cost_weights, p, h->stream, h->rollout_err_dev, h->scene_rows_dev);
+    else if (h->panda_rollout_scenes_on) {   // (one family, weights always: "used" keeps saying whether the WEIGHTS needed them)
+        launch_rollout_panda_v(a, pa, h->pscene_rt, h->panda_cost_weights, h->panda_rows_dev, p, h->stream);
+        h->panda_scene_used = 1; h->panda_weighted_used = panda_weighted(h) ? 1 : 0;
+    }
     else if (panda_weighted(h)) {   // (one family on the run-time scene: "used" keeps saying whether the workspace needed it)
         launch_rollout_panda_w(a, pa, h->pscene_rt, h->panda_cost_weights, p, h->stream);
         h->panda_scene_used = panda_scene_runtime(h) ? 1 : 0; h->panda_weighted_used = 1;
@@ -2068,6 +2158,10 @@ static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code) {
         code = M3_ERR_UNSUPPORTED;
         return why;
     }
+    if (const char* why = panda_rows_unbatched(h)) {   // (... and no table of rows)
+        code = M3_ERR_UNSUPPORTED;
+        return why;
+    }
     if (const char* why = panda_weights_unbatched(h)) {   // (... and no weights: its kernels form the literal cost)
         code = M3_ERR_UNSUPPORTED;
         return why;
@@ -2322,6 +2416,7 @@ extern "C" int m3_sim_pull_state(m3_handle* h) {
     if (!h->views_bound || !h->views.dof_state || !h->views.root_state) return fail(h, M3_ERR_STATE, "m3_sim_pull_state: views not bound");
     if (const char* why = panda_scene_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_sim_pull_state: ") + why).c_str());
     if (h->cfg.env_type == M3_ENV_POINT) launch_sim_pull(h->views, h->sim_world, h->cfg.K_local, h->stream);
+    else if (h->panda_scene_rows_on) launch_psim_pull_v(h->pscene_rt, h->panda_rows_dev, h->views, h->sim_world, h->cfg.K_local, h->stream);
     else if (panda_scene_runtime(h)) launch_psim_pull_s(h->pscene_rt, h->views, h->sim_world, h->cfg.K_local, h->stream);
     else launch_psim_pull(h->pscene, h->views, h->sim_world, h->cfg.K_local, h->stream);
     HIPCHK(h, hipGetLastError());
@@ -2343,6 +2438,7 @@ extern "C" int m3_sim_push_state(m3_handle* h) {
     if (!h->views_bound) return fail(h, M3_ERR_STATE, "m3_sim_push_state: views not bound");
     if (const char* why = panda_scene_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_sim_push_state: ") + why).c_str());
     if (h->cfg.env_type == M3_ENV_POINT) launch_sim_push(h->views, h->sim_world, h->cfg.K_local, h->stream);
+    else if (h->panda_scene_rows_on) launch_psim_push_v(h->pscene_rt, h->panda_rows_dev, h->views, h->sim_world, h->cfg.K_local, h->stream);
     else if (panda_scene_runtime(h)) launch_psim_push_s(h->pscene_rt, h->views, h->sim_world, h->cfg.K_local, h->stream);
     else launch_psim_push(h->pscene, h->views, h->sim_world, h->cfg.K_local, h->stream);
     HIPCHK(h, hipGetLastError());
@@ -2379,8 +2475,10 @@ static int sim_step_impl(m3_handle* h, const float* u) {
         }
     } else {
         if (const char* why = panda_scene_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_sim_step: ") + why).c_str());
-        h->panda_scene_used = panda_scene_runtime(h) ? 1 : 0;
-        if (h->panda_scene_used) launch_psim_step_s(h->pscene_rt, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
+        h->panda_scene_used = (h->panda_scene_rows_on || panda_scene_runtime(h)) ? 1 : 0;
+        if (h->panda_scene_rows_on)
+            launch_psim_step_v(h->pscene_rt, h->panda_rows_dev, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
+        else if (h->panda_scene_used) launch_psim_step_s(h->pscene_rt, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
         else launch_psim_step(h->pscene, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
     }
     HIPCHK(h, hipGetLastError());
@@ -2437,7 +2535,9 @@ extern "C" int m3_cost(m3_handle* h, float* cost) {
         if (const char* why = panda_scene_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_cost: ") + why).c_str());
         if (const char* why = panda_weights_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_cost: ") + why).c_str());
         h->panda_weighted_used = panda_weighted(h) ? 1 : 0;
-        if (h->panda_weighted_used)
+        if (h->panda_scene_rows_on)   // (one kernel, weights always: at the defaults the literal cost's bits)
+            launch_psim_cost_v(h->pscene_rt, h->panda_rows_dev, cp, h->panda_cost_weights, h->sim_world, h->cfg.K_local, h->cfg.k_offset, env0_cube, cost, h->stream);
+        else if (h->panda_weighted_used)
             launch_psim_cost_w(h->pscene_rt, cp, h->panda_cost_weights, h->sim_world, h->cfg.K_local, h->cfg.k_offset, env0_cube, cost, h->stream);
         else if (panda_scene_runtime(h)) launch_psim_cost_s(h->pscene_rt, cp, h->sim_world, h->cfg.K_local, h->cfg.k_offset, env0_cube, cost, h->stream);
         else launch_psim_cost(h->pscene, cp, h->sim_world, h->cfg.K_local, h->cfg.k_offset, env0_cube, cost, h->stream);
@@ -2745,6 +2845,7 @@ extern "C" int m3_panda_episodes_create(m3_handle* world, m3_handle* const* plan
     if (wc.K_local != n || wc.K_global != n) return peps_refuse(M3_ERR_STATE, -1, "the world's K_local must equal n (one row per episode)");
     if (const char* why = panda_scene_refusal(world)) return peps_refuse(M3_ERR_STATE, -1, std::string("the world: ") + why);
     if (const char* why = panda_scene_unbatched(world)) return peps_refuse(M3_ERR_UNSUPPORTED, -1, std::string("the world: ") + why);
+    if (const char* why = panda_rows_unbatched(world)) return peps_refuse(M3_ERR_UNSUPPORTED, -1, std::string("the world: ") + why);
     for (int i = 0; i < n; ++i) {
         m3_handle* h = planners[i];
         if (!h) return peps_refuse(M3_ERR_BAD_ARG, i, "null handle");
@@ -2853,6 +2954,7 @@ static int peps_ready(m3_panda_episodes* eps, const char* who) {
         const int code = why ? M3_ERR_STATE : M3_ERR_UNSUPPORTED;
         if (!why) why = panda_scene_unbatched(h);
         if (!why) why = panda_weights_unbatched(h);
+        if (!why) why = panda_rows_unbatched(h);
         if (why) {
             eps->err = std::string(who) + (i < 0 ? ": the world: " : ": planner " + std::to_string(i) + ": ") + why;
             return code;

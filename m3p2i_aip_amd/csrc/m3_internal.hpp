@@ -428,6 +428,20 @@ void launch_rollout_panda_w(const RolloutArgs& a, const PandaArgs& pa, const Pan
                             const RolloutPlan& p, hipStream_t s);
 void launch_psim_cost_w(const PandaSceneRT& sc, const PandaCostParams& cp, const PandaCostWeights& wt, const float* world, int Kl,
                         int k0, bool env0_cube, float* cost, hipStream_t s);
+void launch_panda_reach_cost_w(const RolloutArgs& a, const PandaArgs& pa, const PandaCostWeights& wt, hipStream_t s);
+
+// the same for a handle with one workspace per row (rollout_panda_rows.hip; panda_scene_rows.hpp: uni, rows): per sample of a
+// planner handle's rollout (m3_set_panda_rollout_scenes) -- always with the weights, behind it the weighted reach-cost kernel
+// when the plan keeps the record buffer -- and per environment of a sim_only handle's step, views and cost
+// (m3_set_panda_scene_rows)
+void launch_rollout_panda_v(const RolloutArgs& a, const PandaArgs& pa, const PandaSceneRT& uni, const PandaCostWeights& wt,
+                            const float* rows, const RolloutPlan& p, hipStream_t s);
+void launch_psim_step_v(const PandaSceneRT& uni, const float* rows, const SimViews& v, float* world, const float* u, float* u_keep,
+                        int Kl, hipStream_t s);
+void launch_psim_pull_v(const PandaSceneRT& uni, const float* rows, const SimViews& v, float* world, int Kl, hipStream_t s);
+void launch_psim_push_v(const PandaSceneRT& uni, const float* rows, const SimViews& v, const float* world, int Kl, hipStream_t s);
+void launch_psim_cost_v(const PandaSceneRT& uni, const float* rows, const PandaCostParams& cp, const PandaCostWeights& wt,
+                        const float* world, int Kl, int k0, bool env0_cube, float* cost, hipStream_t s);
 
 // batched closed-loop episodes of the panda_env (m3_panda_episodes_*): one lane per episode of an N-env world
 struct PandaEpisodeArgs {
@@ -500,6 +514,14 @@ struct m3_handle {
     m3_point_scene* scene_rows = nullptr;   // view, host [Kl]: what was set (m3_get_point_scene_row)
     float* scene_rows_host = nullptr;  // view, pinned host [POINT_SCENE_ROW_WORDS][Kl]: the table as uploaded (point_scene_rows.hpp)
     float* scene_rows_dev = nullptr;   // view, device, the same
+    // m3_set_panda_scene_rows (sim_only panda_env: one workspace per environment) and m3_set_panda_rollout_scenes (panda_env
+    // planner handles: one per sample of the fused rollout); survive m3_reset.  A handle is a planner or sim_only for life, so
+    // both keep their rows in the same three blocks, allocated as one group by the first setter call on the handle.
+    bool panda_scene_rows_on = false;       // the step, the views and m3_cost take the per-row kernels
+    bool panda_rollout_scenes_on = false;   // m3_rollout / m3_command take the per-sample kernels
+    m3_panda_scene* panda_rows = nullptr;   // view, host [Kl]: what was set (m3_get_panda_scene_row / _rollout_scene)
+    float* panda_rows_host = nullptr;       // view, pinned host [PANDA_SCENE_ROW_WORDS][Kl]: the table as uploaded (panda_scene_rows.hpp)
+    float* panda_rows_dev = nullptr;        // view, device, the same
     // world
     float world0[18];
     const float* world0_bound = nullptr;  // device, 18 floats (filled by world_from_sim)

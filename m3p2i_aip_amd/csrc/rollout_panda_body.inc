@@ -2,7 +2,8 @@
 // kb_rollout_panda: the same tokens in both, so that k_rollout_panda compiles to exactly the code it did as a plain kernel
 // (as update_small_body.inc).  In scope where it is included: FORCES, GENERAL, LPS, the scene type `SceneT` (PandaScene, or
 // PandaSceneRT in rollout_panda_scene.hip), `const RolloutArgs& a_`, `const PandaArgs& pa` and `const SceneT& sc_`;
-// with the weighted cost hook (PANDA_BODY_COST, rollout_panda_common.hpp) also `const PandaCostWeights& wt`.
+// with the weighted cost hook (PANDA_BODY_COST, rollout_panda_common.hpp) also `const PandaCostWeights& wt`; with the scene hook
+// (PANDA_BODY_SCENE) also `const float* scene_rows`.
     PANDA_CORNER_LDS(LPS);
     // (a_.lanes samples per 64-wide wavefront: m3_set_rollout_lanes; the idle lanes leave at once)
     // Shadow lanes (quirk Q8, pa.shadows = 1 or 2; reach on an unsharded handle): the reference's reach cost measures every
@@ -37,6 +38,7 @@
     }
     const int Kl = a.Kl, T = a.T;
     const int k = a.k0 + i;
+    PANDA_BODY_SCENE(sc, i)      // (the scene hook: rollout_panda_common.hpp)
     PandaWorld w;
     if (a.sim_dof) panda_world_from_sim(a.sim_dof, a.sim_root, pa.cubeA_actor, pa.cubeB_actor, pa.obs_actor, w);
     else panda_world_from_raw(pa.world0, w);

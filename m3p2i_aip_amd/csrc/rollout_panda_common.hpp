@@ -6,6 +6,8 @@
 #include "m3_internal.hpp"
 #include "panda_dyn.hpp"
 
+#include <cstddef>
+
 namespace m3 {
 
 // raw world, 57 floats: q9 qd9 | cubeA13 | cubeB13 | dyn-obs13 (each: pos3 quat4(xyzw) linvel3 angvel3)
@@ -66,6 +68,32 @@ __device__ __forceinline__ float in_vgpr(float v) {   // keep a uniform value in
 #ifndef PANDA_BODY_COST
 #define PANDA_BODY_COST(w, o, k, cube0, qh0) panda_cost(pa.cp, w, o, k, cube0, qh0)
 #endif
+
+// The scene hook: where the rollout body has copied the kernel-argument scene into `sc` and knows its sample index `i`
+// (a_.lanes, the shadow slots and the ragged last wavefront applied).  Empty everywhere but in rollout_panda_rows.hip, which
+// overwrites the workspace words of `sc` from row i of the per-sample table (panda_scene_rows.hpp) there.
+#ifndef PANDA_BODY_SCENE
+#define PANDA_BODY_SCENE(sc, i)
+#endif
+
+// The kernels' `wt` (the weighted families: rollout_panda_weights.hip, rollout_panda_rows.hip) as it lies in the kernel-argument
+// segment (arguments are laid out like the members of a struct), read through a pointer the compiler cannot see through: named
+// as an ordinary argument, the seven floats were loaded at kernel entry and held (spilled) over the whole step loop -- eight
+// scalar spills more than the twin in every rollout build.  This way each step issues its own scalar load where the cost is
+// formed, and nothing of the weights lives across the substeps.
+// offset of the last of the listed argument types: each argument at the next multiple of its alignment
+template <class Last>
+constexpr size_t kernarg_offset(size_t at) { return (at + alignof(Last) - 1) / alignof(Last) * alignof(Last); }
+template <class First, class Second, class... Rest>
+constexpr size_t kernarg_offset(size_t at) { return kernarg_offset<Second, Rest...>(kernarg_offset<First>(at) + sizeof(First)); }
+template <size_t OFFSET>
+__device__ __forceinline__ PandaCostWeights kernarg_weights() {
+    typedef const char __attribute__((address_space(4)))* kernarg_bytes;
+    typedef const float __attribute__((address_space(4)))* kernarg_floats;
+    kernarg_floats p = (kernarg_floats)((kernarg_bytes)__builtin_amdgcn_kernarg_segment_ptr() + OFFSET);
+    asm volatile("" : "+s"(p));
+    return PandaCostWeights{p[0], p[1], p[2], p[3], p[4], p[5], p[6]};
+}
 
 // k_panda_reach_cost (rollout_panda.hip) and its weighted twin (rollout_panda_weights.hip)
 constexpr int RC_TS = 4, RC_CH = 32;      // time slices per workgroup; steps per LDS chunk

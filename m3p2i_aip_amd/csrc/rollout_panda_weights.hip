@@ -7,8 +7,8 @@
 // forces it).
 //
 // The weights are wave-uniform and are read in one place per step, where the cost is formed after the substeps: the cost hook
-// reads them from the kernel-argument segment there (kernarg_weights below) instead of holding seven more scalars over the
-// substep loop, whose builds already spill two to three hundred.
+// reads them from the kernel-argument segment there (kernarg_weights, rollout_panda_common.hpp) instead of holding seven more
+// scalars over the substep loop, whose builds already spill two to three hundred.
 #define PANDA_BODY_COST(w, o, k, cube0, qh0) panda_cost(pa.cp, kernarg_weights<WT_OFFSET>(), w, o, k, cube0, qh0)
 #include "m3_internal.hpp"
 #include "noise_stream.hpp"
@@ -16,27 +16,7 @@
 #include "rollout_panda_common.hpp"
 #include "wave_min.hpp"
 
-#include <cstddef>
-
 namespace m3 {
-
-// The kernels' `wt` as it lies in the kernel-argument segment (arguments are laid out like the members of a struct), read
-// through a pointer the compiler cannot see through: named as an ordinary argument, the seven floats were loaded at kernel
-// entry and held (spilled) over the whole step loop -- eight scalar spills more than the twin in every rollout build.  This
-// way each step issues its own scalar load where the cost is formed, and nothing of the weights lives across the substeps.
-// offset of the last of the listed argument types: each argument at the next multiple of its alignment
-template <class Last>
-constexpr size_t kernarg_offset(size_t at) { return (at + alignof(Last) - 1) / alignof(Last) * alignof(Last); }
-template <class First, class Second, class... Rest>
-constexpr size_t kernarg_offset(size_t at) { return kernarg_offset<Second, Rest...>(kernarg_offset<First>(at) + sizeof(First)); }
-template <size_t OFFSET>
-__device__ __forceinline__ PandaCostWeights kernarg_weights() {
-    typedef const char __attribute__((address_space(4)))* kernarg_bytes;
-    typedef const float __attribute__((address_space(4)))* kernarg_floats;
-    kernarg_floats p = (kernarg_floats)((kernarg_bytes)__builtin_amdgcn_kernarg_segment_ptr() + OFFSET);
-    asm volatile("" : "+s"(p));
-    return PandaCostWeights{p[0], p[1], p[2], p[3], p[4], p[5], p[6]};
-}
 
 // k_rollout_panda_s's body with the weighted cost: six kernels (FORCES x LPS), GENERAL always on
 template <bool FORCES, int LPS>
@@ -63,13 +43,16 @@ static void launch_rollout_panda_w_lps(const RolloutArgs& a_in, const PandaArgs&
     if (p.forces) hipLaunchKernelGGL((k_rollout_panda_w<true, LPS>), grid, block, 0, s, a, pa, sc, wt);
     else hipLaunchKernelGGL((k_rollout_panda_w<false, LPS>), grid, block, 0, s, a, pa, sc, wt);
 }
+void launch_panda_reach_cost_w(const RolloutArgs& a, const PandaArgs& pa, const PandaCostWeights& wt, hipStream_t s) {
+    hipLaunchKernelGGL(k_panda_reach_cost_w, dim3((a.Kl + 63) / 64), dim3(64 * RC_TS), 0, s, a, pa, wt);
+}
 // pa, p: as plan_rollout_panda left them (the form is chosen exactly as for the literal weights)
 void launch_rollout_panda_w(const RolloutArgs& a, const PandaArgs& pa, const PandaSceneRT& sc, const PandaCostWeights& wt,
                             const RolloutPlan& p, hipStream_t s) {
     if (p.lps == 16) launch_rollout_panda_w_lps<16>(a, pa, sc, wt, p, s);
     else if (p.lps == 8) launch_rollout_panda_w_lps<8>(a, pa, sc, wt, p, s);
     else launch_rollout_panda_w_lps<1>(a, pa, sc, wt, p, s);
-    if (p.rec) hipLaunchKernelGGL(k_panda_reach_cost_w, dim3((a.Kl + 63) / 64), dim3(64 * RC_TS), 0, s, a, pa, wt);
+    if (p.rec) launch_panda_reach_cost_w(a, pa, wt, s);
 }
 
 // ---- step mode: k_psim_cost_s (rollout_panda_scene.hip) with the weighted cost, for m3_cost ----

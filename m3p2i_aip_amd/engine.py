@@ -369,6 +369,53 @@ class HipEngine(_CObject):
         """whether the last rollout or step launched the run-time-scene instance"""
         return self.lib.m3_panda_scene_instance_used(self._h) == 1
 
+    def _panda_rows_array(self, rows):
+        arr = (L.PandaSceneFields * len(rows))()
+        for i, r in enumerate(rows):
+            arr[i] = L.panda_scene_fields(r)     # (None: the reference's workspace; ValueError for an unknown field)
+        return arr
+
+    def set_panda_scene_rows(self, rows=None):
+        """Extension, sim_only panda_env engines: one workspace per environment -- rows[i] the field overrides of environment i
+        over _lib.PANDA_SCENE_DEFAULTS (None: the reference's workspace); len(rows) == K_local.  rows=None clears: the engine
+        is back on its single workspace.  Applies from the next step / cost / view refresh; set_panda_scene afterwards clears
+        the rows."""
+        if rows is None:
+            self._ck(self.lib.m3_set_panda_scene_rows(self._h, None, 0))
+            return
+        rows = list(rows)
+        self._ck(self.lib.m3_set_panda_scene_rows(self._h, self._panda_rows_array(rows), len(rows)))
+
+    def panda_scene_row(self, i):
+        """environment i's workspace as set by set_panda_scene_rows (all fields)"""
+        sc = L.PandaSceneFields()
+        self._ck(self.lib.m3_get_panda_scene_row(self._h, int(i), C.byref(sc)))
+        return L.panda_scene_dict(sc)
+
+    def panda_scene_rows_set(self):
+        return self.lib.m3_panda_scene_rows_set(self._h) == 1
+
+    def set_panda_rollout_scenes(self, rows=None):
+        """Extension, panda_env planner engines: one workspace per SAMPLE of the fused rollout -- rows[i] the field overrides of
+        local sample i (global k_offset + i) over _lib.PANDA_SCENE_DEFAULTS (None: the reference's workspace); len(rows) ==
+        K_local.  rows=None clears: the engine is back on its single workspace.  Applies from the next rollout / command;
+        set_panda_scene afterwards clears the rows.  The reach cost reads the cube of sample 0 as simulated in rows[0] (quirk
+        Q8; multi-modal: the orientation of sample K / 2 in its row): scenes.spread_panda_scenes keeps those rows nominal."""
+        if rows is None:
+            self._ck(self.lib.m3_set_panda_rollout_scenes(self._h, None, 0))
+            return
+        rows = list(rows)
+        self._ck(self.lib.m3_set_panda_rollout_scenes(self._h, self._panda_rows_array(rows), len(rows)))
+
+    def panda_rollout_scene(self, i):
+        """local sample i's workspace as set by set_panda_rollout_scenes (all fields)"""
+        sc = L.PandaSceneFields()
+        self._ck(self.lib.m3_get_panda_rollout_scene(self._h, int(i), C.byref(sc)))
+        return L.panda_scene_dict(sc)
+
+    def panda_rollout_scenes_set(self):
+        return self.lib.m3_panda_rollout_scenes_set(self._h) == 1
+
     def set_panda_cost_weights(self, weights=None):
         """Extension, panda_env: the weights of the task costs (a mapping with keys of _lib.PANDA_COST_WEIGHT_DEFAULTS, missing
         keys = the reference's literal; None = all defaults).  They apply from the next command / rollout / cost call."""

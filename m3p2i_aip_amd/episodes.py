@@ -477,6 +477,10 @@ def _panda_groups(episodes, who):
             if getattr(cfg, key):
                 raise ValueError(f"{who}: episode {idx}: `{key}` asks for a workspace of its own (m3_set_panda_scene), which the "
                                  "lockstep panda episodes do not run (one world handle, one scene); use closed_loop.run")
+        if getattr(cfg, "rollout_workspace_spread", None):
+            raise ValueError(f"{who}: episode {idx}: `rollout_workspace_spread` asks for a workspace per sample "
+                             "(m3_set_panda_rollout_scenes), which the lockstep panda episodes do not run (their planners' batched "
+                             "command carries one scene); use closed_loop.run")
         if getattr(cfg, "panda_cost_weights", None):
             raise ValueError(f"{who}: episode {idx}: `panda_cost_weights` asks for cost weights of its own (m3_set_panda_cost_weights), "
                              "which the lockstep panda episodes do not run (their planners' batched command forms the literal "

@@ -86,7 +86,7 @@ def panda_workspace(actors=None, overrides=None):
 class IsaacGymWrapper:
     def __init__(self, cfg: IsaacGymConfig, env_type: str = "point_env", num_envs: int = 1,
                  viewer: bool = False, device: str = "cuda:0", cube_on_shelf: bool = False,
-                 k_offset: int = 0, num_envs_global: int | None = None, actors=None, point_scenes=None):
+                 k_offset: int = 0, num_envs_global: int | None = None, actors=None, point_scenes=None, panda_scenes=None):
         if viewer or getattr(cfg, "viewer", False):
             # scripts/sim.py:19-27 asks for the viewer of its 1-env world; this build has none: the world
             # runs headless (visualize_trajs / play_with_cube are no-ops), keyboard_control raises
@@ -157,6 +157,28 @@ class IsaacGymWrapper:
                     raise ValueError(f"point_scenes[{i}]: unknown field(s) {unknown}: one of {list(L.POINT_SCENE_DEFAULTS)}")
                 rows.append({**L.POINT_SCENE_DEFAULTS, **{k: float(v) for k, v in given.items()}})
             self.point_scenes = rows
+        # EXTENSION, panda_env: one workspace PER ENVIRONMENT -- panda_scenes[i] the field overrides of environment i over
+        # _lib.PANDA_SCENE_DEFAULTS, None the reference's workspace.  self.panda_scenes: the rows (all fields, the binary32 values
+        # the library holds); self.panda_scene stays the single workspace above, which the engine is back on after
+        # set_panda_scene_rows(None).  A planner with one sample per environment of this wrapper takes the rows over.
+        self.panda_scenes = None
+        if panda_scenes is not None:
+            if env_type != "panda_env":
+                raise ValueError("panda_scenes: panda_env only")
+            panda_scenes = list(panda_scenes)
+            if len(panda_scenes) != int(num_envs):
+                raise ValueError(f"panda_scenes: {len(panda_scenes)} entries for num_envs = {int(num_envs)}")
+            rows = []
+            for i, given in enumerate(panda_scenes):
+                given = dict(given or {})
+                unknown = sorted(set(given) - set(L.PANDA_SCENE_DEFAULTS))
+                if unknown:
+                    raise ValueError(f"panda_scenes[{i}]: unknown field(s) {unknown}: one of {list(L.PANDA_SCENE_DEFAULTS)}")
+                try:
+                    rows.append(L.panda_scene_dict(L.panda_scene_fields(given)))
+                except ValueError as e:
+                    raise ValueError(f"panda_scenes[{i}]: {e}") from None
+            self.panda_scenes = rows
         for i, a in enumerate(self.env_cfg):
             a.handle = i
         self.device = device
@@ -187,6 +209,8 @@ class IsaacGymWrapper:
             self._engine.set_panda_scene(self.panda_scene)
         if self.point_scenes is not None:
             self._engine.set_point_scene_rows(self.point_scenes)
+        if self.panda_scenes is not None:
+            self._engine.set_panda_scene_rows(self.panda_scenes)
 
         # initial scene (start_sim / set_initial_joint_pose / acquire_states: :68-118,222-240)
         root = torch.zeros(nA, 13)
@@ -210,6 +234,17 @@ class IsaacGymWrapper:
                         ax = 0 if a.name in ("wall-1", "wall-2") else 1
                         sign = 1.0 if a.name in ("wall-1", "wall-3") else -1.0
                         root[e, i, ax] = sign * (sc["wall"] + 0.5 * a.size[0])
+        if self.panda_scenes is not None:
+            # row e shows workspace e wherever the single-workspace path writes the workspace into every row: the poses of the
+            # table, the shelf stand and the robot's mount (the views hold no sizes; the link poses of environment e go through
+            # row e's base in the views' refresh below)
+            keys = {"table": "table", "shelf_stand": "shelf", "panda": "base"}
+            ref = L.panda_scene_dict(L.panda_scene_fields(None))
+            for i, a in enumerate(self.env_cfg):
+                if a.name in keys:
+                    for e, sc in enumerate(self.panda_scenes):
+                        if sc[keys[a.name]] != ref[keys[a.name]]:     # (as panda_workspace: only where it is not the reference's)
+                            root[e, i, 0:3] = torch.tensor(list(sc[keys[a.name]][:3]))
         self._root_state = root.to(dev).contiguous()
         body_actor = [i for i, a in enumerate(self.env_cfg) for _ in a.links]   # (a link starts at its actor's root pose)
         self._rigid_body_state = root[:, body_actor, :].to(dev).contiguous()

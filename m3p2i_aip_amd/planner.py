@@ -386,9 +386,28 @@ class MPPI():
         # (extension, off by default, panda_env: the wrapper's workspace, by the same rule)
         if self.env_type == "panda_env":
             ws = getattr(s, "panda_scene", None)
+            ws_pushed = False
             if follow and ws != getattr(self, "_panda_scene_pushed", None):
                 self._engine.set_panda_scene(ws)
                 self._panda_scene_pushed = None if ws is None else dict(ws)
+                ws_pushed = True
+            # (extension, off by default) one workspace per SAMPLE, by the rule of the point arenas below: the rows of a followed
+            # wrapper with one environment per local sample (IsaacGymWrapper(panda_scenes=...)) are pushed once, and again when
+            # the wrapper holds another list or the single workspace was pushed (which clears the library's rows); rows set by
+            # hand (set_panda_rollout_scenes) stand wherever no wrapper's rows are followed
+            rows = self._followed_sim_panda_rows()
+            if rows is not None:
+                if ws_pushed or not self._same_rows(rows, getattr(self, "_sim_panda_rows_pushed", None)):
+                    self._engine.set_panda_rollout_scenes(rows)
+                    self._sim_panda_rows_pushed = rows
+            else:
+                was_following = getattr(self, "_sim_panda_rows_pushed", None) is not None
+                self._sim_panda_rows_pushed = None
+                mine = getattr(self, "_panda_rollout_scenes", None)
+                if mine is not None and (ws_pushed or was_following):
+                    self._engine.set_panda_rollout_scenes(mine[self.k_offset:self.k_offset + self.K_local])
+                elif was_following:
+                    self._engine.set_panda_rollout_scenes(None)
         # (extension, off by default) one arena per SAMPLE: the fused rollout is the step path on a wrapper whose K_local
         # environments carry their own arenas (IsaacGymWrapper(point_scenes=...)), so while the planner follows its wrapper it
         # takes those rows over -- once, and again when the wrapper holds another list (or the single arena was pushed, which
@@ -433,6 +452,41 @@ class MPPI():
         if rows is None or not getattr(self, "follow_sim_scene", True) or getattr(s, "num_envs", None) != self.K_local:
             return None
         return rows
+
+    def _followed_sim_panda_rows(self):
+        """the per-environment workspaces of the attached wrapper this planner's samples take over, or None: only while
+        follow_sim_scene holds and the wrapper has one environment per local sample"""
+        s = self._sim
+        rows = getattr(s, "panda_scenes", None) if s is not None else None
+        if rows is None or not getattr(self, "follow_sim_scene", True) or getattr(s, "num_envs", None) != self.K_local:
+            return None
+        return rows
+
+    @property
+    def has_panda_rollout_scenes(self):
+        """the fused rollout runs (or, from its next command on, will run) one workspace per sample"""
+        return self.env_type == "panda_env" and (getattr(self, "_panda_rollout_scenes", None) is not None
+                                                 or self._followed_sim_panda_rows() is not None)
+
+    def set_panda_rollout_scenes(self, rows):
+        """Extension, panda_env: one workspace per sample of the fused rollout (m3_set_panda_rollout_scenes) -- `rows` the
+        GLOBAL list of K field-override dicts over _lib.PANDA_SCENE_DEFAULTS (None entries: the reference's workspace), of which
+        this planner pushes its shard's slice; None clears.  scenes.spread_panda_scenes builds such a list with the special
+        samples kept nominal.  A wrapper with `panda_scenes` that this planner follows (follow_sim_scene) overrides rows set
+        here."""
+        if self.env_type != "panda_env":
+            raise ValueError("set_panda_rollout_scenes: panda_env only")
+        if rows is None:
+            self._panda_rollout_scenes = None
+            self._sim_panda_rows_pushed = None      # (a followed wrapper's rows are pushed again by the next command)
+            self._engine.set_panda_rollout_scenes(None)
+            return
+        rows = list(rows)
+        if len(rows) != self.K:
+            raise ValueError(f"set_panda_rollout_scenes: {len(rows)} rows for num_samples = {self.K} (the global list)")
+        self._engine.set_panda_rollout_scenes(rows[self.k_offset:self.k_offset + self.K_local])
+        self._panda_rollout_scenes = rows
+        self._sim_panda_rows_pushed = None
 
     @property
     def needs_panda_scene_instance(self):
@@ -711,6 +765,9 @@ def command_batch(planners, states):
         if p.has_rollout_scenes:
             raise ValueError(f"command_batch: planner {i} has an arena per sample (set_rollout_scenes / a wrapper with "
                              "point_scenes): m3_batch_command does not run those, use planner.command")
+        if getattr(p, "has_panda_rollout_scenes", False):
+            raise ValueError(f"command_batch: planner {i} has a workspace per sample (set_panda_rollout_scenes / a wrapper with "
+                             "panda_scenes): m3_batch_command does not run those, use planner.command")
         if not isinstance(p._engine, HipEngine):
             raise ValueError(f"command_batch: planner {i} does not run on the HIP library")
         if p.needs_panda_scene_instance:

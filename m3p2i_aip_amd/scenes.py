@@ -195,6 +195,37 @@ def spread_point_scenes(n, spread, seed=0, base=None, fields=("box_m", "box_mu_g
 PANDA_CUBE_SIZE = 0.05
 
 
+def spread_panda_scenes(n, spread, seed=0, base=None, fields=("cube_m", "mu", "obs_m"), nominal_rows=()):
+    """n workspaces around `base` (field overrides over _lib.PANDA_SCENE_DEFAULTS; None: the reference's workspace), as override
+    dicts for HipEngine.set_panda_rollout_scenes / set_panda_scene_rows / IsaacGymWrapper(panda_scenes=...): each field of `fields`
+    is base's value times a factor uniform in [1 - spread, 1 + spread] (an array field: every component by the field's one
+    factor).  Row i depends on (seed, i) only, so a shard's rows are the slice of the global list.  Rows in `nominal_rows` are
+    `base` unchanged -- a planner keeps its special samples (K - 1; the reach cost's 0 and K / 2, quirk Q8) on its nominal model
+    that way.  The cube's size is no field (panda_scene_from_actors says why)."""
+    import numpy as np
+    from ._lib import PANDA_SCENE_DEFAULTS
+    spread = float(spread)
+    if not 0.0 <= spread < 1.0:
+        raise ValueError(f"spread_panda_scenes: spread {spread!r} is not a share in [0, 1)")
+    base = dict(base or {})
+    fields = tuple(fields)
+    unknown = sorted((set(base) | set(fields)) - set(PANDA_SCENE_DEFAULTS))
+    if unknown:
+        raise ValueError(f"spread_panda_scenes: unknown panda scene field(s) {unknown}: one of {list(PANDA_SCENE_DEFAULTS)}")
+    full = {**PANDA_SCENE_DEFAULTS, **base}
+    nominal = {int(i) % int(n) for i in nominal_rows} if n else set()
+    rows = []
+    for i in range(int(n)):
+        row = dict(base)
+        if i not in nominal and fields:
+            f = np.random.default_rng([int(seed), i]).uniform(1.0 - spread, 1.0 + spread, len(fields))
+            for name, fac in zip(fields, f):
+                v = full[name]
+                row[name] = tuple(float(x) * float(fac) for x in v) if isinstance(PANDA_SCENE_DEFAULTS[name], tuple) else float(v) * float(fac)
+        rows.append(row)
+    return rows
+
+
 def panda_scene_from_actors(actors) -> dict:
     """The fields of m3_panda_scene (keys and order of _lib.PANDA_SCENE_DEFAULTS) from an actor list shaped like PANDA_ENV:
       * `table`, `shelf`: centre from `init_pos`, half extents from `size`; `obs_half` from the plate's `size`;

@@ -37,10 +37,12 @@ class Tamp:
         from m3p2i_aip.planners.motion_planner.cost_functions import Objective
         self.cfg = cfg
         # (the `rollout_arena_spread` config key: the planner's K environments each in an arena of their own -- the planner
-        # attached to this simulator takes the rows over for its fused rollout; None without the key)
+        # attached to this simulator takes the rows over for its fused rollout; None without the key.  panda_env likewise under
+        # `rollout_workspace_spread`: a workspace per environment)
         self.sim = wrapper.IsaacGymWrapper(cfg.isaacgym, cfg.env_type, num_envs=cfg.mppi.num_samples,
                                            viewer=False, device=cfg.mppi.device, cube_on_shelf=cfg.cube_on_shelf,
-                                           point_scenes=compat.rollout_point_scenes(cfg))
+                                           point_scenes=compat.rollout_point_scenes(cfg),
+                                           panda_scenes=compat.rollout_panda_scenes(cfg))
         self.objective = Objective(cfg)
         self.task_planner = task_planner.set_task_planner(cfg)
         self.task_success = False
