@@ -851,6 +851,13 @@ int m3_sim_suction_forces(m3_handle* h, float kp_suction, float* forces_dev);
 int m3_sim_check_and_apply_suction(m3_handle* h, const float* action_dev, float kp_suction, int apply,
                                    int* applied_dev, const int* enabled_dev);
 
+/* Read-only: the wavefront order the LAST m3_rollout / m3_command of the handle went by -- order_dev[slot] = local index of
+ * the sample that lane slot `slot` simulated (device memory, i32 [*n], *n = K_local; owned by the handle, valid until its
+ * next rollout).  NULL and 0 when that rollout went by index: order off (m3_set_wave_order), samples relabelled
+ * (m3_relabel_samples: index order IS wavefront order then), K_local < 128, random sampling, simple mode, noise uploaded
+ * for almost every command, panda_env, or no rollout yet.  Synchronises the handle's stream.  For tests and tools. */
+int m3_wave_order(m3_handle* h, const int** order_dev, int* n);
+
 
 #ifdef __cplusplus
 }

@@ -297,6 +297,7 @@ SYMBOLS = [
     ("m3_cost", C.c_int, [_H, _FP]),
     ("m3_sim_suction_forces", C.c_int, [_H, C.c_float, _FP]),
     ("m3_sim_check_and_apply_suction", C.c_int, [_H, _FP, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    ("m3_wave_order", C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
 ]
 
 _lib = None

@@ -415,6 +415,18 @@ extern "C" int m3_point_rollout_form_used(m3_handle* h) {
     return h ? h->point_form_used : -1;
 }
 
+extern "C" int m3_wave_order(m3_handle* h, const int** order_dev, int* n) {
+    if (!h || !order_dev || !n) return fail(h, M3_ERR_BAD_ARG, "m3_wave_order: null argument");
+    *order_dev = nullptr;
+    *n = 0;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->order_valid) {   // (set by the last rollout's refresh_wave_order; every refusal there leaves it false)
+        *order_dev = h->order;
+        *n = h->cfg.K_local;
+    }
+    return M3_OK;
+}
+
 extern "C" int m3_set_panda_lanes_per_sample(m3_handle* h, int lps) {
     if (!h) return M3_ERR_BAD_ARG;
     if (lps != 0 && lps != 1 && lps != 8 && lps != 16)
@@ -466,14 +478,20 @@ extern "C" int m3_enable_timing(m3_handle* h, int on) {
 // current world; stream-ordered, no sync.  Called by m3_rollout when the noise changed and every
 // ORDER_REFRESH commands (the objects move).
 constexpr unsigned ORDER_REFRESH = 256;
+// first local index of the second mode inside the block that starts at global sample k_offset (0 .. K_local)
+static int block_half(const m3_config& c, int k_offset) {
+    long long half_local = (long long)(c.K_global / 2) - k_offset;
+    if (!c.multi_modal || half_local > c.K_local) half_local = c.K_local;
+    if (half_local < 0) half_local = 0;
+    return (int)half_local;
+}
+
 // one shard's block of noise rows [T][Kl][nu] (k_offset = global index of its first sample): sort into
 // wavefront order; `relabel`: write the rows back in that order (and, for this rank's own block, let the
 // pending suction forces follow their samples)
 static int order_block(m3_handle* h, float* block, int k_offset, bool relabel, bool own) {
     const m3_config& c = h->cfg;
-    long long half_local = (long long)(c.K_global / 2) - k_offset;
-    if (!c.multi_modal || half_local > c.K_local) half_local = c.K_local;
-    if (half_local < 0) half_local = 0;
+    const int half_local = block_half(c, k_offset);
     OrderScene os;
     std::memset(&os, 0, sizeof(os));
     if (h->bind_dof) { os.sim_root = h->bind_root; os.sim_box = h->bind_box; os.sim_dyn = h->bind_dyn; }
@@ -483,7 +501,7 @@ static int order_block(m3_handle* h, float* block, int k_offset, bool relabel, b
     const int specials[3] = {0 - k_offset, c.K_global / 2 - k_offset, c.K_global - 1 - k_offset};
     hipError_t e = launch_wave_order(block, c.K_local, c.T, c.nu,
                                      std::sqrt(c.noise_sigma_diag[0]), std::sqrt(c.noise_sigma_diag[1]),
-                                     (int)half_local, os, h->order_scratch, h->order_temp_bytes, h->order, h->noise_sorted,
+                                     half_local, os, h->order_scratch, h->order_temp_bytes, h->order, h->noise_sorted,
                                      relabel ? specials : nullptr, h->stream);
     if (e != hipSuccess) { h->err = std::string("wave order: ") + hipGetErrorString(e); return M3_ERR_HIP; }
     if (relabel) {
@@ -514,7 +532,15 @@ static int refresh_wave_order(m3_handle* h) {
         c.mode_simple || !h->have_noise || h->noise_churn >= 2)
         return M3_OK;
     if (!h->order) {
-        h->order_temp_bytes = wave_order_temp_bytes(c.K_local);
+        // the sort's own storage: for the largest range any block of this handle is sorted in (each mode's part of its own
+        // block; of every shard's block where the handle holds them all) -- the configuration fixes them, so sized once
+        size_t temp = 0;
+        const int nb = h->regen ? c.K_global / c.K_local : 1;
+        for (int r = 0; r < nb; ++r) {
+            const int half = block_half(c, h->regen ? r * c.K_local : c.k_offset);
+            temp = std::max(temp, std::max(wave_order_temp_bytes(half), wave_order_temp_bytes(c.K_local - half)));
+        }
+        h->order_temp_bytes = temp;
         BlockGroup g(h->mem);   // all three or none: a failure leaves order null, the next rollout tries again
         HIPCHK(h, own_device(h->mem, h->order, sizeof(int) * (size_t)c.K_local));
         HIPCHK(h, own_device(h->mem, h->order_scratch, 3 * sizeof(float) * (size_t)c.K_local + h->order_temp_bytes));

@@ -261,7 +261,7 @@ struct OrderScene {   // where the scene's objects are when the wavefront order 
     float bx, by, dx, dy;   // otherwise these (host world)
     float ox, oy;           // obstacle
 };
-size_t wave_order_temp_bytes(int Kl);
+size_t wave_order_temp_bytes(int n);   // the radix sort's own storage for one range of n keys
 hipError_t launch_wave_order(const float* noise, int Kl, int T, int nu, float s0, float s1, int half_local,
                              const OrderScene& os, void* scratch, size_t temp_bytes, int* order, float* noise_sorted,
                              const int* specials /* null, or 3 local indices (-1: none) */, hipStream_t s);

@@ -118,7 +118,10 @@ void launch_halton_knots(float* knots, int k0, int n, int ncol, const int* prime
 // key = position of the sample's path centroid relative to the mean path (sum_t cumsum_t(scale *
 // delta)) projected on the axis along which the scene's objects (box, dyn-obs, obstacle) are spread
 // (principal axis of their positions; in the reference's point_env they sit in one row).  Samples of a wave
-// then meet the same object, or none.  Lane placement cannot change a sample's numbers (all
+// then meet the same object, or none.  The sort is stable and runs inside each mode's part of the block
+// (a multi-modal planner's two halves follow different means), with the key's full f32 precision in both
+// (tests/wave_order_ref.py is the float64 statement of this order; tests/test_wave_order_gpu.py compares).
+// Lane placement cannot change a sample's numbers (all
 // arithmetic is lane-local; tests/test_full_size_properties.py).  Measured (bench.py, order off ->
 // on): push K=2000 0.191 -> 0.171 ms, hybrid K=4000 0.231 -> 0.210, north-star K=10000 0.208 -> 0.190.
 // Two ways to apply the order: as an indirection (lane slot -> sample; noise rows gathered once so
@@ -130,8 +133,7 @@ void launch_halton_knots(float* knots, int k0, int n, int ncol, const int* prime
 // displacement, radius, Morton cells, sectors x radius (0 .. -5 %); the mid-horizon displacement
 // on the same axis is equivalent.
 __global__ void k_order_keys(const float* __restrict__ noise /*[T][Kl][nu]*/, int Kl, int T, int nu, float s0,
-                             float s1, int half_local, OrderScene os, float* __restrict__ keys,
-                             int* __restrict__ idx) {
+                             float s1, OrderScene os, float* __restrict__ keys, int* __restrict__ idx) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= Kl) return;
     float bx = os.bx, by = os.by, dx = os.dx, dy = os.dy;
@@ -152,8 +154,8 @@ __global__ void k_order_keys(const float* __restrict__ noise /*[T][Kl][nu]*/, in
         cx += s0 * d[0]; cy += s1 * d[1];
         sx += cx; sy += cy;
     }
-    // the two modes of a multi-modal planner follow different means: keep them in separate waves
-    keys[i] = (sx * ex + sy * ey) + (i >= half_local ? 1e9f : 0.0f);
+    // (the two modes of a multi-modal planner are sorted apart: launch_wave_order)
+    keys[i] = sx * ex + sy * ey;
     idx[i] = i;
 }
 
@@ -200,14 +202,17 @@ __global__ void k_gather_rows(const float* __restrict__ src, const int* __restri
         dst[o] = src[(o / Kl) * Kl + order[o % Kl]];
 }
 
-size_t wave_order_temp_bytes(int Kl) {
-    size_t n = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, n, (const float*)nullptr, (float*)nullptr, (const int*)nullptr,
-                                             (int*)nullptr, Kl);
-    return n;
+// the radix sort's own storage for one call over n keys
+size_t wave_order_temp_bytes(int n) {
+    size_t bytes = 0;
+    if (n <= 0) return 0;
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, (const float*)nullptr, (float*)nullptr, (const int*)nullptr,
+                                             (int*)nullptr, n);
+    return bytes;
 }
 
-// scratch: keys_in [Kl] | keys_out [Kl] | idx_in [Kl] (floats / ints), then the radix sort's own storage
+// scratch: keys_in [Kl] | keys_out [Kl] | idx_in [Kl] (floats / ints), then the radix sort's own storage (temp_bytes: enough
+// for the larger of the two ranges, wave_order_temp_bytes)
 hipError_t launch_wave_order(const float* noise, int Kl, int T, int nu, float s0, float s1, int half_local,
                              const OrderScene& os, void* scratch, size_t temp_bytes, int* order, float* noise_sorted,
                              const int* specials, hipStream_t s) {
@@ -215,10 +220,19 @@ hipError_t launch_wave_order(const float* noise, int Kl, int T, int nu, float s0
     float* keys_out = keys_in + Kl;
     int* idx_in = (int*)(keys_out + Kl);
     void* temp = (void*)(idx_in + Kl);
-    hipLaunchKernelGGL(k_order_keys, dim3((Kl + 255) / 256), dim3(256), 0, s, noise, Kl, T, nu, s0, s1, half_local,
-                       os, keys_in, idx_in);
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys_in, keys_out, idx_in, order, Kl, 0, 32, s);
-    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_order_keys, dim3((Kl + 255) / 256), dim3(256), 0, s, noise, Kl, T, nu, s0, s1, os, keys_in, idx_in);
+    // the two modes of a multi-modal planner follow different means: they stay in separate waves, each mode's part of the
+    // block [0, half_local) / [half_local, Kl) sorted on its own (an offset added to the second mode's keys would spend
+    // the key's precision: one f32 ulp at an offset beyond the keys' range is coarser than the spacing of the keys)
+    const int lo[2] = {0, half_local}, hi[2] = {half_local, Kl};
+    for (int m = 0; m < 2; ++m) {
+        const int n = hi[m] - lo[m];
+        if (n <= 0) continue;
+        size_t bytes = temp_bytes;
+        hipError_t e = hipcub::DeviceRadixSort::SortPairs(temp, bytes, keys_in + lo[m], keys_out + lo[m], idx_in + lo[m],
+                                                          order + lo[m], n, 0, 32, s);
+        if (e != hipSuccess) return e;
+    }
     if (specials) hipLaunchKernelGGL(k_fix_specials, dim3(1), dim3(256), 0, s, order, Kl, specials[0], specials[1], specials[2]);
     const size_t n = (size_t)T * Kl * nu;
     int blocks = (int)((n + 255) / 256);

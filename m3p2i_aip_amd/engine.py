@@ -190,6 +190,15 @@ class HipEngine(_CObject):
         """Samples sorted into coherent wavefronts (default) or assigned by index; same results."""
         self._ck(self.lib.m3_set_wave_order(self._h, int(bool(on))))
 
+    def wave_order(self):
+        """The wavefront order the last rollout went by: int32 tensor [K_local] (a copy; slot -> local sample index), or None
+        when it went by index (order off, relabelled, K_local < 128, random sampling, simple mode, noise churn, panda)."""
+        p, n = C.c_void_p(), C.c_int()
+        self._ck(self.lib.m3_wave_order(self._h, C.byref(p), C.byref(n)))
+        if not p.value:
+            return None
+        return torch.as_tensor(_DevArray(p.value, (n.value,), "<i4", self), device=self.device).clone()
+
     def relabel_samples(self):
         """Permute the noise rows once into wavefront order (labels of a generated sample set carry
         no meaning): same sample set, coalesced stores.  See include/m3p2i_hip.h."""
