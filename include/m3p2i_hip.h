@@ -300,9 +300,11 @@ void m3_default_panda_scene(m3_panda_scene* sc);
  * shelf, obs_half, mu) runs the run-time-scene instances of the rollout (all tasks, both samplers, both mppi modes; 1, 8 or 16
  * lanes per sample chosen as before; the reach-cost kernel as before), of the step, of m3_cost and of the views' refresh -- at
  * the default values the same bits.
- * NOT batched: m3_batch_command with a handle that needs the run-time-scene instance, and m3_panda_episodes_create / _act /
- * _act_first with such a world or planner, return M3_ERR_UNSUPPORTED (the message names m3_set_panda_scene and the index of
- * the handle); nothing is launched. */
+ * Batched on request: a batch created with m3_batch_create_ex(..., M3_BATCH_PANDA_RUNTIME, ...) takes a handle that needs the
+ * run-time-scene instance (bit-identical to its own m3_command, like every batched handle).  A batch made by m3_batch_create
+ * -- whose table slots have no room for the larger entry -- returns M3_ERR_UNSUPPORTED for it, and so do
+ * m3_panda_episodes_create / _act / _act_first with such a world or planner, whatever batch they are handed (the message
+ * names m3_set_panda_scene and the index of the handle); nothing is launched. */
 int m3_set_panda_scene(m3_handle* h, const m3_panda_scene* sc);
 int m3_get_panda_scene(const m3_handle* h, m3_panda_scene* out);
 /* Test and A/B switch: -1 the automatic choice above (default), 1 the run-time-scene instances whatever the values, 0 never --
@@ -342,9 +344,11 @@ int m3_panda_scene_rows_set(const m3_handle* h);
  * cost's kernels, which give the literal cost's bits at the default weights; rows that all equal one scene give the bits of
  * m3_set_panda_scene with that scene.  m3_panda_scene_instance_used reports 1; m3_set_panda_scene_instance(h, 0) makes the next
  * command / rollout M3_ERR_STATE ("... forced off ... m3_set_panda_rollout_scenes").
- * NOT batched: m3_batch_command with such a handle, and m3_panda_episodes_create / _observe / _act / _act_first with such a
- * planner, return M3_ERR_UNSUPPORTED (the message names m3_set_panda_rollout_scenes and the index of the handle); nothing is
- * launched. */
+ * Batched on request: a batch created with m3_batch_create_ex(..., M3_BATCH_PANDA_RUNTIME, ...) takes such a handle (each
+ * sample reads its row of the handle's own table; bit-identical to the handle's own m3_command).  A batch made by
+ * m3_batch_create returns M3_ERR_UNSUPPORTED for it, and so do m3_panda_episodes_create / _observe / _act / _act_first with
+ * such a planner, whatever batch they are handed (the message names m3_set_panda_rollout_scenes and the index of the handle);
+ * nothing is launched. */
 int m3_set_panda_rollout_scenes(m3_handle* h, const m3_panda_scene* scenes, int n);
 int m3_get_panda_rollout_scene(const m3_handle* h, int row, m3_panda_scene* out);
 /* 0 / 1: whether the handle's rollout is on per-sample workspaces */
@@ -477,9 +481,11 @@ void m3_default_panda_cost_weights(m3_panda_cost_weights* w);
  * for one -- at the default weights the same bits.  Step, pull and push read no cost and stay as they are.
  * m3_set_panda_scene_instance / m3_panda_scene_instance_used keep their meaning ("used": whether the handle's workspace needed
  * the run-time scene); scene instance 0 with a geometry other than the default refuses as before, whatever the weights.
- * NOT batched: m3_batch_command with a planner that needs the weighted family, and m3_panda_episodes_create / _observe / _act /
- * _act_first with such a planner, return M3_ERR_UNSUPPORTED (the message names m3_set_panda_cost_weights and the index of the
- * handle); nothing is launched.  A sim_only world handle with weights is accepted there: its step reads no weight. */
+ * Batched on request: a batch created with m3_batch_create_ex(..., M3_BATCH_PANDA_RUNTIME, ...) takes a planner that needs the
+ * weighted family (bit-identical to its own m3_command).  A batch made by m3_batch_create returns M3_ERR_UNSUPPORTED for it,
+ * and so do m3_panda_episodes_create / _observe / _act / _act_first with such a planner, whatever batch they are handed (the
+ * message names m3_set_panda_cost_weights and the index of the handle); nothing is launched.  A sim_only world handle with
+ * weights is accepted by the episodes: its step reads no weight. */
 int m3_set_panda_cost_weights(m3_handle* h, const m3_panda_cost_weights* w);
 int m3_get_panda_cost_weights(const m3_handle* h, m3_panda_cost_weights* out);
 /* Test and A/B switch: -1 the automatic choice above (default), 1 the weighted family whatever the weights, 0 never -- with
@@ -711,9 +717,23 @@ int m3_update_finalize(m3_handle* h);
  * The message (m3_batch_last_error) names the offending index.  All work is enqueued on the handles' common stream.
  * actions_host: NULL, or a host buffer that receives the handles' plans one after the other, [rows][nu] each (rows =
  * u_per_command in simple mode, else T: [n][rows][nu] when all agree); the call then synchronises.
- * Per-handle timing (m3_enable_timing / m3_get_timing) is NOT updated by a batched call. */
+ * Per-handle timing (m3_enable_timing / m3_get_timing) is NOT updated by a batched call.
+ *
+ * m3_batch_create_ex(device, max_handles, flags, &out): flags == 0 is m3_batch_create; unknown bits are M3_ERR_BAD_ARG.
+ * M3_BATCH_PANDA_RUNTIME sizes the table slots and the host scratch for a second section of panda_env entries as well, and
+ * m3_batch_command on such a batch accepts, besides everything else, an unsharded panda_env planner handle that needs the
+ * run-time-scene instance (m3_set_panda_scene), the weighted family (m3_set_panda_cost_weights), both, or has a workspace per
+ * sample (m3_set_panda_rollout_scenes).  Every other refusal above stays, in the same order -- among them the "forced off"
+ * ones of m3_set_panda_scene_instance(h, 0) / m3_set_panda_weighted_cost_instance(h, 0) (M3_ERR_STATE) -- and so does the
+ * contract: each handle's results are bit-identical to its own m3_command's, m3_panda_scene_instance_used and
+ * m3_panda_weighted_cost_instance_used included, set as m3_rollout sets them.  Such handles group by family (literal, weighted
+ * on the run-time scene, workspace per sample) ahead of the fields above; a handle with the default workspace and weights
+ * runs the kernel it runs in any batch.  point_env handles with an arena per sample stay refused. */
+#define M3_BATCH_PANDA_RUNTIME 1
 typedef struct m3_batch m3_batch;
 int m3_batch_create(int device, int max_handles, m3_batch** out);   /* all device + pinned workspace allocated here */
+int m3_batch_create_ex(int device, int max_handles, int flags, m3_batch** out);
+int m3_batch_flags(const m3_batch* b);   /* the flags it was created with; M3_ERR_BAD_ARG for NULL */
 void m3_batch_destroy(m3_batch* b);
 const char* m3_batch_last_error(const m3_batch* b);   /* b may be NULL: the last failed m3_batch_create on this thread */
 int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float* actions_host);

@@ -44,6 +44,9 @@ class Config(C.Structure):
                 ("noise_sigma_full", C.c_float * (MAX_NU * MAX_NU)), ("seed", C.c_ulonglong)]
 
 
+BATCH_PANDA_RUNTIME = 1   # M3_BATCH_PANDA_RUNTIME (m3_batch_create_ex)
+
+
 class PointWorld(C.Structure):
     _fields_ = [("robot", C.c_float * 4), ("box", C.c_float * 7), ("dyn_obs", C.c_float * 7)]
 
@@ -258,6 +261,8 @@ SYMBOLS = [
     ("m3_p2p_detach", C.c_int, [_H]),
     ("m3_p2p_set_memory_kind", C.c_int, [_H, C.c_int]),
     ("m3_batch_create", C.c_int, [C.c_int, C.c_int, C.POINTER(_H)]),
+    ("m3_batch_create_ex", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
+    ("m3_batch_flags", C.c_int, [_H]),
     ("m3_batch_destroy", None, [_H]),
     ("m3_batch_last_error", C.c_char_p, [_H]),
     ("m3_batch_command", C.c_int, [_H, C.POINTER(_H), C.c_int, _FP]),

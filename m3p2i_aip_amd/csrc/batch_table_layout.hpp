@@ -2,8 +2,10 @@
 // tests/native/batch_table_layout_host.cpp can run it on its own).
 //
 // A point_env table: one section of rollout entries per variant (PointVariant: plain, weighted, scene -- each variant has an
-// entry type of its own), in that order, then the handles' UpdateArgs.  A panda_env table: its single section of rollout
-// entries, then the UpdateArgs.  Every section starts on a multiple of 16 bytes; a section without handles takes no room.
+// entry type of its own), in that order, then the handles' UpdateArgs.  A panda_env table: the section of literal rollout
+// entries, in a batch created with M3_BATCH_PANDA_RUNTIME then the section of run-time entries (handles with a run-time
+// workspace, tuned weights or a workspace per sample: a larger entry type), then the UpdateArgs.  Every section starts on a
+// multiple of 16 bytes; a section without handles takes no room.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -14,9 +16,11 @@ constexpr int BATCH_ROLLOUT_SECTIONS = 3;   // (POINT_VARIANTS, m3_internal.hpp)
 struct BatchTableSizes {
     size_t entry[BATCH_ROLLOUT_SECTIONS];   // bytes of one rollout entry of each point_env variant
     size_t panda_entry, update;             // ... of a panda_env rollout entry, of one UpdateArgs
+    size_t panda_entry_rt = 0;              // ... of a panda_env run-time entry; 0: a batch without M3_BATCH_PANDA_RUNTIME, whose
+                                            // panda tables have the literal section only (last and with a default: may be left out)
 };
 struct BatchTableLayout {
-    size_t off[BATCH_ROLLOUT_SECTIONS];   // start of each rollout section
+    size_t off[BATCH_ROLLOUT_SECTIONS];   // start of each rollout section (panda_env: 0 the literal, 1 the run-time entries)
     size_t upd_off;                       // start of the update section
     size_t total;                         // bytes of the table (what is copied to the device)
 };
@@ -35,21 +39,29 @@ inline BatchTableLayout batch_table_layout(const BatchTableSizes& z, const int n
     l.total = l.upd_off + handles * z.update;
     return l;
 }
-inline BatchTableLayout batch_table_layout_panda(const BatchTableSizes& z, int n) {
+// n: handles with a literal entry, n_rt: with a run-time entry (only in a batch whose sizes have panda_entry_rt).  Without
+// run-time entries the offsets and the total are those of the single-section table.
+inline BatchTableLayout batch_table_layout_panda(const BatchTableSizes& z, int n, int n_rt = 0) {
     BatchTableLayout l{};
-    l.upd_off = align16((size_t)n * z.panda_entry);
-    l.total = l.upd_off + (size_t)n * z.update;
+    l.off[1] = align16((size_t)n * z.panda_entry);
+    l.off[2] = l.off[1] + (size_t)n_rt * z.panda_entry_rt;   // (no third section: where the second one ends)
+    l.upd_off = align16(l.off[2]);
+    l.total = l.upd_off + ((size_t)n + (size_t)n_rt) * z.update;
     return l;
 }
 
 // The largest total of any call with up to max_handles handles: what m3_batch_create gives a slot.  A handle more never makes
 // a table smaller, so only the splits of exactly max_handles count.  Moving 16 handles from a section into the one with the
 // largest entries keeps every alignment gap (16 entries are a multiple of 16 bytes) and does not shrink the table: the worst
-// split has fewer than 16 handles in each of the other sections.
+// split has fewer than 16 handles in each of the other sections.  The same holds for the two sections of a panda_env table.
 inline size_t batch_table_capacity(const BatchTableSizes& z, int max_handles) {
     const int big = (int)(std::max_element(z.entry, z.entry + BATCH_ROLLOUT_SECTIONS) - z.entry);
     const int o1 = (big + 1) % BATCH_ROLLOUT_SECTIONS, o2 = (big + 2) % BATCH_ROLLOUT_SECTIONS;
     size_t worst = batch_table_layout_panda(z, max_handles).total;
+    if (z.panda_entry_rt != 0)
+        for (int a = 0; a < 16 && a <= max_handles; ++a)
+            worst = std::max({worst, batch_table_layout_panda(z, a, max_handles - a).total,
+                              batch_table_layout_panda(z, max_handles - a, a).total});
     for (int a = 0; a < 16 && a <= max_handles; ++a)
         for (int b = 0; b < 16 && a + b <= max_handles; ++b) {
             int n[BATCH_ROLLOUT_SECTIONS];

@@ -2052,7 +2052,9 @@ extern "C" int m3_command(m3_handle* h, float* action_host) {
 // One command() of each of n unsharded handles of one environment (handle 0's): per group of handles that run the same
 // kernel instance, ONE rollout launch and ONE update launch (a multi-modal group: as many as its residency chunks), the
 // handles' arguments read from a device table indexed by blockIdx.y (DESIGN.md "Batched command").  A panda_env group that
-// keeps the reach-cost record adds one k_panda_reach_cost launch (not counted by m3_batch_launches).  The handles keep
+// keeps the reach-cost record adds one k_panda_reach_cost launch (not counted by m3_batch_launches).  A batch created with
+// M3_BATCH_PANDA_RUNTIME also takes panda_env handles with a run-time workspace, tuned weights or a workspace per sample: the
+// second section of its panda table (BatchPandaEntryRT, rollout_panda_batch_rt.hip).  The handles keep
 // all of their state; the batch owns only the table: BATCH_SLOTS pinned host slots, each with a device slot and an event
 // recorded after the call's last launch (so it guards the host slot's copy AND the device slot's readers, whichever
 // stream they ran on).
@@ -2061,6 +2063,8 @@ constexpr int BATCH_SLOTS = 4;
 
 namespace {
 struct BatchKey {
+    int variant;               // panda_env: 0 kb_rollout_panda (the literal section), 1 kb_rollout_panda_w, 2 kb_rollout_panda_v
+                               // (the run-time section); point_env: 0 (its variants are in the plan)
     RolloutPlan roll;          // rollout: the handle's plan (plan_rollout) ...
     int K, T;                  // ... and sizes
     SmallUpdateInstance upd;   // update: k_update_small's template arguments, width, top-k workgroups
@@ -2069,7 +2073,8 @@ struct BatchKey {
 auto rollout_fields(const BatchKey& k) {
     const RolloutPlan& p = k.roll;
     // (scene, then weighted, first: that is the order of PointVariant, by which the table's sections lie)
-    return std::tie(p.scene, p.weighted, p.instance, p.ref, p.lps, p.forces, p.general, p.shadows, p.rec, k.K, k.T, p.lanes);
+    // (panda_env: the variant first, so that each of its two sections is contiguous in key order)
+    return std::tie(k.variant, p.scene, p.weighted, p.instance, p.ref, p.lps, p.forces, p.general, p.shadows, p.rec, k.K, k.T, p.lanes);
 }
 auto update_fields(const BatchKey& k) { return std::tie(k.upd.nu, k.upd.multi, k.upd.jr, k.upd.wt, k.upd.n_cand, k.T); }
 bool same_rollout(const BatchKey& x, const BatchKey& y) { return rollout_fields(x) == rollout_fields(y); }
@@ -2083,11 +2088,17 @@ struct BatchHandle {   // one handle's command as planned, in call order (copied
     BatchKey key;
 };
 constexpr BatchTableSizes BATCH_TABLE_SIZES = {{sizeof(BatchRolloutEntry), sizeof(BatchRolloutEntryW), sizeof(BatchRolloutEntryS)},
-                                               sizeof(BatchPandaEntry), sizeof(UpdateArgs)};
+                                               sizeof(BatchPandaEntry), sizeof(UpdateArgs), 0};
+// ... of a batch created with M3_BATCH_PANDA_RUNTIME
+constexpr BatchTableSizes BATCH_TABLE_SIZES_RT = {{sizeof(BatchRolloutEntry), sizeof(BatchRolloutEntryW), sizeof(BatchRolloutEntryS)},
+                                                  sizeof(BatchPandaEntry), sizeof(UpdateArgs), sizeof(BatchPandaEntryRT)};
+static_assert(alignof(BatchPandaEntryRT) <= 16 && alignof(BatchPandaEntry) <= 16, "the table's sections start on multiples of 16");
 }  // namespace
 
 struct m3_batch {
     int device = 0, max_handles = 0;
+    int flags = 0;           // m3_batch_create_ex's (M3_BATCH_PANDA_RUNTIME)
+    BatchTableSizes sizes = BATCH_TABLE_SIZES;   // the entry sizes its tables are laid out with (flags)
     std::string err;
     size_t slot_bytes = 0;   // of a slot: the largest table of max_handles handles (batch_table_layout.hpp)
     OwnedBlocks mem{&m3_release_block, 3 * BATCH_SLOTS};   // owns the slots; the three arrays below are views
@@ -2113,9 +2124,15 @@ extern "C" void m3_batch_destroy(m3_batch* b) {
     delete b;
 }
 
-extern "C" int m3_batch_create(int device, int max_handles, m3_batch** out) {
+extern "C" int m3_batch_create(int device, int max_handles, m3_batch** out) { return m3_batch_create_ex(device, max_handles, 0, out); }
+
+extern "C" int m3_batch_flags(const m3_batch* b) { return b ? b->flags : M3_ERR_BAD_ARG; }
+
+// (the messages keep m3_batch_create's name: flags == 0 is that call)
+extern "C" int m3_batch_create_ex(int device, int max_handles, int flags, m3_batch** out) {
     if (!out) { g_batch_err = "m3_batch_create: null argument"; return M3_ERR_BAD_ARG; }
     *out = nullptr;
+    if (flags & ~M3_BATCH_PANDA_RUNTIME) { g_batch_err = "m3_batch_create_ex: unknown flag bits"; return M3_ERR_BAD_ARG; }
     if (max_handles < 1 || max_handles > 65535) {   // (blockIdx.y picks the handle)
         g_batch_err = "m3_batch_create: max_handles must be in 1 .. 65535";
         return M3_ERR_BAD_ARG;
@@ -2131,7 +2148,9 @@ extern "C" int m3_batch_create(int device, int max_handles, m3_batch** out) {
     if (!b) { g_batch_err = "m3_batch_create: out of host memory"; return M3_ERR_HIP; }
     b->device = device;
     b->max_handles = max_handles;
-    b->slot_bytes = batch_table_capacity(BATCH_TABLE_SIZES, max_handles);
+    b->flags = flags;
+    if (flags & M3_BATCH_PANDA_RUNTIME) b->sizes = BATCH_TABLE_SIZES_RT;
+    b->slot_bytes = batch_table_capacity(b->sizes, max_handles);
     try {
         b->seen.resize(max_handles);
         b->hd.resize(max_handles);
@@ -2169,8 +2188,9 @@ extern "C" int m3_batch_launches(const m3_batch* b, int* rollout_launches, int* 
 
 // the conditions under which m3_batch_command refuses a handle of the call's environment, device and stream (nullptr: none;
 // code: the return code) -- m3_episodes_create checks them too.  u: the arguments of the handle's update, as m3_command
-// launches it
-static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code) {
+// launches it.  panda_runtime: the caller's table has the run-time section (a batch created with M3_BATCH_PANDA_RUNTIME), so a
+// panda_env planner that needs the run-time-scene instance, the weighted family or has a workspace per sample passes
+static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code, bool panda_runtime = false) {
     const m3_config& c = h->cfg;
     code = M3_ERR_STATE;
     if (c.K_local != c.K_global) return "sharded handle (K_local != K_global)";
@@ -2180,17 +2200,19 @@ static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code) {
         return "it has an arena per sample (m3_set_point_rollout_scenes), which only m3_rollout / m3_command run";
     }
     if (const char* why = rollout_refusal(h)) return why;
-    if (const char* why = panda_scene_unbatched(h)) {   // (the table's entry carries a PandaScene)
-        code = M3_ERR_UNSUPPORTED;
-        return why;
-    }
-    if (const char* why = panda_rows_unbatched(h)) {   // (... and no table of rows)
-        code = M3_ERR_UNSUPPORTED;
-        return why;
-    }
-    if (const char* why = panda_weights_unbatched(h)) {   // (... and no weights: its kernels form the literal cost)
-        code = M3_ERR_UNSUPPORTED;
-        return why;
+    if (!panda_runtime) {
+        if (const char* why = panda_scene_unbatched(h)) {   // (the table's entry carries a PandaScene)
+            code = M3_ERR_UNSUPPORTED;
+            return why;
+        }
+        if (const char* why = panda_rows_unbatched(h)) {   // (... and no table of rows)
+            code = M3_ERR_UNSUPPORTED;
+            return why;
+        }
+        if (const char* why = panda_weights_unbatched(h)) {   // (... and no weights: its kernels form the literal cost)
+            code = M3_ERR_UNSUPPORTED;
+            return why;
+        }
     }
     fill_update_impl_args(h, u, true);
     code = M3_ERR_UNSUPPORTED;
@@ -2209,8 +2231,15 @@ static int batch_refuse(m3_batch* b, int code, int i, const char* msg) {
     return code;
 }
 
-extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float* actions_host) {
-    if (!b) { g_batch_err = "m3_batch_command: null batch"; return M3_ERR_BAD_ARG; }
+// which kernels a panda_env handle's entry is for (BatchKey::variant), by m3_rollout's own dispatch
+static int batch_panda_variant(const m3_handle* h) {
+    if (h->panda_rollout_scenes_on) return 2;
+    return (panda_weighted(h) || panda_scene_runtime(h)) ? 1 : 0;
+}
+
+// panda_runtime: whether the run-time section may be used -- the batch's flag for m3_batch_command; never for the lockstep
+// panda episodes, whose pre and post kernels know one compiled-in workspace (whatever batch they are handed)
+static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* actions_host, bool panda_runtime) {
     // ---- every check before any launch: a refused call leaves every handle as it was ----
     if (!hs) return batch_refuse(b, M3_ERR_BAD_ARG, -1, "null handle list");
     if (n <= 0 || n > b->max_handles) return batch_refuse(b, M3_ERR_BAD_ARG, -1, "n must be in 1 .. max_handles");
@@ -2235,8 +2264,9 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
                                                                 : "panda_env handle in a batch of point_env handles (one environment per call)");
         if (h->stream != s) return batch_refuse(b, M3_ERR_STATE, i, "its stream differs from handle 0's");
         int code;
-        if (const char* why = batch_refusal(h, hd[i].u, code)) return batch_refuse(b, code, i, why);
+        if (const char* why = batch_refusal(h, hd[i].u, code, panda_runtime)) return batch_refuse(b, code, i, why);
         BatchKey& k = hd[i].key;
+        k.variant = panda ? batch_panda_variant(h) : 0;
         k.upd = update_small_instance(hd[i].u);
         hd[i].u.n_cand = k.upd.n_cand;   // (what launch_update_small hands its instance)
         k.K = h->cfg.K_local; k.T = h->cfg.T;
@@ -2247,6 +2277,8 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
     for (int i = 0; i < n; ++i) {
         const int rc = plan_rollout(hs[i], hd[i].a, hd[i].pa, hd[i].key.roll);
         if (rc != M3_OK) { b->err = "m3_batch_command: " + hs[i]->err; return rc; }
+        // (the run-time families are GENERAL builds only: the plan's choice of the literal kernel's build does not split a group)
+        if (hd[i].key.variant != 0) hd[i].key.roll.general = 1;
     }
     // ---- groups: handles in key order (ties in call order) ----
     std::sort(b->by_roll.begin(), b->by_roll.begin() + n, [hd](int x, int y) {
@@ -2262,13 +2294,17 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
         b->in_flight[slot] = false;
     }
     // point_env: in key order the handles come by variant (rollout_fields), as the table's sections do
+    // panda_env: by section -- the literal entries (variant 0), then the run-time ones
     int count[POINT_VARIANTS] = {};
+    int n_lit = 0;
     if (!panda)
         for (int i = 0; i < n; ++i) ++count[point_variant(hd[i].key.roll)];
-    const BatchTableLayout lay = panda ? batch_table_layout_panda(BATCH_TABLE_SIZES, n) : batch_table_layout(BATCH_TABLE_SIZES, count);
+    else
+        for (int i = 0; i < n; ++i) n_lit += hd[i].key.variant == 0 ? 1 : 0;
+    const BatchTableLayout lay = panda ? batch_table_layout_panda(b->sizes, n_lit, n - n_lit) : batch_table_layout(b->sizes, count);
     // byte offset of the rollout entry of the p-th handle in key order
     auto entry_off = [&](int p) {
-        if (panda) return (size_t)p * sizeof(BatchPandaEntry);
+        if (panda) return p < n_lit ? (size_t)p * sizeof(BatchPandaEntry) : lay.off[1] + (size_t)(p - n_lit) * sizeof(BatchPandaEntryRT);
         int v = 0;
         for (; p >= count[v]; ++v) p -= count[v];
         return lay.off[v] + (size_t)p * BATCH_TABLE_SIZES.entry[v];
@@ -2277,7 +2313,12 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
         const int i = b->by_roll[p];
         const m3_handle* h = hs[i];
         char* e = b->host[slot] + entry_off(p);
-        if (panda) { *reinterpret_cast<BatchPandaEntry*>(e) = {hd[i].a, hd[i].pa, h->pscene}; continue; }
+        if (panda) {
+            if (hd[i].key.variant == 0) *reinterpret_cast<BatchPandaEntry*>(e) = {hd[i].a, hd[i].pa, h->pscene};
+            else *reinterpret_cast<BatchPandaEntryRT*>(e) = {hd[i].a, hd[i].pa, h->pscene_rt, h->panda_cost_weights,
+                                                             hd[i].key.variant == 2 ? h->panda_rows_dev : nullptr};
+            continue;
+        }
         switch (point_variant(hd[i].key.roll)) {
             case POINT_SCENE: *reinterpret_cast<BatchRolloutEntryS*>(e) = {hd[i].a, h->scene_rt, h->cost_weights}; break;
             case POINT_WEIGHTED: *reinterpret_cast<BatchRolloutEntryW*>(e) = {hd[i].a, h->scene, h->cost_weights}; break;
@@ -2296,12 +2337,24 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
         const BatchKey& k = hd[b->by_roll[p]].key;
         int q = p + 1;
         while (q < n && same_rollout(hd[b->by_roll[q]].key, k)) ++q;
-        if (panda) launch_rollout_panda_batch(reinterpret_cast<const BatchPandaEntry*>(dslot + entry_off(p)), q - p, k.roll, k.K, s);
+        if (panda && k.variant != 0)
+            launch_rollout_panda_batch_rt(reinterpret_cast<const BatchPandaEntryRT*>(dslot + entry_off(p)), q - p, k.roll, k.K, k.variant == 2, s);
+        else if (panda) launch_rollout_panda_batch(reinterpret_cast<const BatchPandaEntry*>(dslot + entry_off(p)), q - p, k.roll, k.K, s);
         else launch_rollout_point_batch(dslot + entry_off(p), q - p, k.roll, s);
         ++n_roll;
         p = q;
     }
     HIPCHK(b, hipGetLastError());
+    // what each handle's rollout ran, as m3_rollout records it (a batch without the run-time section runs the literal kernels
+    // only and leaves the record as it always did)
+    if (panda && panda_runtime)
+        for (int i = 0; i < n; ++i) {
+            m3_handle* h = hs[i];
+            const bool rt = panda_scene_runtime(h), wt = panda_weighted(h);
+            if (hd[i].key.variant == 2) { h->panda_scene_used = 1; h->panda_weighted_used = wt ? 1 : 0; }
+            else if (wt) { h->panda_scene_used = rt ? 1 : 0; h->panda_weighted_used = 1; }
+            else { h->panda_scene_used = rt ? 1 : 0; h->panda_weighted_used = 0; }
+        }
     // ---- one update launch per group; multi-modal groups in chunks whose whole grid is resident ----
     for (int p = 0; p < n;) {
         const BatchKey& k = hd[b->by_upd[p]].key;
@@ -2339,6 +2392,11 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
         HIPCHK(b, hipStreamSynchronize(s));
     }
     return M3_OK;
+}
+
+extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float* actions_host) {
+    if (!b) { g_batch_err = "m3_batch_command: null batch"; return M3_ERR_BAD_ARG; }
+    return batch_command(b, hs, n, actions_host, (b->flags & M3_BATCH_PANDA_RUNTIME) != 0);
 }
 
 static int ensure_sim(m3_handle* h);
@@ -3045,7 +3103,8 @@ extern "C" int m3_panda_episodes_act(m3_panda_episodes* eps, m3_batch* batch, co
         eps->live.push_back(h);
     }
     if (!eps->live.empty()) {
-        rc = m3_batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr);
+        // (never the run-time section: a planner or world of these episodes stays on the compiled-in workspace and the literal cost)
+        rc = batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr, false);
         if (rc != M3_OK) { eps->err = std::string("m3_panda_episodes_act: ") + m3_batch_last_error(batch); return rc; }
     }
     return peps_post(eps, ended_host);

@@ -436,6 +436,19 @@ void launch_panda_reach_cost_w(const RolloutArgs& a, const PandaArgs& pa, const 
 // (m3_set_panda_scene_rows)
 void launch_rollout_panda_v(const RolloutArgs& a, const PandaArgs& pa, const PandaSceneRT& uni, const PandaCostWeights& wt,
                             const float* rows, const RolloutPlan& p, hipStream_t s);
+// one panda_env handle's rollout in the second section of m3_batch_command's table (a batch created with
+// M3_BATCH_PANDA_RUNTIME; rollout_panda_batch_rt.hip): a handle that needs the run-time scene, the weighted cost or both, or has
+// a workspace per sample (rows: the handle's device table [PANDA_SCENE_ROW_WORDS][K_local], else null)
+struct BatchPandaEntryRT {
+    RolloutArgs a;
+    PandaArgs pa;
+    PandaSceneRT sc;
+    PandaCostWeights wt;
+    const float* rows;
+};
+// as launch_rollout_panda_batch for such entries: kb_rollout_panda_w, or kb_rollout_panda_v when the group's entries carry
+// rows (per_sample), + one launch of kb_panda_reach_cost_w when the plan keeps the record buffer
+void launch_rollout_panda_batch_rt(const BatchPandaEntryRT* tab, int n, const RolloutPlan& p, int Kl, bool per_sample, hipStream_t s);
 void launch_psim_step_v(const PandaSceneRT& uni, const float* rows, const SimViews& v, float* world, const float* u, float* u_keep,
                         int Kl, hipStream_t s);
 void launch_psim_pull_v(const PandaSceneRT& uni, const float* rows, const SimViews& v, float* world, int Kl, hipStream_t s);

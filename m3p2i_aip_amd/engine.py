@@ -735,11 +735,13 @@ class HipBatch(_CObject):
     panda_env, as the first engine's) in one rollout launch and one update launch per group of handles that run the same
     kernel instance (``m3_batch_command``, include/m3p2i_hip.h).  Each engine's results are bit-identical to its own
     ``command()``, a panda_env engine's automatic kernel form included; the batch holds no planner state, only the device
-    workspace of its argument table (allocated here, for up to ``max_handles`` engines per call)."""
+    workspace of its argument table (allocated here, for up to ``max_handles`` engines per call).
+    ``panda_runtime=True`` (``M3_BATCH_PANDA_RUNTIME``) makes room for the larger table entries of panda_env engines with a
+    workspace of their own, tuned cost weights or a workspace per sample, which any other batch refuses."""
 
     _ptr, _destroy, _last_error = "_b", "m3_batch_destroy", "m3_batch_last_error"
 
-    def __init__(self, max_handles, device=0):
+    def __init__(self, max_handles, device=0, panda_runtime=False):
         if not torch.cuda.is_available():
             raise L.M3Error("HipBatch needs a HIP device (torch.cuda.is_available() is False); there is no CPU fallback")
         self.lib = L.load()
@@ -748,7 +750,10 @@ class HipBatch(_CObject):
         self._b = C.c_void_p()
         torch.cuda.set_device(self.device)
         torch.zeros(1, device=self.device)  # make sure the HIP context exists
-        self._ck(self.lib.m3_batch_create(int(device), self.max_handles, C.byref(self._b)))
+        if panda_runtime:
+            self._ck(self.lib.m3_batch_create_ex(int(device), self.max_handles, L.BATCH_PANDA_RUNTIME, C.byref(self._b)))
+        else:
+            self._ck(self.lib.m3_batch_create(int(device), self.max_handles, C.byref(self._b)))
         self._arr = (C.c_void_p * self.max_handles)()
 
     def command(self, engines, sync_host=False):
@@ -771,6 +776,13 @@ class HipBatch(_CObject):
             return [out[offs[i]:offs[i + 1]].reshape(rows[i], engines[i].cfg.nu) for i in range(n)]
         self._ck(self.lib.m3_batch_command(self._b, arr, n, None))
         return [e._action_out if e._action_out is not None else e.buffer(L.BUF_ACTION_OUT) for e in engines]
+
+    def flags(self):
+        """The flags the batch was created with (``L.BATCH_PANDA_RUNTIME`` or 0)."""
+        flags = self.lib.m3_batch_flags(self._b)
+        if flags < 0:
+            self._ck(flags)
+        return flags
 
     def launches(self):
         """(rollout launches, update launches) of the last successful command."""

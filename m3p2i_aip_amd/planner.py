@@ -743,9 +743,10 @@ class MPPI():
 
 
 _BATCHES = {}   # device index -> the HipBatch command_batch uses (grown when a call lists more planners)
+_BATCHES_PANDA_RUNTIME = {}   # ... with panda_runtime=True: a second batch per device, the default one is not re-created
 
 
-def command_batch(planners, states):
+def command_batch(planners, states, panda_runtime=False):
     """``[p.command(s) for p, s in zip(planners, states)]`` with one batched library call (m3_batch_command) per
     environment in the list: the planners' rollouts and updates run in one launch per group of planners that use the
     same kernel instance (point_env and panda_env planners alike; a list that mixes them makes one call for each).  Each
@@ -753,7 +754,10 @@ def command_batch(planners, states):
     returned tensors are the ones its own command() would have returned, bit for bit -- for a panda_env planner with the
     same automatic kernel form.  A planner whose fused / step decision is still pending gets that first command on its
     own.  Unsharded fused-path planners on the current torch stream only: step-mode or sharded planners and planners with
-    collectives installed raise ValueError (the library refuses the rest, e.g. panda_env with K > 4096, with M3Error)."""
+    collectives installed raise ValueError (the library refuses the rest, e.g. panda_env with K > 4096, with M3Error).
+    ``panda_runtime=True``: panda_env planners with a workspace of their own, panda cost weights of their own or a workspace
+    per sample are batched too (a batch created with M3_BATCH_PANDA_RUNTIME, kept next to the default one); without it they
+    raise ValueError as before."""
     planners, states = list(planners), list(states)
     if len(planners) != len(states):
         raise ValueError("command_batch: one state per planner")
@@ -765,16 +769,16 @@ def command_batch(planners, states):
         if p.has_rollout_scenes:
             raise ValueError(f"command_batch: planner {i} has an arena per sample (set_rollout_scenes / a wrapper with "
                              "point_scenes): m3_batch_command does not run those, use planner.command")
-        if getattr(p, "has_panda_rollout_scenes", False):
+        if not panda_runtime and getattr(p, "has_panda_rollout_scenes", False):
             raise ValueError(f"command_batch: planner {i} has a workspace per sample (set_panda_rollout_scenes / a wrapper with "
                              "panda_scenes): m3_batch_command does not run those, use planner.command")
         if not isinstance(p._engine, HipEngine):
             raise ValueError(f"command_batch: planner {i} does not run on the HIP library")
-        if p.needs_panda_scene_instance:
+        if not panda_runtime and p.needs_panda_scene_instance:
             raise ValueError(f"command_batch: planner {i} plans in a workspace of its own (m3_set_panda_scene: a wrapper with "
                              "panda_scene / actors, or set_panda_scene by hand): m3_batch_command does not run the run-time-scene "
                              "instance, use planner.command")
-        if not getattr(getattr(p, "_objective", None), "has_default_panda_cost_weights", True):
+        if not panda_runtime and not getattr(getattr(p, "_objective", None), "has_default_panda_cost_weights", True):
             raise ValueError(f"command_batch: planner {i} has panda cost weights of its own (m3_set_panda_cost_weights: "
                              "`panda_cost_weights` / set_panda_cost_weights): m3_batch_command does not run the weighted cost "
                              "instance, use planner.command")
@@ -796,11 +800,13 @@ def command_batch(planners, states):
         batched.append(p._engine)
     if batched:
         dev = batched[0].device.index or 0
-        b = _BATCHES.get(dev)
+        cache = _BATCHES_PANDA_RUNTIME if panda_runtime else _BATCHES
+        b = cache.get(dev)
         if b is None or b.max_handles < len(batched):
             if b is not None:
                 b.close()
-            b = _BATCHES[dev] = HipBatch(max(64, len(batched)), device=dev)
+            b = cache[dev] = HipBatch(max(64, len(batched)), device=dev, panda_runtime=True) if panda_runtime else \
+                HipBatch(max(64, len(batched)), device=dev)
         for env in sorted({e.cfg.env_type for e in batched}):     # (the library takes one environment per call)
             b.command([e for e in batched if e.cfg.env_type == env])
     return outs

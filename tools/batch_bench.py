@@ -9,6 +9,14 @@ Both are timed with HIP events around `--iters` iterations after `--warmup` (ms 
 Each configuration runs in a child process of its own under a time limit; the parent prints ONE JSON line.
 
     python tools/batch_bench.py [--only c2_push] [--json out.json] [--iters 50] [--warmup 10] [--repeats 5]
+
+The `*_rt` configurations (panda_env, a batch created with M3_BATCH_PANDA_RUNTIME; not part of the default list, name them with
+--only) measure, per n and in one process on the same worlds, three kinds of handles: `literal` (the default workspace and
+weights: kb_rollout_panda), `weighted` (tuned weights on the default workspace: kb_rollout_panda_w) and `per_sample` (a spread
+of 0.3 over the workspaces as tools/panda_rollout_scenes_bench.py: kb_rollout_panda_v) -- each batched and back to back, with
+the ratios of the non-literal kinds' batched time to the literal one's.  Two controls do the literal handles' work, bit for
+bit, on the other kernels: `weighted_same_work` (the weighted instance forced at the default weights) and
+`per_sample_same_work` (K rows of the default workspace) -- what the kernels cost, apart from what the tuned handles meet.
 """
 import argparse
 import ctypes as C
@@ -36,6 +44,12 @@ PANDA_CONFIGS = {
     "c4_pick": ("pick", ("pick", 12), 4000, 20, (1, 4, 16)),
     "shipped_pick": ("pick", ("pick", 6), 200, 12, (1, 16, 64)),
 }
+
+
+# the same with run-time entries: name -> the PANDA_CONFIGS entry whose worlds it takes
+PANDA_RT_CONFIGS = {"shipped_pick_rt": "shipped_pick", "c4_reach_rt": "c4_reach", "c4_pick_rt": "c4_pick"}
+RT_WEIGHTS = dict(reach_dist=20.0, reach_tilt=5.0, pick_goal=7.5, pick_ori=25.0, collision=500.0, shelf_force=3.0, place_grip=3.0)
+RT_SPREAD = 0.3
 
 
 def panda_world_of(task_phase, K, T, episode, device):
@@ -78,20 +92,38 @@ def measure(name, iters, warmup, repeats):
     from m3p2i_aip_amd import sampling
     from m3p2i_aip_amd.engine import HipBatch, HipEngine, make_config
     engs = []
-    if name in PANDA_CONFIGS:
-        task, phase, K, T, ns = PANDA_CONFIGS[name]
+    kinds = None
+    if name in PANDA_RT_CONFIGS:
+        kinds = ("literal", "weighted", "per_sample", "weighted_same_work", "per_sample_same_work")
+        name_worlds = PANDA_RT_CONFIGS[name]
+    else:
+        name_worlds = name
+    if name_worlds in PANDA_CONFIGS:
+        task, phase, K, T, ns = PANDA_CONFIGS[name_worlds]
         mm = False
         n_max = max(ns)
         pk = dict(u_min=[-2.0] * 7 + [-1.5] * 2, u_max=[2.0] * 7 + [1.5] * 2, noise_sigma_diag=[10.0] * 7 + [0.8] * 2,
                   lambda_=0.05, pre_height_diff=0.05, dt=0.01)
         knots = sampling.halton_knots(K, T, 9, 4, 2, 0, K, scramble="none")
         worlds = [panda_world_of(phase, K, T, e_i, "cuda:0") for e_i in range(n_max)]
-        for w, goal in worlds:
-            e = HipEngine(make_config(K=K, T=T, nu=9, env_type="panda_env", **pk))
-            e.set_noise_knots(knots, 2, 0.5)
-            e.set_objective(task, goal, gripper_cmd=1 if task == "reach" else 2)
-            e.set_world_panda_raw(w)
-            engs.append(e)
+        by_kind = {}
+        for kind in kinds or ("literal",):
+            for w, goal in worlds:
+                e = HipEngine(make_config(K=K, T=T, nu=9, env_type="panda_env", **pk))
+                e.set_noise_knots(knots, 2, 0.5)
+                e.set_objective(task, goal, gripper_cmd=1 if task == "reach" else 2)
+                e.set_world_panda_raw(w)
+                if kind == "weighted":
+                    e.set_panda_cost_weights(RT_WEIGHTS)
+                elif kind == "per_sample":
+                    from m3p2i_aip_amd.scenes import spread_panda_scenes
+                    e.set_panda_rollout_scenes(spread_panda_scenes(K, RT_SPREAD, seed=1, nominal_rows=(0, K // 2, K - 1)))
+                elif kind == "weighted_same_work":
+                    e.set_panda_weighted_cost_instance(1)
+                elif kind == "per_sample_same_work":
+                    e.set_panda_rollout_scenes([None] * K)
+                by_kind.setdefault(kind, []).append(e)
+        engs = by_kind["literal"]
     else:
         scenario, task, goal, K, T, mm, ns = CONFIGS[name]
         pk = dict(u_min=[-3, -3], u_max=[3, 3], noise_sigma_diag=[3, 3], lambda_=0.5)
@@ -105,7 +137,7 @@ def measure(name, iters, warmup, repeats):
             e.set_world_point_raw(world_of(scenario, e_i))
             engs.append(e)
     lib = engs[0].lib
-    batch = HipBatch(n_max)
+    batch = HipBatch(n_max, panda_runtime=True) if kinds else HipBatch(n_max)
     stream = torch.cuda.current_stream()
 
     def timed(fn):
@@ -124,8 +156,8 @@ def measure(name, iters, warmup, repeats):
         return float(np.median(out)), out
 
     rows = []
-    for n in ns:
-        sel = engs[:n]
+    for n, kind in [(n, kind) for n in ns for kind in (kinds or (None,))]:
+        sel = (by_kind[kind] if kind else engs)[:n]
         arr = (C.c_void_p * n)(*[e._h.value for e in sel])
 
         def batched():
@@ -142,11 +174,16 @@ def measure(name, iters, warmup, repeats):
         b_ms, b_all = timed(batched)
         r_launch, u_launch = batch.launches()
         s_ms, s_all = timed(back_to_back)
-        rows.append(dict(n=n, batched_ms=round(b_ms, 4), back_to_back_ms=round(s_ms, 4),
+        rows.append(dict(n=n, **({"kind": kind} if kind else {}), batched_ms=round(b_ms, 4), back_to_back_ms=round(s_ms, 4),
                          speedup=round(s_ms / b_ms, 3), rollout_launches=r_launch, update_launches=u_launch,
-                         panda_lanes_per_sample=sorted({e.panda_lanes_per_sample_used() for e in sel}) if name in PANDA_CONFIGS else None,
+                         panda_lanes_per_sample=sorted({e.panda_lanes_per_sample_used() for e in sel}) if name_worlds in PANDA_CONFIGS else None,
                          batched_repeats_ms=[round(x, 4) for x in b_all], back_to_back_repeats_ms=[round(x, 4) for x in s_all],
                          wall_s=round(time.perf_counter() - t0, 2)))
+    if kinds:   # each non-literal kind's batched time over the literal batch of the same worlds and n
+        lit = {r["n"]: r["batched_ms"] for r in rows if r["kind"] == "literal"}
+        for r in rows:
+            r["batched_over_literal"] = round(r["batched_ms"] / lit[r["n"]], 3)
+        engs = [e for es in by_kind.values() for e in es]
     batch.close()
     for e in engs:
         e.close()
