@@ -1109,40 +1109,6 @@ extern "C" int m3_set_panda_scene_instance(m3_handle* h, int on) {
 
 extern "C" int m3_panda_scene_instance_used(m3_handle* h) { return h ? h->panda_scene_used : M3_ERR_BAD_ARG; }
 
-// ---- which panda_env kernels a handle runs: decided here and nowhere else ----
-// the run-time-scene instances (rollout_panda_scene.hip): by the values -- anything but the two masses off the defaults -- or
-// as m3_set_panda_scene_instance says
-static bool panda_scene_runtime(const m3_handle* h) {
-    if (h->cfg.env_type != M3_ENV_PANDA) return false;
-    return h->panda_scene_instance < 0 ? !panda_scene_geometry_is_default(h->panda_scene) : h->panda_scene_instance != 0;
-}
-// why the handle cannot run its kernels (M3_ERR_STATE; nullptr: it can)
-static const char* panda_scene_refusal(const m3_handle* h) {
-    if (h->cfg.env_type != M3_ENV_PANDA) return nullptr;
-    // (the rows' kernels are run-time-scene kernels: rollout_panda_rows.hip)
-    if (h->panda_scene_instance == 0 && h->panda_scene_rows_on)
-        return "the run-time-scene instance is forced off (m3_set_panda_scene_instance 0) but the handle has a workspace per environment (m3_set_panda_scene_rows)";
-    if (h->panda_scene_instance == 0 && h->panda_rollout_scenes_on)
-        return "the run-time-scene instance is forced off (m3_set_panda_scene_instance 0) but the handle has a workspace per sample (m3_set_panda_rollout_scenes)";
-    if (h->panda_scene_instance == 0 && !panda_scene_geometry_is_default(h->panda_scene))
-        return "the run-time-scene instance is forced off (m3_set_panda_scene_instance 0) but the handle's workspace (m3_set_panda_scene) is not the default";
-    return nullptr;
-}
-// why a path that carries a PandaScene only (m3_batch_command's table, the lockstep episodes' kernels) cannot take the handle
-static const char* panda_scene_unbatched(const m3_handle* h) {
-    return panda_scene_runtime(h) ? "its workspace (m3_set_panda_scene) needs the run-time-scene instance, which only m3_rollout / "
-                                    "m3_command and the handle's own step, cost and views run"
-                                  : nullptr;
-}
-// ... or a handle with a workspace per row, whose kernels (rollout_panda_rows.hip) only the handle's own calls launch
-static const char* panda_rows_unbatched(const m3_handle* h) {
-    if (h->panda_rollout_scenes_on)
-        return "it has a workspace per sample (m3_set_panda_rollout_scenes), which only m3_rollout / m3_command run";
-    if (h->panda_scene_rows_on)
-        return "it has a workspace per environment (m3_set_panda_scene_rows), which only the handle's own step, cost and views run";
-    return nullptr;
-}
-
 // ---- the panda_env cost weights (extension; per-handle state like the point ones: a fixed member, no allocation, no
 // synchronisation) ----
 static const char* const PANDA_COST_WEIGHT_NAMES[7] = {"reach_dist", "reach_tilt", "pick_goal", "pick_ori", "collision",
@@ -1183,30 +1149,60 @@ extern "C" int m3_set_panda_weighted_cost_instance(m3_handle* h, int on) {
 
 extern "C" int m3_panda_weighted_cost_instance_used(m3_handle* h) { return h ? h->panda_weighted_used : M3_ERR_BAD_ARG; }
 
-// the handle's weights are the defaults bit for bit (-0.0f is not 0.0f here: the kernels multiply by them)
-static bool default_panda_cost_weights(const m3_handle* h) {
-    return std::memcmp(&h->panda_cost_weights, &PANDA_COST_WEIGHTS_DEFAULT, sizeof(PandaCostWeights)) == 0;
+// ---- which panda_env kernels a handle runs, what the launch records, why a path refuses the handle: panda_variant.hpp decides,
+// from this reading of the handle.  Here: the reading, the texts and what a launcher receives ----
+static PandaVariantInput panda_input(const m3_handle* h) {
+    PandaVariantInput in;
+    in.scene_instance = h->panda_scene_instance;
+    in.weighted_instance = h->panda_weighted_instance;
+    in.geometry_default = panda_scene_geometry_is_default(h->panda_scene);   // (anything but the two masses off the defaults)
+    // (bit for bit: -0.0f is not 0.0f here, the kernels multiply by them)
+    in.weights_default = std::memcmp(&h->panda_cost_weights, &PANDA_COST_WEIGHTS_DEFAULT, sizeof(PandaCostWeights)) == 0;
+    in.rollout_scenes_on = h->panda_rollout_scenes_on;
+    in.scene_rows_on = h->panda_scene_rows_on;
+    in.sim_only = h->cfg.sim_only != 0;
+    return in;
 }
-// the weighted kernels (rollout_panda_weights.hip: the rollout, the reach-cost kernel, the step-mode cost -- on the run-time
-// scene, whatever panda_scene_runtime says): by the weights, or as m3_set_panda_weighted_cost_instance says
-static bool panda_weighted(const m3_handle* h) {
-    if (h->cfg.env_type != M3_ENV_PANDA) return false;
-    return h->panda_weighted_instance < 0 ? !default_panda_cost_weights(h) : h->panda_weighted_instance != 0;
-}
-// why the handle cannot run a rollout or a cost (M3_ERR_STATE; nullptr: it can)
-static const char* panda_weights_refusal(const m3_handle* h) {
-    if (h->cfg.env_type != M3_ENV_PANDA) return nullptr;
-    if (h->panda_weighted_instance == 0 && !default_panda_cost_weights(h))
-        return "the weighted cost instance is forced off (m3_set_panda_weighted_cost_instance 0) but the handle's cost weights (m3_set_panda_cost_weights) are not the defaults";
+static const char* panda_refusal_text(PandaRefusal r) {
+    switch (r) {
+        case PANDA_REFUSAL_NONE: return nullptr;
+        case PANDA_SCENE_OFF_ENV_ROWS:
+            return "the run-time-scene instance is forced off (m3_set_panda_scene_instance 0) but the handle has a workspace per environment (m3_set_panda_scene_rows)";
+        case PANDA_SCENE_OFF_SAMPLE_ROWS:
+            return "the run-time-scene instance is forced off (m3_set_panda_scene_instance 0) but the handle has a workspace per sample (m3_set_panda_rollout_scenes)";
+        case PANDA_SCENE_OFF_GEOMETRY:
+            return "the run-time-scene instance is forced off (m3_set_panda_scene_instance 0) but the handle's workspace (m3_set_panda_scene) is not the default";
+        case PANDA_WEIGHTS_OFF_TUNED:
+            return "the weighted cost instance is forced off (m3_set_panda_weighted_cost_instance 0) but the handle's cost weights (m3_set_panda_cost_weights) are not the defaults";
+        case PANDA_UNBATCHED_SCENE:
+            return "its workspace (m3_set_panda_scene) needs the run-time-scene instance, which only m3_rollout / "
+                   "m3_command and the handle's own step, cost and views run";
+        case PANDA_UNBATCHED_SAMPLE_ROWS:
+            return "it has a workspace per sample (m3_set_panda_rollout_scenes), which only m3_rollout / m3_command run";
+        case PANDA_UNBATCHED_ENV_ROWS:
+            return "it has a workspace per environment (m3_set_panda_scene_rows), which only the handle's own step, cost and views run";
+        case PANDA_UNBATCHED_WEIGHTS:
+            return "its cost weights (m3_set_panda_cost_weights) need the weighted cost instance, which only m3_rollout / "
+                   "m3_command and the handle's own m3_cost run";
+    }
     return nullptr;
 }
-// why a path whose kernels take the literal cost only (m3_batch_command's table, the lockstep episodes' planners) cannot take
-// the handle.  A sim_only handle passes: its step reads no weight
-static const char* panda_weights_unbatched(const m3_handle* h) {
-    return (!h->cfg.sim_only && panda_weighted(h))
-               ? "its cost weights (m3_set_panda_cost_weights) need the weighted cost instance, which only m3_rollout / "
-                 "m3_command and the handle's own m3_cost run"
-               : nullptr;
+// why the handle cannot run its own kernels on a side (M3_ERR_STATE; nullptr: it can, or it is no panda_env handle)
+static const char* panda_refusal(const m3_handle* h, PandaSide side) {
+    return h->cfg.env_type == M3_ENV_PANDA ? panda_refusal_text(panda_refusal(panda_input(h), side)) : nullptr;
+}
+// why a path that carries a PandaScene and forms the literal cost only (a batch table without the run-time section, the lockstep
+// episodes' kernels) cannot take the handle (M3_ERR_UNSUPPORTED; nullptr as above)
+static const char* panda_unbatched(const m3_handle* h, PandaUnbatchedOrder order) {
+    return h->cfg.env_type == M3_ENV_PANDA ? panda_refusal_text(panda_unbatched(panda_input(h), order)) : nullptr;
+}
+// a launcher's view of the handle for a variant, and the record of what an accepted call launches
+static PandaLaunchScene panda_launch_scene(const m3_handle* h, PandaVariant v) {
+    return {v, &h->pscene, &h->pscene_rt, &h->panda_cost_weights, h->panda_rows_dev};
+}
+static void panda_record_used(m3_handle* h, const PandaDecision& d) {
+    if (d.scene_used != PANDA_USED_UNCHANGED) h->panda_scene_used = d.scene_used;
+    if (d.weighted_used != PANDA_USED_UNCHANGED) h->panda_weighted_used = d.weighted_used;
 }
 
 extern "C" int m3_set_multi_modal(m3_handle* h, int mm) {
@@ -1364,8 +1360,7 @@ static const char* rollout_refusal(const m3_handle* h) {
     if (c.mode_simple && !c.sampling_random && !h->have_noise)
         return "m3_rollout: simple mode needs m3_set_noise or sampling_random";
     if (h->task == M3_TASK_PUSH_PULL && !c.multi_modal) return "m3_rollout: push_pull needs multi_modal";
-    if (const char* why = panda_scene_refusal(h)) return why;
-    if (const char* why = panda_weights_refusal(h)) return why;
+    if (const char* why = panda_refusal(h, PANDA_SIDE_ROLLOUT)) return why;
     return point_variant_refusal(h, SIDE_ROLLOUT);
 }
 
@@ -1481,16 +1476,11 @@ extern "C" int m3_rollout(m3_handle* h) {
     if (h->cfg.env_type == M3_ENV_POINT) h->point_form_used = p.form;
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->scene_rt, h->cost_weights, p, h->stream, h->rollout_err_dev, h->scene_rows_dev);
-    else if (h->panda_rollout_scenes_on) {   // (one family, weights always: "used" keeps saying whether the WEIGHTS needed them)
-        launch_rollout_panda_v(a, pa, h->pscene_rt, h->panda_cost_weights, h->panda_rows_dev, p, h->stream);
-        h->panda_scene_used = 1; h->panda_weighted_used = panda_weighted(h) ? 1 : 0;
+    else {
+        const PandaDecision d = panda_decision(panda_input(h), PANDA_SIDE_ROLLOUT);
+        launch_rollout_panda(a, pa, panda_launch_scene(h, d.variant), p, h->stream);
+        panda_record_used(h, d);
     }
-    else if (panda_weighted(h)) {   // (one family on the run-time scene: "used" keeps saying whether the workspace needed it)
-        launch_rollout_panda_w(a, pa, h->pscene_rt, h->panda_cost_weights, p, h->stream);
-        h->panda_scene_used = panda_scene_runtime(h) ? 1 : 0; h->panda_weighted_used = 1;
-    }
-    else if (panda_scene_runtime(h)) { launch_rollout_panda_s(a, pa, h->pscene_rt, p, h->stream); h->panda_scene_used = 1; h->panda_weighted_used = 0; }
-    else { launch_rollout_panda(a, pa, h->pscene, p, h->stream); h->panda_scene_used = 0; h->panda_weighted_used = 0; }
     HIPCHK(h, hipGetLastError());
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     return M3_OK;
@@ -2086,6 +2076,7 @@ struct BatchHandle {   // one handle's command as planned, in call order (copied
     PandaArgs pa;      // (panda_env only)
     UpdateArgs u;
     BatchKey key;
+    PandaDecision panda;   // (panda_env only: the batch side's, panda_variant.hpp)
 };
 constexpr BatchTableSizes BATCH_TABLE_SIZES = {{sizeof(BatchRolloutEntry), sizeof(BatchRolloutEntryW), sizeof(BatchRolloutEntryS)},
                                                sizeof(BatchPandaEntry), sizeof(UpdateArgs), 0};
@@ -2201,15 +2192,8 @@ static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code, bool pa
     }
     if (const char* why = rollout_refusal(h)) return why;
     if (!panda_runtime) {
-        if (const char* why = panda_scene_unbatched(h)) {   // (the table's entry carries a PandaScene)
-            code = M3_ERR_UNSUPPORTED;
-            return why;
-        }
-        if (const char* why = panda_rows_unbatched(h)) {   // (... and no table of rows)
-            code = M3_ERR_UNSUPPORTED;
-            return why;
-        }
-        if (const char* why = panda_weights_unbatched(h)) {   // (... and no weights: its kernels form the literal cost)
+        // (the table's entry carries a PandaScene, no table of rows and no weights: its kernels form the literal cost)
+        if (const char* why = panda_unbatched(h, PANDA_ROWS_THEN_WEIGHTS)) {
             code = M3_ERR_UNSUPPORTED;
             return why;
         }
@@ -2229,12 +2213,6 @@ static int batch_refuse(m3_batch* b, int code, int i, const char* msg) {
     else std::snprintf(head, sizeof(head), "m3_batch_command: ");
     b->err = std::string(head) + msg;
     return code;
-}
-
-// which kernels a panda_env handle's entry is for (BatchKey::variant), by m3_rollout's own dispatch
-static int batch_panda_variant(const m3_handle* h) {
-    if (h->panda_rollout_scenes_on) return 2;
-    return (panda_weighted(h) || panda_scene_runtime(h)) ? 1 : 0;
 }
 
 // panda_runtime: whether the run-time section may be used -- the batch's flag for m3_batch_command; never for the lockstep
@@ -2266,7 +2244,8 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
         int code;
         if (const char* why = batch_refusal(h, hd[i].u, code, panda_runtime)) return batch_refuse(b, code, i, why);
         BatchKey& k = hd[i].key;
-        k.variant = panda ? batch_panda_variant(h) : 0;
+        if (panda) hd[i].panda = panda_decision(panda_input(h), PANDA_SIDE_BATCH);   // (by m3_rollout's own dispatch)
+        k.variant = panda ? panda_batch_key(hd[i].panda.variant) : 0;
         k.upd = update_small_instance(hd[i].u);
         hd[i].u.n_cand = k.upd.n_cand;   // (what launch_update_small hands its instance)
         k.K = h->cfg.K_local; k.T = h->cfg.T;
@@ -2278,7 +2257,7 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
         const int rc = plan_rollout(hs[i], hd[i].a, hd[i].pa, hd[i].key.roll);
         if (rc != M3_OK) { b->err = "m3_batch_command: " + hs[i]->err; return rc; }
         // (the run-time families are GENERAL builds only: the plan's choice of the literal kernel's build does not split a group)
-        if (hd[i].key.variant != 0) hd[i].key.roll.general = 1;
+        if (panda && panda_general_only(hd[i].panda.variant)) hd[i].key.roll.general = 1;
     }
     // ---- groups: handles in key order (ties in call order) ----
     std::sort(b->by_roll.begin(), b->by_roll.begin() + n, [hd](int x, int y) {
@@ -2300,7 +2279,7 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
     if (!panda)
         for (int i = 0; i < n; ++i) ++count[point_variant(hd[i].key.roll)];
     else
-        for (int i = 0; i < n; ++i) n_lit += hd[i].key.variant == 0 ? 1 : 0;
+        for (int i = 0; i < n; ++i) n_lit += hd[i].panda.variant == PANDA_LITERAL ? 1 : 0;
     const BatchTableLayout lay = panda ? batch_table_layout_panda(b->sizes, n_lit, n - n_lit) : batch_table_layout(b->sizes, count);
     // byte offset of the rollout entry of the p-th handle in key order
     auto entry_off = [&](int p) {
@@ -2314,9 +2293,9 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
         const m3_handle* h = hs[i];
         char* e = b->host[slot] + entry_off(p);
         if (panda) {
-            if (hd[i].key.variant == 0) *reinterpret_cast<BatchPandaEntry*>(e) = {hd[i].a, hd[i].pa, h->pscene};
-            else *reinterpret_cast<BatchPandaEntryRT*>(e) = {hd[i].a, hd[i].pa, h->pscene_rt, h->panda_cost_weights,
-                                                             hd[i].key.variant == 2 ? h->panda_rows_dev : nullptr};
+            const PandaLaunchScene sc = panda_launch_scene(h, hd[i].panda.variant);
+            if (sc.variant == PANDA_LITERAL) *reinterpret_cast<BatchPandaEntry*>(e) = {hd[i].a, hd[i].pa, *sc.lit};
+            else *reinterpret_cast<BatchPandaEntryRT*>(e) = {hd[i].a, hd[i].pa, *sc.rt, *sc.wt, sc.variant == PANDA_ROWS ? sc.rows : nullptr};
             continue;
         }
         switch (point_variant(hd[i].key.roll)) {
@@ -2337,9 +2316,7 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
         const BatchKey& k = hd[b->by_roll[p]].key;
         int q = p + 1;
         while (q < n && same_rollout(hd[b->by_roll[q]].key, k)) ++q;
-        if (panda && k.variant != 0)
-            launch_rollout_panda_batch_rt(reinterpret_cast<const BatchPandaEntryRT*>(dslot + entry_off(p)), q - p, k.roll, k.K, k.variant == 2, s);
-        else if (panda) launch_rollout_panda_batch(reinterpret_cast<const BatchPandaEntry*>(dslot + entry_off(p)), q - p, k.roll, k.K, s);
+        if (panda) launch_rollout_panda_batch(dslot + entry_off(p), q - p, hd[b->by_roll[p]].panda.variant, k.roll, k.K, s);
         else launch_rollout_point_batch(dslot + entry_off(p), q - p, k.roll, s);
         ++n_roll;
         p = q;
@@ -2348,13 +2325,7 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
     // what each handle's rollout ran, as m3_rollout records it (a batch without the run-time section runs the literal kernels
     // only and leaves the record as it always did)
     if (panda && panda_runtime)
-        for (int i = 0; i < n; ++i) {
-            m3_handle* h = hs[i];
-            const bool rt = panda_scene_runtime(h), wt = panda_weighted(h);
-            if (hd[i].key.variant == 2) { h->panda_scene_used = 1; h->panda_weighted_used = wt ? 1 : 0; }
-            else if (wt) { h->panda_scene_used = rt ? 1 : 0; h->panda_weighted_used = 1; }
-            else { h->panda_scene_used = rt ? 1 : 0; h->panda_weighted_used = 0; }
-        }
+        for (int i = 0; i < n; ++i) panda_record_used(hs[i], hd[i].panda);
     // ---- one update launch per group; multi-modal groups in chunks whose whole grid is resident ----
     for (int p = 0; p < n;) {
         const BatchKey& k = hd[b->by_upd[p]].key;
@@ -2498,11 +2469,9 @@ extern "C" int m3_sim_bind_views(m3_handle* h, float* dof, float* root, float* r
 extern "C" int m3_sim_pull_state(m3_handle* h) {
     if (!h) return M3_ERR_BAD_ARG;
     if (!h->views_bound || !h->views.dof_state || !h->views.root_state) return fail(h, M3_ERR_STATE, "m3_sim_pull_state: views not bound");
-    if (const char* why = panda_scene_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_sim_pull_state: ") + why).c_str());
+    if (const char* why = panda_refusal(h, PANDA_SIDE_VIEWS)) return fail(h, M3_ERR_STATE, (std::string("m3_sim_pull_state: ") + why).c_str());
     if (h->cfg.env_type == M3_ENV_POINT) launch_sim_pull(h->views, h->sim_world, h->cfg.K_local, h->stream);
-    else if (h->panda_scene_rows_on) launch_psim_pull_v(h->pscene_rt, h->panda_rows_dev, h->views, h->sim_world, h->cfg.K_local, h->stream);
-    else if (panda_scene_runtime(h)) launch_psim_pull_s(h->pscene_rt, h->views, h->sim_world, h->cfg.K_local, h->stream);
-    else launch_psim_pull(h->pscene, h->views, h->sim_world, h->cfg.K_local, h->stream);
+    else launch_psim_pull(panda_launch_scene(h, panda_decision(panda_input(h), PANDA_SIDE_VIEWS).variant), h->views, h->sim_world, h->cfg.K_local, h->stream);
     HIPCHK(h, hipGetLastError());
     return M3_OK;
 }
@@ -2520,11 +2489,9 @@ extern "C" int m3_sim_shift_actor(m3_handle* h, int actor, float dx, float dy, f
 extern "C" int m3_sim_push_state(m3_handle* h) {
     if (!h) return M3_ERR_BAD_ARG;
     if (!h->views_bound) return fail(h, M3_ERR_STATE, "m3_sim_push_state: views not bound");
-    if (const char* why = panda_scene_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_sim_push_state: ") + why).c_str());
+    if (const char* why = panda_refusal(h, PANDA_SIDE_VIEWS)) return fail(h, M3_ERR_STATE, (std::string("m3_sim_push_state: ") + why).c_str());
     if (h->cfg.env_type == M3_ENV_POINT) launch_sim_push(h->views, h->sim_world, h->cfg.K_local, h->stream);
-    else if (h->panda_scene_rows_on) launch_psim_push_v(h->pscene_rt, h->panda_rows_dev, h->views, h->sim_world, h->cfg.K_local, h->stream);
-    else if (panda_scene_runtime(h)) launch_psim_push_s(h->pscene_rt, h->views, h->sim_world, h->cfg.K_local, h->stream);
-    else launch_psim_push(h->pscene, h->views, h->sim_world, h->cfg.K_local, h->stream);
+    else launch_psim_push(panda_launch_scene(h, panda_decision(panda_input(h), PANDA_SIDE_VIEWS).variant), h->views, h->sim_world, h->cfg.K_local, h->stream);
     HIPCHK(h, hipGetLastError());
     return M3_OK;
 }
@@ -2558,12 +2525,10 @@ static int sim_step_impl(m3_handle* h, const float* u) {
             default: launch_sim_step(h->scene, h->views, h->sim_world, u, h->sim_u, Kl, h->stream); break;
         }
     } else {
-        if (const char* why = panda_scene_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_sim_step: ") + why).c_str());
-        h->panda_scene_used = (h->panda_scene_rows_on || panda_scene_runtime(h)) ? 1 : 0;
-        if (h->panda_scene_rows_on)
-            launch_psim_step_v(h->pscene_rt, h->panda_rows_dev, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
-        else if (h->panda_scene_used) launch_psim_step_s(h->pscene_rt, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
-        else launch_psim_step(h->pscene, h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
+        const PandaDecision d = panda_decision(panda_input(h), PANDA_SIDE_STEP);
+        if (const char* why = panda_refusal_text(d.refusal)) return fail(h, M3_ERR_STATE, (std::string("m3_sim_step: ") + why).c_str());
+        panda_record_used(h, d);
+        launch_psim_step(panda_launch_scene(h, d.variant), h->views, h->sim_world, u, h->sim_u, h->cfg.K_local, h->stream);
     }
     HIPCHK(h, hipGetLastError());
     return M3_OK;
@@ -2616,15 +2581,10 @@ extern "C" int m3_cost(m3_handle* h, float* cost) {
         fill_panda_cost_params(h, cp);
         // quirk Q8 exactly where m3_rollout applies it (its shadow lanes): reach on an unsharded handle
         const bool env0_cube = cp.task == 4 && h->cfg.k_offset == 0 && h->cfg.K_local == h->cfg.K_global && h->cfg.K_global >= 2;
-        if (const char* why = panda_scene_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_cost: ") + why).c_str());
-        if (const char* why = panda_weights_refusal(h)) return fail(h, M3_ERR_STATE, (std::string("m3_cost: ") + why).c_str());
-        h->panda_weighted_used = panda_weighted(h) ? 1 : 0;
-        if (h->panda_scene_rows_on)   // (one kernel, weights always: at the defaults the literal cost's bits)
-            launch_psim_cost_v(h->pscene_rt, h->panda_rows_dev, cp, h->panda_cost_weights, h->sim_world, h->cfg.K_local, h->cfg.k_offset, env0_cube, cost, h->stream);
-        else if (h->panda_weighted_used)
-            launch_psim_cost_w(h->pscene_rt, cp, h->panda_cost_weights, h->sim_world, h->cfg.K_local, h->cfg.k_offset, env0_cube, cost, h->stream);
-        else if (panda_scene_runtime(h)) launch_psim_cost_s(h->pscene_rt, cp, h->sim_world, h->cfg.K_local, h->cfg.k_offset, env0_cube, cost, h->stream);
-        else launch_psim_cost(h->pscene, cp, h->sim_world, h->cfg.K_local, h->cfg.k_offset, env0_cube, cost, h->stream);
+        const PandaDecision d = panda_decision(panda_input(h), PANDA_SIDE_COST);
+        if (const char* why = panda_refusal_text(d.refusal)) return fail(h, M3_ERR_STATE, (std::string("m3_cost: ") + why).c_str());
+        panda_record_used(h, d);
+        launch_psim_cost(panda_launch_scene(h, d.variant), cp, h->sim_world, h->cfg.K_local, h->cfg.k_offset, env0_cube, cost, h->stream);
     }
     HIPCHK(h, hipGetLastError());
     return M3_OK;
@@ -2927,9 +2887,9 @@ extern "C" int m3_panda_episodes_create(m3_handle* world, m3_handle* const* plan
         !world->views.root_state || !world->views.rigid_body_state)
         return peps_refuse(M3_ERR_STATE, -1, "the world must be a sim_only panda_env handle with its views bound");
     if (wc.K_local != n || wc.K_global != n) return peps_refuse(M3_ERR_STATE, -1, "the world's K_local must equal n (one row per episode)");
-    if (const char* why = panda_scene_refusal(world)) return peps_refuse(M3_ERR_STATE, -1, std::string("the world: ") + why);
-    if (const char* why = panda_scene_unbatched(world)) return peps_refuse(M3_ERR_UNSUPPORTED, -1, std::string("the world: ") + why);
-    if (const char* why = panda_rows_unbatched(world)) return peps_refuse(M3_ERR_UNSUPPORTED, -1, std::string("the world: ") + why);
+    // (the world is sim_only: its step reads no weight, and none is asked about)
+    if (const char* why = panda_refusal(world, PANDA_SIDE_STEP)) return peps_refuse(M3_ERR_STATE, -1, std::string("the world: ") + why);
+    if (const char* why = panda_unbatched(world, PANDA_ROWS_THEN_WEIGHTS)) return peps_refuse(M3_ERR_UNSUPPORTED, -1, std::string("the world: ") + why);
     for (int i = 0; i < n; ++i) {
         m3_handle* h = planners[i];
         if (!h) return peps_refuse(M3_ERR_BAD_ARG, i, "null handle");
@@ -3033,12 +2993,9 @@ static int peps_ready(m3_panda_episodes* eps, const char* who) {
     // (a workspace or cost weights set after m3_panda_episodes_create, which refuses them: nothing of this tick is launched)
     for (int i = -1; i < eps->n; ++i) {
         const m3_handle* h = i < 0 ? eps->world : eps->planners[i];
-        const char* why = panda_scene_refusal(h);
-        if (!why && i >= 0) why = panda_weights_refusal(h);   // (... or weights: the world's step reads none)
+        const char* why = panda_refusal(h, i < 0 ? PANDA_SIDE_STEP : PANDA_SIDE_ROLLOUT);   // (the world's step reads no weight)
         const int code = why ? M3_ERR_STATE : M3_ERR_UNSUPPORTED;
-        if (!why) why = panda_scene_unbatched(h);
-        if (!why) why = panda_weights_unbatched(h);
-        if (!why) why = panda_rows_unbatched(h);
+        if (!why) why = panda_unbatched(h, PANDA_WEIGHTS_THEN_ROWS);
         if (why) {
             eps->err = std::string(who) + (i < 0 ? ": the world: " : ": planner " + std::to_string(i) + ": ") + why;
             return code;

@@ -11,6 +11,7 @@
 #include "panda_dyn.hpp"
 #include "panda_scene.hpp"
 #include "owned_blocks.hpp"
+#include "panda_variant.hpp"
 
 namespace m3 {
 
@@ -394,48 +395,11 @@ struct PandaArgs {
 };
 // the plan of a panda rollout launch; pa becomes what the kernels receive (rows: the reach-cost kernel's workgroups with it)
 RolloutPlan plan_rollout_panda(const RolloutArgs& a, PandaArgs& pa);
-void launch_rollout_panda(const RolloutArgs& a, const PandaArgs& pa, const PandaScene& sc, const RolloutPlan& p, hipStream_t s);
 struct BatchPandaEntry {     // one panda_env handle's rollout in m3_batch_command's table (a.lanes: the plan's)
     RolloutArgs a;
     PandaArgs pa;
     PandaScene sc;
 };
-// one launch of the plan's instance for n handles of K_local = Kl and the same plan (tab: device, n entries), + one launch
-// of the reach-cost kernel when the plan keeps the record buffer
-void launch_rollout_panda_batch(const BatchPandaEntry* tab, int n, const RolloutPlan& p, int Kl, hipStream_t s);
-void launch_psim_step(const PandaScene& sc, const SimViews& v, float* world, const float* u, float* u_keep, int Kl,
-                      hipStream_t s);
-void launch_psim_pull(const PandaScene& sc, const SimViews& v, float* world, int Kl, hipStream_t s);
-void launch_psim_push(const PandaScene& sc, const SimViews& v, const float* world, int Kl, hipStream_t s);
-void launch_psim_cost(const PandaScene& sc, const PandaCostParams& cp, const float* world, int Kl, int k0, bool env0_cube,
-                      float* cost, hipStream_t s);
-
-// the same for a handle whose workspace is a kernel argument (m3_set_panda_scene; rollout_panda_scene.hip).  The reach-cost
-// kernel takes no scene and serves both.
-void launch_panda_reach_cost(const RolloutArgs& a, const PandaArgs& pa, hipStream_t s);
-void launch_rollout_panda_s(const RolloutArgs& a, const PandaArgs& pa, const PandaSceneRT& sc, const RolloutPlan& p, hipStream_t s);
-void launch_psim_step_s(const PandaSceneRT& sc, const SimViews& v, float* world, const float* u, float* u_keep, int Kl,
-                        hipStream_t s);
-void launch_psim_pull_s(const PandaSceneRT& sc, const SimViews& v, float* world, int Kl, hipStream_t s);
-void launch_psim_push_s(const PandaSceneRT& sc, const SimViews& v, const float* world, int Kl, hipStream_t s);
-void launch_psim_cost_s(const PandaSceneRT& sc, const PandaCostParams& cp, const float* world, int Kl, int k0, bool env0_cube,
-                        float* cost, hipStream_t s);
-
-// the same for a handle whose cost weights are a kernel argument (m3_set_panda_cost_weights; rollout_panda_weights.hip): the
-// rollout on the run-time scene with the weighted cost -- and, when the plan keeps the record buffer, the weighted reach-cost
-// kernel -- and the step-mode cost.  Step, pull and push read no cost.
-void launch_rollout_panda_w(const RolloutArgs& a, const PandaArgs& pa, const PandaSceneRT& sc, const PandaCostWeights& wt,
-                            const RolloutPlan& p, hipStream_t s);
-void launch_psim_cost_w(const PandaSceneRT& sc, const PandaCostParams& cp, const PandaCostWeights& wt, const float* world, int Kl,
-                        int k0, bool env0_cube, float* cost, hipStream_t s);
-void launch_panda_reach_cost_w(const RolloutArgs& a, const PandaArgs& pa, const PandaCostWeights& wt, hipStream_t s);
-
-// the same for a handle with one workspace per row (rollout_panda_rows.hip; panda_scene_rows.hpp: uni, rows): per sample of a
-// planner handle's rollout (m3_set_panda_rollout_scenes) -- always with the weights, behind it the weighted reach-cost kernel
-// when the plan keeps the record buffer -- and per environment of a sim_only handle's step, views and cost
-// (m3_set_panda_scene_rows)
-void launch_rollout_panda_v(const RolloutArgs& a, const PandaArgs& pa, const PandaSceneRT& uni, const PandaCostWeights& wt,
-                            const float* rows, const RolloutPlan& p, hipStream_t s);
 // one panda_env handle's rollout in the second section of m3_batch_command's table (a batch created with
 // M3_BATCH_PANDA_RUNTIME; rollout_panda_batch_rt.hip): a handle that needs the run-time scene, the weighted cost or both, or has
 // a workspace per sample (rows: the handle's device table [PANDA_SCENE_ROW_WORDS][K_local], else null)
@@ -446,15 +410,31 @@ struct BatchPandaEntryRT {
     PandaCostWeights wt;
     const float* rows;
 };
-// as launch_rollout_panda_batch for such entries: kb_rollout_panda_w, or kb_rollout_panda_v when the group's entries carry
-// rows (per_sample), + one launch of kb_panda_reach_cost_w when the plan keeps the record buffer
-void launch_rollout_panda_batch_rt(const BatchPandaEntryRT* tab, int n, const RolloutPlan& p, int Kl, bool per_sample, hipStream_t s);
-void launch_psim_step_v(const PandaSceneRT& uni, const float* rows, const SimViews& v, float* world, const float* u, float* u_keep,
-                        int Kl, hipStream_t s);
-void launch_psim_pull_v(const PandaSceneRT& uni, const float* rows, const SimViews& v, float* world, int Kl, hipStream_t s);
-void launch_psim_push_v(const PandaSceneRT& uni, const float* rows, const SimViews& v, const float* world, int Kl, hipStream_t s);
-void launch_psim_cost_v(const PandaSceneRT& uni, const float* rows, const PandaCostParams& cp, const PandaCostWeights& wt,
-                        const float* world, int Kl, int k0, bool env0_cube, float* cost, hipStream_t s);
+// What a launch is for: the family (panda_variant.hpp) and everything any family reads of the handle -- each takes what it
+// needs: lit the literal kernels; rt every other family (with rows: its uniform members, panda_scene_rows.hpp); wt the weighted
+// and the rows kernels; rows (per sample of a rollout, per environment of a step, the views or a cost) the rows kernels.
+struct PandaLaunchScene {
+    PandaVariant variant;
+    const PandaScene* lit;
+    const PandaSceneRT* rt;
+    const PandaCostWeights* wt;
+    const float* rows;
+};
+// One launcher per operation (rollout_panda.hip; each forwards to the translation unit that holds the family's kernels).
+// The rollout: pa, p as plan_rollout_panda left them -- the form is chosen alike for every family -- + the family's reach-cost
+// kernel when the plan keeps the record buffer.
+void launch_rollout_panda(const RolloutArgs& a, const PandaArgs& pa, const PandaLaunchScene& sc, const RolloutPlan& p, hipStream_t s);
+// one launch of the plan's instance for n handles of K_local = Kl and the same plan and variant (a batch-side one; tab: device,
+// n entries -- BatchPandaEntry for PANDA_LITERAL, else BatchPandaEntryRT), + one launch of the reach-cost kernel when the plan
+// keeps the record buffer
+void launch_rollout_panda_batch(const void* tab, int n, PandaVariant variant, const RolloutPlan& p, int Kl, hipStream_t s);
+// step mode: step + refresh of the views, the views alone (no weighted form: they read no cost), the cost
+void launch_psim_step(const PandaLaunchScene& sc, const SimViews& v, float* world, const float* u, float* u_keep, int Kl,
+                      hipStream_t s);
+void launch_psim_pull(const PandaLaunchScene& sc, const SimViews& v, float* world, int Kl, hipStream_t s);
+void launch_psim_push(const PandaLaunchScene& sc, const SimViews& v, const float* world, int Kl, hipStream_t s);
+void launch_psim_cost(const PandaLaunchScene& sc, const PandaCostParams& cp, const float* world, int Kl, int k0, bool env0_cube,
+                      float* cost, hipStream_t s);
 
 // batched closed-loop episodes of the panda_env (m3_panda_episodes_*): one lane per episode of an N-env world
 struct PandaEpisodeArgs {

@@ -1,6 +1,9 @@
 // panda_reach_cost_body.inc -- the body of k_panda_reach_cost (rollout_panda.hip), included by the kernel and by its
 // batched form kb_panda_reach_cost (as rollout_panda_body.inc).  In scope where it is included: `const RolloutArgs& a` and
-// `const PandaArgs& pa`; with the weighted cost hook (PANDA_BODY_COST, rollout_panda_common.hpp) also `const PandaCostWeights& wt`.
+// `const PandaArgs& pa`, a selection of the cost hook (rollout_panda_common.hpp) and whatever it names: `WT_OFFSET` or `tab`.
+#ifndef PANDA_BODY_COST
+#error "panda_reach_cost_body.inc: define PANDA_BODY_COST as a selection of rollout_panda_common.hpp in front of this #include"
+#endif
     __shared__ float s_c[RC_CH][64];
     const int Kl = a.Kl, T = a.T;
     const int lane = (int)threadIdx.x & 63, slice = (int)threadIdx.x >> 6;
@@ -37,3 +40,4 @@
     }
     if (slice == 0 && mine) a.J[i] = J;
     if (a.wave_min) wave_min_store(a.wave_min, J, first_half, mine && slice == 0);
+#undef PANDA_BODY_COST

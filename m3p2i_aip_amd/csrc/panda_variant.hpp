@@ -1,0 +1,128 @@
+// panda_variant.hpp -- which panda_env kernels a handle runs, what the launch records and why a path refuses the handle: decided
+// here and nowhere else (host only; no HIP dependency, so that tests/native/panda_variant_host.cpp can walk every input on its
+// own).  m3_api.hip fills PandaVariantInput from the handle and maps the refusals to their texts; the launchers of
+// m3_internal.hpp take the variant.  DESIGN.md section 7h.
+#pragma once
+
+namespace m3 {
+
+// the kernel families (the files they live in: rollout_panda.hip, rollout_panda_scene.hip, rollout_panda_weights.hip,
+// rollout_panda_rows.hip; their table forms in rollout_panda.hip and rollout_panda_batch_rt.hip)
+enum PandaVariant {
+    PANDA_LITERAL,    // the reference's workspace and cost weights compiled in
+    PANDA_SCENE,      // the workspace a kernel argument (PandaSceneRT), the literal cost
+    PANDA_WEIGHTED,   // ... and the cost weights a kernel argument (PandaCostWeights)
+    PANDA_ROWS        // ... and the workspace words of a lane from its row of the handle's table; weights always
+};
+// the families whose cost is the weighted overload of panda_cost (the reach-cost kernel behind their rollout is the weighted one)
+constexpr bool panda_cost_weighted(PandaVariant v) { return v == PANDA_WEIGHTED || v == PANDA_ROWS; }
+// every family but the literal one exists as GENERAL builds only: the plan's choice of the literal kernel's build means nothing
+constexpr bool panda_general_only(PandaVariant v) { return v != PANDA_LITERAL; }
+// BatchKey::variant of a batch-side variant: 0 kb_rollout_panda (the literal section of the table), 1 kb_rollout_panda_w,
+// 2 kb_rollout_panda_v (the run-time section)
+constexpr int panda_batch_key(PandaVariant v) { return v == PANDA_ROWS ? 2 : v == PANDA_LITERAL ? 0 : 1; }
+
+struct PandaVariantInput {
+    int scene_instance;       // m3_set_panda_scene_instance: -1 by the values, 0 / 1 forced
+    int weighted_instance;    // m3_set_panda_weighted_cost_instance: -1 by the weights, 0 / 1 forced
+    bool geometry_default;    // the workspace is the reference's but for the two masses (panda_scene_geometry_is_default)
+    bool weights_default;     // the cost weights are the defaults bit for bit
+    bool rollout_scenes_on;   // m3_set_panda_rollout_scenes: a workspace per sample of the fused rollout
+    bool scene_rows_on;       // m3_set_panda_scene_rows: a workspace per environment of a sim_only handle
+    bool sim_only;
+};
+
+enum PandaSide {
+    PANDA_SIDE_ROLLOUT,   // m3_rollout / m3_command
+    PANDA_SIDE_STEP,      // m3_sim_step*
+    PANDA_SIDE_VIEWS,     // m3_sim_pull_state / m3_sim_push_state
+    PANDA_SIDE_COST,      // m3_cost
+    PANDA_SIDE_BATCH      // m3_batch_command with the run-time section: LITERAL, WEIGHTED (a run-time scene alone too) or ROWS
+};
+
+enum PandaRefusal {
+    PANDA_REFUSAL_NONE,
+    // the handle cannot run its own kernels (M3_ERR_STATE)
+    PANDA_SCENE_OFF_ENV_ROWS,       // the run-time-scene instance is forced off but ... a workspace per environment
+    PANDA_SCENE_OFF_SAMPLE_ROWS,    // ... a workspace per sample
+    PANDA_SCENE_OFF_GEOMETRY,       // ... a workspace that is not the default
+    PANDA_WEIGHTS_OFF_TUNED,        // the weighted cost instance is forced off but the weights are not the defaults
+    // a path whose kernels know the literal family only cannot take the handle (M3_ERR_UNSUPPORTED)
+    PANDA_UNBATCHED_SCENE,
+    PANDA_UNBATCHED_SAMPLE_ROWS,
+    PANDA_UNBATCHED_ENV_ROWS,
+    PANDA_UNBATCHED_WEIGHTS
+};
+
+constexpr int PANDA_USED_UNCHANGED = -1;
+struct PandaDecision {
+    PandaVariant variant;
+    int scene_used, weighted_used;   // what panda_scene_used / panda_weighted_used become: 0, 1 or PANDA_USED_UNCHANGED
+    PandaRefusal refusal;            // of the handle's own kernels on this side; the rest is what an accepted call does
+};
+
+// the run-time-scene instances: by the values -- anything but the two masses off the defaults -- or as the switch says
+inline bool panda_scene_runtime(const PandaVariantInput& in) {
+    return in.scene_instance < 0 ? !in.geometry_default : in.scene_instance != 0;
+}
+// the weighted kernels (on the run-time scene, whatever panda_scene_runtime says): by the weights, or as the switch says
+inline bool panda_weighted(const PandaVariantInput& in) {
+    return in.weighted_instance < 0 ? !in.weights_default : in.weighted_instance != 0;
+}
+
+// why the handle cannot run its kernels.  The rows' kernels are run-time-scene kernels, so the scene switch refuses rows on
+// every side; the weights matter where a cost is formed.
+inline PandaRefusal panda_refusal(const PandaVariantInput& in, PandaSide side) {
+    if (in.scene_instance == 0 && in.scene_rows_on) return PANDA_SCENE_OFF_ENV_ROWS;
+    if (in.scene_instance == 0 && in.rollout_scenes_on) return PANDA_SCENE_OFF_SAMPLE_ROWS;
+    if (in.scene_instance == 0 && !in.geometry_default) return PANDA_SCENE_OFF_GEOMETRY;
+    const bool forms_cost = side == PANDA_SIDE_ROLLOUT || side == PANDA_SIDE_COST || side == PANDA_SIDE_BATCH;
+    if (forms_cost && in.weighted_instance == 0 && !in.weights_default) return PANDA_WEIGHTS_OFF_TUNED;
+    return PANDA_REFUSAL_NONE;
+}
+
+inline PandaDecision panda_decision(const PandaVariantInput& in, PandaSide side) {
+    const bool rt = panda_scene_runtime(in), wt = panda_weighted(in);
+    PandaDecision d{PANDA_LITERAL, PANDA_USED_UNCHANGED, PANDA_USED_UNCHANGED, panda_refusal(in, side)};
+    switch (side) {
+        case PANDA_SIDE_ROLLOUT:
+        case PANDA_SIDE_BATCH:
+            // rows: one family, weights always; weighted: one family on the run-time scene.  "used" keeps saying whether the
+            // WEIGHTS / the WORKSPACE needed the instance
+            d.variant = in.rollout_scenes_on ? PANDA_ROWS : wt ? PANDA_WEIGHTED : rt ? PANDA_SCENE : PANDA_LITERAL;
+            d.scene_used = (in.rollout_scenes_on || rt) ? 1 : 0;
+            d.weighted_used = wt ? 1 : 0;
+            // (the table's run-time section has ONE construction for a scene, weights or both: rollout_panda_batch_rt.hip)
+            if (side == PANDA_SIDE_BATCH && d.variant == PANDA_SCENE) d.variant = PANDA_WEIGHTED;
+            break;
+        case PANDA_SIDE_STEP:
+            d.scene_used = (in.scene_rows_on || rt) ? 1 : 0;
+            [[fallthrough]];        // (the kernels: as the views')
+        case PANDA_SIDE_VIEWS:      // (step, pull and push read no cost: no weighted form)
+            d.variant = in.scene_rows_on ? PANDA_ROWS : rt ? PANDA_SCENE : PANDA_LITERAL;
+            break;
+        case PANDA_SIDE_COST:       // (rows: one kernel, weights always -- at the defaults the literal cost's bits)
+            d.variant = in.scene_rows_on ? PANDA_ROWS : wt ? PANDA_WEIGHTED : rt ? PANDA_SCENE : PANDA_LITERAL;
+            d.weighted_used = wt ? 1 : 0;
+            break;
+    }
+    return d;
+}
+
+// Why a path that carries a PandaScene and the literal cost only (a batch table without the run-time section, the lockstep
+// episodes' kernels) cannot take the handle.  A sim_only handle passes the weights: its step reads none.  Which message wins
+// when several conditions hold is part of each caller's contract, so the order is an argument: the scene comes first, then
+// rows before weights (m3_batch_command, m3_panda_episodes_create) or weights before rows (the episodes' ticks).
+enum PandaUnbatchedOrder { PANDA_ROWS_THEN_WEIGHTS, PANDA_WEIGHTS_THEN_ROWS };
+inline PandaRefusal panda_unbatched(const PandaVariantInput& in, PandaUnbatchedOrder order) {
+    if (panda_scene_runtime(in)) return PANDA_UNBATCHED_SCENE;
+    const PandaRefusal rows = in.rollout_scenes_on ? PANDA_UNBATCHED_SAMPLE_ROWS
+                              : in.scene_rows_on   ? PANDA_UNBATCHED_ENV_ROWS
+                                                   : PANDA_REFUSAL_NONE;
+    const PandaRefusal weights = (!in.sim_only && panda_weighted(in)) ? PANDA_UNBATCHED_WEIGHTS : PANDA_REFUSAL_NONE;
+    const PandaRefusal first = order == PANDA_ROWS_THEN_WEIGHTS ? rows : weights;
+    const PandaRefusal second = order == PANDA_ROWS_THEN_WEIGHTS ? weights : rows;
+    return first != PANDA_REFUSAL_NONE ? first : second;
+}
+
+}  // namespace m3

@@ -10,6 +10,7 @@
 #include "noise_stream.hpp"
 #include "panda_dyn.hpp"
 #include "panda_episode_lane.hpp"
+#include "panda_step_mode.hpp"
 #include "rollout_panda_common.hpp"
 #include "wave_min.hpp"
 
@@ -30,6 +31,8 @@ template <bool FORCES, bool GENERAL, int LPS>
 __global__ __launch_bounds__(64) void k_rollout_panda(const RolloutArgs a_, const PandaArgs pa,
                                                       const PandaScene sc_) {
     using SceneT = PandaScene;
+#define PANDA_BODY_COST PANDA_COST_LITERAL
+#define PANDA_BODY_SCENE PANDA_SCENE_UNIFORM
 #include "rollout_panda_body.inc"
 }
 
@@ -46,6 +49,7 @@ __global__ __launch_bounds__(64) void k_rollout_panda(const RolloutArgs a_, cons
 // order with the rollout's own recurrence (J = J + g c; g = g gamma): the same operations on the same values, the same bits
 // (16 -> 7 us at C4: profiles/r06).
 __global__ __launch_bounds__(64 * RC_TS) void k_panda_reach_cost(const RolloutArgs a, const PandaArgs pa) {
+#define PANDA_BODY_COST PANDA_COST_LITERAL
 #include "panda_reach_cost_body.inc"
 }
 
@@ -116,29 +120,29 @@ RolloutPlan plan_rollout_panda(const RolloutArgs& a, PandaArgs& pa) {
     p.rows = !a.wave_min ? 0 : p.rec ? (a.Kl + 63) / 64 : p.blocks;
     return p;
 }
-// (takes no scene: shared with the run-time-scene rollout, rollout_panda_scene.hip)
-void launch_panda_reach_cost(const RolloutArgs& a, const PandaArgs& pa, hipStream_t s) {
-    const dim3 grid((a.Kl + 63) / 64), block(64 * RC_TS);
-    hipLaunchKernelGGL(k_panda_reach_cost, grid, block, 0, s, a, pa);
+static void launch_rollout_panda_literal(const RolloutArgs& a, const PandaArgs& pa, const PandaLaunchScene& sc, const RolloutPlan& p,
+                                            hipStream_t s) {
+    launch_panda_instance(p, dim3(p.blocks), s, [](auto forces, auto general, auto lps) {
+        return &k_rollout_panda<decltype(forces)::value, decltype(general)::value, decltype(lps)::value>;
+    }, a, pa, *sc.lit);
 }
-template <int LPS>
-static void launch_rollout_panda_lps(const RolloutArgs& a_in, const PandaArgs& pa, const PandaScene& sc, const RolloutPlan& p,
-                                     hipStream_t s) {
-    RolloutArgs a = a_in;
-    a.lanes = p.lanes;
-    const dim3 grid(p.blocks), block(64);
-    if (p.general) {
-        if (p.forces) hipLaunchKernelGGL((k_rollout_panda<true, true, LPS>), grid, block, 0, s, a, pa, sc);
-        else hipLaunchKernelGGL((k_rollout_panda<false, true, LPS>), grid, block, 0, s, a, pa, sc);
-    } else if (p.forces) hipLaunchKernelGGL((k_rollout_panda<true, false, LPS>), grid, block, 0, s, a, pa, sc);
-    else hipLaunchKernelGGL((k_rollout_panda<false, false, LPS>), grid, block, 0, s, a, pa, sc);
+static void launch_panda_reach_cost_literal(const RolloutArgs& a, const PandaArgs& pa, const PandaLaunchScene&, hipStream_t s) {
+    launch_panda_reach_cost(k_panda_reach_cost, a.Kl, 1, s, a, pa);
 }
 // pa: as plan_rollout_panda left it
-void launch_rollout_panda(const RolloutArgs& a, const PandaArgs& pa, const PandaScene& sc, const RolloutPlan& p, hipStream_t s) {
-    if (p.lps == 16) launch_rollout_panda_lps<16>(a, pa, sc, p, s);
-    else if (p.lps == 8) launch_rollout_panda_lps<8>(a, pa, sc, p, s);
-    else launch_rollout_panda_lps<1>(a, pa, sc, p, s);
-    if (p.rec) launch_panda_reach_cost(a, pa, s);
+void launch_rollout_panda(const RolloutArgs& a_in, const PandaArgs& pa, const PandaLaunchScene& sc, const RolloutPlan& p, hipStream_t s) {
+    RolloutArgs a = a_in;
+    a.lanes = p.lanes;
+    switch (sc.variant) {
+        case PANDA_LITERAL: launch_rollout_panda_literal(a, pa, sc, p, s); break;
+        case PANDA_SCENE: launch_rollout_panda_scene(a, pa, sc, p, s); break;
+        case PANDA_WEIGHTED: launch_rollout_panda_weighted(a, pa, sc, p, s); break;
+        case PANDA_ROWS: launch_rollout_panda_rows(a, pa, sc, p, s); break;
+    }
+    if (!p.rec) return;
+    // (the reach-cost kernel reads the record buffer, no scene: the literal one or the weighted one serve every family)
+    if (panda_cost_weighted(sc.variant)) launch_panda_reach_cost_weighted(a, pa, sc, s);
+    else launch_panda_reach_cost_literal(a, pa, sc, s);
 }
 
 // ---- batched command (m3_batch_command) ---------------------------------------------------------------------------
@@ -151,32 +155,28 @@ __global__ __launch_bounds__(64) void kb_rollout_panda(const BatchPandaEntry* __
     const PandaArgs& pa = tab[blockIdx.y].pa;
     const PandaScene& sc_ = tab[blockIdx.y].sc;
     using SceneT = PandaScene;
+#define PANDA_BODY_COST PANDA_COST_LITERAL
+#define PANDA_BODY_SCENE PANDA_SCENE_UNIFORM
 #include "rollout_panda_body.inc"
 }
 __global__ __launch_bounds__(64 * RC_TS) void kb_panda_reach_cost(const BatchPandaEntry* __restrict__ tab) {
     const RolloutArgs& a = tab[blockIdx.y].a;
     const PandaArgs& pa = tab[blockIdx.y].pa;
+#define PANDA_BODY_COST PANDA_COST_LITERAL
 #include "panda_reach_cost_body.inc"
 }
-void launch_rollout_panda_batch(const BatchPandaEntry* tab, int n, const RolloutPlan& p, int Kl, hipStream_t s) {
-    const dim3 grid(p.blocks, n), block(64);
-#define M3_LAUNCH_PBATCH(LPS_)                                                                                             \
-    do {                                                                                                                   \
-        if (p.general) {                                                                                                   \
-            if (p.forces) hipLaunchKernelGGL((kb_rollout_panda<true, true, LPS_>), grid, block, 0, s, tab);                \
-            else hipLaunchKernelGGL((kb_rollout_panda<false, true, LPS_>), grid, block, 0, s, tab);                        \
-        } else if (p.forces) hipLaunchKernelGGL((kb_rollout_panda<true, false, LPS_>), grid, block, 0, s, tab);            \
-        else hipLaunchKernelGGL((kb_rollout_panda<false, false, LPS_>), grid, block, 0, s, tab);                           \
-    } while (0)
-    if (p.lps == 16) M3_LAUNCH_PBATCH(16);
-    else if (p.lps == 8) M3_LAUNCH_PBATCH(8);
-    else M3_LAUNCH_PBATCH(1);
-#undef M3_LAUNCH_PBATCH
-    if (p.rec) hipLaunchKernelGGL(kb_panda_reach_cost, dim3((Kl + 63) / 64, n), dim3(64 * RC_TS), 0, s, tab);
+static void launch_rollout_panda_batch_literal(const BatchPandaEntry* tab, int n, const RolloutPlan& p, int Kl, hipStream_t s) {
+    launch_panda_instance(p, dim3(p.blocks, n), s, [](auto forces, auto general, auto lps) {
+        return &kb_rollout_panda<decltype(forces)::value, decltype(general)::value, decltype(lps)::value>;
+    }, tab);
+    if (p.rec) launch_panda_reach_cost(kb_panda_reach_cost, Kl, n, s, tab);
+}
+void launch_rollout_panda_batch(const void* tab, int n, PandaVariant variant, const RolloutPlan& p, int Kl, hipStream_t s) {
+    if (variant == PANDA_LITERAL) launch_rollout_panda_batch_literal(static_cast<const BatchPandaEntry*>(tab), n, p, Kl, s);
+    else launch_rollout_panda_batch_rt(static_cast<const BatchPandaEntryRT*>(tab), n, variant == PANDA_ROWS, p, Kl, s);
 }
 
-// ======================= step mode (rows and views: rollout_panda_common.hpp) ===========================
-
+// ======================= step mode (pull and push bodies: panda_step_mode.hpp; rows and views: rollout_panda_common.hpp) ==========
 // one sim.step() of every environment and the refresh of the wrapper's views in the same launch
 __global__ __launch_bounds__(64) void k_psim_step(const PandaScene sc, const SimViews v, float* wd, const float* u,
                                                   float* u_keep, int Kl) {
@@ -197,33 +197,27 @@ __global__ __launch_bounds__(64) void k_psim_step(const PandaScene sc, const Sim
     psoa_store(wd, Kl, i, w);
     panda_push_views(sc, v, i, w);
 }
-void launch_psim_step(const PandaScene& sc, const SimViews& v, float* world, const float* u, float* u_keep, int Kl,
-                      hipStream_t s) {
-    hipLaunchKernelGGL(k_psim_step, dim3((Kl + 63) / 64), dim3(64), 0, s, sc, v, world, u, u_keep, Kl);
+static void launch_psim_step_literal(const PandaLaunchScene& sc, const SimViews& v, float* world, const float* u, float* u_keep,
+                                        int Kl, hipStream_t s) {
+    launch_psim(k_psim_step, Kl, s, *sc.lit, v, world, u, u_keep, Kl);
 }
 
 __global__ __launch_bounds__(64) void k_psim_pull(const PandaScene sc, const SimViews v, float* wd, int Kl) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= Kl) return;
-    PandaWorld w;
-    panda_world_from_sim(v.dof_state + (size_t)i * 18, v.root_state + (size_t)i * v.n_actors * 13,
-                         v.box_actor, v.dyn_actor, v.obs_actor, w);  // box_actor = cubeA, dyn_actor = cubeB here
-    panda_infer_held(sc, w);
-    psoa_store(wd, Kl, i, w);
+    psim_pull_body(sc, v, wd, Kl, i);
 }
-void launch_psim_pull(const PandaScene& sc, const SimViews& v, float* world, int Kl, hipStream_t s) {
-    hipLaunchKernelGGL(k_psim_pull, dim3((Kl + 63) / 64), dim3(64), 0, s, sc, v, world, Kl);
+static void launch_psim_pull_literal(const PandaLaunchScene& sc, const SimViews& v, float* world, int Kl, hipStream_t s) {
+    launch_psim(k_psim_pull, Kl, s, *sc.lit, v, world, Kl);
 }
 
 __global__ __launch_bounds__(64) void k_psim_push(const PandaScene sc, const SimViews v, const float* wd, int Kl) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= Kl) return;
-    PandaWorld w;
-    psoa_load(wd, Kl, i, w);
-    panda_push_views(sc, v, i, w);
+    psim_push_body(sc, v, wd, Kl, i);
 }
-void launch_psim_push(const PandaScene& sc, const SimViews& v, const float* world, int Kl, hipStream_t s) {
-    hipLaunchKernelGGL(k_psim_push, dim3((Kl + 63) / 64), dim3(64), 0, s, sc, v, world, Kl);
+static void launch_psim_push_literal(const PandaLaunchScene& sc, const SimViews& v, const float* world, int Kl, hipStream_t s) {
+    launch_psim(k_psim_push, Kl, s, *sc.lit, v, world, Kl);
 }
 
 __global__ __launch_bounds__(64) void k_psim_cost(const PandaScene sc, const PandaCostParams cp, const float* wd,
@@ -246,15 +240,50 @@ __global__ __launch_bounds__(64) void k_psim_cost(const PandaScene sc, const Pan
     for (int j = 0; j < 4; ++j) qh0[j] = wd[(21 + j) * Kl + src];
     cost[i] = panda_cost(cp, w, o, k0 + i, cube0, qh0);
 }
-void launch_psim_cost(const PandaScene& sc, const PandaCostParams& cp, const float* world, int Kl, int k0, bool env0_cube,
+static void launch_psim_cost_literal(const PandaLaunchScene& sc, const PandaCostParams& cp, const float* world, int Kl, int k0,
+                                        bool env0_cube, float* cost, hipStream_t s) {
+    launch_psim(k_psim_cost, Kl, s, *sc.lit, cp, world, Kl, k0, env0_cube ? 1 : 0, cost);
+}
+
+// The launchers: PANDA_WEIGHTED has kernels of its own for the cost only -- step, pull and push read no cost, and a handle's
+// weights never make m3_api.hip ask for them there.
+void launch_psim_step(const PandaLaunchScene& sc, const SimViews& v, float* world, const float* u, float* u_keep, int Kl,
+                      hipStream_t s) {
+    switch (sc.variant) {
+        case PANDA_LITERAL: return launch_psim_step_literal(sc, v, world, u, u_keep, Kl, s);
+        case PANDA_ROWS: return launch_psim_step_rows(sc, v, world, u, u_keep, Kl, s);
+        default: return launch_psim_step_scene(sc, v, world, u, u_keep, Kl, s);
+    }
+}
+void launch_psim_pull(const PandaLaunchScene& sc, const SimViews& v, float* world, int Kl, hipStream_t s) {
+    switch (sc.variant) {
+        case PANDA_LITERAL: return launch_psim_pull_literal(sc, v, world, Kl, s);
+        case PANDA_ROWS: return launch_psim_pull_rows(sc, v, world, Kl, s);
+        default: return launch_psim_pull_scene(sc, v, world, Kl, s);
+    }
+}
+void launch_psim_push(const PandaLaunchScene& sc, const SimViews& v, const float* world, int Kl, hipStream_t s) {
+    switch (sc.variant) {
+        case PANDA_LITERAL: return launch_psim_push_literal(sc, v, world, Kl, s);
+        case PANDA_ROWS: return launch_psim_push_rows(sc, v, world, Kl, s);
+        default: return launch_psim_push_scene(sc, v, world, Kl, s);
+    }
+}
+void launch_psim_cost(const PandaLaunchScene& sc, const PandaCostParams& cp, const float* world, int Kl, int k0, bool env0_cube,
                       float* cost, hipStream_t s) {
-    hipLaunchKernelGGL(k_psim_cost, dim3((Kl + 63) / 64), dim3(64), 0, s, sc, cp, world, Kl, k0, env0_cube ? 1 : 0, cost);
+    switch (sc.variant) {
+        case PANDA_LITERAL: return launch_psim_cost_literal(sc, cp, world, Kl, k0, env0_cube, cost, s);
+        case PANDA_SCENE: return launch_psim_cost_scene(sc, cp, world, Kl, k0, env0_cube, cost, s);
+        case PANDA_WEIGHTED: return launch_psim_cost_weighted(sc, cp, world, Kl, k0, env0_cube, cost, s);
+        case PANDA_ROWS: return launch_psim_cost_rows(sc, cp, world, Kl, k0, env0_cube, cost, s);
+    }
 }
 
 // ======================= batched closed-loop episodes (m3_panda_episodes_*) =======================
 // One lane per episode e of an N-env world.  Both kernels live in this translation unit so that panda_world_from_sim,
 // panda_infer_held, panda_step and panda_push_views are the same text under the same flags as in k_psim_pull / k_psim_step,
 // whose sequence on a 1-env world (and on row 0 of a planner's K-env simulator) they reproduce: same arithmetic, same bits.
+// (Written out, not instances of panda_step_mode.hpp's bodies: as instances their machine code moved.)
 
 // before the command: what run_tamp's state upload and update_plan's sim.step() leave in row 0 of the planner's simulator
 __global__ __launch_bounds__(64) void k_panda_episodes_pre(const PandaScene sc, const PandaEpisodeArgs a) {

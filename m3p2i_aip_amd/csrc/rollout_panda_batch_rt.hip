@@ -21,8 +21,6 @@
 // rows 0 and K / 2 -- and the ragged last wavefront applied; rollout_panda_rows.hip), never the lane, the slot or blockIdx.y:
 // blockIdx.y only picks WHICH handle's table [22][K_local] is read.  Lanes that left (slot >= a_.lanes, i >= Kl) never reach
 // the hook, so every read is inside that table.
-#define PANDA_BODY_COST(w, o, k, cube0, qh0) panda_cost(pa.cp, tab[blockIdx.y].wt, w, o, k, cube0, qh0)
-#define PANDA_BODY_SCENE(sc, i)
 #include "m3_internal.hpp"
 #include "noise_stream.hpp"
 #include "panda_dyn.hpp"
@@ -40,6 +38,8 @@ __global__ __launch_bounds__(64) void kb_rollout_panda_w(const BatchPandaEntryRT
     const PandaArgs& pa = tab[blockIdx.y].pa;
     const PandaSceneRT& sc_ = tab[blockIdx.y].sc;
     using SceneT = PandaSceneRT;
+#define PANDA_BODY_COST PANDA_COST_TABLE_WEIGHTS
+#define PANDA_BODY_SCENE PANDA_SCENE_UNIFORM
 #include "rollout_panda_body.inc"
 }
 
@@ -48,12 +48,11 @@ __global__ __launch_bounds__(64) void kb_rollout_panda_w(const BatchPandaEntryRT
 __global__ __launch_bounds__(64 * RC_TS) void kb_panda_reach_cost_w(const BatchPandaEntryRT* __restrict__ tab) {
     const RolloutArgs& a = tab[blockIdx.y].a;
     const PandaArgs& pa = tab[blockIdx.y].pa;
+#define PANDA_BODY_COST PANDA_COST_TABLE_WEIGHTS
 #include "panda_reach_cost_body.inc"
 }
 
 // k_rollout_panda_v's construction from the table: the sample's 22 workspace words from row i of the handle's own rows
-#undef PANDA_BODY_SCENE
-#define PANDA_BODY_SCENE(sc, i) panda_scene_row_load(sc, tab[blockIdx.y].rows, a_.Kl, i);
 template <bool FORCES, int LPS>
 __global__ __launch_bounds__(64) void kb_rollout_panda_v(const BatchPandaEntryRT* __restrict__ tab) {
     constexpr bool GENERAL = true;
@@ -61,28 +60,23 @@ __global__ __launch_bounds__(64) void kb_rollout_panda_v(const BatchPandaEntryRT
     const PandaArgs& pa = tab[blockIdx.y].pa;
     const PandaSceneRT& sc_ = tab[blockIdx.y].sc;
     using SceneT = PandaSceneRT;
+#define PANDA_BODY_COST PANDA_COST_TABLE_WEIGHTS
+#define PANDA_BODY_SCENE PANDA_SCENE_TABLE_ROWS
 #include "rollout_panda_body.inc"
 }
 
 // p: the group's plan (every member's own); per_sample: the group's entries carry rows (variant 2)
-void launch_rollout_panda_batch_rt(const BatchPandaEntryRT* tab, int n, const RolloutPlan& p, int Kl, bool per_sample, hipStream_t s) {
-    const dim3 grid(p.blocks, n), block(64);
-#define M3_LAUNCH_PBATCH_RT(KERNEL, LPS_)                                                                                  \
-    do {                                                                                                                   \
-        if (p.forces) hipLaunchKernelGGL((KERNEL<true, LPS_>), grid, block, 0, s, tab);                                    \
-        else hipLaunchKernelGGL((KERNEL<false, LPS_>), grid, block, 0, s, tab);                                            \
-    } while (0)
-    if (per_sample) {
-        if (p.lps == 16) M3_LAUNCH_PBATCH_RT(kb_rollout_panda_v, 16);
-        else if (p.lps == 8) M3_LAUNCH_PBATCH_RT(kb_rollout_panda_v, 8);
-        else M3_LAUNCH_PBATCH_RT(kb_rollout_panda_v, 1);
-    } else {
-        if (p.lps == 16) M3_LAUNCH_PBATCH_RT(kb_rollout_panda_w, 16);
-        else if (p.lps == 8) M3_LAUNCH_PBATCH_RT(kb_rollout_panda_w, 8);
-        else M3_LAUNCH_PBATCH_RT(kb_rollout_panda_w, 1);
-    }
-#undef M3_LAUNCH_PBATCH_RT
-    if (p.rec) hipLaunchKernelGGL(kb_panda_reach_cost_w, dim3((Kl + 63) / 64, n), dim3(64 * RC_TS), 0, s, tab);
+void launch_rollout_panda_batch_rt(const BatchPandaEntryRT* tab, int n, bool per_sample, const RolloutPlan& p, int Kl, hipStream_t s) {
+    const dim3 grid(p.blocks, n);
+    if (per_sample)
+        launch_panda_instance(p, grid, s, [](auto forces, auto, auto lps) {
+            return &kb_rollout_panda_v<decltype(forces)::value, decltype(lps)::value>;
+        }, tab);
+    else
+        launch_panda_instance(p, grid, s, [](auto forces, auto, auto lps) {
+            return &kb_rollout_panda_w<decltype(forces)::value, decltype(lps)::value>;
+        }, tab);
+    if (p.rec) launch_panda_reach_cost(kb_panda_reach_cost_w, Kl, n, s, tab);
 }
 
 }  // namespace m3

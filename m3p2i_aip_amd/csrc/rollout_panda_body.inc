@@ -1,9 +1,11 @@
 // rollout_panda_body.inc -- the body of k_rollout_panda (rollout_panda.hip), included by the kernel and by its batched form
 // kb_rollout_panda: the same tokens in both, so that k_rollout_panda compiles to exactly the code it did as a plain kernel
 // (as update_small_body.inc).  In scope where it is included: FORCES, GENERAL, LPS, the scene type `SceneT` (PandaScene, or
-// PandaSceneRT in rollout_panda_scene.hip), `const RolloutArgs& a_`, `const PandaArgs& pa` and `const SceneT& sc_`;
-// with the weighted cost hook (PANDA_BODY_COST, rollout_panda_common.hpp) also `const PandaCostWeights& wt`; with the scene hook
-// (PANDA_BODY_SCENE) also `const float* scene_rows`.
+// PandaSceneRT in rollout_panda_scene.hip), `const RolloutArgs& a_`, `const PandaArgs& pa`, `const SceneT& sc_`, a selection of
+// each of the two hooks (rollout_panda_common.hpp) and whatever the selections name: `WT_OFFSET`, `scene_rows` or `tab`.
+#if !defined(PANDA_BODY_COST) || !defined(PANDA_BODY_SCENE)
+#error "rollout_panda_body.inc: define PANDA_BODY_COST and PANDA_BODY_SCENE as selections of rollout_panda_common.hpp in front of this #include"
+#endif
     PANDA_CORNER_LDS(LPS);
     // (a_.lanes samples per 64-wide wavefront: m3_set_rollout_lanes; the idle lanes leave at once)
     // Shadow lanes (quirk Q8, pa.shadows = 1 or 2; reach on an unsharded handle): the reference's reach cost measures every
@@ -242,3 +244,5 @@
             *(volatile int*)pa.busy_hint = (int)((total * 1000ull) / (all ? all : 1ull)) + 1;    // (+ 1: 0 = nothing reported yet)
         }
     }
+#undef PANDA_BODY_COST
+#undef PANDA_BODY_SCENE

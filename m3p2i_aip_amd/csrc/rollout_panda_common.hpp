@@ -1,12 +1,16 @@
-// rollout_panda_common.hpp -- what the panda_env kernels of rollout_panda.hip (the reference's workspace compiled in) and
-// rollout_panda_scene.hip (the workspace of m3_set_panda_scene as a kernel argument) share: the world's loads from the raw
-// row and from the wrapper's tensors, the solver's per-lane LDS store, the step-mode SoA rows and the refresh of the
-// wrapper's views.  The same text in both translation units, so that both compile the same operations.
+// rollout_panda_common.hpp -- what the panda_env kernel families share (rollout_panda.hip: the reference's workspace and cost
+// compiled in; rollout_panda_scene.hip, _weights.hip, _rows.hip, _batch_rt.hip: the workspace, the cost weights, a workspace
+// per row as kernel arguments): the world's loads from the raw row and from the wrapper's tensors, the solver's per-lane LDS
+// store, the hooks of the two shared bodies, the launch switches, the step-mode SoA rows and the refresh of the wrapper's
+// views.  One text for every translation unit, so that all compile the same operations (panda_step_mode.hpp: the step-mode
+// kernels' bodies).
 #pragma once
 #include "m3_internal.hpp"
 #include "panda_dyn.hpp"
+#include "panda_scene_rows.hpp"
 
 #include <cstddef>
+#include <type_traits>
 
 namespace m3 {
 
@@ -61,21 +65,6 @@ __device__ __forceinline__ float in_vgpr(float v) {   // keep a uniform value in
     return v;
 }
 
-// The cost hook: the one place where the rollout body (rollout_panda_body.inc) and the reach-cost body
-// (panda_reach_cost_body.inc) form a step's cost, selected at compile time.  Every translation unit but
-// rollout_panda_weights.hip takes this default -- panda_cost with the reference's literals, the call the bodies always made.
-// rollout_panda_weights.hip defines the hook before this header, with the kernel argument `wt` (m3_set_panda_cost_weights).
-#ifndef PANDA_BODY_COST
-#define PANDA_BODY_COST(w, o, k, cube0, qh0) panda_cost(pa.cp, w, o, k, cube0, qh0)
-#endif
-
-// The scene hook: where the rollout body has copied the kernel-argument scene into `sc` and knows its sample index `i`
-// (a_.lanes, the shadow slots and the ragged last wavefront applied).  Empty everywhere but in rollout_panda_rows.hip, which
-// overwrites the workspace words of `sc` from row i of the per-sample table (panda_scene_rows.hpp) there.
-#ifndef PANDA_BODY_SCENE
-#define PANDA_BODY_SCENE(sc, i)
-#endif
-
 // The kernels' `wt` (the weighted families: rollout_panda_weights.hip, rollout_panda_rows.hip) as it lies in the kernel-argument
 // segment (arguments are laid out like the members of a struct), read through a pointer the compiler cannot see through: named
 // as an ordinary argument, the seven floats were loaded at kernel entry and held (spilled) over the whole step loop -- eight
@@ -95,8 +84,85 @@ __device__ __forceinline__ PandaCostWeights kernarg_weights() {
     return PandaCostWeights{p[0], p[1], p[2], p[3], p[4], p[5], p[6]};
 }
 
+// ---- the two hooks of the rollout body (rollout_panda_body.inc) and the reach-cost body (panda_reach_cost_body.inc) ----
+// Where a step's cost is formed the bodies expand PANDA_BODY_COST(w, o, k, cube0, qh0); where the kernel-argument scene has been
+// copied into `sc` and the sample index `i` is final (a_.lanes, the shadow slots and the ragged last wavefront applied) the
+// rollout body expands PANDA_BODY_SCENE(sc, i).  A shell selects each hook IN FRONT OF EVERY #include of a body, by defining the
+// hook's name as one of the selections below -- the only definitions there are; the body refuses to compile (#error) without a
+// selection and forgets it at its end, so none leaks into the next shell of the file.
+// They are macros and not callables because the rollout kernels' machine code does not survive a callable that holds or forms
+// anything: with lambdas the register allocation of 4 of the 6 k_rollout_panda_s builds moved, with function objects that of 16
+// of the 24 weighted builds (profiles/panda_variant_dispatch/README.md).
+//
+// the cost: panda_cost with the reference's literals ...
+#define PANDA_COST_LITERAL(w, o, k, cube0, qh0) panda_cost(pa.cp, w, o, k, cube0, qh0)
+// ... with the direct kernels' argument `wt`, read from the kernel-argument segment at the cost site (kernarg_weights, above; the
+// shell names the argument's offset WT_OFFSET) ...
+#define PANDA_COST_KERNARG_WEIGHTS(w, o, k, cube0, qh0) panda_cost(pa.cp, kernarg_weights<WT_OFFSET>(), w, o, k, cube0, qh0)
+// ... with the weights of the table entry, read through the read-only `__restrict__` table at the cost site (never a copy taken
+// before the substep loop: rollout_panda_batch_rt.hip)
+#define PANDA_COST_TABLE_WEIGHTS(w, o, k, cube0, qh0) panda_cost(pa.cp, tab[blockIdx.y].wt, w, o, k, cube0, qh0)
+// the scene: as the kernel received it ...
+#define PANDA_SCENE_UNIFORM(sc, i)
+// ... or its workspace words from row i of a per-sample table [PANDA_SCENE_ROW_WORDS][Kl] (panda_scene_rows.hpp): the direct
+// kernels' argument `scene_rows`, the table entry's `rows`
+#define PANDA_SCENE_KERNARG_ROWS(sc, i) panda_scene_row_load(sc, scene_rows, a_.Kl, i);
+#define PANDA_SCENE_TABLE_ROWS(sc, i) panda_scene_row_load(sc, tab[blockIdx.y].rows, a_.Kl, i);
+
 // k_panda_reach_cost (rollout_panda.hip) and its weighted twin (rollout_panda_weights.hip)
 constexpr int RC_TS = 4, RC_CH = 32;      // time slices per workgroup; steps per LDS chunk
+
+// ---- host: the launch switches, written once ----
+// The GENERAL x FORCES x LPS instance of a rollout kernel family for a plan: pick(forces, general, lps) -- a generic lambda over
+// three std::integral_constant -- names the family's kernel (only the literal family has GENERAL = false builds; the others
+// ignore `general`), args are the kernel's.  (The kernels are instantiated in the order this switch names them -- lanes per
+// sample, then GENERAL, then FORCES -- and that order is the layout of the code object.)
+template <class Pick, class... Args>
+void launch_panda_instance(const RolloutPlan& p, dim3 grid, hipStream_t s, Pick pick, const Args&... args) {
+    using std::false_type;
+    using std::true_type;
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(64), 0, s, args...); };
+    auto with_lps = [&](auto lps) {
+        if (p.general) {
+            if (p.forces) launch(pick(true_type{}, true_type{}, lps));
+            else launch(pick(false_type{}, true_type{}, lps));
+        } else if (p.forces) launch(pick(true_type{}, false_type{}, lps));
+        else launch(pick(false_type{}, false_type{}, lps));
+    };
+    if (p.lps == 16) with_lps(std::integral_constant<int, 16>{});
+    else if (p.lps == 8) with_lps(std::integral_constant<int, 8>{});
+    else with_lps(std::integral_constant<int, 1>{});
+}
+// the reach-cost kernel behind a rollout that kept the record buffer: n handles of K_local = Kl (a direct launch: one)
+template <class Kernel, class... Args>
+void launch_panda_reach_cost(Kernel kernel, int Kl, int n, hipStream_t s, const Args&... args) {
+    hipLaunchKernelGGL(kernel, dim3((Kl + 63) / 64, n), dim3(64 * RC_TS), 0, s, args...);
+}
+// a step-mode kernel: one lane per environment
+template <class Kernel, class... Args>
+void launch_psim(Kernel kernel, int Kl, hipStream_t s, const Args&... args) {
+    hipLaunchKernelGGL(kernel, dim3((Kl + 63) / 64), dim3(64), 0, s, args...);
+}
+
+// The launchers of m3_internal.hpp (rollout_panda.hip) forward by variant to the translation unit that holds the family's
+// kernels -- there is no relocatable device code: a kernel is launched where it is defined.  One signature per operation, every
+// family's part of it takes what it needs from the PandaLaunchScene (the literal parts are local to rollout_panda.hip).
+// (the rollout kernel alone, a.lanes the plan's)
+using PandaRolloutLaunch = void(const RolloutArgs& a, const PandaArgs& pa, const PandaLaunchScene& sc, const RolloutPlan& p, hipStream_t s);
+PandaRolloutLaunch launch_rollout_panda_scene, launch_rollout_panda_weighted, launch_rollout_panda_rows;
+// (the reach-cost kernel reads no scene: the literal one and this one serve every family)
+void launch_panda_reach_cost_weighted(const RolloutArgs& a, const PandaArgs& pa, const PandaLaunchScene& sc, hipStream_t s);
+// (the table's run-time section: kb_rollout_panda_w, with per_sample kb_rollout_panda_v, + the weighted reach-cost kernel)
+void launch_rollout_panda_batch_rt(const BatchPandaEntryRT* tab, int n, bool per_sample, const RolloutPlan& p, int Kl, hipStream_t s);
+using PsimStepLaunch = void(const PandaLaunchScene& sc, const SimViews& v, float* world, const float* u, float* u_keep, int Kl, hipStream_t s);
+using PsimPullLaunch = void(const PandaLaunchScene& sc, const SimViews& v, float* world, int Kl, hipStream_t s);
+using PsimPushLaunch = void(const PandaLaunchScene& sc, const SimViews& v, const float* world, int Kl, hipStream_t s);
+using PsimCostLaunch = void(const PandaLaunchScene& sc, const PandaCostParams& cp, const float* world, int Kl, int k0, bool env0_cube,
+                            float* cost, hipStream_t s);
+PsimStepLaunch launch_psim_step_scene, launch_psim_step_rows;
+PsimPullLaunch launch_psim_pull_scene, launch_psim_pull_rows;
+PsimPushLaunch launch_psim_push_scene, launch_psim_push_rows;
+PsimCostLaunch launch_psim_cost_scene, launch_psim_cost_weighted, launch_psim_cost_rows;
 
 // ======================= step mode ======================================================
 // SoA world rows (NWP = 77): q 0-8 | qd 9-17 | cubeA 18-30 (pos3 quat4 vel3 angvel3) | cubeB 31-43 | plate pos 44-46,

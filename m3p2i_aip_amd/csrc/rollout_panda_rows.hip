@@ -13,12 +13,11 @@
 // and the ragged last wavefront applied; lanes that left (slot >= a_.lanes, i >= Kl) never reach it, so every read is inside
 // [22][Kl].  The lanes of one sample read one row: the DPP / bpermute sharing inside a sample keeps its precondition, and the
 // wave-level decisions of panda_dyn.hpp are ballots of per-lane predicates, each formed from the lane's own scene.
-#define PANDA_BODY_COST(w, o, k, cube0, qh0) panda_cost(pa.cp, kernarg_weights<WT_OFFSET>(), w, o, k, cube0, qh0)
-#define PANDA_BODY_SCENE(sc, i) panda_scene_row_load(sc, scene_rows, a_.Kl, i);
 #include "m3_internal.hpp"
 #include "noise_stream.hpp"
 #include "panda_dyn.hpp"
 #include "panda_scene_rows.hpp"
+#include "panda_step_mode.hpp"
 #include "rollout_panda_common.hpp"
 #include "wave_min.hpp"
 
@@ -31,26 +30,17 @@ __global__ __launch_bounds__(64) void k_rollout_panda_v(const RolloutArgs a_, co
     constexpr bool GENERAL = true;
     constexpr size_t WT_OFFSET = kernarg_offset<RolloutArgs, PandaArgs, PandaSceneRT, PandaCostWeights>(0);
     using SceneT = PandaSceneRT;
+#define PANDA_BODY_COST PANDA_COST_KERNARG_WEIGHTS
+#define PANDA_BODY_SCENE PANDA_SCENE_KERNARG_ROWS
 #include "rollout_panda_body.inc"
 }
 
-template <int LPS>
-static void launch_rollout_panda_v_lps(const RolloutArgs& a_in, const PandaArgs& pa, const PandaSceneRT& sc,
-                                       const PandaCostWeights& wt, const float* rows, const RolloutPlan& p, hipStream_t s) {
-    RolloutArgs a = a_in;
-    a.lanes = p.lanes;
-    const dim3 grid(p.blocks), block(64);
-    if (p.forces) hipLaunchKernelGGL((k_rollout_panda_v<true, LPS>), grid, block, 0, s, a, pa, sc, wt, rows);
-    else hipLaunchKernelGGL((k_rollout_panda_v<false, LPS>), grid, block, 0, s, a, pa, sc, wt, rows);
-}
-// pa, p: as plan_rollout_panda left them (lanes per sample, shadow slots or record exactly as for a single scene).  The record
-// path needs no scene: the weighted reach-cost kernel of rollout_panda_weights.hip behind the rollout.
-void launch_rollout_panda_v(const RolloutArgs& a, const PandaArgs& pa, const PandaSceneRT& uni, const PandaCostWeights& wt,
-                            const float* rows, const RolloutPlan& p, hipStream_t s) {
-    if (p.lps == 16) launch_rollout_panda_v_lps<16>(a, pa, uni, wt, rows, p, s);
-    else if (p.lps == 8) launch_rollout_panda_v_lps<8>(a, pa, uni, wt, rows, p, s);
-    else launch_rollout_panda_v_lps<1>(a, pa, uni, wt, rows, p, s);
-    if (p.rec) launch_panda_reach_cost_w(a, pa, wt, s);
+// (lanes per sample, shadow slots or record exactly as for a single scene.  The record path needs no scene: the weighted
+// reach-cost kernel of rollout_panda_weights.hip behind the rollout)
+void launch_rollout_panda_rows(const RolloutArgs& a, const PandaArgs& pa, const PandaLaunchScene& sc, const RolloutPlan& p, hipStream_t s) {
+    launch_panda_instance(p, dim3(p.blocks), s, [](auto forces, auto, auto lps) {
+        return &k_rollout_panda_v<decltype(forces)::value, decltype(lps)::value>;
+    }, a, pa, *sc.rt, *sc.wt, sc.rows);
 }
 
 // ---- step mode: the bodies of k_psim_step_s / _pull_s / _push_s and of k_psim_cost_w with lane e's scene from row e ----
@@ -74,9 +64,9 @@ __global__ __launch_bounds__(64) void k_psim_step_v(const PandaSceneRT uni, cons
     psoa_store(wd, Kl, i, w);
     panda_push_views(sc, v, i, w);
 }
-void launch_psim_step_v(const PandaSceneRT& uni, const float* rows, const SimViews& v, float* world, const float* u, float* u_keep,
-                        int Kl, hipStream_t s) {
-    hipLaunchKernelGGL(k_psim_step_v, dim3((Kl + 63) / 64), dim3(64), 0, s, uni, rows, v, world, u, u_keep, Kl);
+void launch_psim_step_rows(const PandaLaunchScene& sc, const SimViews& v, float* world, const float* u, float* u_keep, int Kl,
+                           hipStream_t s) {
+    launch_psim(k_psim_step_v, Kl, s, *sc.rt, sc.rows, v, world, u, u_keep, Kl);
 }
 
 __global__ __launch_bounds__(64) void k_psim_pull_v(const PandaSceneRT uni, const float* scene_rows, const SimViews v, float* wd,
@@ -84,14 +74,10 @@ __global__ __launch_bounds__(64) void k_psim_pull_v(const PandaSceneRT uni, cons
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= Kl) return;
     const PandaSceneRT sc = panda_scene_row_scene(uni, scene_rows, Kl, i);
-    PandaWorld w;
-    panda_world_from_sim(v.dof_state + (size_t)i * 18, v.root_state + (size_t)i * v.n_actors * 13,
-                         v.box_actor, v.dyn_actor, v.obs_actor, w);  // box_actor = cubeA, dyn_actor = cubeB here
-    panda_infer_held(sc, w);
-    psoa_store(wd, Kl, i, w);
+    psim_pull_body(sc, v, wd, Kl, i);
 }
-void launch_psim_pull_v(const PandaSceneRT& uni, const float* rows, const SimViews& v, float* world, int Kl, hipStream_t s) {
-    hipLaunchKernelGGL(k_psim_pull_v, dim3((Kl + 63) / 64), dim3(64), 0, s, uni, rows, v, world, Kl);
+void launch_psim_pull_rows(const PandaLaunchScene& sc, const SimViews& v, float* world, int Kl, hipStream_t s) {
+    launch_psim(k_psim_pull_v, Kl, s, *sc.rt, sc.rows, v, world, Kl);
 }
 
 __global__ __launch_bounds__(64) void k_psim_push_v(const PandaSceneRT uni, const float* scene_rows, const SimViews v,
@@ -99,12 +85,10 @@ __global__ __launch_bounds__(64) void k_psim_push_v(const PandaSceneRT uni, cons
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= Kl) return;
     const PandaSceneRT sc = panda_scene_row_scene(uni, scene_rows, Kl, i);
-    PandaWorld w;
-    psoa_load(wd, Kl, i, w);
-    panda_push_views(sc, v, i, w);
+    psim_push_body(sc, v, wd, Kl, i);
 }
-void launch_psim_push_v(const PandaSceneRT& uni, const float* rows, const SimViews& v, const float* world, int Kl, hipStream_t s) {
-    hipLaunchKernelGGL(k_psim_push_v, dim3((Kl + 63) / 64), dim3(64), 0, s, uni, rows, v, world, Kl);
+void launch_psim_push_rows(const PandaLaunchScene& sc, const SimViews& v, const float* world, int Kl, hipStream_t s) {
+    launch_psim(k_psim_push_v, Kl, s, *sc.rt, sc.rows, v, world, Kl);
 }
 
 __global__ __launch_bounds__(64) void k_psim_cost_v(const PandaSceneRT uni, const float* scene_rows, const PandaCostParams cp,
@@ -130,9 +114,9 @@ __global__ __launch_bounds__(64) void k_psim_cost_v(const PandaSceneRT uni, cons
     for (int j = 0; j < 4; ++j) qh0[j] = wd[(21 + j) * Kl + src];
     cost[i] = panda_cost(cp, wt, w, o, k0 + i, cube0, qh0);
 }
-void launch_psim_cost_v(const PandaSceneRT& uni, const float* rows, const PandaCostParams& cp, const PandaCostWeights& wt,
-                        const float* world, int Kl, int k0, bool env0_cube, float* cost, hipStream_t s) {
-    hipLaunchKernelGGL(k_psim_cost_v, dim3((Kl + 63) / 64), dim3(64), 0, s, uni, rows, cp, wt, world, Kl, k0, env0_cube ? 1 : 0, cost);
+void launch_psim_cost_rows(const PandaLaunchScene& sc, const PandaCostParams& cp, const float* world, int Kl, int k0, bool env0_cube,
+                           float* cost, hipStream_t s) {
+    launch_psim(k_psim_cost_v, Kl, s, *sc.rt, sc.rows, cp, *sc.wt, world, Kl, k0, env0_cube ? 1 : 0, cost);
 }
 
 }  // namespace m3

@@ -1,11 +1,13 @@
 // rollout_panda_scene.hip -- the panda_env kernels of a handle whose workspace is not the reference's (m3_set_panda_scene,
 // include/m3p2i_hip.h): robot mount, table, shelf stand, the plate's size and the contact friction are
 // members of the kernel argument (PandaSceneRT) instead of PandaScene's compile-time constants.  The same bodies as
-// rollout_panda.hip over the same device header under the same flags; at the default values the same bits.
+// rollout_panda.hip (rollout_panda_body.inc, panda_step_mode.hpp) over the same device header under the same flags; at the
+// default values the same bits.
 // New kernels only: a handle with the reference's workspace never launches one of these.
 #include "m3_internal.hpp"
 #include "noise_stream.hpp"
 #include "panda_dyn.hpp"
+#include "panda_step_mode.hpp"
 #include "rollout_panda_common.hpp"
 #include "wave_min.hpp"
 
@@ -17,24 +19,15 @@ template <bool FORCES, int LPS>
 __global__ __launch_bounds__(64) void k_rollout_panda_s(const RolloutArgs a_, const PandaArgs pa, const PandaSceneRT sc_) {
     constexpr bool GENERAL = true;
     using SceneT = PandaSceneRT;
+#define PANDA_BODY_COST PANDA_COST_LITERAL
+#define PANDA_BODY_SCENE PANDA_SCENE_UNIFORM
 #include "rollout_panda_body.inc"
 }
-
-template <int LPS>
-static void launch_rollout_panda_s_lps(const RolloutArgs& a_in, const PandaArgs& pa, const PandaSceneRT& sc, const RolloutPlan& p,
-                                       hipStream_t s) {
-    RolloutArgs a = a_in;
-    a.lanes = p.lanes;
-    const dim3 grid(p.blocks), block(64);
-    if (p.forces) hipLaunchKernelGGL((k_rollout_panda_s<true, LPS>), grid, block, 0, s, a, pa, sc);
-    else hipLaunchKernelGGL((k_rollout_panda_s<false, LPS>), grid, block, 0, s, a, pa, sc);
-}
-// pa, p: as plan_rollout_panda left them (the form is chosen exactly as for the compiled-in workspace)
-void launch_rollout_panda_s(const RolloutArgs& a, const PandaArgs& pa, const PandaSceneRT& sc, const RolloutPlan& p, hipStream_t s) {
-    if (p.lps == 16) launch_rollout_panda_s_lps<16>(a, pa, sc, p, s);
-    else if (p.lps == 8) launch_rollout_panda_s_lps<8>(a, pa, sc, p, s);
-    else launch_rollout_panda_s_lps<1>(a, pa, sc, p, s);
-    if (p.rec) launch_panda_reach_cost(a, pa, s);     // (reads the record buffer, no scene: rollout_panda.hip)
+// (the form is chosen exactly as for the compiled-in workspace; the literal reach-cost kernel behind it: rollout_panda.hip)
+void launch_rollout_panda_scene(const RolloutArgs& a, const PandaArgs& pa, const PandaLaunchScene& sc, const RolloutPlan& p, hipStream_t s) {
+    launch_panda_instance(p, dim3(p.blocks), s, [](auto forces, auto, auto lps) {
+        return &k_rollout_panda_s<decltype(forces)::value, decltype(lps)::value>;
+    }, a, pa, *sc.rt);
 }
 
 // ---- step mode: k_psim_step / _pull / _push / _cost (rollout_panda.hip) with the run-time scene ----
@@ -57,33 +50,27 @@ __global__ __launch_bounds__(64) void k_psim_step_s(const PandaSceneRT sc, const
     psoa_store(wd, Kl, i, w);
     panda_push_views(sc, v, i, w);
 }
-void launch_psim_step_s(const PandaSceneRT& sc, const SimViews& v, float* world, const float* u, float* u_keep, int Kl,
-                        hipStream_t s) {
-    hipLaunchKernelGGL(k_psim_step_s, dim3((Kl + 63) / 64), dim3(64), 0, s, sc, v, world, u, u_keep, Kl);
+void launch_psim_step_scene(const PandaLaunchScene& sc, const SimViews& v, float* world, const float* u, float* u_keep, int Kl,
+                            hipStream_t s) {
+    launch_psim(k_psim_step_s, Kl, s, *sc.rt, v, world, u, u_keep, Kl);
 }
 
 __global__ __launch_bounds__(64) void k_psim_pull_s(const PandaSceneRT sc, const SimViews v, float* wd, int Kl) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= Kl) return;
-    PandaWorld w;
-    panda_world_from_sim(v.dof_state + (size_t)i * 18, v.root_state + (size_t)i * v.n_actors * 13,
-                         v.box_actor, v.dyn_actor, v.obs_actor, w);  // box_actor = cubeA, dyn_actor = cubeB here
-    panda_infer_held(sc, w);
-    psoa_store(wd, Kl, i, w);
+    psim_pull_body(sc, v, wd, Kl, i);
 }
-void launch_psim_pull_s(const PandaSceneRT& sc, const SimViews& v, float* world, int Kl, hipStream_t s) {
-    hipLaunchKernelGGL(k_psim_pull_s, dim3((Kl + 63) / 64), dim3(64), 0, s, sc, v, world, Kl);
+void launch_psim_pull_scene(const PandaLaunchScene& sc, const SimViews& v, float* world, int Kl, hipStream_t s) {
+    launch_psim(k_psim_pull_s, Kl, s, *sc.rt, v, world, Kl);
 }
 
 __global__ __launch_bounds__(64) void k_psim_push_s(const PandaSceneRT sc, const SimViews v, const float* wd, int Kl) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= Kl) return;
-    PandaWorld w;
-    psoa_load(wd, Kl, i, w);
-    panda_push_views(sc, v, i, w);
+    psim_push_body(sc, v, wd, Kl, i);
 }
-void launch_psim_push_s(const PandaSceneRT& sc, const SimViews& v, const float* world, int Kl, hipStream_t s) {
-    hipLaunchKernelGGL(k_psim_push_s, dim3((Kl + 63) / 64), dim3(64), 0, s, sc, v, world, Kl);
+void launch_psim_push_scene(const PandaLaunchScene& sc, const SimViews& v, const float* world, int Kl, hipStream_t s) {
+    launch_psim(k_psim_push_s, Kl, s, *sc.rt, v, world, Kl);
 }
 
 __global__ __launch_bounds__(64) void k_psim_cost_s(const PandaSceneRT sc, const PandaCostParams cp, const float* wd,
@@ -106,9 +93,9 @@ __global__ __launch_bounds__(64) void k_psim_cost_s(const PandaSceneRT sc, const
     for (int j = 0; j < 4; ++j) qh0[j] = wd[(21 + j) * Kl + src];
     cost[i] = panda_cost(cp, w, o, k0 + i, cube0, qh0);
 }
-void launch_psim_cost_s(const PandaSceneRT& sc, const PandaCostParams& cp, const float* world, int Kl, int k0, bool env0_cube,
-                        float* cost, hipStream_t s) {
-    hipLaunchKernelGGL(k_psim_cost_s, dim3((Kl + 63) / 64), dim3(64), 0, s, sc, cp, world, Kl, k0, env0_cube ? 1 : 0, cost);
+void launch_psim_cost_scene(const PandaLaunchScene& sc, const PandaCostParams& cp, const float* world, int Kl, int k0, bool env0_cube,
+                            float* cost, hipStream_t s) {
+    launch_psim(k_psim_cost_s, Kl, s, *sc.rt, cp, world, Kl, k0, env0_cube ? 1 : 0, cost);
 }
 
 }  // namespace m3

@@ -7,12 +7,12 @@
 // forces it).
 //
 // The weights are wave-uniform and are read in one place per step, where the cost is formed after the substeps: the cost hook
-// reads them from the kernel-argument segment there (kernarg_weights, rollout_panda_common.hpp) instead of holding seven more
-// scalars over the substep loop, whose builds already spill two to three hundred.
-#define PANDA_BODY_COST(w, o, k, cube0, qh0) panda_cost(pa.cp, kernarg_weights<WT_OFFSET>(), w, o, k, cube0, qh0)
+// (kernarg_weighted_cost, rollout_panda_common.hpp) reads them from the kernel-argument segment there (kernarg_weights) instead
+// of holding seven more scalars over the substep loop, whose builds already spill two to three hundred.
 #include "m3_internal.hpp"
 #include "noise_stream.hpp"
 #include "panda_dyn.hpp"
+#include "panda_step_mode.hpp"
 #include "rollout_panda_common.hpp"
 #include "wave_min.hpp"
 
@@ -25,34 +25,26 @@ __global__ __launch_bounds__(64) void k_rollout_panda_w(const RolloutArgs a_, co
     constexpr bool GENERAL = true;
     constexpr size_t WT_OFFSET = kernarg_offset<RolloutArgs, PandaArgs, PandaSceneRT, PandaCostWeights>(0);
     using SceneT = PandaSceneRT;
+#define PANDA_BODY_COST PANDA_COST_KERNARG_WEIGHTS
+#define PANDA_BODY_SCENE PANDA_SCENE_UNIFORM
 #include "rollout_panda_body.inc"
 }
 
 // k_panda_reach_cost's body with the weighted cost (reads the record buffer, no scene)
 __global__ __launch_bounds__(64 * RC_TS) void k_panda_reach_cost_w(const RolloutArgs a, const PandaArgs pa, const PandaCostWeights wt) {
     constexpr size_t WT_OFFSET = kernarg_offset<RolloutArgs, PandaArgs, PandaCostWeights>(0);
+#define PANDA_BODY_COST PANDA_COST_KERNARG_WEIGHTS
 #include "panda_reach_cost_body.inc"
 }
 
-template <int LPS>
-static void launch_rollout_panda_w_lps(const RolloutArgs& a_in, const PandaArgs& pa, const PandaSceneRT& sc,
-                                       const PandaCostWeights& wt, const RolloutPlan& p, hipStream_t s) {
-    RolloutArgs a = a_in;
-    a.lanes = p.lanes;
-    const dim3 grid(p.blocks), block(64);
-    if (p.forces) hipLaunchKernelGGL((k_rollout_panda_w<true, LPS>), grid, block, 0, s, a, pa, sc, wt);
-    else hipLaunchKernelGGL((k_rollout_panda_w<false, LPS>), grid, block, 0, s, a, pa, sc, wt);
+// (the form is chosen exactly as for the literal weights)
+void launch_rollout_panda_weighted(const RolloutArgs& a, const PandaArgs& pa, const PandaLaunchScene& sc, const RolloutPlan& p, hipStream_t s) {
+    launch_panda_instance(p, dim3(p.blocks), s, [](auto forces, auto, auto lps) {
+        return &k_rollout_panda_w<decltype(forces)::value, decltype(lps)::value>;
+    }, a, pa, *sc.rt, *sc.wt);
 }
-void launch_panda_reach_cost_w(const RolloutArgs& a, const PandaArgs& pa, const PandaCostWeights& wt, hipStream_t s) {
-    hipLaunchKernelGGL(k_panda_reach_cost_w, dim3((a.Kl + 63) / 64), dim3(64 * RC_TS), 0, s, a, pa, wt);
-}
-// pa, p: as plan_rollout_panda left them (the form is chosen exactly as for the literal weights)
-void launch_rollout_panda_w(const RolloutArgs& a, const PandaArgs& pa, const PandaSceneRT& sc, const PandaCostWeights& wt,
-                            const RolloutPlan& p, hipStream_t s) {
-    if (p.lps == 16) launch_rollout_panda_w_lps<16>(a, pa, sc, wt, p, s);
-    else if (p.lps == 8) launch_rollout_panda_w_lps<8>(a, pa, sc, wt, p, s);
-    else launch_rollout_panda_w_lps<1>(a, pa, sc, wt, p, s);
-    if (p.rec) launch_panda_reach_cost_w(a, pa, wt, s);
+void launch_panda_reach_cost_weighted(const RolloutArgs& a, const PandaArgs& pa, const PandaLaunchScene& sc, hipStream_t s) {
+    launch_panda_reach_cost(k_panda_reach_cost_w, a.Kl, 1, s, a, pa, *sc.wt);
 }
 
 // ---- step mode: k_psim_cost_s (rollout_panda_scene.hip) with the weighted cost, for m3_cost ----
@@ -76,9 +68,9 @@ __global__ __launch_bounds__(64) void k_psim_cost_w(const PandaSceneRT sc, const
     for (int j = 0; j < 4; ++j) qh0[j] = wd[(21 + j) * Kl + src];
     cost[i] = panda_cost(cp, wt, w, o, k0 + i, cube0, qh0);
 }
-void launch_psim_cost_w(const PandaSceneRT& sc, const PandaCostParams& cp, const PandaCostWeights& wt, const float* world, int Kl,
-                        int k0, bool env0_cube, float* cost, hipStream_t s) {
-    hipLaunchKernelGGL(k_psim_cost_w, dim3((Kl + 63) / 64), dim3(64), 0, s, sc, cp, wt, world, Kl, k0, env0_cube ? 1 : 0, cost);
+void launch_psim_cost_weighted(const PandaLaunchScene& sc, const PandaCostParams& cp, const float* world, int Kl, int k0,
+                               bool env0_cube, float* cost, hipStream_t s) {
+    launch_psim(k_psim_cost_w, Kl, s, *sc.rt, cp, *sc.wt, world, Kl, k0, env0_cube ? 1 : 0, cost);
 }
 
 }  // namespace m3
