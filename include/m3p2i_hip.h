@@ -304,7 +304,8 @@ void m3_default_panda_scene(m3_panda_scene* sc);
  * run-time-scene instance (bit-identical to its own m3_command, like every batched handle).  A batch made by m3_batch_create
  * -- whose table slots have no room for the larger entry -- returns M3_ERR_UNSUPPORTED for it, and so do
  * m3_panda_episodes_create / _act / _act_first with such a world or planner, whatever batch they are handed (the message
- * names m3_set_panda_scene and the index of the handle); nothing is launched. */
+ * names m3_set_panda_scene and the index of the handle); nothing is launched.  A set created by m3_panda_episodes_create_ex
+ * with M3_PANDA_EPISODES_RUNTIME takes them (include/m3p2i_hip_ext.h). */
 int m3_set_panda_scene(m3_handle* h, const m3_panda_scene* sc);
 int m3_get_panda_scene(const m3_handle* h, m3_panda_scene* out);
 /* Test and A/B switch: -1 the automatic choice above (default), 1 the run-time-scene instances whatever the values, 0 never --
@@ -326,8 +327,9 @@ int m3_panda_scene_instance_used(m3_handle* h);
  * The rows need the run-time scene: with m3_set_panda_scene_instance(h, 0) the next step / cost / view call is M3_ERR_STATE
  * ("... forced off ... m3_set_panda_scene_rows"); m3_panda_scene_instance_used reports 1 while rows are on.  m3_cost takes the
  * handle's cost weights as before (m3_panda_weighted_cost_instance_used keeps saying whether the WEIGHTS needed them).
- * NOT in the lockstep episodes: m3_panda_episodes_create / _observe / _act / _act_first with such a world return
- * M3_ERR_UNSUPPORTED (the message names m3_set_panda_scene_rows); nothing is launched. */
+ * In the lockstep episodes on request: m3_panda_episodes_create / _observe / _act / _act_first with such a world return
+ * M3_ERR_UNSUPPORTED (the message names m3_set_panda_scene_rows), nothing is launched; a set created by
+ * m3_panda_episodes_create_ex with M3_PANDA_EPISODES_RUNTIME steps row e of the world in scenes[e]. */
 int m3_set_panda_scene_rows(m3_handle* h, const m3_panda_scene* scenes, int n);
 /* row `row` as it was set; M3_ERR_STATE while the rows are off */
 int m3_get_panda_scene_row(const m3_handle* h, int row, m3_panda_scene* out);
@@ -348,7 +350,7 @@ int m3_panda_scene_rows_set(const m3_handle* h);
  * sample reads its row of the handle's own table; bit-identical to the handle's own m3_command).  A batch made by
  * m3_batch_create returns M3_ERR_UNSUPPORTED for it, and so do m3_panda_episodes_create / _observe / _act / _act_first with
  * such a planner, whatever batch they are handed (the message names m3_set_panda_rollout_scenes and the index of the handle);
- * nothing is launched. */
+ * nothing is launched.  A set created by m3_panda_episodes_create_ex with M3_PANDA_EPISODES_RUNTIME takes it. */
 int m3_set_panda_rollout_scenes(m3_handle* h, const m3_panda_scene* scenes, int n);
 int m3_get_panda_rollout_scene(const m3_handle* h, int row, m3_panda_scene* out);
 /* 0 / 1: whether the handle's rollout is on per-sample workspaces */
@@ -485,7 +487,8 @@ void m3_default_panda_cost_weights(m3_panda_cost_weights* w);
  * weighted family (bit-identical to its own m3_command).  A batch made by m3_batch_create returns M3_ERR_UNSUPPORTED for it,
  * and so do m3_panda_episodes_create / _observe / _act / _act_first with such a planner, whatever batch they are handed (the
  * message names m3_set_panda_cost_weights and the index of the handle); nothing is launched.  A sim_only world handle with
- * weights is accepted by the episodes: its step reads no weight. */
+ * weights is accepted by the episodes: its step reads no weight.  A set created by m3_panda_episodes_create_ex with
+ * M3_PANDA_EPISODES_RUNTIME takes such a planner. */
 int m3_set_panda_cost_weights(m3_handle* h, const m3_panda_cost_weights* w);
 int m3_get_panda_cost_weights(const m3_handle* h, m3_panda_cost_weights* out);
 /* Test and A/B switch: -1 the automatic choice above (default), 1 the weighted family whatever the weights, 0 never -- with
@@ -820,6 +823,8 @@ typedef struct {
 typedef struct m3_panda_episodes m3_panda_episodes;
 int m3_panda_episodes_create(m3_handle* world, m3_handle* const* planners, int n, int max_ticks, int settle_ticks, int trace,
                              m3_panda_episodes** out);
+/* A set that also takes run-time workspaces, tuned weights and workspaces per row (M3_PANDA_EPISODES_RUNTIME) is made by the
+ * _create_ex form of this call, declared in include/m3p2i_hip_ext.h; every call below serves both kinds of set. */
 int m3_panda_episodes_observe(m3_panda_episodes* eps, const float** rb_host);
 int m3_panda_episodes_act(m3_panda_episodes* eps, m3_batch* batch, const int* ended_host /* [n] */);
 int m3_panda_episodes_act_first(m3_panda_episodes* eps, m3_handle* const* sims /* [n] */, const int* ended_host /* [n] */);

@@ -45,6 +45,7 @@ class Config(C.Structure):
 
 
 BATCH_PANDA_RUNTIME = 1   # M3_BATCH_PANDA_RUNTIME (m3_batch_create_ex)
+PANDA_EPISODES_RUNTIME = 1   # M3_PANDA_EPISODES_RUNTIME (m3_panda_episodes_create_ex)
 
 
 class PointWorld(C.Structure):
@@ -305,6 +306,13 @@ SYMBOLS = [
     ("m3_wave_order", C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
 ]
 
+# every symbol include/m3p2i_hip_ext.h declares -- additive forms of calls above, in a table of their own: SYMBOLS stays the list
+# of include/m3p2i_hip.h, name for name
+SYMBOLS_EXT = [
+    ("m3_panda_episodes_create_ex", C.c_int, [_H, C.POINTER(_H), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
+    ("m3_panda_episodes_flags", C.c_int, [_H]),
+]
+
 _lib = None
 
 
@@ -325,7 +333,7 @@ def load():
     # and streams are interchangeable between torch and the library.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS:
+    for name, res, args in SYMBOLS + SYMBOLS_EXT:
         fn = getattr(lib, name)  # AttributeError if the export is missing
         fn.restype = res
         fn.argtypes = args

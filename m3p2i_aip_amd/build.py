@@ -21,7 +21,7 @@ SOURCES = ["rollout_point.hip", "rollout_point_task0.hip", "rollout_point_task1.
            "rollout_point_task3.hip", "rollout_point_scene.hip", "rollout_point_scene_rows.hip",
            "rollout_point_rollout_scenes.hip",
            "rollout_panda.hip", "rollout_panda_scene.hip", "rollout_panda_weights.hip", "rollout_panda_rows.hip",
-           "rollout_panda_batch_rt.hip",
+           "rollout_panda_batch_rt.hip", "rollout_panda_episodes_rt.hip",
            "update.hip", "update_small.hip", "update_sharded.hip", "sampler.hip", "p2p.hip", "m3_api.hip"]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall",
           "-Wno-unused-function"]
@@ -38,16 +38,17 @@ PER_SOURCE = {
     "rollout_panda_weights.hip": ["-fno-slp-vectorize", "-O2"],   # (likewise)
     "rollout_panda_rows.hip": ["-fno-slp-vectorize", "-O2"],   # (likewise)
     "rollout_panda_batch_rt.hip": ["-fno-slp-vectorize", "-O2"],   # (likewise)
+    "rollout_panda_episodes_rt.hip": ["-fno-slp-vectorize", "-O2"],   # (likewise: k_panda_episodes_pre / _post live in rollout_panda.hip)
 }
 
 
 def source_hash(extra_flags=()):
-    """Identity of a build that survives a rebuild: sha256 over the kernel sources, the public header and every compiler flag
+    """Identity of a build that survives a rebuild: sha256 over the kernel sources, the public headers and every compiler flag
     (the .so's own bytes differ from one link to the next).  Compiled into the library (m3_build_id) -- the key of the committed
     PMC profiles that bench.py's roofline_valu reads."""
     import hashlib
     h = hashlib.sha256()
-    files = sorted(os.listdir(CSRC)) + [os.path.join("..", "..", "include", "m3p2i_hip.h")]
+    files = sorted(os.listdir(CSRC)) + [os.path.join("..", "..", "include", h) for h in ("m3p2i_hip.h", "m3p2i_hip_ext.h")]
     for f in files:
         path = os.path.join(CSRC, f)
         if os.path.isfile(path):
@@ -61,7 +62,7 @@ def _stale():
         return True
     t = os.path.getmtime(OUT)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
-    deps.append(os.path.join(os.path.dirname(HERE), "include", "m3p2i_hip.h"))
+    deps += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("m3p2i_hip.h", "m3p2i_hip_ext.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -14,6 +14,7 @@
 #include "m3_internal.hpp"
 #include "batch_table_layout.hpp"
 #include "panda_episode_lane.hpp"
+#include "panda_episode_tables.hpp"
 #include "point_scene_rows.hpp"
 #include "panda_scene_rows.hpp"
 
@@ -1196,6 +1197,14 @@ static const char* panda_refusal(const m3_handle* h, PandaSide side) {
 static const char* panda_unbatched(const m3_handle* h, PandaUnbatchedOrder order) {
     return h->cfg.env_type == M3_ENV_PANDA ? panda_refusal_text(panda_unbatched(panda_input(h), order)) : nullptr;
 }
+// why a lockstep episode set of that mode cannot take the handle, the world or a planner (code: M3_ERR_STATE for what the
+// handle's own kernels refuse, M3_ERR_UNSUPPORTED for what only the literal mode cannot carry; nullptr as above)
+static const char* panda_episodes_refusal(const m3_handle* h, PandaEpisodesMode mode, PandaUnbatchedOrder order, int& code) {
+    if (h->cfg.env_type != M3_ENV_PANDA) return nullptr;
+    const PandaRefusal r = panda_episodes_refusal(panda_input(h), mode, order);
+    code = panda_refusal_is_state(r) ? M3_ERR_STATE : M3_ERR_UNSUPPORTED;
+    return panda_refusal_text(r);
+}
 // a launcher's view of the handle for a variant, and the record of what an accepted call launches
 static PandaLaunchScene panda_launch_scene(const m3_handle* h, PandaVariant v) {
     return {v, &h->pscene, &h->pscene_rt, &h->panda_cost_weights, h->panda_rows_dev};
@@ -2215,8 +2224,9 @@ static int batch_refuse(m3_batch* b, int code, int i, const char* msg) {
     return code;
 }
 
-// panda_runtime: whether the run-time section may be used -- the batch's flag for m3_batch_command; never for the lockstep
-// panda episodes, whose pre and post kernels know one compiled-in workspace (whatever batch they are handed)
+// panda_runtime: whether the run-time section may be used -- the batch's flag for m3_batch_command and for a lockstep panda
+// episode set created with M3_PANDA_EPISODES_RUNTIME; never for a set created without it, whose pre and post kernels know one
+// compiled-in workspace (whatever batch it is handed)
 static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* actions_host, bool panda_runtime) {
     // ---- every check before any launch: a refused call leaves every handle as it was ----
     if (!hs) return batch_refuse(b, M3_ERR_BAD_ARG, -1, "null handle list");
@@ -2843,11 +2853,20 @@ struct m3_panda_episodes {
     std::vector<const float*> plan;  // each planner's action-out, fixed at create
     std::vector<m3_handle*> live;    // scratch: this tick's batch
     std::vector<m3_panda_episode_status> mirror;   // the device's status words, advanced on the host by the same pe_advance
-    OwnedBlocks mem{&m3_release_block, 3};   // owns the three blocks; dev, trace and pinned are views (and the three below into them)
+    OwnedBlocks mem{&m3_release_block, 7};   // owns the blocks; dev, trace, pinned and the tables are views (and the three below into them)
     char* dev = nullptr;             // status | plan pointers | kept targets | ended | planning view: dof, root, rigid bodies
     float* trace = nullptr;
     char* pinned = nullptr;          // rigid-body rows of the planning view | ended
     size_t rb_bytes = 0;
+    // M3_PANDA_EPISODES_RUNTIME (m3_panda_episodes_create_ex): the two workspace tables [PANDA_SCENE_ROW_WORDS][n]
+    // (panda_episode_tables.hpp), index 0 the planning side (row e: planner e's workspace), 1 the world side (row e: the
+    // workspace of row e of the world).  Each has its device table, its pinned mirror and the host's copy of the scenes the
+    // mirror was packed from; all from create, null / empty without the flag
+    int flags = 0;
+    float* rows_dev[2] = {};
+    float* rows_pinned[2] = {};
+    std::vector<m3_panda_scene> rows_kept[2];
+    bool rows_fresh[2] = {true, true};   // nothing packed yet: the next refresh packs every row
     int* ended_pinned = nullptr;
     int* ended_dev = nullptr;
     float* kept_dev = nullptr;
@@ -2873,10 +2892,43 @@ static int peps_refuse(int code, int i, const std::string& msg) {
     return code;
 }
 
-extern "C" int m3_panda_episodes_create(m3_handle* world, m3_handle* const* planners, int n, int max_ticks, int settle_ticks,
-                                        int trace, m3_panda_episodes** out) {
+// the mode of a set, and which workspace each of its rows runs in: the planning side's row e is what row 0 of planner e's own
+// simulator steps in -- row 0 of its per-sample rows when it has them (the simulator's environment 0), else its single scene,
+// which _bind_world pushes from the simulator it follows; the world side's row e is scenes[e] of m3_set_panda_scene_rows, else
+// the world's single scene
+static PandaEpisodesMode peps_mode(int flags) { return (flags & M3_PANDA_EPISODES_RUNTIME) ? PANDA_EPISODES_RUNTIME : PANDA_EPISODES_LITERAL; }
+static const m3_panda_scene& peps_planner_scene(const m3_handle* h) { return h->panda_rollout_scenes_on ? h->panda_rows[0] : h->panda_scene; }
+static const m3_panda_scene& peps_world_scene(const m3_handle* w, int e) { return w->panda_scene_rows_on ? w->panda_rows[e] : w->panda_scene; }
+
+// Table `side` (0 planning, 1 world) of a run-time set from the handles' current state, on the world's stream: the rows whose
+// workspace changed since the last refresh are packed into the pinned mirror again (make_panda_scene_rt on the host) and the
+// table is uploaded in one copy; nothing changed: no copy.  No allocation, no synchronisation.  The pinned mirror is free to
+// rewrite: the last copy from it was enqueued by an earlier observe (planning side) or act (world side), and every tick's
+// observe has synchronised the stream since -- the planning side is refreshed BEFORE this tick's observe synchronises and after
+// the previous tick's did, the world side after this tick's (tick 0: nothing was in flight but create's own copy, which create
+// waited for).
+static hipError_t peps_refresh_rows(m3_panda_episodes* eps, int side) {
+    const m3_handle* w = eps->world;
+    const int n = eps->n;
+    const int packed = panda_episode_table_refresh(eps->rows_pinned[side], eps->rows_kept[side].data(), eps->rows_fresh[side], n,
+                                                   w->cfg.dt, w->cfg.substeps, [&](int e) -> const m3_panda_scene& {
+                                                       return side == 0 ? peps_planner_scene(eps->planners[e]) : peps_world_scene(w, e);
+                                                   });
+    eps->rows_fresh[side] = false;
+    if (packed == 0) return hipSuccess;
+    return hipMemcpyAsync(eps->rows_dev[side], eps->rows_pinned[side], (size_t)PANDA_SCENE_ROW_WORDS * n * sizeof(float),
+                          hipMemcpyHostToDevice, w->stream);
+}
+static PandaEpisodesLaunchScene peps_launch_scene(const m3_panda_episodes* eps) {
+    return {panda_episodes_variant(peps_mode(eps->flags)), &eps->world->pscene, &eps->world->pscene_rt, eps->rows_dev[0], eps->rows_dev[1]};
+}
+
+// (the messages keep m3_panda_episodes_create's name: flags == 0 is that call)
+static int peps_create(m3_handle* world, m3_handle* const* planners, int n, int max_ticks, int settle_ticks, int trace, int flags,
+                       m3_panda_episodes** out) {
     if (!out) return peps_refuse(M3_ERR_BAD_ARG, -1, "null argument");
     *out = nullptr;
+    const PandaEpisodesMode mode = peps_mode(flags);
     // ---- every check before any allocation or launch ----
     if (!world || !planners) return peps_refuse(M3_ERR_BAD_ARG, -1, "null argument");
     if (n <= 0 || n > 65535) return peps_refuse(M3_ERR_BAD_ARG, -1, "n must be in 1 .. 65535");
@@ -2889,7 +2941,10 @@ extern "C" int m3_panda_episodes_create(m3_handle* world, m3_handle* const* plan
     if (wc.K_local != n || wc.K_global != n) return peps_refuse(M3_ERR_STATE, -1, "the world's K_local must equal n (one row per episode)");
     // (the world is sim_only: its step reads no weight, and none is asked about)
     if (const char* why = panda_refusal(world, PANDA_SIDE_STEP)) return peps_refuse(M3_ERR_STATE, -1, std::string("the world: ") + why);
-    if (const char* why = panda_unbatched(world, PANDA_ROWS_THEN_WEIGHTS)) return peps_refuse(M3_ERR_UNSUPPORTED, -1, std::string("the world: ") + why);
+    {
+        int code = M3_ERR_UNSUPPORTED;
+        if (const char* why = panda_episodes_refusal(world, mode, PANDA_ROWS_THEN_WEIGHTS, code)) return peps_refuse(code, -1, std::string("the world: ") + why);
+    }
     for (int i = 0; i < n; ++i) {
         m3_handle* h = planners[i];
         if (!h) return peps_refuse(M3_ERR_BAD_ARG, i, "null handle");
@@ -2902,7 +2957,8 @@ extern "C" int m3_panda_episodes_create(m3_handle* world, m3_handle* const* plan
         if (h->stream != world->stream) return peps_refuse(M3_ERR_STATE, i, "its stream differs from the world's");
         UpdateArgs u;
         int code;
-        if (const char* why = batch_refusal(h, u, code)) return peps_refuse(code, i, why);
+        // (a run-time set hands its planners to the batch's run-time section: what batch_refusal passes for such a batch)
+        if (const char* why = batch_refusal(h, u, code, mode == PANDA_EPISODES_RUNTIME)) return peps_refuse(code, i, why);
         if (!h->action_out) return peps_refuse(M3_ERR_STATE, i, "no action-out destination (m3_set_action_out)");
     }
     // ---- allocations: all of the set's memory, here ----
@@ -2916,6 +2972,8 @@ extern "C" int m3_panda_episodes_create(m3_handle* world, m3_handle* const* plan
         eps->plan.resize(n);
         eps->live.reserve(n);
         eps->mirror.assign(n, st0);
+        if (mode == PANDA_EPISODES_RUNTIME)
+            for (auto& kept : eps->rows_kept) kept.assign(n, PANDA_SCENE_DEFAULT);
     } catch (...) {
         delete eps;
         return peps_refuse(M3_ERR_HIP, -1, "out of host memory");
@@ -2925,6 +2983,7 @@ extern "C" int m3_panda_episodes_create(m3_handle* world, m3_handle* const* plan
     eps->n = n;
     eps->max_ticks = max_ticks;
     eps->settle_ticks = settle_ticks;
+    eps->flags = flags;
     const SimViews& wv = world->views;
     const size_t st_b = align16((size_t)n * sizeof(m3_panda_episode_status));
     const size_t plan_b = align16((size_t)n * sizeof(const float*));
@@ -2939,6 +2998,15 @@ extern "C" int m3_panda_episodes_create(m3_handle* world, m3_handle* const* plan
     if (e == hipSuccess && trace)
         e = own_device(eps->mem, eps->trace, (size_t)max_ticks * n * m3::PE_TRACE_FLOATS * sizeof(float));
     if (e == hipSuccess) e = own_pinned(eps->mem, eps->pinned, rb_b + end_b, hipHostMallocDefault);
+    if (mode == PANDA_EPISODES_RUNTIME) {
+        // the two tables, filled from the handles as they stand (a tick refreshes what changed since)
+        const size_t table_bytes = (size_t)PANDA_SCENE_ROW_WORDS * n * sizeof(float);
+        for (int side = 0; side < 2; ++side) {
+            if (e == hipSuccess) e = own_device(eps->mem, eps->rows_dev[side], table_bytes);
+            if (e == hipSuccess) e = own_pinned(eps->mem, eps->rows_pinned[side], table_bytes, hipHostMallocDefault);
+            if (e == hipSuccess) e = peps_refresh_rows(eps, side);
+        }
+    }
     char* d_st = eps->dev;
     char* d_plan = d_st + st_b;
     char* d_kept = d_plan + plan_b;
@@ -2982,6 +3050,23 @@ extern "C" int m3_panda_episodes_create(m3_handle* world, m3_handle* const* plan
     return M3_OK;
 }
 
+extern "C" int m3_panda_episodes_create(m3_handle* world, m3_handle* const* planners, int n, int max_ticks, int settle_ticks,
+                                        int trace, m3_panda_episodes** out) {
+    return peps_create(world, planners, n, max_ticks, settle_ticks, trace, 0, out);
+}
+
+extern "C" int m3_panda_episodes_create_ex(m3_handle* world, m3_handle* const* planners, int n, int max_ticks, int settle_ticks,
+                                           int trace, int flags, m3_panda_episodes** out) {
+    if (out) *out = nullptr;
+    if (flags & ~M3_PANDA_EPISODES_RUNTIME) {
+        g_peps_err = "m3_panda_episodes_create_ex: unknown flag bits";
+        return M3_ERR_BAD_ARG;
+    }
+    return peps_create(world, planners, n, max_ticks, settle_ticks, trace, flags, out);
+}
+
+extern "C" int m3_panda_episodes_flags(const m3_panda_episodes* eps) { return eps ? eps->flags : M3_ERR_BAD_ARG; }
+
 static int peps_active(const m3_panda_episodes* eps) {
     int r = 0;
     for (int i = 0; i < eps->n; ++i) r += eps->mirror[i].phase != m3::PE_FROZEN;
@@ -2990,12 +3075,14 @@ static int peps_active(const m3_panda_episodes* eps) {
 
 static int peps_ready(m3_panda_episodes* eps, const char* who) {
     if (peps_active(eps) == 0) { eps->err = std::string(who) + ": every episode has ended and settled"; return M3_ERR_STATE; }
-    // (a workspace or cost weights set after m3_panda_episodes_create, which refuses them: nothing of this tick is launched)
+    // (a workspace or cost weights set after m3_panda_episodes_create, which refuses them, or a switch forced off under a
+    // run-time set: nothing of this tick is launched)
+    const PandaEpisodesMode mode = peps_mode(eps->flags);
     for (int i = -1; i < eps->n; ++i) {
         const m3_handle* h = i < 0 ? eps->world : eps->planners[i];
         const char* why = panda_refusal(h, i < 0 ? PANDA_SIDE_STEP : PANDA_SIDE_ROLLOUT);   // (the world's step reads no weight)
-        const int code = why ? M3_ERR_STATE : M3_ERR_UNSUPPORTED;
-        if (!why) why = panda_unbatched(h, PANDA_WEIGHTS_THEN_ROWS);
+        int code = M3_ERR_STATE;
+        if (!why) why = panda_episodes_refusal(h, mode, PANDA_WEIGHTS_THEN_ROWS, code);
         if (why) {
             eps->err = std::string(who) + (i < 0 ? ": the world: " : ": planner " + std::to_string(i) + ": ") + why;
             return code;
@@ -3016,7 +3103,9 @@ extern "C" int m3_panda_episodes_observe(m3_panda_episodes* eps, const float** r
     int rc = peps_ready(eps, "m3_panda_episodes_observe");
     if (rc != M3_OK) return rc;
     const hipStream_t s = eps->world->stream;
-    m3::launch_panda_episodes_pre(eps->world->pscene, eps->args, s);
+    // (a planner's m3_set_panda_scene / _rollout_scenes since the last tick applies from this one)
+    if (peps_mode(eps->flags) == PANDA_EPISODES_RUNTIME) HIPCHK(eps, peps_refresh_rows(eps, 0));
+    m3::launch_panda_episodes_pre(peps_launch_scene(eps), eps->args, s);
     HIPCHK(eps, hipGetLastError());
     HIPCHK(eps, hipMemcpyAsync(eps->pinned, eps->args.pv.rigid_body_state, eps->rb_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(eps, hipStreamSynchronize(s));
@@ -3031,7 +3120,9 @@ static int peps_post(m3_panda_episodes* eps, const int* ended_host) {
     const hipStream_t s = eps->world->stream;
     for (int i = 0; i < eps->n; ++i) eps->ended_pinned[i] = ended_host[i] != 0;
     HIPCHK(eps, hipMemcpyAsync(eps->ended_dev, eps->ended_pinned, (size_t)eps->n * sizeof(int), hipMemcpyHostToDevice, s));
-    m3::launch_panda_episodes_post(eps->world->pscene, eps->args, eps->tick, s);
+    // (the world's m3_set_panda_scene / _scene_rows since the last tick applies from this one; the mirror: peps_refresh_rows)
+    if (peps_mode(eps->flags) == PANDA_EPISODES_RUNTIME) HIPCHK(eps, peps_refresh_rows(eps, 1));
+    m3::launch_panda_episodes_post(peps_launch_scene(eps), eps->args, eps->tick, s);
     HIPCHK(eps, hipGetLastError());
     for (int i = 0; i < eps->n; ++i)
         (void)m3::pe_advance(eps->mirror[i], eps->ended_pinned[i], eps->tick, eps->args.last_tick, eps->settle_ticks);
@@ -3060,8 +3151,12 @@ extern "C" int m3_panda_episodes_act(m3_panda_episodes* eps, m3_batch* batch, co
         eps->live.push_back(h);
     }
     if (!eps->live.empty()) {
-        // (never the run-time section: a planner or world of these episodes stays on the compiled-in workspace and the literal cost)
-        rc = batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr, false);
+        // (a set created without the flag never uses the run-time section: its planners and world stay on the compiled-in
+        // workspace and the literal cost, whatever batch they are handed.  A run-time set passes the batch's own flag through,
+        // as m3_batch_command does: a batch without the section refuses a planner that needs it, with its code and message,
+        // before anything is launched)
+        const bool section = peps_mode(eps->flags) == PANDA_EPISODES_RUNTIME && (batch->flags & M3_BATCH_PANDA_RUNTIME) != 0;
+        rc = batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr, section);
         if (rc != M3_OK) { eps->err = std::string("m3_panda_episodes_act: ") + m3_batch_last_error(batch); return rc; }
     }
     return peps_post(eps, ended_host);

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../include/m3p2i_hip.h"
+#include "../../include/m3p2i_hip_ext.h"
 #include "planar_dyn.hpp"
 #include "point_cost.hpp"
 #include "panda_dyn.hpp"
@@ -448,8 +449,20 @@ struct PandaEpisodeArgs {
     m3_panda_episode_status* st;   // [n]
     float* trace;                  // [max_ticks][n][PE_TRACE_FLOATS] or null
 };
-void launch_panda_episodes_pre(const PandaScene& sc, const PandaEpisodeArgs& a, hipStream_t s);
-void launch_panda_episodes_post(const PandaScene& sc, const PandaEpisodeArgs& a, int tick, hipStream_t s);
+// What a tick's two launches are for: the family (panda_variant.hpp: panda_episodes_variant -- PANDA_LITERAL, or PANDA_ROWS for a
+// set created with M3_PANDA_EPISODES_RUNTIME) and what either reads: lit the literal kernels (the world's scene); the rows kernels
+// uni (the members of the world's pscene_rt that depend on dt / substeps / iters alone) and the set's two device tables
+// [PANDA_SCENE_ROW_WORDS][n] -- plan_rows the pre kernel (row e: planner e's workspace), world_rows the post kernel (row e: the
+// workspace of row e of the world).
+struct PandaEpisodesLaunchScene {
+    PandaVariant variant;
+    const PandaScene* lit;
+    const PandaSceneRT* uni;
+    const float* plan_rows;
+    const float* world_rows;
+};
+void launch_panda_episodes_pre(const PandaEpisodesLaunchScene& sc, const PandaEpisodeArgs& a, hipStream_t s);
+void launch_panda_episodes_post(const PandaEpisodesLaunchScene& sc, const PandaEpisodeArgs& a, int tick, hipStream_t s);
 
 }  // namespace m3
 

@@ -125,4 +125,19 @@ inline PandaRefusal panda_unbatched(const PandaVariantInput& in, PandaUnbatchedO
     return first != PANDA_REFUSAL_NONE ? first : second;
 }
 
+// The lockstep episodes (m3_panda_episodes_*) come in two modes.  A set made by m3_panda_episodes_create runs the literal pre and
+// post kernels and hands its planners to the literal section of a batch table: it takes what panda_unbatched passes.  A set made
+// with M3_PANDA_EPISODES_RUNTIME runs the rows kernels on its own two tables (a single scene is n equal rows: one family) and
+// hands its planners to the batch's run-time section: nothing is "unbatched" any more, what remains is what the handle's own
+// kernels refuse -- the forced-off switches, on the step side for the world (its step reads no weight) and on the batch side for
+// a planner.  `order` is read by the literal mode only.
+enum PandaEpisodesMode { PANDA_EPISODES_LITERAL, PANDA_EPISODES_RUNTIME };
+constexpr PandaVariant panda_episodes_variant(PandaEpisodesMode mode) { return mode == PANDA_EPISODES_RUNTIME ? PANDA_ROWS : PANDA_LITERAL; }
+inline PandaRefusal panda_episodes_refusal(const PandaVariantInput& in, PandaEpisodesMode mode, PandaUnbatchedOrder order) {
+    if (mode == PANDA_EPISODES_LITERAL) return panda_unbatched(in, order);
+    return panda_refusal(in, in.sim_only ? PANDA_SIDE_STEP : PANDA_SIDE_BATCH);
+}
+// the refusals of panda_refusal are M3_ERR_STATE, those of panda_unbatched M3_ERR_UNSUPPORTED
+constexpr bool panda_refusal_is_state(PandaRefusal r) { return r >= PANDA_SCENE_OFF_ENV_ROWS && r <= PANDA_WEIGHTS_OFF_TUNED; }
+
 }  // namespace m3

@@ -310,8 +310,12 @@ __global__ __launch_bounds__(64) void k_panda_episodes_pre(const PandaScene sc, 
     //     root rows, m3_bind_sim_panda)
     panda_push_views(sc, a.pv, e, w);
 }
-void launch_panda_episodes_pre(const PandaScene& sc, const PandaEpisodeArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_panda_episodes_pre, dim3((a.n + 63) / 64), dim3(64), 0, s, sc, a);
+// (PANDA_ROWS: a set created with M3_PANDA_EPISODES_RUNTIME -- its kernels and tables: rollout_panda_episodes_rt.hip)
+void launch_panda_episodes_pre(const PandaEpisodesLaunchScene& sc, const PandaEpisodeArgs& a, hipStream_t s) {
+    switch (sc.variant) {
+        case PANDA_LITERAL: hipLaunchKernelGGL(k_panda_episodes_pre, dim3((a.n + 63) / 64), dim3(64), 0, s, *sc.lit, a); return;
+        default: return launch_panda_episodes_pre_rows(sc, a, s);
+    }
 }
 
 // after the command: trace row, the 1-env world's step (k_psim_step's body on row e), the end of an episode
@@ -358,8 +362,11 @@ __global__ __launch_bounds__(64) void k_panda_episodes_post(const PandaScene sc,
     // (6) no lane steps after its episode's last step (op == 0 from then on): row e of the views KEEPS the cubes' positions the
     // serial loop reads after its loops -- m3_panda_episodes_status takes them from there
 }
-void launch_panda_episodes_post(const PandaScene& sc, const PandaEpisodeArgs& a, int tick, hipStream_t s) {
-    hipLaunchKernelGGL(k_panda_episodes_post, dim3((a.n + 63) / 64), dim3(64), 0, s, sc, a, tick);
+void launch_panda_episodes_post(const PandaEpisodesLaunchScene& sc, const PandaEpisodeArgs& a, int tick, hipStream_t s) {
+    switch (sc.variant) {
+        case PANDA_LITERAL: hipLaunchKernelGGL(k_panda_episodes_post, dim3((a.n + 63) / 64), dim3(64), 0, s, *sc.lit, a, tick); return;
+        default: return launch_panda_episodes_post_rows(sc, a, tick, s);
+    }
 }
 
 }  // namespace m3

@@ -163,6 +163,9 @@ PsimStepLaunch launch_psim_step_scene, launch_psim_step_rows;
 PsimPullLaunch launch_psim_pull_scene, launch_psim_pull_rows;
 PsimPushLaunch launch_psim_push_scene, launch_psim_push_rows;
 PsimCostLaunch launch_psim_cost_scene, launch_psim_cost_weighted, launch_psim_cost_rows;
+// (the lockstep episodes' pre and post kernels on the set's tables: rollout_panda_episodes_rt.hip)
+void launch_panda_episodes_pre_rows(const PandaEpisodesLaunchScene& sc, const PandaEpisodeArgs& a, hipStream_t s);
+void launch_panda_episodes_post_rows(const PandaEpisodesLaunchScene& sc, const PandaEpisodeArgs& a, int tick, hipStream_t s);
 
 // ======================= step mode ======================================================
 // SoA world rows (NWP = 77): q 0-8 | qd 9-17 | cubeA 18-30 (pos3 quat4 vel3 angvel3) | cubeB 31-43 | plate pos 44-46,

@@ -850,22 +850,37 @@ class HipPandaEpisodes(_CObject):
     the N-env world engine (an ``IsaacGymWrapper(..., "panda_env", num_envs=N)``'s) is episode e's 1-env world, planned by
     ``engines[e]``.  The task planners stay on the host: a tick is ``observe()`` (the link rows they read, one copy, one
     synchronisation), their decisions, ``act(batch, ended)``.  Each engine's ``set_action_out`` tensor is read here and must
-    stay the same.  The set owns its device state, planning views and pinned host copy; a tick allocates nothing."""
+    stay the same.  The set owns its device state, planning views and pinned host copy; a tick allocates nothing.
+    ``panda_runtime=True`` (``M3_PANDA_EPISODES_RUNTIME``, ``m3_panda_episodes_create_ex``) also takes a world with a workspace
+    of its own or one per environment and planners with a workspace of their own, tuned cost weights or a workspace per
+    sample: row e of the world steps in the world's workspace of row e, the planning view of episode e in planner e's; hand
+    ``act`` a ``HipBatch(..., panda_runtime=True)``."""
 
     _ptr, _destroy, _last_error = "_eps", "m3_panda_episodes_destroy", "m3_panda_episodes_last_error"
 
-    def __init__(self, world, engines, max_ticks, settle_ticks=0, trace=False):
+    def __init__(self, world, engines, max_ticks, settle_ticks=0, trace=False, panda_runtime=False):
         self.lib = L.load()
         self.world, self.engines = world, list(engines)
         self.n, self.max_ticks, self.settle_ticks, self.trace_on = len(self.engines), int(max_ticks), int(settle_ticks), bool(trace)
         arr = (C.c_void_p * max(self.n, 1))(*[e._h.value for e in self.engines])
         self._eps = C.c_void_p()
-        self._ck(self.lib.m3_panda_episodes_create(world._h, arr, self.n, self.max_ticks, self.settle_ticks, int(self.trace_on),
-                                                   C.byref(self._eps)))
+        if panda_runtime:
+            self._ck(self.lib.m3_panda_episodes_create_ex(world._h, arr, self.n, self.max_ticks, self.settle_ticks,
+                                                          int(self.trace_on), L.PANDA_EPISODES_RUNTIME, C.byref(self._eps)))
+        else:
+            self._ck(self.lib.m3_panda_episodes_create(world._h, arr, self.n, self.max_ticks, self.settle_ticks, int(self.trace_on),
+                                                       C.byref(self._eps)))
         self._status = (L.PandaEpisodeStatus * self.n)()
         self._ended = (C.c_int * self.n)()
         self._rb = C.POINTER(C.c_float)()
         self.bodies = int(world._simviews[2].shape[1])
+
+    def flags(self):
+        """The flags the set was created with (``L.PANDA_EPISODES_RUNTIME`` or 0)."""
+        flags = self.lib.m3_panda_episodes_flags(self._eps)
+        if flags < 0:
+            self._ck(flags)
+        return flags
 
     def observe(self):
         """Pre kernel, one device-to-host copy, one synchronisation.  Returns the planning view's rigid-body rows as an

@@ -13,6 +13,7 @@ returns, bit for bit: ticks, success, final error, collision ticks, trace rows. 
 """
 from __future__ import annotations
 
+import dataclasses
 import time
 
 import numpy as np
@@ -28,14 +29,16 @@ class _PlannerSide:
     """The planner side of one episode: tools/closed_loop.Tamp (scripts/reactive_tamp.py's REACTIVE_TAMP), built through
     the same module names."""
 
-    def __init__(self, cfg):
+    def __init__(self, cfg, panda_scenes=None):
         from m3p2i_aip.planners.motion_planner import m3p2i
         from m3p2i_aip.planners.task_planner import task_planner
         import m3p2i_aip.utils.isaacgym_utils.isaacgym_wrapper as wrapper
         from m3p2i_aip.planners.motion_planner.cost_functions import Objective
         self.cfg = cfg
+        # (panda_scenes: the `rollout_workspace_spread` rows of a run-time panda set, as Tamp passes them; None everywhere else)
+        extra = {} if panda_scenes is None else dict(panda_scenes=panda_scenes)
         self.sim = wrapper.IsaacGymWrapper(cfg.isaacgym, cfg.env_type, num_envs=cfg.mppi.num_samples,
-                                           viewer=False, device=cfg.mppi.device, cube_on_shelf=cfg.cube_on_shelf)
+                                           viewer=False, device=cfg.mppi.device, cube_on_shelf=cfg.cube_on_shelf, **extra)
         self.objective = Objective(cfg)
         self.task_planner = task_planner.set_task_planner(cfg)
         self.task_success = False
@@ -275,10 +278,20 @@ class RowSim:
 class _PandaSide(_PlannerSide):
     """The planner side of one panda_env episode: Tamp.run_tamp split where the set takes over."""
 
-    def __init__(self, cfg):
-        super().__init__(cfg)
+    def __init__(self, cfg, panda_runtime=False):
+        # (a run-time set: simulator and planner as closed_loop.Tamp builds them -- the spread's rows on the simulator, which
+        # the planner attached to it takes over; the Objective carries `panda_cost_weights` either way)
+        super().__init__(cfg, panda_scenes=compat.rollout_panda_scenes(cfg) if panda_runtime else None)
         self.row_sim = RowSim(cfg.env_type)
         self.rb0 = None
+
+    def push_runtime(self):
+        """What the planner's first command would push to its handle -- the workspace of the simulator it follows, that
+        simulator's rows, the Objective's weights -- now: a run-time set reads them from the handle at its first observe,
+        which comes before that command."""
+        mp = self.motion_planner
+        mp._bind_world()
+        self.objective.push_cost_weights(mp._engine)
 
     def first(self, dof_state, root_state):
         """Tamp.run_tamp of tick 0 on the planner's own K-env simulator: the state upload, the task planner (its step
@@ -313,17 +326,32 @@ class _PandaSide(_PlannerSide):
 class PandaEpisodeSet:
     """One set of config_panda episodes in lockstep: built by the constructor, tick 0 by start() (each planner's first
     command on its own), then tick() while `active`; reports() afterwards.  items: [(config name, overrides, config,
-    jitter)] of one world (same dt, substeps, device, cube_on_shelf); jitter: dict(cube=(dx, dy)) or None."""
+    jitter)] of one world (same dt, substeps, device, cube_on_shelf); jitter: dict(cube=(dx, dy)) or None.
+    panda_runtime: the episodes may differ in their workspaces and weights (`panda_scene`, `world_panda_scene`,
+    `panda_cost_weights`, `rollout_workspace_spread`) -- row e of the world steps in episode e's world workspace, planner e plans
+    in its own (m3_panda_episodes_create_ex with M3_PANDA_EPISODES_RUNTIME, a batch with M3_BATCH_PANDA_RUNTIME)."""
 
-    def __init__(self, items, max_ticks, settle_ticks=0, trace=False):
+    def __init__(self, items, max_ticks, settle_ticks=0, trace=False, panda_runtime=False):
         import m3p2i_aip.utils.isaacgym_utils.isaacgym_wrapper as wrapper
         t0 = time.perf_counter()
         self.items, self.max_ticks, self.settle_ticks, self.trace = list(items), int(max_ticks), int(settle_ticks), bool(trace)
+        self.panda_runtime = bool(panda_runtime)
         cfgs = [cfg for _, _, cfg, _ in self.items]
-        self.sides = [_PandaSide(cfg) for cfg in cfgs]
         c0, n = cfgs[0], len(self.items)
-        self.real = real = wrapper.IsaacGymWrapper(c0.isaacgym, c0.env_type, num_envs=n, viewer=False, device=c0.mppi.device,
-                                                   cube_on_shelf=c0.cube_on_shelf)
+        if self.panda_runtime:
+            self.sides = [_PandaSide(cfg, panda_runtime=True) for cfg in cfgs]
+            # row e: the workspace closed_loop.run builds episode e's 1-env world with (world_isaacgym_config: `panda_scene`
+            # with `world_panda_scene` on top)
+            rows = [getattr(compat.world_isaacgym_config(cfg), "panda_scene", None) for cfg in cfgs]
+            # (every row's workspace comes from the rows: the wrapper's single workspace, which episode 0's `panda_scene` would
+            # set for all rows' views, stays the reference's)
+            plain = dataclasses.replace(c0.isaacgym, panda_scene=None)
+            self.real = real = wrapper.IsaacGymWrapper(plain, c0.env_type, num_envs=n, viewer=False, device=c0.mppi.device,
+                                                       cube_on_shelf=c0.cube_on_shelf, panda_scenes=[r or None for r in rows])
+        else:
+            self.sides = [_PandaSide(cfg) for cfg in cfgs]
+            self.real = real = wrapper.IsaacGymWrapper(c0.isaacgym, c0.env_type, num_envs=n, viewer=False, device=c0.mppi.device,
+                                                       cube_on_shelf=c0.cube_on_shelf)
         # closed_loop.run's jitter of its 1-env world, the same torch ops on row e
         ia = int(real._get_actor_index_by_name("cubeA"))
         jittered = False
@@ -343,9 +371,16 @@ class PandaEpisodeSet:
             mp._engine.set_action_out(out)
             self.outs.append(out)
         real._engine.use_torch_stream()
-        self.eps = HipPandaEpisodes(real._engine, [s.motion_planner._engine for s in self.sides], self.max_ticks,
-                                    settle_ticks=self.settle_ticks, trace=self.trace)
-        self.batch = HipBatch(n, device=torch.device(c0.mppi.device).index or 0)
+        if self.panda_runtime:
+            for side in self.sides:
+                side.push_runtime()
+            self.eps = HipPandaEpisodes(real._engine, [s.motion_planner._engine for s in self.sides], self.max_ticks,
+                                        settle_ticks=self.settle_ticks, trace=self.trace, panda_runtime=True)
+            self.batch = HipBatch(n, device=torch.device(c0.mppi.device).index or 0, panda_runtime=True)
+        else:
+            self.eps = HipPandaEpisodes(real._engine, [s.motion_planner._engine for s in self.sides], self.max_ticks,
+                                        settle_ticks=self.settle_ticks, trace=self.trace)
+            self.batch = HipBatch(n, device=torch.device(c0.mppi.device).index or 0)
         self.alive = [True] * n
         self.timelines = [[] for _ in range(n)]
         self.tasks = [[] for _ in range(n)]          # per running tick, for the trace rows
@@ -437,6 +472,10 @@ class PandaEpisodeSet:
                      build_s=self.build_s, first_s=self.first_s, loop_s=self.loop_s,
                      cube_to_goal_xy=float(torch.norm(cube[:2] - goal[:2])), cube_height_above_goal=float(cube[2] - goal[2]),
                      lanes_per_sample_used=side.motion_planner._engine.panda_lanes_per_sample_used())
+            if self.panda_runtime:      # (what closed_loop.run reports of a planner with a workspace or weights of its own)
+                eng = side.motion_planner._engine
+                r["m3_panda_scene_instance_used"] = eng.panda_scene_instance_used()
+                r["m3_panda_weighted_cost_instance_used"] = eng.panda_weighted_cost_instance_used()
             if self.trace:
                 rows = i if s["success"] else i + 1      # (no row for the success tick: the serial loop ends before it)
                 path, full = [], []
@@ -464,7 +503,7 @@ class PandaEpisodeSet:
             side.close()
 
 
-def _panda_groups(episodes, who):
+def _panda_groups(episodes, who, panda_runtime=False):
     compat.install(force_standins=True)
     groups = {}
     for idx, (cn, ov, jitter) in enumerate(episodes):
@@ -473,15 +512,16 @@ def _panda_groups(episodes, who):
             raise ValueError(f"{who}: episode {idx} is {cfg.env_type} (panda_env only)")
         # the set's one N-env world is built from its first episode's config and every row steps in that handle's scene: an
         # episode's own workspace -- its masses included -- would be dropped, so the keys are refused here, not ignored
-        for key in ("panda_scene", "world_panda_scene"):
+        # (a run-time set carries them: a workspace per row of the world, each planner's own on its handle)
+        for key in () if panda_runtime else ("panda_scene", "world_panda_scene"):
             if getattr(cfg, key):
                 raise ValueError(f"{who}: episode {idx}: `{key}` asks for a workspace of its own (m3_set_panda_scene), which the "
                                  "lockstep panda episodes do not run (one world handle, one scene); use closed_loop.run")
-        if getattr(cfg, "rollout_workspace_spread", None):
+        if not panda_runtime and getattr(cfg, "rollout_workspace_spread", None):
             raise ValueError(f"{who}: episode {idx}: `rollout_workspace_spread` asks for a workspace per sample "
                              "(m3_set_panda_rollout_scenes), which the lockstep panda episodes do not run (their planners' batched "
                              "command carries one scene); use closed_loop.run")
-        if getattr(cfg, "panda_cost_weights", None):
+        if not panda_runtime and getattr(cfg, "panda_cost_weights", None):
             raise ValueError(f"{who}: episode {idx}: `panda_cost_weights` asks for cost weights of its own (m3_set_panda_cost_weights), "
                              "which the lockstep panda episodes do not run (their planners' batched command forms the literal "
                              "cost); use closed_loop.run")
@@ -490,29 +530,34 @@ def _panda_groups(episodes, who):
     return groups
 
 
-def build_panda_set(episodes, max_ticks=600, settle_ticks=0, trace=False):
-    """A PandaEpisodeSet of episodes [(config name, overrides, jitter)] that share one world."""
-    groups = _panda_groups(episodes, "build_panda_set")
+def build_panda_set(episodes, max_ticks=600, settle_ticks=0, trace=False, panda_runtime=False):
+    """A PandaEpisodeSet of episodes [(config name, overrides, jitter)] that share one world (panda_runtime: as
+    run_panda_episodes)."""
+    groups = _panda_groups(episodes, "build_panda_set", panda_runtime)
     if len(groups) != 1:
         raise ValueError("build_panda_set: the episodes' worlds differ (dt, substeps, device, cube_on_shelf)")
-    return PandaEpisodeSet([m for _, m in next(iter(groups.values()))], max_ticks, settle_ticks, trace)
+    return PandaEpisodeSet([m for _, m in next(iter(groups.values()))], max_ticks, settle_ticks, trace, panda_runtime=panda_runtime)
 
 
-def run_panda_episodes(episodes, max_ticks=600, settle_ticks=0, trace=False):
+def run_panda_episodes(episodes, max_ticks=600, settle_ticks=0, trace=False, panda_runtime=False):
     """episodes: [("config_panda", overrides, jitter)] as closed_loop.run takes them (jitter: dict(cube=(dx, dy)) or None).
     Returns one report per episode, in order: what closed_loop.run(cn, overrides, ticks=max_ticks, jitter=jitter,
     settle_ticks=settle_ticks, trace=trace) returns, bit for bit (ticks, success, sim_time_s, timeline, cube_to_goal_xy,
     cube_height_above_goal, trace and full rows if asked), with the set's tick_ms_p50 / tick_ms_p99 in place of the
     per-episode command_ms_*, their split (observe_ms_p50, host_ms_p50, act_ms_p50), build_s / first_s / loop_s of the set
     (construction, tick 0, ticks 1..) and lanes_per_sample_used (the kernel form of the planner's last command).  Episodes
-    whose worlds differ run as separate sets, one after the other.  A lone episode is better served by closed_loop.run."""
+    whose worlds differ run as separate sets, one after the other.  A lone episode is better served by closed_loop.run.
+    panda_runtime=True: the episodes may carry `panda_scene`, `world_panda_scene`, `panda_cost_weights` and
+    `rollout_workspace_spread` overrides, each its own (refused with a ValueError otherwise) -- the reports still equal
+    closed_loop.run's bit for bit and add m3_panda_scene_instance_used / m3_panda_weighted_cost_instance_used; the episodes
+    still group by (dt, substeps, device, cube_on_shelf) only."""
     if int(max_ticks) <= 0:
         raise ValueError("run_panda_episodes: max_ticks must be > 0")
     if int(settle_ticks) < 0:
         raise ValueError("run_panda_episodes: settle_ticks must be >= 0")
     out = [None] * len(episodes)
-    for members in _panda_groups(episodes, "run_panda_episodes").values():
-        es = PandaEpisodeSet([m for _, m in members], int(max_ticks), int(settle_ticks), bool(trace))
+    for members in _panda_groups(episodes, "run_panda_episodes", panda_runtime).values():
+        es = PandaEpisodeSet([m for _, m in members], int(max_ticks), int(settle_ticks), bool(trace), panda_runtime=panda_runtime)
         try:
             es.run()
             reps = es.reports()

@@ -3,11 +3,17 @@
 block-to-goal error, task time, dyn-obs collisions -- next to the logged statistics (tests/golden/behaviour_band.json).
 
     python tools/band_stats.py [--n 20] [--json out.json] [--size baseline|default] [--avoid] [--batched]
-                               [--world-arena-spread S] [scenario ...]
+                               [--world-arena-spread S] [--runtime] [key=value ...] [scenario ...]
 
 --batched: all episodes of all named scenarios in lockstep, one library call per tick (m3p2i_aip_amd/episodes.py,
 DESIGN.md §7c): the same per-episode results as the serial runs, bit for bit.  The `panda` rows likewise, the n episodes
 of each row in lockstep (two library calls per tick with the host's task planners in between, §7d).
+
+--runtime (with --batched, the `panda` rows): the run-time set of the lockstep panda episodes (run_panda_episodes(...,
+panda_runtime=True)), which takes `panda_scene=...`, `world_panda_scene=...`, `panda_cost_weights=...` and
+`rollout_workspace_spread=...` given as key=value arguments -- e.g. --batched --runtime 'world_panda_scene={cube_m: 0.2}'
+'rollout_workspace_spread={spread: 0.3, seed: 1}' panda: does a planner that plans over a spread of models succeed more often
+in a world whose cube is heavier than its model's?  The serial `panda` rows take the same keys.
 
 --world-arena-spread S (with --batched): a randomised band -- each episode's REAL world gets its own box mass, box ground
 friction and robot-box friction, the nominal value times a factor drawn from [1 - S, 1 + S] (world_arena_of; the config key
@@ -180,6 +186,10 @@ def episodes_batched(scenario, n=20, max_sim_time_s=40.0, size="baseline"):
     return band_batched([(scenario, size)], n, max_sim_time_s)[(scenario, size)]
 
 
+# config keys `panda` takes as overrides on the command line (e.g. 'world_panda_scene={cube_m: 0.2}'); batched: with --runtime
+PANDA_RUNTIME_KEYS = ("panda_scene", "world_panda_scene", "panda_cost_weights", "rollout_workspace_spread")
+
+
 def panda_episodes(n=20, overrides=("mppi.num_samples=4000", "mppi.horizon=20"), ticks=600):
     """Panda reactive pick-and-place (config_panda), cubeA's start jittered by +-2 cm (episode 0: the reference scene)."""
     import closed_loop
@@ -196,15 +206,17 @@ def panda_episodes(n=20, overrides=("mppi.num_samples=4000", "mppi.horizon=20"),
                 ticks_to_success=stats([r["ticks"] for r in ok]) if ok else None, runs=runs)
 
 
-def panda_episodes_batched(n=20, overrides=("mppi.num_samples=4000", "mppi.horizon=20"), ticks=600):
+def panda_episodes_batched(n=20, overrides=("mppi.num_samples=4000", "mppi.horizon=20"), ticks=600, runtime=False):
     """panda_episodes() with the n episodes in lockstep (m3p2i_aip_amd.episodes.run_panda_episodes): the same
-    dict, the same per-episode results bit for bit."""
+    dict, the same per-episode results bit for bit.  runtime: the run-time set (panda_runtime=True), which takes `panda_scene`,
+    `world_panda_scene`, `panda_cost_weights` and `rollout_workspace_spread` among the overrides."""
     from m3p2i_aip_amd.episodes import run_panda_episodes
     jit = []
     for e in range(n):
         rng = np.random.default_rng([77, e])
         jit.append(dict(cube=(0.0, 0.0) if e == 0 else tuple(rng.uniform(-0.02, 0.02, 2).tolist())))
-    reps = run_panda_episodes([("config_panda", list(overrides), j) for j in jit], max_ticks=ticks, settle_ticks=SETTLE_TICKS)
+    reps = run_panda_episodes([("config_panda", list(overrides), j) for j in jit], max_ticks=ticks, settle_ticks=SETTLE_TICKS,
+                              panda_runtime=bool(runtime))
     runs = [dict(episode=e, jitter=j, success=r["success"], ticks=r["ticks"], timeline=r["timeline"],
                  cube_to_goal_xy=r["cube_to_goal_xy"], cube_height_above_goal=r["cube_height_above_goal"])
             for e, (j, r) in enumerate(zip(jit, reps))]
@@ -215,11 +227,15 @@ def panda_episodes_batched(n=20, overrides=("mppi.num_samples=4000", "mppi.horiz
 
 
 def main(argv):
-    n, out, names, size, batched, spread = 20, None, [], "baseline", False, 0.0
+    n, out, names, size, batched, spread, runtime, extra = 20, None, [], "baseline", False, 0.0, False, []
     it = iter(argv)
     for a in it:
         if a == "--batched":
             batched = True
+        elif a == "--runtime":
+            runtime = True
+        elif a.split("=", 1)[0] in PANDA_RUNTIME_KEYS and "=" in a:
+            extra.append(a)
         elif a == "--n":
             n = int(next(it))
         elif a == "--json":
@@ -235,6 +251,10 @@ def main(argv):
             names.append(a)
     if spread and not batched:
         raise SystemExit("--world-arena-spread: with --batched (the serial runs keep the nominal world)")
+    if runtime and not batched:
+        raise SystemExit("--runtime: with --batched (the run-time set of the lockstep panda episodes)")
+    if extra and batched and not runtime:
+        raise SystemExit(f"{extra[0].split('=', 1)[0]}: with --batched, the run-time set only (--runtime)")
     allband = json.load(open(os.path.join(ROOT, "tests", "golden", "behaviour_band.json")))
     band = allband["point"]
     res = {}
@@ -244,7 +264,8 @@ def main(argv):
                         ("panda_pick_faure", ["mppi.num_samples=4000", "mppi.horizon=20", "mppi.halton_scramble=faure"]),
                         ("panda_pick_default_size", ["mppi.num_samples=200", "mppi.horizon=12"]),
                         ("panda_pick_default_size_faure", ["mppi.num_samples=200", "mppi.horizon=12", "mppi.halton_scramble=faure"])):
-            r = panda_episodes_batched(n, ov) if batched else panda_episodes(n, ov)
+            ov = ov + extra
+            r = panda_episodes_batched(n, ov, runtime=runtime) if batched else panda_episodes(n, ov)
             r["logged"] = allband["panda"]["reactive_pick"]["final_xy_error_m"]
             res[tag] = r
             e = r["final_xy_error_m"]
