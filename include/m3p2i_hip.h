@@ -559,8 +559,9 @@ int m3_point_scene_rows_set(const m3_handle* h);   /* 0 / 1 */
  * form is never taken (m3_point_rollout_form_used = 0); m3_point_rollout_plan(..., scene = 2, ...) reports the launch.
  * The special samples are the caller's business: the zero-noise / null-action sample K - 1 and, in multi-modal mode, the two
  * best-trajectory samples 0 and K / 2 get their rows like any other sample -- give them the nominal arena to keep them nominal.
- * NOT batched: m3_batch_command with such a handle and m3_episodes_create / m3_episodes_tick with such a planner return
- * M3_ERR_UNSUPPORTED (the message names this call and the index of the handle); nothing is launched.
+ * NOT batched by the calls of this header: m3_batch_command with such a handle and m3_episodes_create / m3_episodes_tick with
+ * such a planner return M3_ERR_UNSUPPORTED (the message names this call and the index of the handle); nothing is launched.
+ * Batched on request: by the batch and the episode set that m3p2i_hip_ext.h declares.
  * Memory: the first call on a handle allocates a device table, its pinned host mirror and a host copy of the rows; later calls
  * reuse them (and wait for the handle's stream before they rewrite the mirror).  The upload is one hipMemcpyAsync on the
  * handle's stream.  m3_rollout and m3_command allocate nothing because of the rows. */
@@ -731,7 +732,8 @@ int m3_update_finalize(m3_handle* h);
  * contract: each handle's results are bit-identical to its own m3_command's, m3_panda_scene_instance_used and
  * m3_panda_weighted_cost_instance_used included, set as m3_rollout sets them.  Such handles group by family (literal, weighted
  * on the run-time scene, workspace per sample) ahead of the fields above; a handle with the default workspace and weights
- * runs the kernel it runs in any batch.  point_env handles with an arena per sample stay refused. */
+ * runs the kernel it runs in any batch.  point_env handles with an arena per sample stay refused by the batches of this
+ * header; m3p2i_hip_ext.h declares the call that makes a batch which takes them. */
 #define M3_BATCH_PANDA_RUNTIME 1
 typedef struct m3_batch m3_batch;
 int m3_batch_create(int device, int max_handles, m3_batch** out);   /* all device + pinned workspace allocated here */

@@ -46,6 +46,9 @@ class Config(C.Structure):
 
 BATCH_PANDA_RUNTIME = 1   # M3_BATCH_PANDA_RUNTIME (m3_batch_create_ex)
 PANDA_EPISODES_RUNTIME = 1   # M3_PANDA_EPISODES_RUNTIME (m3_panda_episodes_create_ex)
+BATCH_SECTION_PANDA_RUNTIME = 1          # M3_BATCH_SECTION_PANDA_RUNTIME (m3_batch_create_sections)
+BATCH_SECTION_POINT_ROLLOUT_SCENES = 2   # M3_BATCH_SECTION_POINT_ROLLOUT_SCENES
+EPISODES_ROLLOUT_SCENES = 1              # M3_EPISODES_ROLLOUT_SCENES (m3_episodes_create_ex)
 
 
 class PointWorld(C.Structure):
@@ -311,6 +314,9 @@ SYMBOLS = [
 SYMBOLS_EXT = [
     ("m3_panda_episodes_create_ex", C.c_int, [_H, C.POINTER(_H), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
     ("m3_panda_episodes_flags", C.c_int, [_H]),
+    ("m3_batch_create_sections", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
+    ("m3_episodes_create_ex", C.c_int, [_H, C.POINTER(_H), C.POINTER(EpisodeSpec), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
+    ("m3_episodes_flags", C.c_int, [_H]),
 ]
 
 _lib = None

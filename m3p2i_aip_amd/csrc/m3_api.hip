@@ -2089,15 +2089,17 @@ struct BatchHandle {   // one handle's command as planned, in call order (copied
 };
 constexpr BatchTableSizes BATCH_TABLE_SIZES = {{sizeof(BatchRolloutEntry), sizeof(BatchRolloutEntryW), sizeof(BatchRolloutEntryS)},
                                                sizeof(BatchPandaEntry), sizeof(UpdateArgs), 0};
-// ... of a batch created with M3_BATCH_PANDA_RUNTIME
-constexpr BatchTableSizes BATCH_TABLE_SIZES_RT = {{sizeof(BatchRolloutEntry), sizeof(BatchRolloutEntryW), sizeof(BatchRolloutEntryS)},
-                                                  sizeof(BatchPandaEntry), sizeof(UpdateArgs), sizeof(BatchPandaEntryRT)};
-static_assert(alignof(BatchPandaEntryRT) <= 16 && alignof(BatchPandaEntry) <= 16, "the table's sections start on multiples of 16");
+// (a batch created with M3_BATCH_SECTION_PANDA_RUNTIME / _POINT_ROLLOUT_SCENES: + panda_entry_rt / point_entry_sv, m3_batch_create)
+static_assert(alignof(BatchPandaEntryRT) <= 16 && alignof(BatchPandaEntry) <= 16 && alignof(BatchRolloutEntrySV) <= 16,
+              "the table's sections start on multiples of 16");
+static_assert(BATCH_POINT_SECTIONS == POINT_SECTIONS, "");
+// the refusal of a point_env handle with an arena per sample by a batch or an episode set that was not created for it
+constexpr const char* POINT_ROWS_UNBATCHED = "it has an arena per sample (m3_set_point_rollout_scenes), which only m3_rollout / m3_command run";
 }  // namespace
 
 struct m3_batch {
     int device = 0, max_handles = 0;
-    int flags = 0;           // m3_batch_create_ex's (M3_BATCH_PANDA_RUNTIME)
+    int flags = 0;           // the sections it was created with (M3_BATCH_SECTION_*; bit 1 is m3_batch_create_ex's M3_BATCH_PANDA_RUNTIME)
     BatchTableSizes sizes = BATCH_TABLE_SIZES;   // the entry sizes its tables are laid out with (flags)
     std::string err;
     size_t slot_bytes = 0;   // of a slot: the largest table of max_handles handles (batch_table_layout.hpp)
@@ -2128,11 +2130,27 @@ extern "C" int m3_batch_create(int device, int max_handles, m3_batch** out) { re
 
 extern "C" int m3_batch_flags(const m3_batch* b) { return b ? b->flags : M3_ERR_BAD_ARG; }
 
+static int batch_create(int device, int max_handles, int flags, m3_batch** out);
 // (the messages keep m3_batch_create's name: flags == 0 is that call)
 extern "C" int m3_batch_create_ex(int device, int max_handles, int flags, m3_batch** out) {
     if (!out) { g_batch_err = "m3_batch_create: null argument"; return M3_ERR_BAD_ARG; }
     *out = nullptr;
     if (flags & ~M3_BATCH_PANDA_RUNTIME) { g_batch_err = "m3_batch_create_ex: unknown flag bits"; return M3_ERR_BAD_ARG; }
+    return batch_create(device, max_handles, flags, out);
+}
+static_assert(M3_BATCH_SECTION_PANDA_RUNTIME == M3_BATCH_PANDA_RUNTIME, "one bit, two names");
+extern "C" int m3_batch_create_sections(int device, int max_handles, int sections, m3_batch** out) {
+    if (out) *out = nullptr;
+    if (sections & ~(M3_BATCH_SECTION_PANDA_RUNTIME | M3_BATCH_SECTION_POINT_ROLLOUT_SCENES)) {
+        g_batch_err = "m3_batch_create_sections: unknown section bits";
+        return M3_ERR_BAD_ARG;
+    }
+    return batch_create(device, max_handles, sections, out);
+}
+// flags: checked section bits
+static int batch_create(int device, int max_handles, int flags, m3_batch** out) {
+    if (!out) { g_batch_err = "m3_batch_create: null argument"; return M3_ERR_BAD_ARG; }
+    *out = nullptr;
     if (max_handles < 1 || max_handles > 65535) {   // (blockIdx.y picks the handle)
         g_batch_err = "m3_batch_create: max_handles must be in 1 .. 65535";
         return M3_ERR_BAD_ARG;
@@ -2149,7 +2167,8 @@ extern "C" int m3_batch_create_ex(int device, int max_handles, int flags, m3_bat
     b->device = device;
     b->max_handles = max_handles;
     b->flags = flags;
-    if (flags & M3_BATCH_PANDA_RUNTIME) b->sizes = BATCH_TABLE_SIZES_RT;
+    if (flags & M3_BATCH_SECTION_PANDA_RUNTIME) b->sizes.panda_entry_rt = sizeof(BatchPandaEntryRT);
+    if (flags & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES) b->sizes.point_entry_sv = sizeof(BatchRolloutEntrySV);
     b->slot_bytes = batch_table_capacity(b->sizes, max_handles);
     try {
         b->seen.resize(max_handles);
@@ -2189,15 +2208,17 @@ extern "C" int m3_batch_launches(const m3_batch* b, int* rollout_launches, int* 
 // the conditions under which m3_batch_command refuses a handle of the call's environment, device and stream (nullptr: none;
 // code: the return code) -- m3_episodes_create checks them too.  u: the arguments of the handle's update, as m3_command
 // launches it.  panda_runtime: the caller's table has the run-time section (a batch created with M3_BATCH_PANDA_RUNTIME), so a
-// panda_env planner that needs the run-time-scene instance, the weighted family or has a workspace per sample passes
-static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code, bool panda_runtime = false) {
+// panda_env planner that needs the run-time-scene instance, the weighted family or has a workspace per sample passes.
+// point_rows: it has the per-sample section (M3_BATCH_SECTION_POINT_ROLLOUT_SCENES), so a point_env planner with an arena per
+// sample passes
+static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code, bool panda_runtime = false, bool point_rows = false) {
     const m3_config& c = h->cfg;
     code = M3_ERR_STATE;
     if (c.K_local != c.K_global) return "sharded handle (K_local != K_global)";
     if (c.sim_only) return "handle was created sim_only";
-    if (h->rollout_scenes_on) {   // (the batched form would be a fourth section of the table: not built)
+    if (h->rollout_scenes_on && !point_rows) {   // (the table's slots have no fourth section)
         code = M3_ERR_UNSUPPORTED;
-        return "it has an arena per sample (m3_set_point_rollout_scenes), which only m3_rollout / m3_command run";
+        return POINT_ROWS_UNBATCHED;
     }
     if (const char* why = rollout_refusal(h)) return why;
     if (!panda_runtime) {
@@ -2226,8 +2247,9 @@ static int batch_refuse(m3_batch* b, int code, int i, const char* msg) {
 
 // panda_runtime: whether the run-time section may be used -- the batch's flag for m3_batch_command and for a lockstep panda
 // episode set created with M3_PANDA_EPISODES_RUNTIME; never for a set created without it, whose pre and post kernels know one
-// compiled-in workspace (whatever batch it is handed)
-static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* actions_host, bool panda_runtime) {
+// compiled-in workspace (whatever batch it is handed).  point_rows: whether the per-sample section of a point_env table may be
+// used -- the batch's flag for m3_batch_command and for a lockstep episode set created with M3_EPISODES_ROLLOUT_SCENES
+static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* actions_host, bool panda_runtime, bool point_rows) {
     // ---- every check before any launch: a refused call leaves every handle as it was ----
     if (!hs) return batch_refuse(b, M3_ERR_BAD_ARG, -1, "null handle list");
     if (n <= 0 || n > b->max_handles) return batch_refuse(b, M3_ERR_BAD_ARG, -1, "n must be in 1 .. max_handles");
@@ -2252,7 +2274,7 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
                                                                 : "panda_env handle in a batch of point_env handles (one environment per call)");
         if (h->stream != s) return batch_refuse(b, M3_ERR_STATE, i, "its stream differs from handle 0's");
         int code;
-        if (const char* why = batch_refusal(h, hd[i].u, code, panda_runtime)) return batch_refuse(b, code, i, why);
+        if (const char* why = batch_refusal(h, hd[i].u, code, panda_runtime, point_rows)) return batch_refuse(b, code, i, why);
         BatchKey& k = hd[i].key;
         if (panda) hd[i].panda = panda_decision(panda_input(h), PANDA_SIDE_BATCH);   // (by m3_rollout's own dispatch)
         k.variant = panda ? panda_batch_key(hd[i].panda.variant) : 0;
@@ -2282,21 +2304,28 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
         HIPCHK(b, hipEventSynchronize(b->done[slot]));
         b->in_flight[slot] = false;
     }
-    // point_env: in key order the handles come by variant (rollout_fields), as the table's sections do
+    // point_env: in key order the handles come by section (rollout_fields: scene 0 by weighted, 1, 2), as the table's sections do
     // panda_env: by section -- the literal entries (variant 0), then the run-time ones
-    int count[POINT_VARIANTS] = {};
+    int count[POINT_SECTIONS] = {};
     int n_lit = 0;
     if (!panda)
-        for (int i = 0; i < n; ++i) ++count[point_variant(hd[i].key.roll)];
+        for (int i = 0; i < n; ++i) ++count[point_section(hd[i].key.roll)];
     else
         for (int i = 0; i < n; ++i) n_lit += hd[i].panda.variant == PANDA_LITERAL ? 1 : 0;
-    const BatchTableLayout lay = panda ? batch_table_layout_panda(b->sizes, n_lit, n - n_lit) : batch_table_layout(b->sizes, count);
+    // (without per-sample handles the four-section layout is the three-section one)
+    BatchTableLayout4 lay = batch_table_layout4(b->sizes, count);
+    if (panda) {
+        const BatchTableLayout lp = batch_table_layout_panda(b->sizes, n_lit, n - n_lit);
+        lay.off[1] = lp.off[1];
+        lay.upd_off = lp.upd_off;
+        lay.total = lp.total;
+    }
     // byte offset of the rollout entry of the p-th handle in key order
     auto entry_off = [&](int p) {
         if (panda) return p < n_lit ? (size_t)p * sizeof(BatchPandaEntry) : lay.off[1] + (size_t)(p - n_lit) * sizeof(BatchPandaEntryRT);
         int v = 0;
         for (; p >= count[v]; ++v) p -= count[v];
-        return lay.off[v] + (size_t)p * BATCH_TABLE_SIZES.entry[v];
+        return lay.off[v] + (size_t)p * batch_point_entry(b->sizes, v);
     };
     for (int p = 0; p < n; ++p) {
         const int i = b->by_roll[p];
@@ -2308,7 +2337,8 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
             else *reinterpret_cast<BatchPandaEntryRT*>(e) = {hd[i].a, hd[i].pa, *sc.rt, *sc.wt, sc.variant == PANDA_ROWS ? sc.rows : nullptr};
             continue;
         }
-        switch (point_variant(hd[i].key.roll)) {
+        switch (point_section(hd[i].key.roll)) {
+            case POINT_SECTION_SV: *reinterpret_cast<BatchRolloutEntrySV*>(e) = {hd[i].a, h->scene_rt, h->cost_weights, h->scene_rows_dev}; break;
             case POINT_SCENE: *reinterpret_cast<BatchRolloutEntryS*>(e) = {hd[i].a, h->scene_rt, h->cost_weights}; break;
             case POINT_WEIGHTED: *reinterpret_cast<BatchRolloutEntryW*>(e) = {hd[i].a, h->scene, h->cost_weights}; break;
             default: *reinterpret_cast<BatchRolloutEntry*>(e) = {hd[i].a, h->scene}; break;
@@ -2377,7 +2407,8 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
 
 extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float* actions_host) {
     if (!b) { g_batch_err = "m3_batch_command: null batch"; return M3_ERR_BAD_ARG; }
-    return batch_command(b, hs, n, actions_host, (b->flags & M3_BATCH_PANDA_RUNTIME) != 0);
+    return batch_command(b, hs, n, actions_host, (b->flags & M3_BATCH_SECTION_PANDA_RUNTIME) != 0,
+                         (b->flags & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES) != 0);
 }
 
 static int ensure_sim(m3_handle* h);
@@ -2609,6 +2640,7 @@ static thread_local std::string g_eps_err;
 struct m3_episodes {
     m3_handle* world = nullptr;
     int n = 0, max_ticks = 0, tick = 0;
+    int flags = 0;                   // m3_episodes_create_ex's (M3_EPISODES_ROLLOUT_SCENES)
     bool mid_tick = false;           // between m3_episodes_begin and m3_episodes_end
     std::string err;
     std::vector<m3_handle*> planners;
@@ -2640,8 +2672,18 @@ static int eps_refuse(int code, int i, const std::string& msg) {
 
 extern "C" int m3_episodes_create(m3_handle* world, m3_handle* const* planners, const m3_episode_spec* specs, int n,
                                   int max_ticks, int trace, m3_episodes** out) {
+    return m3_episodes_create_ex(world, planners, specs, n, max_ticks, trace, 0, out);
+}
+
+extern "C" int m3_episodes_flags(const m3_episodes* eps) { return eps ? eps->flags : M3_ERR_BAD_ARG; }
+
+// (the messages keep m3_episodes_create's name: flags == 0 is that call)
+extern "C" int m3_episodes_create_ex(m3_handle* world, m3_handle* const* planners, const m3_episode_spec* specs, int n,
+                                     int max_ticks, int trace, int flags, m3_episodes** out) {
+    if (out) *out = nullptr;
+    if (flags & ~M3_EPISODES_ROLLOUT_SCENES) { g_eps_err = "m3_episodes_create_ex: unknown flag bits"; return M3_ERR_BAD_ARG; }
     if (!out) return eps_refuse(M3_ERR_BAD_ARG, -1, "null argument");
-    *out = nullptr;
+    const bool point_rows = (flags & M3_EPISODES_ROLLOUT_SCENES) != 0;   // planners with an arena per sample pass
     // ---- every check before any allocation or launch ----
     if (!world || !planners || !specs) return eps_refuse(M3_ERR_BAD_ARG, -1, "null argument");
     if (n <= 0 || n > 65535) return eps_refuse(M3_ERR_BAD_ARG, -1, "n must be in 1 .. 65535");
@@ -2663,7 +2705,7 @@ extern "C" int m3_episodes_create(m3_handle* world, m3_handle* const* planners, 
         if (h->stream != world->stream) return eps_refuse(M3_ERR_STATE, i, "its stream differs from the world's");
         UpdateArgs u;
         int code;
-        if (const char* why = batch_refusal(h, u, code)) return eps_refuse(code, i, why);
+        if (const char* why = batch_refusal(h, u, code, false, point_rows)) return eps_refuse(code, i, why);
         if (!h->action_out) return eps_refuse(M3_ERR_STATE, i, "no action-out destination (m3_set_action_out)");
         const m3_episode_spec& sp = specs[i];
         if (sp.task < M3_TASK_NAVIGATION || sp.task > M3_TASK_PUSH_PULL) return eps_refuse(M3_ERR_BAD_ARG, i, "spec: task is not a point_env task");
@@ -2686,6 +2728,7 @@ extern "C" int m3_episodes_create(m3_handle* world, m3_handle* const* planners, 
     eps->world = world;
     eps->n = n;
     eps->max_ticks = max_ticks;
+    eps->flags = flags;
     const size_t lane_b = align16((size_t)n * sizeof(m3::EpisodeLane));
     const size_t st_b = align16((size_t)n * sizeof(m3_episode_status));
     const size_t gate_b = align16((size_t)n * sizeof(int));
@@ -2790,12 +2833,19 @@ extern "C" int m3_episodes_tick(m3_episodes* eps, m3_batch* batch) {
     // commanded once more -- its plan is never recorded)
     eps->live.clear();
     const m3_handle* w = eps->world;
+    const bool point_rows = (eps->flags & M3_EPISODES_ROLLOUT_SCENES) != 0;
     for (int i = 0; i < eps->n; ++i) {
         if (eps->host[i].done_tick >= 0) continue;
         m3_handle* h = eps->planners[i];
-        if (h->rollout_scenes_on) {   // (set after m3_episodes_create, which refuses it: nothing of this tick is launched)
-            eps->err = "m3_episodes_tick: planner " + std::to_string(i) + ": it has an arena per sample (m3_set_point_rollout_scenes), which only m3_rollout / m3_command run";
+        if (h->rollout_scenes_on && !point_rows) {   // (set after m3_episodes_create, which refuses it: nothing of this tick is launched)
+            eps->err = "m3_episodes_tick: planner " + std::to_string(i) + ": " + POINT_ROWS_UNBATCHED;
             return M3_ERR_UNSUPPORTED;
+        }
+        // (a set created for such planners, a batch without the section: the batch's own refusal, ahead of the pre kernel)
+        if (h->rollout_scenes_on && !(batch->flags & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES)) {
+            rc = batch_refuse(batch, M3_ERR_UNSUPPORTED, (int)eps->live.size(), POINT_ROWS_UNBATCHED);
+            eps->err = std::string("m3_episodes_tick: ") + m3_batch_last_error(batch);
+            return rc;
         }
         // (f) planner i reads row i of the world: the rollout takes row 0 of its bound views
         // (rollout_point_kernel.hpp), so it sees the floats closed_loop.run copies into its K-env sim
@@ -2807,7 +2857,9 @@ extern "C" int m3_episodes_tick(m3_episodes* eps, m3_batch* batch) {
     m3::launch_episodes_pre(eps->args, eps->tick, w->stream);
     HIPCHK(eps, hipGetLastError());
     if (!eps->live.empty()) {
-        rc = m3_batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr);
+        // (a set created without the flag never uses the per-sample section, whatever batch it is handed)
+        rc = batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr, (batch->flags & M3_BATCH_SECTION_PANDA_RUNTIME) != 0,
+                           point_rows && (batch->flags & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES) != 0);
         if (rc != M3_OK) { eps->err = std::string("m3_episodes_tick: ") + m3_batch_last_error(batch); return rc; }
     }
     episodes_post(w, eps->args, eps->tick);
@@ -3156,7 +3208,7 @@ extern "C" int m3_panda_episodes_act(m3_panda_episodes* eps, m3_batch* batch, co
         // as m3_batch_command does: a batch without the section refuses a planner that needs it, with its code and message,
         // before anything is launched)
         const bool section = peps_mode(eps->flags) == PANDA_EPISODES_RUNTIME && (batch->flags & M3_BATCH_PANDA_RUNTIME) != 0;
-        rc = batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr, section);
+        rc = batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr, section, false);
         if (rc != M3_OK) { eps->err = std::string("m3_panda_episodes_act: ") + m3_batch_last_error(batch); return rc; }
     }
     return peps_post(eps, ended_host);

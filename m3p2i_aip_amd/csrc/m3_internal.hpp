@@ -191,6 +191,17 @@ static_assert(sizeof(BatchRolloutEntryW) == 616 && offsetof(BatchRolloutEntryW, 
               offsetof(BatchRolloutEntryW, wt) == 580, "");
 static_assert(sizeof(BatchRolloutEntryS) == 760 && offsetof(BatchRolloutEntryS, sc) == 528 &&
               offsetof(BatchRolloutEntryS, wt) == 724, "");
+// a point_env handle with an arena per sample (m3_set_point_rollout_scenes), in a batch created with the per-sample section:
+// what BatchRolloutEntryS holds -- sc read for its uniform members only -- and the handle's OWN device table of rows
+// [POINT_SCENE_ROW_WORDS][K_local] (point_scene_rows.hpp); the batch stores no rows
+struct BatchRolloutEntrySV {
+    RolloutArgs a;
+    PointSceneRT sc;
+    PointCostWeights wt;
+    const float* rows;
+};
+static_assert(sizeof(BatchRolloutEntrySV) == 768 && offsetof(BatchRolloutEntrySV, sc) == 528 &&
+              offsetof(BatchRolloutEntrySV, wt) == 724 && offsetof(BatchRolloutEntrySV, rows) == 760, "");
 // the k_update_small instance (template arguments, workgroup width, top-k workgroups) an unsharded command takes:
 // launch_update_small launches it, m3_batch_command groups the handles by it
 struct SmallUpdateInstance {
@@ -218,16 +229,19 @@ struct RolloutPlan {
     int form;            // point_env: 0 one wavefront per 64 samples, 1 dynamics + companion wavefront (rollout_point_kernel.hpp:
                          // rollout_point_body2); m3_rollout only -- the batched and episode paths plan with form_request 0
     int scene;           // point_env: the run-time-scene build of the general instance (POINT_SCENE; instance == -1,
-                         // weighted == 1, ref == 0, form == 0); 2: its per-sample twin (m3_set_point_rollout_scenes) -- a
-                         // property of the single-handle launch, no variant of its own and no section of the batch table
+                         // weighted == 1, ref == 0, form == 0); 2: its per-sample twin (m3_set_point_rollout_scenes) -- no
+                         // variant of its own; in a batch created with the per-sample section, the table's fourth section
 };
 inline PointVariant point_variant(const RolloutPlan& p) { return p.scene ? POINT_SCENE : p.weighted ? POINT_WEIGHTED : POINT_PLAIN; }
+// the section of the point_env batch table a plan's entry lies in: its variant's, the per-sample handles behind them
+constexpr int POINT_SECTIONS = POINT_VARIANTS + 1, POINT_SECTION_SV = POINT_VARIANTS;
+inline int point_section(const RolloutPlan& p) { return p.scene == 2 ? POINT_SECTION_SV : (int)point_variant(p); }
 // form_request: m3_set_point_rollout_form's value (0 one wavefront, 1 two wherever available, -1 by rollout_companion_pays)
 // per_sample: the handle carries one arena per sample (variant POINT_SCENE then): RolloutPlan::scene = 2
 RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, PointVariant variant, int form_request = 0,
                                bool per_sample = false);
 // one launch of the plan's instance for n handles of K_local = a.Kl and the same plan (tab: device, n entries of the type of
-// the plan's variant)
+// the plan's variant; p.scene == 2: of BatchRolloutEntrySV)
 void launch_rollout_point_batch(const void* tab, int n, const RolloutPlan& p, hipStream_t s);
 void launch_rollout_point_nav_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
 void launch_rollout_point_push_batch(const BatchRolloutEntry* tab, int blocks, int n, bool ref, hipStream_t s);
@@ -243,6 +257,8 @@ void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const Poin
 // ... of a planner handle with an arena per sample (rollout_point_rollout_scenes.hip; uni, rows: point_scene_rows.hpp)
 void launch_rollout_point_sv(const RolloutArgs& a, const PointSceneRT& uni, const float* rows, const PointCostWeights& wt,
                              int blocks, hipStream_t s);
+// ... of a group of n such handles of the same K, T and lanes (tab: device; blocks: workgroups of one handle)
+void launch_rollout_point_sv_batch(const BatchRolloutEntrySV* tab, int blocks, int n, hipStream_t s);
 // the two-wavefront form of the navigation / push instances (p.form == 1)
 void launch_rollout_point_nav2(const RolloutArgs& a, const PointScene& sc, int blocks, int* err, hipStream_t s);
 void launch_rollout_point_push2(const RolloutArgs& a, const PointScene& sc, int blocks, int* err, hipStream_t s);

@@ -45,4 +45,36 @@ void launch_rollout_point_sv(const RolloutArgs& a, const PointSceneRT& uni, cons
     }
 }
 
+// ---- batched command (m3_batch_command on a batch with the per-sample section): one launch for a group of such handles that
+// share K, T and lanes.  blockIdx.y picks the handle's entry (BatchRolloutEntrySV, m3_internal.hpp; read-only); the entry's
+// scene_rt gives the uniform members, so handles with different dt / substeps share a launch and every trip count stays
+// wave-uniform per handle; the rows are the handle's own device table.  The same body instantiations as the single-handle
+// kernels above, the build picked by the GROUP's wavefront count: same bits.
+__global__ __launch_bounds__(64) void kb_rollout_point_sv(const BatchRolloutEntrySV* __restrict__ tab) {
+    const BatchRolloutEntrySV& e = tab[blockIdx.y];
+    int i;
+    if (!rollout_lane_sample(e.a, i)) return;
+    const PointSceneRT sc = point_scene_row_load(e.sc, e.rows, e.a.Kl, i);
+    rollout_point_body<true, -1, true, true>(e.a, sc, &e.wt);
+}
+template <int OCC>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void kb_rollout_point_sv_occ(
+    const BatchRolloutEntrySV* __restrict__ tab) {
+    const BatchRolloutEntrySV& e = tab[blockIdx.y];
+    int i;
+    if (!rollout_lane_sample(e.a, i)) return;
+    const PointSceneRT sc = point_scene_row_load(e.sc, e.rows, e.a.Kl, i);
+    rollout_point_body<true, -1, false, true>(e.a, sc, &e.wt);
+}
+
+// blocks: workgroups of ONE handle (all handles of the group have the same); n: handles
+void launch_rollout_point_sv_batch(const BatchRolloutEntrySV* tab, int blocks, int n, hipStream_t s) {
+    const dim3 grid(blocks, n), wg(64);
+    switch (rollout_point_build(blocks * n, false)) {
+        case BUILD_OCC3: hipLaunchKernelGGL(kb_rollout_point_sv_occ<3>, grid, wg, 0, s, tab); break;
+        case BUILD_OCC2: hipLaunchKernelGGL(kb_rollout_point_sv_occ<2>, grid, wg, 0, s, tab); break;
+        default: hipLaunchKernelGGL(kb_rollout_point_sv, grid, wg, 0, s, tab); break;
+    }
+}
+
 }  // namespace m3

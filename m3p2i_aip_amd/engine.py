@@ -737,11 +737,13 @@ class HipBatch(_CObject):
     ``command()``, a panda_env engine's automatic kernel form included; the batch holds no planner state, only the device
     workspace of its argument table (allocated here, for up to ``max_handles`` engines per call).
     ``panda_runtime=True`` (``M3_BATCH_PANDA_RUNTIME``) makes room for the larger table entries of panda_env engines with a
-    workspace of their own, tuned cost weights or a workspace per sample, which any other batch refuses."""
+    workspace of their own, tuned cost weights or a workspace per sample, which any other batch refuses.
+    ``point_runtime=True`` (``M3_BATCH_SECTION_POINT_ROLLOUT_SCENES``, ``m3_batch_create_sections``) makes room for the entries
+    of point_env engines with an arena per sample (``set_point_rollout_scenes``), which any other batch refuses."""
 
     _ptr, _destroy, _last_error = "_b", "m3_batch_destroy", "m3_batch_last_error"
 
-    def __init__(self, max_handles, device=0, panda_runtime=False):
+    def __init__(self, max_handles, device=0, panda_runtime=False, point_runtime=False):
         if not torch.cuda.is_available():
             raise L.M3Error("HipBatch needs a HIP device (torch.cuda.is_available() is False); there is no CPU fallback")
         self.lib = L.load()
@@ -750,7 +752,10 @@ class HipBatch(_CObject):
         self._b = C.c_void_p()
         torch.cuda.set_device(self.device)
         torch.zeros(1, device=self.device)  # make sure the HIP context exists
-        if panda_runtime:
+        if point_runtime:
+            sections = L.BATCH_SECTION_POINT_ROLLOUT_SCENES | (L.BATCH_SECTION_PANDA_RUNTIME if panda_runtime else 0)
+            self._ck(self.lib.m3_batch_create_sections(int(device), self.max_handles, sections, C.byref(self._b)))
+        elif panda_runtime:
             self._ck(self.lib.m3_batch_create_ex(int(device), self.max_handles, L.BATCH_PANDA_RUNTIME, C.byref(self._b)))
         else:
             self._ck(self.lib.m3_batch_create(int(device), self.max_handles, C.byref(self._b)))
@@ -778,7 +783,7 @@ class HipBatch(_CObject):
         return [e._action_out if e._action_out is not None else e.buffer(L.BUF_ACTION_OUT) for e in engines]
 
     def flags(self):
-        """The flags the batch was created with (``L.BATCH_PANDA_RUNTIME`` or 0)."""
+        """The sections the batch was created with (``L.BATCH_SECTION_*`` bits; ``L.BATCH_PANDA_RUNTIME`` is bit 1)."""
         flags = self.lib.m3_batch_flags(self._b)
         if flags < 0:
             self._ck(flags)
@@ -796,11 +801,14 @@ class HipEpisodes(_CObject):
     N-env world engine (an ``IsaacGymWrapper(num_envs=N)``'s) is episode e's 1-env world, planned by ``engines[e]``.
     ``specs``: one ``(task, goal, dyn_phase, suction, kp_suction)`` per episode, task a name or M3_TASK_* id, suction one of
     ``L.SUCTION_*``.  Each engine's ``set_action_out`` tensor is read here and must stay the same.  The set owns its
-    device state and pinned status words; a tick allocates nothing."""
+    device state and pinned status words; a tick allocates nothing.
+    ``point_runtime=True`` (``M3_EPISODES_ROLLOUT_SCENES``, ``m3_episodes_create_ex``) also takes planners with an arena per
+    sample (``set_point_rollout_scenes``), at create and at every tick; hand ``tick`` a ``HipBatch(..., point_runtime=True)``.
+    The world's rows step in the world engine's arena either way."""
 
     _ptr, _destroy, _last_error = "_eps", "m3_episodes_destroy", "m3_episodes_last_error"
 
-    def __init__(self, world, engines, specs, max_ticks, trace=False):
+    def __init__(self, world, engines, specs, max_ticks, trace=False, point_runtime=False):
         self.lib = L.load()
         self.world, self.engines = world, list(engines)
         self.n, self.max_ticks, self.trace_on = len(self.engines), int(max_ticks), bool(trace)
@@ -811,13 +819,24 @@ class HipEpisodes(_CObject):
             sp[i].goal[0], sp[i].goal[1] = float(goal[0]), float(goal[1])
             sp[i].dyn_phase, sp[i].suction, sp[i].kp_suction = int(phase), int(suction), float(kp)
         self._eps = C.c_void_p()
-        self._ck(self.lib.m3_episodes_create(world._h, arr, sp, self.n, self.max_ticks, int(self.trace_on), C.byref(self._eps)))
+        if point_runtime:
+            self._ck(self.lib.m3_episodes_create_ex(world._h, arr, sp, self.n, self.max_ticks, int(self.trace_on),
+                                                    L.EPISODES_ROLLOUT_SCENES, C.byref(self._eps)))
+        else:
+            self._ck(self.lib.m3_episodes_create(world._h, arr, sp, self.n, self.max_ticks, int(self.trace_on), C.byref(self._eps)))
         self._status = (L.EpisodeStatus * self.n)()
 
     def tick(self, batch):
         """One tick of every episode: pre kernel, one batched command of the running episodes' planners, post kernel,
         one synchronisation."""
         self._ck(self.lib.m3_episodes_tick(self._eps, batch._b))
+
+    def flags(self):
+        """The flags the set was created with (``L.EPISODES_ROLLOUT_SCENES`` or 0)."""
+        flags = self.lib.m3_episodes_flags(self._eps)
+        if flags < 0:
+            self._ck(flags)
+        return flags
 
     def begin(self):
         """The pre-command half of a tick whose commands the caller issues itself (a planner's first command)."""

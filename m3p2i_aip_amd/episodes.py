@@ -29,14 +29,17 @@ class _PlannerSide:
     """The planner side of one episode: tools/closed_loop.Tamp (scripts/reactive_tamp.py's REACTIVE_TAMP), built through
     the same module names."""
 
-    def __init__(self, cfg, panda_scenes=None):
+    def __init__(self, cfg, panda_scenes=None, point_scenes=None):
         from m3p2i_aip.planners.motion_planner import m3p2i
         from m3p2i_aip.planners.task_planner import task_planner
         import m3p2i_aip.utils.isaacgym_utils.isaacgym_wrapper as wrapper
         from m3p2i_aip.planners.motion_planner.cost_functions import Objective
         self.cfg = cfg
         # (panda_scenes: the `rollout_workspace_spread` rows of a run-time panda set, as Tamp passes them; None everywhere else)
+        # (point_scenes: the `rollout_arena_spread` rows of a point set with point_runtime, likewise)
         extra = {} if panda_scenes is None else dict(panda_scenes=panda_scenes)
+        if point_scenes is not None:
+            extra["point_scenes"] = point_scenes
         self.sim = wrapper.IsaacGymWrapper(cfg.isaacgym, cfg.env_type, num_envs=cfg.mppi.num_samples,
                                            viewer=False, device=cfg.mppi.device, cube_on_shelf=cfg.cube_on_shelf, **extra)
         self.objective = Objective(cfg)
@@ -107,14 +110,22 @@ def _apply_jitter(real, e, jitter):
 class PointEpisodeSet:
     """One set of episodes in lockstep: built by the constructor, tick 0 by start() (each planner's first command on its
     own), then tick() per tick; reports() when no episode runs any more (or at max_ticks).  items: [(config name,
-    overrides, config, jitter)] of one world (same dt, substeps, device)."""
+    overrides, config, jitter)] of one world (same dt, substeps, device).
+    point_runtime: episodes may ask for an arena per sample of their planner (`rollout_arena_spread`): each planner's K-env sim is
+    built with compat.rollout_point_scenes(cfg) as tools/closed_loop.Tamp builds it, so its tick-0 probe keeps the fused path and
+    the engine holds the rows from then on (m3_episodes_create_ex with M3_EPISODES_ROLLOUT_SCENES, a batch with
+    M3_BATCH_SECTION_POINT_ROLLOUT_SCENES).  Episodes with and without the key share the set."""
 
-    def __init__(self, items, max_ticks, trace=False):
+    def __init__(self, items, max_ticks, trace=False, point_runtime=False):
         import m3p2i_aip.utils.isaacgym_utils.isaacgym_wrapper as wrapper
         t0 = time.perf_counter()
         self.items, self.max_ticks, self.trace = list(items), int(max_ticks), bool(trace)
         cfgs = [cfg for _, _, cfg, _ in self.items]
-        self.sides = [_PlannerSide(cfg) for cfg in cfgs]
+        self.point_runtime = bool(point_runtime)
+        if self.point_runtime:
+            self.sides = [_PlannerSide(cfg, point_scenes=compat.rollout_point_scenes(cfg)) for cfg in cfgs]
+        else:
+            self.sides = [_PlannerSide(cfg) for cfg in cfgs]
         c0, n = cfgs[0], len(self.items)
         # each episode's world arena: its `point_scene` with its `world_point_scene` on top.  All the same: the single-arena
         # world as before; otherwise one arena per row (m3_set_point_scene_rows) -- the planners keep their own `point_scene`
@@ -137,8 +148,14 @@ class PointEpisodeSet:
             g = side.task_planner.curr_goal.float().cpu().reshape(-1)
             specs.append((cfg.task, (float(g[0]), float(g[1])), phases[e], _suction_mode(cfg), float(cfg.kp_suction)))
         real._engine.use_torch_stream()
-        self.eps = HipEpisodes(real._engine, [s.motion_planner._engine for s in self.sides], specs, self.max_ticks, trace=self.trace)
-        self.batch = HipBatch(n, device=torch.device(c0.mppi.device).index or 0)
+        engines = [s.motion_planner._engine for s in self.sides]
+        dev = torch.device(c0.mppi.device).index or 0
+        if self.point_runtime:
+            self.eps = HipEpisodes(real._engine, engines, specs, self.max_ticks, trace=self.trace, point_runtime=True)
+            self.batch = HipBatch(n, device=dev, point_runtime=True)
+        else:
+            self.eps = HipEpisodes(real._engine, engines, specs, self.max_ticks, trace=self.trace)
+            self.batch = HipBatch(n, device=dev)
         self.lat = []
         self.build_s = time.perf_counter() - t0
         self.loop_s = 0.0
@@ -208,27 +225,30 @@ class PointEpisodeSet:
             side.close()
 
 
-def build_set(episodes, max_ticks=800, trace=False):
-    """A PointEpisodeSet of episodes [(config name, overrides, jitter)] that share one world."""
+def build_set(episodes, max_ticks=800, trace=False, point_runtime=False):
+    """A PointEpisodeSet of episodes [(config name, overrides, jitter)] that share one world (point_runtime: as
+    run_point_episodes)."""
     compat.install(force_standins=True)
     items = []
     for idx, (cn, ov, jitter) in enumerate(episodes):
         cfg = compat.make_config(cn, list(ov))
         if cfg.env_type != "point_env":
             raise ValueError(f"run_point_episodes: episode {idx} is {cfg.env_type} (point_env only)")
-        if getattr(cfg, "rollout_arena_spread", None):
+        if not point_runtime and getattr(cfg, "rollout_arena_spread", None):
             raise ValueError(f"run_point_episodes: episode {idx} asks for an arena per sample (rollout_arena_spread), which the "
                              "batched command does not run (m3_set_point_rollout_scenes: m3_command only); use closed_loop.run")
         items.append((cn, list(ov), cfg, jitter))
-    return PointEpisodeSet(items, max_ticks, trace)
+    return PointEpisodeSet(items, max_ticks, trace, point_runtime=point_runtime)
 
 
-def run_point_episodes(episodes, max_ticks=800, trace=False):
+def run_point_episodes(episodes, max_ticks=800, trace=False, point_runtime=False):
     """episodes: [(config name, overrides, jitter)] as closed_loop.run takes them (jitter may be None).  Returns one report
     per episode, in order: the dict closed_loop.run returns (ticks, success, sim_time_s, timeline, final_pos_error,
     dyn_obs_collision_ticks, trace if asked), with the set's tick_ms_p50 / tick_ms_p99 in place of the per-episode
     command_ms_*, and build_s (planner and world construction) / loop_s (ticks 1..) of the set.  Episodes whose worlds
-    differ (dt, substeps, device) run as separate sets, one after the other."""
+    differ (dt, substeps, device) run as separate sets, one after the other.
+    point_runtime=True: episodes may carry `rollout_arena_spread` (an arena per sample of the planner's rollout); without it
+    they raise ValueError as before."""
     if int(max_ticks) <= 0:
         raise ValueError("run_point_episodes: max_ticks must be > 0")
     compat.install(force_standins=True)
@@ -237,14 +257,14 @@ def run_point_episodes(episodes, max_ticks=800, trace=False):
         cfg = compat.make_config(cn, list(ov))
         if cfg.env_type != "point_env":
             raise ValueError(f"run_point_episodes: episode {idx} is {cfg.env_type} (point_env only)")
-        if getattr(cfg, "rollout_arena_spread", None):
+        if not point_runtime and getattr(cfg, "rollout_arena_spread", None):
             raise ValueError(f"run_point_episodes: episode {idx} asks for an arena per sample (rollout_arena_spread), which the "
                              "batched command does not run (m3_set_point_rollout_scenes: m3_command only); use closed_loop.run")
         key = (float(cfg.isaacgym.dt), int(cfg.isaacgym.substeps), cfg.mppi.device)
         groups.setdefault(key, []).append((idx, (cn, list(ov), cfg, jitter)))
     out = [None] * len(episodes)
     for members in groups.values():
-        es = PointEpisodeSet([m for _, m in members], int(max_ticks), bool(trace))
+        es = PointEpisodeSet([m for _, m in members], int(max_ticks), bool(trace), point_runtime=point_runtime)
         try:
             es.run()
             reps = es.reports()

@@ -744,9 +744,10 @@ class MPPI():
 
 _BATCHES = {}   # device index -> the HipBatch command_batch uses (grown when a call lists more planners)
 _BATCHES_PANDA_RUNTIME = {}   # ... with panda_runtime=True: a second batch per device, the default one is not re-created
+_BATCHES_POINT_RUNTIME = {}   # ... with point_runtime=True (with or without panda_runtime), keyed (device index, panda_runtime)
 
 
-def command_batch(planners, states, panda_runtime=False):
+def command_batch(planners, states, panda_runtime=False, point_runtime=False):
     """``[p.command(s) for p, s in zip(planners, states)]`` with one batched library call (m3_batch_command) per
     environment in the list: the planners' rollouts and updates run in one launch per group of planners that use the
     same kernel instance (point_env and panda_env planners alike; a list that mixes them makes one call for each).  Each
@@ -757,7 +758,10 @@ def command_batch(planners, states, panda_runtime=False):
     collectives installed raise ValueError (the library refuses the rest, e.g. panda_env with K > 4096, with M3Error).
     ``panda_runtime=True``: panda_env planners with a workspace of their own, panda cost weights of their own or a workspace
     per sample are batched too (a batch created with M3_BATCH_PANDA_RUNTIME, kept next to the default one); without it they
-    raise ValueError as before."""
+    raise ValueError as before.
+    ``point_runtime=True``: point_env planners with an arena per sample (set_rollout_scenes / a wrapper with point_scenes) are
+    batched too (a batch created with M3_BATCH_SECTION_POINT_ROLLOUT_SCENES, a cached batch of its own per device); without
+    it they raise ValueError as before."""
     planners, states = list(planners), list(states)
     if len(planners) != len(states):
         raise ValueError("command_batch: one state per planner")
@@ -766,7 +770,7 @@ def command_batch(planners, states, panda_runtime=False):
             raise ValueError(f"command_batch: planner {i} runs in step mode (user dynamics / running_cost callables)")
         if p.world_size > 1 or p.collective is not None:
             raise ValueError(f"command_batch: planner {i} is sharded or has collectives installed")
-        if p.has_rollout_scenes:
+        if not point_runtime and p.has_rollout_scenes:
             raise ValueError(f"command_batch: planner {i} has an arena per sample (set_rollout_scenes / a wrapper with "
                              "point_scenes): m3_batch_command does not run those, use planner.command")
         if not panda_runtime and getattr(p, "has_panda_rollout_scenes", False):
@@ -800,13 +804,19 @@ def command_batch(planners, states, panda_runtime=False):
         batched.append(p._engine)
     if batched:
         dev = batched[0].device.index or 0
-        cache = _BATCHES_PANDA_RUNTIME if panda_runtime else _BATCHES
-        b = cache.get(dev)
+        cache = _BATCHES_POINT_RUNTIME if point_runtime else _BATCHES_PANDA_RUNTIME if panda_runtime else _BATCHES
+        key = (dev, bool(panda_runtime)) if point_runtime else dev
+        b = cache.get(key)
         if b is None or b.max_handles < len(batched):
             if b is not None:
                 b.close()
-            b = cache[dev] = HipBatch(max(64, len(batched)), device=dev, panda_runtime=True) if panda_runtime else \
-                HipBatch(max(64, len(batched)), device=dev)
+            if point_runtime:
+                b = HipBatch(max(64, len(batched)), device=dev, panda_runtime=bool(panda_runtime), point_runtime=True)
+            elif panda_runtime:
+                b = HipBatch(max(64, len(batched)), device=dev, panda_runtime=True)
+            else:
+                b = HipBatch(max(64, len(batched)), device=dev)
+            cache[key] = b
         for env in sorted({e.cfg.env_type for e in batched}):     # (the library takes one environment per call)
             b.command([e for e in batched if e.cfg.env_type == env])
     return outs

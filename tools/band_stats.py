@@ -95,13 +95,13 @@ def world_arena_of(scenario, episode, spread):
     return dict(box_m=D["box_m"] * fm, box_I=D["box_I"] * fm, box_mu_g=D["box_mu_g"] * fg, mu_rb=D["mu_rb"] * fr)
 
 
-def batched_episode_list(pairs, n=20, world_arena_spread=0.0):
+def batched_episode_list(pairs, n=20, world_arena_spread=0.0, extra=()):
     """What band_batched runs: [(scenario, size, episode, jitter)] and the [(config name, overrides, jitter)] of
-    run_point_episodes, in the same order."""
+    run_point_episodes, in the same order.  extra: overrides of every episode (POINT_RUNTIME_KEYS)."""
     items = [(sc, size, e, jitter_of(sc, e)) for sc, size in pairs for e in range(n)]
     eps = []
     for sc, size, e, j in items:
-        ov = overrides(sc, size)
+        ov = overrides(sc, size) + list(extra)
         arena = world_arena_of(sc, e, world_arena_spread)
         if arena:
             ov.append("world_point_scene={" + ", ".join(f"{k}: {v!r}" for k, v in arena.items()) + "}")
@@ -164,13 +164,14 @@ def _summary(scenario, n, size, runs):
                 command_ms_p50=stats([r["command_ms_p50"] for r in runs]), runs=runs)
 
 
-def band_batched(pairs, n=20, max_sim_time_s=40.0, world_arena_spread=0.0):
+def band_batched(pairs, n=20, max_sim_time_s=40.0, world_arena_spread=0.0, extra=(), runtime=False):
     """episodes() of every (scenario, size) in `pairs` at once: all n * len(pairs) episodes in lockstep
     (m3p2i_aip_amd.episodes.run_point_episodes).  Returns {(scenario, size): the dict episodes() returns}; each run's
-    command_ms_p50 is the set's tick time."""
+    command_ms_p50 is the set's tick time.  runtime: the set created for planners with an arena per sample (point_runtime=True),
+    which takes `rollout_arena_spread` among the `extra` overrides of every episode."""
     from m3p2i_aip_amd.episodes import run_point_episodes
-    items, eps = batched_episode_list(pairs, n, world_arena_spread)
-    reps = run_point_episodes(eps, max_ticks=int(max_sim_time_s / 0.05))
+    items, eps = batched_episode_list(pairs, n, world_arena_spread, extra)
+    reps = run_point_episodes(eps, max_ticks=int(max_sim_time_s / 0.05), point_runtime=bool(runtime))
     out = {}
     for (sc, size, e, j), r in zip(items, reps):
         out.setdefault((sc, size), []).append(dict(episode=e, jitter=j, success=r["success"], final_pos_error_m=r["final_pos_error"],
@@ -188,6 +189,9 @@ def episodes_batched(scenario, n=20, max_sim_time_s=40.0, size="baseline"):
 
 # config keys `panda` takes as overrides on the command line (e.g. 'world_panda_scene={cube_m: 0.2}'); batched: with --runtime
 PANDA_RUNTIME_KEYS = ("panda_scene", "world_panda_scene", "panda_cost_weights", "rollout_workspace_spread")
+# config keys the point scenarios take as overrides on the command line ('rollout_arena_spread={spread: 0.3, seed: 1}': an arena
+# per sample of every planner); with --batched --runtime only (the lockstep set created for such planners)
+POINT_RUNTIME_KEYS = ("rollout_arena_spread",)
 
 
 def panda_episodes(n=20, overrides=("mppi.num_samples=4000", "mppi.horizon=20"), ticks=600):
@@ -227,7 +231,7 @@ def panda_episodes_batched(n=20, overrides=("mppi.num_samples=4000", "mppi.horiz
 
 
 def main(argv):
-    n, out, names, size, batched, spread, runtime, extra = 20, None, [], "baseline", False, 0.0, False, []
+    n, out, names, size, batched, spread, runtime, extra, point_extra = 20, None, [], "baseline", False, 0.0, False, [], []
     it = iter(argv)
     for a in it:
         if a == "--batched":
@@ -236,6 +240,8 @@ def main(argv):
             runtime = True
         elif a.split("=", 1)[0] in PANDA_RUNTIME_KEYS and "=" in a:
             extra.append(a)
+        elif a.split("=", 1)[0] in POINT_RUNTIME_KEYS and "=" in a:
+            point_extra.append(a)
         elif a == "--n":
             n = int(next(it))
         elif a == "--json":
@@ -252,7 +258,9 @@ def main(argv):
     if spread and not batched:
         raise SystemExit("--world-arena-spread: with --batched (the serial runs keep the nominal world)")
     if runtime and not batched:
-        raise SystemExit("--runtime: with --batched (the run-time set of the lockstep panda episodes)")
+        raise SystemExit("--runtime: with --batched (the run-time sets of the lockstep episodes)")
+    if point_extra and not (batched and runtime):
+        raise SystemExit(f"{point_extra[0].split('=', 1)[0]}: with --batched --runtime only (the serial runs: tools/rollout_scenes_bench.py)")
     if extra and batched and not runtime:
         raise SystemExit(f"{extra[0].split('=', 1)[0]}: with --batched, the run-time set only (--runtime)")
     allband = json.load(open(os.path.join(ROOT, "tests", "golden", "behaviour_band.json")))
@@ -276,7 +284,8 @@ def main(argv):
             if out:
                 json.dump(res, open(out, "w"), indent=1)
             return
-    pre = band_batched([(sc, size) for sc in names or list(SCENARIOS)], n, world_arena_spread=spread) if batched else {}
+    pre = band_batched([(sc, size) for sc in names or list(SCENARIOS)], n, world_arena_spread=spread, extra=point_extra,
+                       runtime=runtime) if batched else {}
     for sc in names or list(SCENARIOS):
         r = pre[(sc, size)] if batched else episodes(sc, n, size=size)
         r["logged"] = {k: band[sc][k] for k in ("final_pos_error_m", "task_time_s", "dyn_obs_collisions")}

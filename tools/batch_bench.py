@@ -17,6 +17,13 @@ of 0.3 over the workspaces as tools/panda_rollout_scenes_bench.py: kb_rollout_pa
 the ratios of the non-literal kinds' batched time to the literal one's.  Two controls do the literal handles' work, bit for
 bit, on the other kernels: `weighted_same_work` (the weighted instance forced at the default weights) and
 `per_sample_same_work` (K rows of the default workspace) -- what the kernels cost, apart from what the tuned handles meet.
+
+The `*_sv` configurations (point_env, a batch created with M3_BATCH_SECTION_POINT_ROLLOUT_SCENES; not part of the default list
+either) measure n planners with an arena per sample: `per_sample` (scenes.spread_point_scenes rows, spread 0.3, a seed per
+planner: kb_rollout_point_sv*), batched against n back-to-back m3_command calls of the same handles, beside `scene` (the
+single-arena run-time-scene group of the same n, K, T: the run-time-scene instance forced on at the default arena) and the
+control `per_sample_same_work` (K rows of the default arena: the `scene` handles' work bit for bit, plus the 38 row loads per
+lane).
 """
 import argparse
 import ctypes as C
@@ -50,6 +57,8 @@ PANDA_CONFIGS = {
 PANDA_RT_CONFIGS = {"shipped_pick_rt": "shipped_pick", "c4_reach_rt": "c4_reach", "c4_pick_rt": "c4_pick"}
 RT_WEIGHTS = dict(reach_dist=20.0, reach_tilt=5.0, pick_goal=7.5, pick_ori=25.0, collision=500.0, shelf_force=3.0, place_grip=3.0)
 RT_SPREAD = 0.3
+# point_env planners with an arena per sample: name -> the CONFIGS entry whose worlds it takes
+POINT_SV_CONFIGS = {"c2_push_sv": "c2_push", "shipped_push_sv": "shipped_push"}
 
 
 def panda_world_of(task_phase, K, T, episode, device):
@@ -96,6 +105,9 @@ def measure(name, iters, warmup, repeats):
     if name in PANDA_RT_CONFIGS:
         kinds = ("literal", "weighted", "per_sample", "weighted_same_work", "per_sample_same_work")
         name_worlds = PANDA_RT_CONFIGS[name]
+    elif name in POINT_SV_CONFIGS:
+        kinds = ("scene", "per_sample", "per_sample_same_work")
+        name_worlds = POINT_SV_CONFIGS[name]
     else:
         name_worlds = name
     if name_worlds in PANDA_CONFIGS:
@@ -125,19 +137,32 @@ def measure(name, iters, warmup, repeats):
                 by_kind.setdefault(kind, []).append(e)
         engs = by_kind["literal"]
     else:
-        scenario, task, goal, K, T, mm, ns = CONFIGS[name]
+        scenario, task, goal, K, T, mm, ns = CONFIGS[name_worlds]
         pk = dict(u_min=[-3, -3], u_max=[3, 3], noise_sigma_diag=[3, 3], lambda_=0.5)
         n_max = max(ns)
         knots = sampling.halton_knots(K, T, 2, 4, 2, 0, K, scramble="none")
-        for e_i in range(n_max):
-            e = HipEngine(make_config(K=K, T=T, nu=2, multi_modal=mm, **pk))
-            e.set_noise_knots(knots, 2, 0.5)
-            e.relabel_samples()
-            e.set_objective(task, goal)
-            e.set_world_point_raw(world_of(scenario, e_i))
-            engs.append(e)
+        by_kind = {}
+        for kind in kinds or (None,):
+            for e_i in range(n_max):
+                e = HipEngine(make_config(K=K, T=T, nu=2, multi_modal=mm, **pk))
+                e.set_noise_knots(knots, 2, 0.5)
+                e.relabel_samples()
+                e.set_objective(task, goal)
+                e.set_world_point_raw(world_of(scenario, e_i))
+                if kind == "scene":
+                    e.set_point_scene_instance(1)
+                elif kind == "per_sample":
+                    from m3p2i_aip_amd.scenes import spread_point_scenes
+                    e.set_point_rollout_scenes(spread_point_scenes(K, RT_SPREAD, seed=1 + e_i, nominal_rows=(0, K // 2, K - 1)))
+                elif kind == "per_sample_same_work":
+                    e.set_point_rollout_scenes([None] * K)
+                by_kind.setdefault(kind, []).append(e)
+        engs = by_kind[kinds[0] if kinds else None]
     lib = engs[0].lib
-    batch = HipBatch(n_max, panda_runtime=True) if kinds else HipBatch(n_max)
+    if name in POINT_SV_CONFIGS:
+        batch = HipBatch(n_max, point_runtime=True)
+    else:
+        batch = HipBatch(n_max, panda_runtime=True) if kinds else HipBatch(n_max)
     stream = torch.cuda.current_stream()
 
     def timed(fn):
@@ -179,10 +204,10 @@ def measure(name, iters, warmup, repeats):
                          panda_lanes_per_sample=sorted({e.panda_lanes_per_sample_used() for e in sel}) if name_worlds in PANDA_CONFIGS else None,
                          batched_repeats_ms=[round(x, 4) for x in b_all], back_to_back_repeats_ms=[round(x, 4) for x in s_all],
                          wall_s=round(time.perf_counter() - t0, 2)))
-    if kinds:   # each non-literal kind's batched time over the literal batch of the same worlds and n
-        lit = {r["n"]: r["batched_ms"] for r in rows if r["kind"] == "literal"}
+    if kinds:   # each other kind's batched time over the first kind's batch (literal / scene) of the same worlds and n
+        lit = {r["n"]: r["batched_ms"] for r in rows if r["kind"] == kinds[0]}
         for r in rows:
-            r["batched_over_literal"] = round(r["batched_ms"] / lit[r["n"]], 3)
+            r["batched_over_" + kinds[0]] = round(r["batched_ms"] / lit[r["n"]], 3)
         engs = [e for es in by_kind.values() for e in es]
     batch.close()
     for e in engs:

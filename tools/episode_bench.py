@@ -3,12 +3,19 @@ of the 8-scenario band (tools/band_stats.py) per size, batched against serial, p
 
     python tools/episode_bench.py [--json out.json] [--n 60] [--serial-n 4] [--ticks 100]
     python tools/episode_bench.py --arena-rows [--json out.json] [--rows 64] [--repeats 5] [--ticks 8]
+    python tools/episode_bench.py --rollout-arenas [--json out.json] [--rows 64] [--repeats 5] [--ticks 8]
 
 --arena-rows: what an arena per world row costs (m3_set_point_scene_rows, k_episodes_post_sv).  Three sets of --rows case2 push
 episodes at BASELINE size whose planners all plan in the reference's arena (the batched command is the same work in all three):
 `single` -- one custom arena on the world handle (m3_set_point_scene: k_episodes_post_s, the kernel of the parent commit),
 `rows_same` -- the same arena as --rows identical rows, `rows_distinct` -- --rows different arenas.  The variants alternate
 inside each of --repeats repeats of --ticks ticks; p50 ms per m3_episodes_tick of each and the ratios to `single`.
+
+--rollout-arenas: what an arena per SAMPLE of every planner costs in lockstep (m3_episodes_create_ex with
+M3_EPISODES_ROLLOUT_SCENES, kb_rollout_point_sv*).  Two sets of --rows case2 push episodes at BASELINE size in the
+nominal world, both built with point_runtime=True: `nominal` -- every planner in the reference's arena (the batched push
+instance), `rollout_arenas` -- every planner with `rollout_arena_spread={spread: 0.3, seed: 1 + e}` (one per-sample group).  The
+two alternate inside each of --repeats repeats of --ticks ticks; p50 ms per m3_episodes_tick of each and the ratio.
 
 The serial band time is measured on --serial-n episodes per scenario and scaled to --n (the serial loop's cost is linear
 in the number of episodes); construction of the serial runs is timed by building their planners alone.
@@ -90,6 +97,40 @@ def arena_rows_times(n=64, repeats=5, ticks=8):
             es.close()
 
 
+def rollout_arenas_times(n=64, repeats=5, ticks=8, spread=0.3):
+    import band_stats as bs
+    from m3p2i_aip_amd.episodes import build_set
+    sc = "case2_halton_push_coll"
+    plans = dict(nominal=lambda e: [], rollout_arenas=lambda e: ["rollout_arena_spread={spread: %r, seed: %d}" % (spread, 1 + e)])
+    sets = {}
+    try:
+        for name, extra in plans.items():
+            eps = [("config_point", bs.overrides(sc, "baseline") + extra(e), bs.jitter_of(sc, e % 60)) for e in range(n)]
+            es = sets[name] = build_set(eps, max_ticks=repeats * ticks + 4, point_runtime=True)
+            es.start()
+            assert all(s.motion_planner._engine.point_rollout_scenes_set() == (name == "rollout_arenas") for s in es.sides)
+            for _ in range(3):           # warm-up ticks, not counted
+                es.tick()
+            es.lat.clear()
+        for _ in range(repeats):         # the two sets interleaved inside every repeat
+            for es in sets.values():
+                for _ in range(ticks):
+                    if es.running:
+                        es.tick()
+        out = dict(n=n, K=2000, T=30, spread=spread, repeats=repeats, ticks_per_repeat=ticks, tick_ms_p50={}, tick_ms_min={}, ticks={},
+                   rollout_launches={k: es.batch.launches()[0] for k, es in sets.items()})
+        for name, es in sets.items():
+            lat = np.array(es.lat) * 1e3
+            out["tick_ms_p50"][name] = float(np.percentile(lat, 50))
+            out["tick_ms_min"][name] = float(lat.min())
+            out["ticks"][name] = len(lat)
+        out["ratio_to_nominal"] = out["tick_ms_p50"]["rollout_arenas"] / out["tick_ms_p50"]["nominal"]
+        return out
+    finally:
+        for es in sets.values():
+            es.close()
+
+
 def serial_band(size, n):
     import band_stats as bs
     import closed_loop
@@ -126,6 +167,16 @@ def main(argv):
     if "--arena-rows" in argv:
         opt = dict(zip(argv, argv[1:]))
         res = dict(arena_rows=arena_rows_times(int(opt.get("--rows", 64)), int(opt.get("--repeats", 5)), int(opt.get("--ticks", 8))))
+        print(json.dumps(res), flush=True)
+        if opt.get("--json"):
+            os.makedirs(os.path.dirname(opt["--json"]) or ".", exist_ok=True)
+            json.dump(res, open(opt["--json"], "w"), indent=1)
+        return
+    if "--rollout-arenas" in argv:
+        from m3p2i_aip_amd import _lib as L
+        opt = dict(zip(argv, argv[1:]))
+        res = dict(build_id=L.load().m3_build_id().decode(),
+                   rollout_arenas=rollout_arenas_times(int(opt.get("--rows", 64)), int(opt.get("--repeats", 5)), int(opt.get("--ticks", 8))))
         print(json.dumps(res), flush=True)
         if opt.get("--json"):
             os.makedirs(os.path.dirname(opt["--json"]) or ".", exist_ok=True)

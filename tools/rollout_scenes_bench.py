@@ -18,6 +18,9 @@ seeds: with the nominal planner, and with `rollout_arena_spread={spread: --plann
 error per arm as JSON: evidence, not an assertion.
 
     python tools/rollout_scenes_bench.py --episodes 20 [--world-spread 0.5] [--planner-spread 0.5] [--ticks 600] [--json out.json]
+
+`--batched` (with --episodes): both arms in lockstep, one set of 2 n episodes (m3p2i_aip_amd.episodes.run_point_episodes with
+point_runtime=True: m3_episodes_create_ex, a batch with the per-sample section) -- the episodes of the serial mode, bit for bit.
 """
 import argparse
 import json
@@ -112,9 +115,18 @@ def episodes(a):
     sc = "case2_halton_push_coll"
     arms = {"nominal": [], "randomised": ["rollout_arena_spread={spread: %r, seed: 1}" % a.planner_spread]}
     rows = {name: [] for name in arms}
-    for e in range(a.episodes):
-        arena = world_arena(e, a.world_spread)
-        world = "world_point_scene={" + ", ".join(f"{k}: {v!r}" for k, v in arena.items()) + "}"
+    arenas = [world_arena(e, a.world_spread) for e in range(a.episodes)]
+    worlds = ["world_point_scene={" + ", ".join(f"{k}: {v!r}" for k, v in arena.items()) + "}" for arena in arenas]
+    if a.batched:      # both arms in lockstep: one set of 2 * episodes episodes (m3p2i_aip_amd.episodes, point_runtime=True)
+        from m3p2i_aip_amd.episodes import run_point_episodes
+        order = [(name, e) for e in range(a.episodes) for name in arms]
+        reps = run_point_episodes([("config_point", bs.overrides(sc, "default") + [worlds[e]] + arms[name], bs.jitter_of(sc, 1 + e))
+                                   for name, e in order], max_ticks=a.ticks, point_runtime=True)
+        for (name, e), r in zip(order, reps):
+            rows[name].append(dict(episode=e, success=bool(r["success"]), sim_time_s=r["sim_time_s"], final_pos_error=r["final_pos_error"],
+                                   command_ms_p50=r["tick_ms_p50"], world=arenas[e]))
+    for e in range(0 if a.batched else a.episodes):
+        arena, world = arenas[e], worlds[e]
         for name, extra in arms.items():                # the same seeds (jitter, world) for both arms
             r = closed_loop.run("config_point", bs.overrides(sc, "default") + [world] + extra, ticks=a.ticks, jitter=bs.jitter_of(sc, 1 + e))
             rows[name].append(dict(episode=e, success=bool(r["success"]), sim_time_s=r["sim_time_s"], final_pos_error=r["final_pos_error"],
@@ -128,7 +140,7 @@ def episodes(a):
                              final_pos_error_max=float(max(r["final_pos_error"] for r in rs)),
                              command_ms_p50_median=float(np.median([r["command_ms_p50"] for r in rs])))
     return dict(tool="rollout_scenes_bench", mode="episodes", build_id=L.load().m3_build_id().decode(),
-                device=torch.cuda.get_device_name(0), scenario=sc, ticks=a.ticks, world_spread=a.world_spread,
+                device=torch.cuda.get_device_name(0), scenario=sc, ticks=a.ticks, world_spread=a.world_spread, batched=bool(a.batched),
                 planner_spread=a.planner_spread, summary=summary, episodes=rows)
 
 
@@ -143,6 +155,8 @@ def main():
     ap.add_argument("--world-spread", type=float, default=0.5)
     ap.add_argument("--planner-spread", type=float, default=0.5)
     ap.add_argument("--ticks", type=int, default=600)
+    ap.add_argument("--batched", action="store_true",
+                    help="--episodes: both arms in lockstep (one set; command_ms_p50 is then the set's tick time)")
     a = ap.parse_args()
     out = episodes(a) if a.episodes else timing(a)
     line = json.dumps(out)
