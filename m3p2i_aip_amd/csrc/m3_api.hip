@@ -13,6 +13,7 @@
 
 #include "m3_internal.hpp"
 #include "batch_table_layout.hpp"
+#include "point_views.hpp"
 #include "panda_episode_lane.hpp"
 #include "panda_episode_tables.hpp"
 #include "point_scene_rows.hpp"
@@ -1284,10 +1285,8 @@ extern "C" int m3_set_world_point(m3_handle* h, const m3_point_world* w) {
     for (int b = 0; b < 2; ++b) {
         const float* r = src[b];
         float* p = o + 4 + b * 7;
-        const float qz = r[2], qw = r[3];
         p[0] = r[0]; p[1] = r[1];
-        p[2] = 1.0f - 2.0f * (qz * qz);  // yaw from the (0,0,qz,qw) quaternion
-        p[3] = 2.0f * (qz * qw);
+        yaw_from_quat(r[2], r[3], &p[2], &p[3]);  // yaw from the (0,0,qz,qw) quaternion
         p[4] = r[4]; p[5] = r[5]; p[6] = r[6];
     }
     h->world0_bound = nullptr;

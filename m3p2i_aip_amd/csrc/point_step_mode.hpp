@@ -3,6 +3,7 @@
 #pragma once
 #include "m3_internal.hpp"
 #include "episode_lane.hpp"
+#include "point_views.hpp"
 
 namespace m3 {
 
@@ -27,19 +28,6 @@ __device__ __forceinline__ void soa_store(float* wd, int Kl, int i, const PointW
     p[18 * Kl] = w.fRx; p[19 * Kl] = w.fRy; p[20 * Kl] = w.fBx; p[21 * Kl] = w.fBy;
     p[22 * Kl] = w.fcDx; p[23 * Kl] = w.fcDy; p[24 * Kl] = w.fcBx; p[25 * Kl] = w.fcBy;
     p[26 * Kl] = w.fcRx; p[27 * Kl] = w.fcRy;
-}
-
-__device__ __forceinline__ void write_body13(float* r, float x, float y, float c, float s,
-                                             float vx, float vy, float wz) {
-    // yaw (c, s) -> quaternion (0, 0, sin(th/2), cos(th/2)) with cos(th/2) >= 0
-    float qw = sqrtf(fmaxf(0.5f * (1.0f + c), 0.0f));
-    float qz;
-    if (qw > 1e-4f) qz = s / (2.0f * qw);
-    else { qz = 1.0f; qw = 0.0f; }
-    r[0] = x; r[1] = y;  // r[2] (z) is left as set at init
-    r[3] = 0.0f; r[4] = 0.0f; r[5] = qz; r[6] = qw;
-    r[7] = vx; r[8] = vy; r[9] = 0.0f;
-    r[10] = 0.0f; r[11] = 0.0f; r[12] = wz;
 }
 
 // SoA world of environment i -> the wrapper's views (what a refresh_*_tensor call of Isaac Gym does)

@@ -174,10 +174,10 @@ __device__ __forceinline__ void pull_env(const SimViews& v, float* wd, int Kl, i
     for (int b = 0; b < 2; ++b) {
         const float* r = v.root_state + ((size_t)i * v.n_actors + (b == 0 ? v.box_actor : v.dyn_actor)) * 13;
         const int o = 4 + b * 7;
-        const float qz = r[5], qw = r[6];
+        float c, s;
+        yaw_from_quat(r[5], r[6], &c, &s);
         p[(o + 0) * Kl] = r[0]; p[(o + 1) * Kl] = r[1];
-        p[(o + 2) * Kl] = 1.0f - 2.0f * (qz * qz);
-        p[(o + 3) * Kl] = 2.0f * (qz * qw);
+        p[(o + 2) * Kl] = c; p[(o + 3) * Kl] = s;
         p[(o + 4) * Kl] = r[7]; p[(o + 5) * Kl] = r[8]; p[(o + 6) * Kl] = r[12];
     }
 }

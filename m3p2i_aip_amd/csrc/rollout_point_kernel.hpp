@@ -19,6 +19,7 @@
 
 #include "m3_internal.hpp"
 #include "noise_stream.hpp"
+#include "point_views.hpp"
 #include "wave_min.hpp"
 
 namespace m3 {
@@ -36,12 +37,10 @@ __device__ __forceinline__ void load_world_from_sim(const float* dof, const floa
                                                     int dyn, PointWorld& w) {
     w.rx = dof[0]; w.ry = dof[2]; w.rvx = dof[1]; w.rvy = dof[3];
     const float* r = root + (size_t)box * 13;
-    float qz = r[5], qw = r[6];
-    w.B.x = r[0]; w.B.y = r[1]; w.B.c = 1.0f - 2.0f * (qz * qz); w.B.s = 2.0f * (qz * qw);
+    w.B.x = r[0]; w.B.y = r[1]; yaw_from_quat(r[5], r[6], &w.B.c, &w.B.s);
     w.B.vx = r[7]; w.B.vy = r[8]; w.B.w = r[12];
     r = root + (size_t)dyn * 13;
-    qz = r[5]; qw = r[6];
-    w.D.x = r[0]; w.D.y = r[1]; w.D.c = 1.0f - 2.0f * (qz * qz); w.D.s = 2.0f * (qz * qw);
+    w.D.x = r[0]; w.D.y = r[1]; yaw_from_quat(r[5], r[6], &w.D.c, &w.D.s);
     w.D.vx = r[7]; w.D.vy = r[8]; w.D.w = r[12];
     w.fcDx = w.fcDy = w.fcBx = w.fcBy = w.fcRx = w.fcRy = 0.0f;
 }

@@ -164,7 +164,11 @@ def test_wrapper_getters_and_step(oracle):
     np.testing.assert_array_equal(box[:, :2], worlds[:, 7:9])
     np.testing.assert_allclose(box[:, 2], 0.05)
     q = sim.get_actor_orientation_by_name("box").cpu().numpy()
-    np.testing.assert_allclose(2 * q[:, 2] * q[:, 3], worlds[:, 10], atol=1e-6)   # sin(yaw)
+    from tests import point_views_ref
+    assert not q[:, :2].any()
+    c, s = point_views_ref.yaw_of_quat(q[:, 2], q[:, 3])                          # (cos yaw, sin yaw) of the view, float64
+    np.testing.assert_allclose(c, worlds[:, 9], rtol=0, atol=1e-6)
+    np.testing.assert_allclose(s, worlds[:, 10], rtol=0, atol=1e-6)
     f = sim.get_actor_contact_forces_by_name("dyn-obs", "box").cpu().numpy()
     np.testing.assert_array_equal(f[:, :2], worlds[:, oracle.W_FC_D:oracle.W_FC_D + 2])
     link = sim.get_actor_link_by_name("point_robot", "link_y").cpu().numpy()
