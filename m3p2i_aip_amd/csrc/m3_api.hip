@@ -799,41 +799,65 @@ extern "C" int m3_set_avoid_dyn_obs(m3_handle* h, int on) {
     return M3_OK;
 }
 
-// ---- the point_env cost weights (extension; per-handle state like the objective: no allocation, no synchronisation) ----
+static const char* env_only_text(int env) { return env == M3_ENV_POINT ? ": point_env only" : ": panda_env only"; }
+
+// ---- the tri-state instance switches of both environments (m3_set_weighted_cost_instance, m3_set_point_scene_instance and
+// their panda twins): -1 by `by` (the handle's weights or values), 0 / 1 forced ----
+static int set_instance(m3_handle* h, int env, int m3_handle::*member, int on, const char* who, const char* by) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != env) return fail(h, M3_ERR_UNSUPPORTED, (std::string(who) + env_only_text(env)).c_str());
+    if (on < -1 || on > 1) return fail(h, M3_ERR_BAD_ARG, (std::string(who) + ": -1 (by the " + by + "), 0 or 1").c_str());
+    h->*member = on;
+    return M3_OK;
+}
+
+// ---- the cost weights of both environments (extension; per-handle state like the objective: a fixed member, written in place --
+// no allocation, no synchronisation).  The public struct is n floats in the layout of the member ----
 static const char* const COST_WEIGHT_NAMES[9] = {"nav_dist", "collision", "robot_box", "box_goal", "push_dist",
                                                  "push_align", "pull_dist", "pull_vel", "pull_align"};
 static_assert(sizeof(m3_point_cost_weights) == 9 * sizeof(float) && sizeof(PointCostWeights) == sizeof(m3_point_cost_weights),
               "m3_point_cost_weights: nine floats, the layout of PointCostWeights");
+static const char* const PANDA_COST_WEIGHT_NAMES[7] = {"reach_dist", "reach_tilt", "pick_goal", "pick_ori", "collision",
+                                                       "shelf_force", "place_grip"};
+static_assert(sizeof(m3_panda_cost_weights) == 7 * sizeof(float) && sizeof(PandaCostWeights) == sizeof(m3_panda_cost_weights),
+              "m3_panda_cost_weights: seven floats, the layout of PandaCostWeights");
 
-extern "C" void m3_default_point_cost_weights(m3_point_cost_weights* w) {
-    if (w) std::memcpy(w, &POINT_COST_WEIGHTS_DEFAULT, sizeof(*w));
-}
-
-extern "C" int m3_set_point_cost_weights(m3_handle* h, const m3_point_cost_weights* w) {
+// w: the public struct (null: the defaults); names[n]: its fields
+template <class W>
+static int set_cost_weights(m3_handle* h, int env, W m3_handle::*member, const W& defaults, const void* w, const char* const* names,
+                            int n, const char* who) {
     if (!h) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_point_cost_weights: point_env only");
-    if (!w) { h->cost_weights = POINT_COST_WEIGHTS_DEFAULT; return M3_OK; }
-    const float* f = reinterpret_cast<const float*>(w);
-    for (int i = 0; i < 9; ++i)
-        if (!std::isfinite(f[i]))
-            return fail(h, M3_ERR_BAD_ARG, (std::string("m3_set_point_cost_weights: ") + COST_WEIGHT_NAMES[i] + " is not finite").c_str());
-    std::memcpy(&h->cost_weights, w, sizeof(*w));
+    if (h->cfg.env_type != env) return fail(h, M3_ERR_UNSUPPORTED, (std::string(who) + env_only_text(env)).c_str());
+    if (!w) { h->*member = defaults; return M3_OK; }
+    const float* f = static_cast<const float*>(w);
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(f[i])) return fail(h, M3_ERR_BAD_ARG, (std::string(who) + ": " + names[i] + " is not finite").c_str());
+    std::memcpy(&(h->*member), w, sizeof(W));
     return M3_OK;
 }
-
-extern "C" int m3_get_point_cost_weights(const m3_handle* h, m3_point_cost_weights* out) {
+template <class W> static int get_cost_weights(const m3_handle* h, int env, W m3_handle::*member, void* out) {
     if (!h || !out) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_POINT) return M3_ERR_UNSUPPORTED;
-    std::memcpy(out, &h->cost_weights, sizeof(*out));
+    if (h->cfg.env_type != env) return M3_ERR_UNSUPPORTED;
+    std::memcpy(out, &(h->*member), sizeof(W));
     return M3_OK;
 }
 
+extern "C" void m3_default_point_cost_weights(m3_point_cost_weights* w) { if (w) std::memcpy(w, &POINT_COST_WEIGHTS_DEFAULT, sizeof(*w)); }
+extern "C" int m3_set_point_cost_weights(m3_handle* h, const m3_point_cost_weights* w) {
+    return set_cost_weights(h, M3_ENV_POINT, &m3_handle::cost_weights, POINT_COST_WEIGHTS_DEFAULT, w, COST_WEIGHT_NAMES, 9, "m3_set_point_cost_weights");
+}
+extern "C" int m3_get_point_cost_weights(const m3_handle* h, m3_point_cost_weights* out) { return get_cost_weights(h, M3_ENV_POINT, &m3_handle::cost_weights, out); }
 extern "C" int m3_set_weighted_cost_instance(m3_handle* h, int on) {
-    if (!h) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_weighted_cost_instance: point_env only");
-    if (on < -1 || on > 1) return fail(h, M3_ERR_BAD_ARG, "m3_set_weighted_cost_instance: -1 (by the weights), 0 or 1");
-    h->weighted_instance = on;
-    return M3_OK;
+    return set_instance(h, M3_ENV_POINT, &m3_handle::weighted_instance, on, "m3_set_weighted_cost_instance", "weights");
+}
+
+extern "C" void m3_default_panda_cost_weights(m3_panda_cost_weights* w) { if (w) std::memcpy(w, &PANDA_COST_WEIGHTS_DEFAULT, sizeof(*w)); }
+extern "C" int m3_set_panda_cost_weights(m3_handle* h, const m3_panda_cost_weights* w) {
+    return set_cost_weights(h, M3_ENV_PANDA, &m3_handle::panda_cost_weights, PANDA_COST_WEIGHTS_DEFAULT, w, PANDA_COST_WEIGHT_NAMES, 7, "m3_set_panda_cost_weights");
+}
+extern "C" int m3_get_panda_cost_weights(const m3_handle* h, m3_panda_cost_weights* out) { return get_cost_weights(h, M3_ENV_PANDA, &m3_handle::panda_cost_weights, out); }
+extern "C" int m3_set_panda_weighted_cost_instance(m3_handle* h, int on) {
+    return set_instance(h, M3_ENV_PANDA, &m3_handle::panda_weighted_instance, on, "m3_set_panda_weighted_cost_instance", "weights");
 }
 
 // the handle's weights are the defaults bit for bit (-0.0f is not 0.0f here: the kernels multiply by them)
@@ -850,10 +874,6 @@ static const char* const SCENE_FIELD_NAMES[28] = {
 static const int SCENE_FIELD_RULE[28] = {1, 1, 1, 1, 1, 1, 2, 1, 1, 1, 1, 1, 2, 1, 0, 0, 1, 1, 1, 2, 2, 2, 2, 2, 2, 2, 2, 2};
 static_assert(sizeof(m3_point_scene) == 28 * sizeof(float), "m3_point_scene: twenty-eight floats");
 
-extern "C" void m3_default_point_scene(m3_point_scene* sc) {
-    if (sc) std::memcpy(sc, &POINT_SCENE_DEFAULT, sizeof(*sc));
-}
-
 // the per-field checks of an arena, shared by m3_set_point_scene and every row of m3_set_point_scene_rows: empty if it passes,
 // else "<field> <what is wrong>"
 static std::string point_scene_fault(const m3_point_scene& src) {
@@ -868,55 +888,110 @@ static std::string point_scene_fault(const m3_point_scene& src) {
     return std::string();
 }
 
-extern "C" int m3_set_point_scene(m3_handle* h, const m3_point_scene* sc) {
+// ---- the two kinds of run-time scene, the point_env arena and the panda_env workspace: what differs between them, once.  The
+// single scene (m3_set_*_scene), the rows per environment of a sim_only handle (m3_set_*_scene_rows) and per sample of a
+// planner's rollout (m3_set_*_rollout_scenes) are the templates below over a kind.  Per-handle state like the cost weights:
+// the single scene is a fixed member, written in place -- no allocation, no synchronisation ----
+struct PointSceneKind {
+    using Scene = m3_point_scene;
+    static constexpr int ENV = M3_ENV_POINT;
+    static constexpr const Scene& DEFAULT = POINT_SCENE_DEFAULT;
+    static constexpr int ROW_WORDS = POINT_SCENE_ROW_WORDS;
+    static constexpr Scene m3_handle::*SINGLE = &m3_handle::point_scene;
+    static constexpr SceneRows<Scene> m3_handle::*ROWS = &m3_handle::point_rows;
+    static constexpr const char* SET_SCENE = "m3_set_point_scene";
+    static constexpr const char* SET_ENV_ROWS = "m3_set_point_scene_rows";
+    static constexpr const char* SET_SAMPLE_ROWS = "m3_set_point_rollout_scenes";
+    // (what a planner handle is told by m3_set_point_scene_rows; out of date since m3_set_point_rollout_scenes exists, kept as it is)
+    static constexpr const char* PLANNER_HINT = "a planner's rollouts share one model: m3_set_point_scene";
+    static std::string fault(const Scene& sc) { return point_scene_fault(sc); }
+    // the handle's derived copy of its single scene
+    static void rebuild(m3_handle* h) { h->scene_rt = make_point_scene_rt(h->point_scene, h->cfg.dt, h->cfg.substeps, h->cfg.solver_iters); }
+    static void pack_row(const m3_config& c, const Scene& sc, float* table, int Kl, int i) {
+        point_scene_row_pack(make_point_scene_rt(sc, c.dt, c.substeps, c.solver_iters), table, Kl, i);
+    }
+};
+struct PandaSceneKind {
+    using Scene = m3_panda_scene;
+    static constexpr int ENV = M3_ENV_PANDA;
+    static constexpr const Scene& DEFAULT = PANDA_SCENE_DEFAULT;
+    static constexpr int ROW_WORDS = PANDA_SCENE_ROW_WORDS;
+    static constexpr Scene m3_handle::*SINGLE = &m3_handle::panda_scene;
+    static constexpr SceneRows<Scene> m3_handle::*ROWS = &m3_handle::panda_rows;
+    static constexpr const char* SET_SCENE = "m3_set_panda_scene";
+    static constexpr const char* SET_ENV_ROWS = "m3_set_panda_scene_rows";
+    static constexpr const char* SET_SAMPLE_ROWS = "m3_set_panda_rollout_scenes";
+    static constexpr const char* PLANNER_HINT = "the samples of a planner's rollout: m3_set_panda_rollout_scenes";
+    static std::string fault(const Scene& sc) { return panda_scene_fault(sc); }
+    static void rebuild(m3_handle* h) { build_panda_scenes(h->cfg, h->panda_scene, h->pscene, h->pscene_rt); }
+    static void pack_row(const m3_config& c, const Scene& sc, float* table, int Kl, int i) {
+        panda_scene_row_pack(make_panda_scene_rt(sc, c.dt, c.substeps), table, Kl, i);
+    }
+};
+
+template <class Kind> static void default_scene(typename Kind::Scene* sc) {
+    if (sc) std::memcpy(sc, &Kind::DEFAULT, sizeof(*sc));
+}
+
+template <class Kind> static int set_scene(m3_handle* h, const typename Kind::Scene* sc) {
     if (!h) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_point_scene: point_env only");
-    const m3_point_scene& src = sc ? *sc : POINT_SCENE_DEFAULT;
-    const std::string fault = point_scene_fault(src);
-    if (!fault.empty()) return fail(h, M3_ERR_BAD_ARG, ("m3_set_point_scene: " + fault).c_str());
-    std::memcpy(&h->point_scene, &src, sizeof(src));
-    h->scene_rt = make_point_scene_rt(h->point_scene, h->cfg.dt, h->cfg.substeps, h->cfg.solver_iters);
-    h->scene_rows_on = false;   // the last call wins: the handle is on its single scene (the rows' memory is kept for a later call)
-    h->rollout_scenes_on = false;
+    const std::string who = Kind::SET_SCENE;
+    if (h->cfg.env_type != Kind::ENV) return fail(h, M3_ERR_UNSUPPORTED, (who + env_only_text(Kind::ENV)).c_str());
+    const typename Kind::Scene& src = sc ? *sc : Kind::DEFAULT;
+    const std::string fault = Kind::fault(src);
+    if (!fault.empty()) return fail(h, M3_ERR_BAD_ARG, (who + ": " + fault).c_str());
+    std::memcpy(&(h->*Kind::SINGLE), &src, sizeof(src));
+    Kind::rebuild(h);
+    // the last call wins: the handle is on its single scene (the rows' memory is kept for a later call)
+    (h->*Kind::ROWS).env_on = (h->*Kind::ROWS).sample_on = false;
     return M3_OK;
 }
 
-// The rows of a handle -- per environment (sim_only: m3_set_point_scene_rows) or per sample (planner:
-// m3_set_point_rollout_scenes) -- into its host copy, pinned mirror and device table: scenes are Kl checked rows.
-// THE allocation of both features: the first call on a handle; later calls reuse the three blocks (K_local is fixed at
-// m3_create).  m3_sim_step*, m3_episodes_tick / _begin / _end, m3_rollout and m3_command allocate nothing because of the rows --
-// they read scene_rows_dev and scene_rt, nothing else.
-static int upload_point_scene_rows(m3_handle* h, const m3_point_scene* scenes, const char* who) {
+template <class Kind> static int get_scene(const m3_handle* h, typename Kind::Scene* out) {
+    if (!h || !out) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != Kind::ENV) return M3_ERR_UNSUPPORTED;
+    std::memcpy(out, &(h->*Kind::SINGLE), sizeof(*out));
+    return M3_OK;
+}
+
+// The rows of a handle -- per environment (sim_only) or per sample (planner) -- into its host copy, pinned mirror and device
+// table: scenes are Kl checked rows.  THE allocation of both features: the first call of the kind on a handle; later calls
+// reuse the three blocks (K_local is fixed at m3_create).  m3_sim_step*, m3_cost, m3_episodes_tick / _begin / _end, m3_rollout
+// and m3_command allocate nothing because of the rows -- they read the device table and the handle's scene_rt / pscene_rt,
+// nothing else.
+template <class Kind>
+static int upload_scene_rows(m3_handle* h, const typename Kind::Scene* scenes, const char* who) {
+    using Scene = typename Kind::Scene;
+    SceneRows<Scene>& r = h->*Kind::ROWS;
     const int Kl = h->cfg.K_local;
-    const size_t table_bytes = (size_t)POINT_SCENE_ROW_WORDS * Kl * sizeof(float);
-    if (!h->scene_rows_dev) {
+    const size_t table_bytes = (size_t)Kind::ROW_WORDS * Kl * sizeof(float);
+    if (!r.dev) {
         BlockGroup g(h->mem);   // all three or none
-        hipError_t e = own_host(h->mem, h->scene_rows, (size_t)Kl * sizeof(m3_point_scene));
-        if (e == hipSuccess) e = own_pinned(h->mem, h->scene_rows_host, table_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = own_device(h->mem, h->scene_rows_dev, table_bytes);
+        hipError_t e = own_host(h->mem, r.set, (size_t)Kl * sizeof(Scene));
+        if (e == hipSuccess) e = own_pinned(h->mem, r.host, table_bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = own_device(h->mem, r.dev, table_bytes);
         if (e != hipSuccess) return fail(h, M3_ERR_HIP, (std::string(who) + ": " + hipGetErrorString(e)).c_str());
         g.keep = true;
     } else {
         // the pinned mirror is the source of the previous call's asynchronous upload: that copy is over before it is rewritten
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
-    std::memcpy(h->scene_rows, scenes, (size_t)Kl * sizeof(m3_point_scene));
-    for (int i = 0; i < Kl; ++i)
-        point_scene_row_pack(make_point_scene_rt(scenes[i], h->cfg.dt, h->cfg.substeps, h->cfg.solver_iters), h->scene_rows_host, Kl, i);
-    HIPCHK(h, hipMemcpyAsync(h->scene_rows_dev, h->scene_rows_host, table_bytes, hipMemcpyHostToDevice, h->stream));
+    std::memcpy(r.set, scenes, (size_t)Kl * sizeof(Scene));
+    for (int i = 0; i < Kl; ++i) Kind::pack_row(h->cfg, scenes[i], r.host, Kl, i);
+    HIPCHK(h, hipMemcpyAsync(r.dev, r.host, table_bytes, hipMemcpyHostToDevice, h->stream));
     return M3_OK;
 }
 
-// m3_set_point_scene_rows (sim_only handles: one arena per environment) and, per_sample, m3_set_point_rollout_scenes (planner
-// handles: one arena per sample of the fused rollout).  Every check before any state changes.
-static int set_point_rows(m3_handle* h, const m3_point_scene* scenes, int n, bool per_sample) {
+// m3_set_*_scene_rows (sim_only handles: one scene per environment) and, per_sample, m3_set_*_rollout_scenes (planner handles:
+// one scene per sample of the fused rollout).  Every check before any state changes.
+template <class Kind> static int set_scene_rows(m3_handle* h, const typename Kind::Scene* scenes, int n, bool per_sample) {
     if (!h) return M3_ERR_BAD_ARG;
-    const std::string who = per_sample ? "m3_set_point_rollout_scenes" : "m3_set_point_scene_rows";
-    bool& on = per_sample ? h->rollout_scenes_on : h->scene_rows_on;
-    if (h->cfg.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, (who + ": point_env only").c_str());
+    const std::string who = per_sample ? Kind::SET_SAMPLE_ROWS : Kind::SET_ENV_ROWS;
+    bool& on = per_sample ? (h->*Kind::ROWS).sample_on : (h->*Kind::ROWS).env_on;
+    if (h->cfg.env_type != Kind::ENV) return fail(h, M3_ERR_UNSUPPORTED, (who + env_only_text(Kind::ENV)).c_str());
     if ((h->cfg.sim_only != 0) == per_sample)
-        return fail(h, M3_ERR_STATE, (who + (per_sample ? ": planner handles only (the environments of a sim_only handle: m3_set_point_scene_rows)"
-                                                        : ": sim_only handles only (a planner's rollouts share one model: m3_set_point_scene)")).c_str());
+        return fail(h, M3_ERR_STATE, (who + (per_sample ? std::string(": planner handles only (the environments of a sim_only handle: ") + Kind::SET_ENV_ROWS
+                                                        : std::string(": sim_only handles only (") + Kind::PLANNER_HINT) + ")").c_str());
     if (!scenes) {   // back on the single scene: exactly the kernels of a handle that never had rows (n is not read)
         on = false;
         return M3_OK;
@@ -925,45 +1000,49 @@ static int set_point_rows(m3_handle* h, const m3_point_scene* scenes, int n, boo
     if (n != Kl)
         return fail(h, M3_ERR_SHAPE, (who + ": n is " + std::to_string(n) + ", the handle's K_local " + std::to_string(Kl)).c_str());
     for (int i = 0; i < n; ++i) {
-        const std::string fault = point_scene_fault(scenes[i]);
+        const std::string fault = Kind::fault(scenes[i]);
         if (!fault.empty()) return fail(h, M3_ERR_BAD_ARG, (who + ": row " + std::to_string(i) + ": " + fault).c_str());
     }
-    const int rc = upload_point_scene_rows(h, scenes, who.c_str());
+    const int rc = upload_scene_rows<Kind>(h, scenes, who.c_str());
     if (rc != M3_OK) return rc;
     on = true;
     return M3_OK;
 }
-// row `row` as it was set, while the feature (`on`: its flag) is on
-static int get_point_row(const m3_handle* h, int row, m3_point_scene* out, bool m3_handle::*on) {
+// row `row` as it was set, while the feature (per_sample: which of the two) is on
+template <class Kind> static int get_scene_row(const m3_handle* h, int row, typename Kind::Scene* out, bool per_sample) {
     if (!h || !out) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_POINT) return M3_ERR_UNSUPPORTED;
-    if (!(h->*on)) return M3_ERR_STATE;
+    if (h->cfg.env_type != Kind::ENV) return M3_ERR_UNSUPPORTED;
+    const SceneRows<typename Kind::Scene>& r = h->*Kind::ROWS;
+    if (!(per_sample ? r.sample_on : r.env_on)) return M3_ERR_STATE;
     if (row < 0 || row >= h->cfg.K_local) return M3_ERR_BAD_ARG;
-    std::memcpy(out, &h->scene_rows[row], sizeof(*out));
+    std::memcpy(out, &r.set[row], sizeof(*out));
     return M3_OK;
 }
 
-extern "C" int m3_set_point_scene_rows(m3_handle* h, const m3_point_scene* scenes, int n) { return set_point_rows(h, scenes, n, false); }
-extern "C" int m3_get_point_scene_row(const m3_handle* h, int row, m3_point_scene* out) { return get_point_row(h, row, out, &m3_handle::scene_rows_on); }
-extern "C" int m3_point_scene_rows_set(const m3_handle* h) { return h ? (h->scene_rows_on ? 1 : 0) : M3_ERR_BAD_ARG; }
-
-extern "C" int m3_set_point_rollout_scenes(m3_handle* h, const m3_point_scene* scenes, int n) { return set_point_rows(h, scenes, n, true); }
-extern "C" int m3_get_point_rollout_scene(const m3_handle* h, int row, m3_point_scene* out) { return get_point_row(h, row, out, &m3_handle::rollout_scenes_on); }
-extern "C" int m3_point_rollout_scenes_set(const m3_handle* h) { return h ? (h->rollout_scenes_on ? 1 : 0) : M3_ERR_BAD_ARG; }
-
-extern "C" int m3_get_point_scene(const m3_handle* h, m3_point_scene* out) {
-    if (!h || !out) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_POINT) return M3_ERR_UNSUPPORTED;
-    std::memcpy(out, &h->point_scene, sizeof(*out));
-    return M3_OK;
-}
-
+extern "C" void m3_default_point_scene(m3_point_scene* sc) { default_scene<PointSceneKind>(sc); }
+extern "C" int m3_set_point_scene(m3_handle* h, const m3_point_scene* sc) { return set_scene<PointSceneKind>(h, sc); }
+extern "C" int m3_get_point_scene(const m3_handle* h, m3_point_scene* out) { return get_scene<PointSceneKind>(h, out); }
+extern "C" int m3_set_point_scene_rows(m3_handle* h, const m3_point_scene* scenes, int n) { return set_scene_rows<PointSceneKind>(h, scenes, n, false); }
+extern "C" int m3_get_point_scene_row(const m3_handle* h, int row, m3_point_scene* out) { return get_scene_row<PointSceneKind>(h, row, out, false); }
+extern "C" int m3_point_scene_rows_set(const m3_handle* h) { return h ? (h->point_rows.env_on ? 1 : 0) : M3_ERR_BAD_ARG; }
+extern "C" int m3_set_point_rollout_scenes(m3_handle* h, const m3_point_scene* scenes, int n) { return set_scene_rows<PointSceneKind>(h, scenes, n, true); }
+extern "C" int m3_get_point_rollout_scene(const m3_handle* h, int row, m3_point_scene* out) { return get_scene_row<PointSceneKind>(h, row, out, true); }
+extern "C" int m3_point_rollout_scenes_set(const m3_handle* h) { return h ? (h->point_rows.sample_on ? 1 : 0) : M3_ERR_BAD_ARG; }
 extern "C" int m3_set_point_scene_instance(m3_handle* h, int on) {
-    if (!h) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_point_scene_instance: point_env only");
-    if (on < -1 || on > 1) return fail(h, M3_ERR_BAD_ARG, "m3_set_point_scene_instance: -1 (by the values), 0 or 1");
-    h->scene_instance = on;
-    return M3_OK;
+    return set_instance(h, M3_ENV_POINT, &m3_handle::scene_instance, on, "m3_set_point_scene_instance", "values");
+}
+
+extern "C" void m3_default_panda_scene(m3_panda_scene* sc) { default_scene<PandaSceneKind>(sc); }
+extern "C" int m3_set_panda_scene(m3_handle* h, const m3_panda_scene* sc) { return set_scene<PandaSceneKind>(h, sc); }
+extern "C" int m3_get_panda_scene(const m3_handle* h, m3_panda_scene* out) { return get_scene<PandaSceneKind>(h, out); }
+extern "C" int m3_set_panda_scene_rows(m3_handle* h, const m3_panda_scene* scenes, int n) { return set_scene_rows<PandaSceneKind>(h, scenes, n, false); }
+extern "C" int m3_get_panda_scene_row(const m3_handle* h, int row, m3_panda_scene* out) { return get_scene_row<PandaSceneKind>(h, row, out, false); }
+extern "C" int m3_panda_scene_rows_set(const m3_handle* h) { return h ? (h->panda_rows.env_on ? 1 : 0) : M3_ERR_BAD_ARG; }
+extern "C" int m3_set_panda_rollout_scenes(m3_handle* h, const m3_panda_scene* scenes, int n) { return set_scene_rows<PandaSceneKind>(h, scenes, n, true); }
+extern "C" int m3_get_panda_rollout_scene(const m3_handle* h, int row, m3_panda_scene* out) { return get_scene_row<PandaSceneKind>(h, row, out, true); }
+extern "C" int m3_panda_rollout_scenes_set(const m3_handle* h) { return h ? (h->panda_rows.sample_on ? 1 : 0) : M3_ERR_BAD_ARG; }
+extern "C" int m3_set_panda_scene_instance(m3_handle* h, int on) {
+    return set_instance(h, M3_ENV_PANDA, &m3_handle::panda_scene_instance, on, "m3_set_panda_scene_instance", "values");
 }
 
 // the handle's arena is the default bit for bit (-0.0f is not 0.0f here)
@@ -980,7 +1059,7 @@ enum PointSide { SIDE_COST = 1, SIDE_STEP = 2, SIDE_ROLLOUT = SIDE_COST | SIDE_S
 static PointVariant point_variant(const m3_handle* h, PointSide side) {
     if (h->cfg.env_type != M3_ENV_POINT) return POINT_PLAIN;
     // (per-sample arenas are the run-time-scene variant of the rollout; a planner handle's own step keeps its single scene)
-    const bool rows = side == SIDE_ROLLOUT && h->rollout_scenes_on;
+    const bool rows = side == SIDE_ROLLOUT && h->point_rows.sample_on;
     if ((side & SIDE_STEP) && (h->scene_instance < 0 ? (rows || !default_point_scene(h)) : h->scene_instance != 0)) return POINT_SCENE;
     return (h->weighted_instance < 0 ? !default_cost_weights(h) : h->weighted_instance != 0) ? POINT_WEIGHTED : POINT_PLAIN;
 }
@@ -988,7 +1067,7 @@ static PointVariant point_variant(const m3_handle* h, PointSide side) {
 // argument (m3_set_point_scene), or one arena per environment (m3_set_point_scene_rows)
 enum PointStepVariant { STEP_COMPILED, STEP_RUNTIME, STEP_ROWS };
 static PointStepVariant point_step_variant(const m3_handle* h) {
-    if (h->scene_rows_on) return STEP_ROWS;
+    if (h->point_rows.env_on) return STEP_ROWS;
     return point_variant(h, SIDE_STEP) == POINT_SCENE ? STEP_RUNTIME : STEP_COMPILED;
 }
 // why the handle cannot run that side's kernels (M3_ERR_STATE; nullptr: it can)
@@ -996,158 +1075,16 @@ static const char* point_variant_refusal(const m3_handle* h, PointSide side) {
     if (h->cfg.env_type != M3_ENV_POINT) return nullptr;
     if ((side & SIDE_COST) && h->weighted_instance == 0 && !default_cost_weights(h))
         return "the weighted cost instance is forced off (m3_set_weighted_cost_instance 0) but the handle's cost weights are not the defaults";
-    if ((side & SIDE_STEP) && h->scene_instance == 0 && h->scene_rows_on)
+    if ((side & SIDE_STEP) && h->scene_instance == 0 && h->point_rows.env_on)
         return "the run-time-scene instance is forced off (m3_set_point_scene_instance 0) but the handle has an arena per environment (m3_set_point_scene_rows)";
-    if (side == SIDE_ROLLOUT && h->scene_instance == 0 && h->rollout_scenes_on)
+    if (side == SIDE_ROLLOUT && h->scene_instance == 0 && h->point_rows.sample_on)
         return "the run-time-scene instance is forced off (m3_set_point_scene_instance 0) but the handle has an arena per sample (m3_set_point_rollout_scenes)";
     if ((side & SIDE_STEP) && h->scene_instance == 0 && !default_point_scene(h))
         return "the run-time-scene instance is forced off (m3_set_point_scene_instance 0) but the handle's scene is not the default";
     return nullptr;
 }
 
-// ---- the panda_env workspace (extension; per-handle state like the point arena: fixed members, no allocation, no
-// synchronisation) ----
-extern "C" void m3_default_panda_scene(m3_panda_scene* sc) {
-    if (sc) std::memcpy(sc, &PANDA_SCENE_DEFAULT, sizeof(*sc));
-}
-
-extern "C" int m3_set_panda_scene(m3_handle* h, const m3_panda_scene* sc) {
-    if (!h) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_PANDA) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_panda_scene: panda_env only");
-    const m3_panda_scene& src = sc ? *sc : PANDA_SCENE_DEFAULT;
-    const std::string fault = panda_scene_fault(src);
-    if (!fault.empty()) return fail(h, M3_ERR_BAD_ARG, ("m3_set_panda_scene: " + fault).c_str());
-    std::memcpy(&h->panda_scene, &src, sizeof(src));
-    build_panda_scenes(h->cfg, h->panda_scene, h->pscene, h->pscene_rt);
-    h->panda_scene_rows_on = false;   // the last call wins: the handle is on its single workspace (the rows' memory is kept for a later call)
-    h->panda_rollout_scenes_on = false;
-    return M3_OK;
-}
-
-// The rows of a handle -- per environment (sim_only: m3_set_panda_scene_rows) or per sample (planner:
-// m3_set_panda_rollout_scenes) -- into its host copy, pinned mirror and device table: scenes are Kl checked rows.
-// THE allocation of both features: the first call on a handle; later calls reuse the three blocks (K_local is fixed at
-// m3_create).  m3_sim_step*, m3_cost, m3_rollout and m3_command allocate nothing because of the rows -- they read panda_rows_dev
-// and pscene_rt, nothing else.
-static int upload_panda_scene_rows(m3_handle* h, const m3_panda_scene* scenes, const char* who) {
-    const int Kl = h->cfg.K_local;
-    const size_t table_bytes = (size_t)PANDA_SCENE_ROW_WORDS * Kl * sizeof(float);
-    if (!h->panda_rows_dev) {
-        BlockGroup g(h->mem);   // all three or none
-        hipError_t e = own_host(h->mem, h->panda_rows, (size_t)Kl * sizeof(m3_panda_scene));
-        if (e == hipSuccess) e = own_pinned(h->mem, h->panda_rows_host, table_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = own_device(h->mem, h->panda_rows_dev, table_bytes);
-        if (e != hipSuccess) return fail(h, M3_ERR_HIP, (std::string(who) + ": " + hipGetErrorString(e)).c_str());
-        g.keep = true;
-    } else {
-        // the pinned mirror is the source of the previous call's asynchronous upload: that copy is over before it is rewritten
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    std::memcpy(h->panda_rows, scenes, (size_t)Kl * sizeof(m3_panda_scene));
-    for (int i = 0; i < Kl; ++i)
-        panda_scene_row_pack(make_panda_scene_rt(scenes[i], h->cfg.dt, h->cfg.substeps), h->panda_rows_host, Kl, i);
-    HIPCHK(h, hipMemcpyAsync(h->panda_rows_dev, h->panda_rows_host, table_bytes, hipMemcpyHostToDevice, h->stream));
-    return M3_OK;
-}
-
-// m3_set_panda_scene_rows (sim_only handles: one workspace per environment) and, per_sample, m3_set_panda_rollout_scenes
-// (planner handles: one workspace per sample of the fused rollout).  Every check before any state changes.
-static int set_panda_rows(m3_handle* h, const m3_panda_scene* scenes, int n, bool per_sample) {
-    if (!h) return M3_ERR_BAD_ARG;
-    const std::string who = per_sample ? "m3_set_panda_rollout_scenes" : "m3_set_panda_scene_rows";
-    bool& on = per_sample ? h->panda_rollout_scenes_on : h->panda_scene_rows_on;
-    if (h->cfg.env_type != M3_ENV_PANDA) return fail(h, M3_ERR_UNSUPPORTED, (who + ": panda_env only").c_str());
-    if ((h->cfg.sim_only != 0) == per_sample)
-        return fail(h, M3_ERR_STATE, (who + (per_sample ? ": planner handles only (the environments of a sim_only handle: m3_set_panda_scene_rows)"
-                                                        : ": sim_only handles only (the samples of a planner's rollout: m3_set_panda_rollout_scenes)")).c_str());
-    if (!scenes) {   // back on the single workspace: exactly the kernels of a handle that never had rows (n is not read)
-        on = false;
-        return M3_OK;
-    }
-    const int Kl = h->cfg.K_local;
-    if (n != Kl)
-        return fail(h, M3_ERR_SHAPE, (who + ": n is " + std::to_string(n) + ", the handle's K_local " + std::to_string(Kl)).c_str());
-    for (int i = 0; i < n; ++i) {
-        const std::string fault = panda_scene_fault(scenes[i]);
-        if (!fault.empty()) return fail(h, M3_ERR_BAD_ARG, (who + ": row " + std::to_string(i) + ": " + fault).c_str());
-    }
-    const int rc = upload_panda_scene_rows(h, scenes, who.c_str());
-    if (rc != M3_OK) return rc;
-    on = true;
-    return M3_OK;
-}
-// row `row` as it was set, while the feature (`on`: its flag) is on
-static int get_panda_row(const m3_handle* h, int row, m3_panda_scene* out, bool m3_handle::*on) {
-    if (!h || !out) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_PANDA) return M3_ERR_UNSUPPORTED;
-    if (!(h->*on)) return M3_ERR_STATE;
-    if (row < 0 || row >= h->cfg.K_local) return M3_ERR_BAD_ARG;
-    std::memcpy(out, &h->panda_rows[row], sizeof(*out));
-    return M3_OK;
-}
-
-extern "C" int m3_set_panda_scene_rows(m3_handle* h, const m3_panda_scene* scenes, int n) { return set_panda_rows(h, scenes, n, false); }
-extern "C" int m3_get_panda_scene_row(const m3_handle* h, int row, m3_panda_scene* out) { return get_panda_row(h, row, out, &m3_handle::panda_scene_rows_on); }
-extern "C" int m3_panda_scene_rows_set(const m3_handle* h) { return h ? (h->panda_scene_rows_on ? 1 : 0) : M3_ERR_BAD_ARG; }
-
-extern "C" int m3_set_panda_rollout_scenes(m3_handle* h, const m3_panda_scene* scenes, int n) { return set_panda_rows(h, scenes, n, true); }
-extern "C" int m3_get_panda_rollout_scene(const m3_handle* h, int row, m3_panda_scene* out) { return get_panda_row(h, row, out, &m3_handle::panda_rollout_scenes_on); }
-extern "C" int m3_panda_rollout_scenes_set(const m3_handle* h) { return h ? (h->panda_rollout_scenes_on ? 1 : 0) : M3_ERR_BAD_ARG; }
-
-extern "C" int m3_get_panda_scene(const m3_handle* h, m3_panda_scene* out) {
-    if (!h || !out) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_PANDA) return M3_ERR_UNSUPPORTED;
-    std::memcpy(out, &h->panda_scene, sizeof(*out));
-    return M3_OK;
-}
-
-extern "C" int m3_set_panda_scene_instance(m3_handle* h, int on) {
-    if (!h) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_PANDA) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_panda_scene_instance: panda_env only");
-    if (on < -1 || on > 1) return fail(h, M3_ERR_BAD_ARG, "m3_set_panda_scene_instance: -1 (by the values), 0 or 1");
-    h->panda_scene_instance = on;
-    return M3_OK;
-}
-
 extern "C" int m3_panda_scene_instance_used(m3_handle* h) { return h ? h->panda_scene_used : M3_ERR_BAD_ARG; }
-
-// ---- the panda_env cost weights (extension; per-handle state like the point ones: a fixed member, no allocation, no
-// synchronisation) ----
-static const char* const PANDA_COST_WEIGHT_NAMES[7] = {"reach_dist", "reach_tilt", "pick_goal", "pick_ori", "collision",
-                                                       "shelf_force", "place_grip"};
-static_assert(sizeof(m3_panda_cost_weights) == 7 * sizeof(float) && sizeof(PandaCostWeights) == sizeof(m3_panda_cost_weights),
-              "m3_panda_cost_weights: seven floats, the layout of PandaCostWeights");
-
-extern "C" void m3_default_panda_cost_weights(m3_panda_cost_weights* w) {
-    if (w) std::memcpy(w, &PANDA_COST_WEIGHTS_DEFAULT, sizeof(*w));
-}
-
-extern "C" int m3_set_panda_cost_weights(m3_handle* h, const m3_panda_cost_weights* w) {
-    if (!h) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_PANDA) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_panda_cost_weights: panda_env only");
-    if (!w) { h->panda_cost_weights = PANDA_COST_WEIGHTS_DEFAULT; return M3_OK; }
-    const float* f = reinterpret_cast<const float*>(w);
-    for (int i = 0; i < 7; ++i)
-        if (!std::isfinite(f[i]))
-            return fail(h, M3_ERR_BAD_ARG, (std::string("m3_set_panda_cost_weights: ") + PANDA_COST_WEIGHT_NAMES[i] + " is not finite").c_str());
-    std::memcpy(&h->panda_cost_weights, w, sizeof(*w));
-    return M3_OK;
-}
-
-extern "C" int m3_get_panda_cost_weights(const m3_handle* h, m3_panda_cost_weights* out) {
-    if (!h || !out) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_PANDA) return M3_ERR_UNSUPPORTED;
-    std::memcpy(out, &h->panda_cost_weights, sizeof(*out));
-    return M3_OK;
-}
-
-extern "C" int m3_set_panda_weighted_cost_instance(m3_handle* h, int on) {
-    if (!h) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_PANDA) return fail(h, M3_ERR_UNSUPPORTED, "m3_set_panda_weighted_cost_instance: panda_env only");
-    if (on < -1 || on > 1) return fail(h, M3_ERR_BAD_ARG, "m3_set_panda_weighted_cost_instance: -1 (by the weights), 0 or 1");
-    h->panda_weighted_instance = on;
-    return M3_OK;
-}
 
 extern "C" int m3_panda_weighted_cost_instance_used(m3_handle* h) { return h ? h->panda_weighted_used : M3_ERR_BAD_ARG; }
 
@@ -1160,8 +1097,8 @@ static PandaVariantInput panda_input(const m3_handle* h) {
     in.geometry_default = panda_scene_geometry_is_default(h->panda_scene);   // (anything but the two masses off the defaults)
     // (bit for bit: -0.0f is not 0.0f here, the kernels multiply by them)
     in.weights_default = std::memcmp(&h->panda_cost_weights, &PANDA_COST_WEIGHTS_DEFAULT, sizeof(PandaCostWeights)) == 0;
-    in.rollout_scenes_on = h->panda_rollout_scenes_on;
-    in.scene_rows_on = h->panda_scene_rows_on;
+    in.rollout_scenes_on = h->panda_rows.sample_on;
+    in.scene_rows_on = h->panda_rows.env_on;
     in.sim_only = h->cfg.sim_only != 0;
     return in;
 }
@@ -1208,7 +1145,7 @@ static const char* panda_episodes_refusal(const m3_handle* h, PandaEpisodesMode 
 }
 // a launcher's view of the handle for a variant, and the record of what an accepted call launches
 static PandaLaunchScene panda_launch_scene(const m3_handle* h, PandaVariant v) {
-    return {v, &h->pscene, &h->pscene_rt, &h->panda_cost_weights, h->panda_rows_dev};
+    return {v, &h->pscene, &h->pscene_rt, &h->panda_cost_weights, h->panda_rows.dev};
 }
 static void panda_record_used(m3_handle* h, const PandaDecision& d) {
     if (d.scene_used != PANDA_USED_UNCHANGED) h->panda_scene_used = d.scene_used;
@@ -1459,7 +1396,7 @@ static int plan_rollout(m3_handle* h, RolloutArgs& a, PandaArgs& pa, RolloutPlan
     if (h->cfg.env_type == M3_ENV_POINT) {
         // (the two-wavefront form: m3_rollout's own launch only, and only with the error word to report into)
         p = plan_rollout_point(a, h->scene, point_variant(h, SIDE_ROLLOUT), (own_launch && h->rollout_err_dev) ? h->point_form : 0,
-                               h->rollout_scenes_on);
+                               h->point_rows.sample_on);
     } else {
         fill_panda_args(h, a, pa);
         p = plan_rollout_panda(a, pa);
@@ -1483,7 +1420,7 @@ extern "C" int m3_rollout(m3_handle* h) {
     if (rc != M3_OK) return rc;
     if (h->cfg.env_type == M3_ENV_POINT) h->point_form_used = p.form;
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->scene_rt, h->cost_weights, p, h->stream, h->rollout_err_dev, h->scene_rows_dev);
+    if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->scene_rt, h->cost_weights, p, h->stream, h->rollout_err_dev, h->point_rows.dev);
     else {
         const PandaDecision d = panda_decision(panda_input(h), PANDA_SIDE_ROLLOUT);
         launch_rollout_panda(a, pa, panda_launch_scene(h, d.variant), p, h->stream);
@@ -2215,7 +2152,7 @@ static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code, bool pa
     code = M3_ERR_STATE;
     if (c.K_local != c.K_global) return "sharded handle (K_local != K_global)";
     if (c.sim_only) return "handle was created sim_only";
-    if (h->rollout_scenes_on && !point_rows) {   // (the table's slots have no fourth section)
+    if (h->point_rows.sample_on && !point_rows) {   // (the table's slots have no fourth section)
         code = M3_ERR_UNSUPPORTED;
         return POINT_ROWS_UNBATCHED;
     }
@@ -2337,7 +2274,7 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
             continue;
         }
         switch (point_section(hd[i].key.roll)) {
-            case POINT_SECTION_SV: *reinterpret_cast<BatchRolloutEntrySV*>(e) = {hd[i].a, h->scene_rt, h->cost_weights, h->scene_rows_dev}; break;
+            case POINT_SECTION_SV: *reinterpret_cast<BatchRolloutEntrySV*>(e) = {hd[i].a, h->scene_rt, h->cost_weights, h->point_rows.dev}; break;
             case POINT_SCENE: *reinterpret_cast<BatchRolloutEntryS*>(e) = {hd[i].a, h->scene_rt, h->cost_weights}; break;
             case POINT_WEIGHTED: *reinterpret_cast<BatchRolloutEntryW*>(e) = {hd[i].a, h->scene, h->cost_weights}; break;
             default: *reinterpret_cast<BatchRolloutEntry*>(e) = {hd[i].a, h->scene}; break;
@@ -2560,7 +2497,7 @@ static int sim_step_impl(m3_handle* h, const float* u) {
         if (const char* why = point_variant_refusal(h, SIDE_STEP)) return fail(h, M3_ERR_STATE, (std::string("m3_sim_step: ") + why).c_str());
         const int Kl = h->cfg.K_local;
         switch (point_step_variant(h)) {
-            case STEP_ROWS: launch_sim_step_sv(h->scene_rt, h->scene_rows_dev, h->views, h->sim_world, u, h->sim_u, Kl, h->stream); break;
+            case STEP_ROWS: launch_sim_step_sv(h->scene_rt, h->point_rows.dev, h->views, h->sim_world, u, h->sim_u, Kl, h->stream); break;
             case STEP_RUNTIME: launch_sim_step_s(h->scene_rt, h->views, h->sim_world, u, h->sim_u, Kl, h->stream); break;
             default: launch_sim_step(h->scene, h->views, h->sim_world, u, h->sim_u, Kl, h->stream); break;
         }
@@ -2784,7 +2721,7 @@ static int eps_ready(m3_episodes* eps, const char* who) {
 // the step of the world's rows with the WORLD handle's scene (the planners plan with their own)
 static void episodes_post(const m3_handle* w, const m3::EpisodeArgs& a, int tick) {
     switch (point_step_variant(w)) {
-        case STEP_ROWS: m3::launch_episodes_post_sv(w->scene_rt, w->scene_rows_dev, a, tick, w->stream); break;   // a scene per episode
+        case STEP_ROWS: m3::launch_episodes_post_sv(w->scene_rt, w->point_rows.dev, a, tick, w->stream); break;   // a scene per episode
         case STEP_RUNTIME: m3::launch_episodes_post_s(w->scene_rt, a, tick, w->stream); break;
         default: m3::launch_episodes_post(w->scene, a, tick, w->stream); break;
     }
@@ -2836,12 +2773,12 @@ extern "C" int m3_episodes_tick(m3_episodes* eps, m3_batch* batch) {
     for (int i = 0; i < eps->n; ++i) {
         if (eps->host[i].done_tick >= 0) continue;
         m3_handle* h = eps->planners[i];
-        if (h->rollout_scenes_on && !point_rows) {   // (set after m3_episodes_create, which refuses it: nothing of this tick is launched)
+        if (h->point_rows.sample_on && !point_rows) {   // (set after m3_episodes_create, which refuses it: nothing of this tick is launched)
             eps->err = "m3_episodes_tick: planner " + std::to_string(i) + ": " + POINT_ROWS_UNBATCHED;
             return M3_ERR_UNSUPPORTED;
         }
         // (a set created for such planners, a batch without the section: the batch's own refusal, ahead of the pre kernel)
-        if (h->rollout_scenes_on && !(batch->flags & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES)) {
+        if (h->point_rows.sample_on && !(batch->flags & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES)) {
             rc = batch_refuse(batch, M3_ERR_UNSUPPORTED, (int)eps->live.size(), POINT_ROWS_UNBATCHED);
             eps->err = std::string("m3_episodes_tick: ") + m3_batch_last_error(batch);
             return rc;
@@ -2948,8 +2885,8 @@ static int peps_refuse(int code, int i, const std::string& msg) {
 // which _bind_world pushes from the simulator it follows; the world side's row e is scenes[e] of m3_set_panda_scene_rows, else
 // the world's single scene
 static PandaEpisodesMode peps_mode(int flags) { return (flags & M3_PANDA_EPISODES_RUNTIME) ? PANDA_EPISODES_RUNTIME : PANDA_EPISODES_LITERAL; }
-static const m3_panda_scene& peps_planner_scene(const m3_handle* h) { return h->panda_rollout_scenes_on ? h->panda_rows[0] : h->panda_scene; }
-static const m3_panda_scene& peps_world_scene(const m3_handle* w, int e) { return w->panda_scene_rows_on ? w->panda_rows[e] : w->panda_scene; }
+static const m3_panda_scene& peps_planner_scene(const m3_handle* h) { return h->panda_rows.sample_on ? h->panda_rows.set[0] : h->panda_scene; }
+static const m3_panda_scene& peps_world_scene(const m3_handle* w, int e) { return w->panda_rows.env_on ? w->panda_rows.set[e] : w->panda_scene; }
 
 // Table `side` (0 planning, 1 world) of a run-time set from the handles' current state, on the world's stream: the rows whose
 // workspace changed since the last refresh are packed into the pinned mirror again (make_panda_scene_rt on the host) and the

@@ -482,13 +482,25 @@ void launch_panda_episodes_post(const PandaEpisodesLaunchScene& sc, const PandaE
 
 }  // namespace m3
 
+namespace m3 {
+// One scene per row of a handle (m3_handle::point_rows, ::panda_rows): per environment of a sim_only handle or per sample of a
+// planner's fused rollout.  The three pointers are non-owning views of ledger blocks.
+template <class Scene> struct SceneRows {
+    bool env_on = false;      // sim_only: the step, the views, m3_cost and the episode tick take the per-row kernels
+    bool sample_on = false;   // planner: m3_rollout / m3_command take the per-sample kernels
+    Scene* set = nullptr;     // host [Kl]: what was set (m3_get_*_scene_row / m3_get_*_rollout_scene)
+    float* host = nullptr;    // pinned host [row words][Kl]: the table as uploaded
+    float* dev = nullptr;     // device, the same
+};
+}  // namespace m3
+
 // the ledger's release function bound to HIP (m3_api.hip): the one place that frees
 void m3_release_block(m3::BlockKind kind, void* p);
 
 struct m3_handle {
     m3_config cfg;
     // OWNERSHIP: every block of the handle is an entry of this ledger (owned_blocks.hpp), adopted by one own_* helper call of
-    // m3_api.hip and freed by m3_destroy's release_all().  The named pointers below (buf[], sim_world, order, xb, scene_rows_dev,
+    // m3_api.hip and freed by m3_destroy's release_all().  The named pointers below (buf[], sim_world, order, xb, point_rows.dev,
     // ...) are non-owning views the kernels' argument blocks and the getters read; a new buffer is one helper call, nothing else.
     m3::OwnedBlocks mem{&m3_release_block, 128};
     int* order = nullptr;          // [Kl] lane slot -> local sample (null: identity), sampler.hip
@@ -526,24 +538,12 @@ struct m3_handle {
     m3_point_scene point_scene = m3::POINT_SCENE_DEFAULT;   // m3_set_point_scene (extension, point_env); survives m3_reset
     m3::PointSceneRT scene_rt = {};    // ... with the handle's dt / substeps / iterations (make_point_scene_rt; m3_create, m3_set_point_scene)
     int scene_instance = -1;           // m3_set_point_scene_instance: -1 by the values (not the defaults bit for bit), 0 / 1 forced
-    // m3_set_point_scene_rows (extension, sim_only point_env): one arena per environment; survive m3_reset.  All three blocks
-    // are allocated as one group by the first m3_set_point_scene_rows on the handle; nothing else allocates them.
-    bool scene_rows_on = false;        // the step and the episode tick take the per-row kernels
-    // m3_set_point_rollout_scenes (extension, point_env planner handles): one arena per sample of the fused rollout; survive
-    // m3_reset.  A handle is a planner or sim_only for life, so the rows live in the same three blocks, allocated by the first
-    // m3_set_point_rollout_scenes on the handle.
-    bool rollout_scenes_on = false;    // m3_rollout / m3_command take the per-sample kernels
-    m3_point_scene* scene_rows = nullptr;   // view, host [Kl]: what was set (m3_get_point_scene_row)
-    float* scene_rows_host = nullptr;  // view, pinned host [POINT_SCENE_ROW_WORDS][Kl]: the table as uploaded (point_scene_rows.hpp)
-    float* scene_rows_dev = nullptr;   // view, device, the same
-    // m3_set_panda_scene_rows (sim_only panda_env: one workspace per environment) and m3_set_panda_rollout_scenes (panda_env
-    // planner handles: one per sample of the fused rollout); survive m3_reset.  A handle is a planner or sim_only for life, so
-    // both keep their rows in the same three blocks, allocated as one group by the first setter call on the handle.
-    bool panda_scene_rows_on = false;       // the step, the views and m3_cost take the per-row kernels
-    bool panda_rollout_scenes_on = false;   // m3_rollout / m3_command take the per-sample kernels
-    m3_panda_scene* panda_rows = nullptr;   // view, host [Kl]: what was set (m3_get_panda_scene_row / _rollout_scene)
-    float* panda_rows_host = nullptr;       // view, pinned host [PANDA_SCENE_ROW_WORDS][Kl]: the table as uploaded (panda_scene_rows.hpp)
-    float* panda_rows_dev = nullptr;        // view, device, the same
+    // The rows of a handle, per kind of scene (SceneRows above): m3_set_*_scene_rows on a sim_only handle (one scene per
+    // environment), m3_set_*_rollout_scenes on a planner handle (one per sample of the fused rollout); survive m3_reset.  A handle
+    // is a planner or sim_only for life, so both features keep their rows in the same three blocks, allocated as one group by
+    // the first setter call of that kind on the handle (upload_scene_rows, m3_api.hip); nothing else allocates them.
+    m3::SceneRows<m3_point_scene> point_rows;   // table [POINT_SCENE_ROW_WORDS][Kl] (point_scene_rows.hpp)
+    m3::SceneRows<m3_panda_scene> panda_rows;   // table [PANDA_SCENE_ROW_WORDS][Kl] (panda_scene_rows.hpp)
     // world
     float world0[18];
     const float* world0_bound = nullptr;  // device, 18 floats (filled by world_from_sim)

@@ -6,6 +6,7 @@ path happens inside the HIP kernels.
 """
 from __future__ import annotations
 
+import collections
 import os
 
 import ctypes as C
@@ -101,16 +102,28 @@ class _CObject:
             raise L.M3Error(f"m3p2i_hip error {rc}: {msg.decode() if msg else ''}")
 
 
-def _scene_rows_array(rows):
-    """rows of field overrides over _lib.POINT_SCENE_DEFAULTS (None: the reference's arena) as a PointSceneFields array"""
-    arr = (L.PointSceneFields * max(len(rows), 1))()
-    for i, fields in enumerate(rows):
-        fields = dict(fields or {})
-        unknown = sorted(set(fields) - set(L.POINT_SCENE_DEFAULTS))
-        if unknown:
-            raise ValueError(f"row {i}: unknown point scene field(s) {unknown}: one of {list(L.POINT_SCENE_DEFAULTS)}")
-        arr[i] = L.PointSceneFields(**{**L.POINT_SCENE_DEFAULTS, **{k: float(v) for k, v in fields.items()}})
-    return arr
+def _point_scene_fields(fields, where=""):
+    """PointSceneFields from field overrides over _lib.POINT_SCENE_DEFAULTS (None: the reference's arena)"""
+    fields = dict(fields or {})
+    unknown = sorted(set(fields) - set(L.POINT_SCENE_DEFAULTS))
+    if unknown:
+        raise ValueError(f"{where}unknown point scene field(s) {unknown}: one of {list(L.POINT_SCENE_DEFAULTS)}")
+    return L.PointSceneFields(**{**L.POINT_SCENE_DEFAULTS, **{k: float(v) for k, v in fields.items()}})
+
+
+def _point_scene_dict(sc):
+    return {n: getattr(sc, n) for n in L.POINT_SCENE_DEFAULTS}
+
+
+# A kind of scene rows, the point_env arena or the panda_env workspace: the C struct, row i's mapping -> struct (ValueError for an
+# unknown field), struct -> mapping, and the C (setter, getter) per environment of a sim_only engine and per sample of a planner.
+_SceneKind = collections.namedtuple("_SceneKind", "struct from_row to_dict env_rows sample_rows")
+_POINT_ROWS = _SceneKind(L.PointSceneFields, lambda i, fields: _point_scene_fields(fields, f"row {i}: "), _point_scene_dict,
+                         ("m3_set_point_scene_rows", "m3_get_point_scene_row"),
+                         ("m3_set_point_rollout_scenes", "m3_get_point_rollout_scene"))
+_PANDA_ROWS = _SceneKind(L.PandaSceneFields, lambda i, fields: L.panda_scene_fields(fields), L.panda_scene_dict,
+                         ("m3_set_panda_scene_rows", "m3_get_panda_scene_row"),
+                         ("m3_set_panda_rollout_scenes", "m3_get_panda_rollout_scene"))
 
 
 class HipEngine(_CObject):
@@ -296,32 +309,43 @@ class HipEngine(_CObject):
         if not fields:
             self._ck(self.lib.m3_set_point_scene(self._h, None))
             return
-        unknown = sorted(set(fields) - set(L.POINT_SCENE_DEFAULTS))
-        if unknown:
-            raise ValueError(f"unknown point scene field(s) {unknown}: one of {list(L.POINT_SCENE_DEFAULTS)}")
-        sc = L.PointSceneFields(**{**L.POINT_SCENE_DEFAULTS, **{k: float(v) for k, v in fields.items()}})
+        sc = _point_scene_fields(fields)
         self._ck(self.lib.m3_set_point_scene(self._h, C.byref(sc)))
 
     def point_scene(self):
         sc = L.PointSceneFields()
         self._ck(self.lib.m3_get_point_scene(self._h, C.byref(sc)))
-        return {n: getattr(sc, n) for n in L.POINT_SCENE_DEFAULTS}
+        return _point_scene_dict(sc)
+
+    def _set_rows(self, kind, per_sample, rows):
+        """one scene per environment (sim_only engines) or, per_sample, per sample of the fused rollout (planner engines);
+        rows=None clears"""
+        setter = getattr(self.lib, (kind.sample_rows if per_sample else kind.env_rows)[0])
+        if rows is None:
+            self._ck(setter(self._h, None, 0))
+            return
+        rows = list(rows)
+        # (never a zero-length array, so that an empty list is a wrong length and not the null pointer that clears; the library
+        # reads the rows only once n == K_local)
+        arr = (kind.struct * max(len(rows), 1))()
+        for i, fields in enumerate(rows):
+            arr[i] = kind.from_row(i, fields)
+        self._ck(setter(self._h, arr, len(rows)))
+
+    def _get_row(self, kind, per_sample, i):
+        sc = kind.struct()
+        self._ck(getattr(self.lib, (kind.sample_rows if per_sample else kind.env_rows)[1])(self._h, int(i), C.byref(sc)))
+        return kind.to_dict(sc)
 
     def set_point_scene_rows(self, rows=None):
         """Extension, sim_only point_env engines: one arena per environment -- rows[i] the field overrides of environment i
         over _lib.POINT_SCENE_DEFAULTS (None: the reference's arena); len(rows) == K_local.  rows=None clears: the engine is
         back on its single scene.  Applies from the next step / episode tick; set_point_scene afterwards clears the rows."""
-        if rows is None:
-            self._ck(self.lib.m3_set_point_scene_rows(self._h, None, 0))
-            return
-        rows = list(rows)
-        self._ck(self.lib.m3_set_point_scene_rows(self._h, _scene_rows_array(rows), len(rows)))
+        self._set_rows(_POINT_ROWS, False, rows)
 
     def point_scene_row(self, i):
         """environment i's arena as set by set_point_scene_rows (all fields)"""
-        sc = L.PointSceneFields()
-        self._ck(self.lib.m3_get_point_scene_row(self._h, int(i), C.byref(sc)))
-        return {n: getattr(sc, n) for n in L.POINT_SCENE_DEFAULTS}
+        return self._get_row(_POINT_ROWS, False, i)
 
     def point_scene_rows_set(self):
         return self.lib.m3_point_scene_rows_set(self._h) == 1
@@ -332,17 +356,11 @@ class HipEngine(_CObject):
         K_local.  rows=None clears: the engine is back on its single scene.  Applies from the next rollout / command;
         set_point_scene afterwards clears the rows.  The special samples (K - 1; multi-modal: 0 and K / 2) get their rows like
         any other: scenes.spread_point_scenes keeps them nominal."""
-        if rows is None:
-            self._ck(self.lib.m3_set_point_rollout_scenes(self._h, None, 0))
-            return
-        rows = list(rows)
-        self._ck(self.lib.m3_set_point_rollout_scenes(self._h, _scene_rows_array(rows), len(rows)))
+        self._set_rows(_POINT_ROWS, True, rows)
 
     def point_rollout_scene(self, i):
         """local sample i's arena as set by set_point_rollout_scenes (all fields)"""
-        sc = L.PointSceneFields()
-        self._ck(self.lib.m3_get_point_rollout_scene(self._h, int(i), C.byref(sc)))
-        return {n: getattr(sc, n) for n in L.POINT_SCENE_DEFAULTS}
+        return self._get_row(_POINT_ROWS, True, i)
 
     def point_rollout_scenes_set(self):
         return self.lib.m3_point_rollout_scenes_set(self._h) == 1
@@ -378,28 +396,16 @@ class HipEngine(_CObject):
         """whether the last rollout or step launched the run-time-scene instance"""
         return self.lib.m3_panda_scene_instance_used(self._h) == 1
 
-    def _panda_rows_array(self, rows):
-        arr = (L.PandaSceneFields * len(rows))()
-        for i, r in enumerate(rows):
-            arr[i] = L.panda_scene_fields(r)     # (None: the reference's workspace; ValueError for an unknown field)
-        return arr
-
     def set_panda_scene_rows(self, rows=None):
         """Extension, sim_only panda_env engines: one workspace per environment -- rows[i] the field overrides of environment i
         over _lib.PANDA_SCENE_DEFAULTS (None: the reference's workspace); len(rows) == K_local.  rows=None clears: the engine
         is back on its single workspace.  Applies from the next step / cost / view refresh; set_panda_scene afterwards clears
         the rows."""
-        if rows is None:
-            self._ck(self.lib.m3_set_panda_scene_rows(self._h, None, 0))
-            return
-        rows = list(rows)
-        self._ck(self.lib.m3_set_panda_scene_rows(self._h, self._panda_rows_array(rows), len(rows)))
+        self._set_rows(_PANDA_ROWS, False, rows)
 
     def panda_scene_row(self, i):
         """environment i's workspace as set by set_panda_scene_rows (all fields)"""
-        sc = L.PandaSceneFields()
-        self._ck(self.lib.m3_get_panda_scene_row(self._h, int(i), C.byref(sc)))
-        return L.panda_scene_dict(sc)
+        return self._get_row(_PANDA_ROWS, False, i)
 
     def panda_scene_rows_set(self):
         return self.lib.m3_panda_scene_rows_set(self._h) == 1
@@ -410,17 +416,11 @@ class HipEngine(_CObject):
         K_local.  rows=None clears: the engine is back on its single workspace.  Applies from the next rollout / command;
         set_panda_scene afterwards clears the rows.  The reach cost reads the cube of sample 0 as simulated in rows[0] (quirk
         Q8; multi-modal: the orientation of sample K / 2 in its row): scenes.spread_panda_scenes keeps those rows nominal."""
-        if rows is None:
-            self._ck(self.lib.m3_set_panda_rollout_scenes(self._h, None, 0))
-            return
-        rows = list(rows)
-        self._ck(self.lib.m3_set_panda_rollout_scenes(self._h, self._panda_rows_array(rows), len(rows)))
+        self._set_rows(_PANDA_ROWS, True, rows)
 
     def panda_rollout_scene(self, i):
         """local sample i's workspace as set by set_panda_rollout_scenes (all fields)"""
-        sc = L.PandaSceneFields()
-        self._ck(self.lib.m3_get_panda_rollout_scene(self._h, int(i), C.byref(sc)))
-        return L.panda_scene_dict(sc)
+        return self._get_row(_PANDA_ROWS, True, i)
 
     def panda_rollout_scenes_set(self):
         return self.lib.m3_panda_rollout_scenes_set(self._h) == 1

@@ -25,6 +25,7 @@ late, Q6 null action on the zero-noise sample, Q7 push_pull evaluates both costs
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import Callable, List, Optional
 
@@ -92,6 +93,14 @@ def _get(cfg, name, default=None):
         return getattr(cfg, name)
     except Exception:
         return default
+
+
+# A kind of scene rows as the planner sees it: the attached wrapper's per-environment rows, the engine's setter, where the planner
+# keeps what it pushed last and its own rows, and the public setter's name (its ValueError texts).
+_SceneKind = namedtuple("_SceneKind", "env_type sim_rows set_rows rows_pushed own_rows public_setter")
+_POINT = _SceneKind("point_env", "point_scenes", "set_point_rollout_scenes", "_sim_rows_pushed", "_rollout_scenes", "set_rollout_scenes")
+_PANDA = _SceneKind("panda_env", "panda_scenes", "set_panda_rollout_scenes", "_sim_panda_rows_pushed", "_panda_rollout_scenes",
+                    "set_panda_rollout_scenes")
 
 
 class MPPI():
@@ -383,7 +392,8 @@ class MPPI():
             self._engine.set_point_scene(arena)
             self._point_scene_pushed = None if arena is None else dict(arena)
             arena_pushed = True
-        # (extension, off by default, panda_env: the wrapper's workspace, by the same rule)
+        # (extension, off by default, panda_env: the wrapper's workspace, by the same rule)  Each environment's rows follow its
+        # single scene, which clears the library's rows: the last call wins there.
         if self.env_type == "panda_env":
             ws = getattr(s, "panda_scene", None)
             ws_pushed = False
@@ -391,42 +401,9 @@ class MPPI():
                 self._engine.set_panda_scene(ws)
                 self._panda_scene_pushed = None if ws is None else dict(ws)
                 ws_pushed = True
-            # (extension, off by default) one workspace per SAMPLE, by the rule of the point arenas below: the rows of a followed
-            # wrapper with one environment per local sample (IsaacGymWrapper(panda_scenes=...)) are pushed once, and again when
-            # the wrapper holds another list or the single workspace was pushed (which clears the library's rows); rows set by
-            # hand (set_panda_rollout_scenes) stand wherever no wrapper's rows are followed
-            rows = self._followed_sim_panda_rows()
-            if rows is not None:
-                if ws_pushed or not self._same_rows(rows, getattr(self, "_sim_panda_rows_pushed", None)):
-                    self._engine.set_panda_rollout_scenes(rows)
-                    self._sim_panda_rows_pushed = rows
-            else:
-                was_following = getattr(self, "_sim_panda_rows_pushed", None) is not None
-                self._sim_panda_rows_pushed = None
-                mine = getattr(self, "_panda_rollout_scenes", None)
-                if mine is not None and (ws_pushed or was_following):
-                    self._engine.set_panda_rollout_scenes(mine[self.k_offset:self.k_offset + self.K_local])
-                elif was_following:
-                    self._engine.set_panda_rollout_scenes(None)
-        # (extension, off by default) one arena per SAMPLE: the fused rollout is the step path on a wrapper whose K_local
-        # environments carry their own arenas (IsaacGymWrapper(point_scenes=...)), so while the planner follows its wrapper it
-        # takes those rows over -- once, and again when the wrapper holds another list (or the single arena was pushed, which
-        # clears the library's rows: the last call wins there).  Rows set by hand (set_rollout_scenes) stand wherever no
-        # wrapper's rows are followed.
+            self._sync_rollout_rows(_PANDA, ws_pushed)
         if self.env_type == "point_env":
-            rows = self._followed_sim_rows()
-            if rows is not None:
-                if arena_pushed or not self._same_rows(rows, getattr(self, "_sim_rows_pushed", None)):
-                    self._engine.set_point_rollout_scenes(rows)
-                    self._sim_rows_pushed = rows
-            else:
-                was_following = getattr(self, "_sim_rows_pushed", None) is not None
-                self._sim_rows_pushed = None
-                mine = getattr(self, "_rollout_scenes", None)
-                if mine is not None and (arena_pushed or was_following):
-                    self._engine.set_point_rollout_scenes(mine[self.k_offset:self.k_offset + self.K_local])
-                elif was_following:
-                    self._engine.set_point_rollout_scenes(None)
+            self._sync_rollout_rows(_POINT, arena_pushed)
         if getattr(self, "_bound_sim", None) is not s:
             if self.env_type == "point_env":
                 self._engine.bind_sim_point(s._dof_state, s._root_state,
@@ -444,29 +421,55 @@ class MPPI():
         """the same list object (the common case, no work per command), or equal rows"""
         return a is b or (b is not None and len(a) == len(b) and all(x == y for x, y in zip(a, b)))
 
-    def _followed_sim_rows(self):
-        """the per-environment arenas of the attached wrapper this planner's samples take over, or None: only while
+    def _followed_sim_rows(self, kind):
+        """the per-environment scenes of the attached wrapper this planner's samples take over, or None: only while
         follow_sim_scene holds and the wrapper has one environment per local sample"""
         s = self._sim
-        rows = getattr(s, "point_scenes", None) if s is not None else None
+        rows = getattr(s, kind.sim_rows, None) if s is not None else None
         if rows is None or not getattr(self, "follow_sim_scene", True) or getattr(s, "num_envs", None) != self.K_local:
             return None
         return rows
 
-    def _followed_sim_panda_rows(self):
-        """the per-environment workspaces of the attached wrapper this planner's samples take over, or None: only while
-        follow_sim_scene holds and the wrapper has one environment per local sample"""
-        s = self._sim
-        rows = getattr(s, "panda_scenes", None) if s is not None else None
-        if rows is None or not getattr(self, "follow_sim_scene", True) or getattr(s, "num_envs", None) != self.K_local:
-            return None
-        return rows
+    def _sync_rollout_rows(self, kind, single_pushed):
+        """(extension, off by default) One scene per SAMPLE: the fused rollout is the step path on a wrapper whose K_local
+        environments carry their own scenes (IsaacGymWrapper(point_scenes=... / panda_scenes=...)), so while the planner follows
+        its wrapper it takes those rows over -- once, and again when the wrapper holds another list or the single scene was
+        pushed.  Rows set by hand (set_rollout_scenes / set_panda_rollout_scenes) stand wherever no wrapper's rows are followed."""
+        rows = self._followed_sim_rows(kind)
+        pushed = getattr(self, kind.rows_pushed, None)
+        if rows is not None:
+            if single_pushed or not self._same_rows(rows, pushed):
+                getattr(self._engine, kind.set_rows)(rows)
+                setattr(self, kind.rows_pushed, rows)
+            return
+        setattr(self, kind.rows_pushed, None)
+        mine = getattr(self, kind.own_rows, None)
+        if mine is not None and (single_pushed or pushed is not None):
+            getattr(self._engine, kind.set_rows)(mine[self.k_offset:self.k_offset + self.K_local])
+        elif pushed is not None:
+            getattr(self._engine, kind.set_rows)(None)
+
+    def _set_rollout_rows(self, kind, rows):
+        if self.env_type != kind.env_type:
+            raise ValueError(f"{kind.public_setter}: {kind.env_type} only")
+        push = getattr(self._engine, kind.set_rows)
+        if rows is None:
+            setattr(self, kind.own_rows, None)
+            setattr(self, kind.rows_pushed, None)      # (a followed wrapper's rows are pushed again by the next command)
+            push(None)
+            return
+        rows = list(rows)
+        if len(rows) != self.K:
+            raise ValueError(f"{kind.public_setter}: {len(rows)} rows for num_samples = {self.K} (the global list)")
+        push(rows[self.k_offset:self.k_offset + self.K_local])
+        setattr(self, kind.own_rows, rows)
+        setattr(self, kind.rows_pushed, None)
 
     @property
     def has_panda_rollout_scenes(self):
         """the fused rollout runs (or, from its next command on, will run) one workspace per sample"""
         return self.env_type == "panda_env" and (getattr(self, "_panda_rollout_scenes", None) is not None
-                                                 or self._followed_sim_panda_rows() is not None)
+                                                 or self._followed_sim_rows(_PANDA) is not None)
 
     def set_panda_rollout_scenes(self, rows):
         """Extension, panda_env: one workspace per sample of the fused rollout (m3_set_panda_rollout_scenes) -- `rows` the
@@ -474,19 +477,7 @@ class MPPI():
         this planner pushes its shard's slice; None clears.  scenes.spread_panda_scenes builds such a list with the special
         samples kept nominal.  A wrapper with `panda_scenes` that this planner follows (follow_sim_scene) overrides rows set
         here."""
-        if self.env_type != "panda_env":
-            raise ValueError("set_panda_rollout_scenes: panda_env only")
-        if rows is None:
-            self._panda_rollout_scenes = None
-            self._sim_panda_rows_pushed = None      # (a followed wrapper's rows are pushed again by the next command)
-            self._engine.set_panda_rollout_scenes(None)
-            return
-        rows = list(rows)
-        if len(rows) != self.K:
-            raise ValueError(f"set_panda_rollout_scenes: {len(rows)} rows for num_samples = {self.K} (the global list)")
-        self._engine.set_panda_rollout_scenes(rows[self.k_offset:self.k_offset + self.K_local])
-        self._panda_rollout_scenes = rows
-        self._sim_panda_rows_pushed = None
+        self._set_rollout_rows(_PANDA, rows)
 
     @property
     def needs_panda_scene_instance(self):
@@ -520,26 +511,14 @@ class MPPI():
     def has_rollout_scenes(self):
         """the fused rollout runs (or, from its next command on, will run) one arena per sample"""
         return self.env_type == "point_env" and (getattr(self, "_rollout_scenes", None) is not None
-                                                 or self._followed_sim_rows() is not None)
+                                                 or self._followed_sim_rows(_POINT) is not None)
 
     def set_rollout_scenes(self, rows):
         """Extension, point_env: one arena per sample of the fused rollout (m3_set_point_rollout_scenes) -- `rows` the GLOBAL
         list of K field-override dicts (None entries: the reference's arena), of which this planner pushes its shard's slice;
         None clears.  scenes.spread_point_scenes builds such a list with the special samples kept nominal.  A wrapper with
         `point_scenes` that this planner follows (follow_sim_scene) overrides rows set here."""
-        if self.env_type != "point_env":
-            raise ValueError("set_rollout_scenes: point_env only")
-        if rows is None:
-            self._rollout_scenes = None
-            self._sim_rows_pushed = None      # (a followed wrapper's rows are pushed again by the next command)
-            self._engine.set_point_rollout_scenes(None)
-            return
-        rows = list(rows)
-        if len(rows) != self.K:
-            raise ValueError(f"set_rollout_scenes: {len(rows)} rows for num_samples = {self.K} (the global list)")
-        self._engine.set_point_rollout_scenes(rows[self.k_offset:self.k_offset + self.K_local])
-        self._rollout_scenes = rows
-        self._sim_rows_pushed = None
+        self._set_rollout_rows(_POINT, rows)
 
     def _exchange(self, phase):
         if self.collective is None:

@@ -46,7 +46,7 @@ struct FakeAlloc {
 
 static void* failing_grow(void*, size_t) { return nullptr; }
 
-// the shape of ensure_sim / refresh_wave_order / upload_point_scene_rows: three views, allocated as one group on first use
+// the shape of ensure_sim / refresh_wave_order / upload_scene_rows: three views, allocated as one group on first use
 struct Obj {
     OwnedBlocks mem{&recording_release, 8};
     int* order = nullptr;

@@ -110,8 +110,8 @@ def test_the_destroy_functions_have_no_per_member_lines(sources):
 
 
 def test_the_lazy_groups_allocate_under_one_guard(sources):
-    bodies, _ = function_bodies(sources["m3_api.hip"], r"ensure_sim|refresh_wave_order|upload_point_scene_rows|m3_enable_timing")
-    for name, n_blocks in (("ensure_sim", 2), ("refresh_wave_order", 3), ("upload_point_scene_rows", 3), ("m3_enable_timing", 1)):
+    bodies, _ = function_bodies(sources["m3_api.hip"], r"ensure_sim|refresh_wave_order|upload_scene_rows|m3_enable_timing")
+    for name, n_blocks in (("ensure_sim", 2), ("refresh_wave_order", 3), ("upload_scene_rows", 3), ("m3_enable_timing", 1)):
         body = bodies[name]
         g = body.index("BlockGroup g(h->mem)")
         keep = body.index("g.keep = true")
