@@ -578,6 +578,52 @@ int m3_point_rollout_scenes_set(const m3_handle* h);   /* 0 / 1 */
 int m3_point_rollout_plan(int task, int multi_modal, int mode_simple, int sampling_random, int avoid_dyn_obs, int K_local, int T,
                           int lanes, float dt, int substeps, int solver_iters, int weighted, int scene, int form_request,
                           int want_minima, int out[8]);
+/* The same with `priors`: 1 for a handle with prior samples set (m3_set_prior_samples below; scene is then 1, or 2 with an arena
+ * per sample -- scene = 0 is M3_ERR_BAD_ARG, as a handle with priors always runs the run-time-scene instance).  out[0 .. 7] as
+ * above (instance -1, ref 0, form 0, weighted 1, scene 1 or 2), out[8] = priors. */
+int m3_point_rollout_plan_ex(int task, int multi_modal, int mode_simple, int sampling_random, int avoid_dyn_obs, int K_local, int T,
+                             int lanes, float dt, int substeps, int solver_iters, int weighted, int scene, int form_request,
+                             int want_minima, int priors, int out[9]);
+/* EXTENSION, point_env PLANNER handles, unsharded: PRIOR SAMPLES -- a few of the K samples of the fused rollout take a control
+ * sequence of the caller verbatim instead of clamp(mean + noise): the proposals of ancillary controllers (a straight line to the
+ * goal, "go behind the box and push", yesterday's plan, a learned policy), as in Biased-MPPI.  The softmin update is unchanged.
+ * seqs: host, [n][T][nu] (sample-major, the reference's layout); sample_idx: host, [n] GLOBAL sample indices.
+ * Sample sample_idx[j] of the next rollouts takes a[t] = clamp(seqs[j][t], u_min, u_max), in both mppi modes and with both
+ * samplers.  seqs[j][t] is the control of step t of THIS command's horizon: the library shifts nothing between commands, and
+ * the priors stay as set until replaced or cleared -- a caller that plans every tick sets them every tick.  Everything behind
+ * the select is unchanged: the u_scale multiplication, what is stored in M3_BUF_ACTIONS, the simple mode's noise = e - m
+ * perturbation cost, the update (weights, means, best rows, update_cov, top-k).  The choice of index has a meaning only in
+ * multi-modal mode, where k < K/2 belongs to mode 1 and k >= K/2 to mode 2: a prior informs the mode whose half it sits in.
+ * The prior follows the sample, not the wavefront slot -- as the arena row and the cost weights do: m3_set_wave_order,
+ * m3_relabel_samples and m3_set_rollout_lanes do not change which sample is a prior.  seqs == NULL or n == 0 clears the priors:
+ * the handle then launches exactly the kernels it launched before the call existed.  Survives m3_reset.
+ * Refused, every check before any state changes, the message names the entry: M3_ERR_BAD_ARG for n < 0 or n >
+ * M3_MAX_PRIOR_SAMPLES, a null sample_idx, an index outside 0 .. K_global - 1, index K_global - 1 (the zero-noise / null-action
+ * sample), in multi-modal mode index 0 or K/2 (the best-trajectory samples), an index listed twice ("prior 3: sample 17 listed
+ * twice"), a non-finite value ("prior 2: step 5 control 1 is not finite"; host variant only); M3_ERR_UNSUPPORTED for a
+ * panda_env handle and for a sharded handle (K_local != K_global); M3_ERR_STATE for a sim_only handle.
+ * Which kernels run.  A handle with priors set runs the prior build of the general, weighted, run-time-scene rollout instance
+ * (rollout_point_priors.hip; with or without an arena per sample, tuned cost weights keep working); the two-wavefront form is
+ * never taken; m3_point_rollout_plan_ex(..., priors = 1, ...) reports the launch.  m3_set_point_scene_instance(h, 0) with priors
+ * set refuses the next rollout (M3_ERR_STATE).
+ * NOT batched: m3_batch_command with such a handle and m3_episodes_create* / m3_episodes_tick / _begin / _end with such a planner
+ * return M3_ERR_UNSUPPORTED whatever batch they are given (the message names m3_set_prior_samples and the index of the
+ * handle); nothing is launched and every handle stays as it was.
+ * Memory: the first call on a handle allocates, through the handle's ledger, a device table of M3_MAX_PRIOR_SAMPLES x T x nu
+ * floats, a device slot map int[K_local] (-1: no prior), one pinned host block that mirrors both, and the event below; later
+ * calls reuse them.  Uploads are hipMemcpyAsync on the handle's stream.  Before the mirror is rewritten the setter waits for
+ * the previous upload only, through an event recorded behind it -- not for the stream.  The slot map is uploaded again only when
+ * the indices changed.  m3_rollout and m3_command allocate nothing and synchronise nothing because of priors. */
+#define M3_MAX_PRIOR_SAMPLES 256
+int m3_set_prior_samples(m3_handle* h, const float* seqs, const int* sample_idx, int n);
+/* the same with seqs in DEVICE memory (an ancillary controller that runs on the GPU): one device-to-device hipMemcpyAsync on
+ * the handle's stream; the values are not inspected (the kernel clamps them; a NaN stays a NaN) */
+int m3_set_prior_samples_device(m3_handle* h, const float* seqs_dev, const int* sample_idx, int n);
+int m3_prior_samples_set(const m3_handle* h);   /* n (0: none) */
+/* prior j as it was set: its sample index and, if seq != NULL, its [T][nu] values (host-set priors only: M3_ERR_STATE with seq
+ * != NULL after m3_set_prior_samples_device); M3_ERR_BAD_ARG for j outside 0 .. n - 1 */
+int m3_get_prior_sample(const m3_handle* h, int j, int* sample_idx, float* seq);
+int m3_prior_samples_used(m3_handle* h);        /* 0 / 1: the last rollout launched the prior build; -1 before the first */
 /* Diagnostic, host only (no device call, no handle): the blocks -- device, pinned and host memory, events, peer mappings -- that
  * the process's handles, batches and episode sets hold right now.  Every object owns its memory through one ledger; an object's
  * destroy call takes its blocks off the count, so after every object is destroyed the count is what it was before the first. */

@@ -9,6 +9,7 @@ import ctypes as C
 import os
 
 MAX_NU = 9
+MAX_PRIOR_SAMPLES = 256
 TOPK = 20
 ABI_VERSION = 4
 
@@ -232,6 +233,12 @@ SYMBOLS = [
     ("m3_set_panda_weighted_cost_instance", C.c_int, [_H, C.c_int]),
     ("m3_panda_weighted_cost_instance_used", C.c_int, [_H]),
     ("m3_point_rollout_plan", C.c_int, [C.c_int] * 8 + [C.c_float] + [C.c_int] * 6 + [C.POINTER(C.c_int)]),
+    ("m3_point_rollout_plan_ex", C.c_int, [C.c_int] * 8 + [C.c_float] + [C.c_int] * 7 + [C.POINTER(C.c_int)]),
+    ("m3_set_prior_samples", C.c_int, [_H, C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    ("m3_set_prior_samples_device", C.c_int, [_H, C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    ("m3_prior_samples_set", C.c_int, [_H]),
+    ("m3_get_prior_sample", C.c_int, [_H, C.c_int, C.POINTER(C.c_int), _FP]),
+    ("m3_prior_samples_used", C.c_int, [_H]),
     ("m3_owned_blocks_live", C.c_longlong, []),
     ("m3_set_multi_modal", C.c_int, [_H, C.c_int]),
     ("m3_set_plan", C.c_int, [_H, C.c_int, _FP]),

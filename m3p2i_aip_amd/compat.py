@@ -143,6 +143,10 @@ class ExampleConfig:
                                                                # each in an arena of their own around point_scene (the samples
                                                                # 0, K / 2 and K - 1 stay nominal); rollout_point_scenes builds
                                                                # the rows the planner's K-env simulator carries
+    prior_samples: Optional[Dict[str, object]] = None   # EXTENSION, point_env: `prior_samples={controller: go_to, n: 4}` -- n of the
+                                                        # K rollouts take the proposals of a host-side ancillary controller
+                                                        # (priors.go_to / priors.push_behind), set before every command
+                                                        # (tools/closed_loop.py; MPPI.set_prior_samples)
     rollout_workspace_spread: Optional[Dict[str, object]] = None   # EXTENSION, panda_env: `rollout_workspace_spread={spread: 0.3,
                                                                    # seed: 1, fields: [cube_m, mu, obs_m]}` -- the planner's K
                                                                    # rollouts each in a workspace of their own around panda_scene
@@ -196,6 +200,9 @@ def make_config(config_name="config_point", overrides=()):
     if cfg.rollout_arena_spread:
         cfg.rollout_arena_spread = dict(cfg.rollout_arena_spread)
         _check_rollout_arena_spread(cfg)
+    if cfg.prior_samples:
+        cfg.prior_samples = dict(cfg.prior_samples)
+        check_prior_samples(cfg)
     if cfg.rollout_workspace_spread:
         cfg.rollout_workspace_spread = dict(cfg.rollout_workspace_spread)
         _check_rollout_workspace_spread(cfg)
@@ -221,6 +228,30 @@ def make_config(config_name="config_point", overrides=()):
         if unknown:
             raise ValueError(f"panda_cost_weights: unknown panda cost weight(s) {unknown}: one of {list(PANDA_COST_WEIGHT_DEFAULTS)}")
     return cfg
+
+
+def check_prior_samples(cfg):
+    """the parsed `prior_samples` key as (controller name, n); ValueError for what it cannot mean"""
+    from . import _lib, priors
+    given = dict(cfg.prior_samples)
+    if cfg.env_type != "point_env":
+        raise ValueError("prior_samples: point_env only")
+    unknown = sorted(set(given) - {"controller", "n"})
+    if unknown or given.get("controller") not in priors.CONTROLLERS:
+        raise ValueError(f"prior_samples: {{controller: {' | '.join(priors.CONTROLLERS)}, n: 4}} (unknown key(s) {unknown})")
+    n = int(given.get("n", 4))
+    if not 1 <= n <= min(_lib.MAX_PRIOR_SAMPLES, int(cfg.mppi.num_samples) // 2 - 2):
+        raise ValueError(f"prior_samples: n {n} is not in 1 .. min({_lib.MAX_PRIOR_SAMPLES}, num_samples / 2 - 2)")
+    return str(given["controller"]), n
+
+
+def prior_sample_indices(K, n, multi_modal):
+    """where the n priors of the `prior_samples` key sit among the K samples: the first n non-special samples; in
+    multi-modal mode split between the two halves, so that both modes hear the controller"""
+    if not multi_modal:
+        return list(range(n))
+    first = (n + 1) // 2
+    return list(range(1, 1 + first)) + list(range(K // 2 + 1, K // 2 + 1 + n - first))
 
 
 ROLLOUT_ARENA_SPREAD_KEYS = ("spread", "seed", "fields")

@@ -1045,6 +1045,104 @@ extern "C" int m3_set_panda_scene_instance(m3_handle* h, int on) {
     return set_instance(h, M3_ENV_PANDA, &m3_handle::panda_scene_instance, on, "m3_set_panda_scene_instance", "values");
 }
 
+// ---- prior samples (extension, point_env planner handles, unsharded): samples of the fused rollout that take the caller's
+// control sequences.  THE allocation of the feature is the first setter call on a handle; m3_rollout and m3_command read the
+// two device blocks, nothing else.  Every check before any state changes ----
+static int set_prior_samples(m3_handle* h, const float* seqs, const int* sample_idx, int n, bool device) {
+    if (!h) return M3_ERR_BAD_ARG;
+    const std::string who = device ? "m3_set_prior_samples_device" : "m3_set_prior_samples";
+    const m3_config& c = h->cfg;
+    if (c.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, (who + env_only_text(M3_ENV_POINT)).c_str());
+    if (c.sim_only) return fail(h, M3_ERR_STATE, (who + ": planner handles only (the handle was created sim_only)").c_str());
+    if (c.K_local != c.K_global) return fail(h, M3_ERR_UNSUPPORTED, (who + ": sharded handle (K_local != K_global)").c_str());
+    if (n < 0 || n > M3_MAX_PRIOR_SAMPLES)
+        return fail(h, M3_ERR_BAD_ARG, (who + ": n is " + std::to_string(n) + ", must be in 0 .. " + std::to_string(M3_MAX_PRIOR_SAMPLES)).c_str());
+    PriorSampleState& ps = h->priors;
+    if (!seqs || n == 0) {   // exactly the kernels of a handle that never had priors (the blocks are kept for a later call)
+        ps.n = 0;
+        return M3_OK;
+    }
+    if (!sample_idx) return fail(h, M3_ERR_BAD_ARG, (who + ": null sample_idx").c_str());
+    const int K = c.K_global, T = c.T, nu = c.nu;
+    for (int j = 0; j < n; ++j) {
+        const int k = sample_idx[j];
+        const std::string at = who + ": prior " + std::to_string(j) + ": sample " + std::to_string(k);
+        if (k < 0 || k >= K) return fail(h, M3_ERR_BAD_ARG, (at + " is outside 0 .. K_global - 1 = " + std::to_string(K - 1)).c_str());
+        if (k == K - 1) return fail(h, M3_ERR_BAD_ARG, (at + " is the zero-noise / null-action sample K_global - 1").c_str());
+        if (c.multi_modal && (k == 0 || k == K / 2))
+            return fail(h, M3_ERR_BAD_ARG, (at + " is a best-trajectory sample of the multi-modal planner (0 and K/2)").c_str());
+        for (int q = 0; q < j; ++q)
+            if (sample_idx[q] == k) return fail(h, M3_ERR_BAD_ARG, (at + " listed twice").c_str());
+    }
+    if (!device)
+        for (int j = 0; j < n; ++j)
+            for (int t = 0; t < T; ++t)
+                for (int u = 0; u < nu; ++u)
+                    if (!std::isfinite(seqs[((size_t)j * T + t) * nu + u]))
+                        return fail(h, M3_ERR_BAD_ARG, (who + ": prior " + std::to_string(j) + ": step " + std::to_string(t) + " control " +
+                                                        std::to_string(u) + " is not finite").c_str());
+    const int Kl = c.K_local;
+    const size_t tab_bytes = (size_t)M3_MAX_PRIOR_SAMPLES * T * nu * sizeof(float), slot_bytes = (size_t)Kl * sizeof(int);
+    bool slots_stale = false;
+    if (!ps.tab_dev) {
+        BlockGroup g(h->mem);   // all or none
+        hipError_t e = own_device(h->mem, ps.tab_dev, tab_bytes);
+        if (e == hipSuccess) e = own_device(h->mem, ps.slot_dev, slot_bytes);
+        if (e == hipSuccess) e = own_pinned(h->mem, ps.pinned, tab_bytes + slot_bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = own_event(h->mem, ps.uploaded, hipEventDisableTiming);
+        if (e != hipSuccess) return fail(h, M3_ERR_HIP, (who + ": " + hipGetErrorString(e)).c_str());
+        g.keep = true;
+        int* slot = reinterpret_cast<int*>(ps.pinned + (size_t)M3_MAX_PRIOR_SAMPLES * T * nu);
+        for (int i = 0; i < Kl; ++i) slot[i] = -1;
+        ps.dev_n = 0;
+        slots_stale = true;
+    } else if (ps.upload_pending) {
+        // the pinned mirror is the source of the previous call's asynchronous uploads: those copies, and only those, are over
+        // before it is rewritten
+        HIPCHK(h, hipEventSynchronize(ps.uploaded));
+        ps.upload_pending = false;
+    }
+    int* slot = reinterpret_cast<int*>(ps.pinned + (size_t)M3_MAX_PRIOR_SAMPLES * T * nu);
+    if (slots_stale || ps.dev_n != n || std::memcmp(ps.idx, sample_idx, (size_t)n * sizeof(int)) != 0) {
+        for (int j = 0; j < ps.dev_n; ++j) slot[ps.idx[j] - c.k_offset] = -1;
+        for (int j = 0; j < n; ++j) slot[sample_idx[j] - c.k_offset] = j;
+        std::memcpy(ps.idx, sample_idx, (size_t)n * sizeof(int));
+        ps.dev_n = n;
+        HIPCHK(h, hipMemcpyAsync(ps.slot_dev, slot, slot_bytes, hipMemcpyHostToDevice, h->stream));
+    }
+    const size_t bytes = (size_t)n * T * nu * sizeof(float);
+    if (device) {
+        HIPCHK(h, hipMemcpyAsync(ps.tab_dev, seqs, bytes, hipMemcpyDeviceToDevice, h->stream));
+    } else {
+        std::memcpy(ps.pinned, seqs, bytes);
+        HIPCHK(h, hipMemcpyAsync(ps.tab_dev, ps.pinned, bytes, hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(h, hipEventRecord(ps.uploaded, h->stream));
+    ps.upload_pending = true;
+    ps.host_values = !device;
+    ps.n = n;
+    return M3_OK;
+}
+extern "C" int m3_set_prior_samples(m3_handle* h, const float* seqs, const int* sample_idx, int n) {
+    return set_prior_samples(h, seqs, sample_idx, n, false);
+}
+extern "C" int m3_set_prior_samples_device(m3_handle* h, const float* seqs_dev, const int* sample_idx, int n) {
+    return set_prior_samples(h, seqs_dev, sample_idx, n, true);
+}
+extern "C" int m3_prior_samples_set(const m3_handle* h) { return h ? h->priors.n : M3_ERR_BAD_ARG; }
+extern "C" int m3_get_prior_sample(const m3_handle* h, int j, int* sample_idx, float* seq) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_POINT) return M3_ERR_UNSUPPORTED;
+    const PriorSampleState& ps = h->priors;
+    if (j < 0 || j >= ps.n) return M3_ERR_BAD_ARG;
+    if (seq && !ps.host_values) return M3_ERR_STATE;
+    if (sample_idx) *sample_idx = ps.idx[j];
+    const size_t row = (size_t)h->cfg.T * h->cfg.nu;
+    if (seq) std::memcpy(seq, ps.pinned + (size_t)j * row, row * sizeof(float));
+    return M3_OK;
+}
+extern "C" int m3_prior_samples_used(m3_handle* h) { return h ? h->priors.used : M3_ERR_BAD_ARG; }
+
 // the handle's arena is the default bit for bit (-0.0f is not 0.0f here)
 static bool default_point_scene(const m3_handle* h) {
     return std::memcmp(&h->point_scene, &POINT_SCENE_DEFAULT, sizeof(m3_point_scene)) == 0;
@@ -1059,7 +1157,8 @@ enum PointSide { SIDE_COST = 1, SIDE_STEP = 2, SIDE_ROLLOUT = SIDE_COST | SIDE_S
 static PointVariant point_variant(const m3_handle* h, PointSide side) {
     if (h->cfg.env_type != M3_ENV_POINT) return POINT_PLAIN;
     // (per-sample arenas are the run-time-scene variant of the rollout; a planner handle's own step keeps its single scene)
-    const bool rows = side == SIDE_ROLLOUT && h->point_rows.sample_on;
+    // (... and so is the prior build, m3_set_prior_samples)
+    const bool rows = side == SIDE_ROLLOUT && (h->point_rows.sample_on || h->priors.n > 0);
     if ((side & SIDE_STEP) && (h->scene_instance < 0 ? (rows || !default_point_scene(h)) : h->scene_instance != 0)) return POINT_SCENE;
     return (h->weighted_instance < 0 ? !default_cost_weights(h) : h->weighted_instance != 0) ? POINT_WEIGHTED : POINT_PLAIN;
 }
@@ -1079,6 +1178,8 @@ static const char* point_variant_refusal(const m3_handle* h, PointSide side) {
         return "the run-time-scene instance is forced off (m3_set_point_scene_instance 0) but the handle has an arena per environment (m3_set_point_scene_rows)";
     if (side == SIDE_ROLLOUT && h->scene_instance == 0 && h->point_rows.sample_on)
         return "the run-time-scene instance is forced off (m3_set_point_scene_instance 0) but the handle has an arena per sample (m3_set_point_rollout_scenes)";
+    if (side == SIDE_ROLLOUT && h->scene_instance == 0 && h->priors.n > 0)
+        return "the run-time-scene instance is forced off (m3_set_point_scene_instance 0) but the handle has prior samples (m3_set_prior_samples)";
     if ((side & SIDE_STEP) && h->scene_instance == 0 && !default_point_scene(h))
         return "the run-time-scene instance is forced off (m3_set_point_scene_instance 0) but the handle's scene is not the default";
     return nullptr;
@@ -1396,7 +1497,7 @@ static int plan_rollout(m3_handle* h, RolloutArgs& a, PandaArgs& pa, RolloutPlan
     if (h->cfg.env_type == M3_ENV_POINT) {
         // (the two-wavefront form: m3_rollout's own launch only, and only with the error word to report into)
         p = plan_rollout_point(a, h->scene, point_variant(h, SIDE_ROLLOUT), (own_launch && h->rollout_err_dev) ? h->point_form : 0,
-                               h->point_rows.sample_on);
+                               h->point_rows.sample_on, h->priors.n > 0);
     } else {
         fill_panda_args(h, a, pa);
         p = plan_rollout_panda(a, pa);
@@ -1418,9 +1519,10 @@ extern "C" int m3_rollout(m3_handle* h) {
                                    "(its results are invalid); m3_set_point_rollout_form(h, 0) avoids the form");
     const int rc = plan_rollout(h, a, pa, p, true);
     if (rc != M3_OK) return rc;
-    if (h->cfg.env_type == M3_ENV_POINT) h->point_form_used = p.form;
+    if (h->cfg.env_type == M3_ENV_POINT) { h->point_form_used = p.form; h->priors.used = p.priors; }
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->scene_rt, h->cost_weights, p, h->stream, h->rollout_err_dev, h->point_rows.dev);
+    if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->scene_rt, h->cost_weights, p, h->stream, h->rollout_err_dev, h->point_rows.dev,
+                                                              h->priors.slot_dev, h->priors.tab_dev);
     else {
         const PandaDecision d = panda_decision(panda_input(h), PANDA_SIDE_ROLLOUT);
         launch_rollout_panda(a, pa, panda_launch_scene(h, d.variant), p, h->stream);
@@ -2030,6 +2132,7 @@ static_assert(alignof(BatchPandaEntryRT) <= 16 && alignof(BatchPandaEntry) <= 16
               "the table's sections start on multiples of 16");
 static_assert(BATCH_POINT_SECTIONS == POINT_SECTIONS, "");
 // the refusal of a point_env handle with an arena per sample by a batch or an episode set that was not created for it
+constexpr const char* PRIORS_UNBATCHED = "it has prior samples (m3_set_prior_samples), which only m3_rollout / m3_command run";
 constexpr const char* POINT_ROWS_UNBATCHED = "it has an arena per sample (m3_set_point_rollout_scenes), which only m3_rollout / m3_command run";
 }  // namespace
 
@@ -2155,6 +2258,10 @@ static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code, bool pa
     if (h->point_rows.sample_on && !point_rows) {   // (the table's slots have no fourth section)
         code = M3_ERR_UNSUPPORTED;
         return POINT_ROWS_UNBATCHED;
+    }
+    if (h->priors.n > 0) {   // (no table entry carries a slot map and a table of priors)
+        code = M3_ERR_UNSUPPORTED;
+        return PRIORS_UNBATCHED;
     }
     if (const char* why = rollout_refusal(h)) return why;
     if (!panda_runtime) {
@@ -2734,11 +2841,22 @@ static int eps_status_sync(m3_episodes* eps) {
     return M3_OK;
 }
 
+// a planner that got prior samples after m3_episodes_create (which refuses it): nothing of the tick is launched
+static int eps_priors_refusal(m3_episodes* eps, const char* who) {
+    for (int i = 0; i < eps->n; ++i)
+        if (eps->planners[i]->priors.n > 0) {
+            eps->err = std::string(who) + ": planner " + std::to_string(i) + ": " + PRIORS_UNBATCHED;
+            return M3_ERR_UNSUPPORTED;
+        }
+    return M3_OK;
+}
+
 extern "C" int m3_episodes_begin(m3_episodes* eps) {
     if (!eps) return M3_ERR_BAD_ARG;
     if (eps->mid_tick) { eps->err = "m3_episodes_begin: the tick was begun already"; return M3_ERR_STATE; }
     int rc = eps_ready(eps, "m3_episodes_begin");
     if (rc != M3_OK) return rc;
+    if ((rc = eps_priors_refusal(eps, "m3_episodes_begin")) != M3_OK) return rc;
     m3::launch_episodes_pre(eps->args, eps->tick, eps->world->stream);
     HIPCHK(eps, hipGetLastError());
     eps->mid_tick = true;
@@ -2750,6 +2868,7 @@ extern "C" int m3_episodes_end(m3_episodes* eps) {
     if (!eps->mid_tick) { eps->err = "m3_episodes_end: no tick begun"; return M3_ERR_STATE; }
     int rc = eps_ready(eps, "m3_episodes_end");
     if (rc != M3_OK) return rc;
+    if ((rc = eps_priors_refusal(eps, "m3_episodes_end")) != M3_OK) return rc;
     if (const char* why = point_variant_refusal(eps->world, SIDE_STEP)) { eps->err = std::string("m3_episodes_end: world: ") + why; return M3_ERR_STATE; }
     episodes_post(eps->world, eps->args, eps->tick);
     HIPCHK(eps, hipGetLastError());
@@ -2764,6 +2883,7 @@ extern "C" int m3_episodes_tick(m3_episodes* eps, m3_batch* batch) {
     if (eps->mid_tick) { eps->err = "m3_episodes_tick: inside m3_episodes_begin / m3_episodes_end"; return M3_ERR_STATE; }
     int rc = eps_ready(eps, "m3_episodes_tick");
     if (rc != M3_OK) return rc;
+    if ((rc = eps_priors_refusal(eps, "m3_episodes_tick")) != M3_OK) return rc;
     if (const char* why = point_variant_refusal(eps->world, SIDE_STEP)) { eps->err = std::string("m3_episodes_tick: world: ") + why; return M3_ERR_STATE; }
     // the batch: episodes still running after the last tick's status (one that succeeds in this tick's pre kernel is
     // commanded once more -- its plan is never recorded)

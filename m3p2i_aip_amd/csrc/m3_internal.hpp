@@ -231,6 +231,9 @@ struct RolloutPlan {
     int scene;           // point_env: the run-time-scene build of the general instance (POINT_SCENE; instance == -1,
                          // weighted == 1, ref == 0, form == 0); 2: its per-sample twin (m3_set_point_rollout_scenes) -- no
                          // variant of its own; in a batch created with the per-sample section, the table's fourth section
+    int priors;          // point_env: the prior build of that instance (m3_set_prior_samples, rollout_point_priors.hip; scene 1 or 2,
+                         // instance == -1, weighted == 1, ref == 0, form == 0); m3_rollout only -- the batched and episode
+                         // paths refuse such a handle
 };
 inline PointVariant point_variant(const RolloutPlan& p) { return p.scene ? POINT_SCENE : p.weighted ? POINT_WEIGHTED : POINT_PLAIN; }
 // the section of the point_env batch table a plan's entry lies in: its variant's, the per-sample handles behind them
@@ -238,8 +241,9 @@ constexpr int POINT_SECTIONS = POINT_VARIANTS + 1, POINT_SECTION_SV = POINT_VARI
 inline int point_section(const RolloutPlan& p) { return p.scene == 2 ? POINT_SECTION_SV : (int)point_variant(p); }
 // form_request: m3_set_point_rollout_form's value (0 one wavefront, 1 two wherever available, -1 by rollout_companion_pays)
 // per_sample: the handle carries one arena per sample (variant POINT_SCENE then): RolloutPlan::scene = 2
+// priors: the handle has prior samples set (variant POINT_SCENE then): RolloutPlan::priors = 1
 RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, PointVariant variant, int form_request = 0,
-                               bool per_sample = false);
+                               bool per_sample = false, bool priors = false);
 // one launch of the plan's instance for n handles of K_local = a.Kl and the same plan (tab: device, n entries of the type of
 // the plan's variant; p.scene == 2: of BatchRolloutEntrySV)
 void launch_rollout_point_batch(const void* tab, int n, const RolloutPlan& p, hipStream_t s);
@@ -253,7 +257,11 @@ void launch_rollout_point_pushpull_batch(const BatchRolloutEntry* tab, int block
 // scene_rows: p.scene == 2 only -- the handle's table of per-sample arenas (point_scene_rows.hpp), rt then its uniform members
 void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const PointSceneRT& rt, const PointCostWeights& wt,
                           const RolloutPlan& p, hipStream_t s, int* err = nullptr /* p.form == 1: the hand-over's error word */,
-                          const float* scene_rows = nullptr);
+                          const float* scene_rows = nullptr, const int* prior_slot = nullptr /* p.priors only: the handle's */,
+                          const float* prior_tab = nullptr /* slot map and table of prior samples */);
+// ... of a planner handle with prior samples (rollout_point_priors.hip; rows: null or the handle's per-sample arenas)
+void launch_rollout_point_pr(const RolloutArgs& a, const PointSceneRT& uni, const float* rows, const PointCostWeights& wt,
+                             const int* prior_slot, const float* prior_tab, int blocks, hipStream_t s);
 // ... of a planner handle with an arena per sample (rollout_point_rollout_scenes.hip; uni, rows: point_scene_rows.hpp)
 void launch_rollout_point_sv(const RolloutArgs& a, const PointSceneRT& uni, const float* rows, const PointCostWeights& wt,
                              int blocks, hipStream_t s);
@@ -492,6 +500,21 @@ template <class Scene> struct SceneRows {
     float* host = nullptr;    // pinned host [row words][Kl]: the table as uploaded
     float* dev = nullptr;     // device, the same
 };
+
+// The prior samples of a planner handle (m3_set_prior_samples): samples whose controls are the caller's sequences.  The
+// pointers are non-owning views of ledger blocks, allocated as one group by the first setter call on the handle.
+struct PriorSampleState {
+    int n = 0;                    // priors set (0: none -- the handle launches what it launched before the call existed)
+    bool host_values = false;     // set by m3_set_prior_samples: `pinned` holds the values (m3_get_prior_sample)
+    int idx[M3_MAX_PRIOR_SAMPLES] = {};   // global sample index of prior j ...
+    int dev_n = 0;                // ... of the dev_n priors the device slot map was last built from (>= n: kept over a clear)
+    float* tab_dev = nullptr;     // device [M3_MAX_PRIOR_SAMPLES][T][nu]
+    int* slot_dev = nullptr;      // device [Kl]: local sample -> row of the table, -1: no prior
+    float* pinned = nullptr;      // pinned host mirror of both: the table, behind it the slot map
+    hipEvent_t uploaded = nullptr;   // recorded behind the last upload from `pinned`
+    bool upload_pending = false;
+    int used = -1;                // m3_prior_samples_used
+};
 }  // namespace m3
 
 // the ledger's release function bound to HIP (m3_api.hip): the one place that frees
@@ -544,6 +567,7 @@ struct m3_handle {
     // the first setter call of that kind on the handle (upload_scene_rows, m3_api.hip); nothing else allocates them.
     m3::SceneRows<m3_point_scene> point_rows;   // table [POINT_SCENE_ROW_WORDS][Kl] (point_scene_rows.hpp)
     m3::SceneRows<m3_panda_scene> panda_rows;   // table [PANDA_SCENE_ROW_WORDS][Kl] (panda_scene_rows.hpp)
+    m3::PriorSampleState priors;                // m3_set_prior_samples; survives m3_reset
     // world
     float world0[18];
     const float* world0_bound = nullptr;  // device, 18 floats (filled by world_from_sim)

@@ -28,11 +28,14 @@ int rollout_lanes_for(int Kl) {
 // variant POINT_SCENE: the handle's arena is not the default (or the run-time-scene build is forced on): the general instance on
 // PointSceneRT, which always takes the weights as well -- instance -1, form 0, ref 0, whatever the sampler, the task and the weights.
 // per_sample: the same build with the arena of each lane read from the handle's table (m3_set_point_rollout_scenes): scene = 2.
-RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, PointVariant variant, int form_request, bool per_sample) {
+// priors: the prior build of either (m3_set_prior_samples, rollout_point_priors.hip; the caller passes POINT_SCENE): priors = 1.
+RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, PointVariant variant, int form_request, bool per_sample,
+                               bool priors) {
     const bool weighted = variant != POINT_PLAIN;
     if (variant == POINT_SCENE) {
         RolloutPlan p{};
         p.scene = per_sample ? 2 : 1; p.weighted = 1;
+        p.priors = priors ? 1 : 0;
         p.instance = -1; p.ref = 0; p.form = 0;
         p.lanes = a.lanes;
         p.blocks = (a.Kl + a.lanes - 1) / a.lanes;
@@ -64,10 +67,12 @@ RolloutPlan plan_rollout_point(const RolloutArgs& a, const PointScene& sc, Point
 }
 
 void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const PointSceneRT& rt, const PointCostWeights& wt,
-                          const RolloutPlan& p, hipStream_t s, int* err, const float* scene_rows) {
+                          const RolloutPlan& p, hipStream_t s, int* err, const float* scene_rows, const int* prior_slot,
+                          const float* prior_tab) {
     switch (point_variant(p)) {
         case POINT_SCENE:
-            if (p.scene == 2) launch_rollout_point_sv(a, rt, scene_rows, wt, p.blocks, s);
+            if (p.priors) launch_rollout_point_pr(a, rt, p.scene == 2 ? scene_rows : nullptr, wt, prior_slot, prior_tab, p.blocks, s);
+            else if (p.scene == 2) launch_rollout_point_sv(a, rt, scene_rows, wt, p.blocks, s);
             else launch_rollout_point_instance<true, -1>(a, rt, p.blocks, s, wt);
             return;
         case POINT_WEIGHTED: launch_rollout_point_instance<true, -1>(a, sc, p.blocks, s, wt); return;
@@ -325,9 +330,9 @@ void launch_episodes_post(const PointScene& sc, const EpisodeArgs& a, int tick, 
 
 // Diagnostic (host only, no device call): the form plan_rollout_point gives a point_env rollout with these settings -- what
 // m3_rollout / m3_batch_command would launch.  out: instance, ref, form, weighted, scene, blocks, rows, lanes.
-extern "C" int m3_point_rollout_plan(int task, int multi_modal, int mode_simple, int sampling_random, int avoid_dyn_obs,
-                                     int K_local, int T, int lanes, float dt, int substeps, int solver_iters, int weighted,
-                                     int scene, int form_request, int want_minima, int out[8]) {
+static int point_rollout_plan(int task, int multi_modal, int mode_simple, int sampling_random, int avoid_dyn_obs,
+                              int K_local, int T, int lanes, float dt, int substeps, int solver_iters, int weighted,
+                              int scene, int form_request, int want_minima, int priors, int* out, int* out9) {
     if (!out || K_local < 1 || T < 1 || lanes < 1 || lanes > 64 || substeps < 1) return M3_ERR_BAD_ARG;
     m3::RolloutArgs a{};
     a.Kl = a.Kg = K_local; a.T = T; a.nu = 2; a.lanes = lanes;
@@ -338,11 +343,26 @@ extern "C" int m3_point_rollout_plan(int task, int multi_modal, int mode_simple,
     m3::PointScene sc;
     m3::make_point_scene(sc, dt, substeps, solver_iters);
     if (scene < 0 || scene > 2) return M3_ERR_BAD_ARG;
+    if (priors < 0 || priors > 1 || (priors && !scene)) return M3_ERR_BAD_ARG;
     const m3::PointVariant variant = scene ? m3::POINT_SCENE : weighted ? m3::POINT_WEIGHTED : m3::POINT_PLAIN;
-    const m3::RolloutPlan p = m3::plan_rollout_point(a, sc, variant, form_request, scene == 2);
+    const m3::RolloutPlan p = m3::plan_rollout_point(a, sc, variant, form_request, scene == 2, priors != 0);
     out[0] = p.instance; out[1] = p.ref; out[2] = p.form; out[3] = p.weighted; out[4] = p.scene; out[5] = p.blocks;
     out[6] = p.rows; out[7] = p.lanes;
+    if (out9) out9[8] = p.priors;
     return M3_OK;
+}
+extern "C" int m3_point_rollout_plan(int task, int multi_modal, int mode_simple, int sampling_random, int avoid_dyn_obs,
+                                     int K_local, int T, int lanes, float dt, int substeps, int solver_iters, int weighted,
+                                     int scene, int form_request, int want_minima, int out[8]) {
+    return point_rollout_plan(task, multi_modal, mode_simple, sampling_random, avoid_dyn_obs, K_local, T, lanes, dt, substeps,
+                              solver_iters, weighted, scene, form_request, want_minima, 0, out, nullptr);
+}
+// ... of a handle with prior samples (m3_set_prior_samples): out[8] = priors
+extern "C" int m3_point_rollout_plan_ex(int task, int multi_modal, int mode_simple, int sampling_random, int avoid_dyn_obs,
+                                        int K_local, int T, int lanes, float dt, int substeps, int solver_iters, int weighted,
+                                        int scene, int form_request, int want_minima, int priors, int out[9]) {
+    return point_rollout_plan(task, multi_modal, mode_simple, sampling_random, avoid_dyn_obs, K_local, T, lanes, dt, substeps,
+                              solver_iters, weighted, scene, form_request, want_minima, priors, out, out);
 }
 
 #ifdef M3_ABL_PHASES

@@ -60,9 +60,17 @@ __device__ __forceinline__ void load_world_from_sim(const float* dof, const floa
 // WEIGHTED: the running cost is point_cost_w with *wt (the shells with WT = PointCostWeights below; wt is not read otherwise)
 // SC: the scene type -- PointScene (the reference's arena compiled in) or PointSceneRT (m3_set_point_scene: instantiated in
 // rollout_point.hip, always GENERAL and WEIGHTED)
-template <bool GENERAL, int TASK, bool LONE = true, bool WEIGHTED = false, class SC = PointScene>
+// PR: NoPriors, or PriorSamples (m3_set_prior_samples; rollout_point_priors.hip): samples whose controls are the caller's
+// sequences instead of mean + noise.  With NoPriors nothing of it is compiled in.
+struct NoPriors {};
+struct PriorSamples {
+    const int* slot;     // [Kl] local sample -> row of tab, -1: no prior
+    const float* tab;    // [M3_MAX_PRIOR_SAMPLES][T][2], the controls of THIS command's steps
+};
+template <bool GENERAL, int TASK, bool LONE = true, bool WEIGHTED = false, class SC = PointScene, class PR = NoPriors>
 __device__ __forceinline__ void rollout_point_body(const RolloutArgs& a_, const SC& sc,
-                                                   const PointCostWeights* wt = nullptr) {
+                                                   const PointCostWeights* wt = nullptr, const PR& pr = PR()) {
+    constexpr bool PRIORS = std::is_same<PR, PriorSamples>::value;
     RolloutArgs a = a_;
     if constexpr (!GENERAL) {
         a.sampling_random = 0; a.mode_simple = 0;
@@ -121,6 +129,19 @@ __device__ __forceinline__ void rollout_point_body(const RolloutArgs& a_, const 
         S00 = a.noise_mats[4]; S01 = a.noise_mats[5]; S10 = a.noise_mats[6]; S11 = a.noise_mats[7];
     }
 
+    // the prior of this lane's sample (the row follows the sample i, not the wavefront slot), fetched a step ahead like the
+    // other inputs: one predicated 8-byte load
+    [[maybe_unused]] int ps = -1;
+    [[maybe_unused]] float2 pnxt = make_float2(0.0f, 0.0f);
+    [[maybe_unused]] auto fetch_prior = [&](int t) {
+        float2 pp = make_float2(0.0f, 0.0f);
+        if constexpr (PRIORS) {
+            if (ps >= 0) pp = *reinterpret_cast<const float2*>(pr.tab + ((size_t)ps * T + t) * 2);
+        }
+        return pp;
+    };
+    if constexpr (PRIORS) { ps = pr.slot[i]; pnxt = fetch_prior(0); }
+
     float J = 0.0f, S = 0.0f, g = 1.0f, pc = 0.0f;
     StepIn nxt = fetch(0);
 #ifdef M3_ABL_PHASES
@@ -132,6 +153,10 @@ __device__ __forceinline__ void rollout_point_body(const RolloutArgs& a_, const 
     for (int t = 0; t < T; ++t) {
         const StepIn in = nxt;
         if (t + 1 < T) nxt = fetch(t + 1);
+        [[maybe_unused]] const float2 pin = pnxt;
+        if constexpr (PRIORS) {
+            if (t + 1 < T) pnxt = fetch_prior(t + 1);
+        }
         // ---- A4 / A13: perturbed action for this (k, t) ----
         float d0 = in.d0, d1 = in.d1;
         if (a.sampling_random) {   // N(noise_mu, noise_sigma) = mu + L z: mppi.py:129-131, :340 / :481
@@ -152,6 +177,12 @@ __device__ __forceinline__ void rollout_point_body(const RolloutArgs& a_, const 
             a0 = fmaxf(fminf(m0 + d0 * a.scale_tril[0], a.u_max[0]), a.u_min[0]);  // :394-405
             a1 = fmaxf(fminf(m1 + d1 * a.scale_tril[1], a.u_max[1]), a.u_min[1]);
             if (use_best) { a0 = in.b0; a1 = in.b1; }  // mppi.py:407-409
+        }
+        if constexpr (PRIORS) {   // a select, not a branch around the step
+            const float q0 = fmaxf(fminf(pin.x, a.u_max[0]), a.u_min[0]);
+            const float q1 = fmaxf(fminf(pin.y, a.u_max[1]), a.u_min[1]);
+            a0 = ps >= 0 ? q0 : a0;
+            a1 = ps >= 0 ? q1 : a1;
         }
         float u0 = a.u_scale * a0, u1 = a.u_scale * a1;                 // mppi.py:297
         if (a.sample_null_action && is_last) { u0 = 0.0f; u1 = 0.0f; }  // mppi.py:300-302

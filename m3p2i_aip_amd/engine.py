@@ -365,6 +365,55 @@ class HipEngine(_CObject):
     def point_rollout_scenes_set(self):
         return self.lib.m3_point_rollout_scenes_set(self._h) == 1
 
+    def set_prior_samples(self, seqs=None, indices=None):
+        """Extension, unsharded point_env planner engines: PRIOR SAMPLES -- sample indices[j] of the next rollouts takes
+        clamp(seqs[j], u_min, u_max) as its controls instead of clamp(mean + noise); seqs [n, T, nu] holds the controls of
+        the steps of THIS command's horizon (nothing is shifted between commands), indices the n GLOBAL sample indices
+        (default 0 .. n-1).  A torch tensor on the engine's device is copied device-to-device on the engine's stream (its
+        values are not inspected); anything else goes through the host entry point, which refuses a non-finite value.
+        seqs=None (or n = 0) clears.  See include/m3p2i_hip.h: m3_set_prior_samples."""
+        if seqs is None or len(seqs) == 0:
+            self._ck(self.lib.m3_set_prior_samples(self._h, None, None, 0))
+            return
+        c = self.cfg
+        n = int(seqs.shape[0]) if hasattr(seqs, "shape") else len(seqs)
+        idx = list(range(n)) if indices is None else [int(i) for i in indices]
+        if len(idx) != n:
+            raise ValueError(f"set_prior_samples: {n} sequences but {len(idx)} indices")
+        arr = (C.c_int * max(n, 1))(*idx)
+        if isinstance(seqs, torch.Tensor) and seqs.is_cuda and seqs.device == self.device:
+            d = seqs.to(torch.float32).contiguous()
+            if tuple(d.shape) != (n, c.T, c.nu):
+                raise ValueError(f"set_prior_samples: seqs is {tuple(d.shape)}, expected (n, {c.T}, {c.nu})")
+            # (the copy is ordered on the engine's stream, d lives until the call returns: keep it until that copy is over)
+            self._ck(self.lib.m3_set_prior_samples_device(self._h, d.data_ptr(), arr, n))
+            self._prior_src = d
+            return
+        d = np.ascontiguousarray(seqs.detach().cpu().numpy() if isinstance(seqs, torch.Tensor) else seqs, dtype=np.float32)
+        if d.shape != (n, c.T, c.nu):
+            raise ValueError(f"set_prior_samples: seqs is {d.shape}, expected (n, {c.T}, {c.nu})")
+        self._ck(self.lib.m3_set_prior_samples(self._h, d.ctypes.data, arr, n))
+
+    def prior_samples_set(self):
+        """the number of prior samples set (0: none)"""
+        return int(self.lib.m3_prior_samples_set(self._h))
+
+    def prior_sample(self, j):
+        """(global sample index, [T, nu] float32 array) of prior j as set through the host entry point"""
+        k = C.c_int()
+        seq = np.empty((self.cfg.T, self.cfg.nu), np.float32)
+        self._ck_code(self.lib.m3_get_prior_sample(self._h, int(j), C.byref(k), seq.ctypes.data), "m3_get_prior_sample")
+        return int(k.value), seq
+
+    def prior_samples_used(self):
+        """1 / 0: the last rollout launched the prior build; -1 before the first"""
+        return int(self.lib.m3_prior_samples_used(self._h))
+
+    def _ck_code(self, rc, who):
+        # (the getters leave no message behind)
+        if rc != 0:
+            raise L.M3Error(f"m3p2i_hip error {rc}: {who}")
+
     def set_point_scene_instance(self, on=-1):
         """-1: the run-time-scene kernels exactly when the scene is not the default (default); 1 / 0 forced (tests, A/B)."""
         self._ck(self.lib.m3_set_point_scene_instance(self._h, int(on)))

@@ -67,7 +67,8 @@ class MPPIConfig(object):
     rollout_var_discount: float = 0.95
     sample_null_action: bool = False
     sample_previous_plan: bool = True
-    sample_other_priors: bool = False
+    sample_other_priors: bool = False    # (accepted and ignored, like use_priors below: dead switches of the reference.  Prior
+                                         # samples are set at run time: MPPI.set_prior_samples)
     noise_abs_cost: bool = False
     filter_u: bool = False
     use_priors: bool = False
@@ -602,6 +603,7 @@ class MPPI():
         if self.mppi_mode == "simple":      # mppi.py:341-350
             U = torch.roll(self.U, -1, dims=0)                                   # :221
             act = torch.max(torch.min(U.unsqueeze(0) + delta, self.u_max), self.u_min)
+            act = self._write_priors(act, ks)
             if self.env_type == "panda_env" and self.gripper_command in ("open", "close"):
                 act[:, :, 7:] = 1.5 if self.gripper_command == "open" else -1.5
             return act
@@ -618,11 +620,53 @@ class MPPI():
         if self.multi_modal:
             act[ks == 0] = self.best_traj_1[shift]
             act[ks == self.half_K] = self.best_traj_2[shift]
+        act = self._write_priors(act, ks)
         if self.env_type == "panda_env":
             if self.gripper_command == "open":
                 act[:, :, 7:] = 1.5
             elif self.gripper_command == "close":
                 act[:, :, 7:] = -1.5
+        return act
+
+    def set_prior_samples(self, seqs, indices=None):
+        """Extension, unsharded point_env planners: PRIOR SAMPLES (m3_set_prior_samples) -- sample indices[j] of the next
+        commands rolls out clamp(seqs[j], u_min, u_max) instead of clamp(mean + noise): the proposal of an ancillary controller
+        (priors.go_to, priors.push_behind, yesterday's plan, a policy), taken verbatim.  seqs [n, T, nu] are the controls of
+        the steps of the NEXT command's horizon; nothing is shifted between commands and the priors stay until replaced or
+        cleared (seqs=None), so a caller that plans every tick sets them every tick.  indices default to 0 .. n-1 for a
+        single-mode planner; a multi-modal planner must pass them (k < K/2 informs mode 1, k >= K/2 mode 2; 0, K/2 and K-1
+        are refused).  Applies to the fused path and the step path alike.  The reference's sample_other_priors / use_priors
+        config fields stay ignored, as in the reference."""
+        if self.env_type != "point_env":
+            raise ValueError("set_prior_samples: point_env only")
+        if self.world_size != 1:
+            raise ValueError("set_prior_samples: unsharded planners only")
+        if seqs is None or len(seqs) == 0:
+            self._engine.set_prior_samples(None)
+            self._priors = None
+            return
+        n = int(seqs.shape[0]) if hasattr(seqs, "shape") else len(seqs)
+        if indices is None:
+            if self.multi_modal:    # (whatever the mppi mode: the library refuses 0 and K/2 whenever multi_modal is set)
+                raise ValueError("set_prior_samples: a multi-modal planner needs indices (a prior informs the mode whose half "
+                                 "of the samples it sits in)")
+            indices = range(n)
+        idx = [int(i) for i in indices]
+        self._engine.set_prior_samples(seqs, idx)       # (every refusal of the library before anything is kept here)
+        vals = torch.as_tensor(seqs, dtype=torch.float32).to(self.device).clone()
+        self._priors = (torch.tensor(idx, dtype=torch.long, device=self.device), vals)
+
+    @property
+    def has_prior_samples(self):
+        return getattr(self, "_priors", None) is not None
+
+    def _write_priors(self, act, ks):
+        """the rows of the prior samples, clamped like the kernel's select (step mode)"""
+        pri = getattr(self, "_priors", None)
+        if pri is None:
+            return act
+        idx, vals = pri
+        act[idx - self.k_offset] = torch.max(torch.min(vals, self.u_max), self.u_min)
         return act
 
     def _command_step(self):
@@ -749,6 +793,9 @@ def command_batch(planners, states, panda_runtime=False, point_runtime=False):
             raise ValueError(f"command_batch: planner {i} runs in step mode (user dynamics / running_cost callables)")
         if p.world_size > 1 or p.collective is not None:
             raise ValueError(f"command_batch: planner {i} is sharded or has collectives installed")
+        if getattr(p, "has_prior_samples", False):
+            raise ValueError(f"command_batch: planner {i} has prior samples (set_prior_samples), which only its own command() "
+                             "runs (m3_set_prior_samples)")
         if not point_runtime and p.has_rollout_scenes:
             raise ValueError(f"command_batch: planner {i} has an arena per sample (set_rollout_scenes / a wrapper with "
                              "point_scenes): m3_batch_command does not run those, use planner.command")

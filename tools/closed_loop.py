@@ -70,7 +70,28 @@ class Tamp:
         self.task_success = bool(self.task_planner.check_task_success(self.sim))
         if self.task_success:
             return torch.zeros(self.sim.dofs_per_robot, device=self.cfg.mppi.device)
+        self._set_prior_samples()
         return self.motion_planner.command(self.sim._dof_state[0])[0]
+
+    def _set_prior_samples(self):
+        """the `prior_samples` config key: the proposals of a host-side ancillary controller (m3p2i_aip_amd/priors.py) from
+        this tick's state, for this tick's command -- nothing carries over, so they are set every tick"""
+        cfg = self.cfg
+        if not getattr(cfg, "prior_samples", None):
+            return
+        from m3p2i_aip_amd import priors
+        name, n = compat.check_prior_samples(cfg)
+        m = cfg.mppi
+        speeds = [1.0 - j / n for j in range(n)]
+        robot = self.sim.robot_pos[0].cpu().numpy()
+        goal = torch.as_tensor(self.task_planner.curr_goal).cpu().numpy().reshape(-1)[:2]
+        args = (int(m.horizon), float(cfg.isaacgym.dt), [float(x) for x in m.u_max], speeds)
+        if name == "push_behind" and cfg.task != "navigation":
+            box = self.sim.get_actor_position_by_name("box")[0, :2].cpu().numpy()
+            seqs = priors.push_behind(robot, box, goal, *args)
+        else:
+            seqs = priors.go_to(robot, goal, *args)
+        self.motion_planner.set_prior_samples(seqs, compat.prior_sample_indices(int(m.num_samples), n, bool(cfg.multi_modal)))
 
     # ---- what reactive_tamp.py serves over zerorpc (:43-61, 83-87) + a status call for this tool ----
     def run_tamp_bytes(self, dof_bytes, root_bytes):
