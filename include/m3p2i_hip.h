@@ -606,9 +606,10 @@ int m3_point_rollout_plan_ex(int task, int multi_modal, int mode_simple, int sam
  * (rollout_point_priors.hip; with or without an arena per sample, tuned cost weights keep working); the two-wavefront form is
  * never taken; m3_point_rollout_plan_ex(..., priors = 1, ...) reports the launch.  m3_set_point_scene_instance(h, 0) with priors
  * set refuses the next rollout (M3_ERR_STATE).
- * NOT batched: m3_batch_command with such a handle and m3_episodes_create* / m3_episodes_tick / _begin / _end with such a planner
- * return M3_ERR_UNSUPPORTED whatever batch they are given (the message names m3_set_prior_samples and the index of the
- * handle); nothing is launched and every handle stays as it was.
+ * Batched ON REQUEST only (m3p2i_hip_ext.h: M3_BATCH_SECTION_POINT_PRIORS, M3_EPISODES_PRIORS; the controllers that fill the
+ * table on the device: m3_set_prior_controller).  Every other batch and set: m3_batch_command with such a handle and
+ * m3_episodes_create* / m3_episodes_tick / _begin / _end with such a planner return M3_ERR_UNSUPPORTED (the message names
+ * m3_set_prior_samples and the index of the handle); nothing is launched and every handle stays as it was.
  * Memory: the first call on a handle allocates, through the handle's ledger, a device table of M3_MAX_PRIOR_SAMPLES x T x nu
  * floats, a device slot map int[K_local] (-1: no prior), one pinned host block that mirrors both, and the event below; later
  * calls reuse them.  Uploads are hipMemcpyAsync on the handle's stream.  Before the mirror is rewritten the setter waits for

@@ -50,6 +50,18 @@ PANDA_EPISODES_RUNTIME = 1   # M3_PANDA_EPISODES_RUNTIME (m3_panda_episodes_crea
 BATCH_SECTION_PANDA_RUNTIME = 1          # M3_BATCH_SECTION_PANDA_RUNTIME (m3_batch_create_sections)
 BATCH_SECTION_POINT_ROLLOUT_SCENES = 2   # M3_BATCH_SECTION_POINT_ROLLOUT_SCENES
 EPISODES_ROLLOUT_SCENES = 1              # M3_EPISODES_ROLLOUT_SCENES (m3_episodes_create_ex)
+BATCH_SECTION_POINT_PRIORS = 32          # M3_BATCH_SECTION_POINT_PRIORS (4, 8 and 16 stay unknown section bits)
+EPISODES_PRIORS = 8                      # M3_EPISODES_PRIORS (2 and 4 stay unknown flag bits)
+
+
+PRIOR_CONTROLLER_GO_TO, PRIOR_CONTROLLER_PUSH_BEHIND = 1, 2   # m3_prior_controller.kind (m3p2i_hip_ext.h)
+PRIOR_CONTROLLER_KINDS = {"go_to": PRIOR_CONTROLLER_GO_TO, "push_behind": PRIOR_CONTROLLER_PUSH_BEHIND}
+MAX_PRIOR_CONTROLLER_SEQS = 16
+
+
+class PriorController(C.Structure):   # m3_prior_controller
+    _fields_ = [("kind", C.c_int), ("n", C.c_int), ("speed", C.c_float * MAX_PRIOR_CONTROLLER_SEQS),
+                ("standoff", C.c_float), ("reach", C.c_float)]
 
 
 class PointWorld(C.Structure):
@@ -324,6 +336,11 @@ SYMBOLS_EXT = [
     ("m3_batch_create_sections", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
     ("m3_episodes_create_ex", C.c_int, [_H, C.POINTER(_H), C.POINTER(EpisodeSpec), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_H)]),
     ("m3_episodes_flags", C.c_int, [_H]),
+    ("m3_default_prior_controller", None, [C.POINTER(PriorController), C.c_int, C.c_int]),
+    ("m3_set_prior_controller", C.c_int, [_H, C.POINTER(PriorController), C.POINTER(C.c_int)]),
+    ("m3_get_prior_controller", C.c_int, [_H, C.POINTER(PriorController)]),
+    ("m3_prior_controller_fill", C.c_int, [_H]),
+    ("m3_prior_table", C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
 ]
 
 _lib = None

@@ -19,7 +19,7 @@ OUT = os.path.join(HERE, "lib", "libm3p2i_hip.so")
 OBJ = os.path.join(HERE, "_obj")   # object files (git- and gpurun-ignored)
 SOURCES = ["rollout_point.hip", "rollout_point_task0.hip", "rollout_point_task1.hip", "rollout_point_task2.hip",
            "rollout_point_task3.hip", "rollout_point_scene.hip", "rollout_point_scene_rows.hip",
-           "rollout_point_rollout_scenes.hip", "rollout_point_priors.hip",
+           "rollout_point_rollout_scenes.hip", "rollout_point_priors.hip", "rollout_point_priors_batch.hip", "prior_controllers.hip",
            "rollout_panda.hip", "rollout_panda_scene.hip", "rollout_panda_weights.hip", "rollout_panda_rows.hip",
            "rollout_panda_batch_rt.hip", "rollout_panda_episodes_rt.hip",
            "update.hip", "update_small.hip", "update_sharded.hip", "sampler.hip", "p2p.hip", "m3_api.hip"]
@@ -33,7 +33,7 @@ PER_SOURCE = {
     "rollout_point.hip": ["-O2"], "rollout_point_task0.hip": ["-O2"], "rollout_point_task1.hip": ["-O2"],
     "rollout_point_task2.hip": ["-O2"], "rollout_point_task3.hip": ["-O2"], "rollout_point_scene.hip": ["-O2"],
     "rollout_point_scene_rows.hip": ["-O2"], "rollout_point_rollout_scenes.hip": ["-O2"],
-    "rollout_point_priors.hip": ["-O2"],
+    "rollout_point_priors.hip": ["-O2"], "rollout_point_priors_batch.hip": ["-O2"],   # (its twin's: the same bodies)
     "rollout_panda.hip": ["-fno-slp-vectorize", "-O2"],   # (round 4, world spec v2: -O2 -1.5 % reach / -4.5 % pick; with SLP +18 % / +11 %)
     "rollout_panda_scene.hip": ["-fno-slp-vectorize", "-O2"],   # (rollout_panda.hip's: the same bodies)
     "rollout_panda_weights.hip": ["-fno-slp-vectorize", "-O2"],   # (likewise)

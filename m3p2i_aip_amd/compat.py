@@ -236,13 +236,34 @@ def check_prior_samples(cfg):
     given = dict(cfg.prior_samples)
     if cfg.env_type != "point_env":
         raise ValueError("prior_samples: point_env only")
-    unknown = sorted(set(given) - {"controller", "n"})
+    unknown = sorted(set(given) - {"controller", "n", "device"})
     if unknown or given.get("controller") not in priors.CONTROLLERS:
         raise ValueError(f"prior_samples: {{controller: {' | '.join(priors.CONTROLLERS)}, n: 4}} (unknown key(s) {unknown})")
     n = int(given.get("n", 4))
     if not 1 <= n <= min(_lib.MAX_PRIOR_SAMPLES, int(cfg.mppi.num_samples) // 2 - 2):
         raise ValueError(f"prior_samples: n {n} is not in 1 .. min({_lib.MAX_PRIOR_SAMPLES}, num_samples / 2 - 2)")
+    if "device" in given:
+        if not isinstance(given["device"], bool):
+            raise ValueError(f"prior_samples: device is true or false, not {given['device']!r}")
+        if given["device"] and n > _lib.MAX_PRIOR_CONTROLLER_SEQS:
+            raise ValueError(f"prior_samples: device: true takes n in 1 .. {_lib.MAX_PRIOR_CONTROLLER_SEQS}, not {n}")
     return str(given["controller"]), n
+
+
+def prior_samples_on_device(cfg):
+    """the optional `device: true` of the `prior_samples` key: the controller runs on the device (MPPI.set_prior_controller),
+    set once instead of computed on the host every tick"""
+    given = getattr(cfg, "prior_samples", None)
+    return bool(given) and bool(dict(given).get("device", False))
+
+
+def set_device_prior_controller(cfg, planner):
+    """`prior_samples={..., device: true}`: the key's controller on the planner, once (MPPI.set_prior_controller) -- the kind the
+    host path takes for the task (push_behind where there is a box to go behind, else go_to), the key's n default speed factors,
+    the samples of prior_sample_indices"""
+    name, n = check_prior_samples(cfg)
+    kind = "push_behind" if name == "push_behind" and cfg.task != "navigation" else "go_to"
+    planner.set_prior_controller(kind, n, prior_sample_indices(int(cfg.mppi.num_samples), n, bool(cfg.multi_modal)))
 
 
 def prior_sample_indices(K, n, multi_modal):

@@ -21,7 +21,10 @@ struct BatchTableSizes {
                                             // panda tables have the literal section only (with a default: may be left out)
     size_t point_entry_sv = 0;              // ... of a point_env per-sample entry (a handle with an arena per sample); 0: a batch
                                             // without that section, whose point tables have the three variants' sections only
-                                            // (last and with a default: may be left out)
+                                            // (with a default: may be left out)
+    size_t point_entry_pr = 0;              // ... of a point_env priors entry (a handle with prior samples); 0: a batch without
+                                            // that section, whose point tables end with the per-sample section (last and with a
+                                            // default: may be left out)
 };
 struct BatchTableLayout {
     size_t off[BATCH_ROLLOUT_SECTIONS];   // start of each rollout section (panda_env: 0 the literal, 1 the run-time entries)
@@ -57,6 +60,26 @@ inline BatchTableLayout4 batch_table_layout4(const BatchTableSizes& z, const int
     for (int v = 0; v < BATCH_POINT_SECTIONS; ++v) {
         l.off[v] = align16(end);   // (an empty fourth section starts where the update section does)
         end = l.off[v] + (size_t)n[v] * batch_point_entry(z, v);
+        handles += (size_t)n[v];
+    }
+    l.upd_off = align16(end);
+    l.total = l.upd_off + handles * z.update;
+    return l;
+}
+// The point_env table of a batch with the priors section: the four sections above, then the entries of the handles with prior
+// samples (n[4] of them), then the UpdateArgs.  Without such handles the offsets and the total are those of batch_table_layout4.
+constexpr int BATCH_POINT_SECTIONS5 = BATCH_POINT_SECTIONS + 1;
+struct BatchTableLayout5 {
+    size_t off[BATCH_POINT_SECTIONS5];   // start of each rollout section
+    size_t upd_off, total;               // as BatchTableLayout's
+};
+inline size_t batch_point_entry5(const BatchTableSizes& z, int v) { return v < BATCH_POINT_SECTIONS ? batch_point_entry(z, v) : z.point_entry_pr; }
+inline BatchTableLayout5 batch_table_layout5(const BatchTableSizes& z, const int n[BATCH_POINT_SECTIONS5]) {
+    BatchTableLayout5 l{};
+    size_t end = 0, handles = 0;
+    for (int v = 0; v < BATCH_POINT_SECTIONS5; ++v) {
+        l.off[v] = align16(end);   // (an empty section starts where the next one does)
+        end = l.off[v] + (size_t)n[v] * batch_point_entry5(z, v);
         handles += (size_t)n[v];
     }
     l.upd_off = align16(end);
@@ -105,6 +128,22 @@ inline size_t batch_table_capacity(const BatchTableSizes& z, int max_handles) {
                     n[p1] = a; n[p2] = b; n[p3] = c; n[big4] = max_handles - a - b - c;
                     worst = std::max(worst, batch_table_layout4(z, n).total);
                 }
+    }
+    // (the five sections of a point_env table with the priors section, by the same argument; point_entry_pr == 0 adds nothing)
+    if (z.point_entry_pr != 0) {
+        int big5 = 0;
+        for (int v = 1; v < BATCH_POINT_SECTIONS5; ++v)
+            if (batch_point_entry5(z, v) > batch_point_entry5(z, big5)) big5 = v;
+        int o[BATCH_POINT_SECTIONS5 - 1];
+        for (int r = 1; r < BATCH_POINT_SECTIONS5; ++r) o[r - 1] = (big5 + r) % BATCH_POINT_SECTIONS5;
+        for (int a = 0; a < 16 && a <= max_handles; ++a)
+            for (int b = 0; b < 16 && a + b <= max_handles; ++b)
+                for (int c = 0; c < 16 && a + b + c <= max_handles; ++c)
+                    for (int d = 0; d < 16 && a + b + c + d <= max_handles; ++d) {
+                        int n[BATCH_POINT_SECTIONS5];
+                        n[o[0]] = a; n[o[1]] = b; n[o[2]] = c; n[o[3]] = d; n[big5] = max_handles - a - b - c - d;
+                        worst = std::max(worst, batch_table_layout5(z, n).total);
+                    }
     }
     return worst;
 }

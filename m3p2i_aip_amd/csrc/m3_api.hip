@@ -1048,22 +1048,19 @@ extern "C" int m3_set_panda_scene_instance(m3_handle* h, int on) {
 // ---- prior samples (extension, point_env planner handles, unsharded): samples of the fused rollout that take the caller's
 // control sequences.  THE allocation of the feature is the first setter call on a handle; m3_rollout and m3_command read the
 // two device blocks, nothing else.  Every check before any state changes ----
-static int set_prior_samples(m3_handle* h, const float* seqs, const int* sample_idx, int n, bool device) {
-    if (!h) return M3_ERR_BAD_ARG;
-    const std::string who = device ? "m3_set_prior_samples_device" : "m3_set_prior_samples";
+// the checks on the handle ...
+static int prior_handle_check(m3_handle* h, const std::string& who) {
     const m3_config& c = h->cfg;
     if (c.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, (who + env_only_text(M3_ENV_POINT)).c_str());
     if (c.sim_only) return fail(h, M3_ERR_STATE, (who + ": planner handles only (the handle was created sim_only)").c_str());
     if (c.K_local != c.K_global) return fail(h, M3_ERR_UNSUPPORTED, (who + ": sharded handle (K_local != K_global)").c_str());
-    if (n < 0 || n > M3_MAX_PRIOR_SAMPLES)
-        return fail(h, M3_ERR_BAD_ARG, (who + ": n is " + std::to_string(n) + ", must be in 0 .. " + std::to_string(M3_MAX_PRIOR_SAMPLES)).c_str());
-    PriorSampleState& ps = h->priors;
-    if (!seqs || n == 0) {   // exactly the kernels of a handle that never had priors (the blocks are kept for a later call)
-        ps.n = 0;
-        return M3_OK;
-    }
+    return M3_OK;
+}
+// ... and on the n sample indices
+static int prior_index_check(m3_handle* h, const std::string& who, const int* sample_idx, int n) {
+    const m3_config& c = h->cfg;
     if (!sample_idx) return fail(h, M3_ERR_BAD_ARG, (who + ": null sample_idx").c_str());
-    const int K = c.K_global, T = c.T, nu = c.nu;
+    const int K = c.K_global;
     for (int j = 0; j < n; ++j) {
         const int k = sample_idx[j];
         const std::string at = who + ": prior " + std::to_string(j) + ": sample " + std::to_string(k);
@@ -1074,14 +1071,14 @@ static int set_prior_samples(m3_handle* h, const float* seqs, const int* sample_
         for (int q = 0; q < j; ++q)
             if (sample_idx[q] == k) return fail(h, M3_ERR_BAD_ARG, (at + " listed twice").c_str());
     }
-    if (!device)
-        for (int j = 0; j < n; ++j)
-            for (int t = 0; t < T; ++t)
-                for (int u = 0; u < nu; ++u)
-                    if (!std::isfinite(seqs[((size_t)j * T + t) * nu + u]))
-                        return fail(h, M3_ERR_BAD_ARG, (who + ": prior " + std::to_string(j) + ": step " + std::to_string(t) + " control " +
-                                                        std::to_string(u) + " is not finite").c_str());
-    const int Kl = c.K_local;
+    return M3_OK;
+}
+// The blocks of the feature (allocated by the first call on the handle, as one group) and the slot map of these n indices on
+// the device.  Leaves the pinned mirror free to be rewritten: the previous call's uploads from it are over.
+static int prior_blocks_and_slots(m3_handle* h, const std::string& who, const int* sample_idx, int n) {
+    const m3_config& c = h->cfg;
+    PriorSampleState& ps = h->priors;
+    const int Kl = c.K_local, T = c.T, nu = c.nu;
     const size_t tab_bytes = (size_t)M3_MAX_PRIOR_SAMPLES * T * nu * sizeof(float), slot_bytes = (size_t)Kl * sizeof(int);
     bool slots_stale = false;
     if (!ps.tab_dev) {
@@ -1110,6 +1107,32 @@ static int set_prior_samples(m3_handle* h, const float* seqs, const int* sample_
         ps.dev_n = n;
         HIPCHK(h, hipMemcpyAsync(ps.slot_dev, slot, slot_bytes, hipMemcpyHostToDevice, h->stream));
     }
+    return M3_OK;
+}
+static int set_prior_samples(m3_handle* h, const float* seqs, const int* sample_idx, int n, bool device) {
+    if (!h) return M3_ERR_BAD_ARG;
+    const std::string who = device ? "m3_set_prior_samples_device" : "m3_set_prior_samples";
+    const m3_config& c = h->cfg;
+    int rc = prior_handle_check(h, who);
+    if (rc != M3_OK) return rc;
+    if (n < 0 || n > M3_MAX_PRIOR_SAMPLES)
+        return fail(h, M3_ERR_BAD_ARG, (who + ": n is " + std::to_string(n) + ", must be in 0 .. " + std::to_string(M3_MAX_PRIOR_SAMPLES)).c_str());
+    PriorSampleState& ps = h->priors;
+    if (!seqs || n == 0) {   // exactly the kernels of a handle that never had priors (the blocks are kept for a later call)
+        ps.n = 0;
+        ps.ctl.kind = 0;
+        return M3_OK;
+    }
+    if ((rc = prior_index_check(h, who, sample_idx, n)) != M3_OK) return rc;
+    const int T = c.T, nu = c.nu;
+    if (!device)
+        for (int j = 0; j < n; ++j)
+            for (int t = 0; t < T; ++t)
+                for (int u = 0; u < nu; ++u)
+                    if (!std::isfinite(seqs[((size_t)j * T + t) * nu + u]))
+                        return fail(h, M3_ERR_BAD_ARG, (who + ": prior " + std::to_string(j) + ": step " + std::to_string(t) + " control " +
+                                                        std::to_string(u) + " is not finite").c_str());
+    if ((rc = prior_blocks_and_slots(h, who, sample_idx, n)) != M3_OK) return rc;
     const size_t bytes = (size_t)n * T * nu * sizeof(float);
     if (device) {
         HIPCHK(h, hipMemcpyAsync(ps.tab_dev, seqs, bytes, hipMemcpyDeviceToDevice, h->stream));
@@ -1121,6 +1144,7 @@ static int set_prior_samples(m3_handle* h, const float* seqs, const int* sample_
     ps.upload_pending = true;
     ps.host_values = !device;
     ps.n = n;
+    ps.ctl.kind = 0;   // (against m3_set_prior_controller the last call wins: the table is the caller's again)
     return M3_OK;
 }
 extern "C" int m3_set_prior_samples(m3_handle* h, const float* seqs, const int* sample_idx, int n) {
@@ -1142,6 +1166,67 @@ extern "C" int m3_get_prior_sample(const m3_handle* h, int j, int* sample_idx, f
     return M3_OK;
 }
 extern "C" int m3_prior_samples_used(m3_handle* h) { return h ? h->priors.used : M3_ERR_BAD_ARG; }
+
+// ---- a prior controller (extension, m3p2i_hip_ext.h): the library fills the table, on the device, ahead of every rollout ----
+extern "C" void m3_default_prior_controller(m3_prior_controller* pc, int kind, int n) {
+    if (!pc) return;
+    std::memset(pc, 0, sizeof(*pc));
+    n = std::min(std::max(n, 1), M3_MAX_PRIOR_CONTROLLER_SEQS);
+    pc->kind = kind;
+    pc->n = n;
+    for (int j = 0; j < n; ++j) pc->speed[j] = 1.0f - (float)j / (float)n;
+    pc->standoff = 0.45f;
+    pc->reach = 0.05f;
+}
+extern "C" int m3_set_prior_controller(m3_handle* h, const m3_prior_controller* pc, const int* sample_idx) {
+    if (!h) return M3_ERR_BAD_ARG;
+    const std::string who = "m3_set_prior_controller";
+    int rc = prior_handle_check(h, who);
+    if (rc != M3_OK) return rc;
+    PriorSampleState& ps = h->priors;
+    if (!pc) {   // exactly the kernels of a handle that never had priors (the blocks are kept for a later call)
+        ps.n = 0;
+        ps.ctl.kind = 0;
+        return M3_OK;
+    }
+    if (pc->kind != M3_PRIOR_CONTROLLER_GO_TO && pc->kind != M3_PRIOR_CONTROLLER_PUSH_BEHIND)
+        return fail(h, M3_ERR_BAD_ARG, (who + ": unknown kind " + std::to_string(pc->kind) + " (M3_PRIOR_CONTROLLER_GO_TO = 1, _PUSH_BEHIND = 2)").c_str());
+    if (pc->n < 1 || pc->n > M3_MAX_PRIOR_CONTROLLER_SEQS)
+        return fail(h, M3_ERR_BAD_ARG, (who + ": n is " + std::to_string(pc->n) + ", must be in 1 .. " + std::to_string(M3_MAX_PRIOR_CONTROLLER_SEQS)).c_str());
+    const auto positive = [](float v) { return std::isfinite(v) && v > 0.0f; };
+    for (int j = 0; j < pc->n; ++j)
+        if (!positive(pc->speed[j]))
+            return fail(h, M3_ERR_BAD_ARG, (who + ": speed factor " + std::to_string(j) + " is not a finite positive number").c_str());
+    if (!positive(pc->standoff)) return fail(h, M3_ERR_BAD_ARG, (who + ": standoff is not a finite positive number").c_str());
+    if (!positive(pc->reach)) return fail(h, M3_ERR_BAD_ARG, (who + ": reach is not a finite positive number").c_str());
+    if ((rc = prior_index_check(h, who, sample_idx, pc->n)) != M3_OK) return rc;
+    if ((rc = prior_blocks_and_slots(h, who, sample_idx, pc->n)) != M3_OK) return rc;
+    HIPCHK(h, hipEventRecord(ps.uploaded, h->stream));   // (behind the slot map's copy, if there was one)
+    ps.upload_pending = true;
+    ps.host_values = false;
+    ps.n = pc->n;
+    ps.ctl = *pc;
+    for (int j = pc->n; j < M3_MAX_PRIOR_CONTROLLER_SEQS; ++j) ps.ctl.speed[j] = 0.0f;   // (what the getter returns is defined)
+    return M3_OK;
+}
+extern "C" int m3_get_prior_controller(const m3_handle* h, m3_prior_controller* out) {
+    if (!h || !out) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_POINT) return M3_ERR_UNSUPPORTED;
+    std::memset(out, 0, sizeof(*out));
+    if (h->priors.n > 0 && h->priors.ctl.kind != 0) *out = h->priors.ctl;
+    return M3_OK;
+}
+extern "C" int m3_prior_table(const m3_handle* h, const float** tab_dev, int* n) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_POINT) return M3_ERR_UNSUPPORTED;
+    if (!h->priors.tab_dev) return M3_ERR_STATE;
+    if (tab_dev) *tab_dev = h->priors.tab_dev;
+    if (n) *n = h->priors.n;
+    return M3_OK;
+}
+// the handle has a controller that the next rollout runs
+static bool prior_controller_on(const m3_handle* h) { return h->priors.n > 0 && h->priors.ctl.kind != 0; }
+static PriorControllerArgs prior_controller_args(const m3_handle* h) { return {h->priors.ctl, h->cfg.dt, h->priors.tab_dev}; }
 
 // the handle's arena is the default bit for bit (-0.0f is not 0.0f here)
 static bool default_point_scene(const m3_handle* h) {
@@ -1407,6 +1492,8 @@ static const char* rollout_refusal(const m3_handle* h) {
         return "m3_rollout: simple mode needs m3_set_noise or sampling_random";
     if (h->task == M3_TASK_PUSH_PULL && !c.multi_modal) return "m3_rollout: push_pull needs multi_modal";
     if (const char* why = panda_refusal(h, PANDA_SIDE_ROLLOUT)) return why;
+    if (prior_controller_on(h) && h->priors.ctl.kind == M3_PRIOR_CONTROLLER_PUSH_BEHIND && h->task == M3_TASK_NAVIGATION)
+        return "m3_rollout: the prior controller is PUSH_BEHIND (m3_set_prior_controller) but the task is navigation, which has no box to go behind";
     return point_variant_refusal(h, SIDE_ROLLOUT);
 }
 
@@ -1521,6 +1608,8 @@ extern "C" int m3_rollout(m3_handle* h) {
     if (rc != M3_OK) return rc;
     if (h->cfg.env_type == M3_ENV_POINT) { h->point_form_used = p.form; h->priors.used = p.priors; }
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+    // the handle's ancillary controllers fill its table of priors from the world this rollout starts from, directly ahead of it
+    if (prior_controller_on(h)) launch_prior_controllers(a, prior_controller_args(h), h->stream);
     if (h->cfg.env_type == M3_ENV_POINT) launch_rollout_point(a, h->scene, h->scene_rt, h->cost_weights, p, h->stream, h->rollout_err_dev, h->point_rows.dev,
                                                               h->priors.slot_dev, h->priors.tab_dev);
     else {
@@ -1530,6 +1619,29 @@ extern "C" int m3_rollout(m3_handle* h) {
     }
     HIPCHK(h, hipGetLastError());
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+    return M3_OK;
+}
+
+// the controller alone, for the world currently set or bound: what the next rollout's launch of it would write
+extern "C" int m3_prior_controller_fill(m3_handle* h) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (h->cfg.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, (std::string("m3_prior_controller_fill") + env_only_text(M3_ENV_POINT)).c_str());
+    if (!prior_controller_on(h)) return fail(h, M3_ERR_STATE, "m3_prior_controller_fill: the handle has no prior controller (m3_set_prior_controller)");
+    if (const char* why = rollout_refusal(h)) return fail(h, M3_ERR_STATE, why);
+    // (of the rollout's arguments the kernel reads the world, the goal, u_max and T: no wavefront order is refreshed here)
+    const m3_config& c = h->cfg;
+    RolloutArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.Kg = c.K_global; a.Kl = c.K_local; a.k0 = c.k_offset; a.T = c.T; a.nu = c.nu;
+    for (int j = 0; j < c.nu; ++j) { a.u_min[j] = c.u_min[j]; a.u_max[j] = c.u_max[j]; }
+    fill_cost_params(h, a.cp);
+    std::memcpy(a.world0, h->world0, sizeof(a.world0));
+    if (h->bind_dof) {
+        a.sim_dof = h->bind_dof; a.sim_root = h->bind_root;
+        a.sim_box = h->bind_box; a.sim_dyn = h->bind_dyn;
+    }
+    launch_prior_controllers(a, prior_controller_args(h), h->stream);
+    HIPCHK(h, hipGetLastError());
     return M3_OK;
 }
 
@@ -2111,7 +2223,9 @@ auto rollout_fields(const BatchKey& k) {
     const RolloutPlan& p = k.roll;
     // (scene, then weighted, first: that is the order of PointVariant, by which the table's sections lie)
     // (panda_env: the variant first, so that each of its two sections is contiguous in key order)
-    return std::tie(k.variant, p.scene, p.weighted, p.instance, p.ref, p.lps, p.forces, p.general, p.shadows, p.rec, k.K, k.T, p.lanes);
+    // (priors first: the handles with prior samples sort last, as their section lies; their key carries scene 1 whether or not
+    // they have an arena per sample -- batch_command -- so they group by K, T and lanes alone)
+    return std::tie(k.variant, p.priors, p.scene, p.weighted, p.instance, p.ref, p.lps, p.forces, p.general, p.shadows, p.rec, k.K, k.T, p.lanes);
 }
 auto update_fields(const BatchKey& k) { return std::tie(k.upd.nu, k.upd.multi, k.upd.jr, k.upd.wt, k.upd.n_cand, k.T); }
 bool same_rollout(const BatchKey& x, const BatchKey& y) { return rollout_fields(x) == rollout_fields(y); }
@@ -2128,9 +2242,9 @@ struct BatchHandle {   // one handle's command as planned, in call order (copied
 constexpr BatchTableSizes BATCH_TABLE_SIZES = {{sizeof(BatchRolloutEntry), sizeof(BatchRolloutEntryW), sizeof(BatchRolloutEntryS)},
                                                sizeof(BatchPandaEntry), sizeof(UpdateArgs), 0};
 // (a batch created with M3_BATCH_SECTION_PANDA_RUNTIME / _POINT_ROLLOUT_SCENES: + panda_entry_rt / point_entry_sv, m3_batch_create)
-static_assert(alignof(BatchPandaEntryRT) <= 16 && alignof(BatchPandaEntry) <= 16 && alignof(BatchRolloutEntrySV) <= 16,
-              "the table's sections start on multiples of 16");
-static_assert(BATCH_POINT_SECTIONS == POINT_SECTIONS, "");
+static_assert(alignof(BatchPandaEntryRT) <= 16 && alignof(BatchPandaEntry) <= 16 && alignof(BatchRolloutEntrySV) <= 16 &&
+              alignof(BatchRolloutEntryPR) <= 16, "the table's sections start on multiples of 16");
+static_assert(BATCH_POINT_SECTIONS5 == POINT_SECTIONS, "");
 // the refusal of a point_env handle with an arena per sample by a batch or an episode set that was not created for it
 constexpr const char* PRIORS_UNBATCHED = "it has prior samples (m3_set_prior_samples), which only m3_rollout / m3_command run";
 constexpr const char* POINT_ROWS_UNBATCHED = "it has an arena per sample (m3_set_point_rollout_scenes), which only m3_rollout / m3_command run";
@@ -2180,7 +2294,7 @@ extern "C" int m3_batch_create_ex(int device, int max_handles, int flags, m3_bat
 static_assert(M3_BATCH_SECTION_PANDA_RUNTIME == M3_BATCH_PANDA_RUNTIME, "one bit, two names");
 extern "C" int m3_batch_create_sections(int device, int max_handles, int sections, m3_batch** out) {
     if (out) *out = nullptr;
-    if (sections & ~(M3_BATCH_SECTION_PANDA_RUNTIME | M3_BATCH_SECTION_POINT_ROLLOUT_SCENES)) {
+    if (sections & ~(M3_BATCH_SECTION_PANDA_RUNTIME | M3_BATCH_SECTION_POINT_ROLLOUT_SCENES | M3_BATCH_SECTION_POINT_PRIORS)) {
         g_batch_err = "m3_batch_create_sections: unknown section bits";
         return M3_ERR_BAD_ARG;
     }
@@ -2208,6 +2322,7 @@ static int batch_create(int device, int max_handles, int flags, m3_batch** out) 
     b->flags = flags;
     if (flags & M3_BATCH_SECTION_PANDA_RUNTIME) b->sizes.panda_entry_rt = sizeof(BatchPandaEntryRT);
     if (flags & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES) b->sizes.point_entry_sv = sizeof(BatchRolloutEntrySV);
+    if (flags & M3_BATCH_SECTION_POINT_PRIORS) b->sizes.point_entry_pr = sizeof(BatchRolloutEntryPR);
     b->slot_bytes = batch_table_capacity(b->sizes, max_handles);
     try {
         b->seen.resize(max_handles);
@@ -2249,17 +2364,19 @@ extern "C" int m3_batch_launches(const m3_batch* b, int* rollout_launches, int* 
 // launches it.  panda_runtime: the caller's table has the run-time section (a batch created with M3_BATCH_PANDA_RUNTIME), so a
 // panda_env planner that needs the run-time-scene instance, the weighted family or has a workspace per sample passes.
 // point_rows: it has the per-sample section (M3_BATCH_SECTION_POINT_ROLLOUT_SCENES), so a point_env planner with an arena per
-// sample passes
-static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code, bool panda_runtime = false, bool point_rows = false) {
+// sample passes.  point_priors: it has the priors section (M3_BATCH_SECTION_POINT_PRIORS), so a point_env planner with prior
+// samples passes -- with or without an arena per sample, which that section's entry carries as well
+static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code, bool panda_runtime = false, bool point_rows = false,
+                                 bool point_priors = false) {
     const m3_config& c = h->cfg;
     code = M3_ERR_STATE;
     if (c.K_local != c.K_global) return "sharded handle (K_local != K_global)";
     if (c.sim_only) return "handle was created sim_only";
-    if (h->point_rows.sample_on && !point_rows) {   // (the table's slots have no fourth section)
+    if (h->point_rows.sample_on && !point_rows && !(point_priors && h->priors.n > 0)) {   // (the table's slots have no fourth section)
         code = M3_ERR_UNSUPPORTED;
         return POINT_ROWS_UNBATCHED;
     }
-    if (h->priors.n > 0) {   // (no table entry carries a slot map and a table of priors)
+    if (h->priors.n > 0 && !point_priors) {   // (no table entry carries a slot map and a table of priors)
         code = M3_ERR_UNSUPPORTED;
         return PRIORS_UNBATCHED;
     }
@@ -2291,8 +2408,10 @@ static int batch_refuse(m3_batch* b, int code, int i, const char* msg) {
 // panda_runtime: whether the run-time section may be used -- the batch's flag for m3_batch_command and for a lockstep panda
 // episode set created with M3_PANDA_EPISODES_RUNTIME; never for a set created without it, whose pre and post kernels know one
 // compiled-in workspace (whatever batch it is handed).  point_rows: whether the per-sample section of a point_env table may be
-// used -- the batch's flag for m3_batch_command and for a lockstep episode set created with M3_EPISODES_ROLLOUT_SCENES
-static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* actions_host, bool panda_runtime, bool point_rows) {
+// used -- the batch's flag for m3_batch_command and for a lockstep episode set created with M3_EPISODES_ROLLOUT_SCENES.
+// point_priors: the same for the priors section -- the batch's flag, and for a set only if it was created with M3_EPISODES_PRIORS
+static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* actions_host, bool panda_runtime, bool point_rows,
+                         bool point_priors) {
     // ---- every check before any launch: a refused call leaves every handle as it was ----
     if (!hs) return batch_refuse(b, M3_ERR_BAD_ARG, -1, "null handle list");
     if (n <= 0 || n > b->max_handles) return batch_refuse(b, M3_ERR_BAD_ARG, -1, "n must be in 1 .. max_handles");
@@ -2317,7 +2436,7 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
                                                                 : "panda_env handle in a batch of point_env handles (one environment per call)");
         if (h->stream != s) return batch_refuse(b, M3_ERR_STATE, i, "its stream differs from handle 0's");
         int code;
-        if (const char* why = batch_refusal(h, hd[i].u, code, panda_runtime, point_rows)) return batch_refuse(b, code, i, why);
+        if (const char* why = batch_refusal(h, hd[i].u, code, panda_runtime, point_rows, point_priors)) return batch_refuse(b, code, i, why);
         BatchKey& k = hd[i].key;
         if (panda) hd[i].panda = panda_decision(panda_input(h), PANDA_SIDE_BATCH);   // (by m3_rollout's own dispatch)
         k.variant = panda ? panda_batch_key(hd[i].panda.variant) : 0;
@@ -2333,6 +2452,9 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
         if (rc != M3_OK) { b->err = "m3_batch_command: " + hs[i]->err; return rc; }
         // (the run-time families are GENERAL builds only: the plan's choice of the literal kernel's build does not split a group)
         if (panda && panda_general_only(hd[i].panda.variant)) hd[i].key.roll.general = 1;
+        // (one kernel family serves the handles with priors with and without an arena per sample -- the entry's rows say which:
+        // the arena per sample does not split a group)
+        if (!panda && hd[i].key.roll.priors) hd[i].key.roll.scene = 1;
     }
     // ---- groups: handles in key order (ties in call order) ----
     std::sort(b->by_roll.begin(), b->by_roll.begin() + n, [hd](int x, int y) {
@@ -2355,8 +2477,9 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
         for (int i = 0; i < n; ++i) ++count[point_section(hd[i].key.roll)];
     else
         for (int i = 0; i < n; ++i) n_lit += hd[i].panda.variant == PANDA_LITERAL ? 1 : 0;
-    // (without per-sample handles the four-section layout is the three-section one)
-    BatchTableLayout4 lay = batch_table_layout4(b->sizes, count);
+    // (without per-sample handles the four-section layout is the three-section one; without handles with priors the
+    // five-section layout is the four-section one)
+    BatchTableLayout5 lay = batch_table_layout5(b->sizes, count);
     if (panda) {
         const BatchTableLayout lp = batch_table_layout_panda(b->sizes, n_lit, n - n_lit);
         lay.off[1] = lp.off[1];
@@ -2368,7 +2491,7 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
         if (panda) return p < n_lit ? (size_t)p * sizeof(BatchPandaEntry) : lay.off[1] + (size_t)(p - n_lit) * sizeof(BatchPandaEntryRT);
         int v = 0;
         for (; p >= count[v]; ++v) p -= count[v];
-        return lay.off[v] + (size_t)p * batch_point_entry(b->sizes, v);
+        return lay.off[v] + (size_t)p * batch_point_entry5(b->sizes, v);
     };
     for (int p = 0; p < n; ++p) {
         const int i = b->by_roll[p];
@@ -2381,6 +2504,14 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
             continue;
         }
         switch (point_section(hd[i].key.roll)) {
+            case POINT_SECTION_PR: {
+                // (the handle's own blocks; without a controller kind 0: the table is the caller's)
+                PriorControllerArgs ctl = {{}, h->cfg.dt, h->priors.tab_dev};
+                if (prior_controller_on(h)) ctl.pc = h->priors.ctl;
+                *reinterpret_cast<BatchRolloutEntryPR*>(e) = {hd[i].a, h->scene_rt, h->cost_weights,
+                                                             h->point_rows.sample_on ? h->point_rows.dev : nullptr, h->priors.slot_dev, ctl};
+                break;
+            }
             case POINT_SECTION_SV: *reinterpret_cast<BatchRolloutEntrySV*>(e) = {hd[i].a, h->scene_rt, h->cost_weights, h->point_rows.dev}; break;
             case POINT_SCENE: *reinterpret_cast<BatchRolloutEntryS*>(e) = {hd[i].a, h->scene_rt, h->cost_weights}; break;
             case POINT_WEIGHTED: *reinterpret_cast<BatchRolloutEntryW*>(e) = {hd[i].a, h->scene, h->cost_weights}; break;
@@ -2395,6 +2526,18 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
     // ---- one rollout launch per group (panda_env: + one k_panda_reach_cost launch when the group keeps the record buffer,
     // not counted) ----
     int n_roll = 0, n_upd = 0;
+    // the ancillary controllers of the handles that have one fill their tables of priors from the worlds the rollouts are about
+    // to start from: one launch over the priors section, ahead of the rollout launches (not counted)
+    if (!panda && count[POINT_SECTION_PR] > 0) {
+        bool any = false;
+        for (int i = 0; i < n; ++i) {
+            any = any || prior_controller_on(hs[i]);
+            if (hd[i].key.roll.priors) hs[i]->priors.used = 1;   // (as m3_rollout records it)
+        }
+        if (any)
+            launch_prior_controllers_batch(reinterpret_cast<const BatchRolloutEntryPR*>(dslot + lay.off[POINT_SECTION_PR]),
+                                           count[POINT_SECTION_PR], s);
+    }
     for (int p = 0; p < n;) {
         const BatchKey& k = hd[b->by_roll[p]].key;
         int q = p + 1;
@@ -2451,7 +2594,7 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
 extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float* actions_host) {
     if (!b) { g_batch_err = "m3_batch_command: null batch"; return M3_ERR_BAD_ARG; }
     return batch_command(b, hs, n, actions_host, (b->flags & M3_BATCH_SECTION_PANDA_RUNTIME) != 0,
-                         (b->flags & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES) != 0);
+                         (b->flags & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES) != 0, (b->flags & M3_BATCH_SECTION_POINT_PRIORS) != 0);
 }
 
 static int ensure_sim(m3_handle* h);
@@ -2683,7 +2826,7 @@ static thread_local std::string g_eps_err;
 struct m3_episodes {
     m3_handle* world = nullptr;
     int n = 0, max_ticks = 0, tick = 0;
-    int flags = 0;                   // m3_episodes_create_ex's (M3_EPISODES_ROLLOUT_SCENES)
+    int flags = 0;                   // m3_episodes_create_ex's (M3_EPISODES_ROLLOUT_SCENES, M3_EPISODES_PRIORS)
     bool mid_tick = false;           // between m3_episodes_begin and m3_episodes_end
     std::string err;
     std::vector<m3_handle*> planners;
@@ -2724,9 +2867,10 @@ extern "C" int m3_episodes_flags(const m3_episodes* eps) { return eps ? eps->fla
 extern "C" int m3_episodes_create_ex(m3_handle* world, m3_handle* const* planners, const m3_episode_spec* specs, int n,
                                      int max_ticks, int trace, int flags, m3_episodes** out) {
     if (out) *out = nullptr;
-    if (flags & ~M3_EPISODES_ROLLOUT_SCENES) { g_eps_err = "m3_episodes_create_ex: unknown flag bits"; return M3_ERR_BAD_ARG; }
+    if (flags & ~(M3_EPISODES_ROLLOUT_SCENES | M3_EPISODES_PRIORS)) { g_eps_err = "m3_episodes_create_ex: unknown flag bits"; return M3_ERR_BAD_ARG; }
     if (!out) return eps_refuse(M3_ERR_BAD_ARG, -1, "null argument");
     const bool point_rows = (flags & M3_EPISODES_ROLLOUT_SCENES) != 0;   // planners with an arena per sample pass
+    const bool point_priors = (flags & M3_EPISODES_PRIORS) != 0;         // planners with prior samples pass
     // ---- every check before any allocation or launch ----
     if (!world || !planners || !specs) return eps_refuse(M3_ERR_BAD_ARG, -1, "null argument");
     if (n <= 0 || n > 65535) return eps_refuse(M3_ERR_BAD_ARG, -1, "n must be in 1 .. 65535");
@@ -2748,7 +2892,7 @@ extern "C" int m3_episodes_create_ex(m3_handle* world, m3_handle* const* planner
         if (h->stream != world->stream) return eps_refuse(M3_ERR_STATE, i, "its stream differs from the world's");
         UpdateArgs u;
         int code;
-        if (const char* why = batch_refusal(h, u, code, false, point_rows)) return eps_refuse(code, i, why);
+        if (const char* why = batch_refusal(h, u, code, false, point_rows, point_priors)) return eps_refuse(code, i, why);
         if (!h->action_out) return eps_refuse(M3_ERR_STATE, i, "no action-out destination (m3_set_action_out)");
         const m3_episode_spec& sp = specs[i];
         if (sp.task < M3_TASK_NAVIGATION || sp.task > M3_TASK_PUSH_PULL) return eps_refuse(M3_ERR_BAD_ARG, i, "spec: task is not a point_env task");
@@ -2841,8 +2985,10 @@ static int eps_status_sync(m3_episodes* eps) {
     return M3_OK;
 }
 
-// a planner that got prior samples after m3_episodes_create (which refuses it): nothing of the tick is launched
+// a planner that got prior samples after m3_episodes_create (which refuses it): nothing of the tick is launched.  A set created
+// with M3_EPISODES_PRIORS takes such planners
 static int eps_priors_refusal(m3_episodes* eps, const char* who) {
+    if (eps->flags & M3_EPISODES_PRIORS) return M3_OK;
     for (int i = 0; i < eps->n; ++i)
         if (eps->planners[i]->priors.n > 0) {
             eps->err = std::string(who) + ": planner " + std::to_string(i) + ": " + PRIORS_UNBATCHED;
@@ -2890,15 +3036,24 @@ extern "C" int m3_episodes_tick(m3_episodes* eps, m3_batch* batch) {
     eps->live.clear();
     const m3_handle* w = eps->world;
     const bool point_rows = (eps->flags & M3_EPISODES_ROLLOUT_SCENES) != 0;
+    const bool point_priors = (eps->flags & M3_EPISODES_PRIORS) != 0;
+    const bool batch_priors = (batch->flags & M3_BATCH_SECTION_POINT_PRIORS) != 0;
     for (int i = 0; i < eps->n; ++i) {
         if (eps->host[i].done_tick >= 0) continue;
         m3_handle* h = eps->planners[i];
-        if (h->point_rows.sample_on && !point_rows) {   // (set after m3_episodes_create, which refuses it: nothing of this tick is launched)
+        // (a set created for planners with priors, a batch without the section: the batch's own refusal, ahead of the pre kernel)
+        if (h->priors.n > 0 && !batch_priors) {
+            rc = batch_refuse(batch, M3_ERR_UNSUPPORTED, (int)eps->live.size(), PRIORS_UNBATCHED);
+            eps->err = std::string("m3_episodes_tick: ") + m3_batch_last_error(batch);
+            return rc;
+        }
+        const bool in_priors_section = h->priors.n > 0 && point_priors;   // (its entry carries the rows as well)
+        if (h->point_rows.sample_on && !point_rows && !in_priors_section) {   // (set after m3_episodes_create, which refuses it: nothing of this tick is launched)
             eps->err = "m3_episodes_tick: planner " + std::to_string(i) + ": " + POINT_ROWS_UNBATCHED;
             return M3_ERR_UNSUPPORTED;
         }
         // (a set created for such planners, a batch without the section: the batch's own refusal, ahead of the pre kernel)
-        if (h->point_rows.sample_on && !(batch->flags & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES)) {
+        if (h->point_rows.sample_on && !in_priors_section && !(batch->flags & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES)) {
             rc = batch_refuse(batch, M3_ERR_UNSUPPORTED, (int)eps->live.size(), POINT_ROWS_UNBATCHED);
             eps->err = std::string("m3_episodes_tick: ") + m3_batch_last_error(batch);
             return rc;
@@ -2915,7 +3070,7 @@ extern "C" int m3_episodes_tick(m3_episodes* eps, m3_batch* batch) {
     if (!eps->live.empty()) {
         // (a set created without the flag never uses the per-sample section, whatever batch it is handed)
         rc = batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr, (batch->flags & M3_BATCH_SECTION_PANDA_RUNTIME) != 0,
-                           point_rows && (batch->flags & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES) != 0);
+                           point_rows && (batch->flags & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES) != 0, point_priors && batch_priors);
         if (rc != M3_OK) { eps->err = std::string("m3_episodes_tick: ") + m3_batch_last_error(batch); return rc; }
     }
     episodes_post(w, eps->args, eps->tick);
@@ -3264,7 +3419,7 @@ extern "C" int m3_panda_episodes_act(m3_panda_episodes* eps, m3_batch* batch, co
         // as m3_batch_command does: a batch without the section refuses a planner that needs it, with its code and message,
         // before anything is launched)
         const bool section = peps_mode(eps->flags) == PANDA_EPISODES_RUNTIME && (batch->flags & M3_BATCH_PANDA_RUNTIME) != 0;
-        rc = batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr, section, false);
+        rc = batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr, section, false, false);
         if (rc != M3_OK) { eps->err = std::string("m3_panda_episodes_act: ") + m3_batch_last_error(batch); return rc; }
     }
     return peps_post(eps, ended_host);

@@ -232,13 +232,16 @@ struct RolloutPlan {
                          // weighted == 1, ref == 0, form == 0); 2: its per-sample twin (m3_set_point_rollout_scenes) -- no
                          // variant of its own; in a batch created with the per-sample section, the table's fourth section
     int priors;          // point_env: the prior build of that instance (m3_set_prior_samples, rollout_point_priors.hip; scene 1 or 2,
-                         // instance == -1, weighted == 1, ref == 0, form == 0); m3_rollout only -- the batched and episode
-                         // paths refuse such a handle
+                         // instance == -1, weighted == 1, ref == 0, form == 0); in a batch created with the priors section, the
+                         // table's fifth section -- every other batch and episode set refuses such a handle
 };
 inline PointVariant point_variant(const RolloutPlan& p) { return p.scene ? POINT_SCENE : p.weighted ? POINT_WEIGHTED : POINT_PLAIN; }
 // the section of the point_env batch table a plan's entry lies in: its variant's, the per-sample handles behind them
-constexpr int POINT_SECTIONS = POINT_VARIANTS + 1, POINT_SECTION_SV = POINT_VARIANTS;
-inline int point_section(const RolloutPlan& p) { return p.scene == 2 ? POINT_SECTION_SV : (int)point_variant(p); }
+// (in a batch created with the priors section, the handles with prior samples behind those: the fifth section)
+constexpr int POINT_SECTIONS = POINT_VARIANTS + 2, POINT_SECTION_SV = POINT_VARIANTS, POINT_SECTION_PR = POINT_VARIANTS + 1;
+inline int point_section(const RolloutPlan& p) {
+    return p.priors ? POINT_SECTION_PR : p.scene == 2 ? POINT_SECTION_SV : (int)point_variant(p);
+}
 // form_request: m3_set_point_rollout_form's value (0 one wavefront, 1 two wherever available, -1 by rollout_companion_pays)
 // per_sample: the handle carries one arena per sample (variant POINT_SCENE then): RolloutPlan::scene = 2
 // priors: the handle has prior samples set (variant POINT_SCENE then): RolloutPlan::priors = 1
@@ -262,6 +265,35 @@ void launch_rollout_point(const RolloutArgs& a, const PointScene& sc, const Poin
 // ... of a planner handle with prior samples (rollout_point_priors.hip; rows: null or the handle's per-sample arenas)
 void launch_rollout_point_pr(const RolloutArgs& a, const PointSceneRT& uni, const float* rows, const PointCostWeights& wt,
                              const int* prior_slot, const float* prior_tab, int blocks, hipStream_t s);
+// the ancillary controllers of a handle with a prior controller (m3_set_prior_controller; prior_controllers.hip): fills rows
+// 0 .. c.pc.n - 1 of c.tab from the world, goal, u_max and T of a, the arguments of the rollout launched behind it
+struct PriorControllerArgs {
+    m3_prior_controller pc;
+    float dt;      // the handle's
+    float* tab;    // the handle's table of prior samples, device [M3_MAX_PRIOR_SAMPLES][T][2]
+};
+void launch_prior_controllers(const RolloutArgs& a, const PriorControllerArgs& c, hipStream_t s);
+// a point_env handle with prior samples (m3_set_prior_samples, m3_set_prior_controller), in a batch created with the priors
+// section: what BatchRolloutEntrySV holds (rows: null or the handle's per-sample table), the handle's OWN slot map and table of
+// priors (ctl.tab, [M3_MAX_PRIOR_SAMPLES][T][2]) and its controller (ctl.pc.kind 0: the table is the caller's); the batch stores
+// no priors
+struct BatchRolloutEntryPR {
+    RolloutArgs a;
+    PointSceneRT sc;
+    PointCostWeights wt;
+    const float* rows;
+    const int* prior_slot;
+    PriorControllerArgs ctl;
+};
+static_assert(sizeof(BatchRolloutEntryPR) == 872 && offsetof(BatchRolloutEntryPR, sc) == 528 && offsetof(BatchRolloutEntryPR, wt) == 724 &&
+              offsetof(BatchRolloutEntryPR, rows) == 760 && offsetof(BatchRolloutEntryPR, prior_slot) == 768 &&
+              offsetof(BatchRolloutEntryPR, ctl) == 776 && alignof(BatchRolloutEntryPR) <= 16, "");
+// ... of a group of n such handles of the same K, T and lanes (rollout_point_priors_batch.hip; tab: device; blocks: workgroups
+// of one handle)
+void launch_rollout_point_pr_batch(const BatchRolloutEntryPR* tab, int blocks, int n, hipStream_t s);
+// the controllers of the n entries of a batch's priors section, one launch ahead of its rollout launches (an entry without a
+// controller: nothing)
+void launch_prior_controllers_batch(const BatchRolloutEntryPR* tab, int n, hipStream_t s);
 // ... of a planner handle with an arena per sample (rollout_point_rollout_scenes.hip; uni, rows: point_scene_rows.hpp)
 void launch_rollout_point_sv(const RolloutArgs& a, const PointSceneRT& uni, const float* rows, const PointCostWeights& wt,
                              int blocks, hipStream_t s);
@@ -514,6 +546,8 @@ struct PriorSampleState {
     hipEvent_t uploaded = nullptr;   // recorded behind the last upload from `pinned`
     bool upload_pending = false;
     int used = -1;                // m3_prior_samples_used
+    m3_prior_controller ctl = {}; // m3_set_prior_controller (kind 0: none -- the table is the caller's): the rows 0 .. n - 1 of
+                                  // tab_dev are written by k_prior_controllers ahead of every rollout
 };
 }  // namespace m3
 

@@ -96,7 +96,8 @@ void launch_rollout_point_batch(const void* tab, int n, const RolloutPlan& p, hi
     const bool ref = p.ref != 0;
     switch (point_variant(p)) {
         case POINT_SCENE:
-            if (p.scene == 2) launch_rollout_point_sv_batch(static_cast<const BatchRolloutEntrySV*>(tab), p.blocks, n, s);
+            if (p.priors) launch_rollout_point_pr_batch(static_cast<const BatchRolloutEntryPR*>(tab), p.blocks, n, s);
+            else if (p.scene == 2) launch_rollout_point_sv_batch(static_cast<const BatchRolloutEntrySV*>(tab), p.blocks, n, s);
             else launch_rollout_point_batch_instance<true, -1>(static_cast<const BatchRolloutEntryS*>(tab), p.blocks, n, ref, s);
             return;
         case POINT_WEIGHTED:

@@ -409,6 +409,54 @@ class HipEngine(_CObject):
         """1 / 0: the last rollout launched the prior build; -1 before the first"""
         return int(self.lib.m3_prior_samples_used(self._h))
 
+    def set_prior_controller(self, kind=None, n=4, indices=None, speeds=None, standoff=None, reach=None):
+        """Extension, unsharded point_env planner engines: an ancillary controller ON THE DEVICE (m3_set_prior_controller) --
+        the library fills the table of prior samples from the world each rollout starts from, in a kernel ahead of it; nothing
+        is uploaded per command.  kind: "go_to" | "push_behind" (or the M3_PRIOR_CONTROLLER_* value); n sequences, one per
+        speed factor (default 1 - j / n), the priors of the GLOBAL samples indices (default 0 .. n-1).  kind=None clears
+        controller and priors.  Against set_prior_samples the last call wins."""
+        if kind is None:
+            self._ck(self.lib.m3_set_prior_controller(self._h, None, None))
+            return
+        pc = L.PriorController()
+        self.lib.m3_default_prior_controller(C.byref(pc), int(L.PRIOR_CONTROLLER_KINDS.get(kind, kind)), int(n))
+        pc.n = int(n)     # (the defaults clamp n; the setter refuses what is out of range)
+        if speeds is not None:
+            if len(speeds) != int(n):
+                raise ValueError(f"set_prior_controller: {int(n)} sequences but {len(speeds)} speed factors")
+            if int(n) <= L.MAX_PRIOR_CONTROLLER_SEQS:
+                for j, f in enumerate(speeds):
+                    pc.speed[j] = float(f)
+        if standoff is not None:
+            pc.standoff = float(standoff)
+        if reach is not None:
+            pc.reach = float(reach)
+        idx = list(range(int(n))) if indices is None else [int(i) for i in indices]
+        if len(idx) != int(n):
+            raise ValueError(f"set_prior_controller: {int(n)} sequences but {len(idx)} indices")
+        self._ck(self.lib.m3_set_prior_controller(self._h, C.byref(pc), (C.c_int * max(len(idx), 1))(*idx)))
+
+    def prior_controller(self):
+        """the controller as set ({kind, n, speeds, standoff, reach}), or None"""
+        pc = L.PriorController()
+        self._ck_code(self.lib.m3_get_prior_controller(self._h, C.byref(pc)), "m3_get_prior_controller")
+        if pc.kind == 0:
+            return None
+        return dict(kind=pc.kind, n=pc.n, speeds=[float(pc.speed[j]) for j in range(pc.n)], standoff=float(pc.standoff),
+                    reach=float(pc.reach))
+
+    def prior_controller_fill(self):
+        """launches the controller alone, for the world currently set or bound (what the next rollout's launch would write)"""
+        self._ck(self.lib.m3_prior_controller_fill(self._h))
+
+    def prior_table(self) -> torch.Tensor:
+        """zero-copy view [n, T, nu] of the rows of the table of prior samples that are set (read-only by convention; ordered
+        on the engine's stream)"""
+        p = C.c_void_p()
+        n = C.c_int()
+        self._ck_code(self.lib.m3_prior_table(self._h, C.byref(p), C.byref(n)), "m3_prior_table")
+        return torch.as_tensor(_DevArray(p.value, (max(n.value, 1), self.cfg.T, self.cfg.nu), "<f4", self), device=self.device)[:n.value]
+
     def _ck_code(self, rc, who):
         # (the getters leave no message behind)
         if rc != 0:
@@ -788,11 +836,13 @@ class HipBatch(_CObject):
     ``panda_runtime=True`` (``M3_BATCH_PANDA_RUNTIME``) makes room for the larger table entries of panda_env engines with a
     workspace of their own, tuned cost weights or a workspace per sample, which any other batch refuses.
     ``point_runtime=True`` (``M3_BATCH_SECTION_POINT_ROLLOUT_SCENES``, ``m3_batch_create_sections``) makes room for the entries
-    of point_env engines with an arena per sample (``set_point_rollout_scenes``), which any other batch refuses."""
+    of point_env engines with an arena per sample (``set_point_rollout_scenes``), which any other batch refuses.
+    ``point_priors=True`` (``M3_BATCH_SECTION_POINT_PRIORS``) makes room for the entries of point_env engines with prior samples
+    (``set_prior_samples`` / ``set_prior_controller``; with or without an arena per sample), which any other batch refuses."""
 
     _ptr, _destroy, _last_error = "_b", "m3_batch_destroy", "m3_batch_last_error"
 
-    def __init__(self, max_handles, device=0, panda_runtime=False, point_runtime=False):
+    def __init__(self, max_handles, device=0, panda_runtime=False, point_runtime=False, point_priors=False):
         if not torch.cuda.is_available():
             raise L.M3Error("HipBatch needs a HIP device (torch.cuda.is_available() is False); there is no CPU fallback")
         self.lib = L.load()
@@ -801,8 +851,9 @@ class HipBatch(_CObject):
         self._b = C.c_void_p()
         torch.cuda.set_device(self.device)
         torch.zeros(1, device=self.device)  # make sure the HIP context exists
-        if point_runtime:
-            sections = L.BATCH_SECTION_POINT_ROLLOUT_SCENES | (L.BATCH_SECTION_PANDA_RUNTIME if panda_runtime else 0)
+        if point_runtime or point_priors:
+            sections = ((L.BATCH_SECTION_POINT_ROLLOUT_SCENES if point_runtime else 0) | (L.BATCH_SECTION_PANDA_RUNTIME if panda_runtime else 0)
+                        | (L.BATCH_SECTION_POINT_PRIORS if point_priors else 0))
             self._ck(self.lib.m3_batch_create_sections(int(device), self.max_handles, sections, C.byref(self._b)))
         elif panda_runtime:
             self._ck(self.lib.m3_batch_create_ex(int(device), self.max_handles, L.BATCH_PANDA_RUNTIME, C.byref(self._b)))
@@ -853,11 +904,14 @@ class HipEpisodes(_CObject):
     device state and pinned status words; a tick allocates nothing.
     ``point_runtime=True`` (``M3_EPISODES_ROLLOUT_SCENES``, ``m3_episodes_create_ex``) also takes planners with an arena per
     sample (``set_point_rollout_scenes``), at create and at every tick; hand ``tick`` a ``HipBatch(..., point_runtime=True)``.
-    The world's rows step in the world engine's arena either way."""
+    The world's rows step in the world engine's arena either way.
+    ``point_priors=True`` (``M3_EPISODES_PRIORS``) also takes planners with prior samples (``set_prior_samples`` /
+    ``set_prior_controller``), at create and at every tick; hand ``tick`` a ``HipBatch(..., point_priors=True)``.  A planner's
+    controller reads its episode's row of the world every tick, on the device."""
 
     _ptr, _destroy, _last_error = "_eps", "m3_episodes_destroy", "m3_episodes_last_error"
 
-    def __init__(self, world, engines, specs, max_ticks, trace=False, point_runtime=False):
+    def __init__(self, world, engines, specs, max_ticks, trace=False, point_runtime=False, point_priors=False):
         self.lib = L.load()
         self.world, self.engines = world, list(engines)
         self.n, self.max_ticks, self.trace_on = len(self.engines), int(max_ticks), bool(trace)
@@ -868,9 +922,10 @@ class HipEpisodes(_CObject):
             sp[i].goal[0], sp[i].goal[1] = float(goal[0]), float(goal[1])
             sp[i].dyn_phase, sp[i].suction, sp[i].kp_suction = int(phase), int(suction), float(kp)
         self._eps = C.c_void_p()
-        if point_runtime:
-            self._ck(self.lib.m3_episodes_create_ex(world._h, arr, sp, self.n, self.max_ticks, int(self.trace_on),
-                                                    L.EPISODES_ROLLOUT_SCENES, C.byref(self._eps)))
+        if point_runtime or point_priors:
+            flags = (L.EPISODES_ROLLOUT_SCENES if point_runtime else 0) | (L.EPISODES_PRIORS if point_priors else 0)
+            self._ck(self.lib.m3_episodes_create_ex(world._h, arr, sp, self.n, self.max_ticks, int(self.trace_on), flags,
+                                                    C.byref(self._eps)))
         else:
             self._ck(self.lib.m3_episodes_create(world._h, arr, sp, self.n, self.max_ticks, int(self.trace_on), C.byref(self._eps)))
         self._status = (L.EpisodeStatus * self.n)()
@@ -881,7 +936,7 @@ class HipEpisodes(_CObject):
         self._ck(self.lib.m3_episodes_tick(self._eps, batch._b))
 
     def flags(self):
-        """The flags the set was created with (``L.EPISODES_ROLLOUT_SCENES`` or 0)."""
+        """The flags the set was created with (``L.EPISODES_ROLLOUT_SCENES`` / ``L.EPISODES_PRIORS`` bits)."""
         flags = self.lib.m3_episodes_flags(self._eps)
         if flags < 0:
             self._ck(flags)

@@ -71,6 +71,8 @@ class _PlannerSide:
         self.task_success = bool(self.task_planner.check_task_success(self.sim))
         if self.task_success:
             raise RuntimeError("run_point_episodes: the host's success test disagrees with the device's at tick 0")
+        if compat.prior_samples_on_device(self.cfg):     # (Tamp._set_prior_samples: set once, the device does the rest every tick)
+            compat.set_device_prior_controller(self.cfg, self.motion_planner)
         return self.motion_planner.command(self.sim._dof_state[0])
 
     def close(self):
@@ -114,14 +116,18 @@ class PointEpisodeSet:
     point_runtime: episodes may ask for an arena per sample of their planner (`rollout_arena_spread`): each planner's K-env sim is
     built with compat.rollout_point_scenes(cfg) as tools/closed_loop.Tamp builds it, so its tick-0 probe keeps the fused path and
     the engine holds the rows from then on (m3_episodes_create_ex with M3_EPISODES_ROLLOUT_SCENES, a batch with
-    M3_BATCH_SECTION_POINT_ROLLOUT_SCENES).  Episodes with and without the key share the set."""
+    M3_BATCH_SECTION_POINT_ROLLOUT_SCENES).  Episodes with and without the key share the set.
+    point_priors: episodes may ask for prior samples from a controller on the device (`prior_samples={..., device: true}`): the
+    planner gets its controller before its first command and reads its episode's row of the world every tick, on the device
+    (m3_episodes_create_ex with M3_EPISODES_PRIORS, a batch with M3_BATCH_SECTION_POINT_PRIORS).  Episodes with and without the
+    key share the set."""
 
-    def __init__(self, items, max_ticks, trace=False, point_runtime=False):
+    def __init__(self, items, max_ticks, trace=False, point_runtime=False, point_priors=False):
         import m3p2i_aip.utils.isaacgym_utils.isaacgym_wrapper as wrapper
         t0 = time.perf_counter()
         self.items, self.max_ticks, self.trace = list(items), int(max_ticks), bool(trace)
         cfgs = [cfg for _, _, cfg, _ in self.items]
-        self.point_runtime = bool(point_runtime)
+        self.point_runtime, self.point_priors = bool(point_runtime), bool(point_priors)
         if self.point_runtime:
             self.sides = [_PlannerSide(cfg, point_scenes=compat.rollout_point_scenes(cfg)) for cfg in cfgs]
         else:
@@ -150,7 +156,11 @@ class PointEpisodeSet:
         real._engine.use_torch_stream()
         engines = [s.motion_planner._engine for s in self.sides]
         dev = torch.device(c0.mppi.device).index or 0
-        if self.point_runtime:
+        if self.point_priors:
+            self.eps = HipEpisodes(real._engine, engines, specs, self.max_ticks, trace=self.trace, point_runtime=self.point_runtime,
+                                   point_priors=True)
+            self.batch = HipBatch(n, device=dev, point_runtime=self.point_runtime, point_priors=True)
+        elif self.point_runtime:
             self.eps = HipEpisodes(real._engine, engines, specs, self.max_ticks, trace=self.trace, point_runtime=True)
             self.batch = HipBatch(n, device=dev, point_runtime=True)
         else:
@@ -225,8 +235,21 @@ class PointEpisodeSet:
             side.close()
 
 
-def build_set(episodes, max_ticks=800, trace=False, point_runtime=False):
-    """A PointEpisodeSet of episodes [(config name, overrides, jitter)] that share one world (point_runtime: as
+def _check_episode_priors(cfg, idx, point_priors):
+    """the `prior_samples` key of an episode of a lockstep set: only a controller on the device can serve it (the episodes'
+    worlds live on the device and a tick is one library call for all of them), and only in a set built for priors"""
+    if not getattr(cfg, "prior_samples", None):
+        return
+    if not compat.prior_samples_on_device(cfg):
+        raise ValueError(f"run_point_episodes: episode {idx} asks for prior samples from a host controller (prior_samples without "
+                         "device: true), which a lockstep set cannot serve; use `device: true` or closed_loop.run")
+    if not point_priors:
+        raise ValueError(f"run_point_episodes: episode {idx} asks for prior samples (prior_samples), which the batched command "
+                         "runs only on request (point_priors=True); or use closed_loop.run")
+
+
+def build_set(episodes, max_ticks=800, trace=False, point_runtime=False, point_priors=False):
+    """A PointEpisodeSet of episodes [(config name, overrides, jitter)] that share one world (point_runtime, point_priors: as
     run_point_episodes)."""
     compat.install(force_standins=True)
     items = []
@@ -237,18 +260,21 @@ def build_set(episodes, max_ticks=800, trace=False, point_runtime=False):
         if not point_runtime and getattr(cfg, "rollout_arena_spread", None):
             raise ValueError(f"run_point_episodes: episode {idx} asks for an arena per sample (rollout_arena_spread), which the "
                              "batched command does not run (m3_set_point_rollout_scenes: m3_command only); use closed_loop.run")
+        _check_episode_priors(cfg, idx, point_priors)
         items.append((cn, list(ov), cfg, jitter))
-    return PointEpisodeSet(items, max_ticks, trace, point_runtime=point_runtime)
+    return PointEpisodeSet(items, max_ticks, trace, point_runtime=point_runtime, point_priors=point_priors)
 
 
-def run_point_episodes(episodes, max_ticks=800, trace=False, point_runtime=False):
+def run_point_episodes(episodes, max_ticks=800, trace=False, point_runtime=False, point_priors=False):
     """episodes: [(config name, overrides, jitter)] as closed_loop.run takes them (jitter may be None).  Returns one report
     per episode, in order: the dict closed_loop.run returns (ticks, success, sim_time_s, timeline, final_pos_error,
     dyn_obs_collision_ticks, trace if asked), with the set's tick_ms_p50 / tick_ms_p99 in place of the per-episode
     command_ms_*, and build_s (planner and world construction) / loop_s (ticks 1..) of the set.  Episodes whose worlds
     differ (dt, substeps, device) run as separate sets, one after the other.
     point_runtime=True: episodes may carry `rollout_arena_spread` (an arena per sample of the planner's rollout); without it
-    they raise ValueError as before."""
+    they raise ValueError as before.
+    point_priors=True: episodes may carry `prior_samples={..., device: true}` (prior samples from a controller on the device);
+    without it, and for a host controller (no `device: true`) always, they raise ValueError."""
     if int(max_ticks) <= 0:
         raise ValueError("run_point_episodes: max_ticks must be > 0")
     compat.install(force_standins=True)
@@ -260,11 +286,12 @@ def run_point_episodes(episodes, max_ticks=800, trace=False, point_runtime=False
         if not point_runtime and getattr(cfg, "rollout_arena_spread", None):
             raise ValueError(f"run_point_episodes: episode {idx} asks for an arena per sample (rollout_arena_spread), which the "
                              "batched command does not run (m3_set_point_rollout_scenes: m3_command only); use closed_loop.run")
+        _check_episode_priors(cfg, idx, point_priors)
         key = (float(cfg.isaacgym.dt), int(cfg.isaacgym.substeps), cfg.mppi.device)
         groups.setdefault(key, []).append((idx, (cn, list(ov), cfg, jitter)))
     out = [None] * len(episodes)
     for members in groups.values():
-        es = PointEpisodeSet([m for _, m in members], int(max_ticks), bool(trace), point_runtime=point_runtime)
+        es = PointEpisodeSet([m for _, m in members], int(max_ticks), bool(trace), point_runtime=point_runtime, point_priors=point_priors)
         try:
             es.run()
             reps = es.reports()

@@ -656,6 +656,33 @@ class MPPI():
         vals = torch.as_tensor(seqs, dtype=torch.float32).to(self.device).clone()
         self._priors = (torch.tensor(idx, dtype=torch.long, device=self.device), vals)
 
+    def set_prior_controller(self, kind, n=4, indices=None, speeds=None, standoff=None, reach=None):
+        """Extension, unsharded point_env planners: an ancillary controller ON THE DEVICE (m3_set_prior_controller) -- the
+        priors of samples indices[j] are the sequences of "go_to" / "push_behind" (priors.py, restated in binary32:
+        csrc/prior_controllers.hpp), computed by a kernel ahead of every rollout from the world that rollout starts from: set
+        once, nothing to do per tick.  n sequences, one per speed factor (default 1 - j / n).  The rules of set_prior_samples
+        hold: indices default to 0 .. n-1 for a single-mode planner, a multi-modal planner must pass them.  kind=None clears
+        controller and priors; against set_prior_samples the last call wins."""
+        if self.env_type != "point_env":
+            raise ValueError("set_prior_controller: point_env only")
+        if self.world_size != 1:
+            raise ValueError("set_prior_controller: unsharded planners only")
+        if kind is None:
+            self._engine.set_prior_controller(None)
+            self._priors = None
+            return
+        if kind not in L.PRIOR_CONTROLLER_KINDS:
+            raise ValueError(f"set_prior_controller: kind is one of {list(L.PRIOR_CONTROLLER_KINDS)}")
+        n = int(n)
+        if indices is None:
+            if self.multi_modal:
+                raise ValueError("set_prior_controller: a multi-modal planner needs indices (a prior informs the mode whose half "
+                                 "of the samples it sits in)")
+            indices = range(n)
+        idx = [int(i) for i in indices]
+        self._engine.set_prior_controller(kind, n, idx, speeds, standoff, reach)   # (every refusal of the library first)
+        self._priors = (torch.tensor(idx, dtype=torch.long, device=self.device), None)   # (None: the rows are the device's)
+
     @property
     def has_prior_samples(self):
         return getattr(self, "_priors", None) is not None
@@ -666,6 +693,11 @@ class MPPI():
         if pri is None:
             return act
         idx, vals = pri
+        if vals is None:    # a device controller: the rows it writes for the attached world and objective, as the fused path's
+            self._push_objective()
+            self._bind_world()
+            self._engine.prior_controller_fill()
+            vals = self._engine.prior_table()
         act[idx - self.k_offset] = torch.max(torch.min(vals, self.u_max), self.u_min)
         return act
 
@@ -768,9 +800,10 @@ class MPPI():
 _BATCHES = {}   # device index -> the HipBatch command_batch uses (grown when a call lists more planners)
 _BATCHES_PANDA_RUNTIME = {}   # ... with panda_runtime=True: a second batch per device, the default one is not re-created
 _BATCHES_POINT_RUNTIME = {}   # ... with point_runtime=True (with or without panda_runtime), keyed (device index, panda_runtime)
+_BATCHES_POINT_PRIORS = {}    # ... with point_priors=True, keyed (device index, panda_runtime, point_runtime)
 
 
-def command_batch(planners, states, panda_runtime=False, point_runtime=False):
+def command_batch(planners, states, panda_runtime=False, point_runtime=False, point_priors=False):
     """``[p.command(s) for p, s in zip(planners, states)]`` with one batched library call (m3_batch_command) per
     environment in the list: the planners' rollouts and updates run in one launch per group of planners that use the
     same kernel instance (point_env and panda_env planners alike; a list that mixes them makes one call for each).  Each
@@ -784,7 +817,10 @@ def command_batch(planners, states, panda_runtime=False, point_runtime=False):
     raise ValueError as before.
     ``point_runtime=True``: point_env planners with an arena per sample (set_rollout_scenes / a wrapper with point_scenes) are
     batched too (a batch created with M3_BATCH_SECTION_POINT_ROLLOUT_SCENES, a cached batch of its own per device); without
-    it they raise ValueError as before."""
+    it they raise ValueError as before.
+    ``point_priors=True``: point_env planners with prior samples (set_prior_samples / set_prior_controller; with or without an
+    arena per sample) are batched too (a batch created with M3_BATCH_SECTION_POINT_PRIORS, a cached batch of its own per
+    device); without it they raise ValueError as before."""
     planners, states = list(planners), list(states)
     if len(planners) != len(states):
         raise ValueError("command_batch: one state per planner")
@@ -793,10 +829,10 @@ def command_batch(planners, states, panda_runtime=False, point_runtime=False):
             raise ValueError(f"command_batch: planner {i} runs in step mode (user dynamics / running_cost callables)")
         if p.world_size > 1 or p.collective is not None:
             raise ValueError(f"command_batch: planner {i} is sharded or has collectives installed")
-        if getattr(p, "has_prior_samples", False):
+        if not point_priors and getattr(p, "has_prior_samples", False):
             raise ValueError(f"command_batch: planner {i} has prior samples (set_prior_samples), which only its own command() "
                              "runs (m3_set_prior_samples)")
-        if not point_runtime and p.has_rollout_scenes:
+        if not point_runtime and p.has_rollout_scenes and not (point_priors and getattr(p, "has_prior_samples", False)):
             raise ValueError(f"command_batch: planner {i} has an arena per sample (set_rollout_scenes / a wrapper with "
                              "point_scenes): m3_batch_command does not run those, use planner.command")
         if not panda_runtime and getattr(p, "has_panda_rollout_scenes", False):
@@ -830,13 +866,17 @@ def command_batch(planners, states, panda_runtime=False, point_runtime=False):
         batched.append(p._engine)
     if batched:
         dev = batched[0].device.index or 0
-        cache = _BATCHES_POINT_RUNTIME if point_runtime else _BATCHES_PANDA_RUNTIME if panda_runtime else _BATCHES
-        key = (dev, bool(panda_runtime)) if point_runtime else dev
+        cache = (_BATCHES_POINT_PRIORS if point_priors else _BATCHES_POINT_RUNTIME if point_runtime
+                 else _BATCHES_PANDA_RUNTIME if panda_runtime else _BATCHES)
+        key = ((dev, bool(panda_runtime), bool(point_runtime)) if point_priors else (dev, bool(panda_runtime)) if point_runtime else dev)
         b = cache.get(key)
         if b is None or b.max_handles < len(batched):
             if b is not None:
                 b.close()
-            if point_runtime:
+            if point_priors:
+                b = HipBatch(max(64, len(batched)), device=dev, panda_runtime=bool(panda_runtime), point_runtime=bool(point_runtime),
+                             point_priors=True)
+            elif point_runtime:
                 b = HipBatch(max(64, len(batched)), device=dev, panda_runtime=bool(panda_runtime), point_runtime=True)
             elif panda_runtime:
                 b = HipBatch(max(64, len(batched)), device=dev, panda_runtime=True)

@@ -3,7 +3,7 @@
 block-to-goal error, task time, dyn-obs collisions -- next to the logged statistics (tests/golden/behaviour_band.json).
 
     python tools/band_stats.py [--n 20] [--json out.json] [--size baseline|default] [--avoid] [--batched]
-                               [--world-arena-spread S] [--runtime] [key=value ...] [scenario ...]
+                               [--world-arena-spread S] [--runtime] [--priors] [key=value ...] [scenario ...]
 
 --batched: all episodes of all named scenarios in lockstep, one library call per tick (m3p2i_aip_amd/episodes.py,
 DESIGN.md §7c): the same per-episode results as the serial runs, bit for bit.  The `panda` rows likewise, the n episodes
@@ -14,6 +14,10 @@ panda_runtime=True)), which takes `panda_scene=...`, `world_panda_scene=...`, `p
 `rollout_workspace_spread=...` given as key=value arguments -- e.g. --batched --runtime 'world_panda_scene={cube_m: 0.2}'
 'rollout_workspace_spread={spread: 0.3, seed: 1}' panda: does a planner that plans over a spread of models succeed more often
 in a world whose cube is heavier than its model's?  The serial `panda` rows take the same keys.
+
+--priors (with --batched): the lockstep set created for planners with prior samples (run_point_episodes(..., point_priors=True)),
+which takes 'prior_samples={controller: push_behind, n: 4, device: true}' given as a key=value argument: every planner hears that
+controller, computed on the device from its episode's row of the world every tick.
 
 --world-arena-spread S (with --batched): a randomised band -- each episode's REAL world gets its own box mass, box ground
 friction and robot-box friction, the nominal value times a factor drawn from [1 - S, 1 + S] (world_arena_of; the config key
@@ -164,14 +168,15 @@ def _summary(scenario, n, size, runs):
                 command_ms_p50=stats([r["command_ms_p50"] for r in runs]), runs=runs)
 
 
-def band_batched(pairs, n=20, max_sim_time_s=40.0, world_arena_spread=0.0, extra=(), runtime=False):
+def band_batched(pairs, n=20, max_sim_time_s=40.0, world_arena_spread=0.0, extra=(), runtime=False, priors=False):
     """episodes() of every (scenario, size) in `pairs` at once: all n * len(pairs) episodes in lockstep
     (m3p2i_aip_amd.episodes.run_point_episodes).  Returns {(scenario, size): the dict episodes() returns}; each run's
     command_ms_p50 is the set's tick time.  runtime: the set created for planners with an arena per sample (point_runtime=True),
-    which takes `rollout_arena_spread` among the `extra` overrides of every episode."""
+    which takes `rollout_arena_spread` among the `extra` overrides of every episode.  priors: the set created for planners with
+    prior samples (point_priors=True), which takes `prior_samples={controller: ..., n: 4, device: true}` among them."""
     from m3p2i_aip_amd.episodes import run_point_episodes
     items, eps = batched_episode_list(pairs, n, world_arena_spread, extra)
-    reps = run_point_episodes(eps, max_ticks=int(max_sim_time_s / 0.05), point_runtime=bool(runtime))
+    reps = run_point_episodes(eps, max_ticks=int(max_sim_time_s / 0.05), point_runtime=bool(runtime), point_priors=bool(priors))
     out = {}
     for (sc, size, e, j), r in zip(items, reps):
         out.setdefault((sc, size), []).append(dict(episode=e, jitter=j, success=r["success"], final_pos_error_m=r["final_pos_error"],
@@ -192,6 +197,9 @@ PANDA_RUNTIME_KEYS = ("panda_scene", "world_panda_scene", "panda_cost_weights", 
 # config keys the point scenarios take as overrides on the command line ('rollout_arena_spread={spread: 0.3, seed: 1}': an arena
 # per sample of every planner); with --batched --runtime only (the lockstep set created for such planners)
 POINT_RUNTIME_KEYS = ("rollout_arena_spread",)
+# 'prior_samples={controller: push_behind, n: 4, device: true}': prior samples from a controller on the device for every planner;
+# with --batched --priors only (the lockstep set created for such planners)
+POINT_PRIORS_KEYS = ("prior_samples",)
 
 
 def panda_episodes(n=20, overrides=("mppi.num_samples=4000", "mppi.horizon=20"), ticks=600):
@@ -232,12 +240,17 @@ def panda_episodes_batched(n=20, overrides=("mppi.num_samples=4000", "mppi.horiz
 
 def main(argv):
     n, out, names, size, batched, spread, runtime, extra, point_extra = 20, None, [], "baseline", False, 0.0, False, [], []
+    priors, prior_extra = False, []
     it = iter(argv)
     for a in it:
         if a == "--batched":
             batched = True
         elif a == "--runtime":
             runtime = True
+        elif a == "--priors":
+            priors = True
+        elif a.split("=", 1)[0] in POINT_PRIORS_KEYS and "=" in a:
+            prior_extra.append(a)
         elif a.split("=", 1)[0] in PANDA_RUNTIME_KEYS and "=" in a:
             extra.append(a)
         elif a.split("=", 1)[0] in POINT_RUNTIME_KEYS and "=" in a:
@@ -261,6 +274,8 @@ def main(argv):
         raise SystemExit("--runtime: with --batched (the run-time sets of the lockstep episodes)")
     if point_extra and not (batched and runtime):
         raise SystemExit(f"{point_extra[0].split('=', 1)[0]}: with --batched --runtime only (the serial runs: tools/rollout_scenes_bench.py)")
+    if (priors or prior_extra) and not (batched and priors):
+        raise SystemExit("--priors / prior_samples=...: with --batched --priors only (the serial runs: tools/prior_samples_bench.py)")
     if extra and batched and not runtime:
         raise SystemExit(f"{extra[0].split('=', 1)[0]}: with --batched, the run-time set only (--runtime)")
     allband = json.load(open(os.path.join(ROOT, "tests", "golden", "behaviour_band.json")))
@@ -284,8 +299,8 @@ def main(argv):
             if out:
                 json.dump(res, open(out, "w"), indent=1)
             return
-    pre = band_batched([(sc, size) for sc in names or list(SCENARIOS)], n, world_arena_spread=spread, extra=point_extra,
-                       runtime=runtime) if batched else {}
+    pre = band_batched([(sc, size) for sc in names or list(SCENARIOS)], n, world_arena_spread=spread, extra=point_extra + prior_extra,
+                       runtime=runtime, priors=priors) if batched else {}
     for sc in names or list(SCENARIOS):
         r = pre[(sc, size)] if batched else episodes(sc, n, size=size)
         r["logged"] = {k: band[sc][k] for k in ("final_pos_error_m", "task_time_s", "dyn_obs_collisions")}

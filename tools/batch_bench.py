@@ -24,6 +24,12 @@ planner: kb_rollout_point_sv*), batched against n back-to-back m3_command calls 
 single-arena run-time-scene group of the same n, K, T: the run-time-scene instance forced on at the default arena) and the
 control `per_sample_same_work` (K rows of the default arena: the `scene` handles' work bit for bit, plus the 38 row loads per
 lane).
+
+The `*_pr` configurations (point_env, a batch created with M3_BATCH_SECTION_POINT_PRIORS and _POINT_ROLLOUT_SCENES; not part of
+the default list either; n = 1, 4, 16, 64) measure n planners with prior samples: `priors` (a push_behind controller on the
+device, four sequences per planner: kb_prior_controllers + kb_rollout_point_pr*), batched against n back-to-back m3_command calls
+of the same handles -- the only path such handles had --, beside `per_sample_same_work` (K rows of the default arena, no priors:
+the kernels the prior build twins) of the same run.
 """
 import argparse
 import ctypes as C
@@ -59,6 +65,9 @@ RT_WEIGHTS = dict(reach_dist=20.0, reach_tilt=5.0, pick_goal=7.5, pick_ori=25.0,
 RT_SPREAD = 0.3
 # point_env planners with an arena per sample: name -> the CONFIGS entry whose worlds it takes
 POINT_SV_CONFIGS = {"c2_push_sv": "c2_push", "shipped_push_sv": "shipped_push"}
+# point_env planners with prior samples from a controller on the device: name -> the CONFIGS entry whose worlds it takes
+POINT_PR_CONFIGS = {"c2_push_pr": "c2_push", "shipped_push_pr": "shipped_push"}
+POINT_PR_NS = (1, 4, 16, 64)
 
 
 def panda_world_of(task_phase, K, T, episode, device):
@@ -108,6 +117,9 @@ def measure(name, iters, warmup, repeats):
     elif name in POINT_SV_CONFIGS:
         kinds = ("scene", "per_sample", "per_sample_same_work")
         name_worlds = POINT_SV_CONFIGS[name]
+    elif name in POINT_PR_CONFIGS:
+        kinds = ("per_sample_same_work", "priors")
+        name_worlds = POINT_PR_CONFIGS[name]
     else:
         name_worlds = name
     if name_worlds in PANDA_CONFIGS:
@@ -138,6 +150,8 @@ def measure(name, iters, warmup, repeats):
         engs = by_kind["literal"]
     else:
         scenario, task, goal, K, T, mm, ns = CONFIGS[name_worlds]
+        if name in POINT_PR_CONFIGS:
+            ns = POINT_PR_NS
         pk = dict(u_min=[-3, -3], u_max=[3, 3], noise_sigma_diag=[3, 3], lambda_=0.5)
         n_max = max(ns)
         knots = sampling.halton_knots(K, T, 2, 4, 2, 0, K, scramble="none")
@@ -156,10 +170,14 @@ def measure(name, iters, warmup, repeats):
                     e.set_point_rollout_scenes(spread_point_scenes(K, RT_SPREAD, seed=1 + e_i, nominal_rows=(0, K // 2, K - 1)))
                 elif kind == "per_sample_same_work":
                     e.set_point_rollout_scenes([None] * K)
+                elif kind == "priors":
+                    e.set_prior_controller("push_behind", 4)
                 by_kind.setdefault(kind, []).append(e)
         engs = by_kind[kinds[0] if kinds else None]
     lib = engs[0].lib
-    if name in POINT_SV_CONFIGS:
+    if name in POINT_PR_CONFIGS:
+        batch = HipBatch(n_max, point_runtime=True, point_priors=True)
+    elif name in POINT_SV_CONFIGS:
         batch = HipBatch(n_max, point_runtime=True)
     else:
         batch = HipBatch(n_max, panda_runtime=True) if kinds else HipBatch(n_max)

@@ -82,6 +82,13 @@ class Tamp:
         from m3p2i_aip_amd import priors
         name, n = compat.check_prior_samples(cfg)
         m = cfg.mppi
+        if compat.prior_samples_on_device(cfg):
+            # `device: true`: the same controller as a kernel ahead of every rollout (MPPI.set_prior_controller), which reads
+            # this tick's robot, box and goal on the device -- set once, nothing per tick
+            if not getattr(self, "_prior_controller_set", False):
+                compat.set_device_prior_controller(cfg, self.motion_planner)
+                self._prior_controller_set = True
+            return
         speeds = [1.0 - j / n for j in range(n)]
         robot = self.sim.robot_pos[0].cpu().numpy()
         goal = torch.as_tensor(self.task_planner.curr_goal).cpu().numpy().reshape(-1)[:2]

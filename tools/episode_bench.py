@@ -97,18 +97,19 @@ def arena_rows_times(n=64, repeats=5, ticks=8):
             es.close()
 
 
-def rollout_arenas_times(n=64, repeats=5, ticks=8, spread=0.3):
+def _two_sets_times(plans, base, n, repeats, ticks, spread, check):
+    """two lockstep sets of n episodes of one scenario, `plans`: name -> (extra overrides of episode e, build_set's switches),
+    interleaved inside every repeat; the second set's tick p50 over the first's is `ratio_to_<first>`"""
     import band_stats as bs
     from m3p2i_aip_amd.episodes import build_set
     sc = "case2_halton_push_coll"
-    plans = dict(nominal=lambda e: [], rollout_arenas=lambda e: ["rollout_arena_spread={spread: %r, seed: %d}" % (spread, 1 + e)])
     sets = {}
     try:
-        for name, extra in plans.items():
+        for name, (extra, kw) in plans.items():
             eps = [("config_point", bs.overrides(sc, "baseline") + extra(e), bs.jitter_of(sc, e % 60)) for e in range(n)]
-            es = sets[name] = build_set(eps, max_ticks=repeats * ticks + 4, point_runtime=True)
+            es = sets[name] = build_set(eps, max_ticks=repeats * ticks + 4, **kw)
             es.start()
-            assert all(s.motion_planner._engine.point_rollout_scenes_set() == (name == "rollout_arenas") for s in es.sides)
+            assert all(check(s.motion_planner._engine) == (name != base) for s in es.sides)
             for _ in range(3):           # warm-up ticks, not counted
                 es.tick()
             es.lat.clear()
@@ -124,11 +125,28 @@ def rollout_arenas_times(n=64, repeats=5, ticks=8, spread=0.3):
             out["tick_ms_p50"][name] = float(np.percentile(lat, 50))
             out["tick_ms_min"][name] = float(lat.min())
             out["ticks"][name] = len(lat)
-        out["ratio_to_nominal"] = out["tick_ms_p50"]["rollout_arenas"] / out["tick_ms_p50"]["nominal"]
+        other = [k for k in plans if k != base][0]
+        out["ratio_to_" + base] = out["tick_ms_p50"][other] / out["tick_ms_p50"][base]
         return out
     finally:
         for es in sets.values():
             es.close()
+
+
+def rollout_arenas_times(n=64, repeats=5, ticks=8, spread=0.3):
+    arenas = lambda e: ["rollout_arena_spread={spread: %r, seed: %d}" % (spread, 1 + e)]
+    return _two_sets_times(dict(nominal=(lambda e: [], dict(point_runtime=True)), rollout_arenas=(arenas, dict(point_runtime=True))),
+                           "nominal", n, repeats, ticks, spread, lambda eng: eng.point_rollout_scenes_set())
+
+
+def priors_times(n=64, repeats=5, ticks=8, spread=0.3):
+    """The lockstep tick with controller planners (`prior_samples={controller: push_behind, n: 4, device: true}`: one
+    kb_prior_controllers launch and one kb_rollout_point_pr* group per tick) beside the `rollout arenas` set (an arena per sample of
+    every planner: the kernels the prior build twins)."""
+    arenas = lambda e: ["rollout_arena_spread={spread: %r, seed: %d}" % (spread, 1 + e)]
+    priors = lambda e: ["prior_samples={controller: push_behind, n: 4, device: true}"]
+    return _two_sets_times(dict(rollout_arenas=(arenas, dict(point_runtime=True)), priors=(priors, dict(point_priors=True))),
+                           "rollout_arenas", n, repeats, ticks, spread, lambda eng: eng.prior_controller() is not None)
 
 
 def serial_band(size, n):
@@ -172,16 +190,17 @@ def main(argv):
             os.makedirs(os.path.dirname(opt["--json"]) or ".", exist_ok=True)
             json.dump(res, open(opt["--json"], "w"), indent=1)
         return
-    if "--rollout-arenas" in argv:
-        from m3p2i_aip_amd import _lib as L
-        opt = dict(zip(argv, argv[1:]))
-        res = dict(build_id=L.load().m3_build_id().decode(),
-                   rollout_arenas=rollout_arenas_times(int(opt.get("--rows", 64)), int(opt.get("--repeats", 5)), int(opt.get("--ticks", 8))))
-        print(json.dumps(res), flush=True)
-        if opt.get("--json"):
-            os.makedirs(os.path.dirname(opt["--json"]) or ".", exist_ok=True)
-            json.dump(res, open(opt["--json"], "w"), indent=1)
-        return
+    for switch, key, fn in (("--rollout-arenas", "rollout_arenas", rollout_arenas_times), ("--priors", "priors", priors_times)):
+        if switch in argv:
+            from m3p2i_aip_amd import _lib as L
+            opt = dict(zip(argv, argv[1:]))
+            res = {"build_id": L.load().m3_build_id().decode(),
+                   key: fn(int(opt.get("--rows", 64)), int(opt.get("--repeats", 5)), int(opt.get("--ticks", 8)))}
+            print(json.dumps(res), flush=True)
+            if opt.get("--json"):
+                os.makedirs(os.path.dirname(opt["--json"]) or ".", exist_ok=True)
+                json.dump(res, open(opt["--json"], "w"), indent=1)
+            return
     it = iter(argv)
     for a in it:
         if a == "--json":

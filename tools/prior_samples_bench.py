@@ -4,9 +4,13 @@ Part 1, the cost: push, K = 2000, T = 30, ms per command on ONE handle, the arms
   (a) the untouched handle, (b) the same handle with m3_set_point_scene_instance(h, 1) -- the build the prior kernels twin --,
   (c) n = 1, 8, 64 and 256 priors.  Bar: (c) at most 5 % above (b).
 Part 2, the benefit: closed loop (tools/closed_loop.run) at the reference's shipped size (K = 200, T = 15) and at K = 32, push and
-  navigation, jittered episodes with and without `prior_samples={controller: ..., n: 4}`: success count, task time, final error.
+  navigation, jittered episodes in three arms interleaved on the same seeds -- no priors, `prior_samples={controller: ..., n: 4}`
+  (the numpy controller, uploaded every tick) and the same key with `device: true` (the controller kernel, set once): success count,
+  task time, final error, the host's ms per command.  Condition: the device arm's host ms per command below the host arm's.
 
-    python tools/prior_samples_bench.py [--part 1|2|all] [--rounds 7] [--commands 200] [--episodes 20] [--ticks 400]
+Part 3 (not part of `all`): the rows of part 2 at N = 60 per row in lockstep, no priors against the device controller.
+
+    python tools/prior_samples_bench.py [--part 1|2|3|all] [--rounds 7] [--commands 200] [--episodes 20] [--ticks 400]
                                         [--out profiles/prior_samples_bench.json]
 """
 import json
@@ -85,25 +89,63 @@ def _build_id():
         return None
 
 
-def benefit(episodes, ticks):
-    import closed_loop
+def _jitters(n):
+    """the n jittered starts every row runs on (seeded: the first draws are the same for every n)"""
     rng = np.random.default_rng(0)
-    jit = [dict(dyn_phase=int(rng.integers(0, 100)), box=tuple(rng.uniform(-0.05, 0.05, 2).tolist()),
-                robot=tuple(rng.uniform(-0.05, 0.05, 2).tolist())) for _ in range(episodes)]
+    return [dict(dyn_phase=int(rng.integers(0, 100)), box=tuple(rng.uniform(-0.05, 0.05, 2).tolist()),
+                 robot=tuple(rng.uniform(-0.05, 0.05, 2).tolist())) for _ in range(n)]
+
+
+ARMS = ("none", "host", "device")   # no priors | the numpy controller, uploaded every tick | the controller kernel (device: true)
+
+
+def benefit(episodes, ticks):
+    """Per row (K, task) the three arms INTERLEAVED episode by episode, on the same jitter seeds."""
+    import closed_loop
+    jit = _jitters(episodes)
     rows = []
     for K, T in ((200, 15), (32, 15)):
         for task, controller in (("push", "push_behind"), ("navigation", "go_to")):
-            for with_priors in (False, True):
-                ov = [f"task={task}", f"mppi.num_samples={K}", f"mppi.horizon={T}", f"mppi.u_per_command={T}"]
-                if with_priors:
-                    ov.append("prior_samples={controller: %s, n: 4}" % controller)
-                res = [closed_loop.run("config_point", ov, ticks=ticks, jitter=j) for j in jit]
-                ok = [r for r in res if r["success"]]
-                rows.append(dict(K=K, T=T, task=task, priors=controller if with_priors else None, episodes=episodes,
+            base = [f"task={task}", f"mppi.num_samples={K}", f"mppi.horizon={T}", f"mppi.u_per_command={T}"]
+            key = {"none": [], "host": ["prior_samples={controller: %s, n: 4}" % controller],
+                   "device": ["prior_samples={controller: %s, n: 4, device: true}" % controller]}
+            res = {arm: [] for arm in ARMS}
+            for j in jit:
+                for arm in ARMS:
+                    res[arm].append(closed_loop.run("config_point", base + key[arm], ticks=ticks, jitter=j))
+            for arm in ARMS:
+                ok = [r for r in res[arm] if r["success"]]
+                rows.append(dict(K=K, T=T, task=task, priors=None if arm == "none" else controller, arm=arm, episodes=episodes,
                                  successes=len(ok), max_ticks=ticks,
                                  task_time_s_median=float(np.median([r["sim_time_s"] for r in ok])) if ok else None,
-                                 final_pos_error_median=float(np.median([r["final_pos_error"] for r in res])),
-                                 command_ms_p50_median=float(np.median([r["command_ms_p50"] for r in res]))))
+                                 final_pos_error_median=float(np.median([r["final_pos_error"] for r in res[arm]])),
+                                 command_ms_p50_median=float(np.median([r["command_ms_p50"] for r in res[arm]]))))
+                print(json.dumps(rows[-1]), flush=True)
+            h, d, n0 = (rows[-3 + ARMS.index(a)]["command_ms_p50_median"] for a in ("host", "device", "none"))
+            rows.append(dict(K=K, T=T, task=task, condition="device arm's host ms per command below the host-controller arm's",
+                             met=bool(d < h), device_ms=d, host_ms=h, none_ms=n0, device_minus_none_ms=d - n0))
+            print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
+def lockstep_rows(n=60, ticks=400):
+    """Part 3: the rows of part 2 with N = n episodes per row in LOCKSTEP (m3p2i_aip_amd.episodes.run_point_episodes with
+    point_priors=True), no priors against the device controller, on the first n draws of part 2's jitter seed."""
+    from m3p2i_aip_amd.episodes import run_point_episodes
+    jit = _jitters(n)
+    rows = []
+    for K, T in ((200, 15), (32, 15)):
+        for task, controller in (("push", "push_behind"), ("navigation", "go_to")):
+            base = [f"task={task}", f"mppi.num_samples={K}", f"mppi.horizon={T}", f"mppi.u_per_command={T}"]
+            for arm, extra in (("none", []), ("device", ["prior_samples={controller: %s, n: 4, device: true}" % controller])):
+                reps = run_point_episodes([("config_point", base + extra, j) for j in jit], max_ticks=ticks, point_priors=True)
+                ok = [r for r in reps if r["success"]]
+                rows.append(dict(K=K, T=T, task=task, arm=arm, controller=controller if extra else None, episodes=n, successes=len(ok),
+                                 max_ticks=ticks, jitter_seed="default_rng(0), the first %d draws" % n,
+                                 task_time_s_median=float(np.median([r["sim_time_s"] for r in ok])) if ok else None,
+                                 task_time_s_mean=float(np.mean([r["sim_time_s"] for r in ok])) if ok else None,
+                                 final_pos_error_median=float(np.median([r["final_pos_error"] for r in reps])),
+                                 tick_ms_p50=reps[0]["tick_ms_p50"]))
                 print(json.dumps(rows[-1]), flush=True)
     return rows
 
@@ -121,6 +163,10 @@ def main(argv):
         print(json.dumps(res["cost"], indent=1), flush=True)
     if opt["part"] in ("2", "all"):
         res["benefit"] = benefit(opt["episodes"], opt["ticks"])
+        res["benefit_build_id"], res["benefit_device"] = _build_id(), torch.cuda.get_device_name(0)
+    if opt["part"] == "3":
+        res["lockstep_rows"] = lockstep_rows(60, opt["ticks"])
+        res["lockstep_rows_build_id"] = _build_id()
     os.makedirs(os.path.dirname(opt["out"]), exist_ok=True)
     json.dump(res, open(opt["out"], "w"), indent=1)
     print("wrote", opt["out"])
