@@ -625,6 +625,35 @@ int m3_prior_samples_set(const m3_handle* h);   /* n (0: none) */
  * != NULL after m3_set_prior_samples_device); M3_ERR_BAD_ARG for j outside 0 .. n - 1 */
 int m3_get_prior_sample(const m3_handle* h, int j, int* sample_idx, float* seq);
 int m3_prior_samples_used(m3_handle* h);        /* 0 / 1: the last rollout launched the prior build; -1 before the first */
+/* EXTENSION, panda_env PLANNER handles, unsharded: PRIOR SAMPLES of the arm -- the same mechanism with nu = 9 (seqs: [n][T][9]),
+ * through entry points of its own (the five above keep refusing a panda_env handle: "point_env only").  Sample sample_idx[j]
+ * of the next rollouts assembles its control of step t as a = clamp(seqs[j][t][c], u_min[c], u_max[c]) in place of
+ * clamp(mean[shift(t)] + noise) -- where the multi-modal planner's best-trajectory select sits, in simple mode behind that
+ * branch's clamp -- and everything behind the select is what it is for every sample: the GRIPPER COMMAND's override of controls
+ * 7 and 8 (gripper_cmd 1 / 2: +-1.5 -- the task's, so a prior cannot move the fingers while a gripper command is set; with
+ * gripper_cmd 0 its columns 7 and 8 are taken), u_scale, what is stored in M3_BUF_ACTIONS, simple mode's e - m perturbation
+ * cost, the update.  Both mppi modes, both samplers, single mode and multi-modal (k < K/2 informs mode 1, k >= K/2 mode 2).
+ * Nothing is shifted between commands; the priors stay until replaced or cleared (seqs == NULL or n == 0: the handle then
+ * launches exactly the kernels it launched before).  The prior follows the SAMPLE: m3_set_rollout_lanes,
+ * m3_set_panda_lanes_per_sample, the shadow slots of the reach command (which re-simulate samples 0 and K/2 and take those
+ * samples' priors) and the ragged last wavefront do not move it.  Survives m3_reset.
+ * Refused as above, the message names the entry: M3_ERR_BAD_ARG for n outside 0 .. M3_MAX_PRIOR_SAMPLES, a null sample_idx, an
+ * index out of range, index K_global - 1, in multi-modal mode index 0 or K/2, an index listed twice, a non-finite value (host
+ * variant); M3_ERR_UNSUPPORTED for a point_env handle ("panda_env only") and for a sharded handle; M3_ERR_STATE for a sim_only
+ * handle.
+ * Which kernels run: k_rollout_panda_pr (rollout_panda_priors.hip), one family for a handle with priors -- the workspace and
+ * the cost weights kernel arguments, with or without m3_set_panda_rollout_scenes; m3_panda_scene_instance_used reports 1,
+ * m3_panda_weighted_cost_instance_used follows the weights.  m3_set_panda_scene_instance(h, 0) or
+ * m3_set_panda_weighted_cost_instance(h, 0) with priors set refuses the next rollout (M3_ERR_STATE).
+ * Not batched: m3_batch_command with such a handle and m3_panda_episodes_create* / _observe / _act / _act_first with such a
+ * planner return M3_ERR_UNSUPPORTED (the message names m3_set_panda_prior_samples and the index of the handle); nothing is
+ * launched and every handle stays as it was.
+ * Memory, uploads and synchronisation: as for m3_set_prior_samples (the table is M3_MAX_PRIOR_SAMPLES x T x 9 floats). */
+int m3_set_panda_prior_samples(m3_handle* h, const float* seqs /* [n][T][9] */, const int* sample_idx, int n);
+int m3_set_panda_prior_samples_device(m3_handle* h, const float* seqs_dev, const int* sample_idx, int n);
+int m3_panda_prior_samples_set(const m3_handle* h);   /* n (0: none) */
+int m3_get_panda_prior_sample(const m3_handle* h, int j, int* sample_idx, float* seq);
+int m3_panda_prior_samples_used(m3_handle* h);        /* 0 / 1: the last rollout launched k_rollout_panda_pr; -1 before the first */
 /* Diagnostic, host only (no device call, no handle): the blocks -- device, pinned and host memory, events, peer mappings -- that
  * the process's handles, batches and episode sets hold right now.  Every object owns its memory through one ledger; an object's
  * destroy call takes its blocks off the count, so after every object is destroyed the count is what it was before the first. */

@@ -251,6 +251,11 @@ SYMBOLS = [
     ("m3_prior_samples_set", C.c_int, [_H]),
     ("m3_get_prior_sample", C.c_int, [_H, C.c_int, C.POINTER(C.c_int), _FP]),
     ("m3_prior_samples_used", C.c_int, [_H]),
+    ("m3_set_panda_prior_samples", C.c_int, [_H, C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    ("m3_set_panda_prior_samples_device", C.c_int, [_H, C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    ("m3_panda_prior_samples_set", C.c_int, [_H]),
+    ("m3_get_panda_prior_sample", C.c_int, [_H, C.c_int, C.POINTER(C.c_int), _FP]),
+    ("m3_panda_prior_samples_used", C.c_int, [_H]),
     ("m3_owned_blocks_live", C.c_longlong, []),
     ("m3_set_multi_modal", C.c_int, [_H, C.c_int]),
     ("m3_set_plan", C.c_int, [_H, C.c_int, _FP]),

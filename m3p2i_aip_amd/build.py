@@ -21,7 +21,7 @@ SOURCES = ["rollout_point.hip", "rollout_point_task0.hip", "rollout_point_task1.
            "rollout_point_task3.hip", "rollout_point_scene.hip", "rollout_point_scene_rows.hip",
            "rollout_point_rollout_scenes.hip", "rollout_point_priors.hip", "rollout_point_priors_batch.hip", "prior_controllers.hip",
            "rollout_panda.hip", "rollout_panda_scene.hip", "rollout_panda_weights.hip", "rollout_panda_rows.hip",
-           "rollout_panda_batch_rt.hip", "rollout_panda_episodes_rt.hip",
+           "rollout_panda_priors.hip", "rollout_panda_batch_rt.hip", "rollout_panda_episodes_rt.hip",
            "update.hip", "update_small.hip", "update_sharded.hip", "sampler.hip", "p2p.hip", "m3_api.hip"]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall",
           "-Wno-unused-function"]
@@ -38,6 +38,7 @@ PER_SOURCE = {
     "rollout_panda_scene.hip": ["-fno-slp-vectorize", "-O2"],   # (rollout_panda.hip's: the same bodies)
     "rollout_panda_weights.hip": ["-fno-slp-vectorize", "-O2"],   # (likewise)
     "rollout_panda_rows.hip": ["-fno-slp-vectorize", "-O2"],   # (likewise)
+    "rollout_panda_priors.hip": ["-fno-slp-vectorize", "-O2"],   # (likewise)
     "rollout_panda_batch_rt.hip": ["-fno-slp-vectorize", "-O2"],   # (likewise)
     "rollout_panda_episodes_rt.hip": ["-fno-slp-vectorize", "-O2"],   # (likewise: k_panda_episodes_pre / _post live in rollout_panda.hip)
 }

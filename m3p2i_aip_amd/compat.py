@@ -147,6 +147,11 @@ class ExampleConfig:
                                                         # K rollouts take the proposals of a host-side ancillary controller
                                                         # (priors.go_to / priors.push_behind), set before every command
                                                         # (tools/closed_loop.py; MPPI.set_prior_samples)
+    panda_prior_samples: Optional[Dict[str, object]] = None   # EXTENSION, panda_env: `panda_prior_samples={controller: hold, n: 4}`
+                                                              # or `{controller: joint_go_to, n: 4, q: [7 or 9 joint targets]}` -- n
+                                                              # of the K rollouts take the proposals of a host-side ancillary
+                                                              # controller (priors.hold / priors.joint_go_to), set before every
+                                                              # command (tools/closed_loop.py; MPPI.set_panda_prior_samples)
     rollout_workspace_spread: Optional[Dict[str, object]] = None   # EXTENSION, panda_env: `rollout_workspace_spread={spread: 0.3,
                                                                    # seed: 1, fields: [cube_m, mu, obs_m]}` -- the planner's K
                                                                    # rollouts each in a workspace of their own around panda_scene
@@ -203,6 +208,9 @@ def make_config(config_name="config_point", overrides=()):
     if cfg.prior_samples:
         cfg.prior_samples = dict(cfg.prior_samples)
         check_prior_samples(cfg)
+    if cfg.panda_prior_samples:
+        cfg.panda_prior_samples = dict(cfg.panda_prior_samples)
+        check_panda_prior_samples(cfg)
     if cfg.rollout_workspace_spread:
         cfg.rollout_workspace_spread = dict(cfg.rollout_workspace_spread)
         _check_rollout_workspace_spread(cfg)
@@ -248,6 +256,45 @@ def check_prior_samples(cfg):
         if given["device"] and n > _lib.MAX_PRIOR_CONTROLLER_SEQS:
             raise ValueError(f"prior_samples: device: true takes n in 1 .. {_lib.MAX_PRIOR_CONTROLLER_SEQS}, not {n}")
     return str(given["controller"]), n
+
+
+def check_panda_prior_samples(cfg):
+    """the parsed `panda_prior_samples` key as (controller name, n, q: the joint targets of joint_go_to or None); ValueError for
+    what it cannot mean"""
+    from . import _lib, priors
+    given = dict(cfg.panda_prior_samples)
+    if cfg.env_type != "panda_env":
+        raise ValueError("panda_prior_samples: panda_env only")
+    unknown = sorted(set(given) - {"controller", "n", "q"})
+    if unknown or given.get("controller") not in priors.PANDA_CONTROLLERS:
+        raise ValueError(f"panda_prior_samples: {{controller: {' | '.join(priors.PANDA_CONTROLLERS)}, n: 4, q: [...]}} "
+                         f"(unknown key(s) {unknown})")
+    n = int(given.get("n", 4))
+    if not 1 <= n <= min(_lib.MAX_PRIOR_SAMPLES, int(cfg.mppi.num_samples) // 2 - 2):
+        raise ValueError(f"panda_prior_samples: n {n} is not in 1 .. min({_lib.MAX_PRIOR_SAMPLES}, num_samples / 2 - 2)")
+    name, q = str(given["controller"]), given.get("q")
+    if name == "joint_go_to":
+        if not isinstance(q, (list, tuple)) or len(q) not in (7, 9):
+            raise ValueError(f"panda_prior_samples: joint_go_to takes q: [7 or 9 joint targets], not {q!r}")
+        q = [float(x) for x in q]
+    elif q is not None:
+        raise ValueError("panda_prior_samples: q is joint_go_to's (hold takes none)")
+    return name, n, q
+
+
+def panda_prior_sequences(cfg, q_now):
+    """the [n, T, 9] sequences of the `panda_prior_samples` key for the arm at joint positions q_now (nine), and the sample
+    indices they go to (prior_sample_indices): hold gives n equal rows of zeros, joint_go_to one row per speed factor
+    1 - j / n"""
+    from . import priors
+    name, n, q = check_panda_prior_samples(cfg)
+    m = cfg.mppi
+    if name == "hold":
+        seqs = priors.hold(int(m.horizon), n)
+    else:
+        seqs = priors.joint_go_to(q_now, q, int(m.horizon), float(cfg.isaacgym.dt), [float(x) for x in m.u_max],
+                                  [1.0 - j / n for j in range(n)])
+    return seqs, prior_sample_indices(int(m.num_samples), n, bool(cfg.multi_modal))
 
 
 def prior_samples_on_device(cfg):

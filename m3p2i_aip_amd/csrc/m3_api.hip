@@ -1045,13 +1045,22 @@ extern "C" int m3_set_panda_scene_instance(m3_handle* h, int on) {
     return set_instance(h, M3_ENV_PANDA, &m3_handle::panda_scene_instance, on, "m3_set_panda_scene_instance", "values");
 }
 
-// ---- prior samples (extension, point_env planner handles, unsharded): samples of the fused rollout that take the caller's
-// control sequences.  THE allocation of the feature is the first setter call on a handle; m3_rollout and m3_command read the
-// two device blocks, nothing else.  Every check before any state changes ----
+// ---- prior samples (extension, planner handles, unsharded): samples of the fused rollout that take the caller's control
+// sequences.  THE allocation of the feature is the first setter call on a handle; m3_rollout and m3_command read the two
+// device blocks, nothing else.  Every check before any state changes.  One implementation for both environments (point_env:
+// m3_set_prior_samples, nu = 2; panda_env: m3_set_panda_prior_samples, nu = 9): a PriorKind names the environment, the
+// handle's state of that kind and the entry points' names; nu is the handle's ----
+struct PriorKind {
+    int env;
+    PriorSampleState m3_handle::*state;
+    const char* setter;          // the host entry point; the device one is setter + "_device"
+};
+static const PriorKind PRIOR_KIND_POINT = {M3_ENV_POINT, &m3_handle::priors, "m3_set_prior_samples"};
+static const PriorKind PRIOR_KIND_PANDA = {M3_ENV_PANDA, &m3_handle::panda_priors, "m3_set_panda_prior_samples"};
 // the checks on the handle ...
-static int prior_handle_check(m3_handle* h, const std::string& who) {
+static int prior_handle_check(m3_handle* h, const std::string& who, int env = M3_ENV_POINT) {
     const m3_config& c = h->cfg;
-    if (c.env_type != M3_ENV_POINT) return fail(h, M3_ERR_UNSUPPORTED, (who + env_only_text(M3_ENV_POINT)).c_str());
+    if (c.env_type != env) return fail(h, M3_ERR_UNSUPPORTED, (who + env_only_text(env)).c_str());
     if (c.sim_only) return fail(h, M3_ERR_STATE, (who + ": planner handles only (the handle was created sim_only)").c_str());
     if (c.K_local != c.K_global) return fail(h, M3_ERR_UNSUPPORTED, (who + ": sharded handle (K_local != K_global)").c_str());
     return M3_OK;
@@ -1075,9 +1084,10 @@ static int prior_index_check(m3_handle* h, const std::string& who, const int* sa
 }
 // The blocks of the feature (allocated by the first call on the handle, as one group) and the slot map of these n indices on
 // the device.  Leaves the pinned mirror free to be rewritten: the previous call's uploads from it are over.
-static int prior_blocks_and_slots(m3_handle* h, const std::string& who, const int* sample_idx, int n) {
+static int prior_blocks_and_slots(m3_handle* h, const std::string& who, const int* sample_idx, int n,
+                                  const PriorKind& kind = PRIOR_KIND_POINT) {
     const m3_config& c = h->cfg;
-    PriorSampleState& ps = h->priors;
+    PriorSampleState& ps = h->*kind.state;
     const int Kl = c.K_local, T = c.T, nu = c.nu;
     const size_t tab_bytes = (size_t)M3_MAX_PRIOR_SAMPLES * T * nu * sizeof(float), slot_bytes = (size_t)Kl * sizeof(int);
     bool slots_stale = false;
@@ -1109,15 +1119,15 @@ static int prior_blocks_and_slots(m3_handle* h, const std::string& who, const in
     }
     return M3_OK;
 }
-static int set_prior_samples(m3_handle* h, const float* seqs, const int* sample_idx, int n, bool device) {
+static int set_prior_samples(m3_handle* h, const PriorKind& kind, const float* seqs, const int* sample_idx, int n, bool device) {
     if (!h) return M3_ERR_BAD_ARG;
-    const std::string who = device ? "m3_set_prior_samples_device" : "m3_set_prior_samples";
+    const std::string who = std::string(kind.setter) + (device ? "_device" : "");
     const m3_config& c = h->cfg;
-    int rc = prior_handle_check(h, who);
+    int rc = prior_handle_check(h, who, kind.env);
     if (rc != M3_OK) return rc;
     if (n < 0 || n > M3_MAX_PRIOR_SAMPLES)
         return fail(h, M3_ERR_BAD_ARG, (who + ": n is " + std::to_string(n) + ", must be in 0 .. " + std::to_string(M3_MAX_PRIOR_SAMPLES)).c_str());
-    PriorSampleState& ps = h->priors;
+    PriorSampleState& ps = h->*kind.state;
     if (!seqs || n == 0) {   // exactly the kernels of a handle that never had priors (the blocks are kept for a later call)
         ps.n = 0;
         ps.ctl.kind = 0;
@@ -1132,7 +1142,7 @@ static int set_prior_samples(m3_handle* h, const float* seqs, const int* sample_
                     if (!std::isfinite(seqs[((size_t)j * T + t) * nu + u]))
                         return fail(h, M3_ERR_BAD_ARG, (who + ": prior " + std::to_string(j) + ": step " + std::to_string(t) + " control " +
                                                         std::to_string(u) + " is not finite").c_str());
-    if ((rc = prior_blocks_and_slots(h, who, sample_idx, n)) != M3_OK) return rc;
+    if ((rc = prior_blocks_and_slots(h, who, sample_idx, n, kind)) != M3_OK) return rc;
     const size_t bytes = (size_t)n * T * nu * sizeof(float);
     if (device) {
         HIPCHK(h, hipMemcpyAsync(ps.tab_dev, seqs, bytes, hipMemcpyDeviceToDevice, h->stream));
@@ -1147,17 +1157,10 @@ static int set_prior_samples(m3_handle* h, const float* seqs, const int* sample_
     ps.ctl.kind = 0;   // (against m3_set_prior_controller the last call wins: the table is the caller's again)
     return M3_OK;
 }
-extern "C" int m3_set_prior_samples(m3_handle* h, const float* seqs, const int* sample_idx, int n) {
-    return set_prior_samples(h, seqs, sample_idx, n, false);
-}
-extern "C" int m3_set_prior_samples_device(m3_handle* h, const float* seqs_dev, const int* sample_idx, int n) {
-    return set_prior_samples(h, seqs_dev, sample_idx, n, true);
-}
-extern "C" int m3_prior_samples_set(const m3_handle* h) { return h ? h->priors.n : M3_ERR_BAD_ARG; }
-extern "C" int m3_get_prior_sample(const m3_handle* h, int j, int* sample_idx, float* seq) {
+static int get_prior_sample(const m3_handle* h, const PriorKind& kind, int j, int* sample_idx, float* seq) {
     if (!h) return M3_ERR_BAD_ARG;
-    if (h->cfg.env_type != M3_ENV_POINT) return M3_ERR_UNSUPPORTED;
-    const PriorSampleState& ps = h->priors;
+    if (h->cfg.env_type != kind.env) return M3_ERR_UNSUPPORTED;
+    const PriorSampleState& ps = h->*kind.state;
     if (j < 0 || j >= ps.n) return M3_ERR_BAD_ARG;
     if (seq && !ps.host_values) return M3_ERR_STATE;
     if (sample_idx) *sample_idx = ps.idx[j];
@@ -1165,7 +1168,29 @@ extern "C" int m3_get_prior_sample(const m3_handle* h, int j, int* sample_idx, f
     if (seq) std::memcpy(seq, ps.pinned + (size_t)j * row, row * sizeof(float));
     return M3_OK;
 }
+extern "C" int m3_set_prior_samples(m3_handle* h, const float* seqs, const int* sample_idx, int n) {
+    return set_prior_samples(h, PRIOR_KIND_POINT, seqs, sample_idx, n, false);
+}
+extern "C" int m3_set_prior_samples_device(m3_handle* h, const float* seqs_dev, const int* sample_idx, int n) {
+    return set_prior_samples(h, PRIOR_KIND_POINT, seqs_dev, sample_idx, n, true);
+}
+extern "C" int m3_prior_samples_set(const m3_handle* h) { return h ? h->priors.n : M3_ERR_BAD_ARG; }
+extern "C" int m3_get_prior_sample(const m3_handle* h, int j, int* sample_idx, float* seq) {
+    return get_prior_sample(h, PRIOR_KIND_POINT, j, sample_idx, seq);
+}
 extern "C" int m3_prior_samples_used(m3_handle* h) { return h ? h->priors.used : M3_ERR_BAD_ARG; }
+// (panda_env: the same five)
+extern "C" int m3_set_panda_prior_samples(m3_handle* h, const float* seqs, const int* sample_idx, int n) {
+    return set_prior_samples(h, PRIOR_KIND_PANDA, seqs, sample_idx, n, false);
+}
+extern "C" int m3_set_panda_prior_samples_device(m3_handle* h, const float* seqs_dev, const int* sample_idx, int n) {
+    return set_prior_samples(h, PRIOR_KIND_PANDA, seqs_dev, sample_idx, n, true);
+}
+extern "C" int m3_panda_prior_samples_set(const m3_handle* h) { return h ? h->panda_priors.n : M3_ERR_BAD_ARG; }
+extern "C" int m3_get_panda_prior_sample(const m3_handle* h, int j, int* sample_idx, float* seq) {
+    return get_prior_sample(h, PRIOR_KIND_PANDA, j, sample_idx, seq);
+}
+extern "C" int m3_panda_prior_samples_used(m3_handle* h) { return h ? h->panda_priors.used : M3_ERR_BAD_ARG; }
 
 // ---- a prior controller (extension, m3p2i_hip_ext.h): the library fills the table, on the device, ahead of every rollout ----
 extern "C" void m3_default_prior_controller(m3_prior_controller* pc, int kind, int n) {
@@ -1286,6 +1311,7 @@ static PandaVariantInput panda_input(const m3_handle* h) {
     in.rollout_scenes_on = h->panda_rows.sample_on;
     in.scene_rows_on = h->panda_rows.env_on;
     in.sim_only = h->cfg.sim_only != 0;
+    in.priors_on = h->panda_priors.n > 0;
     return in;
 }
 static const char* panda_refusal_text(PandaRefusal r) {
@@ -1309,6 +1335,12 @@ static const char* panda_refusal_text(PandaRefusal r) {
         case PANDA_UNBATCHED_WEIGHTS:
             return "its cost weights (m3_set_panda_cost_weights) need the weighted cost instance, which only m3_rollout / "
                    "m3_command and the handle's own m3_cost run";
+        case PANDA_SCENE_OFF_PRIORS:
+            return "the run-time-scene instance is forced off (m3_set_panda_scene_instance 0) but the handle has prior samples (m3_set_panda_prior_samples)";
+        case PANDA_WEIGHTS_OFF_PRIORS:
+            return "the weighted cost instance is forced off (m3_set_panda_weighted_cost_instance 0) but the handle has prior samples (m3_set_panda_prior_samples)";
+        case PANDA_UNBATCHED_PRIORS:
+            return "it has prior samples (m3_set_panda_prior_samples), which only m3_rollout / m3_command run";
     }
     return nullptr;
 }
@@ -1331,7 +1363,13 @@ static const char* panda_episodes_refusal(const m3_handle* h, PandaEpisodesMode 
 }
 // a launcher's view of the handle for a variant, and the record of what an accepted call launches
 static PandaLaunchScene panda_launch_scene(const m3_handle* h, PandaVariant v) {
-    return {v, &h->pscene, &h->pscene_rt, &h->panda_cost_weights, h->panda_rows.dev};
+    PandaLaunchScene sc = {v, &h->pscene, &h->pscene_rt, &h->panda_cost_weights, h->panda_rows.dev};
+    if (v == PANDA_PRIORS) {   // (one family with and without a workspace per sample: null rows say "the handle's scene")
+        if (!h->panda_rows.sample_on) sc.rows = nullptr;
+        sc.prior_slot = h->panda_priors.slot_dev;
+        sc.prior_tab = h->panda_priors.tab_dev;
+    }
+    return sc;
 }
 static void panda_record_used(m3_handle* h, const PandaDecision& d) {
     if (d.scene_used != PANDA_USED_UNCHANGED) h->panda_scene_used = d.scene_used;
@@ -1616,6 +1654,7 @@ extern "C" int m3_rollout(m3_handle* h) {
         const PandaDecision d = panda_decision(panda_input(h), PANDA_SIDE_ROLLOUT);
         launch_rollout_panda(a, pa, panda_launch_scene(h, d.variant), p, h->stream);
         panda_record_used(h, d);
+        h->panda_priors.used = d.variant == PANDA_PRIORS ? 1 : 0;
     }
     HIPCHK(h, hipGetLastError());
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
@@ -2379,6 +2418,11 @@ static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code, bool pa
     if (h->priors.n > 0 && !point_priors) {   // (no table entry carries a slot map and a table of priors)
         code = M3_ERR_UNSUPPORTED;
         return PRIORS_UNBATCHED;
+    }
+    // (no table entry carries a slot map and a table of priors, with or without the run-time section)
+    if (c.env_type == M3_ENV_PANDA && panda_refusal(panda_input(h), PANDA_SIDE_BATCH) == PANDA_UNBATCHED_PRIORS) {
+        code = M3_ERR_UNSUPPORTED;
+        return panda_refusal_text(PANDA_UNBATCHED_PRIORS);
     }
     if (const char* why = rollout_refusal(h)) return why;
     if (!panda_runtime) {

@@ -476,6 +476,10 @@ struct PandaLaunchScene {
     const PandaSceneRT* rt;
     const PandaCostWeights* wt;
     const float* rows;
+    // PANDA_PRIORS (m3_set_panda_prior_samples): the handle's slot map [Kl] and table of prior samples [rows][T][9]; its `rows`
+    // are null unless the handle has a workspace per sample as well
+    const int* prior_slot = nullptr;
+    const float* prior_tab = nullptr;
 };
 // One launcher per operation (rollout_panda.hip; each forwards to the translation unit that holds the family's kernels).
 // The rollout: pa, p as plan_rollout_panda left them -- the form is chosen alike for every family -- + the family's reach-cost
@@ -602,6 +606,7 @@ struct m3_handle {
     m3::SceneRows<m3_point_scene> point_rows;   // table [POINT_SCENE_ROW_WORDS][Kl] (point_scene_rows.hpp)
     m3::SceneRows<m3_panda_scene> panda_rows;   // table [PANDA_SCENE_ROW_WORDS][Kl] (panda_scene_rows.hpp)
     m3::PriorSampleState priors;                // m3_set_prior_samples; survives m3_reset
+    m3::PriorSampleState panda_priors;          // m3_set_panda_prior_samples (nu = 9; no controller); survives m3_reset
     // world
     float world0[18];
     const float* world0_bound = nullptr;  // device, 18 floats (filled by world_from_sim)

@@ -7,15 +7,16 @@
 namespace m3 {
 
 // the kernel families (the files they live in: rollout_panda.hip, rollout_panda_scene.hip, rollout_panda_weights.hip,
-// rollout_panda_rows.hip; their table forms in rollout_panda.hip and rollout_panda_batch_rt.hip)
+// rollout_panda_rows.hip, rollout_panda_priors.hip; their table forms in rollout_panda.hip and rollout_panda_batch_rt.hip)
 enum PandaVariant {
     PANDA_LITERAL,    // the reference's workspace and cost weights compiled in
     PANDA_SCENE,      // the workspace a kernel argument (PandaSceneRT), the literal cost
     PANDA_WEIGHTED,   // ... and the cost weights a kernel argument (PandaCostWeights)
-    PANDA_ROWS        // ... and the workspace words of a lane from its row of the handle's table; weights always
+    PANDA_ROWS,       // ... and the workspace words of a lane from its row of the handle's table; weights always
+    PANDA_PRIORS      // ... and the controls of some samples the caller's sequences (m3_set_panda_prior_samples); the rows optional
 };
 // the families whose cost is the weighted overload of panda_cost (the reach-cost kernel behind their rollout is the weighted one)
-constexpr bool panda_cost_weighted(PandaVariant v) { return v == PANDA_WEIGHTED || v == PANDA_ROWS; }
+constexpr bool panda_cost_weighted(PandaVariant v) { return v == PANDA_WEIGHTED || v == PANDA_ROWS || v == PANDA_PRIORS; }
 // every family but the literal one exists as GENERAL builds only: the plan's choice of the literal kernel's build means nothing
 constexpr bool panda_general_only(PandaVariant v) { return v != PANDA_LITERAL; }
 // BatchKey::variant of a batch-side variant: 0 kb_rollout_panda (the literal section of the table), 1 kb_rollout_panda_w,
@@ -30,6 +31,7 @@ struct PandaVariantInput {
     bool rollout_scenes_on;   // m3_set_panda_rollout_scenes: a workspace per sample of the fused rollout
     bool scene_rows_on;       // m3_set_panda_scene_rows: a workspace per environment of a sim_only handle
     bool sim_only;
+    bool priors_on = false;   // m3_set_panda_prior_samples: samples of the fused rollout that take the caller's sequences
 };
 
 enum PandaSide {
@@ -51,7 +53,12 @@ enum PandaRefusal {
     PANDA_UNBATCHED_SCENE,
     PANDA_UNBATCHED_SAMPLE_ROWS,
     PANDA_UNBATCHED_ENV_ROWS,
-    PANDA_UNBATCHED_WEIGHTS
+    PANDA_UNBATCHED_WEIGHTS,
+    // prior samples (m3_set_panda_prior_samples): their kernels are run-time-scene, weighted kernels (M3_ERR_STATE) ...
+    PANDA_SCENE_OFF_PRIORS,         // the run-time-scene instance is forced off but the handle has prior samples
+    PANDA_WEIGHTS_OFF_PRIORS,       // the weighted cost instance is forced off but the handle has prior samples
+    // ... that only m3_rollout / m3_command launch (M3_ERR_UNSUPPORTED)
+    PANDA_UNBATCHED_PRIORS
 };
 
 constexpr int PANDA_USED_UNCHANGED = -1;
@@ -73,11 +80,16 @@ inline bool panda_weighted(const PandaVariantInput& in) {
 // why the handle cannot run its kernels.  The rows' kernels are run-time-scene kernels, so the scene switch refuses rows on
 // every side; the weights matter where a cost is formed.
 inline PandaRefusal panda_refusal(const PandaVariantInput& in, PandaSide side) {
+    // (no table entry carries a slot map and a table of priors: ahead of everything the handle's own kernels would refuse)
+    if (side == PANDA_SIDE_BATCH && in.priors_on) return PANDA_UNBATCHED_PRIORS;
     if (in.scene_instance == 0 && in.scene_rows_on) return PANDA_SCENE_OFF_ENV_ROWS;
     if (in.scene_instance == 0 && in.rollout_scenes_on) return PANDA_SCENE_OFF_SAMPLE_ROWS;
     if (in.scene_instance == 0 && !in.geometry_default) return PANDA_SCENE_OFF_GEOMETRY;
     const bool forms_cost = side == PANDA_SIDE_ROLLOUT || side == PANDA_SIDE_COST || side == PANDA_SIDE_BATCH;
     if (forms_cost && in.weighted_instance == 0 && !in.weights_default) return PANDA_WEIGHTS_OFF_TUNED;
+    // (the prior family is one: run-time scene and weighted cost.  The rollout alone launches it)
+    if (side == PANDA_SIDE_ROLLOUT && in.priors_on && in.scene_instance == 0) return PANDA_SCENE_OFF_PRIORS;
+    if (side == PANDA_SIDE_ROLLOUT && in.priors_on && in.weighted_instance == 0) return PANDA_WEIGHTS_OFF_PRIORS;
     return PANDA_REFUSAL_NONE;
 }
 
@@ -94,6 +106,9 @@ inline PandaDecision panda_decision(const PandaVariantInput& in, PandaSide side)
             d.weighted_used = wt ? 1 : 0;
             // (the table's run-time section has ONE construction for a scene, weights or both: rollout_panda_batch_rt.hip)
             if (side == PANDA_SIDE_BATCH && d.variant == PANDA_SCENE) d.variant = PANDA_WEIGHTED;
+            // prior samples win over every other family (the batch side refuses them: panda_refusal); the workspace is a kernel
+            // argument in all their kernels, "weighted" keeps saying whether the WEIGHTS needed the instance
+            if (side == PANDA_SIDE_ROLLOUT && in.priors_on) { d.variant = PANDA_PRIORS; d.scene_used = 1; }
             break;
         case PANDA_SIDE_STEP:
             d.scene_used = (in.scene_rows_on || rt) ? 1 : 0;
@@ -115,6 +130,7 @@ inline PandaDecision panda_decision(const PandaVariantInput& in, PandaSide side)
 // rows before weights (m3_batch_command, m3_panda_episodes_create) or weights before rows (the episodes' ticks).
 enum PandaUnbatchedOrder { PANDA_ROWS_THEN_WEIGHTS, PANDA_WEIGHTS_THEN_ROWS };
 inline PandaRefusal panda_unbatched(const PandaVariantInput& in, PandaUnbatchedOrder order) {
+    if (in.priors_on) return PANDA_UNBATCHED_PRIORS;
     if (panda_scene_runtime(in)) return PANDA_UNBATCHED_SCENE;
     const PandaRefusal rows = in.rollout_scenes_on ? PANDA_UNBATCHED_SAMPLE_ROWS
                               : in.scene_rows_on   ? PANDA_UNBATCHED_ENV_ROWS
@@ -137,7 +153,10 @@ inline PandaRefusal panda_episodes_refusal(const PandaVariantInput& in, PandaEpi
     if (mode == PANDA_EPISODES_LITERAL) return panda_unbatched(in, order);
     return panda_refusal(in, in.sim_only ? PANDA_SIDE_STEP : PANDA_SIDE_BATCH);
 }
-// the refusals of panda_refusal are M3_ERR_STATE, those of panda_unbatched M3_ERR_UNSUPPORTED
-constexpr bool panda_refusal_is_state(PandaRefusal r) { return r >= PANDA_SCENE_OFF_ENV_ROWS && r <= PANDA_WEIGHTS_OFF_TUNED; }
+// the refusals of panda_refusal are M3_ERR_STATE (but the batch side's PANDA_UNBATCHED_PRIORS), those of panda_unbatched
+// M3_ERR_UNSUPPORTED
+constexpr bool panda_refusal_is_state(PandaRefusal r) {
+    return (r >= PANDA_SCENE_OFF_ENV_ROWS && r <= PANDA_WEIGHTS_OFF_TUNED) || r == PANDA_SCENE_OFF_PRIORS || r == PANDA_WEIGHTS_OFF_PRIORS;
+}
 
 }  // namespace m3

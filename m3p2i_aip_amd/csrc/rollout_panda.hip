@@ -138,6 +138,7 @@ void launch_rollout_panda(const RolloutArgs& a_in, const PandaArgs& pa, const Pa
         case PANDA_SCENE: launch_rollout_panda_scene(a, pa, sc, p, s); break;
         case PANDA_WEIGHTED: launch_rollout_panda_weighted(a, pa, sc, p, s); break;
         case PANDA_ROWS: launch_rollout_panda_rows(a, pa, sc, p, s); break;
+        case PANDA_PRIORS: launch_rollout_panda_priors(a, pa, sc, p, s); break;
     }
     if (!p.rec) return;
     // (the reach-cost kernel reads the record buffer, no scene: the literal one or the weighted one serve every family)
@@ -276,6 +277,7 @@ void launch_psim_cost(const PandaLaunchScene& sc, const PandaCostParams& cp, con
         case PANDA_SCENE: return launch_psim_cost_scene(sc, cp, world, Kl, k0, env0_cube, cost, s);
         case PANDA_WEIGHTED: return launch_psim_cost_weighted(sc, cp, world, Kl, k0, env0_cube, cost, s);
         case PANDA_ROWS: return launch_psim_cost_rows(sc, cp, world, Kl, k0, env0_cube, cost, s);
+        case PANDA_PRIORS: return;   // (a rollout family only: the cost side never decides it, panda_variant.hpp)
     }
 }
 

@@ -2,9 +2,13 @@
 // kb_rollout_panda: the same tokens in both, so that k_rollout_panda compiles to exactly the code it did as a plain kernel
 // (as update_small_body.inc).  In scope where it is included: FORCES, GENERAL, LPS, the scene type `SceneT` (PandaScene, or
 // PandaSceneRT in rollout_panda_scene.hip), `const RolloutArgs& a_`, `const PandaArgs& pa`, `const SceneT& sc_`, a selection of
-// each of the two hooks (rollout_panda_common.hpp) and whatever the selections name: `WT_OFFSET`, `scene_rows` or `tab`.
+// each of the two hooks (rollout_panda_common.hpp), optionally of the third (prior samples), and whatever the selections name:
+// `WT_OFFSET`, `scene_rows` or `tab`, `prior_slot` and `prior_tab`.
 #if !defined(PANDA_BODY_COST) || !defined(PANDA_BODY_SCENE)
 #error "rollout_panda_body.inc: define PANDA_BODY_COST and PANDA_BODY_SCENE as selections of rollout_panda_common.hpp in front of this #include"
+#endif
+#ifndef PANDA_BODY_PRIORS     // (the third hook is optional: no prior samples)
+#define PANDA_BODY_PRIORS PANDA_PRIORS_NONE
 #endif
     PANDA_CORNER_LDS(LPS);
     // (a_.lanes samples per 64-wide wavefront: m3_set_rollout_lanes; the idle lanes leave at once)
@@ -41,6 +45,7 @@
     const int Kl = a.Kl, T = a.T;
     const int k = a.k0 + i;
     PANDA_BODY_SCENE(sc, i)      // (the scene hook: rollout_panda_common.hpp)
+    PANDA_BODY_PRIORS(SLOT, i)   // (the priors hook, here and at three more places)
     PandaWorld w;
     if (a.sim_dof) panda_world_from_sim(a.sim_dof, a.sim_root, pa.cubeA_actor, pa.cubeB_actor, pa.obs_actor, w);
     else panda_world_from_raw(pa.world0, w);
@@ -67,6 +72,7 @@
             nd[j] = a.sampling_random ? 0.0f : dptr[j];
             nm[j] = use_best ? bptr[ts * 9 + j] : mptr[ts * 9 + j];
         }
+        PANDA_BODY_PRIORS(FETCH, t)
     };
     fetch(0);
     FkCarry<LPS> fkc;
@@ -82,6 +88,7 @@
         float cd[9], cm[9];
 #pragma unroll
         for (int j = 0; j < 9; ++j) { cd[j] = nd[j]; cm[j] = nm[j]; }
+        PANDA_BODY_PRIORS(HOLD)
         if (t + 1 < T) fetch(t + 1);
         if constexpr (GENERAL) {
             if (a.sampling_random) {   // N(noise_mu, noise_sigma) = mu + L z (noise_stream.hpp; order as the oracle)
@@ -111,6 +118,7 @@
                 aj = fmaxf(fminf(cm[j] + d * a.scale_tril[j], a.u_max[j]), a.u_min[j]);
                 if (use_best) aj = cm[j];                                              // :407-409
             }
+            PANDA_BODY_PRIORS(SELECT, aj, j)
             if (j >= 7) {                                                              // :412-416 / :346-350
                 if (a.gripper_cmd == 1) aj = 1.5f;
                 else if (a.gripper_cmd == 2) aj = -1.5f;
@@ -246,3 +254,4 @@
     }
 #undef PANDA_BODY_COST
 #undef PANDA_BODY_SCENE
+#undef PANDA_BODY_PRIORS

@@ -108,6 +108,35 @@ __device__ __forceinline__ PandaCostWeights kernarg_weights() {
 // kernels' argument `scene_rows`, the table entry's `rows`
 #define PANDA_SCENE_KERNARG_ROWS(sc, i) panda_scene_row_load(sc, scene_rows, a_.Kl, i);
 #define PANDA_SCENE_TABLE_ROWS(sc, i) panda_scene_row_load(sc, tab[blockIdx.y].rows, a_.Kl, i);
+// ... or the same where the argument may be null (wave-uniform: the handle's one scene then; rollout_panda_priors.hip)
+#define PANDA_SCENE_KERNARG_ROWS_OR_UNIFORM(sc, i) if (scene_rows != nullptr) panda_scene_row_load(sc, scene_rows, a_.Kl, i);
+//
+// The third hook, PANDA_BODY_PRIORS(part, ...): the prior samples of rollout_panda_priors.hip.  It is
+// OPTIONAL -- a shell that selects nothing gets PANDA_PRIORS_NONE, which expands to nothing at each of the four places, so the
+// shells from before the hook compile the tokens they compiled.  The places: SLOT(i) where `i` is final; FETCH(t) inside the
+// body's `fetch`, a step ahead like nd / nm and behind them; HOLD() where the step has taken its copies cd / cm of them; SELECT(aj, j) beside
+// use_best, in simple mode behind that branch's clamp.
+#define PANDA_PRIORS_NONE(part, ...)
+// ... with the kernel's arguments `prior_slot` ([Kl]: row of the table, -1 none) and `prior_tab` ([rows][T][9]).  The slot
+// follows the SAMPLE i (the lanes of a sample, and the shadow slots of samples 0 and K / 2, read one slot and one row).  Both
+// pointers are consumed ahead of the step loop: what the loop keeps is the lane's row pointer (null: no prior), in vector
+// registers.  A prior lane has no use for its noise row -- whatever the mode and the sampler, its control never reads `cd` -- so
+// the nine values of the next step are fetched INTO `nd`, behind the body's own load, and cost no register across the step
+// (with registers of their own the one-lane builds, which sit at the 512-register limit, spilled 8 and 18 more vector
+// registers to scratch than their twins).  HOLD takes them out of `cd` before the random sampler overwrites it.  No branch
+// around the step: lanes without a prior skip the loads and keep their `aj`.
+#define PANDA_PRIORS_KERNARG(part, ...) PANDA_PRIORS_KERNARG_##part(__VA_ARGS__)
+#define PANDA_PRIORS_KERNARG_SLOT(i)                                                                                       \
+    const int prior_row = prior_slot[i];                                                                                   \
+    const float* const prow = prior_row < 0 ? nullptr : prior_tab + (size_t)prior_row * (size_t)(a_.T * 9);
+#define PANDA_PRIORS_KERNARG_FETCH(t)                                                                                      \
+    if (prow != nullptr) {                                                                                                 \
+        _Pragma("unroll") for (int j = 0; j < 9; ++j) nd[j] = prow[(t) * 9 + j];                                           \
+    }
+#define PANDA_PRIORS_KERNARG_HOLD()                                                                                        \
+    float pcur[9];                                                                                                         \
+    _Pragma("unroll") for (int j = 0; j < 9; ++j) pcur[j] = cd[j];
+#define PANDA_PRIORS_KERNARG_SELECT(aj, j) aj = prow != nullptr ? fmaxf(fminf(pcur[j], a.u_max[j]), a.u_min[j]) : aj;
 
 // k_panda_reach_cost (rollout_panda.hip) and its weighted twin (rollout_panda_weights.hip)
 constexpr int RC_TS = 4, RC_CH = 32;      // time slices per workgroup; steps per LDS chunk
@@ -149,7 +178,7 @@ void launch_psim(Kernel kernel, int Kl, hipStream_t s, const Args&... args) {
 // family's part of it takes what it needs from the PandaLaunchScene (the literal parts are local to rollout_panda.hip).
 // (the rollout kernel alone, a.lanes the plan's)
 using PandaRolloutLaunch = void(const RolloutArgs& a, const PandaArgs& pa, const PandaLaunchScene& sc, const RolloutPlan& p, hipStream_t s);
-PandaRolloutLaunch launch_rollout_panda_scene, launch_rollout_panda_weighted, launch_rollout_panda_rows;
+PandaRolloutLaunch launch_rollout_panda_scene, launch_rollout_panda_weighted, launch_rollout_panda_rows, launch_rollout_panda_priors;
 // (the reach-cost kernel reads no scene: the literal one and this one serve every family)
 void launch_panda_reach_cost_weighted(const RolloutArgs& a, const PandaArgs& pa, const PandaLaunchScene& sc, hipStream_t s);
 // (the table's run-time section: kb_rollout_panda_w, with per_sample kb_rollout_panda_v, + the weighted reach-cost kernel)

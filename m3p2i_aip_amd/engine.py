@@ -372,27 +372,52 @@ class HipEngine(_CObject):
         (default 0 .. n-1).  A torch tensor on the engine's device is copied device-to-device on the engine's stream (its
         values are not inspected); anything else goes through the host entry point, which refuses a non-finite value.
         seqs=None (or n = 0) clears.  See include/m3p2i_hip.h: m3_set_prior_samples."""
+        self._set_prior_samples("set_prior_samples", self.lib.m3_set_prior_samples, self.lib.m3_set_prior_samples_device, seqs, indices)
+
+    def _set_prior_samples(self, who, set_host, set_device, seqs, indices):
         if seqs is None or len(seqs) == 0:
-            self._ck(self.lib.m3_set_prior_samples(self._h, None, None, 0))
+            self._ck(set_host(self._h, None, None, 0))
             return
         c = self.cfg
         n = int(seqs.shape[0]) if hasattr(seqs, "shape") else len(seqs)
         idx = list(range(n)) if indices is None else [int(i) for i in indices]
         if len(idx) != n:
-            raise ValueError(f"set_prior_samples: {n} sequences but {len(idx)} indices")
+            raise ValueError(f"{who}: {n} sequences but {len(idx)} indices")
         arr = (C.c_int * max(n, 1))(*idx)
         if isinstance(seqs, torch.Tensor) and seqs.is_cuda and seqs.device == self.device:
             d = seqs.to(torch.float32).contiguous()
             if tuple(d.shape) != (n, c.T, c.nu):
-                raise ValueError(f"set_prior_samples: seqs is {tuple(d.shape)}, expected (n, {c.T}, {c.nu})")
+                raise ValueError(f"{who}: seqs is {tuple(d.shape)}, expected (n, {c.T}, {c.nu})")
             # (the copy is ordered on the engine's stream, d lives until the call returns: keep it until that copy is over)
-            self._ck(self.lib.m3_set_prior_samples_device(self._h, d.data_ptr(), arr, n))
+            self._ck(set_device(self._h, d.data_ptr(), arr, n))
             self._prior_src = d
             return
         d = np.ascontiguousarray(seqs.detach().cpu().numpy() if isinstance(seqs, torch.Tensor) else seqs, dtype=np.float32)
         if d.shape != (n, c.T, c.nu):
-            raise ValueError(f"set_prior_samples: seqs is {d.shape}, expected (n, {c.T}, {c.nu})")
-        self._ck(self.lib.m3_set_prior_samples(self._h, d.ctypes.data, arr, n))
+            raise ValueError(f"{who}: seqs is {d.shape}, expected (n, {c.T}, {c.nu})")
+        self._ck(set_host(self._h, d.ctypes.data, arr, n))
+
+    def set_panda_prior_samples(self, seqs=None, indices=None):
+        """Extension, unsharded panda_env planner engines: PRIOR SAMPLES of the arm -- set_prior_samples with nu = 9 (seqs
+        [n, T, 9]); behind the select the gripper command still overrides controls 7 and 8.  seqs=None (or n = 0) clears.
+        See include/m3p2i_hip.h: m3_set_panda_prior_samples."""
+        self._set_prior_samples("set_panda_prior_samples", self.lib.m3_set_panda_prior_samples,
+                                self.lib.m3_set_panda_prior_samples_device, seqs, indices)
+
+    def panda_prior_samples_set(self):
+        """the number of panda_env prior samples set (0: none)"""
+        return int(self.lib.m3_panda_prior_samples_set(self._h))
+
+    def panda_prior_sample(self, j):
+        """(global sample index, [T, 9] float32 array) of panda_env prior j as set through the host entry point"""
+        k = C.c_int()
+        seq = np.empty((self.cfg.T, self.cfg.nu), np.float32)
+        self._ck_code(self.lib.m3_get_panda_prior_sample(self._h, int(j), C.byref(k), seq.ctypes.data), "m3_get_panda_prior_sample")
+        return int(k.value), seq
+
+    def panda_prior_samples_used(self):
+        """1 / 0: the last rollout launched the panda_env prior kernels; -1 before the first"""
+        return int(self.lib.m3_panda_prior_samples_used(self._h))
 
     def prior_samples_set(self):
         """the number of prior samples set (0: none)"""

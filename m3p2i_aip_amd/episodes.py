@@ -564,6 +564,10 @@ def _panda_groups(episodes, who, panda_runtime=False):
             if getattr(cfg, key):
                 raise ValueError(f"{who}: episode {idx}: `{key}` asks for a workspace of its own (m3_set_panda_scene), which the "
                                  "lockstep panda episodes do not run (one world handle, one scene); use closed_loop.run")
+        if getattr(cfg, "panda_prior_samples", None):    # (with or without the run-time section: no table entry carries priors)
+            raise ValueError(f"{who}: episode {idx}: `panda_prior_samples` asks for prior samples (m3_set_panda_prior_samples), "
+                             "which the lockstep panda episodes do not run (their planners' batched command carries no table of "
+                             "priors); use closed_loop.run")
         if not panda_runtime and getattr(cfg, "rollout_workspace_spread", None):
             raise ValueError(f"{who}: episode {idx}: `rollout_workspace_spread` asks for a workspace per sample "
                              "(m3_set_panda_rollout_scenes), which the lockstep panda episodes do not run (their planners' batched "

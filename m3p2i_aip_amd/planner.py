@@ -639,20 +639,34 @@ class MPPI():
         config fields stay ignored, as in the reference."""
         if self.env_type != "point_env":
             raise ValueError("set_prior_samples: point_env only")
+        self._set_prior_samples("set_prior_samples", self._engine.set_prior_samples, seqs, indices)
+
+    def set_panda_prior_samples(self, seqs, indices=None):
+        """Extension, unsharded panda_env planners: PRIOR SAMPLES of the arm (m3_set_panda_prior_samples) -- the rules of
+        set_prior_samples with nu = 9: seqs [n, T, 9] (priors.hold, priors.joint_go_to, yesterday's plan), indices default to
+        0 .. n-1 for a single-mode planner, a multi-modal planner must pass them, seqs=None clears.  The gripper command stays
+        the task's: while it is "open" / "close" the controls 7 and 8 of a prior sample are overridden like every sample's.
+        Applies to the fused path and the step path alike; command_batch and episodes.run_panda_episodes refuse such a
+        planner."""
+        if self.env_type != "panda_env":
+            raise ValueError("set_panda_prior_samples: panda_env only")
+        self._set_prior_samples("set_panda_prior_samples", self._engine.set_panda_prior_samples, seqs, indices)
+
+    def _set_prior_samples(self, who, engine_set, seqs, indices):
         if self.world_size != 1:
-            raise ValueError("set_prior_samples: unsharded planners only")
+            raise ValueError(f"{who}: unsharded planners only")
         if seqs is None or len(seqs) == 0:
-            self._engine.set_prior_samples(None)
+            engine_set(None)
             self._priors = None
             return
         n = int(seqs.shape[0]) if hasattr(seqs, "shape") else len(seqs)
         if indices is None:
             if self.multi_modal:    # (whatever the mppi mode: the library refuses 0 and K/2 whenever multi_modal is set)
-                raise ValueError("set_prior_samples: a multi-modal planner needs indices (a prior informs the mode whose half "
+                raise ValueError(f"{who}: a multi-modal planner needs indices (a prior informs the mode whose half "
                                  "of the samples it sits in)")
             indices = range(n)
         idx = [int(i) for i in indices]
-        self._engine.set_prior_samples(seqs, idx)       # (every refusal of the library before anything is kept here)
+        engine_set(seqs, idx)       # (every refusal of the library before anything is kept here)
         vals = torch.as_tensor(seqs, dtype=torch.float32).to(self.device).clone()
         self._priors = (torch.tensor(idx, dtype=torch.long, device=self.device), vals)
 
@@ -829,6 +843,9 @@ def command_batch(planners, states, panda_runtime=False, point_runtime=False, po
             raise ValueError(f"command_batch: planner {i} runs in step mode (user dynamics / running_cost callables)")
         if p.world_size > 1 or p.collective is not None:
             raise ValueError(f"command_batch: planner {i} is sharded or has collectives installed")
+        if getattr(p, "env_type", None) == "panda_env" and getattr(p, "has_prior_samples", False):
+            raise ValueError(f"command_batch: planner {i} has prior samples (set_panda_prior_samples), which only its own "
+                             "command() runs (m3_set_panda_prior_samples)")
         if not point_priors and getattr(p, "has_prior_samples", False):
             raise ValueError(f"command_batch: planner {i} has prior samples (set_prior_samples), which only its own command() "
                              "runs (m3_set_prior_samples)")

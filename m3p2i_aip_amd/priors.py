@@ -60,3 +60,42 @@ def push_behind(robot_xy, box_xy, goal_xy, T, dt, u_max, speeds=(1.0, 0.75, 0.5,
 
 
 CONTROLLERS = {"go_to": go_to, "push_behind": push_behind}
+
+
+# ---- panda_env (MPPI.set_panda_prior_samples / m3_set_panda_prior_samples): the control is the joint velocity command of the
+# seven arm joints and the two fingers, tracked by the velocity servo.  Float32 arrays [n, T, 9] ----
+def hold(T, n=1):
+    """Stay where you are: zero velocity commands."""
+    return np.zeros((int(n), int(T), 9), F)
+
+
+def _drive_joint(q, target, T, dt, speed):
+    """_drive for one joint: each step covers what is left of the way, at most speed * dt of it; zero once there."""
+    q, target = float(q), float(target)
+    u = np.zeros(T, np.float64)
+    for t in range(T):
+        d = target - q
+        if d != 0.0:
+            u[t] = np.sign(d) * min(abs(d) / dt, speed)
+        q = q + u[t] * dt
+    return u
+
+
+def joint_go_to(q, q_target, T, dt, u_max, speeds=(1.0, 0.75, 0.5, 0.25)):
+    """Keep going to a joint configuration, KINEMATICALLY (q += u * dt): per joint the saturated proportional drive of _drive,
+    at `factor * |u_max[j]|`, and zero once the joint is there; one sequence per speed factor.  q: the arm's (and, if given,
+    the fingers') positions now; q_target: seven targets (the columns 7 and 8 of the fingers stay zero) or nine (they follow
+    q_target[7:])."""
+    q = np.asarray(q, np.float64).reshape(-1)
+    q_target = np.asarray(q_target, np.float64).reshape(-1)
+    if q_target.shape[0] not in (7, 9) or q.shape[0] < q_target.shape[0]:
+        raise ValueError(f"joint_go_to: q_target has {q_target.shape[0]} entries (7 or 9) and q {q.shape[0]} (at least as many)")
+    lim = np.abs(np.asarray(u_max, np.float64)).reshape(-1)
+    out = np.zeros((len(speeds), int(T), 9), F)
+    for s, f in enumerate(speeds):
+        for j in range(q_target.shape[0]):
+            out[s, :, j] = _drive_joint(q[j], q_target[j], int(T), float(dt), float(f) * float(lim[j]))
+    return out
+
+
+PANDA_CONTROLLERS = {"hold": hold, "joint_go_to": joint_go_to}

@@ -77,6 +77,10 @@ class Tamp:
         """the `prior_samples` config key: the proposals of a host-side ancillary controller (m3p2i_aip_amd/priors.py) from
         this tick's state, for this tick's command -- nothing carries over, so they are set every tick"""
         cfg = self.cfg
+        if getattr(cfg, "panda_prior_samples", None):   # (panda_env: priors.hold / priors.joint_go_to from this tick's joints)
+            q_now = self.sim._dof_state[0].view(-1, 2)[:, 0].cpu().numpy()
+            self.motion_planner.set_panda_prior_samples(*compat.panda_prior_sequences(cfg, q_now))
+            return
         if not getattr(cfg, "prior_samples", None):
             return
         from m3p2i_aip_amd import priors
