@@ -2278,12 +2278,72 @@ struct BatchHandle {   // one handle's command as planned, in call order (copied
     BatchKey key;
     PandaDecision panda;   // (panda_env only: the batch side's, panda_variant.hpp)
 };
-constexpr BatchTableSizes BATCH_TABLE_SIZES = {{sizeof(BatchRolloutEntry), sizeof(BatchRolloutEntryW), sizeof(BatchRolloutEntryS)},
-                                               sizeof(BatchPandaEntry), sizeof(UpdateArgs), 0};
-// (a batch created with M3_BATCH_SECTION_PANDA_RUNTIME / _POINT_ROLLOUT_SCENES: + panda_entry_rt / point_entry_sv, m3_batch_create)
-static_assert(alignof(BatchPandaEntryRT) <= 16 && alignof(BatchPandaEntry) <= 16 && alignof(BatchRolloutEntrySV) <= 16 &&
-              alignof(BatchRolloutEntryPR) <= 16, "the table's sections start on multiples of 16");
-static_assert(BATCH_POINT_SECTIONS5 == POINT_SECTIONS, "");
+// The sections of an environment's table, in the order they lie in: the creation bit that enables the
+// section (M3_BATCH_SECTION_*; 0: every batch has it), the size of its entry type, and how one entry is written from a planned
+// handle.  batch_section_of says which section a planned handle's entry lies in; m3_batch_create and batch_command read
+// nothing else about the sections.
+struct BatchSection {
+    int bit;
+    size_t entry;
+    void (*fill)(void* e, const m3_handle* h, const BatchHandle& d);
+};
+template <class E>
+constexpr BatchSection batch_section(int bit, void (*fill)(void*, const m3_handle*, const BatchHandle&)) {
+    static_assert(alignof(E) <= 16, "the table's sections start on multiples of 16");
+    return {bit, sizeof(E), fill};
+}
+// point_env: by point_section(plan) -- the three variants, the handles with an arena per sample, the handles with prior samples
+const BatchSection BATCH_POINT_SECTIONS[POINT_SECTIONS] = {
+    batch_section<BatchRolloutEntry>(0, [](void* e, const m3_handle* h, const BatchHandle& d) {
+        *static_cast<BatchRolloutEntry*>(e) = {d.a, h->scene};
+    }),
+    batch_section<BatchRolloutEntryW>(0, [](void* e, const m3_handle* h, const BatchHandle& d) {
+        *static_cast<BatchRolloutEntryW*>(e) = {d.a, h->scene, h->cost_weights};
+    }),
+    batch_section<BatchRolloutEntryS>(0, [](void* e, const m3_handle* h, const BatchHandle& d) {
+        *static_cast<BatchRolloutEntryS*>(e) = {d.a, h->scene_rt, h->cost_weights};
+    }),
+    batch_section<BatchRolloutEntrySV>(M3_BATCH_SECTION_POINT_ROLLOUT_SCENES, [](void* e, const m3_handle* h, const BatchHandle& d) {
+        *static_cast<BatchRolloutEntrySV*>(e) = {d.a, h->scene_rt, h->cost_weights, h->point_rows.dev};
+    }),
+    batch_section<BatchRolloutEntryPR>(M3_BATCH_SECTION_POINT_PRIORS, [](void* e, const m3_handle* h, const BatchHandle& d) {
+        // (the handle's own blocks; without a controller kind 0: the table is the caller's)
+        PriorControllerArgs ctl = {{}, h->cfg.dt, h->priors.tab_dev};
+        if (prior_controller_on(h)) ctl.pc = h->priors.ctl;
+        *static_cast<BatchRolloutEntryPR*>(e) = {d.a, h->scene_rt, h->cost_weights, h->point_rows.sample_on ? h->point_rows.dev : nullptr,
+                                                 h->priors.slot_dev, ctl};
+    }),
+};
+static_assert(POINT_PLAIN == 0 && POINT_WEIGHTED == 1 && POINT_SCENE == 2 && POINT_SECTION_SV == 3 && POINT_SECTION_PR == 4, "the order above");
+// panda_env: the literal entries, then the run-time ones (a run-time workspace, tuned weights or a workspace per sample)
+constexpr int PANDA_SECTIONS = 2;
+const BatchSection BATCH_PANDA_SECTIONS[PANDA_SECTIONS] = {
+    batch_section<BatchPandaEntry>(0, [](void* e, const m3_handle* h, const BatchHandle& d) {
+        *static_cast<BatchPandaEntry*>(e) = {d.a, d.pa, *panda_launch_scene(h, d.panda.variant).lit};
+    }),
+    batch_section<BatchPandaEntryRT>(M3_BATCH_SECTION_PANDA_RUNTIME, [](void* e, const m3_handle* h, const BatchHandle& d) {
+        const PandaLaunchScene sc = panda_launch_scene(h, d.panda.variant);
+        *static_cast<BatchPandaEntryRT*>(e) = {d.a, d.pa, *sc.rt, *sc.wt, sc.variant == PANDA_ROWS ? sc.rows : nullptr};
+    }),
+};
+static_assert(POINT_SECTIONS <= BATCH_MAX_SECTIONS && PANDA_SECTIONS <= BATCH_MAX_SECTIONS, "");
+struct BatchSections {
+    const BatchSection* sec;
+    int n;
+};
+BatchSections batch_sections(bool panda) {
+    return panda ? BatchSections{BATCH_PANDA_SECTIONS, PANDA_SECTIONS} : BatchSections{BATCH_POINT_SECTIONS, POINT_SECTIONS};
+}
+int batch_section_of(bool panda, const BatchHandle& d) {
+    return panda ? (d.panda.variant == PANDA_LITERAL ? 0 : 1) : point_section(d.key.roll);
+}
+// the shape of the environment's tables in a batch created with `flags`
+BatchTableShape batch_table_shape(bool panda, int flags) {
+    const BatchSections t = batch_sections(panda);
+    BatchTableShape z{t.n, {}, sizeof(UpdateArgs)};
+    for (int v = 0; v < t.n; ++v) z.entry[v] = (t.sec[v].bit == 0 || (flags & t.sec[v].bit)) ? t.sec[v].entry : 0;
+    return z;
+}
 // the refusal of a point_env handle with an arena per sample by a batch or an episode set that was not created for it
 constexpr const char* PRIORS_UNBATCHED = "it has prior samples (m3_set_prior_samples), which only m3_rollout / m3_command run";
 constexpr const char* POINT_ROWS_UNBATCHED = "it has an arena per sample (m3_set_point_rollout_scenes), which only m3_rollout / m3_command run";
@@ -2292,9 +2352,9 @@ constexpr const char* POINT_ROWS_UNBATCHED = "it has an arena per sample (m3_set
 struct m3_batch {
     int device = 0, max_handles = 0;
     int flags = 0;           // the sections it was created with (M3_BATCH_SECTION_*; bit 1 is m3_batch_create_ex's M3_BATCH_PANDA_RUNTIME)
-    BatchTableSizes sizes = BATCH_TABLE_SIZES;   // the entry sizes its tables are laid out with (flags)
+    BatchTableShape shape[2] = {};   // of its point_env [0] and panda_env [1] tables: the sections it was created with (flags)
     std::string err;
-    size_t slot_bytes = 0;   // of a slot: the largest table of max_handles handles (batch_table_layout.hpp)
+    size_t slot_bytes = 0;   // of a slot: the largest table of max_handles handles of either shape (batch_table_layout.hpp)
     OwnedBlocks mem{&m3_release_block, 3 * BATCH_SLOTS};   // owns the slots; the three arrays below are views
     char* host[BATCH_SLOTS] = {};
     char* dev[BATCH_SLOTS] = {};
@@ -2359,10 +2419,10 @@ static int batch_create(int device, int max_handles, int flags, m3_batch** out) 
     b->device = device;
     b->max_handles = max_handles;
     b->flags = flags;
-    if (flags & M3_BATCH_SECTION_PANDA_RUNTIME) b->sizes.panda_entry_rt = sizeof(BatchPandaEntryRT);
-    if (flags & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES) b->sizes.point_entry_sv = sizeof(BatchRolloutEntrySV);
-    if (flags & M3_BATCH_SECTION_POINT_PRIORS) b->sizes.point_entry_pr = sizeof(BatchRolloutEntryPR);
-    b->slot_bytes = batch_table_capacity(b->sizes, max_handles);
+    for (int panda = 0; panda < 2; ++panda) {
+        b->shape[panda] = batch_table_shape(panda != 0, flags);
+        b->slot_bytes = std::max(b->slot_bytes, batch_table_capacity(b->shape[panda], max_handles));
+    }
     try {
         b->seen.resize(max_handles);
         b->hd.resize(max_handles);
@@ -2400,22 +2460,21 @@ extern "C" int m3_batch_launches(const m3_batch* b, int* rollout_launches, int* 
 
 // the conditions under which m3_batch_command refuses a handle of the call's environment, device and stream (nullptr: none;
 // code: the return code) -- m3_episodes_create checks them too.  u: the arguments of the handle's update, as m3_command
-// launches it.  panda_runtime: the caller's table has the run-time section (a batch created with M3_BATCH_PANDA_RUNTIME), so a
-// panda_env planner that needs the run-time-scene instance, the weighted family or has a workspace per sample passes.
-// point_rows: it has the per-sample section (M3_BATCH_SECTION_POINT_ROLLOUT_SCENES), so a point_env planner with an arena per
-// sample passes.  point_priors: it has the priors section (M3_BATCH_SECTION_POINT_PRIORS), so a point_env planner with prior
-// samples passes -- with or without an arena per sample, which that section's entry carries as well
-static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code, bool panda_runtime = false, bool point_rows = false,
-                                 bool point_priors = false) {
+// launches it.  sections: the M3_BATCH_SECTION_* bits the caller may use.  With the run-time section a panda_env planner that
+// needs the run-time-scene instance, the weighted family or has a workspace per sample passes; with the per-sample section a
+// point_env planner with an arena per sample; with the priors section a point_env planner with prior samples -- with or without
+// an arena per sample, which that section's entry carries as well
+static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code, int sections) {
     const m3_config& c = h->cfg;
+    const bool in_priors_section = h->priors.n > 0 && (sections & M3_BATCH_SECTION_POINT_PRIORS);   // (its entry carries the rows as well)
     code = M3_ERR_STATE;
     if (c.K_local != c.K_global) return "sharded handle (K_local != K_global)";
     if (c.sim_only) return "handle was created sim_only";
-    if (h->point_rows.sample_on && !point_rows && !(point_priors && h->priors.n > 0)) {   // (the table's slots have no fourth section)
+    if (h->point_rows.sample_on && !(sections & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES) && !in_priors_section) {   // (the table's slots have no fourth section)
         code = M3_ERR_UNSUPPORTED;
         return POINT_ROWS_UNBATCHED;
     }
-    if (h->priors.n > 0 && !point_priors) {   // (no table entry carries a slot map and a table of priors)
+    if (h->priors.n > 0 && !in_priors_section) {   // (no table entry carries a slot map and a table of priors)
         code = M3_ERR_UNSUPPORTED;
         return PRIORS_UNBATCHED;
     }
@@ -2425,7 +2484,7 @@ static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code, bool pa
         return panda_refusal_text(PANDA_UNBATCHED_PRIORS);
     }
     if (const char* why = rollout_refusal(h)) return why;
-    if (!panda_runtime) {
+    if (!(sections & M3_BATCH_SECTION_PANDA_RUNTIME)) {
         // (the table's entry carries a PandaScene, no table of rows and no weights: its kernels form the literal cost)
         if (const char* why = panda_unbatched(h, PANDA_ROWS_THEN_WEIGHTS)) {
             code = M3_ERR_UNSUPPORTED;
@@ -2449,13 +2508,9 @@ static int batch_refuse(m3_batch* b, int code, int i, const char* msg) {
     return code;
 }
 
-// panda_runtime: whether the run-time section may be used -- the batch's flag for m3_batch_command and for a lockstep panda
-// episode set created with M3_PANDA_EPISODES_RUNTIME; never for a set created without it, whose pre and post kernels know one
-// compiled-in workspace (whatever batch it is handed).  point_rows: whether the per-sample section of a point_env table may be
-// used -- the batch's flag for m3_batch_command and for a lockstep episode set created with M3_EPISODES_ROLLOUT_SCENES.
-// point_priors: the same for the priors section -- the batch's flag, and for a set only if it was created with M3_EPISODES_PRIORS
-static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* actions_host, bool panda_runtime, bool point_rows,
-                         bool point_priors) {
+// sections: the M3_BATCH_SECTION_* bits of the batch that this call may use -- all of them for m3_batch_command; for a lockstep
+// episode set those that its own flags allow as well (eps_sections, peps_sections), whatever batch it is handed
+static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* actions_host, int sections) {
     // ---- every check before any launch: a refused call leaves every handle as it was ----
     if (!hs) return batch_refuse(b, M3_ERR_BAD_ARG, -1, "null handle list");
     if (n <= 0 || n > b->max_handles) return batch_refuse(b, M3_ERR_BAD_ARG, -1, "n must be in 1 .. max_handles");
@@ -2480,7 +2535,7 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
                                                                 : "panda_env handle in a batch of point_env handles (one environment per call)");
         if (h->stream != s) return batch_refuse(b, M3_ERR_STATE, i, "its stream differs from handle 0's");
         int code;
-        if (const char* why = batch_refusal(h, hd[i].u, code, panda_runtime, point_rows, point_priors)) return batch_refuse(b, code, i, why);
+        if (const char* why = batch_refusal(h, hd[i].u, code, sections)) return batch_refuse(b, code, i, why);
         BatchKey& k = hd[i].key;
         if (panda) hd[i].panda = panda_decision(panda_input(h), PANDA_SIDE_BATCH);   // (by m3_rollout's own dispatch)
         k.variant = panda ? panda_batch_key(hd[i].panda.variant) : 0;
@@ -2513,54 +2568,22 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
         HIPCHK(b, hipEventSynchronize(b->done[slot]));
         b->in_flight[slot] = false;
     }
-    // point_env: in key order the handles come by section (rollout_fields: scene 0 by weighted, 1, 2), as the table's sections do
-    // panda_env: by section -- the literal entries (variant 0), then the run-time ones
-    int count[POINT_SECTIONS] = {};
-    int n_lit = 0;
-    if (!panda)
-        for (int i = 0; i < n; ++i) ++count[point_section(hd[i].key.roll)];
-    else
-        for (int i = 0; i < n; ++i) n_lit += hd[i].panda.variant == PANDA_LITERAL ? 1 : 0;
-    // (without per-sample handles the four-section layout is the three-section one; without handles with priors the
-    // five-section layout is the four-section one)
-    BatchTableLayout5 lay = batch_table_layout5(b->sizes, count);
-    if (panda) {
-        const BatchTableLayout lp = batch_table_layout_panda(b->sizes, n_lit, n - n_lit);
-        lay.off[1] = lp.off[1];
-        lay.upd_off = lp.upd_off;
-        lay.total = lp.total;
-    }
+    // in key order the handles come by section, as the table's sections lie (rollout_fields: point_env priors, then scene 0 by
+    // weighted, 1, 2; panda_env the variant)
+    const BatchTableShape& shape = b->shape[panda];
+    const BatchSection* sec = batch_sections(panda).sec;
+    int count[BATCH_MAX_SECTIONS] = {};
+    for (int i = 0; i < n; ++i) ++count[batch_section_of(panda, hd[i])];
+    const BatchTableLayout lay = batch_table_layout(shape, count);
     // byte offset of the rollout entry of the p-th handle in key order
     auto entry_off = [&](int p) {
-        if (panda) return p < n_lit ? (size_t)p * sizeof(BatchPandaEntry) : lay.off[1] + (size_t)(p - n_lit) * sizeof(BatchPandaEntryRT);
         int v = 0;
         for (; p >= count[v]; ++v) p -= count[v];
-        return lay.off[v] + (size_t)p * batch_point_entry5(b->sizes, v);
+        return lay.off[v] + (size_t)p * shape.entry[v];
     };
     for (int p = 0; p < n; ++p) {
         const int i = b->by_roll[p];
-        const m3_handle* h = hs[i];
-        char* e = b->host[slot] + entry_off(p);
-        if (panda) {
-            const PandaLaunchScene sc = panda_launch_scene(h, hd[i].panda.variant);
-            if (sc.variant == PANDA_LITERAL) *reinterpret_cast<BatchPandaEntry*>(e) = {hd[i].a, hd[i].pa, *sc.lit};
-            else *reinterpret_cast<BatchPandaEntryRT*>(e) = {hd[i].a, hd[i].pa, *sc.rt, *sc.wt, sc.variant == PANDA_ROWS ? sc.rows : nullptr};
-            continue;
-        }
-        switch (point_section(hd[i].key.roll)) {
-            case POINT_SECTION_PR: {
-                // (the handle's own blocks; without a controller kind 0: the table is the caller's)
-                PriorControllerArgs ctl = {{}, h->cfg.dt, h->priors.tab_dev};
-                if (prior_controller_on(h)) ctl.pc = h->priors.ctl;
-                *reinterpret_cast<BatchRolloutEntryPR*>(e) = {hd[i].a, h->scene_rt, h->cost_weights,
-                                                             h->point_rows.sample_on ? h->point_rows.dev : nullptr, h->priors.slot_dev, ctl};
-                break;
-            }
-            case POINT_SECTION_SV: *reinterpret_cast<BatchRolloutEntrySV*>(e) = {hd[i].a, h->scene_rt, h->cost_weights, h->point_rows.dev}; break;
-            case POINT_SCENE: *reinterpret_cast<BatchRolloutEntryS*>(e) = {hd[i].a, h->scene_rt, h->cost_weights}; break;
-            case POINT_WEIGHTED: *reinterpret_cast<BatchRolloutEntryW*>(e) = {hd[i].a, h->scene, h->cost_weights}; break;
-            default: *reinterpret_cast<BatchRolloutEntry*>(e) = {hd[i].a, h->scene}; break;
-        }
+        sec[batch_section_of(panda, hd[i])].fill(b->host[slot] + entry_off(p), hs[i], hd[i]);
     }
     UpdateArgs* hu = reinterpret_cast<UpdateArgs*>(b->host[slot] + lay.upd_off);
     for (int p = 0; p < n; ++p) hu[p] = hd[b->by_upd[p]].u;
@@ -2579,7 +2602,7 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
             if (hd[i].key.roll.priors) hs[i]->priors.used = 1;   // (as m3_rollout records it)
         }
         if (any)
-            launch_prior_controllers_batch(reinterpret_cast<const BatchRolloutEntryPR*>(dslot + lay.off[POINT_SECTION_PR]),
+            launch_prior_controllers_batch(static_cast<const BatchRolloutEntryPR*>(static_cast<const void*>(dslot + lay.off[POINT_SECTION_PR])),
                                            count[POINT_SECTION_PR], s);
     }
     for (int p = 0; p < n;) {
@@ -2594,7 +2617,7 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
     HIPCHK(b, hipGetLastError());
     // what each handle's rollout ran, as m3_rollout records it (a batch without the run-time section runs the literal kernels
     // only and leaves the record as it always did)
-    if (panda && panda_runtime)
+    if (panda && (sections & M3_BATCH_SECTION_PANDA_RUNTIME))
         for (int i = 0; i < n; ++i) panda_record_used(hs[i], hd[i].panda);
     // ---- one update launch per group; multi-modal groups in chunks whose whole grid is resident ----
     for (int p = 0; p < n;) {
@@ -2637,8 +2660,7 @@ static int batch_command(m3_batch* b, m3_handle* const* hs, int n, float* action
 
 extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float* actions_host) {
     if (!b) { g_batch_err = "m3_batch_command: null batch"; return M3_ERR_BAD_ARG; }
-    return batch_command(b, hs, n, actions_host, (b->flags & M3_BATCH_SECTION_PANDA_RUNTIME) != 0,
-                         (b->flags & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES) != 0, (b->flags & M3_BATCH_SECTION_POINT_PRIORS) != 0);
+    return batch_command(b, hs, n, actions_host, b->flags);
 }
 
 static int ensure_sim(m3_handle* h);
@@ -2907,14 +2929,20 @@ extern "C" int m3_episodes_create(m3_handle* world, m3_handle* const* planners, 
 
 extern "C" int m3_episodes_flags(const m3_episodes* eps) { return eps ? eps->flags : M3_ERR_BAD_ARG; }
 
+// the sections of a batch that a set created with `flags` may use: the per-sample section with M3_EPISODES_ROLLOUT_SCENES
+// (planners with an arena per sample pass), the priors section with M3_EPISODES_PRIORS (planners with prior samples pass); the
+// panda run-time section means nothing to point_env planners and is left to the batch
+static int eps_sections(int flags) {
+    return M3_BATCH_SECTION_PANDA_RUNTIME | ((flags & M3_EPISODES_ROLLOUT_SCENES) ? M3_BATCH_SECTION_POINT_ROLLOUT_SCENES : 0) |
+           ((flags & M3_EPISODES_PRIORS) ? M3_BATCH_SECTION_POINT_PRIORS : 0);
+}
+
 // (the messages keep m3_episodes_create's name: flags == 0 is that call)
 extern "C" int m3_episodes_create_ex(m3_handle* world, m3_handle* const* planners, const m3_episode_spec* specs, int n,
                                      int max_ticks, int trace, int flags, m3_episodes** out) {
     if (out) *out = nullptr;
     if (flags & ~(M3_EPISODES_ROLLOUT_SCENES | M3_EPISODES_PRIORS)) { g_eps_err = "m3_episodes_create_ex: unknown flag bits"; return M3_ERR_BAD_ARG; }
     if (!out) return eps_refuse(M3_ERR_BAD_ARG, -1, "null argument");
-    const bool point_rows = (flags & M3_EPISODES_ROLLOUT_SCENES) != 0;   // planners with an arena per sample pass
-    const bool point_priors = (flags & M3_EPISODES_PRIORS) != 0;         // planners with prior samples pass
     // ---- every check before any allocation or launch ----
     if (!world || !planners || !specs) return eps_refuse(M3_ERR_BAD_ARG, -1, "null argument");
     if (n <= 0 || n > 65535) return eps_refuse(M3_ERR_BAD_ARG, -1, "n must be in 1 .. 65535");
@@ -2936,7 +2964,7 @@ extern "C" int m3_episodes_create_ex(m3_handle* world, m3_handle* const* planner
         if (h->stream != world->stream) return eps_refuse(M3_ERR_STATE, i, "its stream differs from the world's");
         UpdateArgs u;
         int code;
-        if (const char* why = batch_refusal(h, u, code, false, point_rows, point_priors)) return eps_refuse(code, i, why);
+        if (const char* why = batch_refusal(h, u, code, eps_sections(flags))) return eps_refuse(code, i, why);
         if (!h->action_out) return eps_refuse(M3_ERR_STATE, i, "no action-out destination (m3_set_action_out)");
         const m3_episode_spec& sp = specs[i];
         if (sp.task < M3_TASK_NAVIGATION || sp.task > M3_TASK_PUSH_PULL) return eps_refuse(M3_ERR_BAD_ARG, i, "spec: task is not a point_env task");
@@ -3079,20 +3107,18 @@ extern "C" int m3_episodes_tick(m3_episodes* eps, m3_batch* batch) {
     // commanded once more -- its plan is never recorded)
     eps->live.clear();
     const m3_handle* w = eps->world;
-    const bool point_rows = (eps->flags & M3_EPISODES_ROLLOUT_SCENES) != 0;
-    const bool point_priors = (eps->flags & M3_EPISODES_PRIORS) != 0;
-    const bool batch_priors = (batch->flags & M3_BATCH_SECTION_POINT_PRIORS) != 0;
+    const int allowed = eps_sections(eps->flags);
     for (int i = 0; i < eps->n; ++i) {
         if (eps->host[i].done_tick >= 0) continue;
         m3_handle* h = eps->planners[i];
         // (a set created for planners with priors, a batch without the section: the batch's own refusal, ahead of the pre kernel)
-        if (h->priors.n > 0 && !batch_priors) {
+        if (h->priors.n > 0 && !(batch->flags & M3_BATCH_SECTION_POINT_PRIORS)) {
             rc = batch_refuse(batch, M3_ERR_UNSUPPORTED, (int)eps->live.size(), PRIORS_UNBATCHED);
             eps->err = std::string("m3_episodes_tick: ") + m3_batch_last_error(batch);
             return rc;
         }
-        const bool in_priors_section = h->priors.n > 0 && point_priors;   // (its entry carries the rows as well)
-        if (h->point_rows.sample_on && !point_rows && !in_priors_section) {   // (set after m3_episodes_create, which refuses it: nothing of this tick is launched)
+        const bool in_priors_section = h->priors.n > 0 && (allowed & M3_BATCH_SECTION_POINT_PRIORS);   // (its entry carries the rows as well)
+        if (h->point_rows.sample_on && !(allowed & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES) && !in_priors_section) {   // (set after m3_episodes_create, which refuses it: nothing of this tick is launched)
             eps->err = "m3_episodes_tick: planner " + std::to_string(i) + ": " + POINT_ROWS_UNBATCHED;
             return M3_ERR_UNSUPPORTED;
         }
@@ -3112,9 +3138,8 @@ extern "C" int m3_episodes_tick(m3_episodes* eps, m3_batch* batch) {
     m3::launch_episodes_pre(eps->args, eps->tick, w->stream);
     HIPCHK(eps, hipGetLastError());
     if (!eps->live.empty()) {
-        // (a set created without the flag never uses the per-sample section, whatever batch it is handed)
-        rc = batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr, (batch->flags & M3_BATCH_SECTION_PANDA_RUNTIME) != 0,
-                           point_rows && (batch->flags & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES) != 0, point_priors && batch_priors);
+        // (a set created without a flag never uses that section, whatever batch it is handed)
+        rc = batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr, batch->flags & allowed);
         if (rc != M3_OK) { eps->err = std::string("m3_episodes_tick: ") + m3_batch_last_error(batch); return rc; }
     }
     episodes_post(w, eps->args, eps->tick);
@@ -3204,6 +3229,10 @@ static int peps_refuse(int code, int i, const std::string& msg) {
 // which _bind_world pushes from the simulator it follows; the world side's row e is scenes[e] of m3_set_panda_scene_rows, else
 // the world's single scene
 static PandaEpisodesMode peps_mode(int flags) { return (flags & M3_PANDA_EPISODES_RUNTIME) ? PANDA_EPISODES_RUNTIME : PANDA_EPISODES_LITERAL; }
+// the sections of a batch that a set created with `flags` may use: a run-time set hands its planners to the run-time section;
+// a set created without the flag never uses it -- its planners and world stay on the compiled-in workspace and the literal
+// cost, whatever batch they are handed
+static int peps_sections(int flags) { return peps_mode(flags) == PANDA_EPISODES_RUNTIME ? M3_BATCH_SECTION_PANDA_RUNTIME : 0; }
 static const m3_panda_scene& peps_planner_scene(const m3_handle* h) { return h->panda_rows.sample_on ? h->panda_rows.set[0] : h->panda_scene; }
 static const m3_panda_scene& peps_world_scene(const m3_handle* w, int e) { return w->panda_rows.env_on ? w->panda_rows.set[e] : w->panda_scene; }
 
@@ -3264,8 +3293,7 @@ static int peps_create(m3_handle* world, m3_handle* const* planners, int n, int 
         if (h->stream != world->stream) return peps_refuse(M3_ERR_STATE, i, "its stream differs from the world's");
         UpdateArgs u;
         int code;
-        // (a run-time set hands its planners to the batch's run-time section: what batch_refusal passes for such a batch)
-        if (const char* why = batch_refusal(h, u, code, mode == PANDA_EPISODES_RUNTIME)) return peps_refuse(code, i, why);
+        if (const char* why = batch_refusal(h, u, code, peps_sections(flags))) return peps_refuse(code, i, why);
         if (!h->action_out) return peps_refuse(M3_ERR_STATE, i, "no action-out destination (m3_set_action_out)");
     }
     // ---- allocations: all of the set's memory, here ----
@@ -3458,12 +3486,9 @@ extern "C" int m3_panda_episodes_act(m3_panda_episodes* eps, m3_batch* batch, co
         eps->live.push_back(h);
     }
     if (!eps->live.empty()) {
-        // (a set created without the flag never uses the run-time section: its planners and world stay on the compiled-in
-        // workspace and the literal cost, whatever batch they are handed.  A run-time set passes the batch's own flag through,
-        // as m3_batch_command does: a batch without the section refuses a planner that needs it, with its code and message,
-        // before anything is launched)
-        const bool section = peps_mode(eps->flags) == PANDA_EPISODES_RUNTIME && (batch->flags & M3_BATCH_PANDA_RUNTIME) != 0;
-        rc = batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr, section, false, false);
+        // (a run-time set passes the batch's own flag through, as m3_batch_command does: a batch without the section refuses a
+        // planner that needs it, with its code and message, before anything is launched)
+        rc = batch_command(batch, eps->live.data(), (int)eps->live.size(), nullptr, batch->flags & peps_sections(eps->flags));
         if (rc != M3_OK) { eps->err = std::string("m3_panda_episodes_act: ") + m3_batch_last_error(batch); return rc; }
     }
     return peps_post(eps, ended_host);

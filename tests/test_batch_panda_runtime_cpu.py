@@ -2,7 +2,7 @@
 with M3_BATCH_PANDA_RUNTIME; include/m3p2i_hip.h) without a GPU:
 
 1. the two-section panda table of csrc/batch_table_layout.hpp, run by a host program with its own main
-   (tests/native/batch_table_layout_rt_host.cpp, plain and under ASan + UBSan) on the entry sizes that a second host program
+   (tests/native/batch_table_layout_host.cpp in its mode `rt`, plain and under ASan + UBSan) on the entry sizes that a second host program
    (tests/native/batch_panda_entry_sizes.hip, the host side of the library's own header) derives with sizeof;
 2. the ctypes declarations against the header, and the thirteen kernels in the built library;
 3. planner.command_batch(..., panda_runtime=True): the three panda refusals are lifted and a batch created with the flag is
@@ -38,14 +38,14 @@ def entry_sizes(tmp_path_factory):
 
 
 def _build_layout(tmp, extra=("-O2",)):
-    out = str(tmp / "batch_table_layout_rt_host")
+    out = str(tmp / "batch_table_layout_host")
     subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + list(extra) +
-                          [os.path.join(HERE, "native", "batch_table_layout_rt_host.cpp"), "-o", out])
+                          [os.path.join(HERE, "native", "batch_table_layout_host.cpp"), "-o", out])
     return out
 
 
 def _run_layout(prog, sizes, env=None):
-    r = subprocess.run([prog] + [str(x) for x in sizes], capture_output=True, text=True, timeout=300, env=env)
+    r = subprocess.run([prog, "rt"] + [str(x) for x in sizes], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-2000:])
     m = re.fullmatch(r"(\d+) checks, 0 failures\n", r.stdout)
     assert m and int(m.group(1)) > 500, r.stdout

@@ -1,6 +1,6 @@
 """Batched command and lockstep episodes of point_env planners with an arena per sample (m3_batch_create_sections,
 m3_episodes_create_ex; DESIGN.md sections 7b.3 and 7c3), the parts that need no GPU: the symbols and the ABI, the four-section
-layout of the argument table as a host program (tests/native/batch_table_layout_sv_host.cpp, once plain and once under
+layout of the argument table as a host program (tests/native/batch_table_layout_host.cpp in its mode `sv`, once plain and once under
 -fsanitize=address,undefined), and the Python paths on the recording stand-in engine of tests/test_point_rollout_scenes_cpu.py."""
 import ctypes as C
 import os
@@ -70,14 +70,14 @@ def test_unknown_bits_and_null_objects_are_refused_without_a_device():
 
 # ------------------------------------------------------------------ 2. the four-section layout, as a host program
 def _build(tmp, extra=("-O2",)):
-    out = str(tmp / "batch_table_layout_sv_host")
+    out = str(tmp / "batch_table_layout_host")
     subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + list(extra) +
-                          [os.path.join(HERE, "native", "batch_table_layout_sv_host.cpp"), "-o", out])
+                          [os.path.join(HERE, "native", "batch_table_layout_host.cpp"), "-o", out])
     return out
 
 
 def _run(prog, env=None):
-    r = subprocess.run([prog], capture_output=True, text=True, timeout=300, env=env)
+    r = subprocess.run([prog, "sv"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-2000:])
     m = re.fullmatch(r"(\d+) checks, 0 failures\n", r.stdout)
     assert m and int(m.group(1)) > 10000, r.stdout

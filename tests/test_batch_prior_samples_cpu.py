@@ -1,6 +1,6 @@
 """Batched command and lockstep episodes of point_env planners with prior samples (M3_BATCH_SECTION_POINT_PRIORS,
 M3_EPISODES_PRIORS), the parts that need no GPU: the defines and what the library says to them without a
-device, the five-section layout of the argument table as a host program (tests/native/batch_table_layout_pr_host.cpp, once plain
+device, the five-section layout of the argument table as a host program (tests/native/batch_table_layout_host.cpp in its mode `pr`, once plain
 and once under -fsanitize=address,undefined), and the Python layer's rules."""
 import ctypes as C
 import os
@@ -51,14 +51,14 @@ def test_the_defines_and_the_bits_without_a_device():
 
 # ------------------------------------------------------------------ 2. the five-section layout, as a host program
 def _build(tmp, extra=("-O2",)):
-    out = str(tmp / "batch_table_layout_pr_host")
+    out = str(tmp / "batch_table_layout_host")
     subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + list(extra) +
-                          [os.path.join(HERE, "native", "batch_table_layout_pr_host.cpp"), "-o", out])
+                          [os.path.join(HERE, "native", "batch_table_layout_host.cpp"), "-o", out])
     return out
 
 
 def _run(prog):
-    r = subprocess.run([prog], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([prog, "pr"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-2000:])
     m = re.fullmatch(r"(\d+) checks, 0 failures\n", r.stdout)
     assert m and int(m.group(1)) > 10000, r.stdout
