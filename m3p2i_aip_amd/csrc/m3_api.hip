@@ -39,6 +39,12 @@ static int fail(m3_handle* h, int code, const char* msg) {
     return code;
 }
 
+// what the update plans of a handle are decided from (update_plan.hpp)
+static UpdatePlanInput update_plan_input(const m3_handle* h, bool fused, bool rollout_minima) {
+    const m3_config& c = h->cfg;
+    return {h->protocol, c.K_local, c.K_global, c.T, c.nu, c.multi_modal != 0, c.mode_simple != 0, fused, h->five_launches, rollout_minima};
+}
+
 // ---- ownership (owned_blocks.hpp): the ledger's release function bound to HIP -- the one place that frees -- and one helper
 // per kind, the only places that allocate: allocate, adopt into the object's ledger, write the object's view ----
 void m3_release_block(BlockKind kind, void* p) {
@@ -242,9 +248,8 @@ extern "C" int m3_create(const m3_config* c, m3_handle** out) {
     if (!h) return fail(nullptr, M3_ERR_HIP, "m3_create: out of host memory");
     h->cfg = *c;
     h->cov_active = c->update_cov && single_halton && !c->sim_only;   // (elsewhere the reference ignores the flag)
-    h->regen = c->shard_mix && c->K_local != c->K_global && c->multi_modal && !c->mode_simple;
-    h->regen_fast = h->regen && c->shard_mix >= 2;
-    h->p3 = h->regen && c->shard_mix == 3;   // ... and O(K_local) work after the gather + a second small exchange
+    h->protocol = update_protocol(c->shard_mix, c->K_local, c->K_global, c->multi_modal, c->mode_simple);
+    const UpdateAlloc ua = update_alloc(update_plan_input(h, false, false));   // what the handle's update plans need
     hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) {
         g_create_err = std::string("hipSetDevice: ") + hipGetErrorString(e);
@@ -275,7 +280,7 @@ extern "C" int m3_create(const m3_config* c, m3_handle** out) {
     A(M3_BUF_STATES, T * Kl * 4 * f);
     A(M3_BUF_ACTIONS, T * Kl * nu * f);
     A(M3_BUF_COST_HORIZON, T * Kl * f);
-    if (!h->regen) A(M3_BUF_TRAJ_COST, Kl * f);   // (regen: the costs are the head of the record)
+    if (!update_costs_head_record(h->protocol)) A(M3_BUF_TRAJ_COST, Kl * f);
     A(M3_BUF_TRAJ_COST_ALL, Kg * f);
     A(M3_BUF_WEIGHTS, Kg * f);
     A(M3_BUF_WEIGHTS_1, (Kg / 2) * f);
@@ -284,7 +289,7 @@ extern "C" int m3_create(const m3_config* c, m3_handle** out) {
     A(M3_BUF_TOP_IDX, M3_TOPK * sizeof(int));
     A(M3_BUF_TOP_TRAJS, M3_TOPK * T * 2 * f);
     A(M3_BUF_REDUCE, (long long)reduce_length((int)T, (int)nu) * f);
-    if (!h->regen) A(M3_BUF_NOISE, T * Kl * nu * f);
+    if (!ua.noise_all) A(M3_BUF_NOISE, T * Kl * nu * f);
     A(M3_BUF_PENDING_FORCE, 4 * Kl * f);
     A(M3_BUF_INFO, sizeof(m3_info));
     A(M3_BUF_COV, 2 * nu * f);
@@ -299,14 +304,14 @@ extern "C" int m3_create(const m3_config* c, m3_handle** out) {
         if (own_device(h->mem, h->noise_mats, (size_t)(2 * nu * nu * f)) != hipSuccess ||
             hipMemcpy(h->noise_mats, mats, (size_t)(2 * nu * nu * f), hipMemcpyHostToDevice) != hipSuccess) rc = M3_ERR_HIP;
     }
-    if (h->regen) {
+    if (ua.noise_all) {   // (the record protocols)
         const long long rl = regen_record_length((int)Kl, (int)T);
         A(M3_BUF_RECORD, rl * f);
         A(M3_BUF_RECORDS_ALL, (Kg / Kl) * rl * f);
         if (rc == M3_OK && own_device(h->mem, h->noise_all, (size_t)(T * Kg * nu * f)) != hipSuccess) rc = M3_ERR_HIP;
         if (rc == M3_OK && hipMemsetAsync(h->noise_all, 0, (size_t)(T * Kg * nu * f), h->stream) != hipSuccess) rc = M3_ERR_HIP;
         if (rc == M3_OK && own_device(h->mem, h->local_top_idx, M3_TOPK * sizeof(int)) != hipSuccess) rc = M3_ERR_HIP;
-        if (h->p3) {
+        if (ua.record_b) {
             A(M3_BUF_RECORD_B, (long long)recb_length((int)T, (int)nu) * f);
             A(M3_BUF_RECORDS_B_ALL, (Kg / Kl) * (long long)recb_length((int)T, (int)nu) * f);
         }
@@ -315,7 +320,7 @@ extern "C" int m3_create(const m3_config* c, m3_handle** out) {
             h->buf[M3_BUF_NOISE] = h->noise_all + (size_t)(c->k_offset / Kl) * T * Kl * nu; h->nbytes[M3_BUF_NOISE] = T * Kl * nu * f;
             h->buf[M3_BUF_NOISE_ALL] = h->noise_all; h->nbytes[M3_BUF_NOISE_ALL] = T * Kg * nu * f;
         }
-    } else if (c->shard_mix && Kl != Kg) {
+    } else if (ua.record) {
         A(M3_BUF_RECORD, (long long)record_length((int)T, (int)nu) * f);
         A(M3_BUF_RECORDS_ALL, (Kg / Kl) * (long long)record_length((int)T, (int)nu) * f);
     }
@@ -323,11 +328,9 @@ extern "C" int m3_create(const m3_config* c, m3_handle** out) {
     if (rc == M3_OK && own_device(h->mem, h->topk_cand, (size_t)topk_workgroups((int)Kg) * M3_TOPK * sizeof(VI)) != hipSuccess) rc = M3_ERR_HIP;
     if (rc == M3_OK && own_device(h->mem, h->part_min, (size_t)mins_workgroups((int)Kg) * 3 * f) != hipSuccess) rc = M3_ERR_HIP;
     if (rc == M3_OK && own_device(h->mem, h->lad, (size_t)ladder_workgroups((int)Kg) * 96 * 3 * f) != hipSuccess) rc = M3_ERR_HIP;
-    // the three-launch update of an unsharded multi-modal handle beyond k_update_small's range (update.hip: k_ladder_search)
-    const bool fused_large = Kl == Kg && c->multi_modal && !c->mode_simple && Kg > 4096 && Kg <= 131072 && T * nu <= 2048;
-    if (rc == M3_OK && own_device(h->mem, h->wpart, (size_t)((h->regen || fused_large) ? std::max(wsum_chunks((int)Kg), regen_chunks((int)Kg)) : wsum_chunks((int)Kl)) * 3 * T * nu * f) != hipSuccess) rc = M3_ERR_HIP;
-    if (rc == M3_OK && own_device(h->mem, h->apart, (size_t)(16 + std::max(apply_workgroups((int)Kg), (h->regen || fused_large) ? regen_chunks((int)Kg) : 0) * 8) * f) != hipSuccess) rc = M3_ERR_HIP;
-    if (rc == M3_OK && fused_large) {
+    if (rc == M3_OK && own_device(h->mem, h->wpart, (size_t)(ua.partials_all ? std::max(wsum_chunks((int)Kg), regen_chunks((int)Kg)) : wsum_chunks((int)Kl)) * 3 * T * nu * f) != hipSuccess) rc = M3_ERR_HIP;
+    if (rc == M3_OK && own_device(h->mem, h->apart, (size_t)(16 + std::max(apply_workgroups((int)Kg), ua.partials_all ? regen_chunks((int)Kg) : 0) * 8) * f) != hipSuccess) rc = M3_ERR_HIP;
+    if (rc == M3_OK && ua.large_form) {   // the three-launch form (update.hip: k_ladder_search)
         const size_t nl = (size_t)ladder_workgroups((int)Kg);
         if (own_device(h->mem, h->wave_min, (size_t)Kl * 3 * f) != hipSuccess) rc = M3_ERR_HIP;      // (one row per rollout workgroup: <= K_local with one lane per wavefront)
         if (rc == M3_OK && own_device(h->mem, h->lflag, nl * sizeof(int)) != hipSuccess) rc = M3_ERR_HIP;
@@ -537,9 +540,10 @@ static int refresh_wave_order(m3_handle* h) {
         // the sort's own storage: for the largest range any block of this handle is sorted in (each mode's part of its own
         // block; of every shard's block where the handle holds them all) -- the configuration fixes them, so sized once
         size_t temp = 0;
-        const int nb = h->regen ? c.K_global / c.K_local : 1;
+        const bool all = update_noise_of_all_ranks(h->protocol);
+        const int nb = all ? c.K_global / c.K_local : 1;
         for (int r = 0; r < nb; ++r) {
-            const int half = block_half(c, h->regen ? r * c.K_local : c.k_offset);
+            const int half = block_half(c, all ? r * c.K_local : c.k_offset);
             temp = std::max(temp, std::max(wave_order_temp_bytes(half), wave_order_temp_bytes(c.K_local - half)));
         }
         h->order_temp_bytes = temp;
@@ -549,7 +553,7 @@ static int refresh_wave_order(m3_handle* h) {
         HIPCHK(h, own_device(h->mem, h->noise_sorted, sizeof(float) * (size_t)c.T * c.K_local * c.nu));
         g.keep = true;
     }
-    if (relabel && h->regen) {
+    if (relabel && update_noise_of_all_ranks(h->protocol)) {
         // every rank holds every shard's noise block (the other ranks' actions are re-generated from
         // them): relabel each block exactly as its owner does -- the same deterministic procedure on the
         // same inputs (noise table, world) -- this rank's own block LAST, so that h->order ends up as its
@@ -631,14 +635,14 @@ static int upload_noise(m3_handle* h, const float* delta, long long n_rows, floa
 extern "C" int m3_set_noise(m3_handle* h, const float* delta, int on_device) {
     if (!h) return M3_ERR_BAD_ARG;
     if (h->cfg.sim_only) return fail(h, M3_ERR_STATE, "m3_set_noise: handle was created sim_only");
-    if (h->regen) return fail(h, M3_ERR_STATE, "m3_set_noise: a one-collective multi-modal shard needs the noise rows of ALL "
+    if (update_noise_of_all_ranks(h->protocol)) return fail(h, M3_ERR_STATE, "m3_set_noise: a one-collective multi-modal shard needs the noise rows of ALL "
                                                "K_global samples (m3_set_noise_global)");
     return upload_noise(h, delta, h->cfg.K_local, (float*)h->buf[M3_BUF_NOISE], on_device, "m3_set_noise");
 }
 
 extern "C" int m3_set_noise_global(m3_handle* h, const float* delta_all, int on_device) {
     if (!h) return M3_ERR_BAD_ARG;
-    if (!h->regen) return fail(h, M3_ERR_STATE, "m3_set_noise_global: only for one-collective multi-modal shards "
+    if (!update_noise_of_all_ranks(h->protocol)) return fail(h, M3_ERR_STATE, "m3_set_noise_global: only for one-collective multi-modal shards "
                                                 "(cfg.shard_mix with multi_modal, K_local < K_global)");
     return upload_noise(h, delta_all, h->cfg.K_global, h->noise_all, on_device, "m3_set_noise_global");
 }
@@ -673,7 +677,7 @@ static int upload_knots(m3_handle* h, const float* knots, long long n_rows, floa
 extern "C" int m3_set_noise_knots(m3_handle* h, const float* knots, int n_knots, int degree, float smoothing,
                                   int on_device) {
     if (!h) return M3_ERR_BAD_ARG;
-    if (h->regen) return fail(h, M3_ERR_STATE, "m3_set_noise_knots: a one-collective multi-modal shard needs the knots of ALL "
+    if (update_noise_of_all_ranks(h->protocol)) return fail(h, M3_ERR_STATE, "m3_set_noise_knots: a one-collective multi-modal shard needs the knots of ALL "
                                                "K_global samples (m3_set_noise_knots_global)");
     return upload_knots(h, knots, h->cfg.K_local, (float*)h->buf[M3_BUF_NOISE], n_knots, degree, smoothing, on_device);
 }
@@ -681,7 +685,7 @@ extern "C" int m3_set_noise_knots(m3_handle* h, const float* knots, int n_knots,
 extern "C" int m3_set_noise_knots_global(m3_handle* h, const float* knots_all, int n_knots, int degree, float smoothing,
                                          int on_device) {
     if (!h) return M3_ERR_BAD_ARG;
-    if (!h->regen) return fail(h, M3_ERR_STATE, "m3_set_noise_knots_global: only for one-collective multi-modal shards");
+    if (!update_noise_of_all_ranks(h->protocol)) return fail(h, M3_ERR_STATE, "m3_set_noise_knots_global: only for one-collective multi-modal shards");
     return upload_knots(h, knots_all, h->cfg.K_global, h->noise_all, n_knots, degree, smoothing, on_device);
 }
 
@@ -727,8 +731,9 @@ extern "C" int m3_set_noise_halton_scrambled(m3_handle* h, int n_knots, int degr
             const std::vector<int> pj = faure_permutation(primes[j]);
             perm.insert(perm.end(), pj.begin(), pj.end());
         }
-    const long long rows = h->regen ? c.K_global : c.K_local;
-    const int k0 = h->regen ? 0 : c.k_offset;
+    const bool all = update_noise_of_all_ranks(h->protocol);
+    const long long rows = all ? c.K_global : c.K_local;
+    const int k0 = all ? 0 : c.k_offset;
     ScopedBlock<float> knots_blk(h->mem);
     ScopedBlock<int> tab_blk(h->mem);   // primes | perm offsets | permutations
     const size_t ntab = (size_t)ncol + perm_off.size() + perm.size();
@@ -745,7 +750,7 @@ extern "C" int m3_set_noise_halton_scrambled(m3_handle* h, int n_knots, int degr
         const bool sc = scramble != M3_HALTON_PLAIN;
         launch_halton_knots(knots, k0, (int)rows, ncol, tab, sc ? tab + 2 * ncol : nullptr, sc ? tab + ncol : nullptr, h->stream);
         // knots [rows][nu][n_knots] == [rows][ncol]: column j * n_knots + q is knot q of control dimension j
-        rc = upload_knots(h, knots, rows, h->regen ? h->noise_all : (float*)h->buf[M3_BUF_NOISE], n_knots, degree, smoothing, 1);
+        rc = upload_knots(h, knots, rows, all ? h->noise_all : (float*)h->buf[M3_BUF_NOISE], n_knots, degree, smoothing, 1);
     }
     (void)hipStreamSynchronize(h->stream);     // (also keeps `host` alive until the copy is done; then the two blocks go)
     if (rc != M3_OK && h->err.empty()) h->err = "m3_set_noise_halton failed";
@@ -761,7 +766,7 @@ extern "C" int m3_sample_noise(m3_handle* h) {
     const m3_config& c = h->cfg;
     if (c.sim_only || !(c.sampling_random || c.mode_simple))
         return fail(h, M3_ERR_STATE, "m3_sample_noise: the handle has a noise table (sampling_random == 0)");
-    if (h->regen) return fail(h, M3_ERR_STATE, "m3_sample_noise: not on a one-collective multi-modal shard");
+    if (update_noise_of_all_ranks(h->protocol)) return fail(h, M3_ERR_STATE, "m3_sample_noise: not on a one-collective multi-modal shard");
     RolloutArgs a;
     std::memset(&a, 0, sizeof(a));
     a.Kg = c.K_global; a.Kl = c.K_local; a.k0 = c.k_offset; a.T = c.T; a.nu = c.nu;
@@ -1710,7 +1715,8 @@ static void fill_update_args(m3_handle* h, UpdateArgs& a) {
     a.lflag = h->lflag;
     a.n_chunk = wsum_chunks(c.K_local);
     a.n_lad = ladder_workgroups(c.K_global);
-    a.Jall = (const float*)h->buf[M3_BUF_TRAJ_COST_ALL];
+    // (unsharded: the local costs ARE the global costs, no copy)
+    a.Jall = (const float*)h->buf[c.K_local == c.K_global ? M3_BUF_TRAJ_COST : M3_BUF_TRAJ_COST_ALL];
     a.w = (float*)h->buf[M3_BUF_WEIGHTS];
     a.w1 = (float*)h->buf[M3_BUF_WEIGHTS_1];
     a.w2 = (float*)h->buf[M3_BUF_WEIGHTS_2];
@@ -1742,7 +1748,7 @@ static void fill_update_args(m3_handle* h, UpdateArgs& a) {
     a.regen = 0;
     a.Jout = nullptr;
     a.Kls = c.K_local;
-    a.rec_len = h->regen ? regen_record_length(c.K_local, c.T) : record_length(c.T, c.nu);
+    a.rec_len = m3_record_len(h);
     if (h->records_src) a.rec_len = h->records_stride;   // (the p2p block's slots are padded to 16 bytes; rec_len is only ever a stride)
     a.noise_all = h->noise_all;
     for (int j = 0; j < c.nu; ++j) {
@@ -1754,181 +1760,10 @@ static void fill_update_args(m3_handle* h, UpdateArgs& a) {
     a.gripper_cmd = h->gripper_cmd;
 }
 
-static bool mix_mode(const m3_handle* h) { return h->cfg.shard_mix && h->cfg.K_local != h->cfg.K_global && !h->regen; }
-
-// fuse: m3_command on an unsharded handle lets k_wsum's last workgroup do k_finalize's work
-static bool can_fuse_finalize(const m3_handle* h) {
-    const m3_config& c = h->cfg;
-    return c.K_local == c.K_global && (long long)c.T * c.nu <= 2048;  // plan staged in 8 KB of LDS
-}
-
-// the arguments update_impl launches with (fuse: m3_command's update, the finalize fused in -- also what m3_batch_command
-// launches for every handle and batch_refusal checks)
+// the arguments of a command's update, the finalize fused in or not (also what m3_batch_command launches for every handle)
 static void fill_update_impl_args(m3_handle* h, UpdateArgs& a, bool fuse) {
     fill_update_args(h, a);
     a.fuse_finalize = fuse ? 1 : 0;
-    if (h->cfg.K_local == h->cfg.K_global)  // unsharded: the local costs ARE the global costs (no copy)
-        a.Jall = (const float*)h->buf[M3_BUF_TRAJ_COST];
-}
-
-static int update_impl(m3_handle* h, bool fuse) {
-    const m3_config& c = h->cfg;
-    if (c.sim_only) return fail(h, M3_ERR_STATE, "m3_update: handle was created sim_only");
-    UpdateArgs a;
-    fill_update_impl_args(h, a, fuse);
-    if (h->regen) {
-        // one-collective multi-modal sharding, phase before the all-gather: the rollout left the shard's
-        // costs at the head of the record; add the shard's own top-k (costs, global indices, trajectories)
-        float* rec = (float*)h->buf[M3_BUF_RECORD];
-        a.Kg = c.K_local;                       // the selection runs over the LOCAL costs ...
-        a.Jall = rec;
-        a.kbase = c.k_offset;                   // ... and reports global indices
-        a.n_cand = c.K_local <= 8192 ? 1 : topk_workgroups(c.K_local);
-        a.top_idx = h->local_top_idx;
-        a.rec_topj = rec + regen_off_topj(c.K_local);
-        a.rec_topi = rec + regen_off_topi(c.K_local);
-        a.top_dst = rec + regen_off_trajs(c.K_local);
-        if (h->regen_fast) {   // ... and its minima + ladder table
-            a.fast = 1;
-            a.rec_mins = rec + regen_off_mins(c.K_local, c.T);
-            a.rec_table = rec + regen_off_table(c.K_local, c.T);
-        }
-        launch_local_topk(a, h->stream);
-        HIPCHK(h, hipGetLastError());
-        if (h->timing) HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-        return M3_OK;
-    }
-    if (mix_mode(h)) {
-        // one-collective sharding: softmin over the LOCAL shard into this rank's record
-        float* rec = (float*)h->buf[M3_BUF_RECORD];
-        a.record = rec;
-        a.rec_topj = rec + REC_TOPJ;
-        a.rec_topi = rec + REC_TOPI;
-        a.reduce = rec + REC_HDR;
-        a.top_dst = a.reduce + reduce_off_top(c.T, c.nu);
-        a.n_cand = topk_workgroups(c.K_local);
-        UpdateArgs aw = a;  // what k_weights and top-k stage A see
-        aw.Kg = c.K_local;
-        aw.Jall = (const float*)h->buf[M3_BUF_TRAJ_COST];
-        aw.w = a.w + c.k_offset;
-        aw.kbase = c.k_offset;
-        if (update_small_applies(aw)) {
-            launch_update_small(aw, h->stream);   // one launch: softmin + sums of the local shard
-        } else {
-            launch_weights(aw, h->stream);
-            launch_wsum(a, h->stream);
-        }
-        HIPCHK(h, hipGetLastError());
-        if (h->timing) HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-        return M3_OK;
-    }
-    if (update_small_applies(a)) {  // K <= 4096: one launch (update.hip, k_update_small)
-        launch_update_small(a, h->stream);
-        HIPCHK(h, hipGetLastError());
-        if (h->timing) HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-        return M3_OK;
-    }
-    if (fuse && h->lflag && c.multi_modal && !c.mode_simple && !h->five_launches) {   // (m3_set_update_launches(h, 5): the round-3 path)
-        // three launches (update.hip: k_ladder_search): the minima are the rows the rollout's workgroups left behind
-        // when the costs are this command's rollout's, k_mins' rows otherwise (costs written by the caller)
-        if (h->use_wave_min) { a.part_min = h->wave_min; a.n_mins = h->wave_min_rows; }
-        else launch_mins(a, h->stream);
-        a.epoch = ++h->lad_epoch;
-        launch_ladder_search(a, h->stream);
-        launch_fused_large(a, h->stream);
-        HIPCHK(h, hipGetLastError());
-        if (h->timing) HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-        return M3_OK;
-    }
-    // (minima + beta ladder for the multi-modal search) -> weights (+ top-k stage A as extra
-    // workgroups) -> weighted sums (+ top-k stage B as an extra workgroup when K > 4096)
-    if (c.multi_modal && !c.mode_simple) {
-        launch_mins(a, h->stream);
-        launch_ladder(a, h->stream);
-    }
-    launch_weights(a, h->stream);
-    launch_wsum(a, h->stream);
-    HIPCHK(h, hipGetLastError());
-    if (h->timing) HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-    return M3_OK;
-}
-
-extern "C" int m3_update(m3_handle* h) {
-    if (!h) return M3_ERR_BAD_ARG;
-    return update_impl(h, false);
-}
-
-// one-collective multi-modal sharding, phase after the all-gather: the whole update on all K_global
-// samples -- the unsharded kernels, with the weighted sums re-generating the actions (k_wsum<REGEN>)
-static int regen_finalize(m3_handle* h) {
-    const m3_config& c = h->cfg;
-    UpdateArgs a;
-    fill_update_args(h, a);
-    a.regen = 1;
-    if (h->regen_fast) {
-        // shard_mix = 2: k_search mixes the shards' ladder tables, k_regen_part / k_regen_done do the rest
-        if ((long long)c.T * c.nu > 2048) return fail(h, M3_ERR_UNSUPPORTED, "m3_finalize: shard_mix = 2 needs T * nu <= 2048");
-        a.fast = 1;
-        a.Kl = c.K_global; a.k0 = 0;
-        a.n_chunk = wsum_chunks(c.K_global);
-        a.top_dst = a.top_trajs;
-        a.fuse_finalize = 1;
-        launch_regen_fast(a, h->stream);
-        HIPCHK(h, hipGetLastError());
-        return M3_OK;
-    }
-    a.Jout = (float*)h->buf[M3_BUF_TRAJ_COST_ALL];   // k_mins compacts the records' costs into it
-    a.Kl = c.K_global; a.k0 = 0;           // the launches cover every sample
-    a.n_chunk = wsum_chunks(c.K_global);
-    a.top_dst = a.top_trajs;               // rows come from the gathered records (topk_finish)
-    const bool fuse = (long long)c.T * c.nu <= 2048;
-    a.fuse_finalize = fuse ? 1 : 0;
-    launch_mins(a, h->stream);
-    launch_ladder(a, h->stream);
-    launch_weights(a, h->stream);
-    launch_wsum(a, h->stream);
-    if (!fuse) launch_finalize(a, h->stream);
-    HIPCHK(h, hipGetLastError());
-    return M3_OK;
-}
-
-// shard_mix = 3, between the two exchanges (update.hip: k_p3_done's comment): searches on the mixed tables, then
-// weights and weighted sums of this rank's OWN samples into its second record
-extern "C" int m3_update_b(m3_handle* h) {
-    if (!h) return M3_ERR_BAD_ARG;
-    if (!h->p3) return fail(h, M3_ERR_STATE, "m3_update_b: only for cfg.shard_mix = 3 handles");
-    const m3_config& c = h->cfg;
-    float* rec = (float*)h->buf[M3_BUF_RECORD];
-    float* recb = (float*)h->buf[M3_BUF_RECORD_B];
-    {   // searches (all ranks' tables; the gathered costs only if one leaves its ladder) + the global top-k
-        UpdateArgs a;
-        fill_update_args(h, a);
-        a.regen = 1; a.fast = 1;
-        a.Kl = c.K_global; a.k0 = 0;
-        a.top_dst = a.top_trajs;
-        launch_p3_search(a, h->stream);
-    }
-    {   // weights of the local samples (global minima / eta / beta from the search)
-        UpdateArgs a;
-        fill_update_args(h, a);
-        a.Kg = c.K_local;
-        a.Jall = rec;
-        a.kbase = c.k_offset;
-        a.w = (float*)h->buf[M3_BUF_WEIGHTS] + c.k_offset;
-        a.w1 = (float*)h->buf[M3_BUF_WEIGHTS_1] + c.k_offset;
-        a.rec_b = recb;
-        launch_p3_local_weights(a, h->stream);
-    }
-    {   // their weighted action sums + the rows of the local best samples
-        UpdateArgs a;
-        fill_update_args(h, a);
-        a.reduce = recb + RECB_HDR;
-        a.n_cand = 0;
-        a.fuse_finalize = 0;
-        launch_wsum(a, h->stream);
-    }
-    HIPCHK(h, hipGetLastError());
-    return M3_OK;
 }
 
 // MPPIConfig.update_cov: the covariance update that follows the mean update (mppi.py:508-516)
@@ -1944,12 +1779,117 @@ static int after_finalize(m3_handle* h) {
 
 // the end of a command whose finalize has been enqueued (m3_finalize, m3_update_finalize, m3_batch_command): the covariance
 // step, the end-of-command timing event (timed: not in a batch), the call count
-static int finish_command(m3_handle* h, bool timed) {
-    const int rc = after_finalize(h);
+static int finish_command(m3_handle* h, bool timed, bool covariance = true) {
+    const int rc = covariance ? after_finalize(h) : M3_OK;
     if (rc != M3_OK) return rc;
     if (timed && h->timing) HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
     h->calls += 1;
     return M3_OK;
+}
+
+// ---- what a step of an update plan sees and where it writes (update_plan.hpp: UpdateView, UpdateDest) ----
+// the launch sees the local shard as if it were all there is, and reports global indices
+static void view_local_shard(const m3_handle* h, UpdateArgs& a) {
+    const m3_config& c = h->cfg;
+    a.Kg = c.K_local;
+    a.kbase = c.k_offset;
+    a.Jall = (const float*)h->buf[M3_BUF_TRAJ_COST];   // (the record protocols: the head of the record)
+    a.w += c.k_offset; a.w1 += c.k_offset;
+}
+// the launch covers every sample of every rank
+static void view_all_samples(const m3_handle* h, UpdateArgs& a) {
+    a.Kl = h->cfg.K_global; a.k0 = 0;
+    a.n_chunk = wsum_chunks(h->cfg.K_global);
+    a.top_dst = a.top_trajs;               // rows come from the gathered records (topk_finish)
+}
+// the step writes into this rank's record (in its protocol's layout) or second record
+static void dest_record(const m3_handle* h, const UpdateStep& st, UpdateArgs& a) {
+    const m3_config& c = h->cfg;
+    float* rec = (float*)h->buf[M3_BUF_RECORD];
+    if (st.dest == UPDATE_DEST_RECORD_B) {
+        float* recb = (float*)h->buf[M3_BUF_RECORD_B];
+        if (st.launch == UPDATE_LAUNCH_WSUM) { a.reduce = recb + RECB_HDR; a.n_cand = 0; }   // the sums + the rows of the local best samples
+        else a.rec_b = recb;                                                                  // the header
+    } else if (update_mix_record(h->protocol)) {
+        a.record = rec;
+        a.rec_topj = rec + REC_TOPJ;
+        a.rec_topi = rec + REC_TOPI;
+        a.reduce = rec + REC_HDR;
+        a.top_dst = a.reduce + reduce_off_top(c.T, c.nu);
+        a.n_cand = topk_workgroups(c.K_local);
+    } else {   // the shard's own top-k (costs, global indices, trajectories) behind its costs
+        a.n_cand = c.K_local <= 8192 ? 1 : topk_workgroups(c.K_local);
+        a.top_idx = h->local_top_idx;
+        a.rec_topj = rec + regen_off_topj(c.K_local);
+        a.rec_topi = rec + regen_off_topi(c.K_local);
+        a.top_dst = rec + regen_off_trajs(c.K_local);
+        if (st.fast) {   // ... and its minima + ladder table
+            a.rec_mins = rec + regen_off_mins(c.K_local, c.T);
+            a.rec_table = rec + regen_off_table(c.K_local, c.T);
+        }
+    }
+}
+
+// The one executor of the update plans: every step launches with freshly filled arguments, its view and its flags.
+static int run_update_plan(m3_handle* h, const UpdatePlan& p) {
+    bool checked = false;
+    for (int i = 0; i < p.n; ++i) {
+        const UpdateStep& st = p.step[i];
+        UpdateArgs a;
+        fill_update_impl_args(h, a, st.fuse_finalize);
+        a.regen = st.regen ? 1 : 0;
+        a.fast = st.fast ? 1 : 0;
+        if (st.view == UPDATE_VIEW_LOCAL) view_local_shard(h, a);
+        else if (st.view == UPDATE_VIEW_ALL) view_all_samples(h, a);
+        if (st.dest != UPDATE_DEST_BUFFERS) dest_record(h, st, a);
+        if (st.regen && !st.fast) a.Jout = (float*)h->buf[M3_BUF_TRAJ_COST_ALL];   // k_mins, the first reader of the gathered records, compacts their costs into it
+        if (st.rollout_minima) { a.part_min = h->wave_min; a.n_mins = h->wave_min_rows; }
+        switch (st.launch) {
+            case UPDATE_LAUNCH_MINS: launch_mins(a, h->stream); break;
+            case UPDATE_LAUNCH_LADDER: launch_ladder(a, h->stream); break;
+            case UPDATE_LAUNCH_WEIGHTS: launch_weights(a, h->stream); break;
+            case UPDATE_LAUNCH_WSUM: launch_wsum(a, h->stream); break;
+            case UPDATE_LAUNCH_FINALIZE: launch_finalize(a, h->stream); break;
+            case UPDATE_LAUNCH_SMALL: launch_update_small(a, h->stream); break;
+            case UPDATE_LAUNCH_LADDER_SEARCH: a.epoch = ++h->lad_epoch; launch_ladder_search(a, h->stream); break;
+            case UPDATE_LAUNCH_FUSED_LARGE: a.epoch = h->lad_epoch; launch_fused_large(a, h->stream); break;   // (the search's epoch)
+            case UPDATE_LAUNCH_LOCAL_TOPK: launch_local_topk(a, h->stream); break;
+            case UPDATE_LAUNCH_MIX: launch_mix(a, h->stream); break;
+            case UPDATE_LAUNCH_REGEN_FAST: launch_regen_fast(a, h->stream); break;
+            case UPDATE_LAUNCH_P3_SEARCH: launch_p3_search(a, h->stream); break;
+            case UPDATE_LAUNCH_P3_LOCAL_WEIGHTS: launch_p3_local_weights(a, h->stream); break;
+            case UPDATE_LAUNCH_P3_DONE: launch_p3_done(a, h->stream); break;
+        }
+        checked = st.ends_update;
+        if (st.ends_update) {
+            HIPCHK(h, hipGetLastError());
+            if (h->timing) HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
+        }
+    }
+    if (!checked) HIPCHK(h, hipGetLastError());
+    return p.ends_command ? finish_command(h, true, p.covariance) : M3_OK;
+}
+
+static int update_refused(m3_handle* h, UpdateRefusal r, bool from_command) {
+    return fail(h, update_refusal_is_state(r) ? M3_ERR_STATE : M3_ERR_UNSUPPORTED, update_refusal_text(r, from_command));
+}
+static int run_update_entry(m3_handle* h, UpdateEntry entry, bool rollout_minima) {
+    const UpdatePlan p = update_plan(update_plan_input(h, false, rollout_minima), entry);
+    if (p.refusal != UPDATE_REFUSAL_NONE) return update_refused(h, p.refusal, false);
+    if (h->cfg.sim_only && (entry == UPDATE_ENTRY_UPDATE || entry == UPDATE_ENTRY_UPDATE_FINALIZE))
+        return fail(h, M3_ERR_STATE, "m3_update: handle was created sim_only");
+    return run_update_plan(h, p);
+}
+
+extern "C" int m3_update(m3_handle* h) {
+    if (!h) return M3_ERR_BAD_ARG;
+    return run_update_entry(h, UPDATE_ENTRY_UPDATE, false);
+}
+
+// shard_mix = 3, between the two exchanges (update_sharded.hip: k_p3_done's comment)
+extern "C" int m3_update_b(m3_handle* h) {
+    if (!h) return M3_ERR_BAD_ARG;
+    return run_update_entry(h, UPDATE_ENTRY_UPDATE_B, false);
 }
 
 // ---- device-side exchange of the records (p2p.hip) -------------------------------------------------------------
@@ -1971,7 +1911,7 @@ static int p2p_alloc(m3_handle* h) {
         explicit DeviceGuard(int d) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; (void)hipSetDevice(d); }
         ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
     } guard(c.device);
-    if (!(c.shard_mix && c.K_local != c.K_global) || !h->buf[M3_BUF_RECORD])
+    if (!update_has_record(h->protocol) || !h->buf[M3_BUF_RECORD])
         return fail(h, M3_ERR_STATE, "m3_p2p: the handle has no record to exchange (needs cfg.shard_mix on a sharded handle)");
     const size_t rl = (size_t)m3_record_len(h), rlb = (size_t)m3_record_b_len(h);
     h->xb_bytes = P2P_HDR_BYTES + 2 * (size_t)p2p_ranks(h) * (((rl + 3) & ~(size_t)3) + ((rlb + 3) & ~(size_t)3)) * sizeof(float);
@@ -2112,7 +2052,7 @@ static void p2p_args(m3_handle* h, P2PArgs& a, int ch) {
 
 extern "C" int m3_p2p_put_ch(m3_handle* h, int ch) {
     if (!h) return M3_ERR_BAD_ARG;
-    if (ch != 0 && !(ch == 1 && h->p3)) return fail(h, M3_ERR_BAD_ARG, "m3_p2p_put: channel 1 exists on shard_mix = 3 handles only");
+    if (ch != 0 && !(ch == 1 && update_second_record(h->protocol))) return fail(h, M3_ERR_BAD_ARG, "m3_p2p_put: channel 1 exists on shard_mix = 3 handles only");
     if (!h->p2p_ready) return fail(h, M3_ERR_STATE, "m3_p2p_put: m3_p2p_connect first");
     h->p2p_seq[ch] += 1;
     P2PArgs a;
@@ -2124,7 +2064,7 @@ extern "C" int m3_p2p_put_ch(m3_handle* h, int ch) {
 
 extern "C" int m3_p2p_wait_ch(m3_handle* h, int ch) {
     if (!h) return M3_ERR_BAD_ARG;
-    if (ch != 0 && !(ch == 1 && h->p3)) return fail(h, M3_ERR_BAD_ARG, "m3_p2p_wait: channel 1 exists on shard_mix = 3 handles only");
+    if (ch != 0 && !(ch == 1 && update_second_record(h->protocol))) return fail(h, M3_ERR_BAD_ARG, "m3_p2p_wait: channel 1 exists on shard_mix = 3 handles only");
     if (!h->p2p_ready || h->p2p_seq[ch] == 0) return fail(h, M3_ERR_STATE, "m3_p2p_wait: no exchange in flight (m3_p2p_put first)");
     P2PArgs a;
     p2p_args(h, a, ch);
@@ -2140,7 +2080,7 @@ extern "C" int m3_p2p_put(m3_handle* h) { return m3_p2p_put_ch(h, 0); }
 extern "C" int m3_p2p_wait(m3_handle* h) { return m3_p2p_wait_ch(h, 0); }
 static int p2p_exchange_ch(m3_handle* h, int ch) {   // put + wait in one launch
     if (!h) return M3_ERR_BAD_ARG;
-    if (ch != 0 && !(ch == 1 && h->p3)) return fail(h, M3_ERR_BAD_ARG, "m3_p2p_exchange: channel 1 exists on shard_mix = 3 handles only");
+    if (ch != 0 && !(ch == 1 && update_second_record(h->protocol))) return fail(h, M3_ERR_BAD_ARG, "m3_p2p_exchange: channel 1 exists on shard_mix = 3 handles only");
     if (!h->p2p_ready) return fail(h, M3_ERR_STATE, "m3_p2p_exchange: m3_p2p_connect first");
     h->p2p_seq[ch] += 1;
     P2PArgs a;
@@ -2178,56 +2118,23 @@ extern "C" int m3_p2p_status(m3_handle* h, int* missing_rank, int* memory_kind) 
 extern "C" int m3_finalize(m3_handle* h) {
     if (!h) return M3_ERR_BAD_ARG;
     struct Consume { m3_handle* h; ~Consume() { h->records_src = nullptr; h->recb_src = nullptr; } } consume{h};   // one exchange, one finalize
-    if (h->p3) {
-        UpdateArgs a;
-        fill_update_args(h, a);
-        a.Kl = h->cfg.K_global; a.k0 = 0;      // (finalize_body: the top trajectories are already in place)
-        launch_p3_done(a, h->stream);
-        HIPCHK(h, hipGetLastError());
-        h->recb_src = nullptr;
-        if (h->timing) HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
-        h->calls += 1;
-        return M3_OK;
-    }
-    if (h->regen) {
-        const int rc = regen_finalize(h);
-        if (rc != M3_OK) return rc;
-        if (h->timing) HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
-        h->calls += 1;
-        return M3_OK;
-    }
-    UpdateArgs a;
-    fill_update_args(h, a);
-    if (mix_mode(h)) launch_mix(a, h->stream);  // records -> the REDUCE buffer an all-reduce would hold, + finalize
-    else launch_finalize(a, h->stream);
-    HIPCHK(h, hipGetLastError());
-    return finish_command(h, true);
+    return run_update_entry(h, UPDATE_ENTRY_FINALIZE, false);
 }
 
 extern "C" int m3_update_finalize(m3_handle* h) {
     if (!h) return M3_ERR_BAD_ARG;
-    if (h->cfg.K_local != h->cfg.K_global)
-        return fail(h, M3_ERR_STATE, "m3_update_finalize: sharded handle (m3_update, collectives, m3_finalize)");
-    if (!can_fuse_finalize(h)) {
-        const int rc = m3_update(h);
-        return rc != M3_OK ? rc : m3_finalize(h);
-    }
-    const int rc = update_impl(h, true);
-    return rc != M3_OK ? rc : finish_command(h, true);
+    return run_update_entry(h, UPDATE_ENTRY_UPDATE_FINALIZE, false);
 }
 
 extern "C" int m3_command(m3_handle* h, float* action_host) {
     if (!h) return M3_ERR_BAD_ARG;
     // a sharded handle needs the collective(s) between the phases: running update + finalize on the
     // local costs alone would return a plan built from zero / stale remote slices without an error
-    if (h->cfg.K_local != h->cfg.K_global)
-        return fail(h, M3_ERR_STATE, "m3_command: sharded handle (K_local != K_global): call m3_rollout, m3_update, "
-                                     "m3_finalize with the collective(s) in between (include/m3p2i_hip.h)");
+    if (const UpdateRefusal r = update_refusal(update_plan_input(h, false, false), UPDATE_ENTRY_UPDATE_FINALIZE)) return update_refused(h, r, true);
     int rc = m3_rollout(h);
     if (rc != M3_OK) return rc;
-    h->use_wave_min = h->wave_min != nullptr && h->wave_min_rows > 0;   // the costs the update reads are this rollout's
-    rc = m3_update_finalize(h);   // weights -> sums + (last workgroup) mean update / filter
-    h->use_wave_min = false;
+    // weights -> sums + (last workgroup) mean update / filter; the costs the update reads are this rollout's
+    rc = run_update_entry(h, UPDATE_ENTRY_UPDATE_FINALIZE, h->wave_min != nullptr && h->wave_min_rows > 0);
     if (rc != M3_OK) return rc;
     if (action_host) {
         HIPCHK(h, hipMemcpyAsync(action_host, plan_dst(h), plan_floats(h->cfg) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -2493,7 +2400,7 @@ static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code, int sec
     }
     fill_update_impl_args(h, u, true);
     code = M3_ERR_UNSUPPORTED;
-    if (!can_fuse_finalize(h) || !update_small_applies(u))
+    if (const UpdatePlanInput in = update_plan_input(h, true, false); !can_fuse_finalize(in) || !update_small_applies(in))
         return c.env_type == M3_ENV_PANDA
                    ? "its command does not take the one-launch update (nu = 9: K <= 4096, T * nu <= 2048)"
                    : "its command does not take the one-launch update (nu = 2: K <= 16384; multi-modal K <= 8192)";
@@ -2665,13 +2572,13 @@ extern "C" int m3_batch_command(m3_batch* b, m3_handle* const* hs, int n, float*
 
 static int ensure_sim(m3_handle* h);
 extern "C" int m3_record_b_len(const m3_handle* h) {
-    if (!h || !h->p3) return 0;
+    if (!h || !update_second_record(h->protocol)) return 0;
     return recb_length(h->cfg.T, h->cfg.nu);
 }
 
 extern "C" int m3_record_len(const m3_handle* h) {
     if (!h) return 0;
-    return h->regen ? regen_record_length(h->cfg.K_local, h->cfg.T) : record_length(h->cfg.T, h->cfg.nu);
+    return update_costs_head_record(h->protocol) ? regen_record_length(h->cfg.K_local, h->cfg.T) : record_length(h->cfg.T, h->cfg.nu);
 }
 
 extern "C" int m3_get_buffer(m3_handle* h, int which, void** p, long long* nbytes) {

@@ -13,6 +13,7 @@
 #include "panda_scene.hpp"
 #include "owned_blocks.hpp"
 #include "panda_variant.hpp"
+#include "update_plan.hpp"
 
 namespace m3 {
 
@@ -98,7 +99,7 @@ struct UpdateArgs {
     float* action_out;   // [T][nu]
     const int* p2p_err;  // device-side exchange attached: its sticky error word (a rank that never arrived: the records hold NaN)
     float* top_trajs;    // [M3_TOPK][T][2]
-    // shard_mix (one-collective sharding): k_weights / top-k see the LOCAL shard (Kg = Kl,
+    // shard_mix (one-collective sharding; which launch sees which view: update_plan.hpp): k_weights / top-k see the LOCAL shard (Kg = Kl,
     // Jall = local costs, w = weights + k0); kbase maps their sample numbers to global indices
     int kbase;           // global index of sample 0 of the costs k_weights sees (0 unless shard_mix)
     int half_g;          // global K/2 (mode split, pull preference)
@@ -113,7 +114,7 @@ struct UpdateArgs {
     // {J of the shard | its top-k} every rank runs the whole update on all K samples; the actions of
     // the other ranks' samples are RE-GENERATED from the replicated noise table and plan instead of
     // being communicated (a_k[t] is a function of the global sample index: mppi.py:381-416)
-    int regen;           // 1: the launch covers all K_global samples (Kl == Kg, k0 == 0 in this struct)
+    int regen;           // 1: the launch covers all K_global samples (Kl == Kg, k0 == 0 in this struct; UPDATE_VIEW_ALL of update_plan.hpp)
     int fast;            // shard_mix = 2: the records carry per-rank minima + ladder tables; the search mixes them
                          // instead of re-evaluating all K costs, and ONE kernel does weights + sums + finalize
     float* rec_mins;     // this rank's record: minima [4] and ladder table [LAD_N][3] (pre-gather launch)
@@ -326,8 +327,7 @@ hipError_t launch_wave_order(const float* noise, int Kl, int T, int nu, float s0
 void launch_gather_rows(const float* src, const int* order, float* dst, int Kl, int rows, hipStream_t s);
 void launch_weights(const UpdateArgs& a, hipStream_t s);
 void launch_wsum(const UpdateArgs& a, hipStream_t s);
-void launch_update_small(const UpdateArgs& a, hipStream_t s);
-bool update_small_applies(const UpdateArgs& a);
+void launch_update_small(const UpdateArgs& a, hipStream_t s);   // (whether it applies: update_plan.hpp, update_small_applies)
 void launch_finalize(const UpdateArgs& a, hipStream_t s);
 void launch_mix(const UpdateArgs& a, hipStream_t s);
 void launch_cov_update(const float* actions, const float* w, const float* mean, float* part, float* cov, int K, int T,
@@ -616,13 +616,11 @@ struct m3_handle {
     bool have_noise = false;
     bool cov_active = false;       // cfg.update_cov on a single-mode halton-spline planner (mppi.py:508-516)
     float* noise_mats = nullptr;   // device [2][nu][nu]: chol(noise_sigma) | noise_sigma^-1 (cfg.full_sigma)
-    bool regen = false;            // one-collective multi-modal sharding (UpdateArgs::regen)
-    bool regen_fast = false;       // ... with per-rank ladder tables in the records (cfg.shard_mix >= 2)
-    bool p3 = false;               // cfg.shard_mix == 3: O(K_local) work after the gather, second small exchange
+    m3::UpdateProtocol protocol = m3::UPDATE_UNSHARDED;   // how the ranks reach one plan (update_plan.hpp; m3_create, from cfg alone)
     const float* recb_src = nullptr;   // second records as exchanged by m3_p2p_exchange(h, 1) (else M3_BUF_RECORDS_B_ALL)
     int recb_stride = 0;
-    float* noise_all = nullptr;    // regen: [n_ranks][T][Kl][nu]; buf[M3_BUF_NOISE] aliases this rank's block
-    int* local_top_idx = nullptr;  // regen: top_idx of the local pre-gather selection (scratch)
+    float* noise_all = nullptr;    // update_noise_of_all_ranks: [n_ranks][T][Kl][nu]; buf[M3_BUF_NOISE] aliases this rank's block
+    int* local_top_idx = nullptr;  // ... and top_idx of the local pre-gather selection (scratch)
     unsigned calls = 0;
     int lanes_override = 0;  // 0 = automatic (rollout_lanes_for)
     int point_form = -1;          // m3_set_point_rollout_form: 0, 1, -1 = automatic
@@ -637,7 +635,7 @@ struct m3_handle {
     int panda_reach_busy = 0;
     int panda_lps_used = 0;           // the form of the last panda rollout (m3_panda_lanes_per_sample_used)
     int panda_lps = 0;       // 0 = automatic (rollout_panda.hip: panda_lps_for), 1, 16
-    // device buffers (views; regen: three of buf[] alias other blocks and are no ledger entries)
+    // device buffers (views; the record protocols: three of buf[] alias other blocks and are no ledger entries)
     void* buf[M3_BUF_COUNT] = {};
     long long nbytes[M3_BUF_COUNT] = {};
     float* world0_dev = nullptr;
@@ -648,10 +646,9 @@ struct m3_handle {
     float* wpart = nullptr;
     float* apart = nullptr;  // + 16 floats of SearchOut at the front
     int* wcount = nullptr;
-    // unsharded multi-modal update with K > 8192 in three launches (update.hip: k_ladder_search)
+    // the three-launch form of the unsharded multi-modal update (update_plan.hpp: update_large_range; update.hip: k_ladder_search)
     float* wave_min = nullptr;     // [rollout workgroups][3] minima left by the rollout (wave_min.hpp)
     int wave_min_rows = 0;         // rows the last rollout wrote
-    bool use_wave_min = false;     // inside m3_command: the costs are the rollout's
     int* lflag = nullptr;
     int lad_epoch = 0;
     bool five_launches = false;    // m3_set_update_launches(h, 5)

@@ -1,11 +1,13 @@
 // update.hip -- importance-weight update of MPPI / M3P2I (gfx950): the general multi-launch path.  (update_small.hip:
 // k_update_small; update_sharded.hip: k_local_topk, k_regen_part / k_regen_done, k_p3_done, k_mix; update_common.hpp: the device
-// code they share.)
+// code they share.)  Which of these a call launches, in what order and on which view of the samples, is update_plan.hpp's
+// decision (the size ranges and protocols stated there once); m3_api.hip's run_update_plan walks the plan.
 //
 //   k_update_small : the WHOLE update (weights, beta search, sums, top-k, mean update / filter) in one
 //               launch for the sizes of the reference's configs: K <= 4096 per GPU (C2, C3, C4, a
-//               shard_mix rank), K <= 16384 for single-mode point_env (the north-star size).  The
-//               kernels below are the general path: larger K and the sharded phases.
+//               shard_mix rank), K <= 16384 for single-mode point_env (the north-star size; the ranges:
+//               update_plan.hpp, update_small_applies).  The kernels below are the general path: larger K
+//               and the sharded phases.
 //   k_mins    : (multi-modal only) per-workgroup minima of the trajectory costs
 //   k_ladder  : (multi-modal only) eta(beta) for the whole ladder of betas the reference's
 //               on-the-fly search can visit, in ONE chip-wide pass

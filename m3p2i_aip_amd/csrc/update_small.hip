@@ -23,6 +23,7 @@ template <int NU, bool MULTI, int JR, int WT = 256>
 __global__ __launch_bounds__(WT) void k_update_small(const UpdateArgs a) {
 #include "update_small_body.inc"
 }
+// Whether a command takes this kernel is the update plan's decision (update_plan.hpp: update_small_applies, the size ranges).
 // The instance of a's command: template arguments (JR: register rows of 256 costs), workgroup width and top-k workgroups.
 // n_cand is what the launched copy of the arguments holds.
 SmallUpdateInstance update_small_instance(const UpdateArgs& a) {
@@ -72,18 +73,6 @@ void launch_update_small(const UpdateArgs& a_, hipStream_t s) {
     } else if (in.jr == 8) M3_LAUNCH_SMALL(9, false, 8, 256);
     else M3_LAUNCH_SMALL(9, false, 16, 256);
 #undef M3_LAUNCH_SMALL
-}
-bool update_small_applies(const UpdateArgs& a) {
-#ifdef M3_EXP_SPLIT_UPDATE   // (experiment build: the multi-launch path at every size)
-    return false;
-#endif
-    // unsharded (finalize fused in), or a shard_mix rank's local softmin (its costs ARE a.Jall)
-    if (!(a.fuse_finalize || a.record) || (a.record && (a.multi_modal || a.fuse_finalize))) return false;
-    // (with two controls: up to 64 register rows in single mode, K <= 16384, the north-star size; 32 in
-    // multi-modal mode, K <= 8192, a C5 shard's size)
-    const int kmax = (a.nu != 2) ? 4096 : a.multi_modal ? 8192 : 16384;
-    // (mppi_mode 'simple' takes the single-mode path with beta = lambda_: mppi.py:226, skill_utils.py:3)
-    return a.Kl == a.Kg && a.Kg <= kmax && a.n_cand == topk_workgroups(a.Kg) && (a.nu == 2 || a.nu == 9);
 }
 
 // ---- batched command (m3_batch_command) ---------------------------------------------------------------------------

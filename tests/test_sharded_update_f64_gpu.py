@@ -6,16 +6,16 @@ driver runs on the float32 NumPy emulation without a GPU (tests/test_sharded_upd
   kernel / host branch                                          reached by (case ids)
   k_weights / k_wsum with k_offset != 0, owner-only rows,       gr_* (unequal shards 300 / 251 / 450: offsets 300 and 551)
     the packed M3_BUF_REDUCE (shard_mix = 0)
-  update_impl mix_mode: k_update_small on the local shard       mix_* with K_local <= 16384 (Panda: <= 4096)
-  update_impl mix_mode: k_weights + k_wsum on the local shard   mix_single_N2_Kl16386_*, mix_panda_N2_Kl4098_*
+  the UPDATE_MIX plan: k_update_small on the local shard        mix_* with K_local <= 16384 (Panda: <= 4096)
+  the UPDATE_MIX plan: k_weights + k_wsum on the local shard    mix_single_N2_Kl16386_*, mix_panda_N2_Kl4098_*
   k_mix (single, simple, Panda's persisted beta)                mix_single_*, mix_simple_*, mix_panda_*
   k_local_topk<16> / <32>, one workgroup                        regen*/p3* with K_local <= 4096 / 4098..8192
   k_local_topk<16>, several workgroups + stage B                regen1_multi_N2_Kl8194_*, regen1_multi_N2_Kl65538_T9 (no ladder
                                                                   workgroups); regen2_* / p3_* with Kl8194 / Kl65536 / Kl65538
   k_local_topk's ladder-table workgroups (registers / memory)   regen2_* / p3_* (K_local <= 8192 / above)
-  regen_finalize, shard_mix = 1: k_mins / k_ladder / k_weights  regen1_*
+  the finalize plan, shard_mix = 1: k_mins / k_ladder / k_weights  regen1_*
     / k_wsum<REGEN> (+ k_finalize: T * nu > 2048)               regen1_multi_N2_Kl40_T1030
-  regen_finalize, shard_mix = 2: k_regen_part / k_regen_done    regen2_* (<2>), regen2_panda_* (<9>); chunk length above
+  the finalize plan, shard_mix = 2: k_regen_part / k_regen_done    regen2_* (<2>), regen2_panda_* (<9>); chunk length above
     (search_body on the mixed tables, topk_merge_records)         K_global = 131072: regen2_multi_N2_Kl65538, regen2_multi_N4_Kl65536
   search_body's fallback passes over the gathered costs         *_fallback (info.iters beyond the ladder asserted)
   m3_update_b: k_search's second workgroup, local weights,      p3_*
@@ -37,7 +37,7 @@ and then evaluate every weight with the global m, beta, eta as the unsharded ker
  Sum, rounded up: extra = (3 (ln 2^24 + 1) + 32 + 16) u = 6.1e-6 relative, added to 2e-5 + 4u|x| on the weights, to 2e-5
  on the etas and the half sums, and (times the actions' scale) to 1e-5 on the means and the plan -- for k_mix (shard_mix = 1,
  single and simple mode) and for shard_mix = 2 / 3 (of which only the eta part applies: still an upper bound).  Gather +
- reduce and shard_mix = 1 multi-modal (regen_finalize: k_mins / k_ladder / k_weights / k_wsum on the gathered costs) form
+ reduce and shard_mix = 1 multi-modal (the finalize plan: k_mins / k_ladder / k_weights / k_wsum on the gathered costs) form
  every weight with the unsharded kernels on all K costs: no extra term, the unsharded bounds as they are.
 Every protocol meets every edge of tests/test_sharded_update_f64_cpu.EDGES once (that module's matrix, run here on the
 kernels), except: shift1e8 under a multi-modal search (whole halves tie at their minimum in float32: the search has no
