@@ -961,6 +961,32 @@ int m3_sim_check_and_apply_suction(m3_handle* h, const float* action_dev, float 
  * for almost every command, panda_env, or no rollout yet.  Synchronises the handle's stream.  For tests and tools. */
 int m3_wave_order(m3_handle* h, const int** order_dev, int* n);
 
+/* ---- sample groups (extension): one control sequence in M models, the costs aggregated ----
+ * group_of [n], n == K_local: group_of[k] in 0 .. K-1 names the group of sample k (the ids are labels), -1 leaves it on its own.
+ * A group has 2 .. 16 members.  After every m3_rollout (so inside m3_command, ahead of the update) each group's member costs in
+ * M3_BUF_TRAJ_COST are replaced, in every member, by the mean of the group's j = max(1, ceil(worst_frac * M_g)) LARGEST member
+ * costs: worst_frac = 1 the mean, <= 1/16 the maximum, in between a CVaR-style tail mean; a NaN member makes the aggregate NaN.
+ * The arithmetic is a spec (csrc/sample_groups.hpp): descending sort, the fixed SUM16 tree, one binary32 division.  The update
+ * then runs unchanged on K costs, so a group counts M_g times in the softmin and a sample on its own once.  That the members of
+ * a group carry the same controls (the same noise rows) is the caller's arrangement.  NULL clears the groups: the handle runs
+ * exactly the kernels of a handle that never had any.  Everything is validated before any state changes, all memory comes from
+ * this call (none from a command), the groups survive m3_reset.
+ * M3_ERR_BAD_ARG: n != K_local, an id outside -1 .. K-1, a group of 1 or of more than 16 members, sample K-1 (zero-noise /
+ * null-action) or, multi-modal, samples 0 and K/2 (best trajectories) inside a group, a multi-modal group with members on both
+ * sides of K/2, worst_frac outside (0, 1].  M3_ERR_UNSUPPORTED: a sharded or sim_only handle, mode_simple / sampling_random
+ * (the noise is a function of the sample index), a handle with prior samples or a prior controller -- and the prior setters,
+ * m3_batch_command and both lockstep episode sets refuse a handle that has groups. */
+int m3_set_sample_groups(m3_handle* h, const int* group_of, int n, float worst_frac);
+int m3_sample_groups_set(m3_handle* h);   /* the number of groups, 0: none */
+/* sample k's group id as given (-1: on its own), the group's size (1) and its j (1); any pointer may be NULL */
+int m3_get_sample_group(const m3_handle* h, int k, int* group, int* size, int* worst_j);
+/* device, f32 [K_local], owned by the handle: the per-model costs of the last rollout, as they were before the aggregation
+ * (samples on their own included).  M3_ERR_STATE before the first m3_set_sample_groups. */
+int m3_sample_group_raw_costs(m3_handle* h, const float** dev);
+/* the aggregation alone, on whatever M3_BUF_TRAJ_COST holds (for callers who write the costs themselves, and for tests);
+ * M3_ERR_STATE without groups */
+int m3_aggregate_sample_groups(m3_handle* h);
+
 
 #ifdef __cplusplus
 }

@@ -331,6 +331,11 @@ SYMBOLS = [
     ("m3_sim_suction_forces", C.c_int, [_H, C.c_float, _FP]),
     ("m3_sim_check_and_apply_suction", C.c_int, [_H, _FP, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     ("m3_wave_order", C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
+    ("m3_set_sample_groups", C.c_int, [_H, C.POINTER(C.c_int), C.c_int, C.c_float]),
+    ("m3_sample_groups_set", C.c_int, [_H]),
+    ("m3_get_sample_group", C.c_int, [_H, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("m3_sample_group_raw_costs", C.c_int, [_H, C.POINTER(C.c_void_p)]),
+    ("m3_aggregate_sample_groups", C.c_int, [_H]),
 ]
 
 # every symbol include/m3p2i_hip_ext.h declares -- additive forms of calls above, in a table of their own: SYMBOLS stays the list

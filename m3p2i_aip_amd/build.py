@@ -22,7 +22,7 @@ SOURCES = ["rollout_point.hip", "rollout_point_task0.hip", "rollout_point_task1.
            "rollout_point_rollout_scenes.hip", "rollout_point_priors.hip", "rollout_point_priors_batch.hip", "prior_controllers.hip",
            "rollout_panda.hip", "rollout_panda_scene.hip", "rollout_panda_weights.hip", "rollout_panda_rows.hip",
            "rollout_panda_priors.hip", "rollout_panda_batch_rt.hip", "rollout_panda_episodes_rt.hip",
-           "update.hip", "update_small.hip", "update_sharded.hip", "sampler.hip", "p2p.hip", "m3_api.hip"]
+           "update.hip", "update_small.hip", "update_sharded.hip", "sampler.hip", "p2p.hip", "sample_groups.hip", "m3_api.hip"]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall",
           "-Wno-unused-function"]
 # per-source flags, measured on the bench configs (tools/time_variants_cfg.sh; later flags win; none of them changes

@@ -143,6 +143,12 @@ class ExampleConfig:
                                                                # each in an arena of their own around point_scene (the samples
                                                                # 0, K / 2 and K - 1 stay nominal); rollout_point_scenes builds
                                                                # the rows the planner's K-env simulator carries
+    rollout_arena_groups: Optional[Dict[str, object]] = None   # EXTENSION, point_env: `rollout_arena_groups={models: 4, spread: 0.3,
+                                                               # seed: 1, fields: [...], worst: 1.0}` -- every control sequence
+                                                               # of the planner rolled out in the same M arenas around
+                                                               # point_scene, the M costs aggregated (mean of the worst share)
+                                                               # ahead of the update: groups.grouped_layout, MPPI.set_sample_groups;
+                                                               # exclusive with rollout_arena_spread
     prior_samples: Optional[Dict[str, object]] = None   # EXTENSION, point_env: `prior_samples={controller: go_to, n: 4}` -- n of the
                                                         # K rollouts take the proposals of a host-side ancillary controller
                                                         # (priors.go_to / priors.push_behind), set before every command
@@ -205,6 +211,9 @@ def make_config(config_name="config_point", overrides=()):
     if cfg.rollout_arena_spread:
         cfg.rollout_arena_spread = dict(cfg.rollout_arena_spread)
         _check_rollout_arena_spread(cfg)
+    if cfg.rollout_arena_groups:
+        cfg.rollout_arena_groups = dict(cfg.rollout_arena_groups)
+        check_rollout_arena_groups(cfg)
     if cfg.prior_samples:
         cfg.prior_samples = dict(cfg.prior_samples)
         check_prior_samples(cfg)
@@ -340,11 +349,63 @@ def _check_rollout_arena_spread(cfg):
     return spread, int(given.get("seed", 0) or 0), fields
 
 
+ROLLOUT_ARENA_GROUPS_KEYS = ("models", "spread", "seed", "fields", "worst")
+
+
+def check_rollout_arena_groups(cfg):
+    """the parsed `rollout_arena_groups` key as (models, spread, seed, fields, worst); ValueError for what it cannot mean"""
+    from . import groups
+    given = dict(cfg.rollout_arena_groups)
+    if cfg.env_type != "point_env":
+        raise ValueError("rollout_arena_groups: point_env only")
+    if getattr(cfg, "rollout_arena_spread", None):
+        raise ValueError("rollout_arena_groups: exclusive with rollout_arena_spread (an arena per sample, or the same M arenas "
+                         "for every control sequence)")
+    if getattr(cfg, "prior_samples", None):
+        raise ValueError("rollout_arena_groups: exclusive with prior_samples (m3_set_sample_groups refuses a handle with priors)")
+    unknown = sorted(set(given) - set(ROLLOUT_ARENA_GROUPS_KEYS))
+    if unknown or "models" not in given or "spread" not in given:
+        raise ValueError(f"rollout_arena_groups: {{models: M, spread: S, seed: n, fields: [...], worst: f}} (unknown key(s) {unknown})")
+    models = given["models"]
+    if isinstance(models, bool) or not isinstance(models, int) or not 2 <= models <= groups.MAX_MEMBERS:
+        raise ValueError(f"rollout_arena_groups: models {models!r} is not an integer in 2 .. {groups.MAX_MEMBERS}")
+    spread = float(given["spread"])
+    if not 0.0 <= spread < 1.0:
+        raise ValueError(f"rollout_arena_groups: spread {spread!r} is not a share in [0, 1)")
+    worst = float(given.get("worst", 1.0))
+    if not 0.0 < worst <= 1.0:
+        raise ValueError(f"rollout_arena_groups: worst {worst!r} is not in (0, 1]")
+    if cfg.mppi.mppi_mode == "simple" or cfg.mppi.sampling_method == "random":
+        raise ValueError("rollout_arena_groups: needs a noise table (mppi_mode halton-spline, sampling_method halton)")
+    fields = tuple(given.get("fields") or ("box_m", "box_mu_g", "mu_rb"))
+    groups.grouped_layout(int(cfg.mppi.num_samples), models, bool(cfg.multi_modal))    # (no room for a group: its ValueError)
+    return models, spread, int(given.get("seed", 0) or 0), fields, worst
+
+
+def rollout_arena_group_layout(cfg):
+    """(group_of, model_of, arenas) of the `rollout_arena_groups` key: groups.grouped_layout for the planner's K samples and
+    the M arenas scenes.spread_point_scenes(M, spread, seed, base=point_scene, fields) -- sample k plans in arenas[model_of[k]],
+    a sample with model -1 in point_scene itself"""
+    from . import groups, scenes
+    models, spread, seed, fields, _ = check_rollout_arena_groups(cfg)
+    group_of, model_of = groups.grouped_layout(int(cfg.mppi.num_samples), models, bool(cfg.multi_modal))
+    arenas = scenes.spread_point_scenes(models, spread, seed, base=getattr(cfg, "point_scene", None), fields=fields)
+    return group_of, model_of, arenas
+
+
 def rollout_point_scenes(cfg, k_offset=0, n=None):
     """The arenas of the planner's samples under the `rollout_arena_spread` key, or None without it: the rows
     [k_offset, k_offset + n) (all K by default) of scenes.spread_point_scenes(K, spread, seed, base=point_scene, fields,
     nominal_rows=(0, K // 2, K - 1)).  The planner's K-env simulator is built with them (IsaacGymWrapper(point_scenes=...));
-    the planner attached to it takes them over, so its fused path stays the step path on that simulator."""
+    the planner attached to it takes them over, so its fused path stays the step path on that simulator.
+    Under the `rollout_arena_groups` key: sample k's row is the arena of its model (rollout_arena_group_layout), the nominal
+    arena for the samples on their own."""
+    if getattr(cfg, "rollout_arena_groups", None):
+        _, model_of, arenas = rollout_arena_group_layout(cfg)
+        base = dict(getattr(cfg, "point_scene", None) or {})
+        rows = [dict(arenas[m]) if m >= 0 else dict(base) for m in model_of.tolist()]
+        n = len(rows) - int(k_offset) if n is None else int(n)
+        return rows[int(k_offset):int(k_offset) + n]
     if not getattr(cfg, "rollout_arena_spread", None):
         return None
     from . import scenes

@@ -18,6 +18,7 @@
 #include "panda_episode_tables.hpp"
 #include "point_scene_rows.hpp"
 #include "panda_scene_rows.hpp"
+#include "sample_groups.hpp"
 
 using namespace m3;
 
@@ -1138,6 +1139,7 @@ static int set_prior_samples(m3_handle* h, const PriorKind& kind, const float* s
         ps.ctl.kind = 0;
         return M3_OK;
     }
+    if (h->groups.n > 0) return fail(h, M3_ERR_UNSUPPORTED, (who + SAMPLE_GROUPS_REFUSE_PRIORS).c_str());
     if ((rc = prior_index_check(h, who, sample_idx, n)) != M3_OK) return rc;
     const int T = c.T, nu = c.nu;
     if (!device)
@@ -1219,6 +1221,7 @@ extern "C" int m3_set_prior_controller(m3_handle* h, const m3_prior_controller* 
         ps.ctl.kind = 0;
         return M3_OK;
     }
+    if (h->groups.n > 0) return fail(h, M3_ERR_UNSUPPORTED, (who + SAMPLE_GROUPS_REFUSE_PRIORS).c_str());
     if (pc->kind != M3_PRIOR_CONTROLLER_GO_TO && pc->kind != M3_PRIOR_CONTROLLER_PUSH_BEHIND)
         return fail(h, M3_ERR_BAD_ARG, (who + ": unknown kind " + std::to_string(pc->kind) + " (M3_PRIOR_CONTROLLER_GO_TO = 1, _PUSH_BEHIND = 2)").c_str());
     if (pc->n < 1 || pc->n > M3_MAX_PRIOR_CONTROLLER_SEQS)
@@ -1257,6 +1260,100 @@ extern "C" int m3_prior_table(const m3_handle* h, const float** tab_dev, int* n)
 // the handle has a controller that the next rollout runs
 static bool prior_controller_on(const m3_handle* h) { return h->priors.n > 0 && h->priors.ctl.kind != 0; }
 static PriorControllerArgs prior_controller_args(const m3_handle* h) { return {h->priors.ctl, h->cfg.dt, h->priors.tab_dev}; }
+
+// ---- sample groups (m3_set_sample_groups): sample_groups.hpp validates, builds the table and owns the
+// refusals; here: the reading of the handle, the blocks, the upload and the launch ----
+static SampleGroupsInput sample_groups_input(const m3_handle* h) {
+    const m3_config& c = h->cfg;
+    return {c.K_local, c.K_global, c.multi_modal != 0, c.mode_simple != 0, c.sampling_random != 0, c.sim_only != 0,
+            h->priors.n > 0 || h->panda_priors.n > 0};
+}
+extern "C" int m3_set_sample_groups(m3_handle* h, const int* group_of, int n, float worst_frac) {
+    if (!h) return M3_ERR_BAD_ARG;
+    SampleGroupState& sg = h->groups;
+    if (!group_of) {   // exactly the kernels of a handle that never had groups (the blocks are kept for a later call)
+        sg.n = 0;
+        sg.n_ungrouped = 0;
+        return M3_OK;
+    }
+    // ---- every check, and the table, before any state changes ----
+    const SampleGroupsInput in = sample_groups_input(h);
+    SampleGroupTable t;
+    try {
+        const SampleGroupFault f = sample_groups_build(in, group_of, n, worst_frac, t);
+        if (f.r != SAMPLE_GROUPS_OK)
+            return fail(h, sample_groups_refusal_is_unsupported(f.r) ? M3_ERR_UNSUPPORTED : M3_ERR_BAD_ARG, sample_groups_refusal_text(f, in).c_str());
+    } catch (const std::bad_alloc&) {
+        return fail(h, M3_ERR_HIP, "m3_set_sample_groups: out of host memory");
+    }
+    const int K = in.K_local, cap = K / 2;
+    const size_t tab_ints = sample_group_table_ints(K);
+    if (!sg.tab_dev) {
+        BlockGroup g(h->mem);   // all or none
+        hipError_t e = own_device(h->mem, sg.tab_dev, tab_ints * sizeof(int));
+        if (e == hipSuccess) e = own_device(h->mem, sg.raw_dev, (size_t)K * sizeof(float));
+        if (e == hipSuccess) e = own_pinned(h->mem, sg.pinned, (tab_ints + 2 * (size_t)K) * sizeof(int), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMemsetAsync(sg.raw_dev, 0, (size_t)K * sizeof(float), h->stream);
+        if (e != hipSuccess) return fail(h, M3_ERR_HIP, (std::string("m3_set_sample_groups: ") + hipGetErrorString(e)).c_str());
+        g.keep = true;
+    }
+    // (the pinned mirror is free to be rewritten: every call that uploads from it ends with a synchronisation)
+    int* p = sg.pinned;
+    for (size_t i = 0; i < tab_ints; ++i) p[i] = -1;
+    std::memcpy(p, t.member.data(), t.member.size() * sizeof(int));
+    std::memcpy(p + (size_t)cap * SAMPLE_GROUP_LANES, t.worst_j.data(), t.worst_j.size() * sizeof(int));
+    if (t.n_ungrouped) std::memcpy(p + (size_t)cap * (SAMPLE_GROUP_LANES + 1), t.ungrouped.data(), t.ungrouped.size() * sizeof(int));
+    std::memcpy(p + tab_ints, group_of, (size_t)K * sizeof(int));
+    std::memcpy(p + tab_ints + K, t.dense.data(), (size_t)K * sizeof(int));
+    sg.n = 0;   // (a failed upload leaves the handle without groups, not with half a table)
+    HIPCHK(h, hipMemcpyAsync(sg.tab_dev, p, tab_ints * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    sg.n = t.n_groups;
+    sg.n_ungrouped = t.n_ungrouped;
+    sg.worst_frac = worst_frac;
+    return M3_OK;
+}
+extern "C" int m3_sample_groups_set(m3_handle* h) { return h ? h->groups.n : M3_ERR_BAD_ARG; }
+extern "C" int m3_get_sample_group(const m3_handle* h, int k, int* group, int* size, int* worst_j) {
+    if (!h) return M3_ERR_BAD_ARG;
+    const int K = h->cfg.K_local;
+    if (k < 0 || k >= K) return M3_ERR_BAD_ARG;
+    const SampleGroupState& sg = h->groups;
+    int id = -1, m = 1, j = 1;
+    if (sg.n > 0) {
+        const size_t tab_ints = sample_group_table_ints(K);
+        const int row = sg.pinned[tab_ints + K + k];
+        if (row >= 0) {
+            id = sg.pinned[tab_ints + k];
+            m = 0;
+            for (int l = 0; l < SAMPLE_GROUP_LANES; ++l) m += sg.pinned[(size_t)row * SAMPLE_GROUP_LANES + l] >= 0;
+            j = sg.pinned[(size_t)(K / 2) * SAMPLE_GROUP_LANES + row];
+        }
+    }
+    if (group) *group = id;
+    if (size) *size = m;
+    if (worst_j) *worst_j = j;
+    return M3_OK;
+}
+extern "C" int m3_sample_group_raw_costs(m3_handle* h, const float** dev) {
+    if (!h || !dev) return M3_ERR_BAD_ARG;
+    if (!h->groups.raw_dev) return fail(h, M3_ERR_STATE, "m3_sample_group_raw_costs: the handle never had sample groups (m3_set_sample_groups)");
+    *dev = h->groups.raw_dev;
+    return M3_OK;
+}
+// the launch at the tail of a rollout (and m3_aggregate_sample_groups'): behind the last writer of M3_BUF_TRAJ_COST on the stream
+static void aggregate_sample_groups(m3_handle* h) {
+    const SampleGroupState& sg = h->groups;
+    launch_sample_groups({sg.tab_dev, sg.n, sg.n_ungrouped, h->cfg.K_local / 2, h->cfg.K_local, (float*)h->buf[M3_BUF_TRAJ_COST], sg.raw_dev},
+                         h->stream);
+}
+extern "C" int m3_aggregate_sample_groups(m3_handle* h) {
+    if (!h) return M3_ERR_BAD_ARG;
+    if (h->groups.n <= 0) return fail(h, M3_ERR_STATE, "m3_aggregate_sample_groups: the handle has no sample groups (m3_set_sample_groups)");
+    aggregate_sample_groups(h);
+    HIPCHK(h, hipGetLastError());
+    return M3_OK;
+}
 
 // the handle's arena is the default bit for bit (-0.0f is not 0.0f here)
 static bool default_point_scene(const m3_handle* h) {
@@ -1661,6 +1758,8 @@ extern "C" int m3_rollout(m3_handle* h) {
         panda_record_used(h, d);
         h->panda_priors.used = d.variant == PANDA_PRIORS ? 1 : 0;
     }
+    // the handle's sample groups: each group's costs become one aggregate, behind the last writer of M3_BUF_TRAJ_COST
+    if (h->groups.n > 0) aggregate_sample_groups(h);
     HIPCHK(h, hipGetLastError());
     if (h->timing) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     return M3_OK;
@@ -2134,7 +2233,8 @@ extern "C" int m3_command(m3_handle* h, float* action_host) {
     int rc = m3_rollout(h);
     if (rc != M3_OK) return rc;
     // weights -> sums + (last workgroup) mean update / filter; the costs the update reads are this rollout's
-    rc = run_update_entry(h, UPDATE_ENTRY_UPDATE_FINALIZE, h->wave_min != nullptr && h->wave_min_rows > 0);
+    // (with sample groups the rollout's rows of wave minima are minima of costs that no longer exist: the update forms its own)
+    rc = run_update_entry(h, UPDATE_ENTRY_UPDATE_FINALIZE, h->groups.n == 0 && h->wave_min != nullptr && h->wave_min_rows > 0);
     if (rc != M3_OK) return rc;
     if (action_host) {
         HIPCHK(h, hipMemcpyAsync(action_host, plan_dst(h), plan_floats(h->cfg) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -2377,6 +2477,10 @@ static const char* batch_refusal(m3_handle* h, UpdateArgs& u, int& code, int sec
     code = M3_ERR_STATE;
     if (c.K_local != c.K_global) return "sharded handle (K_local != K_global)";
     if (c.sim_only) return "handle was created sim_only";
+    if (h->groups.n > 0) {   // (no batched launch aggregates: the update of a batch follows its rollout directly)
+        code = M3_ERR_UNSUPPORTED;
+        return SAMPLE_GROUPS_UNBATCHED;
+    }
     if (h->point_rows.sample_on && !(sections & M3_BATCH_SECTION_POINT_ROLLOUT_SCENES) && !in_priors_section) {   // (the table's slots have no fourth section)
         code = M3_ERR_UNSUPPORTED;
         return POINT_ROWS_UNBATCHED;
@@ -2967,6 +3071,11 @@ static int eps_status_sync(m3_episodes* eps) {
 // a planner that got prior samples after m3_episodes_create (which refuses it): nothing of the tick is launched.  A set created
 // with M3_EPISODES_PRIORS takes such planners
 static int eps_priors_refusal(m3_episodes* eps, const char* who) {
+    for (int i = 0; i < eps->n; ++i)   // (likewise sample groups, which no set takes)
+        if (eps->planners[i]->groups.n > 0) {
+            eps->err = std::string(who) + ": planner " + std::to_string(i) + ": " + SAMPLE_GROUPS_UNBATCHED;
+            return M3_ERR_UNSUPPORTED;
+        }
     if (eps->flags & M3_EPISODES_PRIORS) return M3_OK;
     for (int i = 0; i < eps->n; ++i)
         if (eps->planners[i]->priors.n > 0) {
@@ -3330,11 +3439,16 @@ static int peps_ready(m3_panda_episodes* eps, const char* who) {
             return code;
         }
     }
-    for (int i = 0; i < eps->n; ++i)
+    for (int i = 0; i < eps->n; ++i) {
+        if (eps->planners[i]->groups.n > 0) {   // (sample groups set after create, which refuses them)
+            eps->err = std::string(who) + ": planner " + std::to_string(i) + ": " + SAMPLE_GROUPS_UNBATCHED;
+            return M3_ERR_UNSUPPORTED;
+        }
         if (eps->planners[i]->action_out != eps->plan[i]) {
             eps->err = std::string(who) + ": planner " + std::to_string(i) + "'s action-out destination changed since create";
             return M3_ERR_STATE;
         }
+    }
     return M3_OK;
 }
 

@@ -553,6 +553,25 @@ struct PriorSampleState {
     m3_prior_controller ctl = {}; // m3_set_prior_controller (kind 0: none -- the table is the caller's): the rows 0 .. n - 1 of
                                   // tab_dev are written by k_prior_controllers ahead of every rollout
 };
+
+// The sample groups of a planner handle (m3_set_sample_groups, sample_groups.hpp): the pointers are non-owning views of ledger
+// blocks, allocated as one group by the first setter call on the handle and sized for any partition of its K samples.
+struct SampleGroupState {
+    int n = 0;                    // groups set (0: none -- the handle launches what it launched before the call existed)
+    int n_ungrouped = 0;
+    float worst_frac = 1.0f;
+    int* tab_dev = nullptr;       // device: member[K/2][16] | worst_j[K/2] | ungrouped[K] (sample_group_table_ints)
+    float* raw_dev = nullptr;     // device [K]: the per-model costs of the last rollout (m3_sample_group_raw_costs)
+    int* pinned = nullptr;        // pinned host: the table as uploaded, behind it label[K] (the caller's ids) and dense[K] (rows)
+};
+// what k_sample_groups receives (sample_groups.hip): cap_groups = K/2 rows of the table, n_groups of them in use
+struct SampleGroupArgs {
+    const int* tab;
+    int n_groups, n_ungrouped, cap_groups, K;
+    float* J;      // M3_BUF_TRAJ_COST
+    float* raw;
+};
+void launch_sample_groups(const SampleGroupArgs& a, hipStream_t s);
 }  // namespace m3
 
 // the ledger's release function bound to HIP (m3_api.hip): the one place that frees
@@ -607,6 +626,7 @@ struct m3_handle {
     m3::SceneRows<m3_panda_scene> panda_rows;   // table [PANDA_SCENE_ROW_WORDS][Kl] (panda_scene_rows.hpp)
     m3::PriorSampleState priors;                // m3_set_prior_samples; survives m3_reset
     m3::PriorSampleState panda_priors;          // m3_set_panda_prior_samples (nu = 9; no controller); survives m3_reset
+    m3::SampleGroupState groups;                // m3_set_sample_groups; survives m3_reset
     // world
     float world0[18];
     const float* world0_bound = nullptr;  // device, 18 floats (filled by world_from_sim)

@@ -482,6 +482,39 @@ class HipEngine(_CObject):
         self._ck_code(self.lib.m3_prior_table(self._h, C.byref(p), C.byref(n)), "m3_prior_table")
         return torch.as_tensor(_DevArray(p.value, (max(n.value, 1), self.cfg.T, self.cfg.nu), "<f4", self), device=self.device)[:n.value]
 
+    def set_sample_groups(self, group_of=None, worst=1.0):
+        """Extension, unsharded planner engines: SAMPLE GROUPS -- group_of[k] names the group of local sample k (-1: on its own;
+        2 .. 16 members per group); after every rollout each group's costs become, in every member, the mean of the group's
+        max(1, ceil(worst * size)) largest member costs (worst = 1: the mean; <= 1/16: the maximum), and the update runs on
+        those.  That the members of a group carry the same noise rows is the caller's arrangement (groups.tile_noise;
+        MPPI.set_sample_groups does it).  group_of=None clears.  See include/m3p2i_hip.h: m3_set_sample_groups."""
+        if group_of is None:
+            self._ck(self.lib.m3_set_sample_groups(self._h, None, 0, 1.0))
+            return
+        g = [int(i) for i in (group_of.tolist() if hasattr(group_of, "tolist") else group_of)]
+        self._ck(self.lib.m3_set_sample_groups(self._h, (C.c_int * max(len(g), 1))(*g), len(g), float(worst)))
+
+    def sample_groups_set(self):
+        """the number of sample groups set (0: none)"""
+        return int(self.lib.m3_sample_groups_set(self._h))
+
+    def sample_group(self, k):
+        """(group id as given or -1, size, worst_j) of local sample k"""
+        g, m, j = C.c_int(), C.c_int(), C.c_int()
+        self._ck_code(self.lib.m3_get_sample_group(self._h, int(k), C.byref(g), C.byref(m), C.byref(j)), "m3_get_sample_group")
+        return int(g.value), int(m.value), int(j.value)
+
+    def raw_costs(self) -> torch.Tensor:
+        """zero-copy view [K_local] of the per-model costs of the last rollout, as they were before the groups' aggregation
+        (read-only by convention; ordered on the engine's stream)"""
+        p = C.c_void_p()
+        self._ck(self.lib.m3_sample_group_raw_costs(self._h, C.byref(p)))
+        return torch.as_tensor(_DevArray(p.value, (self.cfg.K_local,), "<f4", self), device=self.device)
+
+    def aggregate_sample_groups(self):
+        """launches the aggregation alone, on whatever BUF_TRAJ_COST holds"""
+        self._ck(self.lib.m3_aggregate_sample_groups(self._h))
+
     def _ck_code(self, rc, who):
         # (the getters leave no message behind)
         if rc != 0:

@@ -237,7 +237,11 @@ class PointEpisodeSet:
 
 def _check_episode_priors(cfg, idx, point_priors):
     """the `prior_samples` key of an episode of a lockstep set: only a controller on the device can serve it (the episodes'
-    worlds live on the device and a tick is one library call for all of them), and only in a set built for priors"""
+    worlds live on the device and a tick is one library call for all of them), and only in a set built for priors.  The
+    `rollout_arena_groups` key no set serves: the batched command has no aggregation between its rollout and its update."""
+    if getattr(cfg, "rollout_arena_groups", None):
+        raise ValueError(f"run_point_episodes: episode {idx} asks for sample groups (rollout_arena_groups), which the batched "
+                         "command does not run (m3_set_sample_groups: m3_command only); use closed_loop.run")
     if not getattr(cfg, "prior_samples", None):
         return
     if not compat.prior_samples_on_device(cfg):

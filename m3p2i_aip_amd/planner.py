@@ -33,7 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from . import sampling, scenes
+from . import groups, sampling, scenes
 from .engine import HipBatch, HipEngine, make_config
 
 # The engine class the planner instantiates.  The product always uses HipEngine (HIP kernels,
@@ -245,6 +245,13 @@ class MPPI():
         self._discover_plugin()
         self.gripper_command = None
         self.collective = None  # set by m3p2i_aip_amd.distributed for world_size > 1
+        self._sample_groups = None
+        ag = _get(cfg, "rollout_arena_groups", None)
+        if ag:
+            # (extension, off by default: the `rollout_arena_groups` config key -- the arenas themselves are the rows of the
+            # K-env simulator this planner attaches to, compat.rollout_point_scenes)
+            group_of, _ = groups.grouped_layout(self.K, int(dict(ag)["models"]), self.multi_modal)
+            self.set_sample_groups(group_of, float(dict(ag).get("worst", 1.0)))
 
     # ------------------------------------------------------------------ plugin discovery
     def _discover_plugin(self):
@@ -357,6 +364,45 @@ class MPPI():
         if self.relabel_samples:
             e.relabel_samples()   # the sampler's row labels are arbitrary: wavefront-coherent ones
         self._have_noise = True
+        self._tile_group_noise()
+
+    def set_sample_groups(self, group_of, worst=1.0):
+        """Extension, unsharded halton-spline planners with a noise table: SAMPLE GROUPS (m3_set_sample_groups) -- group_of[k]
+        names the group of sample k (-1: on its own; 2 .. 16 members; K - 1 and, multi-modal, 0 and K / 2 stay on their own; a
+        multi-modal group keeps to one half).  The members of a group take the noise row of the group's first member
+        (groups.tile_noise, applied to the table that is there and to every later one), so they roll the same controls out --
+        in different models when the planner has a scene per sample (set_rollout_scenes / a wrapper with point_scenes;
+        groups.grouped_layout gives both lists).  After every rollout each group's costs become the mean of its
+        max(1, ceil(worst * size)) worst members; the update then weighs K costs as ever, so a group counts size times in the
+        softmin and a sample on its own once.  group_of=None clears (the noise rows stay tiled until the next table).  Applies
+        to the fused path and the step path alike; command_batch and the lockstep episodes refuse such a planner."""
+        if group_of is None:
+            self._engine.set_sample_groups(None)
+            self._sample_groups = None
+            return
+        if self.world_size != 1:
+            raise ValueError("set_sample_groups: unsharded planners only")
+        g = np.asarray(group_of, dtype=np.int64).reshape(-1)
+        self._engine.set_sample_groups(g, worst)       # (every refusal of the library before anything is kept here)
+        self._sample_groups = (g, float(worst))
+        if self._have_noise:
+            self._tile_group_noise()
+
+    @property
+    def has_sample_groups(self):
+        return getattr(self, "_sample_groups", None) is not None
+
+    @property
+    def raw_costs(self):
+        """[K] the per-model costs of the last rollout, before the groups' aggregation (cost_total holds the aggregates)"""
+        return self._engine.raw_costs()
+
+    def _tile_group_noise(self):
+        """the members of every group on their first member's noise row, through set_noise: the upload also ends a pending or
+        periodic relabelling of the rows, which would tear the members' rows apart again"""
+        if not self.has_sample_groups or self.delta is None:
+            return
+        self._engine.set_noise(groups.tile_noise(self.delta, self._sample_groups[0]))
 
     @property
     def delta(self):
@@ -748,6 +794,8 @@ class MPPI():
                 noise = noise.abs()                                              # :366-367
             J = Ssum + torch.sum(U.unsqueeze(0) * ((self.lambda_ * noise) @ self.noise_sigma_inv), dim=(1, 2))
         self._buf(L.BUF_TRAJ_COST).copy_(J)
+        if self.has_sample_groups:
+            e.aggregate_sample_groups()     # (what the fused rollout's tail does)
         out = self._next_action_slot()
         self._update_exchange_finalize()
         return out
@@ -803,6 +851,7 @@ class MPPI():
         sharded multi-modal planner with shard_mix (engine.needs_global_noise)."""
         self._engine.set_noise(torch.as_tensor(delta, dtype=torch.float32).to(self.device))
         self._have_noise = True
+        self._tile_group_noise()
 
     def _shift_action(self, action_seq):
         saved = action_seq[-1].clone()
@@ -843,6 +892,9 @@ def command_batch(planners, states, panda_runtime=False, point_runtime=False, po
             raise ValueError(f"command_batch: planner {i} runs in step mode (user dynamics / running_cost callables)")
         if p.world_size > 1 or p.collective is not None:
             raise ValueError(f"command_batch: planner {i} is sharded or has collectives installed")
+        if getattr(p, "has_sample_groups", False):
+            raise ValueError(f"command_batch: planner {i} has sample groups (set_sample_groups / `rollout_arena_groups`), which "
+                             "only its own command() runs (m3_set_sample_groups)")
         if getattr(p, "env_type", None) == "panda_env" and getattr(p, "has_prior_samples", False):
             raise ValueError(f"command_batch: planner {i} has prior samples (set_panda_prior_samples), which only its own "
                              "command() runs (m3_set_panda_prior_samples)")
